@@ -30,6 +30,9 @@ One JSON line on rank 0: value = E / step time (max over ranks, K steps between 
   kernels       the same figures for every kernel of the step;
   cpu_baseline  oracle/gat_oracle.c (CPU port of the same level) on this host's cores, N=1 only;
   epoch_ms      Cora / Pubmed / PPI-shaped epochs (train.py:151-179, train_ppi.py) replayed from one HIP graph, N=1 only.
+
+--dump-outputs DIR writes what the last timed step computed -- the level output and the gradients -- as DIR/<name>.npy (float32,
+at most 64 MB: a fixed, seeded sample of rows when larger); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -77,7 +80,12 @@ def parse():
                          "of the whole level after its forward (also copy-free), hidden behind the backward only")
     ap.add_argument("--as-rank-of", type=int, default=0,
                     help="single process: run the work of rank 0 of a world of this size (per-rank time model, no collectives)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (level output and gradients) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of rows when the full arrays are larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.cpu_steps < 1:
         ap.error("--cpu-steps must be >= 1")
     return args
@@ -251,6 +259,30 @@ def gatv2_level_record(pg, ops, graph, X, H, Fo, steps=10):
             "note": "v2_backward_row_col = column pass (gathers [Gp_i | m,1/Z,D | Whi_i], leaves de per transposed edge) + row pass "
                     "(gathers the Whj half of [Whi_j | Whj_j], de through perm) + their fix-ups, one C call; per-kernel times: "
                     "profiles/ rocprof summary of tools/v2_bench.py"}
+
+
+DUMP_BUDGET = 64 << 20      # --dump-outputs: bytes written in all
+
+
+def dump_outputs(path, whole, by_row, n, dev):
+    """--dump-outputs: whole = {name: tensor}, written as they are; by_row = {name: (width, rows -> [len(rows), width] tensor)}, the
+    [n, width] outputs: all n rows, or -- when that would pass DUMP_BUDGET -- the same fixed, seeded sample of rows for each (numpy
+    default_rng(0), sorted).  Every array as float32 <path>/<name>.npy; returns the record of what was written."""
+    os.makedirs(path, exist_ok=True)
+    header = 4096               # per file, more than an .npy header takes
+    left = DUMP_BUDGET - header * (len(whole) + len(by_row)) - sum(4 * t.numel() for t in whole.values())
+    k = min(n, left // (4 * sum(w for w, _ in by_row.values())))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(dev)
+    arrays = {name: t for name, t in whole.items()}
+    arrays.update({name: fn(idx) for name, (_, fn) in by_row.items()})
+    shapes = {}
+    for name, t in arrays.items():
+        a_ = t.detach().float().contiguous().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a_)
+        shapes[name] = list(a_.shape)
+    return {"dir": path, "arrays": shapes,
+            "rows": "all" if k == n else f"{k} of {n}, the same seeded sample (numpy default_rng(0), sorted) for {sorted(by_row)}"}
 
 
 def self_launch(args):
@@ -467,9 +499,13 @@ def main():
     barrier()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
         ev[k][0].record()
-        step()
+        if k == args.steps - 1:
+            last = step()
+        else:
+            step()
         ev[k][1].record()
     barrier()
     dt = time.perf_counter() - t0
@@ -480,6 +516,36 @@ def main():
     ms = dt / args.steps * 1e3
     step_ms = sorted(a_.elapsed_time(b_) for a_, b_ in ev)
     ms_median = step_ms[len(step_ms) // 2]
+
+    # ---- --dump-outputs: what the last timed step handed its caller, taken now (the legs below reuse the same tensors / static
+    # buffers).  out [N, H F'] at the caller's rows (N > 1: every rank's heads, out of the internal node order); the gradients of
+    # this rank's parameters (and dX with --dx).
+    dump_record = None
+    if args.dump_outputs and rank == 0:
+        if replicate:
+            grads = {"dW": W_all.grad, "da": a_all.grad}
+        elif use_pg or not args.hip_graph:
+            grads = {"dW": W_loc.grad, "da": a_loc.grad}
+            if args.dx:
+                grads["dX"] = Xb.grad
+        else:
+            dx_, dW_, da_ = lvl.grads[:3]
+            grads = {"dW": dW_, "da": da_}
+            if args.dx:
+                grads["dX"] = dx_
+        dX_ = grads.pop("dX", None)
+        if use_pg:          # column-blocked [world, N, w], rows in the internal order when to_int is set
+            def out_rows(idx):
+                src = idx if to_int is None else to_int.index_select(0, idx)
+                return last.index_select(1, src).permute(1, 0, 2).reshape(len(idx), -1)
+        else:
+            def out_rows(idx):
+                return last.index_select(0, idx)
+        by_row = {"out": (last.shape[0] * last.shape[2] if use_pg else last.shape[1], out_rows)}
+        if dX_ is not None:
+            by_row["dX"] = (Fin, lambda idx: dX_.index_select(0, idx))
+        dump_record = dump_outputs(args.dump_outputs, grads, by_row, N, dev)
+    del last
 
     # ---- the same K steps with the two streamed GEMMs on the fp32 MFMA pipe (the gemm_mode argument of the C ABI): reported beside
     # the headline so that the effect of the split-bf16 products is on record in every run.  Single GPU, stream launches.
@@ -685,6 +751,8 @@ def main():
             "alt": alt,
             "alt_node_order": alt_order,
         }
+        if dump_record is not None:
+            line["dump_outputs"] = dump_record
         if cpu_record is not None:
             line["cpu_baseline"] = cpu_record
         if world == 1 and model_world == 1 and not args.no_v2 and not args.dx:

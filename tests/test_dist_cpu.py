@@ -35,6 +35,18 @@ def _run_world(world, H2, H1):
         assert p.returncode == 0 and f"rank {r} ok" in out, out[-2000:]
 
 
+def _run_world_threads(world, H2, H1):
+    """The same ranks as threads of ONE worker process, a gloo group each (tests/dist_worker.py `threads`): a CPU backward
+    opens the GPU in every process that runs one, and a GPU host lets only a few processes hold it at once."""
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dist_worker.py")
+    env = dict(os.environ, OMP_NUM_THREADS="1", MKL_NUM_THREADS="1")
+    p = subprocess.run([sys.executable, worker, "threads", str(world), str(H2), str(H1)], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=240)
+    assert p.returncode == 0, p.stdout[-3000:]
+    for r in range(world):
+        assert f"rank {r} ok" in p.stdout, p.stdout[-2000:]
+
+
 @pytest.mark.parametrize("H2", [2, 1])        # H2 = 1: rank 1 owns no head of the last level
 def test_head_parallel_world2_gloo(H2):
     _run_world(2, H2, 3)
@@ -44,8 +56,8 @@ def test_head_parallel_world8_gloo():
     """The shape of the driver's 8-GPU run (bench.py --gpus 8: 8 heads, ONE per rank) plus an uneven last level (6 heads on
     8 ranks: two ranks own none and still take part in every collective): all-gather / reduce-scatter / all-reduce algebra
     and sync_head_parameters over 8 gloo ranks against the unsharded oracle (the N = 8 path had only ever
-    been rehearsed at 2 and 4 ranks)."""
-    _run_world(8, 6, 8)
+    been rehearsed at 2 and 4 ranks).  The 8 ranks are threads of one process (_run_world_threads)."""
+    _run_world_threads(8, 6, 8)
 
 
 def test_partition_heads():
