@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PYGAT_ABI_VERSION 14
+#define PYGAT_ABI_VERSION 15
 
 enum {
   PYGAT_OK = 0,
@@ -69,7 +69,8 @@ int pygat_device_count(void);
 int pygat_device_name(char* host_buf, int len);
 /* Registers per lane and scratch bytes per lane of a tuned kernel as the LOADED code object reports them (hipFuncGetAttributes):
  * "k2_headline" (fused forward, 8 heads x 16, training), "k4_headline_da" (column pass with the a-gradient sums), "tn_x3w"
- * (streamed-K weight gradient), "x3gw" (general split-bf16 GEMM).  The attention kernels were tuned at four waves per SIMD
+ * (streamed-K weight gradient), "x3gw" (general split-bf16 GEMM), "k1_x3_tail" (the headline projection with the
+ * self-loop-only tail's output folded in, ABI 15).  The attention kernels were tuned at four waves per SIMD
  * without scratch; `amdgpu_waves_per_eu` makes the compiler spill rather than fail, so tests/test_gpu_properties.py asks. */
 int pygat_kernel_footprint(const char* kernel, int* num_regs, int* scratch_bytes);
 
@@ -417,6 +418,15 @@ int pygat_gat_backward_tail(int row_first, int n_rows, int H, int Fo, int flags,
                             const int32_t* user_row, float* dWh, int64_t ld_dwh, int zero_cols, float* ds, float* dt, void* stream);
 /* (ld_dwh: row stride of dWh, 0 = H*Fp; zero_cols: columns behind the H*Fp gradient columns of a row to clear -- GATv2: dWW_i =
  *  [Gp_i | 0] with ld_dwh = 2 H Fp, zero_cols = H Fp; ds, dt may be NULL) */
+
+/* The tail's forward folded into the projection (ABI 15), for levels without a skip projection: pygat_project_blocked (Sk =
+ * NULL) for the rows before row_first; for the rows [row_first, n) it writes out[user_row ? user_row[i] : i] = ELU(Wh_i) (flags:
+ * PYGAT_F_ELU or 0) -- pygat_gat_forward_tail's output; m / Z / qneg are not touched -- and leaves Wh_i unspecified: on the
+ * split-bf16 projection with s from the accumulators (F' = Fp of 8 / 16) the epilogue stores the output instead of Wh; any
+ * other call projects every row and runs the tail stream after it.  Bitwise the same output either way. */
+int pygat_project_tail_blocked(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, const pygat_col_blocks* x_blk,
+                               const float* Wcat, int64_t ldw, const float* a_pad, float* Wh, float* s, int split_k, void* ws,
+                               int gemm_mode, int row_first, const int32_t* user_row, float* out, int flags, void* stream);
 
 /* ------------------------------------------------ GATv2 (next row of the scope table)
  * The reference's SpGraphAttentionLayerV2 (layers.py:258-313): per head

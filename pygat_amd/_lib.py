@@ -23,7 +23,7 @@ from .config import config as _config  # noqa: E402
 if _config.lib_path:
     LIB_PATH = os.path.abspath(_config.lib_path)
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 F_ELU = 1
 F_SKIP = 2
 F_MAIN_ONLY = 4
@@ -36,7 +36,7 @@ SYMBOLS = [
     "pygat_exclusive_scan_i32", "pygat_dense_fill_cols", "pygat_csr_symmetric_perm",
     "pygat_gemm_workspace_bytes", "pygat_gemm_f32", "pygat_gemm_f32_blocked", "pygat_project_blocked", "pygat_wgrad_blocked", "pygat_pack_params", "pygat_pack_params_heads", "pygat_stack_heads", "pygat_stack_heads_padded", "pygat_project", "pygat_attn_scores",
     "pygat_unpack_wgrad",
-    "pygat_edge_pairs", "pygat_slot_bounds", "pygat_slot_meta", "pygat_partials_bytes", "pygat_head_group", "pygat_gat_forward", "pygat_gat_forward_phases_ok", "pygat_gat_forward_tail", "pygat_gat_backward_col_tail", "pygat_gat_backward_tail", "pygat_head_mean",
+    "pygat_edge_pairs", "pygat_slot_bounds", "pygat_slot_meta", "pygat_partials_bytes", "pygat_head_group", "pygat_gat_forward", "pygat_gat_forward_phases_ok", "pygat_gat_forward_tail", "pygat_gat_backward_col_tail", "pygat_gat_backward_tail", "pygat_project_tail_blocked", "pygat_head_mean",
     "pygat_gat_backward_prepare", "pygat_gat_backward_row", "pygat_gat_backward_col", "pygat_gat_backward_rowsum",
     "pygat_gat_backward_col_da_bytes", "pygat_a_grad_fold",
     "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
@@ -120,6 +120,7 @@ def _load():
     lib.pygat_gat_forward_tail.argtypes = [i, i, i, i, i, p, i64, p, p, p, p, p, p, p]
     lib.pygat_gat_backward_col_tail.argtypes = [i, i, i, i, p, p, p, p]
     lib.pygat_gat_backward_tail.argtypes = [i, i, i, i, i, p, p, p, p, i64, i, p, p, p]
+    lib.pygat_project_tail_blocked.argtypes = [i, i, i, i, p, i64, CB, p, i64, p, p, p, i, p, i, i, p, p, i, p]
     lib.pygat_head_mean.argtypes = [i, i, i, p, p, p, p]
     lib.pygat_gat_backward_prepare.argtypes = [i, i, i, i, i, p, p, p, p, p, p, p, p, p, f, p, i, i, i, p, p]
     lib.pygat_gat_backward_row.argtypes = [C.POINTER(Graph), i, i, f, p, p, p, p, p, p, i, i, i, p]

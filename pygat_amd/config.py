@@ -46,6 +46,7 @@ class Config:
     pad_k: bool                           # PYGAT_PAD_K=0            odd input widths run as they are
     renumber: bool                        # PYGAT_RENUMBER=0         large first levels in the caller's node order (no internal degree order)
     tail: bool                            # PYGAT_TAIL=0             self-loop-only nodes through the fused kernels like every other row
+    tail_fused: bool                      # PYGAT_TAIL_FUSED=0       that tail through its own streams instead of the projection / dW GEMMs
 
     @staticmethod
     def from_env() -> "Config":
@@ -65,6 +66,7 @@ class Config:
             pad_k=_flag("PYGAT_PAD_K", True),
             renumber=_flag("PYGAT_RENUMBER", True),
             tail=_flag("PYGAT_TAIL", True),
+            tail_fused=_flag("PYGAT_TAIL_FUSED", True),
         )
 
     def describe(self) -> dict:

@@ -36,7 +36,8 @@ extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* sc
   if (!strcmp(kernel, "k4_headline_da")) return pygat::footprint_k4_headline_da(num_regs, scratch_bytes);
   if (!strcmp(kernel, "tn_x3w")) return pygat::footprint_gemm_x3(0, num_regs, scratch_bytes);
   if (!strcmp(kernel, "x3gw")) return pygat::footprint_gemm_x3(1, num_regs, scratch_bytes);
-  pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw)", kernel);
+  if (!strcmp(kernel, "k1_x3_tail")) return pygat::footprint_gemm_x3(2, num_regs, scratch_bytes);
+  pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw, k1_x3_tail)", kernel);
   return PYGAT_EINVAL;
 }
 

@@ -36,6 +36,14 @@ struct SmallKArgs {
   // rows: a lane's four consecutive columns of a row go out as one 16-byte store; s_vec: the same for the lane's s values
   int vec_out, s_vec;
   int lds_rows;   // 1: the epilogue turns every 32 x 32 tile through the wave's own LDS patch and stores WHOLE 128-byte lines
+  // Self-loop-only tail (k1_gemm_x3.hip, try_project_x3_tail; read only by the kernels built for it): rows r >= row_first store
+  // ELU(C[r, :]) (tail_elu; C itself otherwise) at tail_out + (urow ? urow[r] : r) * ld_out instead of the output segments --
+  // the level's output h'_r, alpha_rr = 1 (k12_tail.hip) -- and nothing at out.
+  int64_t row_first;
+  const int32_t* urow;
+  float* tail_out;
+  int64_t ld_out;
+  int tail_elu;
 };
 
 struct TnArgs {
@@ -74,10 +82,15 @@ __device__ __forceinline__ float* out_segment(const pygat_out_segments& out, int
 bool gemm_split(int mode);
 
 // each returns 1 (or the slab count) if it took the call, 0 if the shape does not qualify, < 0 on a launch error
-int try_gemm_smallk_x3(const SmallKArgs& g, int NT, dim3 grid, hipStream_t st);
+// tl: 0 = no tail; 1 / 2 = the SmallKArgs tail fields are set, without / with urow (the projection path only)
+int try_gemm_smallk_x3(const SmallKArgs& g, int NT, dim3 grid, hipStream_t st, int tl = 0);
 // [Wh | s] of a projection whose heads are 8 or 16 columns wide: s from the accumulators (SmallKArgs::sr_a)
 int try_project_x3(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
                    float* s, const float* a_pad, bool split, hipStream_t st);
+// the same with the self-loop-only tail's out = ELU(Wh) stored by the epilogue (SmallKArgs tail fields; Fo == Fp, no skip)
+int try_project_x3_tail(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
+                        float* s, const float* a_pad, bool split, hipStream_t st, int64_t row_first, const int32_t* urow,
+                        float* out, int elu);
 int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st);
 // any operand layout, K % 4 == 0, aligned rows, M, N > 64 (k1_gemm_x3.hip, gemm_x3g_kernel): 1 if it took the call
 int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,

@@ -601,6 +601,9 @@ int try_gemm_tn_stream(int M, int N, int64_t K, const float* A, int64_t lda, con
                        int max_splits, float* ws, bool split, hipStream_t st, int N1, const float* B2, int64_t ldb2);
 int try_project_x3(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
                    float* s, const float* a_pad, bool split, hipStream_t st);
+int try_project_x3_tail(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
+                        float* s, const float* a_pad, bool split, hipStream_t st, int64_t row_first, const int32_t* urow,
+                        float* out, int elu);
 int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                  const pygat_out_segments* out, int accumulate, int splits, int64_t k_per_split, float* ws, hipStream_t st,
                  ColBlocks ab, ColBlocks cb, int* splits_used);
@@ -752,6 +755,31 @@ extern "C" int pygat_project_blocked(int n, int Fin, int H, int Fo, const float*
   seg.col_start[k] = ncols;
   seg.nseg = k;
   return pygat_gemm_f32_blocked(0, 0, n, ncols, Fin, X, ldx, x_blk, Wcat, ldw, &seg, nullptr, 0, split_k, ws, gemm_mode, stream);
+}
+
+// The projection of a level whose self-loop-only tail (rows [row_first, n) of a degree-ordered pattern, k12_tail.hip) needs
+// nothing but its output: rows before row_first as pygat_project_blocked, and for the tail rows out[user_row[i]] = ELU(Wh_i)
+// (flags & PYGAT_F_ELU) -- what pygat_gat_forward_tail writes -- in place of Wh_i, whose rows are left unspecified.  On the
+// split-bf16 projection with s from the accumulators the epilogue stores the tail's output straight from the tile
+// (gemm_smallk_x3_kernel, TL); any other call projects every row and runs the tail stream after it.
+extern "C" int pygat_project_tail_blocked(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, const pygat_col_blocks* x_blk,
+                                          const float* Wcat, int64_t ldw, const float* a_pad, float* Wh, float* s, int split_k,
+                                          void* ws, int gemm_mode, int row_first, const int32_t* user_row, float* out, int flags,
+                                          void* stream) {
+  const int Fp = padded_width(Fo);
+  PYGAT_REQUIRE(n > 0 && Fin > 0 && H > 0 && Fp > 0 && X && Wcat && Wh && s && out, "project_tail: bad arguments");
+  PYGAT_REQUIRE(row_first >= 0 && row_first < n, "project_tail: tail rows [%d, %d) empty", row_first, n);
+  PYGAT_REQUIRE((flags & ~PYGAT_F_ELU) == 0, "project_tail: flags other than PYGAT_F_ELU (a skip projection takes the tail stream)");
+  PYGAT_REQUIRE(gemm_mode >= PYGAT_GEMM_DEFAULT && gemm_mode <= PYGAT_GEMM_FP32_MFMA, "project_tail: unknown product mode %d", gemm_mode);
+  if (!col_blocks_on(x_blk) && a_pad && split_k <= 1 && Fo == Fp) {
+    const int r = try_project_x3_tail(n, Fin, H, Fp, X, ldx, Wcat, ldw, Wh, s, a_pad, gemm_split(gemm_mode), (hipStream_t)stream,
+                                      row_first, user_row, out, (flags & PYGAT_F_ELU) ? 1 : 0);
+    if (r < 0) return r;
+    if (r == 1) return PYGAT_OK;
+  }
+  const int rc = pygat_project_blocked(n, Fin, H, Fo, X, ldx, x_blk, Wcat, ldw, a_pad, Wh, nullptr, s, split_k, ws, gemm_mode, stream);
+  if (rc) return rc;
+  return pygat_gat_forward_tail(row_first, n - row_first, H, Fo, flags, Wh, 0, nullptr, out, user_row, nullptr, nullptr, nullptr, stream);
 }
 
 // Weight gradient of one level (autograd of layers.py:35,134):  dW_h = X^T dWh_h, all heads in one GEMM.

@@ -14,6 +14,7 @@
 //
 // The split costs ~5.5 VALU operations per element and is done where the element is already in registers.
 #include "gemm_fast.h"
+#include "attn_common.h"   // (elu1: the output of a self-loop-only row, as K2 and the tail stream form it)
 #include <stdlib.h>
 #include <type_traits>
 
@@ -141,7 +142,10 @@ __device__ __forceinline__ float half_wave_sum(float x) {
 // diagnostic builds only (tools/build_variant.sh): the stamps of the last launch, 8 words per wave of at most 2048 work-groups x 8
 __device__ unsigned long long k1_stamps[2048 * 8 * 8];
 #endif
-template <bool TB, int NT, int SM, int SPC>
+//   * TL > 0 (try_project_x3_tail; SmallKArgs tail fields): rows >= row_first leave as the level's output ELU(C[r, :]) at their
+//     user row (TL = 2: urow[r]; TL = 1: r) instead of Wh -- the same store instructions with a per-row address and value, in
+//     the epilogue, where a lane already holds the row's bytes; the user rows are loaded there too (no register in the loop).
+template <bool TB, int NT, int SM, int SPC, int TL = 0>
 __global__ __launch_bounds__(512) void gemm_smallk_x3_kernel(SmallKArgs g) {
   constexpr bool SV = (SM == 1);
   constexpr int SRF = (SM >= 4) ? SM : 0;
@@ -236,6 +240,26 @@ __global__ __launch_bounds__(512) void gemm_smallk_x3_kernel(SmallKArgs g) {
     const int64_t row = row0 + fr;
     const bool row_ok = FAST || row < g.M;
     const bool full = FAST || row0 + 32 <= g.M;  // wave-uniform
+    // TL > 0: the user rows of the rows this lane stores -- FAST: rows row0 + (lane >> 3) + 8 q (the LDS patch read-back),
+    // otherwise row (clamped inside M).  Loaded first, so that the s reduction below runs under their latency.
+    int32_t tu[FAST ? 4 : 1];   // (32-bit: row indices of a [M x N] table, M < 2^31)
+    if constexpr (TL > 0) {
+#pragma unroll
+      for (int q = 0; q < (FAST ? 4 : 1); ++q) {
+        const int64_t r = FAST ? row0 + (lane >> 3) + 8 * q : (row < g.M ? row : g.M - 1);
+        tu[q] = TL == 2 ? g.urow[r] : (int32_t)r;
+      }
+    }
+    (void)tu;
+    // TL > 0: route one row's four values -- a tail row to its user row of the output, ELU'd (the tail's alpha_rr = 1)
+    auto tail_route = [&](int64_t r, int64_t u, int col, float4& v, float*& dst) {
+      const bool tl = r >= g.row_first;
+      const bool el = tl && g.tail_elu;
+      const float4 e = make_float4(elu1(v.x), elu1(v.y), elu1(v.z), elu1(v.w));
+      v.x = el ? e.x : v.x; v.y = el ? e.y : v.y; v.z = el ? e.z : v.z; v.w = el ? e.w : v.w;
+      dst = tl ? g.tail_out + u * g.ld_out + col : dst;   // (u: the user row, widened here)
+    };
+    (void)tail_route;
     if constexpr (SV) {
       if (sv_on) {
 #pragma unroll
@@ -326,8 +350,12 @@ __global__ __launch_bounds__(512) void gemm_smallk_x3_kernel(SmallKArgs g) {
             st4(patch + fr * 36 + 8 * gq + 4 * fh, make_float4(acc[nt][4 * gq], acc[nt][4 * gq + 1], acc[nt][4 * gq + 2], acc[nt][4 * gq + 3]));
           float* bq = base + (row0 + (lane >> 3)) * ld + 4 * (lane & 7);
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            st4(bq + (int64_t)8 * q * ld, ld4(patch + ((lane >> 3) + 8 * q) * 36 + 4 * (lane & 7)));
+          for (int q = 0; q < 4; ++q) {
+            float4 v = ld4(patch + ((lane >> 3) + 8 * q) * 36 + 4 * (lane & 7));
+            float* dst = bq + (int64_t)8 * q * ld;
+            if constexpr (TL > 0) tail_route(row0 + (lane >> 3) + 8 * q, tu[q], colt + 4 * (lane & 7), v, dst);
+            st4(dst, v);
+          }
         }
       } else {
       const bool vec = full && !g.accumulate && g.vec_out && colt + 32 <= g.N;
@@ -335,18 +363,25 @@ __global__ __launch_bounds__(512) void gemm_smallk_x3_kernel(SmallKArgs g) {
         int64_t ld;
         float* base = out_segment(g.out, colt, ld) + row * ld + 4 * fh;
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-          st4(base + 8 * gq, make_float4(acc[nt][4 * gq], acc[nt][4 * gq + 1], acc[nt][4 * gq + 2], acc[nt][4 * gq + 3]));
+        for (int gq = 0; gq < 4; ++gq) {
+          float4 v = make_float4(acc[nt][4 * gq], acc[nt][4 * gq + 1], acc[nt][4 * gq + 2], acc[nt][4 * gq + 3]);
+          float* dst = base + 8 * gq;
+          if constexpr (TL > 0) tail_route(row, tu[0], colt + 8 * gq + 4 * fh, v, dst);
+          st4(dst, v);
+        }
       } else if (!(PYGAT_DIAG_K1 & 1)) {   // (every segment starts at a multiple of 4 columns: try_gemm_smallk_x3)
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const int col4 = colt + 8 * gq + 4 * fh;
           int64_t ld;
           float* p = out_segment(g.out, col4, ld) + row * ld;
+          float4 v = make_float4(acc[nt][4 * gq], acc[nt][4 * gq + 1], acc[nt][4 * gq + 2], acc[nt][4 * gq + 3]);
+          if constexpr (TL > 0) tail_route(row, tu[0], col4, v, p);   // (no accumulate with a tail)
+          const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (row_ok && col4 + j < g.N) {
-              if (g.accumulate) p[j] += acc[nt][4 * gq + j]; else p[j] = acc[nt][4 * gq + j];
+              if (g.accumulate) p[j] += vv[j]; else p[j] = vv[j];
             }
         }
       }
@@ -615,6 +650,28 @@ static hipError_t launch_smallk_x3(const SmallKArgs& g, int NT, dim3 grid, size_
   return hipGetLastError();
 }
 
+// the projection with the self-loop-only tail (try_project_x3_tail): s from the accumulators (SM = 8 / 16), two or four column
+// tiles (heads of 8 / 16 columns, eight of them, or 128-column tiles of wider levels), TL 1 / 2
+template <int SM, int SPC>
+static hipError_t launch_smallk_x3_tail(const SmallKArgs& g, int NT, int tl, dim3 grid, size_t lds, hipStream_t st) {
+  int dev = -1;
+  (void)hipGetDevice(&dev);
+#define PYGAT_X3_LAUNCH(n, t)                                                                             \
+  {                                                                                                       \
+    static bool attr_set[64] = {};                                                                        \
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {                                                         \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_smallk_x3_kernel<false, n, SM, SPC, t>), \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+      if (dev >= 0 && dev < 64) attr_set[dev] = true;                                                     \
+    }                                                                                                     \
+    hipLaunchKernelGGL((gemm_smallk_x3_kernel<false, n, SM, SPC, t>), grid, dim3(512), lds, st, g);       \
+  }
+  if (NT == 4) { if (tl == 2) PYGAT_X3_LAUNCH(4, 2) else PYGAT_X3_LAUNCH(4, 1) }
+  else { if (tl == 2) PYGAT_X3_LAUNCH(2, 2) else PYGAT_X3_LAUNCH(2, 1) }
+#undef PYGAT_X3_LAUNCH
+  return hipGetLastError();
+}
+
 // s on the VALU (SV) in the pipelined loop: one or two column tiles only (with more the s accumulators spill)
 template <int SPC>
 static hipError_t launch_smallk_x3_sv(const SmallKArgs& g, int NT, dim3 grid, size_t lds, hipStream_t st) {
@@ -635,7 +692,7 @@ static hipError_t launch_smallk_x3_sv(const SmallKArgs& g, int NT, dim3 grid, si
   return hipGetLastError();
 }
 
-int try_gemm_smallk_x3(const SmallKArgs& g_in, int NT, dim3 grid, hipStream_t st) {
+int try_gemm_smallk_x3(const SmallKArgs& g_in, int NT, dim3 grid, hipStream_t st, int tl) {
   SmallKArgs g = g_in;
   const size_t lds = (size_t)3 * (32 * NT) * (g.K + 8) * sizeof(uint16_t) + (g.svec ? (size_t)g.K * 8 * sizeof(float) : 0) +
                      (g.sr_a ? (size_t)32 * NT * sizeof(float) : 0) + 16;   // (+ the four turn words of the MFMA token)
@@ -657,7 +714,13 @@ int try_gemm_smallk_x3(const SmallKArgs& g_in, int NT, dim3 grid, hipStream_t st
   // (five column tiles: the pipelined K = 128 loop spills)
   const int spc = (generic || g.accumulate || g.svec || (NT == 5 && g.K == 128)) ? 0 : (g.K == 128 ? 2 : (g.K == 64 ? 1 : 0));
   hipError_t e;
-  if (g.sr_a) {
+  if (tl) {   // (the tail: the branch-free epilogue or nothing -- its rows must not land in Wh)
+    if (!g.sr_a || spc == 0 || g.transB || g.svec || g.accumulate || !g.lds_rows || !g.s_vec || (NT != 2 && NT != 4) ||
+        (g.sr_fp != 8 && g.sr_fp != 16) || (g.N % (32 * NT)) != 0 || !g.tail_out || (g.ld_out % 4) != 0 || !aligned16(g.tail_out))
+      return 0;
+    if (spc == 2) e = g.sr_fp == 16 ? launch_smallk_x3_tail<16, 2>(g, NT, tl, grid, ldsz, st) : launch_smallk_x3_tail<8, 2>(g, NT, tl, grid, ldsz, st);
+    else e = g.sr_fp == 16 ? launch_smallk_x3_tail<16, 1>(g, NT, tl, grid, ldsz, st) : launch_smallk_x3_tail<8, 1>(g, NT, tl, grid, ldsz, st);
+  } else if (g.sr_a) {
     if (spc == 0 || g.transB || g.svec || (g.sr_fp != 8 && g.sr_fp != 16) || (g.N % (32 * NT)) != 0) return 0;
     if (spc == 2) e = g.sr_fp == 16 ? launch_smallk_x3<false, 16, 2>(g, NT, grid, ldsz, st) : launch_smallk_x3<false, 8, 2>(g, NT, grid, ldsz, st);
     else e = g.sr_fp == 16 ? launch_smallk_x3<false, 16, 1>(g, NT, grid, ldsz, st) : launch_smallk_x3<false, 8, 1>(g, NT, grid, ldsz, st);
@@ -683,6 +746,13 @@ int try_gemm_smallk_x3(const SmallKArgs& g_in, int NT, dim3 grid, hipStream_t st
 
 int try_project_x3(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
                    float* s, const float* a_pad, bool split, hipStream_t st) {
+  return try_project_x3_tail(n, Fin, H, Fp, X, ldx, Wcat, ldw, Wh, s, a_pad, split, st, -1, nullptr, nullptr, 0);
+}
+
+// row_first >= 0: rows [row_first, n) store out[urow ? urow[r] : r] = ELU(Wh_r) (elu) instead of Wh_r (out: H Fp floats a row)
+int try_project_x3_tail(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, const float* Wcat, int64_t ldw, float* Wh,
+                        float* s, const float* a_pad, bool split, hipStream_t st, int64_t row_first, const int32_t* urow,
+                        float* out, int elu) {
   const int R = H * Fp;
   if (!split || !a_pad || (Fp != 8 && Fp != 16) || (R % 32) != 0 || (Fin != 64 && Fin != 128) || n < 8192) return 0;
   if (!aligned16(X) || (ldx % 4) != 0) return 0;
@@ -694,11 +764,12 @@ int try_project_x3(int n, int Fin, int H, int Fp, const float* X, int64_t ldx, c
   g.out.nseg = 1; g.out.col_start[0] = 0; g.out.col_start[1] = R; g.out.ptr[0] = Wh; g.out.ld[0] = R;
   g.svec = nullptr; g.sv_ld = 0; g.sv_n = 0; g.s_out = s; g.s_ld = H;
   g.tiles_m = (int)cdiv(n, 256); g.transB = 0; g.sr_a = a_pad; g.sr_fp = Fp;
+  g.row_first = row_first; g.urow = urow; g.tail_out = out; g.ld_out = R; g.tail_elu = elu;
   const int tiles_n = R / (32 * NT);
   int gx = 256 / tiles_n;
   if (gx < 1) gx = 1;
   if (gx > g.tiles_m) gx = g.tiles_m;
-  return try_gemm_smallk_x3(g, NT, dim3((unsigned)gx, (unsigned)tiles_n, 1), st);
+  return try_gemm_smallk_x3(g, NT, dim3((unsigned)gx, (unsigned)tiles_n, 1), st, row_first < 0 ? 0 : (urow ? 2 : 1));
 }
 
 
@@ -1574,7 +1645,8 @@ int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A
 int footprint_gemm_x3(int which, int* regs, int* scratch) {
   hipFuncAttributes at;
   const void* fn = which == 0 ? reinterpret_cast<const void*>(&gemm_tn_x3w_kernel)
-                              : reinterpret_cast<const void*>(&gemm_x3gw_kernel<true, false>);
+                 : which == 1 ? reinterpret_cast<const void*>(&gemm_x3gw_kernel<true, false>)
+                              : reinterpret_cast<const void*>(&gemm_smallk_x3_kernel<false, 4, 16, 2, 2>);   // projection + tail output
   const hipError_t e = hipFuncGetAttributes(&at, fn);
   if (e != hipSuccess) {
     (void)hipGetLastError();

@@ -117,6 +117,15 @@ RENUMBER_MIN_BYTES_TAIL = 48 << 20
 # the nodes and more.  TAIL = False / PYGAT_TAIL=0 switches it off.
 TAIL = _config.tail
 TAIL_MIN_SHARE = 0.05
+# ... and where the projection takes it (ABI 15), the forward stream does not run: the projection's epilogue stores the tail's
+# output ELU(Wh_i) at its user row instead of Wh_i (pygat_project_tail_blocked) -- the tail's Wh rows are neither written nor
+# read.  Bitwise the same results.  Split-bf16 mode, no skip projection, F' = Fp, an ordinary x, and nothing in the backward
+# reading the tail's Wh rows (the a-gradient folded into the column pass).  Measured at config 5 (profiles/INDEX.md, tail):
+# projection 229 -> 254 us, the 125 us stream gone.  (The backward's dWh rows formed inside the weight gradient from G / y was
+# built and measured too: the streamed-K kernel went from 244 to 453 us, more than the 151 us stream it replaced -- the G / y
+# rows are gathers at the caller's rows -- so the backward keeps its stream.)  TAIL_FUSED = False / PYGAT_TAIL_FUSED=0 keeps the
+# forward stream too.
+TAIL_FUSED = _config.tail_fused
 
 
 def head_group(N: int, H: int, Fo: int) -> int:
@@ -476,26 +485,15 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
             if split_k > 1 else None
         if xs is not None and need[0]:
             xs = None                                   # a gradient into x: the dense path forms it
-        with _span("k1_project"):
-            if xs is not None:
-                check(lib.pygat_project_sparse(L.N, Fin, H, Fo, xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(),
-                                               Wcat.data_ptr(), L.ldw, 0.0, None, 0, None, Wh.data_ptr(), _ptr(Sk), s.data_ptr(),
-                                               st), "project_sparse")
-            else:
-                check(lib.pygat_project_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), Wcat.data_ptr(), L.ldw, a_pad.data_ptr(),
-                                                Wh.data_ptr(), _ptr(Sk), s.data_ptr(), split_k, _ptr(ws), GEMM_MODES[L.mode], st),
-                      "project")
-        # K2
         flags = (_lib.F_ELU if concat else 0) | (_lib.F_SKIP if skip else 0)
-        # mean over ONE head = that head (Cora / Citeseer output level, train.py:55,66): K2 writes `out` itself (its epilogue
-        # adds the skip rows, no ELU), no head-mean launch; hattn is then only kept for the backward
-        single = (not concat) and H == 1
-        hattn = torch.empty(L.N, L.R, dtype=f32, device=dev) if (not concat and (need_grad or not single)) else None
-        m = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
-        Z = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
         flavour = backward_flavour(L.R) if need_grad else None
-        aneg = torch.empty(L.N, L.R, dtype=f32, device=dev) if flavour == "rowlocal" else None
-        qneg = torch.empty(L.N, H, dtype=f32, device=dev) if flavour == "rowlocal" else None
+        # (a degree-ordered pattern: reached through the renumbering above -- user_row maps `out` / G to the caller's rows -- or
+        # handed in by a model that keeps ALL its node arrays in internal order, graph.InternalOrderView: no map)
+        if (TAIL and graph.degree_sorted and concat and graph.symmetric
+                and (not need_grad or (flavour == "rowlocal" and L.hg >= H and bwd_heads is None))):
+            t = graph.fwd.self_loop_tail(L.ts)
+            if t is not None and L.N - t[0] >= TAIL_MIN_SHARE * L.N:
+                tail = (t[0], t[2], t[1])
         out = pipeline[2] if (pipeline is not None and len(pipeline) > 2 and concat) else None    # the caller's buffer (dist.py:
         if out is not None:                                                                           # the rank's block of the exchange)
             if tuple(out.shape) != (L.N, H * Fo) or out.dtype != f32 or not out.is_contiguous() or out.device != dev:
@@ -506,15 +504,42 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
             out = torch.empty(0, dtype=f32, device=dev).set_(out.untyped_storage(), out.storage_offset(), out.shape, out.stride())
         else:
             out = torch.empty(L.N, H * Fo if concat else Fo, dtype=f32, device=dev)
+        # the tail's output straight from the projection's epilogue (TAIL_FUSED): its Wh rows are then never written, so
+        # nothing may read them -- with a backward, the a-gradient has to come from the column pass (its fold reads the prefix)
+        fuse_fwd = (TAIL_FUSED and tail is not None and not skip and L.Fo == L.Fp and xs is None and x.dim() == 2
+                    and L.mode == "split-bf16"
+                    and (not need_grad or (DA_IN_K4 and need[2] and L.N * L.R * 4 >= DA_MIN_BYTES
+                                           and lib.pygat_gat_backward_col_da_bytes(tail[1], H, Fo, H) > 0)))
+        with _span("k1_project"):
+            if xs is not None:
+                check(lib.pygat_project_sparse(L.N, Fin, H, Fo, xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(),
+                                               Wcat.data_ptr(), L.ldw, 0.0, None, 0, None, Wh.data_ptr(), _ptr(Sk), s.data_ptr(),
+                                               st), "project_sparse")
+            elif fuse_fwd:
+                check(lib.pygat_project_tail_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), Wcat.data_ptr(), L.ldw,
+                                                     a_pad.data_ptr(), Wh.data_ptr(), s.data_ptr(), split_k, _ptr(ws),
+                                                     GEMM_MODES[L.mode], tail[0], _ptr(user_row), out.data_ptr(), flags, st),
+                      "project_tail")
+            else:
+                check(lib.pygat_project_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), Wcat.data_ptr(), L.ldw, a_pad.data_ptr(),
+                                                Wh.data_ptr(), _ptr(Sk), s.data_ptr(), split_k, _ptr(ws), GEMM_MODES[L.mode], st),
+                      "project")
+        # K2
+        # mean over ONE head = that head (Cora / Citeseer output level, train.py:55,66): K2 writes `out` itself (its epilogue
+        # adds the skip rows, no ELU), no head-mean launch; hattn is then only kept for the backward
+        single = (not concat) and H == 1
+        hattn = torch.empty(L.N, L.R, dtype=f32, device=dev) if (not concat and (need_grad or not single)) else None
+        m = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
+        Z = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
+        aneg = torch.empty(L.N, L.R, dtype=f32, device=dev) if flavour == "rowlocal" else None
+        qneg = torch.empty(L.N, H, dtype=f32, device=dev) if flavour == "rowlocal" else None
         part = torch.empty(lib.pygat_partials_bytes(graph.nnz, L.ts, H, L.Fp) // 4, dtype=f32,
                            device=dev)
-        # (a degree-ordered pattern: reached through the renumbering above -- user_row maps `out` / G to the caller's rows -- or
-        # handed in by a model that keeps ALL its node arrays in internal order, graph.InternalOrderView: no map)
-        if (TAIL and graph.degree_sorted and concat and graph.symmetric
-                and (not need_grad or (flavour == "rowlocal" and L.hg >= H and bwd_heads is None))):
-            t = graph.fwd.self_loop_tail(L.ts)
-            if t is not None and L.N - t[0] >= TAIL_MIN_SHARE * L.N:
-                tail = (t[0], t[2], t[1])
+        if fuse_fwd and m is not None:     # the tail's records as pygat_gat_forward_tail leaves them: m = 0, Z = 1, qneg = 0
+            m[tail[0]:].zero_()
+            Z[tail[0]:].fill_(1.0)
+            if qneg is not None:
+                qneg[tail[0]:].zero_()
         chunks = [(graph.fwd.ref(L.ts) if tail is None else tail[1], 0, L.N if tail is None else tail[0])]
         if pipeline is not None and concat and pipeline[0] > 1:
             chunks = (graph.fwd.row_chunks(int(pipeline[0]), L.ts) if tail is None
@@ -541,7 +566,7 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
                 continue
             with _span("k2_forward"):
                 k2(gref, flags, st)
-                if tail is not None and c == len(chunks) - 1:     # the self-loop-only rows: out = ELU(Wh (+ skip)), one stream
+                if tail is not None and c == len(chunks) - 1 and not fuse_fwd:   # the self-loop-only rows: out = ELU(Wh (+ skip))
                     check(lib.pygat_gat_forward_tail(tail[0], L.N - tail[0], H, Fo, flags, Wh.data_ptr(), 0, _ptr(Sk), out.data_ptr(),
                                                      _ptr(user_row), _ptr(m), _ptr(Z), _ptr(qneg), st), "gat_forward_tail")
             if pipeline is not None and concat:
@@ -549,8 +574,9 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         if phases:
             main_s.wait_stream(side_s)
             if tail is not None:       # (pipelined chunks: the tail is one more hand-off, after the last chunk's)
-                check(lib.pygat_gat_forward_tail(tail[0], L.N - tail[0], H, Fo, flags, Wh.data_ptr(), 0, _ptr(Sk), out.data_ptr(),
-                                                 _ptr(user_row), _ptr(m), _ptr(Z), _ptr(qneg), st), "gat_forward_tail")
+                if not fuse_fwd:
+                    check(lib.pygat_gat_forward_tail(tail[0], L.N - tail[0], H, Fo, flags, Wh.data_ptr(), 0, _ptr(Sk), out.data_ptr(),
+                                                     _ptr(user_row), _ptr(m), _ptr(Z), _ptr(qneg), st), "gat_forward_tail")
                 pipeline[1](len(chunks), tail[0], L.N, out)
         if not concat and not single:
             check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
@@ -560,6 +586,7 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         ctx.graph, ctx.L, ctx.alpha, ctx.concat, ctx.flags = graph, L, float(alpha), concat, flags
         ctx.user_row = user_row
         ctx.tail = tail
+        ctx.tail_fwd_fused = fuse_fwd
         ctx.xs = xs
         ctx.flavour = flavour
         ctx.bwd_heads = None
