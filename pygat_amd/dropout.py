@@ -81,6 +81,9 @@ class GATLevelDropoutFn(torch.autograd.Function):
     def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha, concat, p, mask_x, mask_wh, mask_att, seed, xs=None):
         if not x.is_cuda:
             raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
+        if graph.user_row is not None:    # (its K2 would write `out` through the map, its backward read G without it)
+            raise ValueError("pygat_amd: the dropout level does not take a graph with a row map (CSRGraph.degree_ordered); "
+                             "pass CSRGraph.internal_view() and keep x and `out` in internal order instead")
         ctx.in_dtypes = (x.dtype, W.dtype, a.dtype, None if Wskip is None else Wskip.dtype)
         x = x.contiguous().float(); W = W.contiguous().float(); a = a.contiguous().float()
         H, Fin, Fo = W.shape

@@ -44,7 +44,11 @@ class GATv2LevelFn(torch.autograd.Function):
         # Internal node order + self-loop-only tail, as for the v1 level (ops._level_forward): no masks, no
         # gradient into x, concat.  A node whose only edge is its self loop has alpha_ii = 1: h'_i = ELU(Whi_i (+ skip_i))
         # (layers.py:296 with one edge), dWhi_i = Gp_i, dWhj_i = 0, no share in da.
-        user_row = tail = None
+        # (a degree-ordered graph handed in directly carries its row map: out / G / the saved output at the caller's rows)
+        user_row, tail = graph.user_row, None
+        if user_row is not None and not concat:
+            raise ValueError("pygat_amd: a graph with a row map (CSRGraph.degree_ordered) takes no mean over heads; pass "
+                             "CSRGraph.internal_view() and keep x and `out` in internal order instead")
         if (ops.RENUMBER and masks is None and not ctx.needs_input_grad[0] and concat and graph.user_row is None
                 and not graph.degree_sorted and L.N * 2 * L.R * 4 >= min(ops.RENUMBER_MIN_BYTES, ops.RENUMBER_MIN_BYTES_TAIL)
                 and not torch.cuda.is_current_stream_capturing()):

@@ -167,7 +167,8 @@ class _Pattern:
         the rows [row_first, n) have only their self loop and occupy exactly the slots [first_slot, n_slots); `prefix` is the
         pygat_graph* of the slots before them (slot_first 0, slot_count first_slot) for pygat_gat_forward / pygat_gat_backward_col /
         pygat_a_grad_fold, the tail goes to pygat_gat_forward_tail / pygat_gat_backward_col_tail (csrc/k12_tail.hip).
-        None when there is no such tail.  Computed once per slot length (two host reads)."""
+        None when there is no such tail, when it does not begin a slot of its own, or when it is every row (an empty prefix).
+        Computed once per slot length (two host reads)."""
         ts = slot_edges or self.slot_edges
         key = ("tail", ts)
         if key not in self._alt:
@@ -181,7 +182,8 @@ class _Pattern:
                 if n1 < self.n and bool((deg[n1:] == 1).all().item()) and bool((self.col[rp[n1]:].long() == torch.arange(n1, self.n, device=self.col.device)).all().item()):
                     first_row = meta[:, 2].long()
                     k = int(torch.searchsorted(first_row, torch.tensor(n1, device=first_row.device)).item())
-                    if k < meta.shape[0]:
+                    # k = 0 (every row self-loop-only): no slot prefix -- and slot_count 0 would mean ALL slots to the C ABI
+                    if 0 < k < meta.shape[0]:
                         row_first = int(first_row[k].item())
                         pre = _lib.Graph()
                         C.memmove(C.byref(pre), C.byref(st), C.sizeof(_lib.Graph))

@@ -448,9 +448,14 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         raise ValueError(f"x has {L.N} rows but the graph has {graph.n} nodes")
     if L.blocks is not None:
         xs = None
-    user_row = None
-    tail = None      # (first tail row, pygat_graph* of the slot prefix) when the self-loop-only tail goes through its own streams
+    # a degree-ordered graph handed in directly (CSRGraph.degree_ordered: x in internal order) carries its row map: `out` is
+    # written, G and the saved output are read at the caller's rows -- by every kernel of the level, the tail's included
+    user_row = graph.user_row
     single_out = (not concat) and H == 1
+    if user_row is not None and (pipeline is not None or not (concat or single_out)):
+        raise ValueError("pygat_amd: a graph with a row map (CSRGraph.degree_ordered) takes neither a pipeline nor a mean over "
+                         "several heads; pass CSRGraph.internal_view() and keep x and `out` in internal order instead")
+    tail = None      # (first tail row, pygat_graph* of the slot prefix) when the self-loop-only tail goes through its own streams
     if (RENUMBER and not need[0] and xs is None and pipeline is None and x.dim() == 2 and (concat or single_out)
             and graph.user_row is None and not graph.degree_sorted and L.N * L.R * 4 >= min(RENUMBER_MIN_BYTES, RENUMBER_MIN_BYTES_TAIL)
             and not torch.cuda.is_current_stream_capturing()):     # (a captured graph would bake this epoch's permuted copy of x in)
