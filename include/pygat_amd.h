@@ -433,6 +433,8 @@ int pygat_project_tail_blocked(int n, int Fin, int H, int Fo, const float* X, in
  *   e_ij = a . LeakyReLU(Whi_i + Whj_j), alpha = row softmax, h'_i = sum_j alpha_ij Whi_j  (Whi is aggregated,
  *   layers.py:296).  WW [n x 2R] holds [Whi | Whj] rows (one projection GEMM with W[:Fin] and W[Fin:]),
  *   a2 [H x Fp] the zero-padded attention vectors.  Same outputs / flags / part as pygat_gat_forward.
+ *   Limits: F' <= 256 per head as everywhere, and R = H * Fp <= 1024 (a [Whi | Whj] row of at most 2048 floats, never
+ *   split into head windows); pygat_gatv2_forward / _backward return an error above that; GATv2LevelFn raises ValueError first.
  * (GraphAttentionLayerV2, layers.py:204-230, broadcasts one logit per ROW and is therefore a neighbour mean:
  *  it maps onto pygat_gat_forward with s = 0 and a = 0.)
  */

@@ -41,6 +41,8 @@ class GATv2LevelFn(torch.autograd.Function):
             raise ValueError(f"shape mismatch: x {tuple(x.shape)}, W {tuple(W.shape)}, a {tuple(a.shape)}")
         skip = Wskip is not None
         L = _Level(x, H, Fo, skip)
+        if L.R > 1024:     # before anything runs: K2's V2 variant and csrc/k6_gatv2_backward.hip take one [Whi | Whj] row of 2R <= 2048 floats
+            raise ValueError(f"pygat_amd: GATv2 row too wide: H x padded F' = {H} x {L.Fp} = {L.R} > 1024; shard the heads")
         # Internal node order + self-loop-only tail, as for the v1 level (ops._level_forward): no masks, no
         # gradient into x, concat.  A node whose only edge is its self loop has alpha_ii = 1: h'_i = ELU(Whi_i (+ skip_i))
         # (layers.py:296 with one edge), dWhi_i = Gp_i, dWhj_i = 0, no share in da.
@@ -66,8 +68,6 @@ class GATv2LevelFn(torch.autograd.Function):
             t = graph.fwd.self_loop_tail(L.ts)
             if t is not None and L.N - t[0] >= ops.TAIL_MIN_SHARE * L.N:
                 tail = (t[0], t[2])
-        if 2 * L.R > 2048:
-            raise ValueError("pygat_amd: GATv2 row too wide; shard the heads")
         dev, f32 = x.device, torch.float32
         R, Fp = L.R, L.Fp
         # operand of the projection: columns [Wi heads | Wj heads | skip heads], heads padded to Fp

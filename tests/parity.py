@@ -82,17 +82,17 @@ FLIP_FACTOR = 2
 FLIP_SLACK = 3
 
 
-def _flip_leash(report, rel, tau, what):
+def _flip_leash(report, rel, tau, what, units="edges", scale="|s|+|t|"):
     """rel[k] = |z64| / (|s| + |t|) of candidate k.  Asserts the leash described above; returns the log line."""
     for side in ("hip", "fp32"):
         for k in report[side + "_flip_idx"]:
-            assert rel[k] <= tau, f"{what}: {side} flip at candidate {k} with |z|/(|s|+|t|) = {rel[k]:.2e} outside the band {tau:.1e}"
+            assert rel[k] <= tau, f"{what}: {side} flip at candidate {k} with |z|/({scale}) = {rel[k]:.2e} outside the band {tau:.1e}"
     nh, nf = len(report["hip_flip_idx"]), len(report["fp32_flip_idx"])
     assert nh <= FLIP_FACTOR * nf + FLIP_SLACK, (
-        f"{what}: the HIP path takes the other LeakyReLU branch at {nh} of {report['candidates']} near-kink edges, the fp32 "
+        f"{what}: the HIP path takes the other LeakyReLU branch at {nh} of {report['candidates']} near-kink {units}, the fp32 "
         f"oracle at {nf}: more than {FLIP_FACTOR} x + {FLIP_SLACK}")
     far = max([rel[k] for k in report["hip_flip_idx"]], default=0.0)
-    return (f"{what}: {report['candidates']} edges within {tau:.0e} (|s|+|t|) of the kink; branch flips hip {nh} "
+    return (f"{what}: {report['candidates']} {units} within {tau:.0e} ({scale}) of the kink; branch flips hip {nh} "
             f"(farthest at {far:.1e}), fp32 oracle {nf}")
 
 
@@ -365,3 +365,180 @@ def check_autograd(got_out, got_grads, fn, leaves64, G64, names, what="level"):
             continue
         rep[name] = close_grad(got, r64.reshape(got.shape), r32.reshape(got.shape), f"{what} {name}")[0]
     return rep, (y64, g64)
+
+
+# ---------------------------------------------------------------------------------------------------
+# The same flip-aware rule for a GATv2 level (SpGraphAttentionLayerV2, layers.py:234-316; csrc/k6_gatv2_backward.hip).
+#
+# There the LeakyReLU acts per FEATURE: e_ij = sum_f a_f LeakyReLU(z_ijf), z_ijf = Whi_i[f] + Whj_j[f], so every
+# (edge, head, feature) has a kink of its own.  A flip of (e = (i, j), h, f) changes dz_ijf = de_ij a_f (1 or alpha) by
+# D = de_ij a_f sgn, sgn = (alpha - 1) if z > 0 else (1 - alpha); everything downstream is linear in dz:
+#   dW_h[:Fin, f] += D X_i,  dW_h[Fin:, f] += D X_j,  dX_i += D W_h[:Fin, f],  dX_j += D W_h[Fin:, f],
+#   da_h[f] += de_ij z sgn (the LeakyReLU value itself moves by z sgn: tiny inside the band, kept all the same);
+# nothing reaches dW_skip, and `out` moves by a_f z sgn only.
+#   * candidates: (e, h, f) with |z| <= KINK_TAU * (|Whi_i[f]| + |Whj_j[f]|) in fp64 -- Whi and Whj are fp32 dot products
+#     over Fin terms, the same rounding band as v1's s_i, t_j (at most KINK_MAX, nearest first);
+#   * the fit is `_explain` over dX, dW and da jointly, restricted to the entries a candidate can touch (the rows i, j of dX,
+#     the columns (h, f) of dW, all of da): the rest of each tensor does not depend on the flips;
+#   * the leash is v1's (_flip_leash); the remainder is priced by close_grad's rule, max(1e-5, 4 x the fp32 oracle's own
+#     error after the same flip treatment).
+# Ground truth: oracle.level_forward_v2 through torch autograd in fp64, its fp32 run = the reference's own precision;
+# z and de_ij = alpha_ij (dp_ij - D_i), dp_ij = Gp_i . Whi_j, are formed in fp64 numpy, in edge chunks.
+# ---------------------------------------------------------------------------------------------------
+def v2_kinks(X, rowptr, col, W, a, alpha, concat, G, Wskip=None, tau=KINK_TAU, cap=KINK_MAX, chunk=1 << 20):
+    """Near-kink (edge, head, feature) triples of a GATv2 level in fp64.  X [N,Fin], W [H,2Fin,F], a [H,F], G = dL/dout.
+    -> dict(h, e, f, i, j, z, de, rel) sorted by rel = |z| / (|Whi_i[f]| + |Whj_j[f]|), at most `cap` entries, plus
+    n_band = the number inside the band before the cap."""
+    X = np.asarray(X, np.float64); W = np.asarray(W, np.float64); a = np.asarray(a, np.float64).reshape(W.shape[0], -1)
+    G = np.asarray(G, np.float64)
+    rowptr = np.asarray(rowptr, np.int64); col = np.asarray(col, np.int64)
+    N, Fin = X.shape; H, _, Fo = W.shape
+    deg = np.diff(rowptr)
+    assert deg.min() > 0, "v2_kinks: every row needs an edge (the levels reject empty rows)"
+    src = np.repeat(np.arange(N), deg)
+    # row blocks of about `chunk` (edge, feature) entries: segment sums over whole rows with reduceat
+    blocks, r0 = [], 0
+    while r0 < N:
+        r1 = int(np.searchsorted(rowptr, rowptr[r0] + max(1, chunk // max(Fo, 1)), side="right")) - 1
+        r1 = min(N, max(r1, r0 + 1))
+        blocks.append((r0, r1, int(rowptr[r0]), int(rowptr[r1])))
+        r0 = r1
+    found = []
+    for h in range(H):
+        Whi, Whj = X @ W[h, :Fin], X @ W[h, Fin:]
+        Gp = np.empty((N, Fo)); de = np.empty(len(col))
+        for r0, r1, e0, e1 in blocks:
+            s_, c_, seg = src[e0:e1], col[e0:e1], rowptr[r0:r1] - e0
+            z = Whi[s_] + Whj[c_]
+            ev = np.where(z > 0, z, alpha * z) @ a[h]
+            p = np.exp(ev - np.maximum.reduceat(ev, seg)[s_ - r0])
+            al = p / np.add.reduceat(p, seg)[s_ - r0]
+            hp = np.add.reduceat(al[:, None] * Whi[c_], seg, axis=0)        # aggregation of Whi at the neighbour
+            pre = hp if Wskip is None else hp + X[r0:r1] @ np.asarray(Wskip, np.float64)[h]
+            if concat:
+                Gp[r0:r1] = G[r0:r1, h * Fo:(h + 1) * Fo] * np.where(pre > 0, 1.0, np.exp(np.minimum(pre, 0)))
+            else:
+                Gp[r0:r1] = G[r0:r1] / H
+            dp = np.einsum("ef,ef->e", Gp[s_], Whi[c_])
+            de[e0:e1] = al * (dp - np.add.reduceat(al * dp, seg)[s_ - r0])
+            rel = np.abs(z) / np.maximum(np.abs(Whi[s_]) + np.abs(Whj[c_]), 1e-300)
+            ee, ff = np.nonzero(rel <= tau)
+            if len(ee):
+                found.append((np.full(len(ee), h), e0 + ee, ff, z[ee, ff], de[e0 + ee], rel[ee, ff]))
+    if found:
+        hh, ee, ff, zz, dd, rr = (np.concatenate(v) for v in zip(*found))
+    else:
+        hh = ee = ff = np.zeros(0, np.int64); zz = dd = rr = np.zeros(0)
+    order = np.argsort(rr, kind="stable")[:cap]
+    ee = ee[order]
+    return dict(h=hh[order], e=ee, f=ff[order], i=src[ee], j=col[ee], z=zz[order], de=dd[order], rel=rr[order], n_band=len(rr))
+
+
+def _v2_flip_effects(k, X, W, a, alpha):
+    """Per candidate q: (i, j, h, f, D, dda) -- the sparse effect of taking the other branch at (e, h, f)."""
+    Fin = X.shape[1]
+    sgn = np.where(k["z"] > 0, alpha - 1.0, 1.0 - alpha)
+    D = k["de"] * a[k["h"], k["f"]] * sgn
+    dda = k["de"] * k["z"] * sgn
+    return D, dda, Fin
+
+
+def _v2_apply(resid, k, D, dda, q, X, W, Fin, sign=-1.0):
+    """Add sign x (effect of flip q) to the full-size residual tensors."""
+    i, j, h, f = int(k["i"][q]), int(k["j"][q]), int(k["h"][q]), int(k["f"][q])
+    resid["dW"][h, :Fin, f] += sign * D[q] * X[i]
+    resid["dW"][h, Fin:, f] += sign * D[q] * X[j]
+    resid["da"][h, f] += sign * dda[q]
+    if "dX" in resid:
+        resid["dX"][i] += sign * D[q] * W[h, :Fin, f]
+        resid["dX"][j] += sign * D[q] * W[h, Fin:, f]
+
+
+def v2_oracle(X, rowptr, col, W, a, alpha, concat, G, Wskip=None, dtype=torch.float64):
+    """out and every gradient of oracle.level_forward_v2 through torch autograd, as numpy fp64."""
+    from oracle import gat_oracle as O
+    leaves = [torch.as_tensor(np.asarray(v, np.float64)).to(dtype).requires_grad_(True)
+              for v in ((X, W, a) if Wskip is None else (X, W, a, Wskip))]
+    y = O.level_forward_v2(leaves[0], (rowptr, col), leaves[1], leaves[2], alpha, concat, leaves[3] if Wskip is not None else None)
+    gr = torch.autograd.grad(y, leaves, torch.as_tensor(np.asarray(G, np.float64)).to(dtype))
+    res = {n: g.detach().double().numpy() for n, g in zip(("dX", "dW", "da", "dW_skip"), gr)}
+    res["out"] = y.detach().double().numpy()
+    return res
+
+
+def close_level_grads_v2(got, X, rowptr, col, W, a, alpha, concat, G, Wskip=None, what="v2 level", factor=4.0, floor=ATOL,
+                         refs=None):
+    """The GATv2 counterpart of close_level_grads: got = dict(dX (or None), dW [H,2Fin,F], da [H,F][, dW_skip]) from the HIP
+    path; X, W, a, G, Wskip the fp64 arrays whose fp32 roundings it was fed.  refs = (ref64, ref32) of v2_oracle if already
+    formed.  Returns a report dict (as close_level_grads')."""
+    X = np.asarray(X, np.float64); W = np.asarray(W, np.float64); a = np.asarray(a, np.float64).reshape(W.shape[0], -1)
+    G = np.asarray(G, np.float64)
+    Sk = None if Wskip is None else np.asarray(Wskip, np.float64)
+    f32 = lambda v: None if v is None else v.astype(np.float32).astype(np.float64)  # noqa: E731
+    if refs is None:
+        refs = (v2_oracle(X, rowptr, col, W, a, alpha, concat, G, Sk),
+                v2_oracle(f32(X), rowptr, col, f32(W), f32(a), alpha, concat, f32(G), f32(Sk), dtype=torch.float32))
+    ref64, ref32 = refs
+    with_dx = got.get("dX") is not None
+    names = (["dX"] if with_dx else []) + ["dW", "da"]
+    k = v2_kinks(X, rowptr, col, W, a, alpha, concat, G, Sk)
+    nc = len(k["e"])
+    D, dda, Fin = _v2_flip_effects(k, X, W, a, alpha)
+    # the entries a candidate can touch: rows of dX, (h, f) columns of dW (all of da takes part)
+    rows = np.unique(np.concatenate([k["i"], k["j"]])) if nc else np.zeros(0, np.int64)
+    rpos = {int(r): q for q, r in enumerate(rows)}
+    hf = sorted({(int(h), int(f)) for h, f in zip(k["h"], k["f"])})
+    cpos = {c: q for q, c in enumerate(hf)}
+    cols = []
+    for q in range(nc):
+        i, j, h, f = int(k["i"][q]), int(k["j"][q]), int(k["h"][q]), int(k["f"][q])
+        c = {"dWT": np.zeros((len(hf), 2 * Fin)), "da": np.zeros_like(a)}
+        c["dWT"][cpos[(h, f)], :Fin] = D[q] * X[i]
+        c["dWT"][cpos[(h, f)], Fin:] = D[q] * X[j]
+        c["da"][h, f] = dda[q]
+        if with_dx:
+            c["dXT"] = np.zeros((len(rows), Fin))
+            c["dXT"][rpos[i]] += D[q] * W[h, :Fin, f]
+            c["dXT"][rpos[j]] += D[q] * W[h, Fin:, f]
+        cols.append(c)
+    fit_names = (["dXT"] if with_dx else []) + ["dWT", "da"]
+    hh_, ff_ = (np.array([c[0] for c in hf], np.int64), np.array([c[1] for c in hf], np.int64))
+    report = {"candidates": nc, "in_band": k["n_band"]}
+    for side, vals in (("hip", {n: _np64(got[n]).reshape(ref64[n].shape) for n in names}),
+                       ("fp32", {n: np.asarray(ref32[n], np.float64) for n in names})):
+        resid = {n: vals[n] - ref64[n] for n in names}
+        report[side + "_raw"] = {n: float(np.abs(resid[n]).max()) for n in names}
+        sub = {"dWT": resid["dW"][hh_, :, ff_] if nc else np.zeros((0, 2 * Fin)), "da": resid["da"]}
+        if with_dx:
+            sub["dXT"] = resid["dX"][rows]
+        sig = _explain(sub, cols, fit_names) if nc else np.zeros(0)
+        for q in range(nc):
+            if sig[q]:
+                _v2_apply(resid, k, D, dda, q, X, W, Fin)
+        report[side] = {n: float(np.abs(resid[n]).max()) for n in names}
+        report[side + "_flip_idx"] = [q for q in range(nc) if sig[q]]
+        report[side + "_flips"] = [(int(k["h"][q]), int(k["e"][q]), int(k["f"][q])) for q in range(nc) if sig[q]]
+    report["flips"] = _flip_leash(report, k["rel"], KINK_TAU, what, "(edge, feature) pairs", "|Whi|+|Whj|")
+    for n in names:
+        assert np.isfinite(_np64(got[n])).all(), f"{what} {n}: non-finite values"
+        tol = max(floor, factor * report["fp32"][n])
+        assert report["hip"][n] <= tol, (
+            f"{what} {n}: max abs err {report['hip'][n]:.3e} (raw {report['hip_raw'][n]:.3e}) > {tol:.3e} = max({floor:.0e}, "
+            f"{factor:g} x fp32-oracle err {report['fp32'][n]:.3e}) after {len(report['hip_flips'])} LeakyReLU branch flips "
+            f"({nc} near-kink (edge, feature) pairs); max |ref| {np.abs(ref64[n]).max():.3g}")
+    if Sk is not None and got.get("dW_skip") is not None:        # no kink on this path
+        close_grad(got["dW_skip"], ref64["dW_skip"], ref32["dW_skip"], f"{what} dW_skip", factor, floor)
+    report["ref64"], report["ref32"] = ref64, ref32
+    return report
+
+
+def check_level_v2(out, grads, X, rowptr, col, W, a, alpha, concat, G, Wskip=None, what="v2 level", verbose=True):
+    """A whole GATv2 level against the oracle: `out` by close_fwd, grads = dict(dX|None, dW, da[, dW_skip]) by the flip-aware
+    close_level_grads_v2."""
+    rep = close_level_grads_v2(grads, X, rowptr, col, W, a, alpha, concat, G, Wskip, what)
+    rep["out_err"] = close_fwd(out, rep["ref64"]["out"], f"{what} out", rep["ref32"]["out"])
+    if verbose:
+        names = [n for n in ("dX", "dW", "da") if n in rep["hip"]]
+        print(f"{rep['flips']}; out {rep['out_err']:.2e}; "
+              + ", ".join(f"{n} {rep['hip'][n]:.2e} (fp32 oracle {rep['fp32'][n]:.2e})" for n in names))
+    return rep

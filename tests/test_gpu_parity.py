@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import gat_oracle as O
+from ladder_case import _ladder_graph
 from parity import check_level, close_fwd, close_grad
 
 pytestmark = pytest.mark.gpu
@@ -581,24 +582,6 @@ def test_pubmed_full_model_logits_and_output_level(pg, topologies):
 
 
 # ------------------------------------------------------------------- cut rows of every length, all row widths
-def _ladder_graph(N=360, seed=5):
-    """Symmetric pattern + self loops whose degrees run from 3 to ~180: with 4-edge slots the cut-row list holds chains of 2 ...
-    40+ pieces -- packed entries (several rows per wave of the list-driven fix-ups), every remainder of the last wave, and
-    `wide` entries (more than 32 pieces: a whole work-group each)."""
-    rng = np.random.default_rng(seed)
-    r, c = [], []
-    for i in range(N):
-        d = 170 if i % 45 == 0 else (40 if i % 45 == 7 else 1 + (i * 7) % 6)   # forward neighbours, symmetrised below
-        nb = (i + 1 + rng.choice(N - 1, size=d, replace=False)) % N
-        r.append(np.full(d, i)); c.append(nb)
-    r = np.concatenate(r); c = np.concatenate(c)
-    rr = np.concatenate([r, c, np.arange(N)]); cc = np.concatenate([c, r, np.arange(N)])
-    key = np.unique(rr.astype(np.int64) * N + cc)
-    rr = (key // N).astype(np.int32); cc = (key % N).astype(np.int32)
-    rowptr = np.zeros(N + 1, dtype=np.int64); np.add.at(rowptr, rr + 1, 1)
-    return np.cumsum(rowptr).astype(np.int32), cc
-
-
 @pytest.mark.parametrize("H,Fo", [(1, 16), (2, 16), (4, 16), (8, 16), (8, 64)])   # 4 / 8 / 16 / 32 / 64 lanes per row
 def test_cut_rows_of_every_length(pg, H, Fo):
     rowptr, col = _ladder_graph()
