@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PYGAT_ABI_VERSION 15
+#define PYGAT_ABI_VERSION 16
 
 enum {
   PYGAT_OK = 0,
@@ -454,6 +454,26 @@ size_t pygat_gatv2_workspace_bytes(int64_t nnz, int slot_edges, int H, int Fo);
 int pygat_gatv2_backward(const pygat_graph* g, const pygat_graph* gT, const int32_t* perm_t, const int32_t* perm_f,
                          int H, int Fo, float alpha, const float* WW, const float* a2, const float* GRW,
                          const float* att_mask, float* dWW, float* da, void* ws, void* stream);
+
+/* ------------------------------------------------ K13: attention coefficients (ABI 16, csrc/k13_attention.hip)
+ * att [nnz x H] fp32, head-contiguous per edge: att[k*H + h] = exp(e_ij - m_i) / Z_i for edge k = (i, j) of the CALLER's
+ * pattern (rowptr [n+1], edge_rc [nnz][2] = (row, col) per edge, 8-byte aligned), the coefficient the forward normalised by,
+ * taken after the x / Wh dropout masks (the tables carry them) and before the attention mask.
+ *   v1:    e_ij = LeakyReLU(s_i + t_j),  t_j = Wh_j . a_dst  (a_pad [H][2][Fp] as for pygat_gat_forward);
+ *   GATv2: e_ij = a . LeakyReLU(Whi_i + Whj_j),  WW [n x 2R] = [Whi | Whj], a2 [H x Fp]  (R = H * Fp <= 1024).
+ * The tables (Wh / WW, s, m, Z) are the level's, as its forward left them, with n rows each; to_internal (NULL: identity)
+ * maps a caller node to its table row when the level ran in an internal node order (CSRGraph.degree_ordered).  m, Z: the
+ * row maxima and sums pygat_gat_forward / pygat_gatv2_forward wrote.  A row with exactly one edge gets exactly 1.0 and none
+ * of its table rows is read (the self-loop-only tail: unwritten Wh rows with PYGAT_F_ELU fused into the projection, m / Z
+ * fill values).  v1 scratch: t [n x H] floats; t is formed for the table rows [0, t_rows) only -- rows at and after t_rows
+ * must be self-loop-only rows that no other row gathers (the tail of a symmetric degree-ordered pattern).  Edge-parallel,
+ * no atomics, bitwise reproducible.  Memory is the caller's; alpha = the LeakyReLU slope. */
+int pygat_gat_attention(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, const int32_t* to_internal,
+                        int H, int Fo, float alpha, const float* Wh, int64_t ldwh, const float* s, const float* a_pad,
+                        const float* m, const float* Z, int t_rows, float* t, float* att, void* stream);
+int pygat_gatv2_attention(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, const int32_t* to_internal,
+                          int H, int Fo, float alpha, const float* WW, const float* a2, const float* m, const float* Z,
+                          float* att, void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

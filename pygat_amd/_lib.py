@@ -23,7 +23,7 @@ from .config import config as _config  # noqa: E402
 if _config.lib_path:
     LIB_PATH = os.path.abspath(_config.lib_path)
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 F_ELU = 1
 F_SKIP = 2
 F_MAIN_ONLY = 4
@@ -41,6 +41,7 @@ SYMBOLS = [
     "pygat_gat_backward_col_da_bytes", "pygat_a_grad_fold",
     "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
     "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
+    "pygat_gat_attention", "pygat_gatv2_attention",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -137,6 +138,8 @@ def _load():
     lib.pygat_gatv2_workspace_bytes.argtypes = [i64, i, i, i]
     lib.pygat_gatv2_workspace_bytes.restype = sz
     lib.pygat_gatv2_backward.argtypes = [C.POINTER(Graph), C.POINTER(Graph), p, p, i, i, f, p, p, p, p, p, p, p, p]
+    lib.pygat_gat_attention.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, p, p, p, i, p, p, p]
+    lib.pygat_gatv2_attention.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz

@@ -233,8 +233,10 @@ class AllReduceSum(torch.autograd.Function):
 
 
 def gat_level_head_parallel(x, graph, Ws, As, Wskips, alpha: float, concat: bool, dropout: float = 0.0,
-                            level_fn: Optional[Callable] = None) -> torch.Tensor:
+                            level_fn: Optional[Callable] = None, return_attention: bool = False) -> torch.Tensor:
     """One level with its heads sharded over the ranks; returns the full (replicated) output."""
+    if return_attention:
+        raise ValueError("pygat_amd: return_attention does not take head_parallel=True; run the level on one device")
     rank, world = _world()
     H = len(Ws)
     Fo = Ws[0].shape[1]

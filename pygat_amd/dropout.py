@@ -78,7 +78,7 @@ class GATLevelDropoutFn(torch.autograd.Function):
     is, and the masks are drawn in-kernel (csrc/k7_dropout.hip)."""
 
     @staticmethod
-    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha, concat, p, mask_x, mask_wh, mask_att, seed, xs=None):
+    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha, concat, p, mask_x, mask_wh, mask_att, seed, xs=None, att=None):
         if not x.is_cuda:
             raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
         if graph.user_row is not None:    # (its K2 would write `out` through the map, its backward read G without it)
@@ -173,6 +173,9 @@ class GATLevelDropoutFn(torch.autograd.Function):
                                             a_pad.data_ptr(), _ptr(Sk), matt.data_ptr(),
                                             out.data_ptr() if (concat or H == 1) else None, _ptr(hattn), m.data_ptr(), Z.data_ptr(),
                                             _ptr(aneg), _ptr(qneg), part.data_ptr(), st), "gat_forward")
+            if att is not None:      # Wh carries its mask (attn_scores applied it in place); matt is not applied
+                with _span("k13_attention"):
+                    att.launch_v1(H, Fo, alpha, Wh, R, s, a_pad, m, Z, L.N, st)
             if not concat and H > 1:     # (the mean over one head is that head: K2 wrote `out` itself, see ops._level_forward)
                 check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
         ctx.save_for_backward(x if use_bits else Ae, bits if use_bits else Bp, a_pad, Wh, s, Sk, out if concat else hattn, m, Z,
@@ -244,11 +247,11 @@ class GATLevelDropoutFn(torch.autograd.Function):
                                                  GR.data_ptr() if L.skip else None, RW, wss.data_ptr(), dW.data_ptr(), _ptr(dWs), st),
                           "wgrad_sparse")
                 cast = lambda g_, k: g_ if g_ is None or g_.dtype == ctx.in_dtypes[k] else g_.to(ctx.in_dtypes[k])  # noqa: E731
-                return (None, cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None)
+                return (None, cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None, None)
             if ctx.use_bits:     # Ae is x and Bp the mask bytes on this path
                 dx, dW, dWs = _backward_bits(ctx, Ae, Bp, Wcat, dWh, GR, RW, st)
                 cast = lambda g_, k: g_ if g_ is None or g_.dtype == ctx.in_dtypes[k] else g_.to(ctx.in_dtypes[k])  # noqa: E731
-                return cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None
+                return cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None, None
             # dW_h = (x o m_h)^T dWh_h: the diagonal blocks of A'^T dWh
             dBp = torch.empty(HF, R, dtype=f32, device=dev)
             with _span("k5_wgrad"):
@@ -276,7 +279,7 @@ class GATLevelDropoutFn(torch.autograd.Function):
                                                  None if ctx.explicit else mx_or_seed.data_ptr(), STREAM_X,
                                                  dx.data_ptr(), Fin, 0, st), "dropout_head_sum")
         cast = lambda g_, k: g_ if g_ is None or g_.dtype == ctx.in_dtypes[k] else g_.to(ctx.in_dtypes[k])  # noqa: E731
-        return cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None
+        return cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None, None, None, None, None
 
 
 def _backward_bits(ctx, x, bits, Wcat, dWh, GR, RW, st):
@@ -323,12 +326,18 @@ def _backward_bits(ctx, x, bits, Wcat, dWh, GR, RW, st):
 
 def gat_level_dropout(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                       Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, p: float,
-                      head_mean: bool = False, masks: Optional[dict] = None, generator=None, xs=None) -> torch.Tensor:
+                      head_mean: bool = False, masks: Optional[dict] = None, generator=None, xs=None,
+                      return_attention: bool = False):
     """One level in training mode with dropout p.  `masks` (tests) = {"x","wh","att"} pre-scaled; without them the
-    masks are drawn in-kernel from one int64 seed taken from torch's (graph-safe) generator."""
+    masks are drawn in-kernel from one int64 seed taken from torch's (graph-safe) generator.
+    return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level: after the x and Wh masks, before the attention
+    mask (layers.py:132-153), so every row sums to 1."""
     del head_mean  # implied by `concat` (models.py:23): concat=False <=> last level <=> head mean
+    att = ops.AttentionTarget(graph, len(Ws), x.device) if return_attention else None
     W, a, Wskip = stack_heads(list(Ws), list(As), None if Wskips is None else list(Wskips))   # one launch, not a cat per kind
     if masks is not None:
-        return GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, masks["x"], masks["wh"], masks["att"], None, xs)
-    seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=x.device, generator=generator)
-    return GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, None, None, None, seed, xs)
+        out = GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, masks["x"], masks["wh"], masks["att"], None, xs, att)
+    else:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=x.device, generator=generator)
+        out = GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, None, None, None, seed, xs, att)
+    return (out, att.alpha) if return_attention else out

@@ -24,14 +24,14 @@ from .ops import _Level, _ptr, _span, _stream, gemm, gat_level, gemm_mode, get_g
 
 
 class GATv2LevelFn(torch.autograd.Function):
-    """forward(x, W[H,2Fin,F'], a[H,F'], Wskip[H,Fin,F']|None, graph, alpha, concat, masks|None).
+    """forward(x, W[H,2Fin,F'], a[H,F'], Wskip[H,Fin,F']|None, graph, alpha, concat, masks|None, att|None).
 
     masks (train-mode dropout, layers.py:266,271-272,293): dict of pre-scaled keep masks
     {"x": [H,N,Fin], "whi": [H,N,F'], "whj": [H,N,F'], "att": [E,H]}; each head draws its own input mask
     (models.py:32), so the projection then runs per head on the masked input."""
 
     @staticmethod
-    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha: float, concat: bool, masks=None):
+    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha: float, concat: bool, masks=None, att=None):
         if not x.is_cuda:
             raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
         x = x.contiguous().float(); W = W.contiguous().float(); a = a.contiguous().float()
@@ -55,7 +55,7 @@ class GATv2LevelFn(torch.autograd.Function):
                 and not graph.degree_sorted and L.N * 2 * L.R * 4 >= min(ops.RENUMBER_MIN_BYTES, ops.RENUMBER_MIN_BYTES_TAIL)
                 and not torch.cuda.is_current_stream_capturing()):
             from .features import permuted_rows
-            g_int, to_user, _ = graph.degree_ordered()
+            g_int, to_user, to_int = graph.degree_ordered()
             worth = L.N * 2 * L.R * 4 >= ops.RENUMBER_MIN_BYTES
             if not worth and ops.TAIL and graph.symmetric:
                 t = g_int.fwd.self_loop_tail(graph.slot_edges)
@@ -63,6 +63,8 @@ class GATv2LevelFn(torch.autograd.Function):
             xp = permuted_rows(x, to_user) if worth else None
             if xp is not None:
                 x, graph, user_row = xp, g_int, to_user
+                if att is not None:
+                    att.renumbered(to_int)
         L.ts = graph.slot_edges
         if ops.TAIL and masks is None and graph.degree_sorted and concat and graph.symmetric:
             t = graph.fwd.self_loop_tail(L.ts)
@@ -109,8 +111,9 @@ class GATv2LevelFn(torch.autograd.Function):
                 m = Z = None
             flags = (_lib.F_ELU if concat else 0) | (_lib.F_SKIP if skip else 0)
             hattn = torch.empty(L.N, R, dtype=f32, device=dev) if not concat else None
-            m = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
-            Z = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
+            # (the V2 forward's instantiation does not depend on m: asking for the attention changes no output bit)
+            m = torch.empty(L.N, H, dtype=f32, device=dev) if (need_grad or att is not None) else None
+            Z = torch.empty(L.N, H, dtype=f32, device=dev) if (need_grad or att is not None) else None
             out = torch.empty(L.N, H * Fo if concat else Fo, dtype=f32, device=dev)
             part = torch.empty(lib.pygat_partials_bytes(graph.nnz, L.ts, H, Fp) // 4, dtype=f32, device=dev)
             with _span("v2_forward"):
@@ -121,6 +124,9 @@ class GATv2LevelFn(torch.autograd.Function):
                 if tail is not None:
                     check(lib.pygat_gat_forward_tail(tail[0], L.N - tail[0], H, Fo, flags, WW.data_ptr(), 2 * R, _ptr(Sk), out.data_ptr(),
                                                      _ptr(user_row), _ptr(m), _ptr(Z), None, st), "gat_forward_tail")
+            if att is not None:      # (the tail's rows have one edge each: alpha = 1, their tables are not read)
+                with _span("k13_attention"):
+                    att.launch_v2(H, Fo, alpha, WW, a2, m, Z, st)
             if not concat:
                 check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
         if need_grad:
@@ -191,7 +197,7 @@ class GATv2LevelFn(torch.autograd.Function):
                 dW = torch.cat([dv[:, 0:H, :Fo].permute(1, 0, 2), dv[:, H:2 * H, :Fo].permute(1, 0, 2)], dim=1).contiguous()
                 if L.skip:
                     dWs = dSc.view(Fin, H, Fp)[:, :, :Fo].permute(1, 0, 2).contiguous()
-                return dx, dW, da_p, dWs, None, None, None, None
+                return dx, dW, da_p, dWs, None, None, None, None, None
             # dWcat[:, :2R] = x^T dWW ; skip columns = x^T Gp
             dWc = torch.empty(Fin, 2 * R, dtype=f32, device=dev)
             with _span("v2_wgrad"):
@@ -208,7 +214,7 @@ class GATv2LevelFn(torch.autograd.Function):
                 if L.skip:
                     gemm(False, True, L.N, Fin, R, Gp, LG, Wcat[:, 2 * R:], ncols, [(Fin, dx, Fin)], accumulate=True,
                          split_k=1)
-        return dx, dW, da_p, dWs, None, None, None, None
+        return dx, dW, da_p, dWs, None, None, None, None, None
 
 
 def draw_masks_v2(p: float, H: int, N: int, Fin: int, Fo: int, E: int, device, generator=None):
@@ -221,14 +227,18 @@ def draw_masks_v2(p: float, H: int, N: int, Fin: int, Fo: int, E: int, device, g
 
 def gatv2_level(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                 Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, dropout: float = 0.0,
-                masks: Optional[dict] = None) -> torch.Tensor:
+                masks: Optional[dict] = None, return_attention: bool = False):
     """All heads of one SpGraphAttentionLayerV2 level.  Ws: H tensors [2Fin,F']; As: H tensors of F' elements.
-    dropout > 0 (training): per-head masks are drawn here unless given (`masks`, tests)."""
+    dropout > 0 (training): per-head masks are drawn here unless given (`masks`, tests).
+    return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level (after the x / Whi / Whj masks, before the
+    attention mask)."""
+    att = ops.AttentionTarget(graph, len(Ws), x.device) if return_attention else None
     W, a, Wskip = stack_heads(list(Ws), list(As), None if Wskips is None else list(Wskips))   # one launch, not a cat per kind
     if masks is None and dropout > 0.0:
         H, Fin2, Fo = W.shape
         masks = draw_masks_v2(dropout, H, x.shape[0], Fin2 // 2, Fo, graph.nnz, x.device)
-    return GATv2LevelFn.apply(x, W, a, Wskip, graph, alpha, concat, masks)
+    out = GATv2LevelFn.apply(x, W, a, Wskip, graph, alpha, concat, masks, att)
+    return (out, att.alpha) if return_attention else out
 
 
 class _V2Base(nn.Module):
@@ -255,10 +265,11 @@ class SpGraphAttentionLayerV2(_V2Base):
             self.skip_projection = nn.Parameter(torch.empty(size=(in_features, out_features)))
             nn.init.xavier_uniform_(self.skip_projection.data, gain=1.414)
 
-    def forward(self, input, adj):
+    def forward(self, input, adj, return_attention=False):
+        """return_attention: -> (out, alpha [E, 1]) in the order of adj.nonzero() (CSRGraph.edge_index())."""
         return gatv2_level(input, as_graph(adj, self.pattern_mode), [self.W], [self.a],
                            [self.skip_projection] if self.skip_connection else None, self.alpha, self.concat,
-                           self.dropout if self.training else 0.0)
+                           self.dropout if self.training else 0.0, return_attention=return_attention)
 
 
 class GraphAttentionLayerV2(_V2Base):
@@ -276,9 +287,10 @@ class GraphAttentionLayerV2(_V2Base):
             self.skip_projection = nn.Parameter(torch.empty(size=(in_features, out_features)))
             nn.init.xavier_uniform_(self.skip_projection.data, gain=1.414)
 
-    def forward(self, h, adj, masks=None):
+    def forward(self, h, adj, masks=None, return_attention=False):
         """`masks` (tests only): explicit pre-scaled keep masks {"x" [1,N,Fin], "wh" [1,N,F'] (the Wh2 mask,
-        layers.py:212), "att" [E,1]} instead of in-kernel draws."""
+        layers.py:212), "att" [E,1]} instead of in-kernel draws.  return_attention: -> (out, alpha [E, 1]) in the order of
+        adj > 0 -- the uniform 1 / deg_i of the row-broadcast logits."""
         Fo = self.out_features
         zero_a = torch.zeros(2 * Fo, 1, dtype=self.W.dtype, device=self.W.device)   # uniform attention
         graph = as_graph(adj, self.pattern_mode)
@@ -289,8 +301,11 @@ class GraphAttentionLayerV2(_V2Base):
             # reaches the output: the layer is gat_level_dropout on W[Fin:] with a = 0.
             from .dropout import gat_level_dropout
             out = gat_level_dropout(h, graph, [self.W[self.in_features:]], [zero_a], skips, self.alpha, self.concat,
-                                    self.dropout, masks=masks)
+                                    self.dropout, masks=masks, return_attention=return_attention)
         else:
-            out = gat_level(h, graph, [self.W[self.in_features:]], [zero_a], skips, self.alpha, self.concat)
+            out = gat_level(h, graph, [self.W[self.in_features:]], [zero_a], skips, self.alpha, self.concat,
+                            return_attention=return_attention)
+        out, att = out if return_attention else (out, None)
         # the reference's autograd gives a and W[:Fin] exactly-zero gradients (not None): keep them in the graph
-        return out + 0.0 * (self.a.sum() + self.W[:self.in_features].sum())
+        out = out + 0.0 * (self.a.sum() + self.W[:self.in_features].sum())
+        return (out, att) if return_attention else out

@@ -250,6 +250,10 @@ class InternalOrderView:
         self.perm_t, self.perm_f = g_int.perm_t, g_int.perm_f
         self.to_user, self.to_internal = to_user, to_internal
 
+    def edge_index(self) -> torch.Tensor:
+        """int64 [2, E] (internal node ids), the edge order of the attention a level on this view returns."""
+        return self.base.edge_index()
+
 
 class CSRGraph:
     degree_sorted = False      # True for the patterns CSRGraph.degree_ordered builds
@@ -358,6 +362,11 @@ class CSRGraph:
             g.degree_sorted = True
             self._ordered = (g, urow, to_int.to(torch.int32).contiguous())
         return self._ordered
+
+    def edge_index(self) -> torch.Tensor:
+        """int64 [2, E]: row 0 = softmax row i, row 1 = gathered node j of every edge (layers.py:129), in CSR order -- the
+        order of the attention coefficients a level returns for this graph (return_attention)."""
+        return self.fwd.edge_rc.t().long()
 
     def internal_view(self) -> InternalOrderView:
         """The degree-ordered pattern for node arrays that are themselves in internal order (see InternalOrderView)."""

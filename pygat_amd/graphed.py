@@ -61,6 +61,12 @@ class _Replay(torch.autograd.Function):
         return (None,) + tuple(None if g is None else g.detach().clone() for g in lvl.grads)
 
 
+def _no_attention(return_attention: bool, what: str) -> None:
+    if return_attention:
+        raise ValueError(f"pygat_amd: {what} does not take return_attention (a captured graph replays fixed buffers); call the "
+                         "level or model eagerly with return_attention=True")
+
+
 class GraphedLevel:
     """One GAT level, forward + backward, as two HIP graphs (the op boundary of ops.GATLevelFn, replayed).
 
@@ -100,8 +106,9 @@ class GraphedLevel:
 
     # -- without autograd: the two replays as plain calls (bench.py, pipelines that own their buffers)
     @torch.no_grad()
-    def forward(self, x=None, W=None, a=None, Wskip=None) -> torch.Tensor:
+    def forward(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False) -> torch.Tensor:
         """Replay the forward; returns the static output buffer.  None = keep the static input as it is."""
+        _no_attention(return_attention, "GraphedLevel")
         for dst, src in zip(self.inputs, [x, W, a] + ([Wskip] if self.Wskip is not None else [])):
             if src is not None and dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
@@ -117,7 +124,8 @@ class GraphedLevel:
         self.g_bwd.replay()
         return self.grads
 
-    def __call__(self, x=None, W=None, a=None, Wskip=None) -> torch.Tensor:
+    def __call__(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False) -> torch.Tensor:
+        _no_attention(return_attention, "GraphedLevel")
         args = [x, W, a] + ([Wskip] if self.Wskip is not None else [])
         # tensors that require grad must be passed for autograd to route gradients to them; None = the static buffer
         args = [s if t is None else t for t, s in zip(args, self.inputs)]
@@ -197,9 +205,10 @@ class FusedEpoch:
         self.epochs += 1
         return loss, val
 
-    def run(self):
+    def run(self, return_attention: bool = False):
         """One epoch = one graph replay.  Returns (train loss, eval value) as views of static device tensors:
         read them (`.item()`, `.clone()`) before the next call if they are to be kept."""
+        _no_attention(return_attention, "FusedEpoch")
         if self.g is None:
             return self._eager_epoch()
         if self.x._version != self._x_version:

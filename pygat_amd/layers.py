@@ -40,13 +40,16 @@ class _FusedGATLayer(nn.Module):
             init(p.data, gain=_GAIN)
             setattr(self, name, p)
 
-    def forward(self, h, adj):
+    def forward(self, h, adj, return_attention=False):
+        """return_attention: -> (out, alpha [E, 1]), the attention coefficient of every edge of the layer's pattern in
+        row-major order (adj.nonzero() / adj > 0: CSRGraph.edge_index()), detached."""
         graph = as_graph(adj, self.pattern_mode)
         skips = [self.skip_projection] if self.skip_connection else None
         if self.training and self.dropout > 0.0:
             from .dropout import gat_level_dropout
-            return gat_level_dropout(h, graph, [self.W], [self.a], skips, self.alpha, self.concat, self.dropout)
-        return gat_level(h, graph, [self.W], [self.a], skips, self.alpha, self.concat)
+            return gat_level_dropout(h, graph, [self.W], [self.a], skips, self.alpha, self.concat, self.dropout,
+                                     return_attention=return_attention)
+        return gat_level(h, graph, [self.W], [self.a], skips, self.alpha, self.concat, return_attention=return_attention)
 
     def __repr__(self):
         return f"{type(self).__name__} ({self.in_features} -> {self.out_features})"

@@ -355,7 +355,7 @@ class GATLevelFn(torch.autograd.Function):
     all-gather on its own stream, pygat_amd/dist.py) while the next chunk is computed.  concat levels only."""
 
     @staticmethod
-    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha: float, concat: bool, bwd_heads=None, pipeline=None):
+    def forward(ctx, x, W, a, Wskip, graph: CSRGraph, alpha: float, concat: bool, bwd_heads=None, pipeline=None, att=None):
         if not x.is_cuda:
             raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
         # the path computes in float32 (like the reference's sparse layer, layers.py:150); other float dtypes are cast
@@ -373,13 +373,14 @@ class GATLevelFn(torch.autograd.Function):
         def pack(Wcat, ldw, a_pad, st):
             check(lib.pygat_pack_params(H, Fin, Fo, W.data_ptr(), a.data_ptr(), _ptr(Wskip), Wcat.data_ptr(), ldw,
                                         a_pad.data_ptr(), st), "pack_params")
-        return _level_forward(ctx, tuple(ctx.needs_input_grad[:4]), x, H, Fo, skip, pack, graph, alpha, concat, bwd_heads, pipeline)
+        return _level_forward(ctx, tuple(ctx.needs_input_grad[:4]), x, H, Fo, skip, pack, graph, alpha, concat, bwd_heads, pipeline,
+                              att=att)
 
     @staticmethod
     def backward(ctx, G):
         dx, dW, da, dWs = _level_backward(ctx, G)
         cast = lambda g_, k: g_ if g_ is None or g_.dtype == ctx.in_dtypes[k] else g_.to(ctx.in_dtypes[k])  # noqa: E731
-        return (cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None)
+        return (cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None)
 
 
 PAD_K = _config.pad_k     # development knob: 0 = run odd input widths as they are
@@ -391,10 +392,10 @@ class GATLevelHeadsFn(torch.autograd.Function):
     skip_projection [Fin,F'] tensor PER HEAD (layers.py:21-28,111-119; models.py:15-27) -- instead of stacked: the packing
     kernel reads them through a pointer table (pygat_pack_params_heads), so no torch.stack (a cat launch per parameter
     kind, level and forward: a tenth of a small graph's epoch) precedes the level.
-    forward(x, graph, alpha, concat, pipeline, H, skip, *Ws, *As[, *Wskips]) -> out."""
+    forward(x, graph, alpha, concat, pipeline, H, skip, xs, att, *Ws, *As[, *Wskips]) -> out (att: see AttentionTarget)."""
 
     @staticmethod
-    def forward(ctx, x, graph: CSRGraph, alpha: float, concat: bool, pipeline, H: int, skip: bool, xs, *params):
+    def forward(ctx, x, graph: CSRGraph, alpha: float, concat: bool, pipeline, H: int, skip: bool, xs, att, *params):
         if not x.is_cuda:
             raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
         Ws, As = params[:H], params[H:2 * H]
@@ -414,9 +415,9 @@ class GATLevelHeadsFn(torch.autograd.Function):
         def pack(Wcat, ldw, a_pad, st):
             check(lib.pygat_pack_params_heads(H, Fin, Fo, wp, ap, sp, Wcat.data_ptr(), ldw, a_pad.data_ptr(), st), "pack_params_heads")
         n = ctx.needs_input_grad
-        need = (n[0], any(n[8:8 + H]), any(n[8 + H:8 + 2 * H]), skip and any(n[8 + 2 * H:8 + 3 * H]))
+        need = (n[0], any(n[9:9 + H]), any(n[9 + H:9 + 2 * H]), skip and any(n[9 + 2 * H:9 + 3 * H]))
         ctx.H, ctx.skip = H, skip
-        return _level_forward(ctx, need, x, H, Fo, skip, pack, graph, alpha, concat, None, pipeline, xs=xs)
+        return _level_forward(ctx, need, x, H, Fo, skip, pack, graph, alpha, concat, None, pipeline, xs=xs, att=att)
 
     @staticmethod
     def backward(ctx, G):
@@ -433,13 +434,17 @@ class GATLevelHeadsFn(torch.autograd.Function):
             for k in range(H):
                 outs.append(None if dWs is None else dWs[k])
         outs = [g_ if g_ is None or g_.dtype == dt else g_.to(dt) for g_, dt in zip(outs, ctx.param_dtypes)]
-        return (dx, None, None, None, None, None, None, None) + tuple(outs)
+        return (dx, None, None, None, None, None, None, None, None) + tuple(outs)
 
 
-def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: float, concat: bool, bwd_heads, pipeline, xs=None):
+def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: float, concat: bool, bwd_heads, pipeline, xs=None,
+                   att=None):
     """Body of the level's forward, shared by GATLevelFn (stacked parameters) and GATLevelHeadsFn (one tensor per head).
     need = (x, W, a, Wskip) gradient flags; pack(Wcat, ldw, a_pad, stream) launches the parameter packing; xs: the
-    SparseFeatures of x (features.py) -- projection and weight gradient on the non-zeros only -- or None."""
+    SparseFeatures of x (features.py) -- projection and weight gradient on the non-zeros only -- or None.  att: an
+    AttentionTarget the forward fills with the level's attention coefficients, or None."""
+    if att is not None and pipeline is not None:
+        raise ValueError("pygat_amd: return_attention does not take a pipeline")
     if x.dim() == 3 and not blocked_input_ok(x):
         raise ValueError(f"column-blocked input {tuple(x.shape)}: blocks must be a power of two >= 16 floats wide (float32, GPU)")
     L = _Level(x, H, Fo, skip)
@@ -460,7 +465,7 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
             and graph.user_row is None and not graph.degree_sorted and L.N * L.R * 4 >= min(RENUMBER_MIN_BYTES, RENUMBER_MIN_BYTES_TAIL)
             and not torch.cuda.is_current_stream_capturing()):     # (a captured graph would bake this epoch's permuted copy of x in)
         from .features import permuted_rows
-        g_int, to_user, _ = graph.degree_ordered()
+        g_int, to_user, to_int = graph.degree_ordered()
         worth = L.N * L.R * 4 >= RENUMBER_MIN_BYTES
         if not worth and TAIL and concat and graph.symmetric:     # a narrower table: only with a self-loop-only tail to stream
             t = g_int.fwd.self_loop_tail(slot_edges_for(L.R, g_int.slot_edges))
@@ -468,6 +473,8 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         xp = permuted_rows(x, to_user) if worth else None
         if xp is not None:
             x, graph, user_row = xp, g_int, to_user
+            if att is not None:
+                att.renumbered(to_int)
     L.ts = slot_edges_for(L.R, graph.slot_edges)
     L.mode = get_gemm_mode()     # this thread's product mode, fixed for the level: its backward (another thread) uses it too
     dev, f32 = x.device, torch.float32
@@ -534,8 +541,9 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         # adds the skip rows, no ELU), no head-mean launch; hattn is then only kept for the backward
         single = (not concat) and H == 1
         hattn = torch.empty(L.N, L.R, dtype=f32, device=dev) if (not concat and (need_grad or not single)) else None
-        m = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
-        Z = torch.empty(L.N, H, dtype=f32, device=dev) if need_grad else None
+        # (K2 picks its instantiation by aneg, not by m: asking for the attention changes no output bit)
+        m = torch.empty(L.N, H, dtype=f32, device=dev) if (need_grad or att is not None) else None
+        Z = torch.empty(L.N, H, dtype=f32, device=dev) if (need_grad or att is not None) else None
         aneg = torch.empty(L.N, L.R, dtype=f32, device=dev) if flavour == "rowlocal" else None
         qneg = torch.empty(L.N, H, dtype=f32, device=dev) if flavour == "rowlocal" else None
         part = torch.empty(lib.pygat_partials_bytes(graph.nnz, L.ts, H, L.Fp) // 4, dtype=f32,
@@ -583,6 +591,9 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
                     check(lib.pygat_gat_forward_tail(tail[0], L.N - tail[0], H, Fo, flags, Wh.data_ptr(), 0, _ptr(Sk), out.data_ptr(),
                                                      _ptr(user_row), _ptr(m), _ptr(Z), _ptr(qneg), st), "gat_forward_tail")
                 pipeline[1](len(chunks), tail[0], L.N, out)
+        if att is not None:      # (the tail's rows have one edge each: alpha = 1, their t, Wh, m, Z rows are not read)
+            with _span("k13_attention"):
+                att.launch_v1(H, Fo, alpha, Wh, L.R, s, a_pad, m, Z, L.N if tail is None else tail[0], st)
         if not concat and not single:
             check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
     if need_grad:
@@ -747,6 +758,38 @@ def _level_backward(ctx, G):
     return dx, dW, (da if ctx.need[2] else None), dWs
 
 
+class AttentionTarget:
+    """Where a level writes its attention coefficients (return_attention): alpha [E, H] float32, not differentiable, row k =
+    edge k of the CALLER's pattern (graph.fwd: rowptr, edge_rc).  The level's tables may be in another node order: `to_internal`
+    (caller node -> table row) is set when the level renumbers by itself (ops._level_forward, GATv2LevelFn), or given as
+    order = (caller graph, to_internal) by a caller that hands the level an InternalOrderView of its graph (GAT.forward)."""
+
+    def __init__(self, graph, H: int, device, order=None):
+        g, self.to_internal = (graph, None) if order is None else order
+        self.pattern = g.fwd
+        self.alpha = torch.empty(g.nnz, H, dtype=torch.float32, device=device)
+        if self.pattern.n != graph.n or g.nnz != graph.nnz:
+            raise ValueError(f"pygat_amd: attention_order: a graph of {self.pattern.n} nodes / {g.nnz} edges for a level on "
+                             f"{graph.n} / {graph.nnz}")
+
+    def renumbered(self, to_internal: torch.Tensor) -> None:
+        self.to_internal = to_internal
+
+    def _pattern_args(self):
+        p = self.pattern
+        return (p.n, p.nnz, p.rowptr.data_ptr(), p.edge_rc.data_ptr(), _ptr(self.to_internal))
+
+    def launch_v1(self, H, Fo, slope, Wh, ldwh, s, a_pad, m, Z, t_rows, st):
+        t = torch.empty(self.pattern.n, H, dtype=torch.float32, device=Wh.device)      # t_q = Wh_q . a_dst, rows < t_rows
+        check(lib.pygat_gat_attention(*self._pattern_args(), H, Fo, float(slope), Wh.data_ptr(), ldwh, s.data_ptr(),
+                                      a_pad.data_ptr(), m.data_ptr(), Z.data_ptr(), int(t_rows), t.data_ptr(),
+                                      self.alpha.data_ptr(), st), "gat_attention")
+
+    def launch_v2(self, H, Fo, slope, WW, a2, m, Z, st):
+        check(lib.pygat_gatv2_attention(*self._pattern_args(), H, Fo, float(slope), WW.data_ptr(), a2.data_ptr(), m.data_ptr(),
+                                        Z.data_ptr(), self.alpha.data_ptr(), st), "gatv2_attention")
+
+
 class StackHeads(torch.autograd.Function):
     """(W [H,Fin,F'], a [H,2F'], Wskip [H,Fin,F'] | None) from the per-head parameter tensors in ONE launch (torch.stack: a
     cat launch per parameter kind); backward: views of the stacked gradients.  forward(H, skip, rows, *Ws, *As[, *Wskips]);
@@ -797,11 +840,23 @@ def stack_heads(Ws, As, Wskips):
 
 
 def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
-              Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, pipeline=None, xs=None) -> torch.Tensor:
+              Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, pipeline=None, xs=None,
+              return_attention: bool = False, attention_order=None):
     """All heads of one level. Ws: H tensors [Fin,F']; As: H tensors with 2F' elements
     ([2F',1] as in GraphAttentionLayer, layers.py:23, or [1,2F'] as in SpGraphAttentionLayer,
     layers.py:114); Wskips: H tensors [Fin,F'] or None.  pipeline: see GATLevelFn.  xs: features.SparseFeatures of x
-    (a first level on sparse input features) or None."""
+    (a first level on sparse input features) or None.
+    return_attention: -> (out, alpha), alpha [E, H] float32 (detached) = the softmax coefficient of every edge and head, in
+    the edge order of `graph` (graph.edge_index()); attention_order: see AttentionTarget."""
+    H = len(Ws)
+    if return_attention and pipeline is not None:
+        raise ValueError("pygat_amd: return_attention does not take a pipeline")
+    att = AttentionTarget(graph, H, x.device, attention_order) if return_attention else None
+    out = _gat_level(x, graph, Ws, As, Wskips, alpha, concat, pipeline, xs, att)
+    return (out, att.alpha) if return_attention else out
+
+
+def _gat_level(x, graph, Ws, As, Wskips, alpha, concat, pipeline, xs, att):
     H = len(Ws)
     Fin = x.shape[1]
     if (xs is None and PAD_K and Fin % 16 and 16 < Fin <= 1024 and x.is_cuda and not x.requires_grad and x.dim() == 2
@@ -812,11 +867,11 @@ def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: 
         from .features import padded_columns
         xp = padded_columns(x, 16)
         W, a, Wskip = StackHeads.apply(H, Wskips is not None, xp.shape[1], *Ws, *As, *(Wskips if Wskips is not None else ()))
-        return GATLevelFn.apply(xp, W, a, Wskip, graph, alpha, concat, None, pipeline)
+        return GATLevelFn.apply(xp, W, a, Wskip, graph, alpha, concat, None, pipeline, att)
     if H <= MAX_HEAD_TABLE:        # parameters read in place through a pointer table: no torch.stack launches
-        return GATLevelHeadsFn.apply(x, graph, alpha, concat, pipeline, H, Wskips is not None, xs, *Ws, *As,
+        return GATLevelHeadsFn.apply(x, graph, alpha, concat, pipeline, H, Wskips is not None, xs, att, *Ws, *As,
                                      *(Wskips if Wskips is not None else ()))
     W = torch.stack(list(Ws), 0)
     a = torch.stack([p.reshape(-1) for p in As], 0)
     Wskip = torch.stack(list(Wskips), 0) if Wskips is not None else None
-    return GATLevelFn.apply(x, W, a, Wskip, graph, alpha, concat, None, pipeline)
+    return GATLevelFn.apply(x, W, a, Wskip, graph, alpha, concat, None, pipeline, att)
