@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: one GAT level forward+backward on a synthetic R-MAT graph.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, K timed steps, --dump-outputs, the
+result line.  --full adds every other leg (listed below), each measured after the timed steps or in a process of its own.
 
 Workload (BASELINE.json config 5 / SURVEY.md 8(d)): R-MAT scale 20 (N = 1,048,576 nodes),
 5,000,000 edge draws with (a,b,c,d) = (0.57,0.19,0.19,0.05), seed 1, symmetrised, de-duplicated,
@@ -23,12 +26,15 @@ is fixed -> "scaling": "strong".
 (--forward-exchange replicate is a labelled experiment: no collective, every rank recomputes all
 heads' forward.)
 
-One JSON line on rank 0: value = E / step time (max over ranks, K steps between barriers), plus
+One JSON line on rank 0: value = E / step time (max over ranks, K steps between barriers), ms_per_step, the configuration; with
+--full also
   roofline      the kernel with the largest share of the step (HIP events around every launch in an
                 instrumented pass of the same steps right after the timed region, so that the timed
                 steps carry no event records; SURVEY.md 8(d) algorithmic bytes / flops);
   kernels       the same figures for every kernel of the step;
   cpu_baseline  oracle/gat_oracle.c (CPU port of the same level) on this host's cores, N=1 only;
+  alt, alt_node_order   the same K steps with the streamed GEMMs on the fp32 MFMA pipe / in the caller's node order, N=1 only;
+  gatv2         one SpGraphAttentionLayerV2 level on the same graph and input, N=1 only;
   epoch_ms      Cora / Pubmed / PPI-shaped epochs (train.py:151-179, train_ppi.py) replayed from one HIP graph, N=1 only.
 
 --dump-outputs DIR writes what the last timed step computed -- the level output and the gradients -- as DIR/<name>.npy (float32,
@@ -62,6 +68,10 @@ def parse():
     ap.add_argument("--fout", type=int, default=16)
     ap.add_argument("--dx", action="store_true", help="also back-propagate into the input features")
     ap.add_argument("--hip-graph", action="store_true", help="replay the level from captured HIP graphs (pygat_amd.GraphedLevel)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, measure everything else the line can carry: cpu_baseline, alt / alt_node_order, "
+                         "the instrumented pass behind roofline / kernels, gatv2, epoch_ms (the --no-* options below take legs out "
+                         "of a --full run; a run without --full has none of them)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-dense-cpu", action="store_true", help="skip the dense-formulation CPU figure inside the cpu_baseline leg (~15 s)")
     ap.add_argument("--no-epoch", action="store_true", help="skip the Cora / Pubmed epoch_ms leg")
@@ -348,7 +358,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_record = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         try:        # the cpu_baseline leg: library rebuilt for this host (-march=native) and the whole leg run in a child
                     # process NOW, before this process touches the GPU (round 3 ran it in-process, after the GPU legs, on
                     # every hardware thread beside torch's own OpenMP pool: 2.37 s/step one round, 4.63 the next)
@@ -550,7 +560,7 @@ def main():
     # ---- the same K steps with the two streamed GEMMs on the fp32 MFMA pipe (the gemm_mode argument of the C ABI): reported beside
     # the headline so that the effect of the split-bf16 products is on record in every run.  Single GPU, stream launches.
     alt = None
-    if world == 1 and pg.get_gemm_mode() == "split-bf16" and not (args.hip_graph and not replicate) and not args.no_alt:
+    if args.full and world == 1 and pg.get_gemm_mode() == "split-bf16" and not (args.hip_graph and not replicate) and not args.no_alt:
         try:
             pg.set_gemm_mode("fp32-mfma")
             for _ in range(max(2, args.warmup)):
@@ -571,7 +581,7 @@ def main():
     # tables in an internal degree order (x permuted once per feature tensor, outputs / gradients at the caller's rows through a
     # map inside the kernels: pygat_amd/ops.py); the line reports what that layout choice is worth.
     alt_order = None
-    if world == 1 and not (args.hip_graph and not replicate) and ops.RENUMBER and not args.no_alt:
+    if args.full and world == 1 and not (args.hip_graph and not replicate) and ops.RENUMBER and not args.no_alt:
         try:
             ops.RENUMBER = False
             for _ in range(max(2, args.warmup)):
@@ -589,30 +599,32 @@ def main():
         barrier()
 
     # ---- instrumented pass: the same steps launched eagerly with HIP events around every kernel ------
-    timer = ops.KernelTimer()
-    if replicate:
-        inst_fwd, inst_bwd = level_fwd, level_bwd
-    else:
-        W_i = W[hs:he].contiguous().requires_grad_(True)
-        a_i = a[hs:he].contiguous().requires_grad_(True)
-        X_i = X.clone().requires_grad_(True) if args.dx else X
+    timer = None
+    if args.full:
+        timer = ops.KernelTimer()
+        if replicate:
+            inst_fwd, inst_bwd = level_fwd, level_bwd
+        else:
+            W_i = W[hs:he].contiguous().requires_grad_(True)
+            a_i = a[hs:he].contiguous().requires_grad_(True)
+            X_i = X.clone().requires_grad_(True) if args.dx else X
 
-        def inst_fwd():
-            W_i.grad = a_i.grad = None
-            if args.dx:
-                X_i.grad = None
-            return pg.GATLevelFn.apply(X_i, W_i, a_i, None, graph, 0.2, True)
+            def inst_fwd():
+                W_i.grad = a_i.grad = None
+                if args.dx:
+                    X_i.grad = None
+                return pg.GATLevelFn.apply(X_i, W_i, a_i, None, graph, 0.2, True)
 
-        def inst_bwd(out):
-            out.backward(G_loc)
-    for _ in range(2):
-        inst_bwd(inst_fwd())
-    torch.cuda.synchronize()
-    ops.TIMER = timer
-    for _ in range(min(args.steps, 20)):
-        inst_bwd(inst_fwd())
-    torch.cuda.synchronize()
-    ops.TIMER = None
+            def inst_bwd(out):
+                out.backward(G_loc)
+        for _ in range(2):
+            inst_bwd(inst_fwd())
+        torch.cuda.synchronize()
+        ops.TIMER = timer
+        for _ in range(min(args.steps, 20)):
+            inst_bwd(inst_fwd())
+        torch.cuda.synchronize()
+        ops.TIMER = None
 
     if args.verify:
         full = step()
@@ -630,10 +642,7 @@ def main():
                 assert err < 1e-5, err
 
     if rank == 0:
-        kt = {k: float(np.mean(v)) for k, v in timer.times_ms().items()}
         Fp = pg.padded_width(Fo)
-        Rf, Hf = k2_heads * Fp, k2_heads            # forward kernels
-        Rb, Hb = h_loc * Fp, h_loc                  # backward kernels
         # rows K3a prepares: all of them, or -- internal degree order with the self-loop-only tail streamed by itself and no skip
         # projection (pygat_amd/ops.py TAIL; csrc/k12_tail.hip) -- the rows before the tail: the tail's Gp never goes through GR
         n_k3a, tail_rows = N, 0
@@ -644,6 +653,39 @@ def main():
             t = graph.degree_ordered()[0].fwd.self_loop_tail(slot_edges_for(h_loc * Fp, graph.slot_edges))
             if t is not None and N - t[0] >= ops.TAIL_MIN_SHARE * N:
                 n_k3a, tail_rows, renumbered = t[0], N - t[0], True
+        line = {
+            "metric": "GAT-layer fwd+bwd edges/sec", "value": E / (ms * 1e-3), "unit": "edges/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+            "ms_per_step_median": ms_median,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"RMAT scale {args.scale} ({N} nodes, {E} edges incl. self loops, max degree "
+                                   f"{int((rowptr[1:] - rowptr[:-1]).max())}), Fin {Fin}, {H} heads x {Fo}, concat+ELU, "
+                                   f"dropout 0, fwd+bwd (dW, da{', dX' if args.dx else ''})",
+                       "nodes": N, "edges": E, "fin": Fin, "heads": H, "f_out": Fo,
+                       "parallelism": (f"head-parallel x{model_world}, "
+                                       + ("forward replicated (no collective; experiment)" if replicate
+                                          else "copy-free exchange of the head outputs (grouped RCCL send/recv per row chunk into the "
+                                               "column-blocked activation) overlapped with the forward's later chunks and the backward")
+                                       + (" (rank-0 work only, modelled)" if model_world != world else ""))
+                       if model_world > 1 else "single GPU",
+                       "heads_per_gpu": h_loc,
+                       "gemm_products": pg.get_gemm_mode(),
+                       "node_order": ("internal degree order (x permuted once per feature tensor and cached; out / G / saved output "
+                                      "addressed at the caller's rows inside K2 / K3a; no permutation pass in the step)"
+                                      + (f"; the {tail_rows} self-loop-only nodes (alpha_ii = 1 exactly) as a contiguous tail through two "
+                                         f"plain streams inside the k2_forward / k4_backward_col spans, K3a on the {n_k3a} rows before them"
+                                         if tail_rows else "")
+                                      if renumbered else "caller's"),
+                       "launch": "HIP-graph replay (pygat_amd.GraphedLevel)" if (args.hip_graph and not replicate)
+                       else "stream launches (pygat_amd.GATLevelFn)"}}
+        if dump_record is not None:
+            line["dump_outputs"] = dump_record
+    # ---- --full: the figures of the instrumented pass, the records of the legs above, and the legs that time another layer / model
+    if rank == 0 and args.full:
+        kt ={k: float(np.mean(v)) for k, v in timer.times_ms().items()}
+        Rf, Hf = k2_heads * Fp, k2_heads            # forward kernels
+        Rb, Hb = h_loc * Fp, h_loc                  # backward kernels
         # SURVEY.md 8(d) byte / flop models
         model = {
             "k1_project": ("mfma", 2.0 * N * Fin * (Rf + 2 * Hf)),
@@ -718,41 +760,14 @@ def main():
         roof = dict(dominant)
         roof["timing"] = "HIP events around each launch, instrumented eager pass of the same steps after the timed region"
         roof["traffic_source"] = traffic_source
-        line = {
-            "metric": "GAT-layer fwd+bwd edges/sec", "value": E / (ms * 1e-3), "unit": "edges/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-            "ms_per_step_median": ms_median,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"RMAT scale {args.scale} ({N} nodes, {E} edges incl. self loops, max degree "
-                                   f"{int((rowptr[1:] - rowptr[:-1]).max())}), Fin {Fin}, {H} heads x {Fo}, concat+ELU, "
-                                   f"dropout 0, fwd+bwd (dW, da{', dX' if args.dx else ''})",
-                       "nodes": N, "edges": E, "fin": Fin, "heads": H, "f_out": Fo,
-                       "parallelism": (f"head-parallel x{model_world}, "
-                                       + ("forward replicated (no collective; experiment)" if replicate
-                                          else "copy-free exchange of the head outputs (grouped RCCL send/recv per row chunk into the "
-                                               "column-blocked activation) overlapped with the forward's later chunks and the backward")
-                                       + (" (rank-0 work only, modelled)" if model_world != world else ""))
-                       if model_world > 1 else "single GPU",
-                       "heads_per_gpu": h_loc,
-                       "gemm_products": pg.get_gemm_mode(),
-                       "node_order": ("internal degree order (x permuted once per feature tensor and cached; out / G / saved output "
-                                      "addressed at the caller's rows inside K2 / K3a; no permutation pass in the step)"
-                                      + (f"; the {tail_rows} self-loop-only nodes (alpha_ii = 1 exactly) as a contiguous tail through two "
-                                         f"plain streams inside the k2_forward / k4_backward_col spans, K3a on the {n_k3a} rows before them"
-                                         if tail_rows else "")
-                                      if renumbered else "caller's"),
-                       "launch": "HIP-graph replay (pygat_amd.GraphedLevel)" if (args.hip_graph and not replicate)
-                       else "stream launches (pygat_amd.GATLevelFn)"},
+        line.update({
             "roofline": roof,
             "kernels": kernels,
             "kernels_ms_sum": float(sum(kt.values())),
             "traffic_source": traffic_source,
             "alt": alt,
             "alt_node_order": alt_order,
-        }
-        if dump_record is not None:
-            line["dump_outputs"] = dump_record
+        })
         if cpu_record is not None:
             line["cpu_baseline"] = cpu_record
         if world == 1 and model_world == 1 and not args.no_v2 and not args.dx:
@@ -767,6 +782,7 @@ def main():
                     line["epoch_ms"][name] = epoch_ms(pg, dev, name, epochs=100 if name == "ppi" else 200)
                 except Exception as ex:
                     line["epoch_ms"][name] = {"ms": None, "error": repr(ex)}
+    if rank == 0:
         print(json.dumps(line), file=real_stdout, flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py with module-level switches of pygat_amd.ops set first (A/B of Python-side experiments on one box):
-    python3 tools/run_bench_with.py TAIL_OVERLAP=True RENUMBER_MIN_BYTES=0 -- --no-cpu --no-epoch --no-v2"""
+    python3 tools/run_bench_with.py TAIL_OVERLAP=True RENUMBER_MIN_BYTES=0 -- --full --no-cpu --no-epoch --no-v2"""
 import ast
 import os
 import runpy
