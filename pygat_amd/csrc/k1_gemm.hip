@@ -668,7 +668,7 @@ extern "C" int pygat_gemm_f32_blocked(int transA, int transB, int M, int N, int6
       return PYGAT_OK;
     }
   }
-  if (split) {   // any layout on the bf16 pipe from exactly split operands (gemm_x3g_kernel); odd shapes fall through
+  if (split) {   // any layout on the bf16 pipe from exactly split operands (gemm_x3gw_kernel); odd shapes fall through
     const int64_t kps16 = cdiv(cdiv(K, split_k), 16) * 16;
     int sp = (int)cdiv(K, kps16);
     const int r = try_gemm_x3g(transA, transB, M, N, K, A, lda, B, ldb, out, accumulate, sp, kps16, (float*)ws, st, ab, cb, &sp);

@@ -64,37 +64,22 @@ __device__ __forceinline__ void pair_of(const float4& a, const float4& b, int j,
 }
 // PYGAT_DIAG_K1 (tools/build_variant.sh only; never set in the shipped library): bit 0 no output stores, bit 1 no s
 // reduction, bit 2 A rows folded onto 256 rows (cache-resident reads), bit 3 one piece product instead of nine --
-// decomposes the projection kernel's time into its store / reduction / HBM-read / MFMA shares.
+// decomposes the projection kernel's time into its store / reduction / HBM-read / MFMA shares.  All four act in
+// gemm_smallk_x3_kernel only (bit 2 in its pipelined loop's tile_ptr, bit 3 in mma9t); the weight-gradient and general
+// kernels below carry no diagnostic bit.
 #ifndef PYGAT_DIAG_K1
 #define PYGAT_DIAG_K1 0
 #endif
 #ifndef PYGAT_K1_LDS_ROWS
 #define PYGAT_K1_LDS_ROWS 1   // the projection's epilogue stores whole lines through LDS patches (0: 16-byte stores of 32 rows each)
 #endif
-// all nine piece products of one 32 x 32 x 16 block, small terms first
-template <class TB_>
-__device__ __forceinline__ f32x16 mma9(const Frag3& a, const TB_& bh, const TB_& bm, const TB_& bl, f32x16 c) {
-#if (PYGAT_DIAG_K1 & 8)
-  return mfma_bf16(a.h, bh, c);
-#endif
-  c = mfma_bf16(a.l, bl, c);
-  c = mfma_bf16(a.l, bm, c);
-  c = mfma_bf16(a.m, bl, c);
-  c = mfma_bf16(a.l, bh, c);
-  c = mfma_bf16(a.h, bl, c);
-  c = mfma_bf16(a.m, bm, c);
-  c = mfma_bf16(a.m, bh, c);
-  c = mfma_bf16(a.h, bm, c);
-  c = mfma_bf16(a.h, bh, c);
-  return c;
-}
-
-// The same nine products with the operand ROLES swapped: the weight fragment is the MFMA's A operand, the streamed row
-// fragment its B operand (both are "lane (i, h) holds k = 8 h .. + 7 of row / column i": nothing is loaded differently), so
-// the 32 x 32 tile comes out TRANSPOSED -- register q of lane (r, h) is C[row r][column (q & 3) + 8 (q >> 2) + 4 h]: a lane
-// holds 16 columns of ONE row, four at a time consecutive.  What that buys the epilogue of gemm_smallk_x3_kernel (round 4):
-// 16-byte stores (16 per 32 x 128 tile and wave instead of 64 dword stores), and the per-head sums s = Wh . a_src as eight
-// in-lane FMAs + one half-wave swap per head instead of a four-step DPP reduction per accumulator register.
+// All nine piece products of one 32 x 32 x 16 block, small terms first, with the operand ROLES swapped: the weight fragment
+// is the MFMA's A operand, the streamed row fragment its B operand (both are "lane (i, h) holds k = 8 h .. + 7 of row / column
+// i": nothing is loaded differently), so the 32 x 32 tile comes out TRANSPOSED -- register q of lane (r, h) is C[row r][column
+// (q & 3) + 8 (q >> 2) + 4 h]: a lane holds 16 columns of ONE row, four at a time consecutive.  What that buys the epilogue of
+// gemm_smallk_x3_kernel (round 4): 16-byte stores (16 per 32 x 128 tile and wave instead of 64 dword stores), and the per-head
+// sums s = Wh . a_src as eight in-lane FMAs + one half-wave swap per head instead of a four-step DPP reduction per
+// accumulator register.
 template <class TB_>
 __device__ __forceinline__ f32x16 mma9t(const Frag3& x, const TB_& wh, const TB_& wm, const TB_& wl, f32x16 c) {
 #if (PYGAT_DIAG_K1 & 8)
@@ -774,181 +759,36 @@ int try_project_x3_tail(int n, int Fin, int H, int Fp, const float* X, int64_t l
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// C[M x N] = A^T B with A [K x M], B [K x N], K huge (one row per node): dW = X^T dWh.  Both operands are k-strided,
-// the bf16 MFMA wants 8 consecutive k per lane: the work-group (4 waves, a 128 x 128 tile of C over one K slab) moves
-// 16 k rows of both operands per step through LDS --
-//   * thread (kp = tid & 7, c4 = tid >> 3) loads rows k0 + 2 kp, k0 + 2 kp + 1, columns 4 c4 .. + 3 of A and of B with
-//     16-byte loads (a wave covers 128 contiguous bytes of 16 rows), three steps ahead, into a register ring;
-//   * it splits the (k even, k odd) pair of every column ONCE for the whole work-group (the register-only version
-//     split every element in two waves and was bound by those VALU instructions) and writes the three packed pieces
-//     to images [column][16 k] with 40-byte rows: the dword writes of a half-wave (8 k pairs x 4 column groups) and
-//     the 8-byte fragment reads of a half-wave (32 columns) both touch every bank once.  (48-byte rows read with
-//     ds_read_b128 put two column groups of every write on the same banks: a third of the LDS cycles were conflicts);
-//   * a wave owns a 64 x 64 block of C: 4 fragments x 3 pieces x 2 ds_read_b64 feed 36 MFMAs;
-//   * two LDS stages, one barrier per step; the splits and LDS writes of step i + 1 sit between the MFMAs of step i.
-// Needs 16-byte aligned rows (lda, ldb, M, N multiples of 4).
-constexpr int TNX_RS = 10;                         // dwords per image row (8 of data + 2: see the kernel's comment)
-constexpr int TNX_IMG = 128 * TNX_RS;              // dwords per piece image
-constexpr int TNX_STAGE = 6 * TNX_IMG;             // A(h, m, l), B(h, m, l)
-__device__ __forceinline__ uint4 ld_frag(const uint32_t* p) {   // 8-byte aligned: two ds_read_b64
-  const uint2 a = *reinterpret_cast<const uint2*>(p), b = *reinterpret_cast<const uint2*>(p + 2);
-  return make_uint4(a.x, a.y, b.x, b.y);
-}
-
-__global__ __launch_bounds__(256) void gemm_tn_x3_kernel(TnArgs g) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_tn[];   // [2 * TNX_STAGE]: 60 KB, two work-groups per CU
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int m0 = blockIdx.y * 128, n0 = blockIdx.z * 128;
-  const int64_t kbeg = (int64_t)blockIdx.x * g.k_per_split;
-  const int64_t kend = (kbeg + g.k_per_split < g.K) ? kbeg + g.k_per_split : g.K;
-  const int nsteps = (int)((kend - kbeg + 15) / 16);
-  // loader role: columns past M / N read column 0 (their products only reach rows / columns of C never stored)
-  const int kp = tid & 7, c4 = tid >> 3;
-  const float* la = g.A + ((m0 + 4 * c4 + 3 < g.M) ? m0 + 4 * c4 : 0);
-  const float* lb = g.B + ((n0 + 4 * c4 + 3 < g.N) ? n0 + 4 * c4 : 0);
-  // rows past kend (the last step of the last slab) read row kend - 1, and A's copy is zeroed
-#define PYGAT_TNL_LOAD(R, STEP)                                                               \
-  {                                                                                           \
-    const int64_t k__ = kbeg + 16 * (int64_t)(STEP) + 2 * kp;   /* (steps past the slab: row kend - 1, zeroed) */ \
-    int64_t k0__ = k__ < kend ? k__ : kend - 1, k1__ = k__ + 1 < kend ? k__ + 1 : kend - 1;   \
-    if (PYGAT_DIAG_K1 & 4) { k0__ &= 255; k1__ &= 255; }   /* diagnostic builds only: cache-resident operand rows */ \
-    R##a0 = ld4(la + k0__ * g.lda); R##a1 = ld4(la + k1__ * g.lda);                           \
-    R##b0 = ld4(lb + k0__ * g.ldb); R##b1 = ld4(lb + k1__ * g.ldb);                           \
-    R##z0 = k__ < kend ? 1.f : 0.f; R##z1 = k__ + 1 < kend ? 1.f : 0.f;                       \
-  }
-  // split the pairs (row 2 kp, row 2 kp + 1) of the thread's four columns and store the pieces: dword kp of the
-  // column's row in each piece image
-#define PYGAT_TNL_PUT(IMGBASE, X0, X1, COL)                                                   \
-  {                                                                                           \
-    uint32_t h__, m__, l__;                                                                   \
-    split_pair((X0), (X1), h__, m__, l__);                                                    \
-    uint32_t* q__ = (IMGBASE) + (4 * c4 + (COL)) * TNX_RS + kp;                               \
-    q__[0] = h__; q__[TNX_IMG] = m__; q__[2 * TNX_IMG] = l__;                                 \
-  }
-#define PYGAT_TNL_PUTA(R, STAGE, C, CMP)                                                       \
-  PYGAT_TNL_PUT(lds_tn + (STAGE) * TNX_STAGE, R##a0.CMP * R##z0, R##a1.CMP * R##z1, C)
-#define PYGAT_TNL_PUTB(R, STAGE, C, CMP)                                                       \
-  PYGAT_TNL_PUT(lds_tn + (STAGE) * TNX_STAGE + 3 * TNX_IMG, R##b0.CMP, R##b1.CMP, C)
-#define PYGAT_TNL_SPLIT(R, STAGE)                                                             \
-  PYGAT_TNL_PUTA(R, STAGE, 0, x) PYGAT_TNL_PUTA(R, STAGE, 1, y) PYGAT_TNL_PUTA(R, STAGE, 2, z) PYGAT_TNL_PUTA(R, STAGE, 3, w) \
-  PYGAT_TNL_PUTB(R, STAGE, 0, x) PYGAT_TNL_PUTB(R, STAGE, 1, y) PYGAT_TNL_PUTB(R, STAGE, 2, z) PYGAT_TNL_PUTB(R, STAGE, 3, w)
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  // consumer role: wave (w >> 1, w & 1) owns rows 64 (w >> 1) .., columns 64 (w & 1) .. of the tile
-  const uint32_t* fa = lds_tn + (64 * (w >> 1) + fr) * TNX_RS + 4 * fh;
-  const uint32_t* fb = lds_tn + 3 * TNX_IMG + (64 * (w & 1) + fr) * TNX_RS + 4 * fh;
-  // (the fragment reads come FIRST in program order: hipcc cannot tell the two stages apart and keeps LDS reads
-  // behind every earlier LDS write -- with the split in front, no MFMA could start before its last write)
-#define PYGAT_TNL_READ(STAGE)                                                                 \
-  uint4 fq[4][3];                                                                             \
-  {                                                                                           \
-    const uint32_t* a__ = fa + (STAGE) * TNX_STAGE;                                           \
-    const uint32_t* b__ = fb + (STAGE) * TNX_STAGE;                                           \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                           \
-      fq[0][p] = ld_frag(a__ + p * TNX_IMG);                                                  \
-      fq[1][p] = ld_frag(a__ + p * TNX_IMG + 32 * TNX_RS);                                    \
-      fq[2][p] = ld_frag(b__ + p * TNX_IMG);                                                  \
-      fq[3][p] = ld_frag(b__ + p * TNX_IMG + 32 * TNX_RS);                                    \
-    }                                                                                         \
-  }
-  // one 32 x 32 tile of the wave's block: its nine MFMAs with a quarter of the next step's split (22 VALU
-  // instructions, 6 LDS writes) between them -- small scheduling regions, the whole step in one is beyond what
-  // hipcc's group scheduler arranges
-#define PYGAT_TNL_QUARTER(TM, TN, PUT0, PUT1)                                                 \
-  {                                                                                           \
-    PUT0 PUT1                                                                                 \
-    Frag3 af__;                                                                               \
-    af__.h = __builtin_bit_cast(U4, fq[TM][0]); af__.m = __builtin_bit_cast(U4, fq[TM][1]);   \
-    af__.l = __builtin_bit_cast(U4, fq[TM][2]);                                               \
-    acc[TM][TN] = mma9(af__, fq[2 + TN][0], fq[2 + TN][1], fq[2 + TN][2], acc[TM][TN]);       \
-    _Pragma("unroll") for (int m__ = 0; m__ < 9; ++m__) {                                     \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                      \
-      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                      \
-      if (m__ < 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                         \
-    }                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-  }
-#define PYGAT_TNL_STEP(RSPLIT, RLOAD, I)                                                      \
-  {                                                                                           \
-    PYGAT_TNL_LOAD(RLOAD, (I) + 3)                                                            \
-    PYGAT_TNL_READ((I) & 1)                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    const int sn__ = ((I) + 1) & 1;   /* (past the last step: clamped data into the idle stage) */ \
-    PYGAT_TNL_QUARTER(0, 0, PYGAT_TNL_PUTA(RSPLIT, sn__, 0, x), PYGAT_TNL_PUTA(RSPLIT, sn__, 1, y)) \
-    PYGAT_TNL_QUARTER(0, 1, PYGAT_TNL_PUTA(RSPLIT, sn__, 2, z), PYGAT_TNL_PUTA(RSPLIT, sn__, 3, w)) \
-    PYGAT_TNL_QUARTER(1, 0, PYGAT_TNL_PUTB(RSPLIT, sn__, 0, x), PYGAT_TNL_PUTB(RSPLIT, sn__, 1, y)) \
-    PYGAT_TNL_QUARTER(1, 1, PYGAT_TNL_PUTB(RSPLIT, sn__, 2, z), PYGAT_TNL_PUTB(RSPLIT, sn__, 3, w)) \
-    __syncthreads();                                                                          \
-  }
-  float4 r0a0, r0a1, r0b0, r0b1, r1a0, r1a1, r1b0, r1b1, r2a0, r2a1, r2b0, r2b1;
-  float r0z0, r0z1, r1z0, r1z1, r2z0, r2z1;
-  PYGAT_TNL_LOAD(r0, 0)
-  __builtin_amdgcn_sched_barrier(0);   // (issue order = wait order, see gemm_smallk_x3_kernel)
-  PYGAT_TNL_LOAD(r1, 1)
-  __builtin_amdgcn_sched_barrier(0);
-  PYGAT_TNL_LOAD(r2, 2)
-  __builtin_amdgcn_sched_barrier(0);
-  PYGAT_TNL_SPLIT(r0, 0)
-  __syncthreads();
-  // step i: MFMAs on stage i & 1; ring slot (i + 1) % 3 is split into stage (i + 1) & 1; slot i % 3 (split during
-  // step i - 1) takes the loads of step i + 3
-  // (three steps per turn, unconditionally: the one or two steps past the slab multiply zeroed rows of A -- with the two steps
-  // under `if (i + k < nsteps)` the loop had joins, and behind them hipcc gave a load the registers of an address still in
-  // use: `s_waitcnt vmcnt(0)` at the top of every turn, the loads issued three steps ahead waited for after one)
-  for (int i = 0; i < nsteps; i += 3) {
-    PYGAT_TNL_STEP(r1, r0, i)
-    PYGAT_TNL_STEP(r2, r1, i + 1)
-    PYGAT_TNL_STEP(r0, r2, i + 2)
-  }
-#undef PYGAT_TNL_LOAD
-#undef PYGAT_TNL_PUT
-#undef PYGAT_TNL_SPLIT
-#undef PYGAT_TNL_QUARTER
-#undef PYGAT_TNL_PUTA
-#undef PYGAT_TNL_PUTB
-#undef PYGAT_TNL_READ
-#undef PYGAT_TNL_STEP
-  float* base = g.ws + (int64_t)blockIdx.x * g.M * g.N;
-  const int wm0 = m0 + 64 * (w >> 1), wn0 = n0 + 64 * (w & 1);
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-      const int col = wn0 + 32 * tn + fr;
-      if (col >= g.N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm0 + 32 * tm + (r & 3) + 8 * (r >> 2) + 4 * fh;
-        if (row < g.M) base[(int64_t)row * g.N + col] = acc[tm][tn][r];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The same GEMM on v_mfma_f32_16x16x32_bf16 (round 5).  MI355X_MICROARCH.md (DVFS give-back, item 7): on random data the chip
-// holds a higher clock under the 16 x 16 x 32 shape than under 32 x 32 x 16 at equal cycles per flop; the nine-product loop of
-// this file, LDS-fed, two waves per SIMD, measured 1.08-1.11 x (tools/micro/mfma_shape_x9.hip, profiles/r5*_mfma_shape_x9.txt).
-// The 16 x 16 x 32 instruction sums 32 k of one row, so an LDS stage holds 32 k rows instead of 16:
+// C[M x N] = A^T B with A [K x M], B [K x N], K huge (one row per node): dW = X^T dWh, on v_mfma_f32_16x16x32_bf16.  Both
+// operands are k-strided and the bf16 MFMA wants 8 consecutive k per lane, so a work-group moves 32 k rows of both operands per
+// step through LDS:
 //   * work-group = 8 waves (512 threads), ONE per CU, a 128 x 128 tile of C over one K slab; wave (w >> 1, w & 1) owns rows
 //     32 (w >> 1) .., columns 64 (w & 1) ..: 2 x 4 tiles of 16 x 16, eight accumulators of four registers;
+//   * thread (kp = tid & 7, c4 = (tid >> 3) & 31, half = tid >> 8) loads rows k0 + 2 pr, + 1 (pr = kp + 8 half), columns
+//     4 c4 .. + 3 of A and of B with 16-byte loads (a wave covers 128 contiguous bytes of 16 rows), three steps ahead, into a
+//     three-slot register ring;
+//   * it splits the (k even, k odd) pair of every column ONCE for the whole work-group (a register-only version, every wave
+//     splitting what it multiplies, was bound by those VALU instructions) and writes the three packed pieces as dwords;
 //   * stage = 32 k x (128 + 128) columns x three pieces, images [column][32 k] with NO row padding (64-byte rows): the four
 //     8-k slices of a row sit rotated by (row >> 1) & 3, which makes the 16-byte fragment reads of every ds_read_b128 lane
 //     group (16 lanes: 8 rows of one slice + 8 rows of the next) hit all 64 banks once, and the dword writes of a half-wave
-//     2-way at worst (free for ds_write_b32); two stages = 96 KB;
-//   * thread (kp = tid & 7, c4 = (tid >> 3) & 31, half = tid >> 8) loads rows k0 + 2 pr, + 1 (pr = kp + 8 half) x 4 columns of
-//     both operands (a wave covers 128 contiguous bytes of 16 rows, as above), three steps ahead; one barrier per 32 k --
-//     half as many per flop as the 16-k kernel -- and the split work of a step is spread over eight waves instead of four.
-// Same-lease A/B at config 5 (gpurun_out r5h, tools/ab_variants.sh): k5_wgrad 0.285-0.302 -> 0.260-0.265 ms, step 3.18 -> 3.15 ms;
-// parity tests unchanged (same nine products, fp32 accumulators).  -DPYGAT_TN_WIDE=0 builds the 32 x 32 x 16 kernel above.
-#ifndef PYGAT_TN_WIDE
-#define PYGAT_TN_WIDE 1
-#endif
+//     2-way at worst (free for ds_write_b32);
+//   * two LDS stages (96 KB), one barrier per 32 k; the splits and LDS writes of step i + 1 sit between the MFMAs of step i,
+//     an eighth of them per 16 x 16 tile.  The fragment reads of a step come FIRST in program order: hipcc cannot tell the
+//     two stages apart and keeps LDS reads behind every earlier LDS write -- with the split in front, no MFMA could start
+//     before its last write;
+//   * the loop takes three steps per turn, unconditionally: the one or two steps past the slab multiply zeroed rows of A.
+//     With those steps under `if (i + k < nsteps)` the loop had joins, and behind them hipcc gave a load the registers of an
+//     address still in use: `s_waitcnt vmcnt(0)` at the top of every turn, the loads issued three steps ahead waited for
+//     after one.
+// Output: slab blockIdx.x of the split-K workspace (the caller reduces the slabs).
+// Needs 16-byte aligned rows (lda, ldb, M, N multiples of 4).
+// Why this MFMA shape (MI355X_MICROARCH.md, DVFS give-back, item 7): on random data the chip holds a higher clock under
+// 16 x 16 x 32 than under 32 x 32 x 16 at equal cycles per flop; the nine-product loop of this file, LDS-fed, two waves per
+// SIMD, measured 1.08-1.11 x (tools/micro/mfma_shape_x9.hip, profiles/r5f_mfma_shape_x9.txt).  Against round 4's 32 x 32 x 16
+// kernel (4 waves, 16 k per step, two work-groups per CU) it also has half as many barriers per flop and spreads a step's
+// split work over eight waves instead of four: same-lease A/B at config 5 (profiles/r5h_wgrad_16x16x32_same_lease.txt),
+// k5_wgrad 0.285-0.302 -> 0.260-0.265 ms, step 3.18 -> 3.15 ms; parity tests unchanged (same nine products, fp32 accumulators).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TNW_RS = 16;                         // dwords per image row: 32 k of bf16
 constexpr int TNW_IMG = 128 * TNW_RS;              // dwords per piece image (8 KB)
@@ -1006,7 +846,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
   const int fso = 4 * ((fq + (fi >> 1)) & 3);
   const uint32_t* fa = lds_tw + (32 * (w >> 1) + fi) * TNW_RS + fso;
   const uint32_t* fb = lds_tw + 3 * TNW_IMG + (64 * (w & 1) + fi) * TNW_RS + fso;
-  // (fragment reads FIRST in program order, as in the kernel above)
+  // (fragment reads FIRST in program order: see the kernel's comment)
 #define PYGAT_TWL_READ(STAGE)                                                                 \
   uint4 fqa[2][3], fqb[4][3];                                                                 \
   {                                                                                           \
@@ -1019,7 +859,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
         fqb[t][p] = *reinterpret_cast<const uint4*>(b__ + p * TNW_IMG + 16 * t * TNW_RS);     \
     }                                                                                         \
   }
-  // one 16 x 16 tile: its nine MFMAs (small terms first, as mma9) with an eighth of the next step's split (11 VALU
+  // one 16 x 16 tile: its nine MFMAs (small terms first, as mma9t) with an eighth of the next step's split (11 VALU
   // instructions, 3 LDS writes) between them
 #define PYGAT_TWL_GROUP(TM, TN, PUT0)                                                         \
   {                                                                                           \
@@ -1060,7 +900,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
   __builtin_amdgcn_sched_barrier(0);
   PYGAT_TWL_SPLIT(r0, 0)
   __syncthreads();
-  for (int i = 0; i < nsteps; i += 3) {     // (three steps per turn, unconditionally: see the kernel above)
+  for (int i = 0; i < nsteps; i += 3) {     // (three steps per turn, unconditionally: see the kernel's comment)
     PYGAT_TWL_STEP(r1, r0, i)
     PYGAT_TWL_STEP(r2, r1, i + 1)
     PYGAT_TWL_STEP(r0, r2, i + 2)
@@ -1095,66 +935,65 @@ int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st) {
   if (!aligned16(g.A) || !aligned16(g.B) || (g.lda % 4) != 0 || (g.ldb % 4) != 0 || (g.M % 4) != 0 || (g.N % 4) != 0) return 0;
   int dev = -1;
   (void)hipGetDevice(&dev);
-#if PYGAT_TN_WIDE
-  {   // the 16 x 16 x 32 kernel: one 8-wave work-group per CU, 32-k steps, three per loop turn
-    const int tiles = (int)(cdiv(g.M, 128) * cdiv(g.N, 128));
-    int sw = splits;
-    if (sw * tiles > 256) sw = 256 / tiles > 0 ? 256 / tiles : 1;
-    TnArgs gw = g;
-    gw.k_per_split = cdiv(cdiv(g.K, sw), 96) * 96;
-    sw = (int)cdiv(g.K, gw.k_per_split);
-    constexpr size_t ldsw = 2 * TNW_STAGE * sizeof(uint32_t);
-    static bool attr_w[64] = {};
-    if (dev < 0 || dev >= 64 || !attr_w[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-      if (dev >= 0 && dev < 64) attr_w[dev] = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_x3w_kernel, dim3((unsigned)sw, (unsigned)cdiv(g.M, 128), (unsigned)cdiv(g.N, 128)), dim3(512), ldsw, st, gw);
-    hipError_t ew = hipGetLastError();
-    if (ew != hipSuccess) {
-      set_error("gemm_tn_x3w: %s", hipGetErrorString(ew));
-      return PYGAT_EHIP;
-    }
-    return sw;
+  // one 8-wave work-group per CU: at most 256 of them, slabs of whole loop turns (three 32-k steps)
+  const int tiles = (int)(cdiv(g.M, 128) * cdiv(g.N, 128));
+  int sw = splits;
+  if (sw * tiles > 256) sw = 256 / tiles > 0 ? 256 / tiles : 1;
+  TnArgs gw = g;
+  gw.k_per_split = cdiv(cdiv(g.K, sw), 96) * 96;
+  sw = (int)cdiv(g.K, gw.k_per_split);
+  constexpr size_t ldsw = 2 * TNW_STAGE * sizeof(uint32_t);
+  static bool attr_w[64] = {};   // per device: the attribute belongs to the device's code object
+  if (dev < 0 || dev >= 64 || !attr_w[dev]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
+    if (dev >= 0 && dev < 64) attr_w[dev] = true;
   }
-#endif
-  dim3 grid((unsigned)splits, (unsigned)cdiv(g.M, 128), (unsigned)cdiv(g.N, 128));
-  constexpr size_t lds = 2 * TNX_STAGE * sizeof(uint32_t);
-  static bool attr_set[64] = {};   // per device: the attribute belongs to the device's code object
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(gemm_tn_x3_kernel, grid, dim3(256), lds, st, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("gemm_tn_x3: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(gemm_tn_x3w_kernel, dim3((unsigned)sw, (unsigned)cdiv(g.M, 128), (unsigned)cdiv(g.N, 128)), dim3(512), ldsw, st, gw);
+  hipError_t ew = hipGetLastError();
+  if (ew != hipSuccess) {
+    set_error("gemm_tn_x3w: %s", hipGetErrorString(ew));
     return PYGAT_EHIP;
   }
-  return splits;
+  return sw;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same pipeline for ANY operand layout: C[M x N] = op(A) op(B) with every product formed from the exact three-way
 // bf16 split (projections with K > 256 or few rows: the PPI levels' 1024 -> 1024 GEMMs, layers.py:35,134,48,166; their
-// input gradients dX = dWh W^T; GATv2's projections; weight gradients the streamed-K kernel above does not take).
-// gemm_tn_x3_kernel is the (k-strided, k-strided) case of it and stays as tuned for the headline's dW.
+// input gradients dX = dWh W^T; GATv2's projections; weight gradients gemm_tn_x3w_kernel does not take, which is the
+// (k-strided, k-strided), slabs-only case of this kernel with a three-slot ring).
 //
-// An operand is either K-STRIDED ([K x cols], cols contiguous: A of a transA call, B of a plain one) and staged as
-// above -- thread (kp, c4) loads rows 2 kp, 2 kp + 1 x 4 columns and writes the packed (k even, k odd) pieces as dwords --
-// or K-CONTIGUOUS ([rows x K]: A of a plain call, B of a transB one): thread (h = (tid >> 4) & 1, row = (tid & 15) +
-// 16 (tid >> 5)) loads the 8 floats k0 + 8 h .. + 7 of its row (two 16-byte loads; a row's 16 k of a step are one
-// 64-byte sector), splits the four (k, k + 1) pairs and writes each piece's four dwords as two ds_write_b64 into the
-// SAME image layout ([row or column][16 k], 40-byte rows): the 16 lanes of a ds_write_b64 group hold 16 consecutive
-// rows of one h, 16 x 40 bytes hit the 16 even banks, the pair fills the odd ones -- conflict-free like the dword
-// writes of the k-strided stage.  Consumer side, scheduling (split + LDS writes of step i + 1 between the MFMAs of
-// step i, 9-MFMA regions), the three-slot load ring and the two LDS stages are those of the kernel above.
+// Work-group, LDS image, consumer side and scheduling are gemm_tn_x3w_kernel's: 8 waves, one work-group per CU, a 128 x 128 tile
+// of C over one K slab, wave (w >> 1, w & 1) = rows 32 (w >> 1) .., columns 64 (w & 1) .., 32 k per step, images [row or column]
+// [32 k] of 64-byte rows with the four 8-k slices rotated by (row >> 1) & 3, two LDS stages (96 KB), one barrier per step, the
+// fragment reads first, then per 16 x 16 tile its nine MFMAs with an eighth of step i + 1's split and LDS writes between them.
+// What differs is how an operand reaches its image.  It is either
+//   * K-STRIDED ([K x cols], cols contiguous: A of a transA call, B of a plain one): thread (kp, c4, half) loads rows 2 pr,
+//     2 pr + 1 (pr = kp + 8 half) x columns 4 c4 .. + 3 and writes the packed (k even, k odd) pieces of one column per eighth
+//     as three dwords, exactly as in gemm_tn_x3w_kernel; or
+//   * K-CONTIGUOUS ([rows x K]: A of a plain call, B of a transB one): thread (row = (tid & 15) + 16 (tid >> 6), slice
+//     q = (tid >> 4) & 3) loads the 8 floats k0 + 8 q .. + 7 of its row (two 16-byte loads; a row's 32 k of a step are 128
+//     contiguous bytes), splits one (k, k + 1) pair per eighth into piece registers and, with the fourth pair, writes each piece's
+//     slice with ONE ds_write_b128 at its rotated place (8 consecutive rows of one slice: the 8-lane groups of a b128 write
+//     hit 32 banks once).
+// Either way the split is done once per work-group.  A's copy of k positions past the slab is zeroed (only a slab's last step
+// has any; the 1 / 0 factors are recomputed from the step index instead of riding in the ring); rows / columns past M / N read
+// a row / column inside the matrix, and their products only reach elements of C that are never stored.
 //
-// Two-level accumulation (see gemm_f32_kernel): every 96 k the running 64 x 64 block is added into a second register
-// set.  DIRECT output (ws == nullptr): rows / columns routed to the output segments, optional accumulate; otherwise
-// slab blockIdx.x of the split-K workspace.
+// Two-slot load ring: step i splits the slot loaded during step i - 1 and refills the other one with step i + 2 (the weight-
+// gradient kernel keeps three slots; here the second accumulator set takes the registers).
+// Two-level accumulation (see gemm_f32_kernel): every four steps = 128 k the running accumulators are added into a second
+// register set and cleared.
+// Output: DIRECT (ws == nullptr): columns routed to the output segments (out_segment), or to the column blocks of a blocked
+// C (cb, common.h: one launch, no slabs), optional accumulate; otherwise slab blockIdx.x of the split-K workspace, which the
+// caller reduces.  A k-contiguous A may itself be column-blocked (ab): an 8-float slice never straddles a block.
 // Needs 16-byte aligned rows: ld % 4 == 0 for both operands, K % 4 == 0 and 4-aligned slabs for a k-contiguous one,
 // the contiguous extent (M or N) of a k-strided one a multiple of 4 or its rows padded to one.
+//
+// Measured against round 4's general kernel (32 x 32 x 16 MFMAs, 4 waves, 16 k per step, two work-groups per CU), same lease
+// (profiles/r5i_x3g_16x16x32_same_lease.txt): PPI level-2 input gradient 3144 x 1024 x 1024 (200 tiles) 87.4 -> 69.5 us,
+// level-3 65.4 -> 53.5, weight gradient 84.5 -> 78 (4 slabs instead of 8), projection (425 tiles = two rounds of one-per-CU
+// work-groups) 146 -> 140; PPI epoch 2.35 -> 2.14 ms.  (Why the 16 x 16 x 32 shape: gemm_tn_x3w_kernel.)
 struct X3gArgs {
   int M, N;
   int64_t K;
@@ -1169,204 +1008,6 @@ struct X3gArgs {
   ColBlocks ab, cb;   // column blocks of the stored A / of C (common.h; one block = an ordinary matrix)
 };
 
-struct X3gSlot {      // one step of both operands, in flight
-  float4 a0, a1, b0, b1;
-};
-
-template <bool KCA, bool KCB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_x3g_kernel(X3gArgs g) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_xg[];   // [2 * TNX_STAGE]: 60 KB, two work-groups per CU
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int m0 = blockIdx.y * 128, n0 = blockIdx.z * 128;
-  const int64_t kbeg = (int64_t)blockIdx.x * g.k_per_split;
-  const int64_t kend = (kbeg + g.k_per_split < g.K) ? kbeg + g.k_per_split : g.K;
-  const int nsteps = (int)((kend - kbeg + 15) / 16);
-  // loader roles
-  const int kp = tid & 7, c4 = tid >> 3;                                  // k-strided
-  const int lh = (tid >> 4) & 1, lrow = (tid & 15) + 16 * (tid >> 5);     // k-contiguous
-  const float* la;
-  const float* lb;
-  if constexpr (KCA) la = g.A + (int64_t)((m0 + lrow < g.M) ? m0 + lrow : g.M - 1) * g.lda;   // rows past M: the last row
-  else la = g.A + blk_off((m0 + 4 * c4 < g.M) ? m0 + 4 * c4 : 0, g.ab);   // columns past M: column 0 (a float4 may run up to 3 columns into the row's padding)
-  if constexpr (KCB) lb = g.B + (int64_t)((n0 + lrow < g.N) ? n0 + lrow : g.N - 1) * g.ldb;
-  else lb = g.B + ((n0 + 4 * c4 < g.N) ? n0 + 4 * c4 : 0);
-  // (their products only reach rows / columns of C that are never stored)
-
-  auto load = [&](X3gSlot& r, int step) {
-    const int st = step < nsteps ? step : nsteps - 1;
-    const int64_t ks = kbeg + 16 * (int64_t)st;
-    {   // k-strided addressing (rows 2 kp, 2 kp + 1 of the step)
-      const int64_t k = ks + 2 * kp;
-      const int64_t k0 = k < kend ? k : kend - 1, k1 = k + 1 < kend ? k + 1 : kend - 1;
-      if constexpr (!KCA) { r.a0 = ld4(la + k0 * g.lda); r.a1 = ld4(la + k1 * g.lda); }
-      if constexpr (!KCB) { r.b0 = ld4(lb + k0 * g.ldb); r.b1 = ld4(lb + k1 * g.ldb); }
-    }
-    {   // k-contiguous addressing (floats 8 lh .. + 7 of the step)
-      const int64_t k = ks + 8 * lh;
-      const int64_t k0 = k < kend ? k : kend - 4, k1 = k + 4 < kend ? k + 4 : kend - 4;
-      // (a column-blocked A: the step's 16 k -- and kend - 4 >= ks -- lie in ONE block, blocks being >= 16 wide and slabs
-      // starting at multiples of 16: the block offset is a scalar of the step)
-      if constexpr (KCA) { const float* las = la + (blk_off(ks, g.ab) - ks); r.a0 = ld4(las + k0); r.a1 = ld4(las + k1); }
-      if constexpr (KCB) { r.b0 = ld4(lb + k0); r.b1 = ld4(lb + k1); }
-    }
-  };
-  // half H (0 / 1) of one operand's split + LDS writes: two of the step's eight "put units"
-  auto put_strided = [&](uint32_t* img, const float4& x0, const float4& x1, float z0, float z1, auto half_tag) {
-    constexpr int HALF = decltype(half_tag)::value;
-    float p0, p1, q0, q1;
-    if constexpr (HALF == 0) { p0 = x0.x; p1 = x1.x; q0 = x0.y; q1 = x1.y; } else { p0 = x0.z; p1 = x1.z; q0 = x0.w; q1 = x1.w; }
-    uint32_t h, m, l;
-    split_pair(p0 * z0, p1 * z1, h, m, l);
-    uint32_t* d = img + (4 * c4 + 2 * HALF) * TNX_RS + kp;
-    d[0] = h; d[TNX_IMG] = m; d[2 * TNX_IMG] = l;
-    split_pair(q0 * z0, q1 * z1, h, m, l);
-    d += TNX_RS;
-    d[0] = h; d[TNX_IMG] = m; d[2 * TNX_IMG] = l;
-  };
-  auto put_contig = [&](uint32_t* img, const float4& x, float z) {   // one float4 = two (k, k + 1) pairs
-    uint32_t h0, m0_, l0, h1, m1, l1;
-    split_pair(x.x * z, x.y * z, h0, m0_, l0);
-    split_pair(x.z * z, x.w * z, h1, m1, l1);
-    return [=](uint32_t* d) {
-      *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(d + TNX_IMG) = make_uint2(m0_, m1);
-      *reinterpret_cast<uint2*>(d + 2 * TNX_IMG) = make_uint2(l0, l1);
-    }(img);
-  };
-  // A's copy of k positions past the slab is zeroed (only the last step of a slab has any): step index -> 1 / 0 factors
-  // of the thread's two rows (k-strided) or two float4 (k-contiguous), recomputed here instead of riding in the ring
-  auto put_a = [&](const X3gSlot& r, int stage, int step_of_r, auto half_tag) {
-    constexpr int HALF = decltype(half_tag)::value;
-    uint32_t* img = lds_xg + stage * TNX_STAGE;
-    const int64_t ks = kbeg + 16 * (int64_t)step_of_r;
-    if constexpr (KCA) {
-      const int64_t k = ks + 8 * lh + 4 * HALF;
-      put_contig(img + lrow * TNX_RS + 4 * lh + 2 * HALF, HALF == 0 ? r.a0 : r.a1, k < kend ? 1.f : 0.f);
-    } else {
-      const int64_t k = ks + 2 * kp;
-      put_strided(img, r.a0, r.a1, k < kend ? 1.f : 0.f, k + 1 < kend ? 1.f : 0.f, half_tag);
-    }
-  };
-  auto put_b = [&](const X3gSlot& r, int stage, auto half_tag) {
-    constexpr int HALF = decltype(half_tag)::value;
-    uint32_t* img = lds_xg + stage * TNX_STAGE + 3 * TNX_IMG;
-    if constexpr (KCB) put_contig(img + lrow * TNX_RS + 4 * lh + 2 * HALF, HALF == 0 ? r.b0 : r.b1, 1.f);
-    else put_strided(img, r.b0, r.b1, 1.f, 1.f, half_tag);
-  };
-
-  f32x16 acc[2][2], acc2[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acc2[i][j][r] = 0.f; }
-  // consumer role: wave (w >> 1, w & 1) owns rows 64 (w >> 1) .., columns 64 (w & 1) .. of the tile
-  const uint32_t* fa = lds_xg + (64 * (w >> 1) + fr) * TNX_RS + 4 * fh;
-  const uint32_t* fb = lds_xg + 3 * TNX_IMG + (64 * (w & 1) + fr) * TNX_RS + 4 * fh;
-
-  using H0 = std::integral_constant<int, 0>;
-  using H1 = std::integral_constant<int, 1>;
-  // one step: global loads of step i + 2, fragment reads of stage i & 1 (FIRST in program order, see the kernel
-  // above), then per 32 x 32 tile of the wave's block its nine MFMAs with a quarter of step i + 1's split between them
-  auto step = [&](const X3gSlot& rs, X3gSlot& rl, int i) {
-    load(rl, i + 2);
-    uint4 fq[4][3];
-    {
-      const uint32_t* a_ = fa + (i & 1) * TNX_STAGE;
-      const uint32_t* b_ = fb + (i & 1) * TNX_STAGE;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        fq[0][p] = ld_frag(a_ + p * TNX_IMG);
-        fq[1][p] = ld_frag(a_ + p * TNX_IMG + 32 * TNX_RS);
-        fq[2][p] = ld_frag(b_ + p * TNX_IMG);
-        fq[3][p] = ld_frag(b_ + p * TNX_IMG + 32 * TNX_RS);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int sn = (i + 1) & 1;   // (past the last step: clamped data into the idle stage)
-    auto quarter = [&](auto tm_tag, auto tn_tag) {
-      constexpr int TM = decltype(tm_tag)::value, TN = decltype(tn_tag)::value;
-      Frag3 af;
-      af.h = __builtin_bit_cast(U4, fq[TM][0]); af.m = __builtin_bit_cast(U4, fq[TM][1]); af.l = __builtin_bit_cast(U4, fq[TM][2]);
-      acc[TM][TN] = mma9(af, fq[2 + TN][0], fq[2 + TN][1], fq[2 + TN][2], acc[TM][TN]);
-#pragma unroll
-      for (int m = 0; m < 9; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-        if (m < 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    put_a(rs, sn, i + 1, H0{}); quarter(H0{}, H0{});
-    put_a(rs, sn, i + 1, H1{}); quarter(H0{}, H1{});
-    put_b(rs, sn, H0{}); quarter(H1{}, H0{});
-    put_b(rs, sn, H1{}); quarter(H1{}, H1{});
-    __syncthreads();
-  };
-
-  // two-slot load ring (the streamed-K kernel above keeps three: here the second accumulator set takes the registers,
-  // and two co-resident work-groups x two steps x 16 KB are 64 KB in flight per CU): step i splits the slot loaded
-  // during step i - 1 and refills the other one with step i + 2
-  X3gSlot r0, r1;
-  load(r0, 0);
-  __builtin_amdgcn_sched_barrier(0);   // (issue order = wait order)
-  load(r1, 1);
-  __builtin_amdgcn_sched_barrier(0);
-  put_a(r0, 0, 0, H0{}); put_a(r0, 0, 0, H1{}); put_b(r0, 0, H0{}); put_b(r0, 0, H1{});
-  __syncthreads();
-  for (int i = 0; i < nsteps; i += 2) {
-    step(r1, r0, i);
-    if (i + 1 < nsteps) step(r0, r1, i + 1);
-    if (((i >> 1) % 3) == 2) {      // every 6 steps = 96 k
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { acc2[a][b][r] += acc[a][b][r]; acc[a][b][r] = 0.f; }
-    }
-  }
-  const int wm0 = m0 + 64 * (w >> 1), wn0 = n0 + 64 * (w & 1);
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-      const int col = wn0 + 32 * tn + fr;
-      if (col >= g.N) continue;
-      float* base;
-      int64_t ld;
-      if (g.ws) { base = g.ws + (int64_t)blockIdx.x * g.M * g.N + col; ld = g.N; }
-      else if (g.cb.lw < 62) { base = g.out.ptr[0] + blk_off(col, g.cb); ld = g.out.ld[0]; }
-      else base = out_segment(g.out, col, ld);
-      const bool add = !g.ws && g.accumulate;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm0 + 32 * tm + (r & 3) + 8 * (r >> 2) + 4 * fh;
-        if (row < g.M) {
-          float* p = base + (int64_t)row * ld;
-          const float v = acc[tm][tn][r] + acc2[tm][tn][r];
-          *p = add ? *p + v : v;
-        }
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// gemm_x3g_kernel on v_mfma_f32_16x16x32_bf16 (round 5; see gemm_tn_x3w_kernel for the why and the LDS image): 8 waves, one
-// work-group per CU, 32 k per stage, 128 x 128 tile, wave (w >> 1, w & 1) = rows 32 (w >> 1) .., columns 64 (w & 1) ...
-// K-STRIDED operand: thread (kp, c4, half) as in gemm_tn_x3w_kernel.  K-CONTIGUOUS operand: thread (row = (tid & 15) + 16 (tid >> 6),
-// slice q = (tid >> 4) & 3) loads the 8 floats k0 + 8 q .. + 7 of its row, splits the four pairs and writes each piece's slice with
-// ONE ds_write_b128 (8 consecutive rows of one slice, rotated by (row >> 1) & 3: the 8-lane groups of a b128 write hit 32 banks once).
-// Two-level accumulation every 96 k (three steps), output / slabs / column blocks as gemm_x3g_kernel.
-// Same-lease A/B (gpurun_out r5i, tools/ab_x3gw.sh; profiles/r5i_x3g_16x16x32_same_lease.txt): PPI level-2 input gradient
-// 3144 x 1024 x 1024 (200 tiles) 87.4 -> 69.5 us, level-3 65.4 -> 53.5, weight gradient 84.5 -> 78 (4 slabs instead of 8),
-// projection (425 tiles = two rounds of one-per-CU work-groups) 146 -> 140; PPI epoch 2.35 -> 2.14 ms.
-// -DPYGAT_X3G_WIDE=0 builds the 32 x 32 x 16 kernel above as the general kernel.
-#ifndef PYGAT_X3G_WIDE
-#define PYGAT_X3G_WIDE 1
-#endif
 struct X3gwSlot {      // one 32-k step of both operands, in flight
   float4 a0, a1, b0, b1;
 };
@@ -1520,7 +1161,7 @@ __global__ __launch_bounds__(512) void gemm_x3gw_kernel(X3gArgs g) {
   for (int i = 0; i < nsteps; i += 2) {
     step(r1, r0, i);
     if (i + 1 < nsteps) step(r0, r1, i + 1);
-    if (((i >> 1) & 1) == 1) {      // every 4 steps = 128 k (the 16-k kernel: 96)
+    if (((i >> 1) & 1) == 1) {      // every 4 steps = 128 k
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1574,22 +1215,21 @@ int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A
   g.out = *out; g.accumulate = accumulate;
   g.ab = ab; g.cb = cb;
   if (cb.lw < 62 && splits > 1) return 0;
-#if PYGAT_X3G_WIDE
-  {   // the 16 x 16 x 32 kernel: ONE 8-wave work-group per CU.  Slabs: as many as fill the CUs once (the caller sized them for two
-      // 4-wave work-groups per CU), in whole 32-k steps
-    const int tiles = (int)(cdiv(M, 128) * cdiv(N, 128));
-    int sw = splits;
+  // ONE 8-wave work-group per CU.  Slabs: as many as fill the CUs once, in whole 32-k steps (the caller's count is an upper
+  // bound: ops._split_k sizes it for 512 work-groups)
+  const int tiles = (int)(cdiv(M, 128) * cdiv(N, 128));
+  int sw = splits;
+  if (sw > 1) {
+    if (sw * tiles > 256) sw = 256 / tiles > 1 ? 256 / tiles : 1;
     if (sw > 1) {
-      if (sw * tiles > 256) sw = 256 / tiles > 1 ? 256 / tiles : 1;
-      if (sw > 1) {
-        g.k_per_split = cdiv(cdiv(K, sw), 32) * 32;
-        sw = (int)cdiv(K, g.k_per_split);
-      }
-      if (sw <= 1) { sw = 1; g.k_per_split = K; g.ws = nullptr; }
+      g.k_per_split = cdiv(cdiv(K, sw), 32) * 32;
+      sw = (int)cdiv(K, g.k_per_split);
     }
-    if (splits_used) *splits_used = sw;
-    constexpr size_t ldsw = 2 * TNW_STAGE * sizeof(uint32_t);
-    dim3 gridw((unsigned)sw, (unsigned)cdiv(M, 128), (unsigned)cdiv(N, 128));
+    if (sw <= 1) { sw = 1; g.k_per_split = K; g.ws = nullptr; }
+  }
+  if (splits_used) *splits_used = sw;
+  constexpr size_t ldsw = 2 * TNW_STAGE * sizeof(uint32_t);
+  dim3 gridw((unsigned)sw, (unsigned)cdiv(M, 128), (unsigned)cdiv(N, 128));
 #define PYGAT_X3GW_LAUNCH(KA, KB)                                                                                         \
   do {                                                                                                                    \
     int dev = -1;                                                                                                         \
@@ -1602,41 +1242,14 @@ int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A
     }                                                                                                                     \
     hipLaunchKernelGGL((gemm_x3gw_kernel<KA, KB>), gridw, dim3(512), ldsw, st, g);                                        \
   } while (0)
-    if (kca && kcb) PYGAT_X3GW_LAUNCH(true, true);
-    else if (kca) PYGAT_X3GW_LAUNCH(true, false);
-    else if (kcb) PYGAT_X3GW_LAUNCH(false, true);
-    else PYGAT_X3GW_LAUNCH(false, false);
+  if (kca && kcb) PYGAT_X3GW_LAUNCH(true, true);
+  else if (kca) PYGAT_X3GW_LAUNCH(true, false);
+  else if (kcb) PYGAT_X3GW_LAUNCH(false, true);
+  else PYGAT_X3GW_LAUNCH(false, false);
 #undef PYGAT_X3GW_LAUNCH
-    hipError_t ew = hipGetLastError();
-    if (ew != hipSuccess) {
-      set_error("gemm_x3gw: %s", hipGetErrorString(ew));
-      return PYGAT_EHIP;
-    }
-    return 1;
-  }
-#endif
-  dim3 grid((unsigned)splits, (unsigned)cdiv(M, 128), (unsigned)cdiv(N, 128));
-  constexpr size_t lds = 2 * TNX_STAGE * sizeof(uint32_t);
-#define PYGAT_X3G_LAUNCH(KA, KB)                                                                                          \
-  do {                                                                                                                    \
-    int dev = -1;                                                                                                         \
-    (void)hipGetDevice(&dev);                                                                                             \
-    static bool attr_set[64] = {};                                                                                        \
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3g_kernel<KA, KB>),                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-      if (dev >= 0 && dev < 64) attr_set[dev] = true;                                                                     \
-    }                                                                                                                     \
-    hipLaunchKernelGGL((gemm_x3g_kernel<KA, KB>), grid, dim3(256), lds, st, g);                                           \
-  } while (0)
-  if (kca && kcb) PYGAT_X3G_LAUNCH(true, true);
-  else if (kca) PYGAT_X3G_LAUNCH(true, false);
-  else if (kcb) PYGAT_X3G_LAUNCH(false, true);
-  else PYGAT_X3G_LAUNCH(false, false);
-#undef PYGAT_X3G_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("gemm_x3g: %s", hipGetErrorString(e));
+  hipError_t ew = hipGetLastError();
+  if (ew != hipSuccess) {
+    set_error("gemm_x3gw: %s", hipGetErrorString(ew));
     return PYGAT_EHIP;
   }
   return 1;

@@ -32,20 +32,9 @@ struct ColArgs {
   float* da_part;  // DA instantiations: [work-groups][2 R] = (sum ds_j Wh_j | sum dt_j Wh_j) over the rows the work-group finished
 };
 
-#ifndef PYGAT_K4_DA_ATOMIC
-#define PYGAT_K4_DA_ATOMIC 0
-#endif
-#ifndef PYGAT_K4_DA_WROW
-#define PYGAT_K4_DA_WROW 0   // 1: the finished row's Wh from the registers of the round's previous edge where there is one --
-                             // measured: the longer-lived rows cost 36 bytes of scratch at four waves (K4 1.26 -> 1.39 ms) or
-                             // the fourth wave at 144 VGPRs (1.38 ms); the fetch in the flush stays (gpurun_out r4g)
-#endif
 #ifndef PYGAT_DIAG_K4
 #define PYGAT_DIAG_K4 0   // tools/build_variant.sh only: bit 0 no LDS sums, bit 1 no Wh_j load either (then da is wrong, the time is the point)
 #endif
-__device__ __forceinline__ void lds_add(float* p, float v) {   // ds_add_f32 without a return value
-  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // CR > 0 (with LPH > 0, VEC == 1): dense row tables of CR floats, heads of 4 LPH columns -- constant strides
 // DA (round 4): the attention-vector gradient da_src = sum_j ds_j Wh_j, da_dst = sum_j dt_j Wh_j (autograd of layers.py:60-61,
@@ -56,7 +45,7 @@ __device__ __forceinline__ void lds_add(float* p, float v) {   // ds_add_f32 wit
 template <int VEC, int LPH = 0, int CR = 0, bool DA = false>
 __device__ __forceinline__ void col_finish(const ColArgs& a, const LaneCols<VEC>& lc, int j,
                                            const float4 (&acc)[VEC], const float (&dt)[VEC], float4* da_lds = nullptr,
-                                           int da_stride = 0, const float4* wrow = nullptr) {
+                                           int da_stride = 0) {
   const int Fp = CR ? 4 * LPH : a.rs.Fp;
   const int64_t ldr = CR ? CR : a.rs.ldr, ldh = CR ? CR / (4 * (LPH ? LPH : 1)) : a.rs.ldh;
 #pragma unroll
@@ -66,14 +55,19 @@ __device__ __forceinline__ void col_finish(const ColArgs& a, const LaneCols<VEC>
     const float dsj = a.ds ? a.ds[(int64_t)j * ldh + h] : 0.f;
     const float4 as = ld4(a.a_pad + (int64_t)h * 2 * Fp + f0);
     const float4 ad = ld4(a.a_pad + (int64_t)h * 2 * Fp + Fp + f0);
-    // DA: Wh_j.  wrow: the caller still holds it in registers (the row's last edge was gathered in this round of U edges:
-    // three flushes of four); else it is fetched HERE, with the other loads of the flush and before its stores -- vmcnt
-    // counts loads and stores together in issue order (issued behind the dWh / dt stores, the wait for this load was a wait
-    // for their acknowledgement from HBM: K4 1.21 -> 2.12 ms in the first build of this path, gpurun_out r4b).  The fetch is
+    // DA: Wh_j, fetched HERE, with the other loads of the flush and before its stores -- vmcnt counts loads and stores
+    // together in issue order (issued behind the dWh / dt stores, the wait for this load was a wait for their
+    // acknowledgement from HBM: K4 1.21 -> 2.12 ms in the first build of this path, round 4 run r4b).  The fetch is
     // not free even so: the row comes from L2, not L1 (16 waves of 640-byte gathers turn the 32 KB L1 over every round), and
-    // one more 512-byte read per finished row cost K4 0.05 ms (diagnostic builds, gpurun_out r4f).
+    // one more 512-byte read per finished row cost K4 0.05 ms (diagnostic builds, round 4 run r4f).  Taking the row from the
+    // caller's registers instead, where the finished row's last edge was gathered in the same round of U edges (three
+    // flushes of four), was measured and removed: the longer-lived rows cost 36 bytes of scratch at four waves (K4 1.26 ->
+    // 1.39 ms) or the fourth wave at 144 VGPRs (1.38 ms; round 4 run r4g; DESIGN_HISTORY.md section 8).
+    // (In a lambda, which hipcc folds in only after its early CSE: the row offset j * ldr is then not merged up front with
+    // the dWh store's, and the da instantiation keeps, instruction for instruction, the schedule its figures were measured
+    // on.  Written as a plain expression one address shift moves two instructions down.)
     float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (DA && !(PYGAT_DIAG_K4 & 2)) w = wrow ? wrow[v] : ld4(a.Wh + (int64_t)j * ldr + co);
+    if constexpr (DA && !(PYGAT_DIAG_K4 & 2)) w = [&] { return ld4(a.Wh + (int64_t)j * ldr + co); }();
     float4 o;
     o.x = acc[v].x + dsj * as.x + dt[v] * ad.x;
     o.y = acc[v].y + dsj * as.y + dt[v] * ad.y;
@@ -84,15 +78,10 @@ __device__ __forceinline__ void col_finish(const ColArgs& a, const LaneCols<VEC>
       // Read-modify-write of the lane's own two float4s, ONE AFTER THE OTHER (the fence keeps hipcc from fetching both up
       // front: with both in flight the kernel's peak is 130 VGPRs = three waves per SIMD instead of four).  Only this lane
       // touches these eight words, in program order: the sums are as reproducible as register accumulators.
-      // (ds_add_f32 instead -- one product register at a time, 128 VGPRs -- was measured: LDS float atomics retire about
-      // one lane per clock, K4 1.20 -> 2.14 ms; gpurun_out r4b / r4c.)
+      // (ds_add_f32 instead -- one product register at a time, 128 VGPRs -- was measured and removed: LDS float atomics
+      // retire about one lane per clock, K4 1.20 -> 2.14 ms; round 4 runs r4b / r4c)
 #if PYGAT_DIAG_K4 & 1     /* diagnostic builds only: the Wh_j load without the LDS sums */
       asm volatile("" :: "v"(w.x), "v"(w.y), "v"(w.z), "v"(w.w));
-#elif PYGAT_K4_DA_ATOMIC
-      float* xs = reinterpret_cast<float*>(da_lds);
-      float* ys = reinterpret_cast<float*>(da_lds + da_stride);
-      lds_add(xs + 0, dsj * w.x); lds_add(xs + 1, dsj * w.y); lds_add(xs + 2, dsj * w.z); lds_add(xs + 3, dsj * w.w);
-      lds_add(ys + 0, dt[v] * w.x); lds_add(ys + 1, dt[v] * w.y); lds_add(ys + 2, dt[v] * w.z); lds_add(ys + 3, dt[v] * w.w);
 #else
       {
         float4 x = da_lds[0];
@@ -114,8 +103,7 @@ __device__ __forceinline__ void col_finish(const ColArgs& a, const LaneCols<VEC>
 template <int VEC, int LPH = 0, int CR = 0, bool DA = false>
 __device__ __forceinline__ void col_flush(const ColArgs& a, const LaneCols<VEC>& lc, int64_t q, int j,
                                           bool is_head, bool is_tail, const float4 (&acc)[VEC],
-                                          const float (&dt)[VEC], float4* da_lds = nullptr, int da_stride = 0,
-                                          const float4* wrow = nullptr) {
+                                          const float (&dt)[VEC], float4* da_lds = nullptr, int da_stride = 0) {
   if (is_head || is_tail) {
     // (the slot id is looked up again HERE, in the rare cut-row branch: kept live through the walk -- it no longer follows
     // from the block and thread ids alone once a slot_order is allowed -- it cost the 8 x 16 da instantiation 12 bytes of scratch)
@@ -128,7 +116,7 @@ __device__ __forceinline__ void col_flush(const ColArgs& a, const LaneCols<VEC>&
       if (((lc.cofs[v] >> 2) & (a.rs.lph - 1)) == 0) p[a.rs.R + lc.head[v]] = dt[v];
     }
   } else {
-    col_finish<VEC, LPH, CR, DA>(a, lc, j, acc, dt, da_lds, da_stride, wrow);
+    col_finish<VEC, LPH, CR, DA>(a, lc, j, acc, dt, da_lds, da_stride);
   }
 }
 
@@ -262,9 +250,7 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
     for (int u = 0; u < U; ++u) {
       if (e + u < e1) {
         if (p[u].x != cur) {
-          // (u > 0: the finished row's last edge is edge u - 1 of this round, its Wh row is still in wv[u - 1])
-          col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, cur == r_first && head_partial, false, acc, dt, da_lds, da_stride,
-                                      (DA && PYGAT_K4_DA_WROW && u > 0) ? wv[u > 0 ? u - 1 : 0] : nullptr);
+          col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, cur == r_first && head_partial, false, acc, dt, da_lds, da_stride);
           cur = p[u].x;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); dt[v] = 0.f; }

@@ -204,14 +204,16 @@ def _split_k(M: int, N: int, K: int, streamed_k: bool = False, mode: Optional[st
     nt = -(-N // 32)
     if streamed_k and K >= 4096 and M * N <= 512 * 512 and (mode or get_gemm_mode()) == "split-bf16" and M > 64 and N > 64 \
             and M % 4 == 0 and N % 4 == 0:
-        # the split-bf16 kernel (128 x 128 tiles through 60 KB of LDS): two work-groups per CU
+        # the split-bf16 kernel (128 x 128 tiles): an upper bound of 512 work-groups, sized for round 4's two 4-wave
+        # work-groups per CU -- try_gemm_tn_x3 caps it at one 8-wave work-group per CU (256)
         tiles = -(-M // 128) * -(-N // 128)
         return max(1, min(512 // tiles, K // 256)) if tiles < 512 else 1
     if streamed_k and K >= 4096 and M * N <= 512 * 512:
         tiles = -(-M // 128) * -(-N // (32 * min(nt, 5 if nt == 5 else 4)))
         return max(1, min(256 // tiles, K // 256)) if tiles < 256 else 1
     if (mode or get_gemm_mode()) == "split-bf16" and _x3g_takes(streamed_k, transB, M, N, K) and not (not streamed_k and K <= 256 and M >= 8192):
-        # general split kernel, 128 x 128 tiles, two work-groups per CU.  Its partial sums are expensive (written and
+        # general split kernel, 128 x 128 tiles (try_gemm_x3g caps the slabs at one 8-wave work-group per CU; the figures
+        # below are round 4's, two 4-wave work-groups per CU).  Its partial sums are expensive (written and
         # re-read by the reduce launch): measured on PPI level 2 (tools/gemm_bench.py --splits), projection 3144 x 2056 x
         # 1024 (425 tiles) 145 / 221 us at 1 / 2 slabs, input gradient 3144 x 1024 x 1024 (200 tiles) 82 / 115 us, weight
         # gradient 1024 x 1024 x 3144 (64 tiles) 217 / 140 / 105 / 89 / 82 us at 1 / 2 / 3 / 4 / 8: slabs only when the

@@ -36,7 +36,7 @@ SHAPES = [
     (False, True, 10007, 100, 64), (False, True, 70001, 100, 64), (False, False, 70001, 72, 128), (False, False, 300000, 128, 64),
     (True, False, 128, 128, 100000), (True, False, 100, 200, 65537), (True, False, 72, 130, 50001),
     (True, False, 256, 256, 20011),
-    # the general split kernel (gemm_x3g_kernel: any layout, K > 256 or few rows): the PPI levels' projections, input and
+    # the general split kernel (gemm_x3gw_kernel: any layout, K > 256 or few rows): the PPI levels' projections, input and
     # weight gradients, ragged M / N, K tails of a step (K % 16 != 0) and of the accumulator flush period
     (False, False, 3144, 2056, 1024), (False, True, 3144, 1024, 1024), (True, False, 1024, 1024, 3144),
     (False, False, 1612, 1548, 1024), (False, True, 1000, 1024, 768), (True, False, 1024, 260, 3144),

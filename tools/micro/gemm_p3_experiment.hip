@@ -1,13 +1,14 @@
 // EXPERIMENT, NOT BUILT INTO THE LIBRARY (round 4): fp32 GEMM from operands split into their bf16 planes
-// ONCE, by a pass of its own, instead of once per work-group inside gemm_x3g_kernel.  Correct (bit-exactness and accuracy
+// ONCE, by a pass of its own, instead of once per work-group inside round 4's general split kernel (the 32 x 32 x 16
+// predecessor of gemm_x3gw_kernel, k1_gemm_x3.hip; it splits in the same place).  Correct (bit-exactness and accuracy
 // cases of tests/test_gpu_gemm_split.py passed when it was wired in as pygat_gemm_p3_f32) and no faster: on the PPI level-2
-// shapes under rocprofv3 the plane GEMM takes 92.5 us on average against gemm_x3g_kernel's 94 us (139.5 / 80.1 / 62.6), plus
+// shapes under rocprofv3 the plane GEMM takes 92.5 us on average against round 4's general kernel's 94 us (139.5 / 80.1 / 62.6), plus
 // 16 us of pre-split passes -- the in-kernel split is not what bounds the general split kernel (PPI epoch 2.30 -> 2.53 ms).
 // Needs pygat_amd/csrc/gemm_fast.h and a host wrapper of gemm_splitk_reduce_kernel (launch_splitk_reduce) to build.
 // Compute-bound fp32 GEMMs of the wide levels (PPI: 3144 x 1024 x 2056 projections, layers.py:35,134,48,166; their input and
 // weight gradients; GATv2's projections) from operands split ONCE.
 //
-// gemm_x3g_kernel (k1_gemm_x3.hip) cuts every fp32 operand into its three bf16 pieces INSIDE the GEMM, once per work-group:
+// The general split kernel (k1_gemm_x3.hip; figures: round 4's) cuts every fp32 operand into its three bf16 pieces INSIDE the GEMM, once per work-group:
 // a 128 x 128 tile re-splits its A rows for each of the N / 128 column tiles and its B columns for each of the M / 128 row
 // tiles (PPI level 2: x17 and x25), and the split -- 5.5 VALU operations per element plus the LDS writes -- sits between the
 // MFMAs of every step (MFMA pipe 0.55-0.6 busy, 100 TF fp32-equivalent).  Here the cut is a pass of its own:
@@ -20,7 +21,7 @@
 //              rows (ds_write_b128; the 16 lanes of a ds_read_b128 group hit 16 different 16-byte slots of the bank row) ->
 //              fragments by ds_read_b128 -> 36 MFMAs per wave and step with NO vector-ALU work between them but addresses
 //              (32 k per step held 48 staging registers beside 128 of accumulators: 208 bytes of scratch).
-//              Two accumulator levels as in gemm_x3g_kernel (the running tile is added into a second register set every
+//              Two accumulator levels as in gemm_x3gw_kernel (the running tile is added into a second register set every
 //              128 k: an MFMA accumulator is one fp32 summation chain).  Output through the segment table with optional
 //              accumulate, or split-K slabs (weight gradients: few tiles, long K).
 // Every product is still the exact sum of nine bf16 piece products in fp32: same arithmetic as the other split-bf16 kernels,

@@ -1,6 +1,6 @@
 // does v_mfma_f32_16x16x32_bf16 buy the nine-product (exact three-way bf16 split) GEMM loop the
-// 1.12-1.15 x MI355X_MICROARCH.md (DVFS give-back, item 7) reports for bare loops?  Same structure as gemm_x3g_kernel's consumer
-// side -- work-groups of 4 waves, each wave a 64 x 64 block of a 128 x 128 tile, three bf16 images of A and of B in LDS with
+// 1.12-1.15 x MI355X_MICROARCH.md (DVFS give-back, item 7) reports for bare loops?  Same structure as the consumer side of round 4's
+// general split kernel -- work-groups of 4 waves, each wave a 64 x 64 block of a 128 x 128 tile, three bf16 images of A and of B in LDS with
 // 16-byte fragments read by ds_read_b128, all nine piece products of a block chained on one accumulator -- on random data, with
 // FILL vector instructions per 32 k and wave (the split + LDS-write work of the real kernel: ~260) placed between the MFMAs:
 //   shape 32: per 16 k   2 x 2 tiles of 32 x 32 x 16,  12 fragment reads,  36 MFMAs of 32 cycles

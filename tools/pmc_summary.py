@@ -88,6 +88,9 @@ def main():
         "k3c_rowsum": ("pygat::gat_bwd_rowsum_kernel",),
         "k5_agrad": ("pygat::a_grad_partial", "pygat::a_grad_final"),
         "k5_afold": ("pygat::a_grad_fold", "pygat::a_grad_final"),
+        # (gemm_tn_x3_kernel: round 4's weight-gradient kernel, gone from the sources -- the name stays because the committed
+        # summaries of rounds 3-4, profiles/r03g ... r4z_pmc_bench.json, which --promote reads, carry it: counters collected
+        # from a build of that time still fold into the same span)
         "k5_wgrad": ("pygat::gemm_tn_x3_kernel", "pygat::gemm_tn_x3w_kernel", "pygat::gemm_splitk_reduce_kernel", "pygat::unpack_wgrad"),
     }
     traffic = {}
