@@ -475,6 +475,30 @@ int pygat_gatv2_attention(int n, int64_t nnz, const int32_t* rowptr, const int32
                           int H, int Fo, float alpha, const float* WW, const float* a2, const float* m, const float* Z,
                           float* att, void* stream);
 
+/* ------------------------------------------------ K14: gradient through the attention coefficients (csrc/k14_alpha_grad.hip)
+ * Additive under ABI 16 (no existing entry point changes).  A [nnz x H] = dL/d att of pygat_gat_attention, in the CALLER's edge
+ * order; z_ij = s_i + t_j, l_ij = (z_ij > 0 ? 1 : alpha), att_ij recomputed from (s_i, t_j, m_i, Z_i) as K13 forms it:
+ *   rows:  c_i = sum_k att_ik A_ik,  ds2_i = sum_j l_ij att_ij (A_ij - c_i)        over the forward pattern (rowptr, edge_rc);
+ *          rec [n x H x 4] = (s_i, m_i, Z_i, c_i) per node and head, Z = 0 marking a row of at most one edge
+ *   cols:  dt2_j = sum_i l_ij att_ij (A_ij - c_i)                                   over the transposed pattern (rowptr_t,
+ *          edge_rc_t = (j, i) per transposed edge; a symmetric pattern passes its forward arrays), A of transposed edge k at row
+ *          perm_t[k]; reads the rec the row pass left
+ *   apply: dWh_q += ds2_q a_src + dt2_q a_dst for the table rows q < n_rows (a_pad [H][2][Fp], dWh [n_rows x H*Fp]).
+ * The caller adds da through pygat_a_grad(ds2, dt2).  Tables (s, t, m, Z, rec, ds2, dt2) have n rows in the level's node order,
+ * to_internal (NULL: identity) maps a caller node to its table row; t is the [n x H] table pygat_gat_attention left.  A row of
+ * exactly one edge has att = 1, a constant: it contributes exactly zero, and neither its table rows nor its rows of A are read.
+ * H <= 64.  Fo is only validated (1..256, as every entry point of a level does): the passes work on the per-head score tables and
+ * never touch an F'-wide row.  Scratch, the caller's: rec n*H*4 floats (16-byte aligned); part ceil(nnz / 2048) * 5 * H * 3 floats (both passes may
+ * share it).  No float atomics, fixed summation order: bitwise reproducible.  alpha = the LeakyReLU slope. */
+int pygat_alpha_grad_rows(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, const int32_t* to_internal,
+                          int H, int Fo, float alpha, const float* s, const float* t, const float* m, const float* Z,
+                          const float* A, float* rec, float* ds2, float* part, void* stream);
+int pygat_alpha_grad_cols(int n, int64_t nnz, const int32_t* rowptr_t, const int32_t* edge_rc_t, const int32_t* perm_t,
+                          const int32_t* to_internal, int H, int Fo, float alpha, const float* t, const float* rec,
+                          const float* A, float* dt2, float* part, void* stream);
+int pygat_alpha_grad_apply(int n_rows, int H, int Fo, const float* a_pad, const float* ds2, const float* dt2, float* dWh,
+                           void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

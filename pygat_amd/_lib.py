@@ -42,6 +42,7 @@ SYMBOLS = [
     "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
     "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
     "pygat_gat_attention", "pygat_gatv2_attention",
+    "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -140,6 +141,9 @@ def _load():
     lib.pygat_gatv2_backward.argtypes = [C.POINTER(Graph), C.POINTER(Graph), p, p, i, i, f, p, p, p, p, p, p, p, p]
     lib.pygat_gat_attention.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, p, p, p, i, p, p, p]
     lib.pygat_gatv2_attention.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p]
+    lib.pygat_alpha_grad_rows.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p]
+    lib.pygat_alpha_grad_cols.argtypes = [i, i64, p, p, p, p, i, i, f, p, p, p, p, p, p]
+    lib.pygat_alpha_grad_apply.argtypes = [i, i, i, p, p, p, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz

@@ -28,6 +28,7 @@ namespace pygat {
 int footprint_k2_headline(int* regs, int* scratch);
 int footprint_k4_headline_da(int* regs, int* scratch);
 int footprint_gemm_x3(int which, int* regs, int* scratch);
+int footprint_k14(int which, int* regs, int* scratch);
 }  // namespace pygat
 
 extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* scratch_bytes) {
@@ -37,7 +38,11 @@ extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* sc
   if (!strcmp(kernel, "tn_x3w")) return pygat::footprint_gemm_x3(0, num_regs, scratch_bytes);
   if (!strcmp(kernel, "x3gw")) return pygat::footprint_gemm_x3(1, num_regs, scratch_bytes);
   if (!strcmp(kernel, "k1_x3_tail")) return pygat::footprint_gemm_x3(2, num_regs, scratch_bytes);
-  pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw, k1_x3_tail)", kernel);
+  static const char* const k14[] = {"k14_rows_long", "k14_cols_long", "k14_rows_wave", "k14_cols_wave", "k14_apply"};
+  for (int w = 0; w < 5; ++w)
+    if (!strcmp(kernel, k14[w])) return pygat::footprint_k14(w, num_regs, scratch_bytes);
+  pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw, k1_x3_tail, k14_rows_long, "
+                   "k14_cols_long, k14_rows_wave, k14_cols_wave, k14_apply)", kernel);
   return PYGAT_EINVAL;
 }
 

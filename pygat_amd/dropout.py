@@ -184,13 +184,19 @@ class GATLevelDropoutFn(torch.autograd.Function):
             graph, L, float(alpha), concat, flags, p, explicit
         ctx.use_bits = use_bits
         ctx.flavour = flavour
+        if att is not None and att.grad:     # alpha as a second differentiable output (ops._level_forward)
+            ctx.set_materialize_grads(False)
+            ctx.att_bwd, ctx.out_shape = att.backward_state(), tuple(out.shape)
+            return out, att.alpha
         return out
 
     @staticmethod
-    def backward(ctx, G):
+    def backward(ctx, G, A=None):
         Ae, Bp, a_pad, Wh, s, Sk, y, m, Z, mx_or_seed, mwh, matt, aneg, qneg, Wcat = ctx.saved_tensors
         graph, L, H, Fo, p = ctx.graph, ctx.L, ctx.L.H, ctx.L.Fo, ctx.p
         dev, f32 = Ae.device, torch.float32
+        if G is None:        # (a "grad" level whose loss reaches it through alpha alone)
+            G = torch.zeros(ctx.out_shape, dtype=f32, device=dev)
         G = G.contiguous().float()
         HF, R, Fin = H * L.Fin, L.R, L.Fin
         ncb = Bp.shape[1] if Bp.dim() == 2 else 0     # (wide path only: Bp is the block-diagonal weight stack there)
@@ -230,10 +236,22 @@ class GATLevelDropoutFn(torch.autograd.Function):
                                                     ds.data_ptr(), part.data_ptr(), 0, 0, st), "gat_backward_rowsum")
             da = torch.empty(H, 2 * Fo, dtype=f32, device=dev)
             ws = torch.empty(lib.pygat_agrad_workspace_bytes(H, Fo) // 4, dtype=f32, device=dev)
+            da2 = None
+            if A is not None:
+                # the loss through alpha (csrc/k14_alpha_grad.hip): alpha was taken from the masked Wh, before the attention
+                # mask, so (ds', dt') enter dWh here -- in front of the pass below that takes dWh back through the Wh mask
+                ds2, dt2 = ctx.att_bwd.scores(A, s, m, Z, ctx.alpha, st)
+                check(lib.pygat_alpha_grad_apply(L.N, H, Fo, a_pad.data_ptr(), ds2.data_ptr(), dt2.data_ptr(), dWh.data_ptr(), st),
+                      "alpha_grad_apply")
+                da2 = torch.empty(H, 2 * Fo, dtype=f32, device=dev)
+                check(lib.pygat_a_grad(L.N, H, Fo, Wh.data_ptr(), ds2.data_ptr(), dt2.data_ptr(), da2.data_ptr(), ws.data_ptr(),
+                                       None, None, None, 0, 0, st), "a_grad")
             # the same pass takes dWh back through the Wh dropout (x mwh), after finishing it where the flavour asks for that
             check(lib.pygat_a_grad(L.N, H, Fo, Wh.data_ptr(), ds.data_ptr(), dt.data_ptr(), da.data_ptr(), ws.data_ptr(),
                                    None if two_gather else a_pad.data_ptr(), dWh.data_ptr(), mwh.data_ptr(), 0, 0, st),
                   "a_grad")
+            if da2 is not None:
+                da += da2
             xs = getattr(ctx, "xs", None)
             if xs is not None:   # weight gradients on the non-zeros of x under the same decisions (forward: project_sparse)
                 dW = torch.empty(H, Fin, Fo, dtype=f32, device=dev)
@@ -327,17 +345,21 @@ def _backward_bits(ctx, x, bits, Wcat, dWh, GR, RW, st):
 def gat_level_dropout(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                       Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, p: float,
                       head_mean: bool = False, masks: Optional[dict] = None, generator=None, xs=None,
-                      return_attention: bool = False):
+                      return_attention=False):
     """One level in training mode with dropout p.  `masks` (tests) = {"x","wh","att"} pre-scaled; without them the
     masks are drawn in-kernel from one int64 seed taken from torch's (graph-safe) generator.
     return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level: after the x and Wh masks, before the attention
-    mask (layers.py:132-153), so every row sums to 1."""
+    mask (layers.py:132-153), so every row sums to 1.  return_attention="grad": alpha is a second differentiable output, as
+    for ops.gat_level; its gradient flows back through the Wh mask and the x masks like dWh does."""
     del head_mean  # implied by `concat` (models.py:23): concat=False <=> last level <=> head mean
-    att = ops.AttentionTarget(graph, len(Ws), x.device) if return_attention else None
+    grad = ops.attention_mode(return_attention)
+    att = ops.AttentionTarget(graph, len(Ws), x.device, grad=grad) if return_attention else None
     W, a, Wskip = stack_heads(list(Ws), list(As), None if Wskips is None else list(Wskips))   # one launch, not a cat per kind
     if masks is not None:
         out = GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, masks["x"], masks["wh"], masks["att"], None, xs, att)
     else:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=x.device, generator=generator)
         out = GATLevelDropoutFn.apply(x, W, a, Wskip, graph, alpha, concat, p, None, None, None, seed, xs, att)
+    if grad:
+        return out           # (out, alpha): both outputs of the level's autograd node
     return (out, att.alpha) if return_attention else out

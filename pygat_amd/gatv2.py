@@ -227,11 +227,12 @@ def draw_masks_v2(p: float, H: int, N: int, Fin: int, Fo: int, E: int, device, g
 
 def gatv2_level(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                 Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, dropout: float = 0.0,
-                masks: Optional[dict] = None, return_attention: bool = False):
+                masks: Optional[dict] = None, return_attention=False):
     """All heads of one SpGraphAttentionLayerV2 level.  Ws: H tensors [2Fin,F']; As: H tensors of F' elements.
     dropout > 0 (training): per-head masks are drawn here unless given (`masks`, tests).
     return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level (after the x / Whi / Whj masks, before the
-    attention mask)."""
+    attention mask); detached -- return_attention="grad" (ops.gat_level) is refused: the GATv2 score gradient is not built."""
+    _no_grad_attention(return_attention, "gatv2_level")
     att = ops.AttentionTarget(graph, len(Ws), x.device) if return_attention else None
     W, a, Wskip = stack_heads(list(Ws), list(As), None if Wskips is None else list(Wskips))   # one launch, not a cat per kind
     if masks is None and dropout > 0.0:
@@ -239,6 +240,12 @@ def gatv2_level(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[tor
         masks = draw_masks_v2(dropout, H, x.shape[0], Fin2 // 2, Fo, graph.nnz, x.device)
     out = GATv2LevelFn.apply(x, W, a, Wskip, graph, alpha, concat, masks, att)
     return (out, att.alpha) if return_attention else out
+
+
+def _no_grad_attention(return_attention, what: str) -> None:
+    if ops.attention_mode(return_attention):
+        raise ValueError(f"pygat_amd: {what} does not take return_attention=\"grad\": differentiable attention coefficients cover "
+                         "the GAT (v1) level only; return_attention=True gives the detached coefficients")
 
 
 class _V2Base(nn.Module):
@@ -291,6 +298,7 @@ class GraphAttentionLayerV2(_V2Base):
         """`masks` (tests only): explicit pre-scaled keep masks {"x" [1,N,Fin], "wh" [1,N,F'] (the Wh2 mask,
         layers.py:212), "att" [E,1]} instead of in-kernel draws.  return_attention: -> (out, alpha [E, 1]) in the order of
         adj > 0 -- the uniform 1 / deg_i of the row-broadcast logits."""
+        _no_grad_attention(return_attention, "GraphAttentionLayerV2")
         Fo = self.out_features
         zero_a = torch.zeros(2 * Fo, 1, dtype=self.W.dtype, device=self.W.device)   # uniform attention
         graph = as_graph(adj, self.pattern_mode)

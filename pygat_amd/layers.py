@@ -42,7 +42,8 @@ class _FusedGATLayer(nn.Module):
 
     def forward(self, h, adj, return_attention=False):
         """return_attention: -> (out, alpha [E, 1]), the attention coefficient of every edge of the layer's pattern in
-        row-major order (adj.nonzero() / adj > 0: CSRGraph.edge_index()), detached."""
+        row-major order (adj.nonzero() / adj > 0: CSRGraph.edge_index()), detached; return_attention="grad": the same alpha as
+        a differentiable output (ops.gat_level)."""
         graph = as_graph(adj, self.pattern_mode)
         skips = [self.skip_projection] if self.skip_connection else None
         if self.training and self.dropout > 0.0:

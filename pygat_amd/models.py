@@ -50,7 +50,11 @@ class GAT(nn.Module):
 
     def forward(self, x, adj, return_attention=False):
         """return_attention: -> (out, [alpha_1, ..., alpha_L]), alpha_l [E, H_l] (detached) in the edge order of
-        as_graph(adj) (its edge_index()), whatever node order the levels ran in."""
+        as_graph(adj) (its edge_index()), whatever node order the levels ran in.  return_attention="grad": every alpha_l is a
+        differentiable output of its level (ops.gat_level; the v1 layers only)."""
+        if isinstance(return_attention, str) and self._kind != "v1":
+            from .gatv2 import _no_grad_attention
+            _no_grad_attention(return_attention, "a GATv2 model")
         if return_attention and (self.head_parallel or self.level_fn is not None):
             raise ValueError("pygat_amd: return_attention takes neither head_parallel=True nor a level_fn")
         graph = adj if self.level_fn is not None else as_graph(adj, self.pattern_mode)
@@ -71,7 +75,7 @@ class GAT(nn.Module):
             concat = lvl < len(self.gat_layers) - 1
             if self._kind == "other":   # e.g. GraphAttentionLayerV2: one head per call, as the reference does
                 if return_attention:
-                    ys, hs = zip(*[att(x, graph, return_attention=True) for att in heads])
+                    ys, hs = zip(*[att(x, graph, return_attention=return_attention) for att in heads])
                     alphas.append(torch.cat(hs, dim=1))
                 else:
                     ys = [att(x, graph) for att in heads]
@@ -80,7 +84,7 @@ class GAT(nn.Module):
             Ws, As = [h.W for h in heads], [h.a for h in heads]
             Sk = [h.skip_projection for h in heads] if self.skip_connection else None
             fn = self.level_fn
-            ra = {"return_attention": True} if return_attention else {}
+            ra = {"return_attention": return_attention} if return_attention else {}
             if self._kind == "v2sp" and fn is None:
                 from .gatv2 import gatv2_level
                 fn = lambda x_, g_, W_, a_, sk_, al_, cc_: gatv2_level(x_, g_, W_, a_, sk_, al_, cc_, p_drop, **ra)  # noqa: E731
@@ -99,7 +103,7 @@ class GAT(nn.Module):
                     from .dropout import gat_level_dropout
                     x = gat_level_dropout(x, graph, Ws, As, Sk, self.alpha, concat, p_drop, xs=xs, **ra)
                 elif return_attention and to_internal is not None:    # (levels on the internal view: alpha in the caller's order)
-                    x = gat_level(x, graph, Ws, As, Sk, self.alpha, concat, xs=xs, return_attention=True,
+                    x = gat_level(x, graph, Ws, As, Sk, self.alpha, concat, xs=xs, return_attention=return_attention,
                                   attention_order=(user_graph, to_internal))
                 else:
                     x = gat_level(x, graph, Ws, As, Sk, self.alpha, concat, xs=xs, **ra)

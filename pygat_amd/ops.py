@@ -340,7 +340,8 @@ def blocked_input_ok(x3: torch.Tensor) -> bool:
 
 
 class GATLevelFn(torch.autograd.Function):
-    """forward(x, W[H,Fin,F'], a[H,2F'], Wskip[H,Fin,F']|None, graph, alpha, concat[, bwd_heads]) -> out.
+    """forward(x, W[H,Fin,F'], a[H,2F'], Wskip[H,Fin,F']|None, graph, alpha, concat[, bwd_heads]) -> out
+    (att = an AttentionTarget with grad=True: -> (out, alpha), both differentiable).
 
     x may be COLUMN-BLOCKED: a 3-D tensor [blocks, N, w] = the activation of a head-parallel hidden level as the exchange
     left it (block b = rank b's head columns of every node; pygat_amd/dist.py), read in place by the projection and the
@@ -379,8 +380,8 @@ class GATLevelFn(torch.autograd.Function):
                               att=att)
 
     @staticmethod
-    def backward(ctx, G):
-        dx, dW, da, dWs = _level_backward(ctx, G)
+    def backward(ctx, G, A=None):
+        dx, dW, da, dWs = _level_backward(ctx, G, A)
         cast = lambda g_, k: g_ if g_ is None or g_.dtype == ctx.in_dtypes[k] else g_.to(ctx.in_dtypes[k])  # noqa: E731
         return (cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None)
 
@@ -394,7 +395,8 @@ class GATLevelHeadsFn(torch.autograd.Function):
     skip_projection [Fin,F'] tensor PER HEAD (layers.py:21-28,111-119; models.py:15-27) -- instead of stacked: the packing
     kernel reads them through a pointer table (pygat_pack_params_heads), so no torch.stack (a cat launch per parameter
     kind, level and forward: a tenth of a small graph's epoch) precedes the level.
-    forward(x, graph, alpha, concat, pipeline, H, skip, xs, att, *Ws, *As[, *Wskips]) -> out (att: see AttentionTarget)."""
+    forward(x, graph, alpha, concat, pipeline, H, skip, xs, att, *Ws, *As[, *Wskips]) -> out (att: see AttentionTarget;
+    an att with grad=True: -> (out, alpha), both differentiable)."""
 
     @staticmethod
     def forward(ctx, x, graph: CSRGraph, alpha: float, concat: bool, pipeline, H: int, skip: bool, xs, att, *params):
@@ -422,8 +424,8 @@ class GATLevelHeadsFn(torch.autograd.Function):
         return _level_forward(ctx, need, x, H, Fo, skip, pack, graph, alpha, concat, None, pipeline, xs=xs, att=att)
 
     @staticmethod
-    def backward(ctx, G):
-        dx, dW, da, dWs = _level_backward(ctx, G)
+    def backward(ctx, G, A=None):
+        dx, dW, da, dWs = _level_backward(ctx, G, A)
         H = ctx.H
         if dx is not None and dx.dtype != ctx.in_dtype_x:
             dx = dx.to(ctx.in_dtype_x)
@@ -447,6 +449,8 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
     AttentionTarget the forward fills with the level's attention coefficients, or None."""
     if att is not None and pipeline is not None:
         raise ValueError("pygat_amd: return_attention does not take a pipeline")
+    if att is not None and att.grad and bwd_heads is not None:
+        raise ValueError("pygat_amd: return_attention=\"grad\" does not take a backward over a head range (head_parallel)")
     if x.dim() == 3 and not blocked_input_ok(x):
         raise ValueError(f"column-blocked input {tuple(x.shape)}: blocks must be a power of two >= 16 floats wide (float32, GPU)")
     L = _Level(x, H, Fo, skip)
@@ -615,13 +619,22 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
             if skip or need[0]:
                 raise ValueError("pygat_amd: bwd_heads supports neither a skip projection nor a gradient into x")
             ctx.bwd_heads = (hb, hr)
+    if att is not None and att.grad:
+        # alpha is a second output of the node: an absent gradient stays None (a loss on `out` alone launches nothing new)
+        ctx.set_materialize_grads(False)
+        if need_grad:
+            ctx.att_bwd, ctx.out_shape = att.backward_state(), tuple(out.shape)
+        return out, att.alpha
     return out
 
-def _level_backward(ctx, G):
-    """Body of the level's backward: -> (dx | None, dW [H,Fin,F'] | None, da [H,2F'] | None, dWskip | None)."""
+def _level_backward(ctx, G, A=None):
+    """Body of the level's backward: -> (dx | None, dW [H,Fin,F'] | None, da [H,2F'] | None, dWskip | None).
+    A: dL/d alpha [E, H] of a level that returned its coefficients as a differentiable output (return_attention="grad"), or None."""
     x, Wcat, a_pad, Wh, s, Sk, y, m, Z, aneg, qneg = ctx.saved_tensors
     graph, L, H, Fo = ctx.graph, ctx.L, ctx.L.H, ctx.L.Fo
     dev, f32 = x.device, torch.float32
+    if G is None:        # (only a level in "grad" mode sees this: the loss reaches it through alpha alone)
+        G = torch.zeros(ctx.out_shape, dtype=f32, device=dev)
     G = G.contiguous().float()
     ranged = ctx.bwd_heads is not None
     hb, hr = ctx.bwd_heads if ranged else (0, 0)       # (0, 0) = all heads in the C ABI
@@ -704,7 +717,7 @@ def _level_backward(ctx, G):
         finish = rowsum and not fold_ds
         # when a_grad does not rewrite dWh, nothing downstream depends on it: run it on the side stream,
         # beside the weight-gradient GEMM (TIMER spans stay on the main stream: no fork while timing kernels)
-        fork = OVERLAP_BACKWARD and not finish and TIMER is None and ctx.need[1]
+        fork = OVERLAP_BACKWARD and not finish and TIMER is None and ctx.need[1] and A is None
         if fork:
             main, side = torch.cuda.current_stream(), _side_stream(dev)
             side.wait_stream(main)      # the tensors it touches stay referenced until the join below
@@ -719,6 +732,21 @@ def _level_backward(ctx, G):
                                        ws.data_ptr(), a_pad.data_ptr() if finish else None,
                                        dWh.data_ptr() if finish else None, None, hb, hr,
                                        side.cuda_stream if fork else st), "a_grad")
+        if A is not None:
+            # the loss through alpha: (ds', dt') from the row and column passes of K14; their rank-one terms go into dWh and da
+            # here, before the weight and input gradients consume them -- everything above is as for a loss on `out` alone.  The
+            # self-loop-only tail contributes nothing (alpha = 1) and its Wh rows may be unwritten: the rows before it only.
+            live = L.N if tail is None else tail[0]
+            ds2, dt2 = ctx.att_bwd.scores(A, s, m, Z, ctx.alpha, st)
+            with _span("k14_alpha_apply"):
+                check(lib.pygat_alpha_grad_apply(live, H, Fo, a_pad.data_ptr(), ds2.data_ptr(), dt2.data_ptr(), dWh.data_ptr(), st),
+                      "alpha_grad_apply")
+                if ctx.need[2]:
+                    da2 = torch.empty(H, 2 * Fo, dtype=f32, device=dev)
+                    ws2 = torch.empty_like(ws)
+                    check(lib.pygat_a_grad(live, H, Fo, Wh.data_ptr(), ds2.data_ptr(), dt2.data_ptr(), da2.data_ptr(), ws2.data_ptr(),
+                                           None, None, None, 0, 0, st), "a_grad")
+                    da += da2
         # dW = x^T dWh (split-K over the nodes), dWskip = x^T Gp
         dW = dWs = dx = None
         if sparse_w and (ctx.need[1] or (L.skip and ctx.need[3])):
@@ -762,13 +790,21 @@ def _level_backward(ctx, G):
 
 class AttentionTarget:
     """Where a level writes its attention coefficients (return_attention): alpha [E, H] float32, not differentiable, row k =
-    edge k of the CALLER's pattern (graph.fwd: rowptr, edge_rc).  The level's tables may be in another node order: `to_internal`
+    edge k of the CALLER's pattern (graph.fwd: rowptr, edge_rc).
+    grad=True (return_attention="grad"): the level returns alpha as a second, differentiable output.  The target then keeps `t`,
+    the pattern and the node map for the level's backward (AlphaGradState); at most MAX_GRAD_HEADS heads.  The level's tables may be in another node order: `to_internal`
     (caller node -> table row) is set when the level renumbers by itself (ops._level_forward, GATv2LevelFn), or given as
     order = (caller graph, to_internal) by a caller that hands the level an InternalOrderView of its graph (GAT.forward)."""
 
-    def __init__(self, graph, H: int, device, order=None):
+    MAX_GRAD_HEADS = 64      # csrc/k14_alpha_grad.hip: a wave's lanes cover the heads
+
+    def __init__(self, graph, H: int, device, order=None, grad: bool = False):
+        if grad and H > self.MAX_GRAD_HEADS:
+            raise ValueError(f"pygat_amd: return_attention=\"grad\" takes at most {self.MAX_GRAD_HEADS} heads per level, not {H}; "
+                             "return_attention=True gives the detached coefficients")
         g, self.to_internal = (graph, None) if order is None else order
         self.pattern = g.fwd
+        self.grad, self.t, self._graph = bool(grad), None, g
         self.alpha = torch.empty(g.nnz, H, dtype=torch.float32, device=device)
         if self.pattern.n != graph.n or g.nnz != graph.nnz:
             raise ValueError(f"pygat_amd: attention_order: a graph of {self.pattern.n} nodes / {g.nnz} edges for a level on "
@@ -786,10 +822,57 @@ class AttentionTarget:
         check(lib.pygat_gat_attention(*self._pattern_args(), H, Fo, float(slope), Wh.data_ptr(), ldwh, s.data_ptr(),
                                       a_pad.data_ptr(), m.data_ptr(), Z.data_ptr(), int(t_rows), t.data_ptr(),
                                       self.alpha.data_ptr(), st), "gat_attention")
+        if self.grad:
+            self.t, self.Fo = t, int(Fo)
+
+    def backward_state(self) -> "AlphaGradState":
+        """What the backward of a "grad" level needs (NOT alpha itself: the node's own output would keep the node alive)."""
+        if self.t is None:
+            raise ValueError("pygat_amd: return_attention=\"grad\" covers the GAT (v1) level only")
+        return AlphaGradState(self._graph, self.t, self.to_internal, self.Fo)
 
     def launch_v2(self, H, Fo, slope, WW, a2, m, Z, st):
         check(lib.pygat_gatv2_attention(*self._pattern_args(), H, Fo, float(slope), WW.data_ptr(), a2.data_ptr(), m.data_ptr(),
                                         Z.data_ptr(), self.alpha.data_ptr(), st), "gatv2_attention")
+
+
+class AlphaGradState:
+    """The caller's pattern (forward and transposed, with perm_t), the node map and the t table of a level whose attention
+    coefficients are a differentiable output: scores() runs the row and the column pass of csrc/k14_alpha_grad.hip."""
+
+    def __init__(self, graph, t: torch.Tensor, to_internal: Optional[torch.Tensor], Fo: int):
+        self.graph, self.t, self.to_internal, self.Fo = graph, t, to_internal, Fo
+
+    def scores(self, A: torch.Tensor, s, m, Z, slope: float, st: int):
+        """A [E, H] = dL/d alpha in the caller's edge order -> (ds', dt') [N, H] in the level's node order."""
+        g, t = self.graph, self.t
+        n, H = t.shape
+        if tuple(A.shape) != (g.nnz, H):
+            raise ValueError(f"pygat_amd: gradient of alpha {tuple(A.shape)}: expected {(g.nnz, H)}")
+        A = A.contiguous().float()
+        dev, f32 = t.device, torch.float32
+        rec = torch.empty(n, H, 4, dtype=f32, device=dev)
+        part = torch.empty(-(-g.nnz // 2048) * 5 * H * 3, dtype=f32, device=dev)
+        ds2 = torch.empty(n, H, dtype=f32, device=dev)
+        dt2 = torch.empty(n, H, dtype=f32, device=dev)
+        f, b = g.fwd, g.bwd
+        with _span("k14_alpha_rows"):
+            check(lib.pygat_alpha_grad_rows(f.n, f.nnz, f.rowptr.data_ptr(), f.edge_rc.data_ptr(), _ptr(self.to_internal), H, self.Fo,
+                                            float(slope), s.data_ptr(), t.data_ptr(), m.data_ptr(), Z.data_ptr(), A.data_ptr(),
+                                            rec.data_ptr(), ds2.data_ptr(), part.data_ptr(), st), "alpha_grad_rows")
+        with _span("k14_alpha_cols"):
+            check(lib.pygat_alpha_grad_cols(b.n, b.nnz, b.rowptr.data_ptr(), b.edge_rc.data_ptr(), g.perm_t.data_ptr(),
+                                            _ptr(self.to_internal), H, self.Fo, float(slope), t.data_ptr(), rec.data_ptr(), A.data_ptr(),
+                                            dt2.data_ptr(), part.data_ptr(), st), "alpha_grad_cols")
+        return ds2, dt2
+
+
+def alpha_grad_scores(graph: CSRGraph, s, t, m, Z, A, slope: float, Fo: int, to_internal=None):
+    """Just the two passes of csrc/k14_alpha_grad.hip: node tables s, t, m, Z [N, H] (float32, the level's node order), A [E, H] =
+    dL/d alpha in the edge order of `graph` -> (ds', dt') [N, H], the score gradients a loss on alpha adds to a level's backward."""
+    with torch.cuda.device(t.device):
+        return AlphaGradState(graph, t.contiguous(), to_internal, Fo).scores(A, s.contiguous(), m.contiguous(), Z.contiguous(), slope,
+                                                                         _stream())
 
 
 class StackHeads(torch.autograd.Function):
@@ -843,19 +926,33 @@ def stack_heads(Ws, As, Wskips):
 
 def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
               Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, pipeline=None, xs=None,
-              return_attention: bool = False, attention_order=None):
+              return_attention=False, attention_order=None):
     """All heads of one level. Ws: H tensors [Fin,F']; As: H tensors with 2F' elements
     ([2F',1] as in GraphAttentionLayer, layers.py:23, or [1,2F'] as in SpGraphAttentionLayer,
     layers.py:114); Wskips: H tensors [Fin,F'] or None.  pipeline: see GATLevelFn.  xs: features.SparseFeatures of x
     (a first level on sparse input features) or None.
     return_attention: -> (out, alpha), alpha [E, H] float32 (detached) = the softmax coefficient of every edge and head, in
-    the edge order of `graph` (graph.edge_index()); attention_order: see AttentionTarget."""
+    the edge order of `graph` (graph.edge_index()); attention_order: see AttentionTarget.
+    return_attention="grad": the same alpha as a second DIFFERENTIABLE output of the level -- a loss may use out, alpha or both
+    (csrc/k14_alpha_grad.hip); a loss on `out` alone runs the backward it runs without it."""
     H = len(Ws)
     if return_attention and pipeline is not None:
         raise ValueError("pygat_amd: return_attention does not take a pipeline")
-    att = AttentionTarget(graph, H, x.device, attention_order) if return_attention else None
+    grad = attention_mode(return_attention)
+    att = AttentionTarget(graph, H, x.device, attention_order, grad=grad) if return_attention else None
     out = _gat_level(x, graph, Ws, As, Wskips, alpha, concat, pipeline, xs, att)
+    if grad:
+        return out           # (out, alpha): both outputs of the level's autograd node
     return (out, att.alpha) if return_attention else out
+
+
+def attention_mode(return_attention) -> bool:
+    """return_attention: False / True (detached coefficients) / "grad" (differentiable) -> is it "grad"?"""
+    if isinstance(return_attention, str):
+        if return_attention != "grad":
+            raise ValueError(f"pygat_amd: return_attention={return_attention!r}: expected False, True or \"grad\"")
+        return True
+    return False
 
 
 def _gat_level(x, graph, Ws, As, Wskips, alpha, concat, pipeline, xs, att):

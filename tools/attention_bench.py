@@ -4,6 +4,11 @@ bench.py times): the no-grad forward of the v1 level and of the GATv2 level with
 alternating pairs (one pair = one forward without, one with; each timed over --reps calls).  Prints one JSON line per level kind.
 
     python tools/attention_bench.py [--pairs 7] [--reps 10] [--kinds v1,v2]
+    python tools/attention_bench.py --grad-legs [--iters 50] [--warmup 10] [--out FILE]
+        (training step of the v1 level, forward + backward, with return_attention False / True / "grad" -- the last with a loss on
+        both outputs -- interleaved iteration by iteration, one device-event pair per step, medians; then the HIP-event spans of
+        the K14 launches and of K4 from the same process, K14 against its byte model, and the new kernels' register / scratch
+        footprint.  One JSON object.)
     rocprofv3 --kernel-trace --stats -d DIR -o att -- python tools/attention_bench.py --profile
         (--profile: a few forwards with the attention, no timing -- the kernel table gives the k13 launches' time; the byte model
         below turns it into a fraction of the 8 TB/s roof: python tools/attention_bench.py --roof DIR)
@@ -12,7 +17,11 @@ Byte model of the attention pass (csrc/k13_attention.hip; what an edge must move
 row-local reads -- s, m, Z, the rowptr pair, GATv2's Whi row -- and nothing else):
   v1: per edge (row, col) 8 B + two map entries 8 B + the t_j gather 4H + the coefficients 4H;  the t stream: every row before the
       self-loop-only tail reads its Wh row (4R) and writes t (4H).
-  v2: per edge 8 + 8 + the Whj_j gather 4R + the coefficients 4H;  Whi rows 4R once per row."""
+  v2: per edge 8 + 8 + the Whj_j gather 4R + the coefficients 4H;  Whi rows 4R once per row.
+Byte model of the alpha-gradient passes (csrc/k14_alpha_grad.hip), N' = rows of more than one edge:
+  rows: per edge (row, col) 8 + A 4H + the t_j gather 4H;  per row of N' its (s, m, Z) 12H in, the record 16H and ds' 4H out, less
+        the 8H the issue's model leaves to caches = 24H;  cols: per edge 8 + A through perm_t 4H + the record gather 16H; dt' 4H per
+        node;  the long-row scan of each pass reads every (row, col) pair once more, 8 B per edge, and the rowptr pair of each row."""
 import argparse
 import glob
 import json
@@ -113,6 +122,86 @@ def roof(d, args):
     print(json.dumps(out))
 
 
+def alpha_grad_model(n, E, H, n_multi):
+    rows = E * (8 + 4 * H + 4 * H) + n_multi * (16 * H + 8 * H)
+    cols = E * (8 + 4 * H + 16 * H) + n * 4 * H
+    scan = E * 8 + n * 8
+    return {"rows": rows + scan, "cols": cols + scan}
+
+
+def grad_legs(args):
+    """fwd + bwd of the v1 level at config 5 with return_attention False (a) / True (b) / "grad" and a loss on both outputs (c)."""
+    import ctypes as C
+    import torch
+    import pygat_amd as pg
+    from pygat_amd import ops
+    from pygat_amd._lib import lib
+    graph, X, P1, _ = setup(args)
+    Ws = [w.clone().requires_grad_(True) for w in P1[0]]
+    As = [v.clone().requires_grad_(True) for v in P1[1]]
+    H = args.heads
+    gen = torch.Generator(device=X.device).manual_seed(3)
+    G = torch.randn(graph.n, H * args.fout, generator=gen, device=X.device)
+    A = torch.randn(graph.nnz, H, generator=gen, device=X.device)
+
+    def step(mode):
+        for p in Ws + As:
+            p.grad = None
+        r = pg.gat_level(X, graph, Ws, As, None, 0.2, True, return_attention=mode)
+        if mode == "grad":
+            torch.autograd.backward([r[0], r[1]], [G, A])
+        else:
+            (r[0] if mode else r).backward(G)
+
+    legs = {"a_false": False, "b_true": True, "c_grad": "grad"}
+    for _ in range(max(10, args.warmup)):
+        for m in legs.values():
+            step(m)
+    torch.cuda.synchronize()
+    iters = max(50, args.iters)
+    ev = {k: [] for k in legs}
+    for _ in range(iters):
+        for k, m in legs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); step(m); b.record()
+            ev[k].append((a, b))
+    torch.cuda.synchronize()
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    out = {"graph": {"n": graph.n, "E": graph.nnz}, "heads": H, "fout": args.fout, "fin": args.fin, "iters": iters,
+           "warmup": max(10, args.warmup), "step_ms_median": {k: round(med([a.elapsed_time(b) for a, b in v]), 4) for k, v in ev.items()}}
+    sm = out["step_ms_median"]
+    out["true_minus_false_ms"] = round(sm["b_true"] - sm["a_false"], 4)
+    out["grad_minus_true_ms"] = round(sm["c_grad"] - sm["b_true"], 4)
+    # kernel spans of leg (c), same process: HIP events around the launches (ops.KernelTimer)
+    ops.TIMER = ops.KernelTimer()
+    for _ in range(iters):
+        step("grad")
+    torch.cuda.synchronize()
+    spans = {k: round(med(v) * 1e3, 1) for k, v in ops.TIMER.times_ms().items()}
+    ops.TIMER = None
+    out["span_us_median"] = spans
+    import numpy as np
+    deg = np.diff(graph.fwd.rowptr.cpu().numpy())
+    model = alpha_grad_model(graph.n, graph.nnz, H, int((deg > 1).sum()))
+    out["k14"] = {}
+    for key, span in (("rows", "k14_alpha_rows"), ("cols", "k14_alpha_cols")):
+        us = spans.get(span)
+        out["k14"][key] = {"us": us, "model_bytes": model[key], "roof_us": round(model[key] / ROOF * 1e6, 1),
+                           "roof_fraction": None if not us else round(model[key] / ROOF * 1e6 / us, 3)}
+    out["k14"]["apply_and_da_us"] = spans.get("k14_alpha_apply")
+    out["k4_backward_col_us"] = spans.get("k4_backward_col")
+    out["footprint"] = {}
+    for name in ("k14_rows_long", "k14_cols_long", "k14_rows_wave", "k14_cols_wave", "k14_apply"):
+        regs, scratch = C.c_int(-1), C.c_int(-1)
+        rc = lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch))
+        out["footprint"][name] = {"regs": regs.value, "scratch_bytes": scratch.value} if rc == 0 else lib.pygat_last_error().decode()
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(txt + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=7)
@@ -125,9 +214,14 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-calls", type=int, default=5)
     ap.add_argument("--roof", metavar="DIR")
+    ap.add_argument("--grad-legs", action="store_true")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out", metavar="FILE")
     args = ap.parse_args()
     if args.roof:
         return roof(args.roof, args)
+    if args.grad_legs:
+        return grad_legs(args)
     import torch
     graph, X, P1, P2 = setup(args)
     with torch.no_grad():
