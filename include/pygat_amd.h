@@ -359,6 +359,29 @@ int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, 
                            const float* att_mask, const float* ds,
                            float* dWh, float* dt, float* dz_t, void* part, float* da_part, int h_first, int h_count,
                            int head_group, void* stream);
+/* The two launches of pygat_gat_backward_col one by one (additive under ABI 16): phase = 0 (both: pygat_gat_backward_col),
+ * PYGAT_F_MAIN_ONLY (the walk over the slots: rows that lie inside a slot are final after it, the pieces of cut rows are in
+ * `part`) or PYGAT_F_FIXUP_ONLY (finishes the cut rows from `part`).  A single phase needs the level in one head window with
+ * a list-driven fix-up: pygat_gat_backward_col_phases_ok(gT, H, F', head_group) == 1 (a graph with a cut-row list and no
+ * slot_order; 0: not supported, negative: a bad graph or shape).  Same arguments as pygat_gat_backward_col otherwise. */
+int pygat_gat_backward_col_phases_ok(const pygat_graph* gT, int H, int Fo, int head_group);
+int pygat_gat_backward_col_phase(const pygat_graph* gT, const int32_t* perm_t, int H, int Fo, float alpha,
+                                 const float* Wh, const float* a_pad, const float* GR,
+                                 const float* att_mask, const float* ds,
+                                 float* dWh, float* dt, float* dz_t, void* part, float* da_part, int h_first, int h_count,
+                                 int head_group, int phase, void* stream);
+/* The fix-up phase and the backward stream of the self-loop-only tail (pygat_gat_backward_tail, below) in ONE launch, after
+ * pygat_gat_backward_col_phase(..., PYGAT_F_MAIN_ONLY) over the slot prefix gT: the leading work-groups finish the cut rows
+ * from `part` (dWh_j, dt_j; ds is read for the ds_j a_src term), the ones behind them stream the rows [row_first, row_first +
+ * n_rows): dWh_j = G_u ELU'(y_u) with u = user_row[j] (NULL: j), ds_j = dt_j = 0.  The two write disjoint rows (every cut row
+ * lies before the tail) and neither reads what the other writes: no work-group waits for another, and each value is formed
+ * exactly as by the two launches it replaces.  The fix-up is a few hundred latency-bound work-groups: resident beside the
+ * stream they cost the step nothing, as a launch of their own they own a place in the sequence.  Needs
+ * pygat_gat_backward_col_phases_ok == 1, a concat level without a skip projection, ds != NULL (the row-local backward);
+ * flags: PYGAT_F_ELU or 0. */
+int pygat_gat_backward_col_finish(const pygat_graph* gT, int H, int Fo, const float* a_pad, float* ds, float* dWh, float* dt,
+                                  void* part, int head_group, int row_first, int n_rows, int flags, const float* G,
+                                  const float* y, const int32_t* user_row, void* stream);
 /* da [H x 2F'] from the records of a column pass that ran with da_part, plus the rows of gT's cut-row list (their ds, dt
  * and Wh rows are read here).  Same gT / head_group as that pass; ws >= pygat_agrad_workspace_bytes(H, F').  Fixed
  * summation order, no atomics: bitwise reproducible. */

@@ -39,6 +39,7 @@ SYMBOLS = [
     "pygat_edge_pairs", "pygat_slot_bounds", "pygat_slot_meta", "pygat_partials_bytes", "pygat_head_group", "pygat_gat_forward", "pygat_gat_forward_phases_ok", "pygat_gat_forward_tail", "pygat_gat_backward_col_tail", "pygat_gat_backward_tail", "pygat_project_tail_blocked", "pygat_head_mean",
     "pygat_gat_backward_prepare", "pygat_gat_backward_row", "pygat_gat_backward_col", "pygat_gat_backward_rowsum",
     "pygat_gat_backward_col_da_bytes", "pygat_a_grad_fold",
+    "pygat_gat_backward_col_phases_ok", "pygat_gat_backward_col_phase", "pygat_gat_backward_col_finish",
     "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
     "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
     "pygat_gat_attention", "pygat_gatv2_attention",
@@ -129,6 +130,9 @@ def _load():
     lib.pygat_gat_backward_col.argtypes = [C.POINTER(Graph), p, i, i, f, p, p, p, p, p, p, p, p, p, p, i, i, i, p]
     lib.pygat_gat_backward_col_da_bytes.argtypes = [C.POINTER(Graph), i, i, i]
     lib.pygat_gat_backward_col_da_bytes.restype = sz
+    lib.pygat_gat_backward_col_phases_ok.argtypes = [C.POINTER(Graph), i, i, i]
+    lib.pygat_gat_backward_col_phase.argtypes = [C.POINTER(Graph), p, i, i, f, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]
+    lib.pygat_gat_backward_col_finish.argtypes = [C.POINTER(Graph), i, i, p, p, p, p, p, i, i, i, i, p, p, p, p]
     lib.pygat_a_grad_fold.argtypes = [C.POINTER(Graph), i, i, p, p, p, p, p, p, i, p]
     lib.pygat_gat_backward_rowsum.argtypes = [C.POINTER(Graph), p, i, i, p, p, p, i, i, p]
     lib.pygat_agrad_workspace_bytes.argtypes = [i, i]

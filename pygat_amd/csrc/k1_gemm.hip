@@ -345,12 +345,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 // 64 consecutive output elements: wave q sums slabs q, q+8, ... in order (256-B coalesced reads,
 // unrolled so several are in flight), then the 8 partial sums are added in wave order -- the same
 // association on every run.
-__global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(int M, int N, int splits,
-                                                                 const float* __restrict__ ws,
-                                                                 pygat_out_segments out, int accumulate) {
-  const int64_t tot = (int64_t)M * N;
+__device__ __forceinline__ float splitk_sum(int64_t tot, int splits, const float* __restrict__ ws, int64_t i) {
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * 64 + lane;
   float v = 0.f;
   if (i < tot) {
     int z = q;
@@ -364,16 +360,42 @@ __global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(int M, int N, i
   __shared__ float sm[8][64];
   sm[q][lane] = v;
   __syncthreads();
+  float acc = 0.f;
   if (q == 0 && i < tot) {
-    float acc = 0.f;
 #pragma unroll
     for (int z = 0; z < 8; ++z) acc += sm[z][lane];
+  }
+  return acc;   // (the sum in wave 0, for i < tot)
+}
+
+__global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(int M, int N, int splits,
+                                                                 const float* __restrict__ ws,
+                                                                 pygat_out_segments out, int accumulate) {
+  const int64_t tot = (int64_t)M * N;
+  const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const float acc = splitk_sum(tot, splits, ws, i);
+  if ((threadIdx.x >> 6) == 0 && i < tot) {
     const int row = (int)(i / N), col = (int)(i % N);
     int s = 0;
     for (int k = 1; k < out.nseg; ++k)
       if (col >= out.col_start[k]) s = k;
     float* p = out.ptr[s] + (int64_t)row * out.ld[s] + (col - out.col_start[s]);
     if (accumulate) *p += acc; else *p = acc;
+  }
+}
+
+// The weight gradient's reduce: the same sums, stored straight into the per-head layout dW [H x Fin x F'] (column h Fp + f of
+// row k -> dW[h][k][f]; the padding columns f >= F' are dropped) -- no packed [Fin x R] copy and no unpack launch behind it.
+__global__ __launch_bounds__(512) void wgrad_splitk_reduce_kernel(int Fin, int H, int Fo, int Fp, int splits,
+                                                                  const float* __restrict__ ws, float* __restrict__ dW) {
+  const int N = H * Fp;
+  const int64_t tot = (int64_t)Fin * N;
+  const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const float acc = splitk_sum(tot, splits, ws, i);
+  if ((threadIdx.x >> 6) == 0 && i < tot) {
+    const int k = (int)(i / N), col = (int)(i % N);
+    const int h = col / Fp, f = col % Fp;
+    if (f < Fo) dW[((int64_t)h * Fin + k) * Fo + f] = acc;
   }
 }
 
@@ -881,6 +903,16 @@ extern "C" int pygat_wgrad_blocked(int n, int Fin, int H, int Fo, const float* X
                          (const float*)slabs, seg, 0);
       PYGAT_CHECK_LAUNCH("wgrad(reduce)");
       done = true;
+    }
+  }
+  if (!blocked && !done && !ds && split_k > 1) {    // plain X^T dWh on the streamed-K kernel: its reduce writes dW itself
+    const int r = try_gemm_tn_stream(Fin, R, n, X, ldx, dWh, ldd, split_k, slabs, split, st, R, nullptr, 0);
+    if (r < 0) return r;
+    if (r >= 1) {
+      hipLaunchKernelGGL(wgrad_splitk_reduce_kernel, dim3((unsigned)cdiv((int64_t)Fin * R, 64)), dim3(512), 0, st, Fin, H, Fo, Fp, r,
+                         (const float*)slabs, dW);
+      PYGAT_CHECK_LAUNCH("wgrad(reduce)");
+      return PYGAT_OK;
     }
   }
   if (!done) {                                      // any shape: the general path, once per operand

@@ -11,6 +11,7 @@
 // per-edge buffer through the edge permutation.  ds comes from K3b.  Rows cut by a slot border go
 // through `part` + a fix-up launch (fixed order).  No atomics.
 #include "attn_common.h"
+#include "tail_stream.h"
 
 namespace pygat {
 
@@ -405,18 +406,19 @@ __global__ __launch_bounds__(256) void gat_bwd_col_fixup_kernel(ColArgs a) {
 
 // list-driven variant: entry q of g.cut = (owner slot k, row, pieces); the first n_cut_wide entries (long
 // chains) get a whole work-group each, the others one wave each.
+// (the body, for work-group `bid` of the fix-up's grid: also run by the leading work-groups of gat_bwd_col_finish_kernel)
 template <int LPR, int VEC>
-__global__ __launch_bounds__(64 * FIX_LIST_WAVES) void gat_bwd_col_fixup_list_kernel(ColArgs a) {
+__device__ __forceinline__ void col_fixup_list_body(const ColArgs& a, const int bid) {
   constexpr int EPW = 64 / LPR;
   constexpr int PF = (VEC == 1) ? 4 : 2;
   constexpr int RPW = fix_rows_per_wave(LPR), GP = EPW / RPW;   // packed entries: RPW rows per wave, GP lane groups each
   extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [FIX_LIST_WAVES][R + 2H]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const bool wide = (int)blockIdx.x < a.g.n_cut_wide;   // (block-uniform)
+  const bool wide = bid < a.g.n_cut_wide;   // (block-uniform)
   const int slot = lane / LPR;
   const int G = wide ? EPW : GP, g = slot % G;
-  const int q0 = wide ? (int)blockIdx.x
-                      : a.g.n_cut_wide + (((int)blockIdx.x - a.g.n_cut_wide) * FIX_LIST_WAVES + w) * RPW + slot / GP;
+  const int q0 = wide ? bid
+                      : a.g.n_cut_wide + ((bid - a.g.n_cut_wide) * FIX_LIST_WAVES + w) * RPW + slot / GP;
   const bool have = q0 < a.g.n_cut;
   const int qe = have ? q0 : a.g.n_cut - 1;
   const int64_t k = a.g.cut[3 * qe];
@@ -496,6 +498,34 @@ __global__ __launch_bounds__(64 * FIX_LIST_WAVES) void gat_bwd_col_fixup_list_ke
   if (wsel == 0 && g == 0 && npieces > 0) col_finish<VEC>(a, lc, r, acc, dt);
 }
 
+template <int LPR, int VEC>
+__global__ __launch_bounds__(64 * FIX_LIST_WAVES) void gat_bwd_col_fixup_list_kernel(ColArgs a) {
+  col_fixup_list_body<LPR, VEC>(a, (int)blockIdx.x);
+}
+
+// The fix-up and the backward stream of the self-loop-only tail (tail_stream.h) in ONE launch: work-groups [0, fix_blocks)
+// are the list-driven fix-up's, the ones behind them stream the tail, one 16-byte chunk per thread.  The branch is
+// block-uniform and no work-group waits for another: the two bodies write disjoint rows of dWh, ds and dt (cut rows lie
+// before the tail, whose rows have one edge each), and neither reads what the other writes.  The fix-up is latency per wave
+// (a few hundred work-groups, a chain of dependent loads each), the stream is bytes: dispatched first, the fix-up's
+// work-groups are resident while the stream runs, instead of owning a place in the launch sequence.
+struct ColTailArgs {
+  int row_first, n_rows, Fo, flags;
+  const float* G;
+  const float* y;
+  const int32_t* urow;
+  float* ds;
+};
+template <int LPR, int VEC>
+__global__ __launch_bounds__(64 * FIX_LIST_WAVES) void gat_bwd_col_finish_kernel(ColArgs a, ColTailArgs t, int fix_blocks) {
+  if ((int)blockIdx.x < fix_blocks) {   // (block-uniform)
+    col_fixup_list_body<LPR, VEC>(a, (int)blockIdx.x);
+  } else {
+    bwd_tail_item(((int64_t)blockIdx.x - fix_blocks) * (64 * FIX_LIST_WAVES) + threadIdx.x, t.row_first, t.n_rows, a.rs.H, t.Fo,
+                  a.rs.Fp, t.flags, t.G, t.y, t.urow, a.dWh, a.rs.ldr, 0, t.ds, a.dt);
+  }
+}
+
 
 }  // namespace pygat
 
@@ -528,11 +558,11 @@ extern "C" size_t pygat_gat_backward_col_da_bytes(const pygat_graph* gT, int H, 
   return (size_t)col_da_blocks(g, H, Fp, head_group_arg(head_group, g.n, H, Fp), nullptr) * 2 * (size_t)H * Fp * sizeof(float);
 }
 
-extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, int Fo, float alpha,
-                                      const float* Wh, const float* a_pad, const float* GR,
-                                      const float* att_mask, const float* ds, float* dWh, float* dt, float* dz_t,
-                                      void* part, float* da_part, int h_first, int h_count, int head_group, void* stream) {
-
+// phase: 0 = both launches, PYGAT_F_MAIN_ONLY / PYGAT_F_FIXUP_ONLY = one of them (pygat_gat_backward_col_phase)
+static int backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, int Fo, float alpha,
+                        const float* Wh, const float* a_pad, const float* GR,
+                        const float* att_mask, const float* ds, float* dWh, float* dt, float* dz_t,
+                        void* part, float* da_part, int h_first, int h_count, int head_group, int phase, void* stream) {
   ColArgs a;
   int rc = check_graph(gT, &a.g, 2);
   if (rc) return rc;
@@ -548,6 +578,11 @@ extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm
                 "gat_backward_col: row tables must be 16-byte aligned");
   const int hg = head_group_arg(head_group, a.g.n, rg.hr, Fp);
   PYGAT_REQUIRE(hg > 0, "gat_backward_col: head_group=%d gives rows of more than 1024 floats per pass", head_group);
+  PYGAT_REQUIRE(phase == 0 || phase == PYGAT_F_MAIN_ONLY || phase == PYGAT_F_FIXUP_ONLY,
+                "gat_backward_col: phase=%d (0, PYGAT_F_MAIN_ONLY or PYGAT_F_FIXUP_ONLY)", phase);
+  // (one phase: the partial records of ONE window must outlive the call -- the windows of a wider level share `part`)
+  PYGAT_REQUIRE(phase == 0 || hg >= rg.hr, "gat_backward_col: a single phase needs the level in one head window (pygat_gat_backward_col_phases_ok)");
+  const bool do_main = phase != PYGAT_F_FIXUP_ONLY, do_fix = phase != PYGAT_F_MAIN_ONLY;
   if (da_part) {
     PYGAT_REQUIRE(ds && rg.hr == H && aligned16(da_part) && col_da_blocks(a.g, H, Fp, hg, nullptr) > 0,
                   "gat_backward_col: da_part needs ds, 8 heads x 16 in one pass and a cut-row list "
@@ -572,7 +607,8 @@ extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm
     const unsigned bt = (vec == 1 && lpr <= 8) ? (unsigned)narrow_block() : 256u;
     const unsigned blocks = (unsigned)cdiv(cdiv(nslots, 64 / lpr), bt / 64);
     const size_t da_lds = da_part ? 2 * (size_t)bt * sizeof(float4) : 0;
-    if (dz_t) {
+    if (!do_main) {   // (the fix-up phase alone)
+    } else if (dz_t) {
       PYGAT_DISPATCH_LANES(lpr, vec,
                            hipLaunchKernelGGL((gat_bwd_col_kernel<LPR, VEC, true>), dim3(blocks), dim3(bt), 0, st, a));
     } else if (lpr == 32 && vec == 1 && a.rs.lph == 4) {   // 8 heads x 16: the headline shape
@@ -591,6 +627,7 @@ extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm
                            hipLaunchKernelGGL((gat_bwd_col_kernel<LPR, VEC, false>), dim3(blocks), dim3(bt), 0, st, a));
     }
     PYGAT_CHECK_LAUNCH("gat_backward_col");
+    if (!do_fix) continue;
     const size_t fix_lds = (a.g.cut ? FIX_LIST_WAVES : 4) * (size_t)(a.rs.R + 2 * a.rs.H) * sizeof(float);
     if (a.g.cut) {
       if (a.g.n_cut > 0) {
@@ -604,5 +641,69 @@ extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm
     }
     PYGAT_CHECK_LAUNCH("gat_backward_col_fixup");
   }
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_gat_backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, int Fo, float alpha,
+                                      const float* Wh, const float* a_pad, const float* GR,
+                                      const float* att_mask, const float* ds, float* dWh, float* dt, float* dz_t,
+                                      void* part, float* da_part, int h_first, int h_count, int head_group, void* stream) {
+  return backward_col(gT, perm_t, H, Fo, alpha, Wh, a_pad, GR, att_mask, ds, dWh, dt, dz_t, part, da_part, h_first, h_count, head_group,
+                      0, stream);
+}
+
+extern "C" int pygat_gat_backward_col_phase(const pygat_graph* gT, const int32_t* perm_t, int H, int Fo, float alpha,
+                                            const float* Wh, const float* a_pad, const float* GR,
+                                            const float* att_mask, const float* ds, float* dWh, float* dt, float* dz_t,
+                                            void* part, float* da_part, int h_first, int h_count, int head_group, int phase,
+                                            void* stream) {
+  return backward_col(gT, perm_t, H, Fo, alpha, Wh, a_pad, GR, att_mask, ds, dWh, dt, dz_t, part, da_part, h_first, h_count, head_group,
+                      phase, stream);
+}
+
+// 1: the column pass of all H heads over gT runs in one head window with a list-driven fix-up -- its two launches may be
+// asked for one by one (pygat_gat_backward_col_phase) and the fix-up may share a launch with the tail's stream
+// (pygat_gat_backward_col_finish); 0: it does not; negative: a bad graph or shape
+extern "C" int pygat_gat_backward_col_phases_ok(const pygat_graph* gT, int H, int Fo, int head_group) {
+  GraphDev g;
+  const int rc = check_graph(gT, &g, 2);
+  if (rc) return rc;
+  const int Fp = padded_width(Fo);
+  PYGAT_REQUIRE(H > 0 && Fp > 0, "gat_backward_col_phases_ok: unsupported H=%d F'=%d", H, Fo);
+  RowShape rs;
+  if (!g.cut || g.order || !make_window_shape(H, Fo, H, &rs)) return 0;
+  return head_group_arg(head_group, g.n, H, Fp) >= H ? 1 : 0;
+}
+
+extern "C" int pygat_gat_backward_col_finish(const pygat_graph* gT, int H, int Fo, const float* a_pad, float* ds, float* dWh,
+                                             float* dt, void* part, int head_group, int row_first, int n_rows, int flags,
+                                             const float* G, const float* y, const int32_t* user_row, void* stream) {
+  ColArgs a;
+  int rc = check_graph(gT, &a.g, 2);
+  if (rc) return rc;
+  const int Fp = padded_width(Fo);
+  PYGAT_REQUIRE(H > 0 && Fp > 0, "gat_backward_col_finish: unsupported H=%d F'=%d", H, Fo);
+  PYGAT_REQUIRE(pygat_gat_backward_col_phases_ok(gT, H, Fo, head_group) == 1,
+                "gat_backward_col_finish: needs a cut-row list, no slot_order and the level in one head window "
+                "(pygat_gat_backward_col_phases_ok)");
+  PYGAT_REQUIRE(a_pad && ds && dWh && dt && part && G && y, "gat_backward_col_finish: null pointer");
+  PYGAT_REQUIRE(row_first >= 0 && n_rows > 0 && (int64_t)row_first + n_rows <= a.g.n,
+                "gat_backward_col_finish: tail rows [%d, +%d) outside the %d nodes", row_first, n_rows, a.g.n);
+  PYGAT_REQUIRE(aligned16(dWh) && aligned16(a_pad) && aligned16(part) && (Fo != Fp || (aligned16(G) && aligned16(y))),
+                "gat_backward_col_finish: row tables must be 16-byte aligned");
+  PYGAT_REQUIRE(make_window_shape(H, Fo, H, &a.rs), "gat_backward_col_finish: unsupported H=%d F'=%d", H, Fo);
+  a.alpha = 0.f; a.perm = nullptr; a.mask = nullptr; a.Wh = nullptr; a.GR = nullptr; a.ldgr = 0; a.dz_t = nullptr; a.da_part = nullptr;
+  a.a_pad = a_pad; a.ds = ds; a.dWh = dWh; a.dt = dt; a.part = (float*)part;
+  ColTailArgs t;
+  t.row_first = row_first; t.n_rows = n_rows; t.Fo = Fo; t.flags = flags & PYGAT_F_ELU; t.G = G; t.y = y; t.urow = user_row; t.ds = ds;
+  int lpr, vec;
+  pick_lanes(a.rs, &lpr, &vec);
+  const int fb = a.g.n_cut > 0 ? (int)(a.g.n_cut_wide + cdiv(a.g.n_cut - a.g.n_cut_wide, FIX_LIST_WAVES * fix_rows_per_wave(lpr))) : 0;
+  const int64_t tb = cdiv((int64_t)n_rows * (a.rs.R / 4), 64 * FIX_LIST_WAVES);
+  PYGAT_REQUIRE(fb + tb < ((int64_t)1 << 31), "gat_backward_col_finish: grid too large");
+  const size_t fix_lds = FIX_LIST_WAVES * (size_t)(a.rs.R + 2 * a.rs.H) * sizeof(float);
+  PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_bwd_col_finish_kernel<LPR, VEC>), dim3((unsigned)(fb + tb)),
+                                                    dim3(64 * FIX_LIST_WAVES), fix_lds, (hipStream_t)stream, a, t, fb));
+  PYGAT_CHECK_LAUNCH("gat_backward_col_finish");
   return PYGAT_OK;
 }

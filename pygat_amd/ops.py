@@ -126,6 +126,12 @@ TAIL_MIN_SHARE = 0.05
 # rows are gathers at the caller's rows -- so the backward keeps its stream.)  TAIL_FUSED = False / PYGAT_TAIL_FUSED=0 keeps the
 # forward stream too.
 TAIL_FUSED = _config.tail_fused
+# The backward's tail stream and the column pass's cut-row fix-up in ONE launch (pygat_gat_backward_col_finish: the fix-up's
+# work-groups first, the stream's behind them; disjoint rows, no work-group waits for another, bitwise the two launches'
+# results), on tables of COL_FINISH_MIN_BYTES and more: there the fix-up is a launch of tens of microseconds of latency (some
+# ten thousand cut rows) that hides beside the stream.  Below it the level keeps the two launches -- a fix-up of a few
+# work-groups has nothing to hide, and the call sequence of small levels is what the tail tests pin.
+COL_FINISH_MIN_BYTES = 32 << 20
 
 
 def head_group(N: int, H: int, Fo: int) -> int:
@@ -554,11 +560,9 @@ def _level_forward(ctx, need, x, H, Fo, skip, pack, graph: CSRGraph, alpha: floa
         qneg = torch.empty(L.N, H, dtype=f32, device=dev) if flavour == "rowlocal" else None
         part = torch.empty(lib.pygat_partials_bytes(graph.nnz, L.ts, H, L.Fp) // 4, dtype=f32,
                            device=dev)
-        if fuse_fwd and m is not None:     # the tail's records as pygat_gat_forward_tail leaves them: m = 0, Z = 1, qneg = 0
-            m[tail[0]:].zero_()
-            Z[tail[0]:].fill_(1.0)
-            if qneg is not None:
-                qneg[tail[0]:].zero_()
+        # (fuse_fwd: the tail's rows of m, Z and qneg stay unwritten -- nothing reads them.  K3a runs on the rows before the
+        # tail (no skip projection: fused_tail in the backward), K4 and its fix-up take m / Z from the GR rows of the prefix
+        # nodes they gather, the a-gradient fold reads Wh / ds / dt of cut rows, and K13 / K14 skip rows of one edge.)
         chunks = [(graph.fwd.ref(L.ts) if tail is None else tail[1], 0, L.N if tail is None else tail[0])]
         if pipeline is not None and concat and pipeline[0] > 1:
             chunks = (graph.fwd.row_chunks(int(pipeline[0]), L.ts) if tail is None
@@ -670,7 +674,20 @@ def _level_backward(ctx, G, A=None):
                                                  ds.data_ptr() if rowlocal else None, hb, hr, hgw, _ptr(getattr(ctx, "user_row", None)), st),
                       "gat_backward_prepare")
         two_gather = ctx.flavour == "two-gather"
-        if rowlocal:        # ds is known: the column pass finishes dWh on its own
+        # the tail's stream in the launch of the column pass's fix-up (COL_FINISH_MIN_BYTES)
+        col_finish = (rowlocal and fused_tail and not ranged and L.N * L.R * 4 >= COL_FINISH_MIN_BYTES
+                      and lib.pygat_gat_backward_col_phases_ok(gT, H, Fo, hgw) == 1)
+        if col_finish:
+            with _span("k4_backward_col"):
+                check(lib.pygat_gat_backward_col_phase(gT, None, H, Fo, ctx.alpha, Wh.data_ptr(),
+                                                       a_pad.data_ptr(), GR.data_ptr(), None, ds.data_ptr(),
+                                                       dWh.data_ptr(), dt.data_ptr(), None, part.data_ptr(), _ptr(da_part), hb, hr, hgw,
+                                                       _lib.F_MAIN_ONLY, st), "gat_backward_col_phase")
+                check(lib.pygat_gat_backward_col_finish(gT, H, Fo, a_pad.data_ptr(), ds.data_ptr(), dWh.data_ptr(), dt.data_ptr(),
+                                                        part.data_ptr(), hgw, tail[0], L.N - tail[0], ctx.flags, G.data_ptr(),
+                                                        y.data_ptr(), _ptr(getattr(ctx, "user_row", None)), st),
+                      "gat_backward_col_finish")
+        elif rowlocal:        # ds is known: the column pass finishes dWh on its own
             with _span("k4_backward_col"):
                 check(lib.pygat_gat_backward_col(gT, None, H, Fo, ctx.alpha, Wh.data_ptr(),
                                                  a_pad.data_ptr(), GR.data_ptr(), None, ds.data_ptr(),
