@@ -522,6 +522,38 @@ int pygat_alpha_grad_cols(int n, int64_t nnz, const int32_t* rowptr_t, const int
 int pygat_alpha_grad_apply(int n_rows, int H, int Fo, const float* a_pad, const float* ds2, const float* dt2, float* dWh,
                            void* stream);
 
+/* ------------------------------------------------ K15: a per-edge logit term for the GAT level (csrc/k15_edge_logit.hip)
+ * Additive under ABI 16 (no existing entry point changes).  u [nnz x H] in the CALLER's edge order (row k = edge k of
+ * rowptr / edge_rc) enters the score in front of the LeakyReLU:
+ *   z_ij = (s_i + t_j) + u_ij,  att_ij = softmax_j LeakyReLU(z_ij),  h'_i = sum_j att_ij Wh_j.
+ *   forward   hattn [n x R] = h' (padded heads, pad columns 0), m, Z [n x H]; with PYGAT_F_ELU (a concat level) also
+ *             out [n x H*F'] = ELU(h' (+ sk with PYGAT_F_SKIP)); a head-mean level runs pygat_head_mean(hattn, sk) afterwards.
+ *             Online softmax in edge order.  A row of at most one edge gets (m, Z) = (0, 0): the mark every later pass tests.
+ *   attention att [nnz x H] from (s, t, m, Z, u), one coefficient per edge and head; a marked row gets exactly 1.0.
+ *   rows      Gp [n x R] = dL/d(h' + skip) (through the ELU from the saved output y with PYGAT_F_ELU, else G [n x F'] / H),
+ *             D_i = Gp_i . h'_i, du_ij = l_ij att_ij (Gp_i . Wh_j - D_i) [nnz x H] = dL/du, ds_i = sum_j du_ij [n x H].
+ *   cols      over the transposed pattern (rowptr_t, edge_rc_t = (j, i) per transposed edge, whose u / du row is perm_t[k]; a
+ *             symmetric pattern passes its forward arrays): dt_j = sum_i du_ij, dWh_j = sum_i att_ij Gp_i + ds_j a_src + dt_j a_dst.
+ * s, t [n x H] = Wh . a_src, Wh . a_dst (pygat_attn_scores); Wh [n x R] as the projection left it; all tables in the caller's node
+ * order.  A row of exactly one edge has att = 1: its rows of u are never read and its du is exactly 0.  u_rows = rows of u (and
+ * of att / du): it must equal nnz.  R = H * padded F' <= 1024.  ws >= the size pygat_gat_edge_workspace_bytes reports, 16-byte
+ * aligned, the caller's (the three walking passes may share it): partial records of the rows (columns) of more than 512
+ * edges, one per 2048-edge chunk, merged in chunk order.  No float atomics: bitwise reproducible.  alpha = the LeakyReLU slope. */
+int pygat_gat_edge_workspace_bytes(int64_t nnz, int H, int Fo, size_t* bytes);   /* an error code like the launchers: bad sizes are refused */
+int pygat_gat_edge_forward(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, int H, int Fo, float alpha,
+                           int flags, const float* Wh, const float* s, const float* t, const float* sk, const float* u,
+                           int64_t u_rows, float* out, float* hattn, float* m, float* Z, void* ws, void* stream);
+int pygat_gat_edge_alpha(int n, int64_t nnz, const int32_t* edge_rc, int H, float alpha, const float* s, const float* t,
+                             const float* m, const float* Z, const float* u, int64_t u_rows, float* att, void* stream);
+int pygat_gat_edge_backward_rows(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, int H, int Fo, float alpha,
+                                 int flags, const float* Wh, const float* s, const float* t, const float* m, const float* Z,
+                                 const float* u, int64_t u_rows, const float* G, const float* y, const float* hattn,
+                                 float* Gp, float* du, float* ds, void* ws, void* stream);
+int pygat_gat_edge_backward_cols(int n, int64_t nnz, const int32_t* rowptr_t, const int32_t* edge_rc_t, const int32_t* perm_t,
+                                 int H, int Fo, float alpha, const float* s, const float* t, const float* m, const float* Z,
+                                 const float* u, int64_t u_rows, const float* Gp, const float* du, const float* ds,
+                                 const float* a_pad, float* dt, float* dWh, void* ws, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

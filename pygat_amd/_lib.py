@@ -44,6 +44,8 @@ SYMBOLS = [
     "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
     "pygat_gat_attention", "pygat_gatv2_attention",
     "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
+    "pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
+    "pygat_gat_edge_backward_cols",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -52,7 +54,6 @@ SYMBOLS = [
     "pygat_nll_workspace_bytes", "pygat_elu_logsoftmax_nll", "pygat_elu_logsoftmax_nll_backward",
     "pygat_project_sparse", "pygat_wgrad_sparse", "pygat_wgrad_sparse_workspace_bytes", "pygat_dropout_narrow", "pygat_dx_dropout", "pygat_adam_step", "pygat_bce_workspace_bytes", "pygat_bce_with_logits", "pygat_bce_with_logits_backward",
 ]
-
 
 MAX_ADAM_TENSORS = 48    # PYGAT_ADAM_MAX_TENSORS
 MAX_SEGMENTS = 4    # PYGAT_MAX_SEGMENTS
@@ -148,6 +149,11 @@ def _load():
     lib.pygat_alpha_grad_rows.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p]
     lib.pygat_alpha_grad_cols.argtypes = [i, i64, p, p, p, p, i, i, f, p, p, p, p, p, p]
     lib.pygat_alpha_grad_apply.argtypes = [i, i, i, p, p, p, p, p]
+    lib.pygat_gat_edge_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
+    lib.pygat_gat_edge_forward.argtypes = [i, i64, p, p, i, i, f, i, p, p, p, p, p, i64, p, p, p, p, p, p]
+    lib.pygat_gat_edge_alpha.argtypes = [i, i64, p, i, f, p, p, p, p, p, i64, p, p]
+    lib.pygat_gat_edge_backward_rows.argtypes = [i, i64, p, p, i, i, f, i, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
+    lib.pygat_gat_edge_backward_cols.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
@@ -202,6 +208,13 @@ def check(rc: int, what: str = "") -> None:
     if rc == -1:
         raise ValueError(f"pygat_amd {what}: {msg}")
     raise RuntimeError(f"pygat_amd {what}: {msg} (code {rc})")
+
+
+def edge_workspace_bytes(nnz: int, H: int, f_out: int) -> int:
+    """Scratch of the edge-logit passes (pygat_gat_edge_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_gat_edge_workspace_bytes(int(nnz), int(H), int(f_out), C.byref(n)), "gat_edge_workspace_bytes")
+    return n.value
 
 
 def padded_width(f_out: int) -> int:

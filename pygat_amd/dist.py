@@ -233,8 +233,10 @@ class AllReduceSum(torch.autograd.Function):
 
 
 def gat_level_head_parallel(x, graph, Ws, As, Wskips, alpha: float, concat: bool, dropout: float = 0.0,
-                            level_fn: Optional[Callable] = None, return_attention: bool = False) -> torch.Tensor:
+                            level_fn: Optional[Callable] = None, return_attention: bool = False, edge_logit=None) -> torch.Tensor:
     """One level with its heads sharded over the ranks; returns the full (replicated) output."""
+    if edge_logit is not None:
+        raise ValueError("pygat_amd: head_parallel does not take edge_logit; run the level on one device (ops.gat_level)")
     if return_attention:
         raise ValueError("pygat_amd: return_attention does not take head_parallel=True; run the level on one device")
     rank, world = _world()

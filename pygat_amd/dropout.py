@@ -345,12 +345,13 @@ def _backward_bits(ctx, x, bits, Wcat, dWh, GR, RW, st):
 def gat_level_dropout(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                       Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, p: float,
                       head_mean: bool = False, masks: Optional[dict] = None, generator=None, xs=None,
-                      return_attention=False):
+                      return_attention=False, edge_logit=None):
     """One level in training mode with dropout p.  `masks` (tests) = {"x","wh","att"} pre-scaled; without them the
     masks are drawn in-kernel from one int64 seed taken from torch's (graph-safe) generator.
     return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level: after the x and Wh masks, before the attention
     mask (layers.py:132-153), so every row sums to 1.  return_attention="grad": alpha is a second differentiable output, as
     for ops.gat_level; its gradient flows back through the Wh mask and the x masks like dWh does."""
+    ops.no_edge_logit(edge_logit, "the dropout level (gat_level_dropout)")
     del head_mean  # implied by `concat` (models.py:23): concat=False <=> last level <=> head mean
     grad = ops.attention_mode(return_attention)
     att = ops.AttentionTarget(graph, len(Ws), x.device, grad=grad) if return_attention else None

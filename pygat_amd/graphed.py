@@ -106,8 +106,11 @@ class GraphedLevel:
 
     # -- without autograd: the two replays as plain calls (bench.py, pipelines that own their buffers)
     @torch.no_grad()
-    def forward(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False) -> torch.Tensor:
+    def forward(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False, edge_logit=None) -> torch.Tensor:
         """Replay the forward; returns the static output buffer.  None = keep the static input as it is."""
+        if edge_logit is not None:
+            raise ValueError("pygat_amd: GraphedLevel does not take edge_logit (its captured graph holds the plain level); call "
+                             "gat_level eagerly")
         _no_attention(return_attention, "GraphedLevel")
         for dst, src in zip(self.inputs, [x, W, a] + ([Wskip] if self.Wskip is not None else [])):
             if src is not None and dst.data_ptr() != src.data_ptr():

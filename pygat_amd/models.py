@@ -48,10 +48,23 @@ class GAT(nn.Module):
         self._kind = ("v1" if issubclass(layer_type, (GraphAttentionLayer, SpGraphAttentionLayer))
                       else "v2sp" if issubclass(layer_type, SpGraphAttentionLayerV2) else "other")
 
-    def forward(self, x, adj, return_attention=False):
+    def forward(self, x, adj, return_attention=False, edge_logits=None):
         """return_attention: -> (out, [alpha_1, ..., alpha_L]), alpha_l [E, H_l] (detached) in the edge order of
         as_graph(adj) (its edge_index()), whatever node order the levels ran in.  return_attention="grad": every alpha_l is a
-        differentiable output of its level (ops.gat_level; the v1 layers only)."""
+        differentiable output of its level (ops.gat_level; the v1 layers only).
+        edge_logits: one entry per level, a tensor u_l [E, H_l] / [E, 1] / [E] or None: the per-edge logit term of that level
+        (ops.gat_level(..., edge_logit=u_l)), rows in the edge order of as_graph(adj).  The v1 layers, eval mode or dropout 0, no
+        head_parallel; the model then stays in the caller's node order."""
+        use_u = edge_logits is not None and any(u is not None for u in edge_logits)
+        if use_u:
+            if len(edge_logits) != len(self.gat_layers):
+                raise ValueError(f"pygat_amd: edge_logits has {len(edge_logits)} entries for {len(self.gat_layers)} levels")
+            if self._kind != "v1":
+                raise ValueError("pygat_amd: edge_logits covers the GAT (v1) layers only")
+            if self.head_parallel or self.level_fn is not None:
+                raise ValueError("pygat_amd: edge_logits takes neither head_parallel=True nor a level_fn")
+            if self.training and self.dropout > 0.0:
+                raise ValueError("pygat_amd: edge_logits is not taken by the dropout level (train mode with dropout > 0)")
         if isinstance(return_attention, str) and self._kind != "v1":
             from .gatv2 import _no_grad_attention
             _no_grad_attention(return_attention, "a GATv2 model")
@@ -65,7 +78,7 @@ class GAT(nn.Module):
         # previous level's output as it lies (hidden levels too), the self-loop-only nodes go through their tail streams, a
         # head-parallel model exchanges internal-order rows, and only the final [N, C] output is put back into the caller's order.
         to_internal = None
-        if self._internal_order_pays(x, graph, p_drop):
+        if not use_u and self._internal_order_pays(x, graph, p_drop):
             from .features import permuted_rows
             view = graph.internal_view()
             xp = permuted_rows(x, view.to_user) if not x.requires_grad else x.index_select(0, view.to_user.long())
@@ -99,7 +112,9 @@ class GAT(nn.Module):
                 if lvl == 0:
                     Fp = 1 << max(2, (heads[0].W.shape[1] - 1).bit_length())
                     xs = as_sparse_features(x, len(heads) * Fp * (2 if self.skip_connection else 1) + len(heads))
-                if p_drop > 0.0:
+                if use_u and edge_logits[lvl] is not None:
+                    x = gat_level(x, graph, Ws, As, Sk, self.alpha, concat, edge_logit=edge_logits[lvl], **ra)
+                elif p_drop > 0.0:
                     from .dropout import gat_level_dropout
                     x = gat_level_dropout(x, graph, Ws, As, Sk, self.alpha, concat, p_drop, xs=xs, **ra)
                 elif return_attention and to_internal is not None:    # (levels on the internal view: alpha in the caller's order)

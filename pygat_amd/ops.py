@@ -392,6 +392,178 @@ class GATLevelFn(torch.autograd.Function):
         return (cast(dx, 0), cast(dW, 1), cast(da, 2), cast(dWs, 3), None, None, None, None, None, None)
 
 
+class GATEdgeLevelFn(torch.autograd.Function):
+    """The GAT level with a per-edge logit term (csrc/k15_edge_logit.hip): z_ij = s_i + t_j + u_ij in front of the LeakyReLU.
+    forward(x, W [H,Fin,F'], a [H,2F'], Wskip [H,Fin,F'] | None, u [E,H], graph, alpha, concat, att) -> out; u follows the
+    edge order of `graph` (graph.edge_index()) and its gradient is du_ij = dz_ij.  att: a float32 [E, H] tensor the forward
+    fills with the attention coefficients (detached), or None.  The level runs in the caller's node order on an ordinary 2-D
+    x: no renumbering, no self-loop tail, no head windows (H x padded F' <= 1024)."""
+
+    @staticmethod
+    def forward(ctx, x, W, a, Wskip, u, graph: CSRGraph, alpha: float, concat: bool, att):
+        if not x.is_cuda:
+            raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
+        ctx.in_dtypes = (x.dtype, W.dtype, a.dtype, None if Wskip is None else Wskip.dtype, u.dtype)
+        x = x.contiguous().float()
+        W = W.contiguous().float(); a = a.contiguous().float(); u = u.contiguous().float()
+        H, Fin, Fo = W.shape
+        if x.dim() != 2 or x.shape[1] != Fin or a.shape != (H, 2 * Fo):
+            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, W {tuple(W.shape)}, a {tuple(a.shape)}")
+        skip = Wskip is not None
+        if skip:
+            Wskip = Wskip.contiguous().float()
+        L = _Level(x, H, Fo, skip)
+        if L.N != graph.n:
+            raise ValueError(f"x has {L.N} rows but the graph has {graph.n} nodes")
+        if tuple(u.shape) != (graph.nnz, H):
+            raise ValueError(f"pygat_amd: edge_logit {tuple(u.shape)}: expected {(graph.nnz, H)} (one row per edge of the graph)")
+        if L.R > 1024:
+            raise ValueError(f"pygat_amd: edge_logit takes rows of at most 1024 floats (H x padded F'), not {H} x {L.Fp}")
+        L.mode = get_gemm_mode()
+        dev, f32 = x.device, torch.float32
+        f = graph.fwd
+        flags = (_lib.F_ELU if concat else 0) | (_lib.F_SKIP if skip else 0)
+        with torch.cuda.device(dev):
+            st = _stream()
+            Wcat = torch.empty(Fin, L.ldw, dtype=f32, device=dev)
+            a_pad = torch.empty(H, 2, L.Fp, dtype=f32, device=dev)
+            check(lib.pygat_pack_params(H, Fin, Fo, W.data_ptr(), a.data_ptr(), _ptr(Wskip), Wcat.data_ptr(), L.ldw, a_pad.data_ptr(), st),
+                  "pack_params")
+            Wh = torch.empty(L.N, L.R, dtype=f32, device=dev)
+            Sk = torch.empty(L.N, L.R, dtype=f32, device=dev) if skip else None
+            s = torch.empty(L.N, H, dtype=f32, device=dev)
+            t = torch.empty(L.N, H, dtype=f32, device=dev)
+            ncols = L.R * (2 if skip else 1) + H
+            tiles = -(-L.N // 128) * -(-ncols // 128)
+            split_k = max(1, min(-(-384 // tiles), Fin // _K1_SLAB)) if tiles < 256 else 1
+            ws = torch.empty(lib.pygat_gemm_workspace_bytes(L.N, ncols, split_k) // 4, dtype=f32, device=dev) if split_k > 1 else None
+            with _span("k1_project"):
+                check(lib.pygat_project_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, None, Wcat.data_ptr(), L.ldw, a_pad.data_ptr(),
+                                                Wh.data_ptr(), _ptr(Sk), s.data_ptr(), split_k, _ptr(ws), GEMM_MODES[L.mode], st),
+                      "project")
+                # s and t both from the Wh table, as the attention kernels form them
+                check(lib.pygat_attn_scores(L.N, H, Fo, Wh.data_ptr(), None, a_pad.data_ptr(), s.data_ptr(), t.data_ptr(), st),
+                      "attn_scores")
+            hattn = torch.empty(L.N, L.R, dtype=f32, device=dev)
+            m = torch.empty(L.N, H, dtype=f32, device=dev)
+            Z = torch.empty(L.N, H, dtype=f32, device=dev)
+            out = torch.empty(L.N, H * Fo if concat else Fo, dtype=f32, device=dev)
+            part = torch.empty(_lib.edge_workspace_bytes(graph.nnz, H, Fo) // 4, dtype=f32, device=dev)
+            with _span("k15_edge_forward"):
+                check(lib.pygat_gat_edge_forward(f.n, f.nnz, f.rowptr.data_ptr(), f.edge_rc.data_ptr(), H, Fo, float(alpha), flags,
+                                                 Wh.data_ptr(), s.data_ptr(), t.data_ptr(), _ptr(Sk), u.data_ptr(), u.shape[0],
+                                                 out.data_ptr() if concat else None, hattn.data_ptr(), m.data_ptr(), Z.data_ptr(),
+                                                 part.data_ptr(), st), "gat_edge_forward")
+            if not concat:
+                check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
+            if att is not None:
+                with _span("k15_edge_alpha"):
+                    check(lib.pygat_gat_edge_alpha(f.n, f.nnz, f.edge_rc.data_ptr(), H, float(alpha), s.data_ptr(), t.data_ptr(),
+                                                       m.data_ptr(), Z.data_ptr(), u.data_ptr(), u.shape[0], att.data_ptr(), st),
+                          "gat_edge_alpha")
+        if any(ctx.needs_input_grad[:5]):
+            ctx.save_for_backward(x, Wcat, a_pad, Wh, Sk, s, t, m, Z, hattn, out if concat else None, u)
+            ctx.graph, ctx.L, ctx.alpha, ctx.concat, ctx.flags = graph, L, float(alpha), concat, flags
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        x, Wcat, a_pad, Wh, Sk, s, t, m, Z, hattn, y, u = ctx.saved_tensors
+        graph, L = ctx.graph, ctx.L
+        H, Fo, Fin = L.H, L.Fo, L.Fin
+        need = ctx.needs_input_grad
+        dev, f32 = x.device, torch.float32
+        G = G.contiguous().float()
+        f, b = graph.fwd, graph.bwd
+        with torch.cuda.device(dev):
+            st = _stream()
+            Gp = torch.empty(L.N, L.R, dtype=f32, device=dev)
+            du = torch.empty(graph.nnz, H, dtype=f32, device=dev)
+            ds = torch.empty(L.N, H, dtype=f32, device=dev)
+            dt = torch.empty(L.N, H, dtype=f32, device=dev)
+            dWh = torch.empty(L.N, L.R, dtype=f32, device=dev)
+            part = torch.empty(_lib.edge_workspace_bytes(graph.nnz, H, Fo) // 4, dtype=f32, device=dev)
+            with _span("k15_edge_rows"):
+                check(lib.pygat_gat_edge_backward_rows(f.n, f.nnz, f.rowptr.data_ptr(), f.edge_rc.data_ptr(), H, Fo, ctx.alpha, ctx.flags,
+                                                       Wh.data_ptr(), s.data_ptr(), t.data_ptr(), m.data_ptr(), Z.data_ptr(),
+                                                       u.data_ptr(), u.shape[0], G.data_ptr(), _ptr(y), hattn.data_ptr(),
+                                                       Gp.data_ptr(), du.data_ptr(), ds.data_ptr(), part.data_ptr(), st),
+                      "gat_edge_backward_rows")
+            with _span("k15_edge_cols"):
+                check(lib.pygat_gat_edge_backward_cols(b.n, b.nnz, b.rowptr.data_ptr(), b.edge_rc.data_ptr(), graph.perm_t.data_ptr(),
+                                                       H, Fo, ctx.alpha, s.data_ptr(), t.data_ptr(), m.data_ptr(), Z.data_ptr(),
+                                                       u.data_ptr(), u.shape[0], Gp.data_ptr(), du.data_ptr(), ds.data_ptr(),
+                                                       a_pad.data_ptr(), dt.data_ptr(), dWh.data_ptr(), part.data_ptr(), st),
+                      "gat_edge_backward_cols")
+            dx = dW = da = dWs = None
+            if need[2]:
+                da = torch.empty(H, 2 * Fo, dtype=f32, device=dev)
+                wsa = torch.empty(lib.pygat_agrad_workspace_bytes(H, Fo) // 4, dtype=f32, device=dev)
+                with _span("k5_agrad"):
+                    check(lib.pygat_a_grad(L.N, H, Fo, Wh.data_ptr(), ds.data_ptr(), dt.data_ptr(), da.data_ptr(), wsa.data_ptr(),
+                                           None, None, None, 0, 0, st), "a_grad")
+            if need[1]:
+                split_k = _split_k(Fin, L.R, L.N, streamed_k=True, mode=L.mode)
+                wsw = torch.empty(lib.pygat_wgrad_workspace_bytes(Fin, H, Fo, split_k) // 4, dtype=f32, device=dev)
+                dW = torch.empty(H, Fin, Fo, dtype=f32, device=dev)
+                with _span("k5_wgrad"):
+                    check(lib.pygat_wgrad_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, None, dWh.data_ptr(), None, a_pad.data_ptr(),
+                                                  dW.data_ptr(), split_k, wsw.data_ptr(), 0, 0, GEMM_MODES[L.mode], st), "wgrad")
+            if L.skip and need[3]:
+                dSc = torch.empty(Fin, L.R, dtype=f32, device=dev)
+                gemm(True, False, Fin, L.R, L.N, x, L.ldx, Gp, L.R, [(L.R, dSc, L.R)], mode=L.mode)
+                dWs = torch.empty(H, Fin, Fo, dtype=f32, device=dev)
+                check(lib.pygat_unpack_wgrad(H, Fin, Fo, dSc.data_ptr(), L.R, 0, dWs.data_ptr(), st), "unpack")
+            if need[0]:
+                dx = torch.empty(x.shape, dtype=f32, device=dev)
+                with _span("k5_xgrad"):
+                    gemm(False, True, L.N, Fin, L.R, dWh, L.R, Wcat, L.ldw, [(Fin, dx, L.ldx)], mode=L.mode)
+                    if L.skip:
+                        gemm(False, True, L.N, Fin, L.R, Gp, L.R, Wcat[:, L.R:], L.ldw, [(Fin, dx, L.ldx)], accumulate=True, split_k=1,
+                             mode=L.mode)
+        outs = [dx, dW, da, dWs, du if need[4] else None]
+        outs = [g_ if g_ is None or g_.dtype == dt_ else g_.to(dt_) for g_, dt_ in zip(outs, ctx.in_dtypes)]
+        return (*outs, None, None, None, None)
+
+
+def _edge_logit_level(x, graph, Ws, As, Wskips, alpha, concat, edge_logit, return_attention, pipeline, xs, attention_order,
+                      bwd_heads=None):
+    """gat_level(..., edge_logit=u): checks, broadcast of u over the heads, and the level (GATEdgeLevelFn)."""
+    from .graph import InternalOrderView
+    H = len(Ws)
+    for name, val in (("pipeline", pipeline), ("xs", xs), ("bwd_heads", bwd_heads), ("attention_order", attention_order)):
+        if val is not None:
+            raise ValueError(f"pygat_amd: edge_logit does not take {name}: the edge-logit level runs whole, on a dense x, in the "
+                             "caller's node order")
+    if isinstance(return_attention, str):
+        attention_mode(return_attention)
+        raise ValueError("pygat_amd: edge_logit does not take return_attention=\"grad\"; return_attention=True gives the detached "
+                         "coefficients")
+    if isinstance(graph, InternalOrderView) or getattr(graph, "user_row", None) is not None:
+        raise ValueError("pygat_amd: edge_logit needs the caller's graph (a CSRGraph without a row map), not an InternalOrderView "
+                         "or CSRGraph.degree_ordered(): its rows follow graph.edge_index()")
+    if not isinstance(edge_logit, torch.Tensor) or not edge_logit.is_floating_point():
+        raise ValueError("pygat_amd: edge_logit must be a floating-point tensor [E, H], [E, 1] or [E]")
+    if x.dim() != 2:
+        raise ValueError("pygat_amd: edge_logit does not take a column-blocked x")
+    u = edge_logit
+    E = graph.nnz
+    if u.dim() == 1:
+        u = u[:, None]
+    if u.dim() != 2 or u.shape[0] != E or u.shape[1] not in (1, H):
+        raise ValueError(f"pygat_amd: edge_logit {tuple(edge_logit.shape)}: expected [{E}, {H}], [{E}, 1] or [{E}] "
+                         "(one row per edge of graph.edge_index())")
+    if u.shape[1] != H:
+        u = u.expand(E, H)       # (autograd sums the gradient over the heads)
+    u = u.to(x.device)
+    W = torch.stack(list(Ws), 0)
+    a = torch.stack([p.reshape(-1) for p in As], 0)
+    Wskip = torch.stack(list(Wskips), 0) if Wskips is not None else None
+    att = torch.empty(E, H, dtype=torch.float32, device=x.device) if return_attention else None
+    out = GATEdgeLevelFn.apply(x, W, a, Wskip, u, graph, alpha, concat, att)
+    return (out, att) if return_attention else out
+
+
 PAD_K = _config.pad_k     # development knob: 0 = run odd input widths as they are
 MAX_HEAD_TABLE = 16     # PYGAT_MAX_HEADS_TABLE: heads whose parameter pointers travel as kernel arguments
 
@@ -943,7 +1115,7 @@ def stack_heads(Ws, As, Wskips):
 
 def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
               Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, pipeline=None, xs=None,
-              return_attention=False, attention_order=None):
+              return_attention=False, attention_order=None, edge_logit=None):
     """All heads of one level. Ws: H tensors [Fin,F']; As: H tensors with 2F' elements
     ([2F',1] as in GraphAttentionLayer, layers.py:23, or [1,2F'] as in SpGraphAttentionLayer,
     layers.py:114); Wskips: H tensors [Fin,F'] or None.  pipeline: see GATLevelFn.  xs: features.SparseFeatures of x
@@ -951,8 +1123,16 @@ def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: 
     return_attention: -> (out, alpha), alpha [E, H] float32 (detached) = the softmax coefficient of every edge and head, in
     the edge order of `graph` (graph.edge_index()); attention_order: see AttentionTarget.
     return_attention="grad": the same alpha as a second DIFFERENTIABLE output of the level -- a loss may use out, alpha or both
-    (csrc/k14_alpha_grad.hip); a loss on `out` alone runs the backward it runs without it."""
+    (csrc/k14_alpha_grad.hip); a loss on `out` alone runs the backward it runs without it.
+    edge_logit: u [E, H] (or [E] / [E, 1], the same term for every head) added to the score of every edge in front of the
+    LeakyReLU, z_ij = s_i + t_j + u_ij, row k = edge k of graph.edge_index() (csrc/k15_edge_logit.hip).  Differentiable:
+    its gradient is dz_ij (summed over the heads for the broadcast forms).  A row with one edge has alpha = 1 and never reads
+    its u.  The edge-logit level runs in the caller's node order on a dense 2-D x and takes neither a pipeline, sparse xs, an
+    attention_order, return_attention="grad", a column-blocked x nor a graph with a row map / an InternalOrderView (ValueError);
+    return_attention=True is supported.  None: the level takes exactly the path it takes without the argument."""
     H = len(Ws)
+    if edge_logit is not None:
+        return _edge_logit_level(x, graph, Ws, As, Wskips, alpha, concat, edge_logit, return_attention, pipeline, xs, attention_order)
     if return_attention and pipeline is not None:
         raise ValueError("pygat_amd: return_attention does not take a pipeline")
     grad = attention_mode(return_attention)
@@ -961,6 +1141,13 @@ def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: 
     if grad:
         return out           # (out, alpha): both outputs of the level's autograd node
     return (out, att.alpha) if return_attention else out
+
+
+def no_edge_logit(edge_logit, what: str) -> None:
+    """The entry points the edge-logit term (gat_level(..., edge_logit=u), csrc/k15_edge_logit.hip) does not cover."""
+    if edge_logit is not None:
+        raise ValueError(f"pygat_amd: {what} does not take edge_logit: the per-edge logit term covers the plain GAT (v1) level "
+                         "(ops.gat_level) only")
 
 
 def attention_mode(return_attention) -> bool:
