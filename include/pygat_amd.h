@@ -554,6 +554,24 @@ int pygat_gat_edge_backward_cols(int n, int64_t nnz, const int32_t* rowptr_t, co
                                  const float* u, int64_t u_rows, const float* Gp, const float* du, const float* ds,
                                  const float* a_pad, float* dt, float* dWh, void* ws, void* stream);
 
+/* ------------------------------------------------ K16: the inference forward on a bf16 feature table (csrc/k16_bf16_forward.hip)
+ * Additive under ABI 16 (no existing entry point changes).  With Q = round-to-nearest-even from fp32 to bf16 the level is exactly
+ * the fp32 level applied to the table Whq = Q(Wh): s_i = Whq_i . a_src and t_j = Whq_j . a_dst from the ROUNDED rows, logits,
+ * LeakyReLU, online softmax, the weighted sum, skip and ELU in fp32, fp32 outputs.  Forward only (no backward exists).
+ *   pack      Whq [n x R] (uint16 bf16 bit patterns, row stride R = H * padded F', padded columns 0, 16-byte aligned) and
+ *             s [n x H] from the fp32 projection Wh (row stride ldwh >= R floats) and a_pad (pygat_pack_params).
+ *   forward   the nnz split of pygat_gat_forward on the slots / slot_meta / cut_rows of g, a lane gathering 8 table elements
+ *             (16 bytes; 4 at padded F' = 4): out [n x H*F'] = epilogue(h' (+ sk with PYGAT_F_SKIP)), ELU with PYGAT_F_ELU,
+ *             and / or hattn [n x R] = h' (a head-mean level runs pygat_head_mean(hattn, sk) afterwards).  flags: PYGAT_F_ELU |
+ *             PYGAT_F_SKIP only.  g must carry neither user_row (the pass writes row i) nor a slot range.  head_group: heads per
+ *             pass, 0 = as many as a pass takes (rows of 1024 floats; 64 heads at padded F' = 4); more than that is refused.
+ *             part >= the size pygat_gat_bf16_workspace_bytes reports for g's nnz and slot_edges, 16-byte aligned: two fp32
+ *             records per slot for the rows a slot border cuts, merged in slot order.  No float atomics: bitwise reproducible. */
+int pygat_gat_bf16_workspace_bytes(int64_t nnz, int slot_edges, int H, int Fo, size_t* bytes);   /* an error code like the launchers */
+int pygat_gat_pack_bf16(int n, int H, int Fo, const float* Wh, int64_t ldwh, const float* a_pad, void* Whq, float* s, void* stream);
+int pygat_gat_forward_bf16(const pygat_graph* g, int H, int Fo, float alpha, int flags, const void* Whq, const float* s,
+                           const float* a_pad, const float* sk, float* out, float* hattn, int head_group, void* part, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

@@ -46,6 +46,7 @@ SYMBOLS = [
     "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
     "pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
     "pygat_gat_edge_backward_cols",
+    "pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -154,6 +155,9 @@ def _load():
     lib.pygat_gat_edge_alpha.argtypes = [i, i64, p, i, f, p, p, p, p, p, i64, p, p]
     lib.pygat_gat_edge_backward_rows.argtypes = [i, i64, p, p, i, i, f, i, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
     lib.pygat_gat_edge_backward_cols.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
+    lib.pygat_gat_bf16_workspace_bytes.argtypes = [i64, i, i, i, C.POINTER(sz)]
+    lib.pygat_gat_pack_bf16.argtypes = [i, i, i, p, i64, p, p, p, p]
+    lib.pygat_gat_forward_bf16.argtypes = [C.POINTER(Graph), i, i, f, i, p, p, p, p, p, p, i, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
@@ -214,6 +218,13 @@ def edge_workspace_bytes(nnz: int, H: int, f_out: int) -> int:
     """Scratch of the edge-logit passes (pygat_gat_edge_workspace_bytes)."""
     n = C.c_size_t(0)
     check(lib.pygat_gat_edge_workspace_bytes(int(nnz), int(H), int(f_out), C.byref(n)), "gat_edge_workspace_bytes")
+    return n.value
+
+
+def bf16_workspace_bytes(nnz: int, slot_edges: int, H: int, f_out: int) -> int:
+    """Partial records of the bf16-table forward (pygat_gat_bf16_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_gat_bf16_workspace_bytes(int(nnz), int(slot_edges), int(H), int(f_out), C.byref(n)), "gat_bf16_workspace_bytes")
     return n.value
 
 

@@ -227,12 +227,13 @@ def draw_masks_v2(p: float, H: int, N: int, Fin: int, Fo: int, E: int, device, g
 
 def gatv2_level(x, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
                 Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, dropout: float = 0.0,
-                masks: Optional[dict] = None, return_attention=False, edge_logit=None):
+                masks: Optional[dict] = None, return_attention=False, edge_logit=None, table_dtype=None):
     """All heads of one SpGraphAttentionLayerV2 level.  Ws: H tensors [2Fin,F']; As: H tensors of F' elements.
     dropout > 0 (training): per-head masks are drawn here unless given (`masks`, tests).
     return_attention: -> (out, alpha), alpha [E, H] as for ops.gat_level (after the x / Whi / Whj masks, before the
     attention mask); detached -- return_attention="grad" (ops.gat_level) is refused: the GATv2 score gradient is not built."""
     ops.no_edge_logit(edge_logit, "gatv2_level")      # (the per-edge logit term is built for the v1 level only)
+    ops.no_table_dtype(table_dtype, "gatv2_level")
     _no_grad_attention(return_attention, "gatv2_level")
     att = ops.AttentionTarget(graph, len(Ws), x.device) if return_attention else None
     W, a, Wskip = stack_heads(list(Ws), list(As), None if Wskips is None else list(Wskips))   # one launch, not a cat per kind
@@ -273,9 +274,10 @@ class SpGraphAttentionLayerV2(_V2Base):
             self.skip_projection = nn.Parameter(torch.empty(size=(in_features, out_features)))
             nn.init.xavier_uniform_(self.skip_projection.data, gain=1.414)
 
-    def forward(self, input, adj, return_attention=False, edge_logit=None):
+    def forward(self, input, adj, return_attention=False, edge_logit=None, table_dtype=None):
         """return_attention: -> (out, alpha [E, 1]) in the order of adj.nonzero() (CSRGraph.edge_index()).  edge_logit: refused."""
         ops.no_edge_logit(edge_logit, "SpGraphAttentionLayerV2")
+        ops.no_table_dtype(table_dtype, "SpGraphAttentionLayerV2")
         return gatv2_level(input, as_graph(adj, self.pattern_mode), [self.W], [self.a],
                            [self.skip_projection] if self.skip_connection else None, self.alpha, self.concat,
                            self.dropout if self.training else 0.0, return_attention=return_attention)
@@ -296,11 +298,12 @@ class GraphAttentionLayerV2(_V2Base):
             self.skip_projection = nn.Parameter(torch.empty(size=(in_features, out_features)))
             nn.init.xavier_uniform_(self.skip_projection.data, gain=1.414)
 
-    def forward(self, h, adj, masks=None, return_attention=False, edge_logit=None):
+    def forward(self, h, adj, masks=None, return_attention=False, edge_logit=None, table_dtype=None):
         """`masks` (tests only): explicit pre-scaled keep masks {"x" [1,N,Fin], "wh" [1,N,F'] (the Wh2 mask,
         layers.py:212), "att" [E,1]} instead of in-kernel draws.  return_attention: -> (out, alpha [E, 1]) in the order of
         adj > 0 -- the uniform 1 / deg_i of the row-broadcast logits."""
         ops.no_edge_logit(edge_logit, "GraphAttentionLayerV2")
+        ops.no_table_dtype(table_dtype, "GraphAttentionLayerV2")
         _no_grad_attention(return_attention, "GraphAttentionLayerV2")
         Fo = self.out_features
         zero_a = torch.zeros(2 * Fo, 1, dtype=self.W.dtype, device=self.W.device)   # uniform attention

@@ -67,6 +67,12 @@ def _no_attention(return_attention: bool, what: str) -> None:
                          "level or model eagerly with return_attention=True")
 
 
+def _no_table_dtype(table_dtype, what: str) -> None:
+    if table_dtype is not None:
+        raise ValueError(f"pygat_amd: {what} does not take table_dtype (its captured graph holds the fp32 level); call gat_level "
+                         "or the model eagerly with table_dtype=torch.bfloat16")
+
+
 class GraphedLevel:
     """One GAT level, forward + backward, as two HIP graphs (the op boundary of ops.GATLevelFn, replayed).
 
@@ -106,8 +112,10 @@ class GraphedLevel:
 
     # -- without autograd: the two replays as plain calls (bench.py, pipelines that own their buffers)
     @torch.no_grad()
-    def forward(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False, edge_logit=None) -> torch.Tensor:
+    def forward(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False, edge_logit=None,
+                table_dtype=None) -> torch.Tensor:
         """Replay the forward; returns the static output buffer.  None = keep the static input as it is."""
+        _no_table_dtype(table_dtype, "GraphedLevel")
         if edge_logit is not None:
             raise ValueError("pygat_amd: GraphedLevel does not take edge_logit (its captured graph holds the plain level); call "
                              "gat_level eagerly")
@@ -127,8 +135,9 @@ class GraphedLevel:
         self.g_bwd.replay()
         return self.grads
 
-    def __call__(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False) -> torch.Tensor:
+    def __call__(self, x=None, W=None, a=None, Wskip=None, return_attention: bool = False, table_dtype=None) -> torch.Tensor:
         _no_attention(return_attention, "GraphedLevel")
+        _no_table_dtype(table_dtype, "GraphedLevel")
         args = [x, W, a] + ([Wskip] if self.Wskip is not None else [])
         # tensors that require grad must be passed for autograd to route gradients to them; None = the static buffer
         args = [s if t is None else t for t, s in zip(args, self.inputs)]
@@ -208,10 +217,11 @@ class FusedEpoch:
         self.epochs += 1
         return loss, val
 
-    def run(self, return_attention: bool = False):
+    def run(self, return_attention: bool = False, table_dtype=None):
         """One epoch = one graph replay.  Returns (train loss, eval value) as views of static device tensors:
         read them (`.item()`, `.clone()`) before the next call if they are to be kept."""
         _no_attention(return_attention, "FusedEpoch")
+        _no_table_dtype(table_dtype, "FusedEpoch")
         if self.g is None:
             return self._eager_epoch()
         if self.x._version != self._x_version:

@@ -40,13 +40,20 @@ class _FusedGATLayer(nn.Module):
             init(p.data, gain=_GAIN)
             setattr(self, name, p)
 
-    def forward(self, h, adj, return_attention=False, edge_logit=None):
+    def forward(self, h, adj, return_attention=False, edge_logit=None, table_dtype=None):
         """return_attention: -> (out, alpha [E, 1]), the attention coefficient of every edge of the layer's pattern in
         row-major order (adj.nonzero() / adj > 0: CSRGraph.edge_index()), detached; return_attention="grad": the same alpha as
         a differentiable output (ops.gat_level).  edge_logit: u [E, 1] or [E], a per-edge term added to the logit in front of
-        the LeakyReLU, in the same edge order; differentiable (ops.gat_level); not with train-mode dropout."""
+        the LeakyReLU, in the same edge order; differentiable (ops.gat_level); not with train-mode dropout.
+        table_dtype=torch.bfloat16: the inference forward on a bf16 feature table (ops.gat_level); no backward, not with
+        train-mode dropout."""
         graph = as_graph(adj, self.pattern_mode)
         skips = [self.skip_projection] if self.skip_connection else None
+        if table_dtype is not None:
+            if self.training and self.dropout > 0.0:
+                raise ValueError("pygat_amd: table_dtype is not taken by the dropout level (train mode with dropout > 0)")
+            return gat_level(h, graph, [self.W], [self.a], skips, self.alpha, self.concat, return_attention=return_attention,
+                             edge_logit=edge_logit, table_dtype=table_dtype)
         if edge_logit is not None:
             if self.training and self.dropout > 0.0:
                 raise ValueError("pygat_amd: edge_logit is not taken by the dropout level (train mode with dropout > 0)")

@@ -48,13 +48,18 @@ class GAT(nn.Module):
         self._kind = ("v1" if issubclass(layer_type, (GraphAttentionLayer, SpGraphAttentionLayer))
                       else "v2sp" if issubclass(layer_type, SpGraphAttentionLayerV2) else "other")
 
-    def forward(self, x, adj, return_attention=False, edge_logits=None):
+    def forward(self, x, adj, return_attention=False, edge_logits=None, table_dtype=None):
         """return_attention: -> (out, [alpha_1, ..., alpha_L]), alpha_l [E, H_l] (detached) in the edge order of
         as_graph(adj) (its edge_index()), whatever node order the levels ran in.  return_attention="grad": every alpha_l is a
         differentiable output of its level (ops.gat_level; the v1 layers only).
         edge_logits: one entry per level, a tensor u_l [E, H_l] / [E, 1] / [E] or None: the per-edge logit term of that level
         (ops.gat_level(..., edge_logit=u_l)), rows in the edge order of as_graph(adj).  The v1 layers, eval mode or dropout 0, no
-        head_parallel; the model then stays in the caller's node order."""
+        head_parallel; the model then stays in the caller's node order.
+        table_dtype=torch.bfloat16: every level runs its inference forward on a bf16 feature table (ops.gat_level(...,
+        table_dtype=)), in the caller's node order (no internal renumbering, no tail streams).  The v1 layers, eval mode or
+        dropout 0, no gradients; neither return_attention, edge_logits, head_parallel nor a level_fn."""
+        if table_dtype is not None:
+            return self._forward_table(x, adj, return_attention, edge_logits, table_dtype)
         use_u = edge_logits is not None and any(u is not None for u in edge_logits)
         if use_u:
             if len(edge_logits) != len(self.gat_layers):
@@ -128,6 +133,23 @@ class GAT(nn.Module):
         if to_internal is not None:
             x = x.index_select(0, to_internal.long())        # the final [N, C] output back in the caller's order (differentiable)
         return (x, alphas) if return_attention else x
+
+    def _forward_table(self, x, adj, return_attention, edge_logits, table_dtype):
+        """forward(..., table_dtype=): one gat_level call per level on the caller's graph."""
+        if self._kind != "v1":
+            raise ValueError("pygat_amd: table_dtype covers the GAT (v1) layers only")
+        if self.head_parallel or self.level_fn is not None:
+            raise ValueError("pygat_amd: table_dtype takes neither head_parallel=True nor a level_fn")
+        if self.training and self.dropout > 0.0:
+            raise ValueError("pygat_amd: table_dtype is not taken by the dropout level (train mode with dropout > 0)")
+        if return_attention or (edge_logits is not None and any(u is not None for u in edge_logits)):
+            raise ValueError("pygat_amd: table_dtype takes neither return_attention nor edge_logits")
+        graph = as_graph(adj, self.pattern_mode)
+        for lvl, heads in enumerate(self.gat_layers):
+            Sk = [h.skip_projection for h in heads] if self.skip_connection else None
+            x = gat_level(x, graph, [h.W for h in heads], [h.a for h in heads], Sk, self.alpha, lvl < len(self.gat_layers) - 1,
+                          table_dtype=table_dtype)
+        return x
 
     def _internal_order_pays(self, x, graph, p_drop) -> bool:
         """Model-level internal node order: the v1 layers without dropout (the dropout path and GATv2 keep the caller's order), a

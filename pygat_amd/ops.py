@@ -564,6 +564,88 @@ def _edge_logit_level(x, graph, Ws, As, Wskips, alpha, concat, edge_logit, retur
     return (out, att) if return_attention else out
 
 
+def _bf16_level(x, graph, Ws, As, Wskips, alpha, concat, table_dtype, return_attention, pipeline, xs, attention_order, edge_logit):
+    """gat_level(..., table_dtype=torch.bfloat16): the inference forward on a bf16 feature table (csrc/k16_bf16_forward.hip).
+    The projection runs as always (K1, the caller's GEMM mode, fp32); the pack pass rounds it once to Whq = bf16(Wh) (nearest,
+    ties to even) and forms s from the rounded rows; the forward gathers Whq, forms t from the gathered rows and does everything
+    else in fp32: the level is the fp32 level applied to Whq.  The skip term stays fp32.  No backward."""
+    from .graph import InternalOrderView
+    if table_dtype is not torch.bfloat16:
+        raise ValueError(f"pygat_amd: table_dtype={table_dtype!r}: expected None (the fp32 tables) or torch.bfloat16")
+    for name, val in (("pipeline", pipeline), ("sparse xs", xs), ("attention_order", attention_order), ("edge_logit", edge_logit)):
+        if val is not None:
+            raise ValueError(f"pygat_amd: table_dtype does not take {name}: the bf16-table forward runs whole, on a dense x, in the "
+                             "caller's node order")
+    if return_attention:
+        raise ValueError("pygat_amd: table_dtype does not take return_attention (the bf16-table forward keeps no softmax state)")
+    if isinstance(graph, InternalOrderView) or getattr(graph, "user_row", None) is not None:
+        raise ValueError("pygat_amd: table_dtype needs the caller's graph (a CSRGraph without a row map), not an InternalOrderView "
+                         "or CSRGraph.degree_ordered()")
+    if x.dim() != 2:
+        raise ValueError("pygat_amd: table_dtype does not take a column-blocked x")
+    params = list(Ws) + list(As) + (list(Wskips) if Wskips is not None else [])
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        raise ValueError("pygat_amd: the bf16-table forward is inference only (it has no backward): call it under torch.no_grad() "
+                         "or on detached parameters")
+    if not x.is_cuda:
+        raise RuntimeError("pygat_amd: inputs must be on the GPU; the hot path has no CPU fallback")
+    with torch.no_grad():
+        x = x.contiguous().float()
+        W = torch.stack([w.float() for w in Ws], 0).contiguous()
+        a = torch.stack([p.reshape(-1).float() for p in As], 0).contiguous()
+        Wskip = torch.stack([w.float() for w in Wskips], 0).contiguous() if Wskips is not None else None
+        H, Fin, Fo = W.shape
+        if x.shape[1] != Fin or a.shape != (H, 2 * Fo):
+            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, W {tuple(W.shape)}, a {tuple(a.shape)}")
+        skip = Wskip is not None
+        L = _Level(x, H, Fo, skip)
+        if L.N != graph.n:
+            raise ValueError(f"x has {L.N} rows but the graph has {graph.n} nodes")
+        L.ts = slot_edges_for(L.R, graph.slot_edges)
+        L.mode = get_gemm_mode()
+        dev, f32 = x.device, torch.float32
+        flags = (_lib.F_ELU if concat else 0) | (_lib.F_SKIP if skip else 0)
+        with torch.cuda.device(dev):
+            st = _stream()
+            Wcat = torch.empty(Fin, L.ldw, dtype=f32, device=dev)
+            a_pad = torch.empty(H, 2, L.Fp, dtype=f32, device=dev)
+            check(lib.pygat_pack_params(H, Fin, Fo, W.data_ptr(), a.data_ptr(), _ptr(Wskip), Wcat.data_ptr(), L.ldw, a_pad.data_ptr(), st),
+                  "pack_params")
+            Wh = torch.empty(L.N, L.R, dtype=f32, device=dev)
+            Sk = torch.empty(L.N, L.R, dtype=f32, device=dev) if skip else None
+            s = torch.empty(L.N, H, dtype=f32, device=dev)
+            ncols = L.R * (2 if skip else 1) + H
+            tiles = -(-L.N // 128) * -(-ncols // 128)
+            split_k = max(1, min(-(-384 // tiles), Fin // _K1_SLAB)) if tiles < 256 else 1
+            ws = torch.empty(lib.pygat_gemm_workspace_bytes(L.N, ncols, split_k) // 4, dtype=f32, device=dev) if split_k > 1 else None
+            with _span("k1_project"):
+                check(lib.pygat_project_blocked(L.N, Fin, H, Fo, x.data_ptr(), L.ldx, None, Wcat.data_ptr(), L.ldw, a_pad.data_ptr(),
+                                                Wh.data_ptr(), _ptr(Sk), s.data_ptr(), split_k, _ptr(ws), GEMM_MODES[L.mode], st),
+                      "project")
+            Whq = torch.empty(L.N, L.R, dtype=torch.int16, device=dev)      # bf16 bit patterns
+            with _span("k16_pack"):
+                check(lib.pygat_gat_pack_bf16(L.N, H, Fo, Wh.data_ptr(), L.R, a_pad.data_ptr(), Whq.data_ptr(), s.data_ptr(), st),
+                      "gat_pack_bf16")      # (s: K1's scores are replaced by the ones of the rounded rows)
+            single = (not concat) and H == 1      # a mean over one head is that head: the forward writes `out` itself
+            hattn = torch.empty(L.N, L.R, dtype=f32, device=dev) if not (concat or single) else None
+            out = torch.empty(L.N, H * Fo if concat else Fo, dtype=f32, device=dev)
+            part = torch.empty(_lib.bf16_workspace_bytes(graph.nnz, L.ts, H, Fo) // 4, dtype=f32, device=dev)
+            with _span("k16_forward"):
+                check(lib.pygat_gat_forward_bf16(graph.fwd.ref(L.ts), H, Fo, float(alpha), flags, Whq.data_ptr(), s.data_ptr(),
+                                                 a_pad.data_ptr(), _ptr(Sk), out.data_ptr() if (concat or single) else None, _ptr(hattn),
+                                                 0, part.data_ptr(), st), "gat_forward_bf16")
+            if hattn is not None:
+                check(lib.pygat_head_mean(L.N, H, Fo, hattn.data_ptr(), _ptr(Sk), out.data_ptr(), st), "head_mean")
+    return out
+
+
+def no_table_dtype(table_dtype, what: str) -> None:
+    """The entry points the bf16 feature table (gat_level(..., table_dtype=torch.bfloat16), csrc/k16_bf16_forward.hip) does not cover."""
+    if table_dtype is not None:
+        raise ValueError(f"pygat_amd: {what} does not take table_dtype: the bf16 feature table covers the inference forward of the "
+                         "plain GAT (v1) level (ops.gat_level) only")
+
+
 PAD_K = _config.pad_k     # development knob: 0 = run odd input widths as they are
 MAX_HEAD_TABLE = 16     # PYGAT_MAX_HEADS_TABLE: heads whose parameter pointers travel as kernel arguments
 
@@ -1115,7 +1197,7 @@ def stack_heads(Ws, As, Wskips):
 
 def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: Sequence[torch.Tensor],
               Wskips: Optional[Sequence[torch.Tensor]], alpha: float, concat: bool, pipeline=None, xs=None,
-              return_attention=False, attention_order=None, edge_logit=None):
+              return_attention=False, attention_order=None, edge_logit=None, table_dtype=None):
     """All heads of one level. Ws: H tensors [Fin,F']; As: H tensors with 2F' elements
     ([2F',1] as in GraphAttentionLayer, layers.py:23, or [1,2F'] as in SpGraphAttentionLayer,
     layers.py:114); Wskips: H tensors [Fin,F'] or None.  pipeline: see GATLevelFn.  xs: features.SparseFeatures of x
@@ -1129,8 +1211,16 @@ def gat_level(x: torch.Tensor, graph: CSRGraph, Ws: Sequence[torch.Tensor], As: 
     its gradient is dz_ij (summed over the heads for the broadcast forms).  A row with one edge has alpha = 1 and never reads
     its u.  The edge-logit level runs in the caller's node order on a dense 2-D x and takes neither a pipeline, sparse xs, an
     attention_order, return_attention="grad", a column-blocked x nor a graph with a row map / an InternalOrderView (ValueError);
-    return_attention=True is supported.  None: the level takes exactly the path it takes without the argument."""
+    return_attention=True is supported.  None: the level takes exactly the path it takes without the argument.
+    table_dtype: None (the fp32 tables: exactly the path without the argument) or torch.bfloat16 -- the INFERENCE forward on a
+    bf16 feature table (csrc/k16_bf16_forward.hip): the level is the fp32 level applied to Whq = bf16(x W) (round to nearest
+    even, once per element; s and t from the rounded rows; softmax, sums, skip term, ELU and output fp32), its gathers move
+    2 instead of 4 bytes per table element.  No backward: ValueError when autograd is on and x or a parameter requires grad,
+    and for a pipeline, sparse xs, return_attention, attention_order, edge_logit, a column-blocked x or a row-map graph."""
     H = len(Ws)
+    if table_dtype is not None:
+        return _bf16_level(x, graph, Ws, As, Wskips, alpha, concat, table_dtype, return_attention, pipeline, xs, attention_order,
+                           edge_logit)
     if edge_logit is not None:
         return _edge_logit_level(x, graph, Ws, As, Wskips, alpha, concat, edge_logit, return_attention, pipeline, xs, attention_order)
     if return_attention and pipeline is not None:
