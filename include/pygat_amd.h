@@ -572,6 +572,28 @@ int pygat_gat_pack_bf16(int n, int H, int Fo, const float* Wh, int64_t ldwh, con
 int pygat_gat_forward_bf16(const pygat_graph* g, int H, int Fo, float alpha, int flags, const void* Whq, const float* s,
                            const float* a_pad, const float* sk, float* out, float* hattn, int head_group, void* part, void* stream);
 
+/* ------------------------------------------------ K17: the sparse-region SpMM as an op of its own (csrc/k17_spmm.hip)
+ * Additive under ABI 16 (no existing entry point changes).  The reference's SpecialSpmmFunction (layers.py:70-95) for H heads:
+ *   forward      out[i, h, f] = sum_{k in row i} val[perm[k], h] * b[col[k], h, f]  over a CSR pattern (rowptr [n_rows + 1], col
+ *                [nnz]); perm[k] = the caller's entry index of CSR position k (NULL: k itself), val [nnz x H] in the CALLER's entry
+ *                order.  Entries of a row are added in CSR order; repeated (row, col) pairs are separate entries and add.  A row
+ *                without entries gets exact zeros.  The gradient with respect to b is this call on the transposed pattern (rowptr_t,
+ *                row_t, perm_t) with G in place of b and n_cols in place of n_rows.
+ *   grad_values  dval[k, h] = sum_f G[row_k, h, f] * b[col_k, h, f] for every entry k of edge_rc [nnz][2] = (row, col), the caller's
+ *                order (8-byte aligned).  No pattern, no workspace.
+ * Rows of b / out / G are H*F floats (heads side by side, NOT padded) with row strides ldb / ldo / ldg >= H*F.  16-byte loads are used
+ * where F % 4 == 0 and the tables and their strides are 16-byte multiples, single floats otherwise: any F >= 1 is taken.  Limits,
+ * refused with PYGAT_EINVAL: 1 <= H <= 64, F >= 1, H*F <= 1024, 0 <= nnz < 2^31 (n_rows, n_cols are ints).  col / edge_rc are NOT
+ * range-checked: the caller validates its pattern once.  ws >= the size pygat_spmm_workspace_bytes reports, 16-byte aligned, the
+ * caller's: partial sums of the rows of more than 512 entries, one record per 2048-entry chunk, added in chunk order.  fp32, no float
+ * atomics, fixed summation order: bitwise reproducible.  Nothing allocates or synchronises. */
+int pygat_spmm_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes);   /* an error code like the launchers */
+int pygat_spmm_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                       int H, int F, const float* val, const float* b, int64_t ldb, float* out, int64_t ldo,
+                       void* ws, void* stream);
+int pygat_spmm_grad_values(int64_t nnz, const int32_t* edge_rc, int H, int F, const float* G, int64_t ldg,
+                           const float* b, int64_t ldb, float* dval, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

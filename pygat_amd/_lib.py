@@ -47,6 +47,7 @@ SYMBOLS = [
     "pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
     "pygat_gat_edge_backward_cols",
     "pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16",
+    "pygat_spmm_workspace_bytes", "pygat_spmm_forward", "pygat_spmm_grad_values",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -158,6 +159,9 @@ def _load():
     lib.pygat_gat_bf16_workspace_bytes.argtypes = [i64, i, i, i, C.POINTER(sz)]
     lib.pygat_gat_pack_bf16.argtypes = [i, i, i, p, i64, p, p, p, p]
     lib.pygat_gat_forward_bf16.argtypes = [C.POINTER(Graph), i, i, f, i, p, p, p, p, p, p, i, p, p]
+    lib.pygat_spmm_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
+    lib.pygat_spmm_forward.argtypes = [i, i64, p, p, p, i, i, p, p, i64, p, i64, p, p]
+    lib.pygat_spmm_grad_values.argtypes = [i64, p, i, i, p, i64, p, i64, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
@@ -225,6 +229,13 @@ def bf16_workspace_bytes(nnz: int, slot_edges: int, H: int, f_out: int) -> int:
     """Partial records of the bf16-table forward (pygat_gat_bf16_workspace_bytes)."""
     n = C.c_size_t(0)
     check(lib.pygat_gat_bf16_workspace_bytes(int(nnz), int(slot_edges), int(H), int(f_out), C.byref(n)), "gat_bf16_workspace_bytes")
+    return n.value
+
+
+def spmm_workspace_bytes(nnz: int, H: int, F: int) -> int:
+    """Partial records of the long rows of pygat_spmm_forward (pygat_spmm_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_spmm_workspace_bytes(int(nnz), int(H), int(F), C.byref(n)), "spmm_workspace_bytes")
     return n.value
 
 

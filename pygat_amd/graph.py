@@ -254,6 +254,10 @@ class InternalOrderView:
         """int64 [2, E] (internal node ids), the edge order of the attention a level on this view returns."""
         return self.base.edge_index()
 
+    def edge_pattern(self):
+        """The EdgePattern of the internal-order pattern (entry order = edge_index())."""
+        return self.base.edge_pattern()
+
 
 class CSRGraph:
     degree_sorted = False      # True for the patterns CSRGraph.degree_ordered builds
@@ -367,6 +371,16 @@ class CSRGraph:
         """int64 [2, E]: row 0 = softmax row i, row 1 = gathered node j of every edge (layers.py:129), in CSR order -- the
         order of the attention coefficients a level returns for this graph (return_attention)."""
         return self.fwd.edge_rc.t().long()
+
+    def edge_pattern(self):
+        """The pattern as pygat_amd.spmm reads it (an EdgePattern of shape (n, n), cached): its entry order is edge_index(), so the
+        alpha [E, H] a level returns for this graph plugs into spmm(graph.edge_pattern(), alpha, table) unchanged.  It shares
+        this graph's rowptr / col, and its transpose (or mirror permutation) for the gradient with respect to the table."""
+        if getattr(self, "_edge_pattern", None) is None:
+            from .spmm import EdgePattern
+            self._edge_pattern = EdgePattern((self.n, self.n), self.fwd.edge_rc, self.fwd.rowptr, self.fwd.col, None,
+                                             (self.bwd.rowptr, self.bwd.col, self.perm_t))
+        return self._edge_pattern
 
     def internal_view(self) -> InternalOrderView:
         """The degree-ordered pattern for node arrays that are themselves in internal order (see InternalOrderView)."""
