@@ -1,5 +1,7 @@
-// Lane mapping shared by the fused attention kernels K2 (forward), K3 (row
-// backward) and K4 (column backward).
+// Lane mapping and nnz-split skeleton shared by the fused attention kernels K2 (forward), K3 (row
+// backward), K4 (column backward), K6 (GATv2 backward) and K16 (bf16 forward): how a slot is opened (SlotView), which
+// record a piece of a cut row lies in (piece_record), the screening loop of the fix-up kernels that have no cut-row list
+// (screen_cut_rows) and the launch geometry of a pass (main_grid, fixup_grid).
 //
 // A node row is R = H*Fp floats (all local heads interleaved, each padded to
 // Fp = power of two), i.e. NCH = R/4 float4 "chunks".  The CSR edge list is cut
@@ -223,6 +225,30 @@ __device__ __forceinline__ float elu1(float x) {
 __device__ __forceinline__ int64_t slot_at(const GraphDev& g, int64_t q) { return g.order ? (int64_t)g.order[q] : q; }
 #endif
 
+// Launch geometry of a pass over `nslots` slots.  Main launch: a wave carries 64 / lpr slots; narrow rows take one-wave
+// work-groups (narrow_block), the others four waves.
+struct MainGrid { unsigned bt, blocks; };
+static inline MainGrid main_grid(int64_t nslots, int lpr, int vec) {
+  MainGrid m;
+  m.bt = (vec == 1 && lpr <= 8) ? narrow_block() : 256u;
+  m.blocks = (unsigned)cdiv(cdiv(nslots, 64 / lpr), m.bt / 64);
+  return m;
+}
+// Fix-up launch: driven by the graph's cut-row list (`listed`) -- one work-group of FIX_LIST_WAVES waves per wide entry, then
+// fix_rows_per_wave(lpr) entries per wave -- or, without a list, one work-group of four waves per FIX_SCREEN slots.
+// wave_rows (K16): four-wave work-groups whose waves work alone, on one list entry or on FIX_SCREEN slots each.
+// blocks == 0: the list is empty, there is nothing to launch.
+struct FixGrid { bool listed; unsigned blocks; int waves; };
+static inline FixGrid fixup_grid(const GraphDev& g, int lpr, bool wave_rows = false) {
+  FixGrid f;
+  f.listed = g.cut != nullptr;
+  f.waves = (f.listed && !wave_rows) ? FIX_LIST_WAVES : 4;
+  if (wave_rows) f.blocks = (unsigned)cdiv(f.listed ? (int64_t)g.n_cut : cdiv(g.kn, FIX_SCREEN), 4);
+  else if (!f.listed) f.blocks = (unsigned)cdiv(g.kn, FIX_SCREEN);
+  else f.blocks = g.n_cut > 0 ? (unsigned)(g.n_cut_wide + cdiv(g.n_cut - g.n_cut_wide, FIX_LIST_WAVES * fix_rows_per_wave(lpr))) : 0u;
+  return f;
+}
+
 // Work-groups of the column pass (pygat_gat_backward_col) over gT for a level of H heads = its da_part records, or 0 when the
 // pass does not take the attention-vector gradient along: no cut-row list (the rows its fix-up finishes are folded in by
 // pygat_a_grad_fold from that list), head windows (hg < H), or a row shape other than 8 heads x 16 -- the one
@@ -236,9 +262,8 @@ static inline int64_t col_da_blocks(const GraphDev& g, int H, int Fp, int hg, in
   int lpr, vec;
   pick_lanes(rs, &lpr, &vec);
   if (vec != 1 || H != 8 || Fp != 16) return 0;
-  const unsigned bt = (lpr <= 8) ? narrow_block() : 256u;
   if (lpr_out) *lpr_out = lpr;
-  return cdiv(cdiv(g.kn, 64 / lpr), bt / 64);   // (kn: the active slots -- all of them, or the prefix of the call)
+  return main_grid(g.kn, lpr, vec).blocks;   // (kn: the active slots -- all of them, or the prefix of the call)
 }
 
 #ifdef __HIPCC__
@@ -257,6 +282,73 @@ __device__ __forceinline__ int64_t slot_of(const GraphDev& g, int64_t pos) {
   int64_t k = pos / g.ts;
   if (g.sb && pos < g.sb[k]) --k;
   return k;
+}
+
+// A slot as its lane group sees it when it starts to walk: the edge range, the first row, whether that row began in an earlier
+// slot (its state then goes to the head record 2k) and what is known up front of the last row.
+struct SlotView {
+  int64_t e0, e1;
+  int r_first;
+  bool head_partial;
+  bool tail_known, tail_flag;   // slot_meta says whether the last row continues; without it rowptr does (slot_tail_partial)
+};
+// by the chain slot_begin -> edge_rc -> rowptr
+__device__ __forceinline__ SlotView open_slot_chain(const GraphDev& g, int64_t k) {
+  SlotView s;
+  slot_range(g, k, &s.e0, &s.e1);
+  s.r_first = g.rc[s.e0].x;
+  s.head_partial = g.rowptr[s.r_first] < s.e0;
+  s.tail_known = false; s.tail_flag = false;
+  return s;
+}
+// from the slot's slot_meta record where the graph has them (wave-uniform branch), else by the chain
+__device__ __forceinline__ SlotView open_slot(const GraphDev& g, int64_t k) {
+  SlotView s;
+  if (g.meta) {
+    const int4 mt = g.meta[k];
+    s.e0 = mt.x; s.e1 = mt.y; s.r_first = mt.z;
+    s.head_partial = (mt.w & 1) != 0; s.tail_known = true; s.tail_flag = (mt.w & 2) != 0;
+  } else {
+    s = open_slot_chain(g, k);
+  }
+  return s;
+}
+// did `cur` begin in an earlier slot (only the slot's first row can: its state then goes to the head record 2k)
+__device__ __forceinline__ bool slot_head_partial(const SlotView& s, int cur) { return cur == s.r_first && s.head_partial; }
+// does `cur`, the last row of the slot, continue in the next slot (its state then goes to the tail record 2k + 1)
+__device__ __forceinline__ bool slot_tail_partial(const GraphDev& g, const SlotView& s, int cur) {
+  return s.tail_known ? s.tail_flag : g.rowptr[cur + 1] > s.e1;
+}
+
+// record of piece q of the cut row that slot k owns: tail(k), head(k + 1), head(k + 2), ...
+__device__ __forceinline__ int64_t piece_record(int64_t k, int q) { return q == 0 ? 2 * k + 1 : 2 * (k + q); }
+
+// Slot k OWNS a cut row if its last row starts inside k and continues beyond: that row and the end of its edges.
+__device__ __forceinline__ bool slot_owns_cut_row(const GraphDev& g, int64_t k, int* r, int* row_end) {
+  int64_t e0, e1;
+  slot_range(g, k, &e0, &e1);
+  *r = g.rc[e1 - 1].x;
+  *row_end = g.rowptr[*r + 1];
+  return (int64_t)*row_end > e1 && (int64_t)g.rowptr[*r] >= e0;
+}
+// Screening loop of the fix-up kernels that have no cut-row list: the calling wave screens the FIX_SCREEN slots from `kbase`
+// (below `kend`), one per lane, and calls merge(k, row, npieces) for every cut row they own, in slot order.  The waves of a
+// work-group that screen the same slots see the same rows in the same order, so `merge` may hold barriers.
+template <typename Merge>
+__device__ __forceinline__ void screen_cut_rows(const GraphDev& g, int64_t kbase, int64_t kend, Merge&& merge) {
+  const int lane = threadIdx.x & 63;
+  int my_r = 0, my_end = 0;
+  bool owner = false;
+  if (lane < FIX_SCREEN && kbase + lane < kend) owner = slot_owns_cut_row(g, kbase + lane, &my_r, &my_end);
+  unsigned long long todo = __ballot(owner);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const int64_t k = kbase + src;
+    const int r = __shfl(my_r, src);
+    const int64_t row_end = __shfl(my_end, src);
+    merge(k, r, (int)(slot_of(g, row_end - 1) - k) + 1);
+  }
 }
 
 template <int VEC>

@@ -29,6 +29,19 @@ void set_error(const char* fmt, ...);
     }                                                                     \
   } while (0)
 
+// register / scratch footprint of kernel `fn` as the loaded code object reports it (the tail of every pygat_kernel_footprint helper)
+static inline int kernel_footprint_of(const void* fn, int* regs, int* scratch) {
+  hipFuncAttributes at;
+  const hipError_t e = hipFuncGetAttributes(&at, fn);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("kernel_footprint: %s", hipGetErrorString(e));
+    return PYGAT_EHIP;
+  }
+  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
+  return PYGAT_OK;
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 #ifdef __HIPCC__

@@ -229,15 +229,7 @@ int footprint_k14(int which, int* regs, int* scratch) {
                    : which == 2 ? reinterpret_cast<const void*>(&alpha_grad_wave_kernel<false>)
                    : which == 3 ? reinterpret_cast<const void*>(&alpha_grad_wave_kernel<true>)
                                 : reinterpret_cast<const void*>(&alpha_grad_apply_kernel);
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
+  return kernel_footprint_of(fn, regs, scratch);
 }
 
 }  // namespace pygat

@@ -367,15 +367,7 @@ int footprint_k15(const char* name, int* regs, int* scratch) {
     set_error("kernel_footprint: unknown kernel '%s' (k15_att, k15_{fwd,rows,cols}_{long,row}_l<LPR>v<VEC>)", name);
     return PYGAT_EINVAL;
   }
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
+  return kernel_footprint_of(fn, regs, scratch);
 }
 
 static int el_check(const char* what, int n, int64_t nnz, int64_t u_rows, const int32_t* rowptr, const int32_t* edge_rc, int H, int Fo,

@@ -235,19 +235,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC == 1 ? 
   const int64_t kl = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * EPW + lane / LPR;
   if (kl >= a.g.kn) return;   // lane groups are independent: no cross-group op below
   const int64_t k = a.g.order ? a.g.order[kl] : kl;
-  int64_t e0, e1;
+  const SlotView sl = open_slot(a.g, k);
+  const int64_t e0 = sl.e0, e1 = sl.e1;
   const int2* __restrict__ rc = a.g.rc;
-  int r_first;
-  bool head_partial, tail_known = false, tail_flag = false;
-  if (a.g.meta) {   // one record instead of the chain slot_begin -> edge_rc -> rowptr
-    const int4 mt = a.g.meta[k];
-    e0 = mt.x; e1 = mt.y; r_first = mt.z;
-    head_partial = (mt.w & 1) != 0; tail_known = true; tail_flag = (mt.w & 2) != 0;
-  } else {
-    slot_range(a.g, k, &e0, &e1);
-    r_first = rc[e0].x;
-    head_partial = a.g.rowptr[r_first] < e0;
-  }
   const BfCols<VEC> lc = bf_cols<CW, LPR, VEC>(a);
   const int lph = a.lph;
   float adst[VEC][CW];   // this lane's slice of a_dst (zero on invalid chunks; the padded columns of a_pad are zero)
@@ -259,7 +249,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC == 1 ? 
       if (!lc.valid[v]) q = make_float4(0.f, 0.f, 0.f, 0.f);
       adst[v][kk] = q.x; adst[v][kk + 1] = q.y; adst[v][kk + 2] = q.z; adst[v][kk + 3] = q.w;
     }
-  int cur = r_first;
+  int cur = sl.r_first;
   BfState<CW, VEC> st;
   st.reset();
   for (int64_t e = e0; e < e1; e += U) {
@@ -289,7 +279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC == 1 ? 
       }
       if (e + u < e1) {
         if (p[u].x != cur) {
-          bf_flush<CW, VEC>(a, lc, k, cur, cur == r_first && head_partial, false, st);
+          bf_flush<CW, VEC>(a, lc, k, cur, slot_head_partial(sl, cur), false, st);
           cur = p[u].x;
           st.reset();
         }
@@ -298,8 +288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VEC == 1 ? 
       }
     }
   }
-  const bool tail_partial = tail_known ? tail_flag : a.g.rowptr[cur + 1] > e1;
-  bf_flush<CW, VEC>(a, lc, k, cur, cur == r_first && head_partial, tail_partial, st);
+  bf_flush<CW, VEC>(a, lc, k, cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur), st);
 }
 
 // Merge of one cut row by one wave: its pieces tail(k), head(k + 1), ..., head(k + npieces - 1) are dealt round-robin to the
@@ -317,7 +306,7 @@ __device__ __forceinline__ void bf_merge_row(const BfArgs& a, const BfCols<VEC>&
     for (int f = 0; f < PF; ++f) {
       const int qq = q + f * G;
       const int qc = qq < npieces ? qq : q;   // clamped: the loads stay unconditional
-      bf_part_load<CW, VEC>(a, lc, a.part + (qc == 0 ? 2 * k + 1 : 2 * (k + qc)) * a.ps, rec[f]);
+      bf_part_load<CW, VEC>(a, lc, a.part + piece_record(k, qc) * a.ps, rec[f]);
     }
 #pragma unroll
     for (int f = 0; f < PF; ++f)
@@ -345,7 +334,6 @@ __device__ __forceinline__ void bf_merge_row(const BfArgs& a, const BfCols<VEC>&
 // beyond -- and merges the rows they own in turn.
 template <int CW, int LPR, int VEC>
 __global__ __launch_bounds__(256) void bf_fixup_kernel(BfArgs a) {
-  const int lane = threadIdx.x & 63;
   const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const BfCols<VEC> lc = bf_cols<CW, LPR, VEC>(a);
   if (a.g.cut) {
@@ -353,26 +341,7 @@ __global__ __launch_bounds__(256) void bf_fixup_kernel(BfArgs a) {
     bf_merge_row<CW, LPR, VEC>(a, lc, a.g.cut[3 * wv], a.g.cut[3 * wv + 1], a.g.cut[3 * wv + 2]);
     return;
   }
-  const int64_t kbase = wv * FIX_SCREEN, nslots = a.g.kn;
-  if (kbase >= nslots) return;
-  int my_r = 0, my_end = 0;
-  bool owner = false;
-  if (lane < FIX_SCREEN && kbase + lane < nslots) {
-    int64_t e0, e1;
-    slot_range(a.g, kbase + lane, &e0, &e1);
-    my_r = a.g.rc[e1 - 1].x;
-    my_end = a.g.rowptr[my_r + 1];
-    owner = (int64_t)my_end > e1 && (int64_t)a.g.rowptr[my_r] >= e0;
-  }
-  unsigned long long todo = __ballot(owner);
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int64_t k = kbase + src;
-    const int r = __shfl(my_r, src);
-    const int64_t row_end = __shfl(my_end, src);
-    bf_merge_row<CW, LPR, VEC>(a, lc, k, r, (int)(slot_of(a.g, row_end - 1) - k) + 1);
-  }
+  screen_cut_rows(a.g, wv * FIX_SCREEN, a.g.kn, [&](int64_t k, int r, int npieces) { bf_merge_row<CW, LPR, VEC>(a, lc, k, r, npieces); });
 }
 
 // lane shapes: CW = 8 -> (LPR, 1) for LPR = 1 .. 64 and (64, 2); CW = 4 -> (LPR, 1)
@@ -434,15 +403,7 @@ int footprint_k16(const char* name, int* regs, int* scratch) {
     set_error("kernel_footprint: unknown kernel '%s' (k16_pack, k16_{fwd,fix}_c<CW>l<LPR>v<VEC>)", name);
     return PYGAT_EINVAL;
   }
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
+  return kernel_footprint_of(fn, regs, scratch);
 }
 
 }  // namespace pygat
@@ -519,14 +480,12 @@ extern "C" int pygat_gat_forward_bf16(const pygat_graph* g, int H, int Fo, float
     a.part = static_cast<float*>(part);   // reused by the windows: the launches are ordered on the stream
     int lpr, vec;
     bf_pick_lanes(a.nch, &lpr, &vec);
-    const unsigned bt = (vec == 1 && lpr <= 8) ? narrow_block() : 256u;
-    const unsigned blocks = (unsigned)cdiv(cdiv(nslots, 64 / lpr), bt / 64);
-    PYGAT_BF_DISPATCH(CWv, lpr, vec, hipLaunchKernelGGL((bf_fwd_kernel<CW, LPR, VEC>), dim3(blocks), dim3(bt), 0, st, a));
+    const MainGrid mg = main_grid(nslots, lpr, vec);
+    PYGAT_BF_DISPATCH(CWv, lpr, vec, hipLaunchKernelGGL((bf_fwd_kernel<CW, LPR, VEC>), dim3(mg.blocks), dim3(mg.bt), 0, st, a));
     PYGAT_CHECK_LAUNCH("gat_forward_bf16");
-    const bool listed = a.g.cut != nullptr;
-    if (listed && a.g.n_cut == 0) continue;
-    const unsigned fb = (unsigned)cdiv(listed ? (int64_t)a.g.n_cut : cdiv(nslots, FIX_SCREEN), 4);
-    PYGAT_BF_DISPATCH(CWv, lpr, vec, hipLaunchKernelGGL((bf_fixup_kernel<CW, LPR, VEC>), dim3(fb), dim3(256), 0, st, a));
+    const FixGrid fg = fixup_grid(a.g, lpr, /*wave_rows=*/true);   // a wave per list entry, or per FIX_SCREEN slots
+    if (fg.blocks == 0) continue;
+    PYGAT_BF_DISPATCH(CWv, lpr, vec, hipLaunchKernelGGL((bf_fixup_kernel<CW, LPR, VEC>), dim3(fg.blocks), dim3(64 * fg.waves), 0, st, a));
     PYGAT_CHECK_LAUNCH("gat_forward_bf16_fixup");
   }
   return PYGAT_OK;

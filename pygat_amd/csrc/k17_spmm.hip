@@ -290,15 +290,7 @@ int footprint_k17(const char* name, int* regs, int* scratch) {
     set_error("kernel_footprint: unknown kernel '%s' (k17_sddmm_c<CW>, k17_spmm_{long,row}_c<CW>l<LPR>v<VEC>)", name);
     return PYGAT_EINVAL;
   }
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
+  return kernel_footprint_of(fn, regs, scratch);
 }
 
 static int sp_check_shape(const char* what, int64_t nnz, int H, int F) {

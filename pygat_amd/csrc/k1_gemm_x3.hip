@@ -1256,18 +1256,10 @@ int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A
 }
 
 int footprint_gemm_x3(int which, int* regs, int* scratch) {
-  hipFuncAttributes at;
   const void* fn = which == 0 ? reinterpret_cast<const void*>(&gemm_tn_x3w_kernel)
                  : which == 1 ? reinterpret_cast<const void*>(&gemm_x3gw_kernel<true, false>)
                               : reinterpret_cast<const void*>(&gemm_smallk_x3_kernel<false, 4, 16, 2, 2>);   // projection + tail output
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
+  return kernel_footprint_of(fn, regs, scratch);
 }
 
 }  // namespace pygat

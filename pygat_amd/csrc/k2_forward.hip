@@ -252,6 +252,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((AUX && FAS
   const int64_t kl = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * EPW + lane / LPR;
   if (kl >= a.g.kn) return;  // lane groups are independent: no cross-lane op below
   const int64_t k = a.g.order ? a.g.order[kl] : a.g.k0 + kl;  // slot id (slot_order: the whole range, k0 = 0)
+  // (open_slot / slot_head_partial / slot_tail_partial of attn_common.h, spelled out: this walk keeps the schedule it was measured with)
   int64_t e0, e1;
   const int2* __restrict__ rc = a.g.rc;
   int r_first;
@@ -378,7 +379,7 @@ __device__ __forceinline__ void fwd_merge_row(const FwdArgs& a, const LaneCols<V
       for (int f = 0; f < PF; ++f) {
         const int qq = q + f * G;
         const int qc = qq < npieces ? qq : q;   // clamped: the loads stay unconditional
-        part_load<VEC, AUX>(a, lc, a.part + (qc == 0 ? 2 * k + 1 : 2 * (k + qc)) * PS, rec[f]);
+        part_load<VEC, AUX>(a, lc, a.part + piece_record(k, qc) * PS, rec[f]);
       }
 #pragma unroll
       for (int f = 0; f < PF; ++f)
@@ -425,31 +426,13 @@ __global__ __launch_bounds__(256) void gat_fwd_fixup_kernel(FwdArgs a) {
   constexpr int EPW = 64 / LPR;
   constexpr int PF = (VEC == 1) ? 4 : 2;
   extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [4][PS]
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t kbase = a.g.k0 + (int64_t)blockIdx.x * FIX_SCREEN;
-  const int64_t nslots = a.g.k0 + a.g.kn;
-  int my_r = 0, my_end = 0;
-  bool owner = false;
-  if (lane < FIX_SCREEN && kbase + lane < nslots) {
-    int64_t e0, e1;
-    slot_range(a.g, kbase + lane, &e0, &e1);
-    my_r = a.g.rc[e1 - 1].x;
-    my_end = a.g.rowptr[my_r + 1];
-    owner = (int64_t)my_end > e1 && (int64_t)a.g.rowptr[my_r] >= e0;
-  }
-  unsigned long long todo = __ballot(owner);  // identical in the 4 waves
+  const int w = threadIdx.x >> 6;
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int64_t k = kbase + src;
-    const int r = __shfl(my_r, src);
-    const int64_t row_end = __shfl(my_end, src);
-    const int64_t k_e = slot_of(a.g, row_end - 1);
-    const int npieces = (int)(k_e - k) + 1;
+  // (the 4 waves screen the same slots: each row is merged by all of them)
+  screen_cut_rows(a.g, a.g.k0 + (int64_t)blockIdx.x * FIX_SCREEN, a.g.k0 + a.g.kn, [&](int64_t k, int r, int npieces) {
     const bool wide = npieces > EPW * PF;  // more pieces than one wave takes in a single round
     fwd_merge_row<LPR, VEC, AUX, 4>(a, lc, fix_sm, k, r, npieces, wide, w);
-  }
+  });
 }
 
 // list-driven variant: entry q of g.cut = (owner slot k, row, pieces); the first n_cut_wide entries (long
@@ -569,10 +552,8 @@ static int launch_forward(const pygat_graph* g, int H, int Fo, float alpha, int 
     a.part = (float*)part;   // reused by the windows: the launches are ordered on the stream
     int lpr, vec;
     pick_lanes(a.rs, &lpr, &vec);
-    // narrow rows (a wave carries 8-64 slots, the whole grid is a few ten waves per SIMD): one-wave work-groups, so that a
-    // SIMD slot is refilled as soon as ITS wave ends instead of when the slowest of four does
-    const unsigned bt = (vec == 1 && lpr <= 8) ? narrow_block() : 256u;
-    const unsigned blocks = (unsigned)cdiv(cdiv(nslots, 64 / lpr), bt / 64);
+    const MainGrid mg = main_grid(nslots, lpr, vec);
+    const unsigned bt = mg.bt, blocks = mg.blocks;
     const bool aux = aneg != nullptr;
     // 32-bit element offsets: the gathered table and s below 2^32 bytes
     // measured (config 5, same box): the training forward 1.147 -> 1.114 ms (5 instead of 4 waves per SIMD), the plain
@@ -593,20 +574,17 @@ static int launch_forward(const pygat_graph* g, int H, int Fo, float alpha, int 
     else PYGAT_FWD(false, false, false);
 #undef PYGAT_FWD
     PYGAT_CHECK_LAUNCH("gat_forward");
-    const bool listed = a.g.cut != nullptr;   // the caller listed the cut rows: go straight to them
-    const int fix_waves = listed ? FIX_LIST_WAVES : 4;
-    const size_t fix_lds = fix_waves * (size_t)(aux ? part_stride<true>(a.rs) : part_stride<false>(a.rs)) * sizeof(float);
-    const unsigned fb = listed ? (unsigned)(a.g.n_cut_wide + cdiv(a.g.n_cut - a.g.n_cut_wide, FIX_LIST_WAVES * fix_rows_per_wave(lpr)))
-                               : (unsigned)cdiv(nslots, FIX_SCREEN);
-    if ((listed && a.g.n_cut == 0) || !do_fix) continue;
+    const FixGrid fg = fixup_grid(a.g, lpr);   // (listed: the caller listed the cut rows, go straight to them)
+    const size_t fix_lds = fg.waves * (size_t)(aux ? part_stride<true>(a.rs) : part_stride<false>(a.rs)) * sizeof(float);
+    if (fg.blocks == 0 || !do_fix) continue;
 #define PYGAT_FIX(AUXV)                                                                                               \
     do {                                                                                                              \
-      if (listed) {                                                                                                   \
-        PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_fwd_fixup_list_kernel<LPR, VEC, AUXV>), dim3(fb),     \
-                                                          dim3(64 * FIX_LIST_WAVES), fix_lds, st, a));                \
+      if (fg.listed) {                                                                                                \
+        PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_fwd_fixup_list_kernel<LPR, VEC, AUXV>), dim3(fg.blocks), \
+                                                          dim3(64 * fg.waves), fix_lds, st, a));                      \
       } else {                                                                                                        \
-        PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_fwd_fixup_kernel<LPR, VEC, AUXV>), dim3(fb), dim3(256), \
-                                                          fix_lds, st, a));                                           \
+        PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_fwd_fixup_kernel<LPR, VEC, AUXV>), dim3(fg.blocks),   \
+                                                          dim3(64 * fg.waves), fix_lds, st, a));                      \
       }                                                                                                               \
     } while (0)
     if (aux) PYGAT_FIX(true); else PYGAT_FIX(false);
@@ -623,21 +601,9 @@ extern "C" int pygat_head_group(int n, int H, int Fo) {
 }
 
 
-// register / scratch footprint of a kernel of this file as the loaded code object reports it (pygat_kernel_footprint)
-static int footprint_of(const void* fn, int* regs, int* scratch) {
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    pygat::set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
-}
 namespace pygat {
-int footprint_k2_headline(int* regs, int* scratch) {
-  return footprint_of(reinterpret_cast<const void*>(&gat_fwd_kernel<32, 1, false, true, true, 4, 128>), regs, scratch);
+int footprint_k2_headline(int* regs, int* scratch) {   // (pygat_kernel_footprint)
+  return kernel_footprint_of(reinterpret_cast<const void*>(&gat_fwd_kernel<32, 1, false, true, true, 4, 128>), regs, scratch);
 }
 }  // namespace pygat
 

@@ -238,8 +238,8 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(RowArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t k = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
   if (k >= num_slots(a.g)) return;
-  int64_t e0, e1;
-  slot_range(a.g, k, &e0, &e1);
+  const SlotView sl = open_slot_chain(a.g, k);
+  const int64_t e0 = sl.e0, e1 = sl.e1;
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
   const int R = a.rs.R;
   const int64_t RW = a.ldgr, ldr = a.rs.ldr, ldh = a.rs.ldh;
@@ -251,9 +251,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(RowArgs a) {
     adst[v] = ld4(a.a_pad + (int64_t)lc.head[v] * 2 * a.rs.Fp + a.rs.Fp + (lc.cofs[v] & (a.rs.Fp - 1)));
     if (!lc.valid[v]) adst[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  const int r_first = rc[e0].x;
-  const bool head_partial = a.g.rowptr[r_first] < e0;
-  int cur = r_first;
+  int cur = sl.r_first;
   int rprev = -1;
   float4 gcur[VEC], rtcur[VEC];
   float acc[VEC];
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(RowArgs a) {
     for (int u = 0; u < U; ++u) {
       if (e + u < e1) {
         if (p[u].x != cur) {
-          row_flush<VEC>(a, lc, k, cur, cur == r_first && head_partial, false, acc);
+          row_flush<VEC>(a, lc, k, cur, slot_head_partial(sl, cur), false, acc);
           cur = p[u].x;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
@@ -320,8 +318,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(RowArgs a) {
       }
     }
   }
-  const bool tail_partial = a.g.rowptr[cur + 1] > e1;
-  row_flush<VEC>(a, lc, k, cur, cur == r_first && head_partial, tail_partial, acc);
+  row_flush<VEC>(a, lc, k, cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur), acc);
 }
 
 // Row-sum pass: ds_i = sum over the forward edges k of row i of dz_t[perm_f[k]] -- the light replacement of the
@@ -334,14 +331,12 @@ __global__ __launch_bounds__(256) void gat_bwd_rowsum_kernel(RowArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t k = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
   if (k >= num_slots(a.g)) return;
-  int64_t e0, e1;
-  slot_range(a.g, k, &e0, &e1);
+  const SlotView sl = open_slot_chain(a.g, k);
+  const int64_t e0 = sl.e0, e1 = sl.e1;
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
   const int64_t ldh = a.rs.ldh;
   const int2* __restrict__ rc = a.g.rc;
-  const int r_first = rc[e0].x;
-  const bool head_partial = a.g.rowptr[r_first] < e0;
-  int cur = r_first;
+  int cur = sl.r_first;
   float acc[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
@@ -360,7 +355,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rowsum_kernel(RowArgs a) {
     for (int u = 0; u < U; ++u) {
       if (e + u < e1) {
         if (row[u] != cur) {
-          row_flush<VEC>(a, lc, k, cur, cur == r_first && head_partial, false, acc);
+          row_flush<VEC>(a, lc, k, cur, slot_head_partial(sl, cur), false, acc);
           cur = row[u];
 #pragma unroll
           for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
@@ -370,8 +365,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rowsum_kernel(RowArgs a) {
       }
     }
   }
-  const bool tail_partial = a.g.rowptr[cur + 1] > e1;
-  row_flush<VEC>(a, lc, k, cur, cur == r_first && head_partial, tail_partial, acc);
+  row_flush<VEC>(a, lc, k, cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur), acc);
 }
 
 // cut rows: one thread per (slot, head) screens ownership and sums the pieces in slot order
@@ -381,11 +375,8 @@ __global__ __launch_bounds__(256) void gat_bwd_row_fixup_kernel(RowArgs a) {
   const int64_t k = idx / H;
   const int h = (int)(idx % H);
   if (k >= num_slots(a.g)) return;
-  int64_t e0, e1;
-  slot_range(a.g, k, &e0, &e1);
-  const int r = a.g.rc[e1 - 1].x;
-  const int64_t row_end = a.g.rowptr[r + 1];
-  if (row_end <= e1 || (int64_t)a.g.rowptr[r] < e0) return;
+  int r, row_end;
+  if (!slot_owns_cut_row(a.g, k, &r, &row_end)) return;
   const int64_t k_e = slot_of(a.g, row_end - 1);
   float acc = a.part[(2 * k + 1) * H + h];
   for (int64_t kk = k + 1; kk <= k_e; ++kk) acc += a.part[(2 * kk) * H + h];
@@ -404,7 +395,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_fixup_list_kernel(RowArgs a) 
   const int H = a.rs.H;
   for (int h = 0; h < H; ++h) {
     float acc = 0.f;
-    for (int q = lane; q < npieces; q += 64) acc += a.part[(q == 0 ? 2 * k + 1 : 2 * (k + q)) * (int64_t)H + h];
+    for (int q = lane; q < npieces; q += 64) acc += a.part[piece_record(k, q) * H + h];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) a.ds[(int64_t)r * a.rs.ldh + h] = acc;

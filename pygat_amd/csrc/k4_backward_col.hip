@@ -155,19 +155,9 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
 #endif
   constexpr bool NARROW = (VEC == 1 && LPR <= 8) || (PYGAT_K4_PREFETCH_ALL && VEC == 1);
   constexpr int U = (VEC == 1) ? 4 : 2;
-  int64_t e0, e1;
-  int r_first;
-  bool head_partial, tail_known = false, tail_flag = false;
+  const SlotView sl = open_slot(a.g, k);
+  const int64_t e0 = sl.e0, e1 = sl.e1;
   const int2* __restrict__ rc = a.g.rc;
-  if (a.g.meta) {   // (wave-uniform) one record instead of the chain slot_begin -> edge_rc -> rowptr
-    const int4 mt = a.g.meta[k];
-    e0 = mt.x; e1 = mt.y; r_first = mt.z;
-    head_partial = (mt.w & 1) != 0; tail_known = true; tail_flag = (mt.w & 2) != 0;
-  } else {
-    slot_range(a.g, k, &e0, &e1);
-    r_first = rc[e0].x;
-    head_partial = a.g.rowptr[r_first] < e0;
-  }
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
   const int R = CR ? CR : a.rs.R;
   constexpr int HC = CR / (4 * (LPH ? LPH : 1));   // heads, when CR > 0
@@ -179,7 +169,7 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
     adst[v] = ld4(a.a_pad + (int64_t)lc.head[v] * 2 * a.rs.Fp + a.rs.Fp + (lc.cofs[v] & (a.rs.Fp - 1)));
     if (!lc.valid[v]) adst[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  int cur = r_first;
+  int cur = sl.r_first;
   float4 acc[VEC];
   float dt[VEC];
 #pragma unroll
@@ -251,7 +241,7 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
     for (int u = 0; u < U; ++u) {
       if (e + u < e1) {
         if (p[u].x != cur) {
-          col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, cur == r_first && head_partial, false, acc, dt, da_lds, da_stride);
+          col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, slot_head_partial(sl, cur), false, acc, dt, da_lds, da_stride);
           cur = p[u].x;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); dt[v] = 0.f; }
@@ -265,8 +255,7 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
       }
     }
   }
-  const bool tail_partial = tail_known ? tail_flag : a.g.rowptr[cur + 1] > e1;
-  col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, cur == r_first && head_partial, tail_partial, acc, dt, da_lds, da_stride);
+  col_flush<VEC, LPH, CR, DA>(a, lc, q, cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur), acc, dt, da_lds, da_stride);
 }
 
 template <int LPR, int VEC, bool WRITE_DZ, int LPH = 0, int CR = 0, bool DA = false>
@@ -307,140 +296,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CR > 0 ? (D
   }
 }
 
-// Fix-up of cut rows (same scheme as gat_fwd_fixup_kernel): a work-group screens FIX_SCREEN slots, the
-// owner slot of a cut row is the one where the row starts; its pieces tail(k), head(k+1), ..., head(k_e)
-// are summed by the 4 waves x EPW lane groups and combined through LDS in a fixed order.
-template <int LPR, int VEC>
-__global__ __launch_bounds__(256) void gat_bwd_col_fixup_kernel(ColArgs a) {
+// Merge of one cut row (the counterpart of fwd_merge_row): its pieces tail(k), head(k + 1), ..., head(k + npieces - 1) are
+// dealt round-robin to nw (1, or the NW waves of the work-group when `wide`) waves x G lane groups, PF records in flight each,
+// summed inside a wave with shuffles and across waves through LDS, always in the same order.
+// G: a wide row has the whole wave (64 / LPR lane groups); otherwise GP lane groups share a row and 64 / LPR / GP rows lie side
+// by side in the wave, each lane group with its own k, r, npieces (the packed entries of the list).  `wide` is work-group
+// uniform and then every wave of the work-group calls; a row that is not wide is merged by the one wave that calls, as wave 0.
+template <int LPR, int VEC, int NW, int GP = 64 / LPR>
+__device__ __forceinline__ void col_merge_row(const ColArgs& a, const LaneCols<VEC>& lc, float* fix_sm, int64_t k, int r,
+                                              int npieces, bool wide, int w) {
   constexpr int EPW = 64 / LPR;
   constexpr int PF = (VEC == 1) ? 4 : 2;
-  extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [4][R + 2H]
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t kbase = (int64_t)blockIdx.x * FIX_SCREEN;
-  const int64_t nslots = num_slots(a.g);
-  int my_r = 0, my_end = 0;
-  bool owner = false;
-  if (lane < FIX_SCREEN && kbase + lane < nslots) {
-    int64_t e0, e1;
-    slot_range(a.g, kbase + lane, &e0, &e1);
-    my_r = a.g.rc[e1 - 1].x;
-    my_end = a.g.rowptr[my_r + 1];
-    owner = (int64_t)my_end > e1 && (int64_t)a.g.rowptr[my_r] >= e0;
-  }
-  unsigned long long todo = __ballot(owner);
-  const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
-  const int slot = lane / LPR;
-  const int64_t PS = a.rs.R + 2 * a.rs.H;
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int64_t k = kbase + src;
-    const int r = __shfl(my_r, src);
-    const int64_t row_end = __shfl(my_end, src);
-    const int64_t k_e = slot_of(a.g, row_end - 1);
-    const int npieces = (int)(k_e - k) + 1;
-    const bool wide = npieces > EPW * PF;
-    float4 acc[VEC];
-    float dt[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); dt[v] = 0.f; }
-    if (wide || w == 0) {
-      const int nw = wide ? 4 : 1;
-      for (int q = (wide ? w : 0) * EPW * PF + slot; q < npieces; q += nw * EPW * PF) {
-        float4 xp[PF][VEC];
-        float tp[PF][VEC];
-#pragma unroll
-        for (int f = 0; f < PF; ++f) {
-          const int qq = q + f * EPW;
-          const int qc = qq < npieces ? qq : q;
-          const float* p = a.part + (qc == 0 ? 2 * k + 1 : 2 * (k + qc)) * PS;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) {
-            xp[f][v] = ld4(p + lc.cofs[v]); tp[f][v] = p[a.rs.R + lc.head[v]];
-          }
-        }
-#pragma unroll
-        for (int f = 0; f < PF; ++f)
-          if (q + f * EPW < npieces) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-              acc[v].x += xp[f][v].x; acc[v].y += xp[f][v].y; acc[v].z += xp[f][v].z; acc[v].w += xp[f][v].w;
-              dt[v] += tp[f][v];
-            }
-          }
-      }
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        acc[v] = slot_sum4<LPR>(acc[v]);
-        dt[v] = slot_sum<LPR>(dt[v]);
-      }
-    }
-    if (wide) {
-      if (slot == 0) {
-        float* p = fix_sm + w * PS;
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (lc.valid[v]) {
-            st4(p + lc.cofs[v], acc[v]);
-            if (((lc.cofs[v] >> 2) & (a.rs.lph - 1)) == 0) p[a.rs.R + lc.head[v]] = dt[v];
-          }
-      }
-      __syncthreads();
-      if (w == 0 && slot == 0) {
-#pragma unroll
-        for (int ww = 1; ww < 4; ++ww) {
-          const float* p = fix_sm + ww * PS;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) {
-            const float4 x = ld4(p + lc.cofs[v]);
-            acc[v].x += x.x; acc[v].y += x.y; acc[v].z += x.z; acc[v].w += x.w;
-            dt[v] += p[a.rs.R + lc.head[v]];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (w == 0 && slot == 0) col_finish<VEC>(a, lc, r, acc, dt);
-  }
-}
-
-// list-driven variant: entry q of g.cut = (owner slot k, row, pieces); the first n_cut_wide entries (long
-// chains) get a whole work-group each, the others one wave each.
-// (the body, for work-group `bid` of the fix-up's grid: also run by the leading work-groups of gat_bwd_col_finish_kernel)
-template <int LPR, int VEC>
-__device__ __forceinline__ void col_fixup_list_body(const ColArgs& a, const int bid) {
-  constexpr int EPW = 64 / LPR;
-  constexpr int PF = (VEC == 1) ? 4 : 2;
-  constexpr int RPW = fix_rows_per_wave(LPR), GP = EPW / RPW;   // packed entries: RPW rows per wave, GP lane groups each
-  extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [FIX_LIST_WAVES][R + 2H]
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const bool wide = bid < a.g.n_cut_wide;   // (block-uniform)
-  const int slot = lane / LPR;
+  const int slot = (threadIdx.x & 63) / LPR;
   const int G = wide ? EPW : GP, g = slot % G;
-  const int q0 = wide ? bid
-                      : a.g.n_cut_wide + ((bid - a.g.n_cut_wide) * FIX_LIST_WAVES + w) * RPW + slot / GP;
-  const bool have = q0 < a.g.n_cut;
-  const int qe = have ? q0 : a.g.n_cut - 1;
-  const int64_t k = a.g.cut[3 * qe];
-  const int r = a.g.cut[3 * qe + 1];
-  const int npieces = have ? a.g.cut[3 * qe + 2] : 0;
-  const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
   const int64_t PS = a.rs.R + 2 * a.rs.H;
-  const int wsel = wide ? w : 0;   // wave index inside the merge; a lone wave plays wave 0
   float4 acc[VEC];
   float dt[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); dt[v] = 0.f; }
   {
-    const int nw = wide ? FIX_LIST_WAVES : 1;
+    const int nw = wide ? NW : 1;
     for (int q = (wide ? w : 0) * G * PF + g; q < npieces; q += nw * G * PF) {
       float4 xp[PF][VEC];
       float tp[PF][VEC];
 #pragma unroll
       for (int f = 0; f < PF; ++f) {
         const int qq = q + f * G;
-        const int qc = qq < npieces ? qq : q;
-        const float* p = a.part + (qc == 0 ? 2 * k + 1 : 2 * (k + qc)) * PS;
+        const int qc = qq < npieces ? qq : q;   // clamped: the loads stay unconditional
+        const float* p = a.part + piece_record(k, qc) * PS;
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
           xp[f][v] = ld4(p + lc.cofs[v]); tp[f][v] = p[a.rs.R + lc.head[v]];
@@ -483,7 +366,7 @@ __device__ __forceinline__ void col_fixup_list_body(const ColArgs& a, const int 
     __syncthreads();
     if (w == 0 && slot == 0) {
 #pragma unroll
-      for (int ww = 1; ww < FIX_LIST_WAVES; ++ww) {
+      for (int ww = 1; ww < NW; ++ww) {
         const float* p = fix_sm + ww * PS;
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -495,7 +378,42 @@ __device__ __forceinline__ void col_fixup_list_body(const ColArgs& a, const int 
     }
     __syncthreads();
   }
-  if (wsel == 0 && g == 0 && npieces > 0) col_finish<VEC>(a, lc, r, acc, dt);
+  if (w == 0 && g == 0 && npieces > 0) col_finish<VEC>(a, lc, r, acc, dt);
+}
+
+// Fix-up of cut rows without a list (same scheme as gat_fwd_fixup_kernel): a work-group screens FIX_SCREEN slots and its 4 waves
+// merge every cut row they own in turn.
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void gat_bwd_col_fixup_kernel(ColArgs a) {
+  constexpr int EPW = 64 / LPR;
+  constexpr int PF = (VEC == 1) ? 4 : 2;
+  extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [4][R + 2H]
+  const int w = threadIdx.x >> 6;
+  const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
+  screen_cut_rows(a.g, (int64_t)blockIdx.x * FIX_SCREEN, num_slots(a.g), [&](int64_t k, int r, int npieces) {
+    const bool wide = npieces > EPW * PF;  // more pieces than one wave takes in a single round
+    if (wide || w == 0) col_merge_row<LPR, VEC, 4>(a, lc, fix_sm, k, r, npieces, wide, w);
+  });
+}
+
+// list-driven variant: entry q of g.cut = (owner slot k, row, pieces); the first n_cut_wide entries (long
+// chains) get a whole work-group each, the others are packed fix_rows_per_wave(LPR) to a wave.
+// (the body, for work-group `bid` of the fix-up's grid: also run by the leading work-groups of gat_bwd_col_finish_kernel)
+template <int LPR, int VEC>
+__device__ __forceinline__ void col_fixup_list_body(const ColArgs& a, const int bid) {
+  constexpr int RPW = fix_rows_per_wave(LPR), GP = 64 / LPR / RPW;
+  extern __shared__ __attribute__((aligned(16))) float fix_sm[];  // [FIX_LIST_WAVES][R + 2H]
+  const int w = threadIdx.x >> 6;
+  const bool wide = bid < a.g.n_cut_wide;   // (block-uniform)
+  const int q0 = wide ? bid
+                      : a.g.n_cut_wide + ((bid - a.g.n_cut_wide) * FIX_LIST_WAVES + w) * RPW + ((threadIdx.x & 63) / LPR) / GP;
+  const bool have = q0 < a.g.n_cut;
+  const int qe = have ? q0 : a.g.n_cut - 1;
+  const int64_t k = a.g.cut[3 * qe];
+  const int r = a.g.cut[3 * qe + 1];
+  const int npieces = have ? a.g.cut[3 * qe + 2] : 0;
+  const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
+  col_merge_row<LPR, VEC, FIX_LIST_WAVES, GP>(a, lc, fix_sm, k, r, npieces, wide, wide ? w : 0);
 }
 
 template <int LPR, int VEC>
@@ -532,21 +450,9 @@ __global__ __launch_bounds__(64 * FIX_LIST_WAVES) void gat_bwd_col_finish_kernel
 using namespace pygat;
 
 
-// register / scratch footprint of a kernel of this file as the loaded code object reports it (pygat_kernel_footprint)
-static int footprint_of(const void* fn, int* regs, int* scratch) {
-  hipFuncAttributes at;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    pygat::set_error("kernel_footprint: %s", hipGetErrorString(e));
-    return PYGAT_EHIP;
-  }
-  *regs = at.numRegs; *scratch = (int)at.localSizeBytes;
-  return PYGAT_OK;
-}
 namespace pygat {
-int footprint_k4_headline_da(int* regs, int* scratch) {
-  return footprint_of(reinterpret_cast<const void*>(&gat_bwd_col_kernel<32, 1, false, 4, 128, true>), regs, scratch);
+int footprint_k4_headline_da(int* regs, int* scratch) {   // (pygat_kernel_footprint)
+  return kernel_footprint_of(reinterpret_cast<const void*>(&gat_bwd_col_kernel<32, 1, false, 4, 128, true>), regs, scratch);
 }
 }  // namespace pygat
 
@@ -602,10 +508,8 @@ static int backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, int
     a.dWh = dWh + (int64_t)gh * Fp; a.dt = dt + gh; a.part = (float*)part;
     int lpr, vec;
     pick_lanes(a.rs, &lpr, &vec);
-    // narrow rows (a wave carries 8-64 slots, the whole grid is a few ten waves per SIMD): one-wave work-groups, so that a
-    // SIMD slot is refilled as soon as ITS wave ends instead of when the slowest of four does
-    const unsigned bt = (vec == 1 && lpr <= 8) ? (unsigned)narrow_block() : 256u;
-    const unsigned blocks = (unsigned)cdiv(cdiv(nslots, 64 / lpr), bt / 64);
+    const MainGrid mg = main_grid(nslots, lpr, vec);
+    const unsigned bt = mg.bt, blocks = mg.blocks;
     const size_t da_lds = da_part ? 2 * (size_t)bt * sizeof(float4) : 0;
     if (!do_main) {   // (the fix-up phase alone)
     } else if (dz_t) {
@@ -628,16 +532,15 @@ static int backward_col(const pygat_graph* gT, const int32_t* perm_t, int H, int
     }
     PYGAT_CHECK_LAUNCH("gat_backward_col");
     if (!do_fix) continue;
-    const size_t fix_lds = (a.g.cut ? FIX_LIST_WAVES : 4) * (size_t)(a.rs.R + 2 * a.rs.H) * sizeof(float);
-    if (a.g.cut) {
-      if (a.g.n_cut > 0) {
-        const unsigned fb = (unsigned)(a.g.n_cut_wide + cdiv(a.g.n_cut - a.g.n_cut_wide, FIX_LIST_WAVES * fix_rows_per_wave(lpr)));
-        PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_bwd_col_fixup_list_kernel<LPR, VEC>), dim3(fb),
-                                                          dim3(64 * FIX_LIST_WAVES), fix_lds, st, a));
-      }
+    const FixGrid fg = fixup_grid(a.g, lpr);
+    const size_t fix_lds = fg.waves * (size_t)(a.rs.R + 2 * a.rs.H) * sizeof(float);
+    if (fg.blocks == 0) continue;   // (an empty list)
+    if (fg.listed) {
+      PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_bwd_col_fixup_list_kernel<LPR, VEC>), dim3(fg.blocks),
+                                                        dim3(64 * fg.waves), fix_lds, st, a));
     } else {
-      PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_bwd_col_fixup_kernel<LPR, VEC>),
-                                                        dim3((unsigned)cdiv(nslots, FIX_SCREEN)), dim3(256), fix_lds, st, a));
+      PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((gat_bwd_col_fixup_kernel<LPR, VEC>), dim3(fg.blocks),
+                                                        dim3(64 * fg.waves), fix_lds, st, a));
     }
     PYGAT_CHECK_LAUNCH("gat_backward_col_fixup");
   }
@@ -698,7 +601,7 @@ extern "C" int pygat_gat_backward_col_finish(const pygat_graph* gT, int H, int F
   t.row_first = row_first; t.n_rows = n_rows; t.Fo = Fo; t.flags = flags & PYGAT_F_ELU; t.G = G; t.y = y; t.urow = user_row; t.ds = ds;
   int lpr, vec;
   pick_lanes(a.rs, &lpr, &vec);
-  const int fb = a.g.n_cut > 0 ? (int)(a.g.n_cut_wide + cdiv(a.g.n_cut - a.g.n_cut_wide, FIX_LIST_WAVES * fix_rows_per_wave(lpr))) : 0;
+  const int fb = (int)fixup_grid(a.g, lpr).blocks;   // (listed: pygat_gat_backward_col_phases_ok)
   const int64_t tb = cdiv((int64_t)n_rows * (a.rs.R / 4), 64 * FIX_LIST_WAVES);
   PYGAT_REQUIRE(fb + tb < ((int64_t)1 << 31), "gat_backward_col_finish: grid too large");
   const size_t fix_lds = FIX_LIST_WAVES * (size_t)(a.rs.R + 2 * a.rs.H) * sizeof(float);

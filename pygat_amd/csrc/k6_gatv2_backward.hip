@@ -72,12 +72,10 @@ __global__ __launch_bounds__(256) void gat2_bwd_row_kernel(V2Args a) {
     acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   if (active) {
-    int64_t e0, e1;
-    slot_range(a.g, k, &e0, &e1);
+    const SlotView sl = open_slot_chain(a.g, k);
+    const int64_t e0 = sl.e0, e1 = sl.e1;
     const int2* __restrict__ rc = a.g.rc;
-    const int r_first = rc[e0].x;
-    const bool head_partial = a.g.rowptr[r_first] < e0;
-    int cur = r_first;
+    int cur = sl.r_first;
     auto flush = [&](int i, bool is_head, bool is_tail) {   // a whole row: added into dWhi_i = dWW[i, :R] (the column pass wrote it)
       if (is_head || is_tail) {
         float* dst = a.part + (2 * k + (is_head ? 0 : 1)) * (int64_t)R;
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_row_kernel(V2Args a) {
       for (int u = 0; u < U; ++u) {
         if (e + u < e1) {
           if (p[u].x != cur) {
-            flush(cur, cur == r_first && head_partial, false);
+            flush(cur, slot_head_partial(sl, cur), false);
             cur = p[u].x;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_row_kernel(V2Args a) {
         }
       }
     }
-    flush(cur, cur == r_first && head_partial, a.g.rowptr[cur + 1] > e1);
+    flush(cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur));
   }
   // da: lane groups -> wave (shuffles) -> work-group (LDS) -> one record per work-group, fixed order
 #pragma unroll
@@ -156,11 +154,8 @@ __global__ __launch_bounds__(256) void gat2_rowsum_fixup_kernel(V2Args a, int wi
   const int64_t k = idx / width;
   const int c = (int)(idx % width);
   if (k >= num_slots(a.g)) return;
-  int64_t e0, e1;
-  slot_range(a.g, k, &e0, &e1);
-  const int r = a.g.rc[e1 - 1].x;
-  const int64_t row_end = a.g.rowptr[r + 1];
-  if (row_end <= e1 || (int64_t)a.g.rowptr[r] < e0) return;
+  int r, row_end;
+  if (!slot_owns_cut_row(a.g, k, &r, &row_end)) return;
   const int64_t k_e = slot_of(a.g, row_end - 1);
   float acc = a.part[(2 * k + 1) * (int64_t)width + c];
   for (int64_t kk = k + 1; kk <= k_e; ++kk) acc += a.part[(2 * kk) * (int64_t)width + c];
@@ -224,8 +219,8 @@ __global__ __launch_bounds__(256) void gat2_bwd_col_kernel(V2Args a) {
   const int lane = threadIdx.x & 63;
   const int64_t k = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
   if (k >= a.g.kn) return;
-  int64_t e0, e1;
-  slot_range(a.g, k, &e0, &e1);
+  const SlotView sl = open_slot_chain(a.g, k);
+  const int64_t e0 = sl.e0, e1 = sl.e1;
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(a.rs);
   const int H = a.rs.H, R = a.rs.R;
   const int64_t LW = 2 * (int64_t)R, LG = 2 * (int64_t)R + 4 * H;
@@ -239,9 +234,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_col_kernel(V2Args a) {
     accA[v] = make_float4(0.f, 0.f, 0.f, 0.f);
     accJ[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  const int r_first = rc[e0].x;
-  const bool head_partial = a.g.rowptr[r_first] < e0;
-  int cur = r_first;
+  int cur = sl.r_first;
   auto flush = [&](int j, bool is_head, bool is_tail) {
     if (is_head || is_tail) {
       float* dst = a.part + (2 * k + (is_head ? 0 : 1)) * LW;
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_col_kernel(V2Args a) {
     for (int u = 0; u < U; ++u) {
       if (e + u < e1) {
         if (p[u].x != cur) {
-          flush(cur, cur == r_first && head_partial, false);
+          flush(cur, slot_head_partial(sl, cur), false);
           cur = p[u].x;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) { accA[v] = make_float4(0.f, 0.f, 0.f, 0.f); accJ[v] = make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -297,7 +290,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_col_kernel(V2Args a) {
       }
     }
   }
-  flush(cur, cur == r_first && head_partial, a.g.rowptr[cur + 1] > e1);
+  flush(cur, slot_head_partial(sl, cur), slot_tail_partial(a.g, sl, cur));
 }
 
 }  // namespace pygat
