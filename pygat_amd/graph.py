@@ -398,8 +398,12 @@ class CSRGraph:
             raise ValueError("adjacency must be square [N,N]")
         if not adj.is_cuda:
             raise ValueError("adjacency must live on the GPU (there is no CPU path)")
-        a = adj if (adj.dtype == torch.float32 and adj.stride(1) == 1) else adj.float().contiguous()
-        n, ld, m = a.shape[0], a.stride(0), (1 if mode == "positive" else 0)
+        m = 1 if mode == "positive" else 0
+        if adj.dtype == torch.float32:
+            a = adj if adj.stride(1) == 1 else adj.contiguous()
+        else:      # the 0/1 mask in adj's OWN dtype: a float64 1e-60 is an entry, and would be 0 after a conversion to fp32
+            a = ((adj > 0) if m else (adj != 0)).float().contiguous()
+        n, ld = a.shape[0], a.stride(0)
         dev = a.device
         with torch.cuda.device(dev):
             counts = torch.empty(n, dtype=torch.int32, device=dev)

@@ -85,7 +85,13 @@ def test_dense_to_csr_and_perm(pg):
     adj2 = adj.clone(); adj2[0, 1] = adj2[1, 0] = -1.0
     gp = pg.CSRGraph.from_dense(adj2.cuda(), "positive")
     gn = pg.CSRGraph.from_dense(adj2.cuda(), "nonzero")
-    assert gn.nnz - gp.nnz in (0, 2) and gn.nnz >= g.nnz
+    # exactly: "positive" drops the two negative entries and nothing else, "nonzero" keeps every entry
+    pos = (adj2 > 0).numpy()
+    assert gn.nnz == int((adj2 != 0).sum()) and gp.nnz == int(pos.sum()) and gn.nnz - gp.nnz == 2
+    assert np.array_equal(gp.fwd.rowptr.cpu().numpy(), np.concatenate([[0], np.cumsum(pos.sum(1))]))
+    assert np.array_equal(gp.fwd.col.cpu().numpy(), np.nonzero(pos)[1])
+    rc = gn.fwd.edge_rc.cpu().numpy()
+    assert np.array_equal(rc, np.stack(np.nonzero((adj2 != 0).numpy()), 1))
 
 
 def test_scan_large(pg):
