@@ -6,6 +6,9 @@
 //               head h) = word (h & 3) of Philox(counter = (col, row, stream_id, h >> 2)) -- four HEADS per call, so
 //               that the sparse kernels, which meet the non-zeros of x one (row, col) at a time, spend one call per
 //               non-zero and four heads instead of one per head (the first layout cost them 4 x the Philox work).
+// tests/philox_ref.py restates the generator, the keep rule of make_rng and the layouts (the flat one of k7_dropout.hip's
+// mask kernels included) in NumPy, and tests/test_gpu_dropout_seeded.py compares the kernels with it bit for bit: a change
+// of a layout changes that file in the same commit.
 #pragma once
 #include "common.h"
 

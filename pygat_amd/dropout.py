@@ -23,7 +23,9 @@ ONE MFMA GEMM with K = H*Fin for all heads.  s,t are re-derived from the dropped
 drawn in-kernel (Philox-4x32-10) from one int64 seed taken from torch's generator; the
 reference's own RNG stream cannot be reproduced bit-for-bit by any other implementation, so
 parity is tested with EXPLICIT masks against the oracle (tests/test_gpu_dropout.py), through
-the same kernels.
+the same kernels.  The seeded masks themselves are deterministic: tests/philox_ref.py rebuilds them
+from the seed in NumPy, and tests/test_gpu_dropout_seeded.py holds the kernels to it bit for bit and
+the seeded level, forward and backward, to the oracle run under those masks.
 """
 from __future__ import annotations
 
