@@ -511,8 +511,10 @@ int pygat_gatv2_attention(int n, int64_t nnz, const int32_t* rowptr, const int32
  * to_internal (NULL: identity) maps a caller node to its table row; t is the [n x H] table pygat_gat_attention left.  A row of
  * exactly one edge has att = 1, a constant: it contributes exactly zero, and neither its table rows nor its rows of A are read.
  * H <= 64.  Fo is only validated (1..256, as every entry point of a level does): the passes work on the per-head score tables and
- * never touch an F'-wide row.  Scratch, the caller's: rec n*H*4 floats (16-byte aligned); part ceil(nnz / 2048) * 5 * H * 3 floats (both passes may
- * share it).  No float atomics, fixed summation order: bitwise reproducible.  alpha = the LeakyReLU slope. */
+ * never touch an F'-wide row.  Scratch, the caller's: rec n*H*4 floats (16-byte aligned); part >= the size
+ * pygat_alpha_grad_workspace_bytes reports (both passes may share it): the partial records of the long rows (csrc/long_rows.h).
+ * No float atomics, fixed summation order: bitwise reproducible.  alpha = the LeakyReLU slope. */
+int pygat_alpha_grad_workspace_bytes(int64_t nnz, int H, size_t* bytes);   /* an error code like the launchers; additive under ABI 16 */
 int pygat_alpha_grad_rows(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, const int32_t* to_internal,
                           int H, int Fo, float alpha, const float* s, const float* t, const float* m, const float* Z,
                           const float* A, float* rec, float* ds2, float* part, void* stream);
@@ -537,8 +539,8 @@ int pygat_alpha_grad_apply(int n_rows, int H, int Fo, const float* a_pad, const 
  * s, t [n x H] = Wh . a_src, Wh . a_dst (pygat_attn_scores); Wh [n x R] as the projection left it; all tables in the caller's node
  * order.  A row of exactly one edge has att = 1: its rows of u are never read and its du is exactly 0.  u_rows = rows of u (and
  * of att / du): it must equal nnz.  R = H * padded F' <= 1024.  ws >= the size pygat_gat_edge_workspace_bytes reports, 16-byte
- * aligned, the caller's (the three walking passes may share it): partial records of the rows (columns) of more than 512
- * edges, one per 2048-edge chunk, merged in chunk order.  No float atomics: bitwise reproducible.  alpha = the LeakyReLU slope. */
+ * aligned, the caller's (the three walking passes may share it): the partial records of the long rows (columns), merged in chunk
+ * order (csrc/long_rows.h).  No float atomics: bitwise reproducible.  alpha = the LeakyReLU slope. */
 int pygat_gat_edge_workspace_bytes(int64_t nnz, int H, int Fo, size_t* bytes);   /* an error code like the launchers: bad sizes are refused */
 int pygat_gat_edge_forward(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, int H, int Fo, float alpha,
                            int flags, const float* Wh, const float* s, const float* t, const float* sk, const float* u,
@@ -585,8 +587,8 @@ int pygat_gat_forward_bf16(const pygat_graph* g, int H, int Fo, float alpha, int
  * where F % 4 == 0 and the tables and their strides are 16-byte multiples, single floats otherwise: any F >= 1 is taken.  Limits,
  * refused with PYGAT_EINVAL: 1 <= H <= 64, F >= 1, H*F <= 1024, 0 <= nnz < 2^31 (n_rows, n_cols are ints).  col / edge_rc are NOT
  * range-checked: the caller validates its pattern once.  ws >= the size pygat_spmm_workspace_bytes reports, 16-byte aligned, the
- * caller's: partial sums of the rows of more than 512 entries, one record per 2048-entry chunk, added in chunk order.  fp32, no float
- * atomics, fixed summation order: bitwise reproducible.  Nothing allocates or synchronises. */
+ * caller's: the partial records of the long rows, added in chunk order (csrc/long_rows.h).  fp32, no float atomics, fixed summation
+ * order: bitwise reproducible.  Nothing allocates or synchronises. */
 int pygat_spmm_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes);   /* an error code like the launchers */
 int pygat_spmm_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
                        int H, int F, const float* val, const float* b, int64_t ldb, float* out, int64_t ldo,

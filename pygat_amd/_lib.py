@@ -43,7 +43,7 @@ SYMBOLS = [
     "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
     "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
     "pygat_gat_attention", "pygat_gatv2_attention",
-    "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
+    "pygat_alpha_grad_workspace_bytes", "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
     "pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
     "pygat_gat_edge_backward_cols",
     "pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16",
@@ -148,6 +148,7 @@ def _load():
     lib.pygat_gatv2_backward.argtypes = [C.POINTER(Graph), C.POINTER(Graph), p, p, i, i, f, p, p, p, p, p, p, p, p]
     lib.pygat_gat_attention.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, p, p, p, i, p, p, p]
     lib.pygat_gatv2_attention.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p]
+    lib.pygat_alpha_grad_workspace_bytes.argtypes = [i64, i, C.POINTER(sz)]
     lib.pygat_alpha_grad_rows.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p]
     lib.pygat_alpha_grad_cols.argtypes = [i, i64, p, p, p, p, i, i, f, p, p, p, p, p, p]
     lib.pygat_alpha_grad_apply.argtypes = [i, i, i, p, p, p, p, p]
@@ -216,6 +217,13 @@ def check(rc: int, what: str = "") -> None:
     if rc == -1:
         raise ValueError(f"pygat_amd {what}: {msg}")
     raise RuntimeError(f"pygat_amd {what}: {msg} (code {rc})")
+
+
+def alpha_grad_workspace_bytes(nnz: int, H: int) -> int:
+    """Partial records of the long rows of pygat_alpha_grad_rows / _cols (pygat_alpha_grad_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_alpha_grad_workspace_bytes(int(nnz), int(H), C.byref(n)), "alpha_grad_workspace_bytes")
+    return n.value
 
 
 def edge_workspace_bytes(nnz: int, H: int, f_out: int) -> int:

@@ -10,19 +10,14 @@
 // internal node order: `map` (caller node -> table row) is applied to both ends of every edge, as K13 does.
 //
 // Work split.  One WAVE per row (column): its lanes cover (edge, head) pairs -- lane l works on head l % H, so the [E x H]
-// gradient is read in consecutive floats -- and the lanes of a head are summed in a fixed order.  A row of more than
-// AG_LONG edges (R-MAT: up to 26 779) would serialise on one wave: a first launch cuts the edge array into chunks of
-// AG_CHUNK edges, a work-group sums the piece of every long row that meets its chunk and leaves one partial record per
-// (chunk, piece); the row's wave then adds the records in chunk order.  No float atomics, every sum in a fixed order: two
-// runs give the same bits.  A row with exactly one edge has alpha = 1, a constant: it contributes exactly zero and neither
-// its tables nor its rows of A are read (the row pass marks it with Z = 0 in its record, the column pass tests that first).
-#include "common.h"
+// gradient is read in consecutive floats -- and the lanes of a head are summed in a fixed order.  A long row (R-MAT: up to
+// 26 779 edges) goes through partial records (the rule of long_rows.h), four waves per chunk: they walk the piece of a long row
+// edge-interleaved and are added through LDS in wave order; a record is three sums per head, and records add.  No float atomics,
+// every sum in a fixed order: two runs give the same bits.  A row with exactly one edge has alpha = 1, a constant: it contributes
+// exactly zero and neither its tables nor its rows of A are read (the row pass marks it with Z = 0, the column pass tests that).
+#include "long_rows.h"
 
 namespace pygat {
-
-constexpr int AG_CHUNK = 2048;                      // edges per chunk of the long-row launch
-constexpr int AG_LONG = 512;                        // rows / columns of more edges than this go through partial records
-constexpr int AG_SLOTS = AG_CHUNK / AG_LONG + 1;    // long rows that can meet one chunk: one running in + those that start in it
 
 __device__ __forceinline__ float lrelu14(float z, float alpha) { return z > 0.f ? z : alpha * z; }
 
@@ -38,7 +33,7 @@ struct AlphaGradArgs {
   const float* A;              // dL/d alpha [nnz x H]
   float* rec;                  // [n x H x 4] = (s, m, Z, c) per node and head; Z = 0: a row that contributes nothing
   float* out;                  // ds' (row pass) / dt' (column pass), [n x H]
-  float* part;                 // [chunks x AG_SLOTS x H x 3]
+  float* part;                 // [long_records(nnz) x H x 3]
 };
 
 // what a lane keeps of the row (column) it works for, for its head
@@ -93,33 +88,15 @@ __device__ __forceinline__ float head_sum(float v, int lane, int H, int G) {
   return tot;
 }
 
-__device__ __forceinline__ int long_slot(int64_t start, int64_t chunk_first) {
-  return start < chunk_first ? 0 : 1 + (int)((start - chunk_first) / AG_LONG);
-}
-
-// launch 1: per chunk of AG_CHUNK edges, the partial sums of every long row over its edges inside the chunk
+// launch 1: per chunk, the partial sums of every long row over its edges inside the chunk; the four waves find the same rows
 template <bool COL>
 __global__ __launch_bounds__(256) void alpha_grad_long_kernel(AlphaGradArgs g) {
-  __shared__ int owner[AG_SLOTS];
   __shared__ float red[4][64][3];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t c0 = (int64_t)blockIdx.x * AG_CHUNK;
-  const int64_t c1 = c0 + AG_CHUNK < g.nnz ? c0 + AG_CHUNK : g.nnz;
-  if (tid < AG_SLOTS) owner[tid] = -1;
-  __syncthreads();
-  for (int64_t e = c0 + tid; e < c1; e += 256) {
-    const int r = g.rc[e].x;
-    const int64_t start = g.rowptr[r];
-    if ((e == c0 || start == e) && (int64_t)g.rowptr[r + 1] - start > AG_LONG) owner[long_slot(start, c0)] = r;
-  }
-  __syncthreads();
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const int H = g.H, h = lane % H;
   const int64_t step = 4 * (g.G / H);
-  for (int k = 0; k < AG_SLOTS; ++k) {
-    const int r = owner[k];                                  // (uniform in the work-group)
-    if (r < 0) continue;
-    const int64_t start = g.rowptr[r], end = g.rowptr[r + 1];
-    const int64_t e0 = start > c0 ? start : c0, e1 = end < c1 ? end : c1;
+  for_long_rows(g.rowptr, g.rc[ch.c0].x, g.rc[ch.c1 - 1].x, ch, [&](int r, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
     float3 acc = make_float3(0.f, 0.f, 0.f);
     if (lane < g.G) {
       const Owner o = load_owner<COL>(g, g.map ? (int64_t)g.map[r] : (int64_t)r, h);
@@ -133,11 +110,11 @@ __global__ __launch_bounds__(256) void alpha_grad_long_kernel(AlphaGradArgs g) {
     if (lane < H) { red[wv][lane][0] = acc.x; red[wv][lane][1] = acc.y; red[wv][lane][2] = acc.z; }
     __syncthreads();
     if (tid < H) {
-      float* p = g.part + (((int64_t)blockIdx.x * AG_SLOTS + k) * H + tid) * 3;
+      float* p = g.part + (long_record(blockIdx.x, slot) * H + tid) * 3;
       for (int c = 0; c < 3; ++c) p[c] = ((red[0][tid][c] + red[1][tid][c]) + red[2][tid][c]) + red[3][tid][c];
     }
     __syncthreads();
-  }
+  });
 }
 
 // launch 2: one wave per row (column)
@@ -159,13 +136,13 @@ __global__ __launch_bounds__(256) void alpha_grad_wave_kernel(AlphaGradArgs g) {
   float3 acc = make_float3(0.f, 0.f, 0.f);
   Owner o;
   o.a = o.b = o.c = 0.f;
-  if (end - start > AG_LONG) {
+  if (end - start > LONG_ROW) {
     if (lane < H) {
       if constexpr (!COL) o = load_owner<COL>(g, q, h);
-      for (int64_t b = start / AG_CHUNK; b <= (end - 1) / AG_CHUNK; ++b) {
-        const float* p = g.part + ((b * AG_SLOTS + long_slot(start, b * AG_CHUNK)) * H + lane) * 3;
+      for_long_records(start, end, [&](int64_t rec) {
+        const float* p = g.part + (rec * H + lane) * 3;
         acc.x += p[0]; acc.y += p[1]; acc.z += p[2];
-      }
+      });
     }
   } else {
     if (lane < g.G && end > start) {
@@ -217,7 +194,7 @@ static int check_common(const char* what, int n, int64_t nnz, const int32_t* row
 
 template <bool COL>
 static void launch_passes(const AlphaGradArgs& g, hipStream_t st) {
-  hipLaunchKernelGGL(alpha_grad_long_kernel<COL>, dim3((unsigned)cdiv(g.nnz, AG_CHUNK)), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(alpha_grad_long_kernel<COL>, dim3((unsigned)long_chunks(g.nnz)), dim3(256), 0, st, g);
   hipLaunchKernelGGL(alpha_grad_wave_kernel<COL>, dim3((unsigned)cdiv(g.n, 4)), dim3(256), 0, st, g);
 }
 
@@ -235,6 +212,12 @@ int footprint_k14(int which, int* regs, int* scratch) {
 }  // namespace pygat
 
 using namespace pygat;
+
+extern "C" int pygat_alpha_grad_workspace_bytes(int64_t nnz, int H, size_t* bytes) {
+  PYGAT_REQUIRE(bytes && nnz > 0 && H > 0 && H <= 64, "alpha_grad_workspace_bytes: null bytes, or nnz=%lld / H=%d out of range", (long long)nnz, H);
+  *bytes = (size_t)(long_records(nnz) * H * 3) * sizeof(float);
+  return PYGAT_OK;
+}
 
 extern "C" int pygat_alpha_grad_rows(int n, int64_t nnz, const int32_t* rowptr, const int32_t* edge_rc, const int32_t* to_internal,
                                      int H, int Fo, float alpha, const float* s, const float* t, const float* m, const float* Z,

@@ -8,20 +8,16 @@
 //   cols      walks the TRANSPOSED pattern: dt_j = sum_i du_ij (du and u of transposed edge k at row perm_t[k]),
 //             dWh_j = sum_i att_ij Gp_i + ds_j a_src + dt_j a_dst, att recomputed from (s_i, m_i, Z_i, t_j, u_ij).
 // Lane mapping of attn_common.h: a group of LPR lanes holds one row (VEC 16-byte chunks per lane), the lanes of a head are
-// consecutive, the per-head dot products are DPP sums.  A row (column) of more than EL_LONG edges would serialise on its lane
-// group: a first launch cuts the edge array into chunks of EL_CHUNK edges, one wave per chunk -- its 64 / LPR lane groups walk
-// the piece of every long row that meets the chunk edge-interleaved, are merged in a fixed butterfly and leave one partial
-// record per (chunk, piece) -- and the row's lane group merges the records in chunk order.  No float atomics, every sum in a
-// fixed order: two runs give the same bits.  A row with exactly one edge has att = 1: its u is never read, its du is exactly
-// 0; the forward marks it with Z = 0 and every later pass tests that first.
+// consecutive, the per-head dot products are DPP sums.  A long row (column) goes through partial records (the rule of
+// long_rows.h), one wave per chunk: its 64 / LPR lane groups walk the piece of a long row edge-interleaved and are merged in a
+// fixed butterfly; a record is [R sums | m | Z], merged by el_merge.  No float atomics, every sum in a fixed order: the same bits.
+// A row with exactly one edge has att = 1: its u is never read, its du is exactly 0; the forward marks it with Z = 0 for later passes.
 #include "attn_common.h"
+#include "long_rows.h"
 #include <string.h>
 
 namespace pygat {
 
-constexpr int EL_CHUNK = 2048;                      // edges per chunk of the long-row launch
-constexpr int EL_LONG = 512;                        // rows / columns of more edges go through partial records
-constexpr int EL_SLOTS = EL_CHUNK / EL_LONG + 1;    // long rows that meet one chunk: one running in, four that start in it
 enum { EL_FWD = 0, EL_ROWS = 1, EL_COLS = 2 };
 
 struct ElArgs {
@@ -40,7 +36,7 @@ struct ElArgs {
   float *out, *hattn, *mo, *Zo;         // forward
   float *Gp, *du, *ds;                  // rows
   float *dt, *dWh;                      // cols
-  float* part;                          // [chunks x EL_SLOTS x pstride]: R sums, then H maxima, then H scalar sums
+  float* part;                          // [long_records(nnz) x pstride]: R sums, then H maxima, then H scalar sums
   int64_t pstride;
 };
 
@@ -62,9 +58,6 @@ __device__ __forceinline__ float4 el_axpy(float p, float4 w, float4 a) {
   return make_float4(fmaf(p, w.x, a.x), fmaf(p, w.y, a.y), fmaf(p, w.z, a.z), fmaf(p, w.w, a.w));
 }
 __device__ __forceinline__ float4 el_scale(float4 a, float f) { return make_float4(a.x * f, a.y * f, a.z * f, a.w * f); }
-__device__ __forceinline__ int el_piece_slot(int64_t start, int64_t chunk_first) {
-  return start < chunk_first ? 0 : 1 + (int)((start - chunk_first) / EL_LONG);
-}
 
 template <int OP, int VEC>
 __device__ __forceinline__ void el_init(ElState<VEC>& st) {
@@ -184,25 +177,15 @@ __device__ __forceinline__ void el_edge(const ElArgs& g, const LaneCols<VEC>& lc
   }
 }
 
-template <int VEC>
-__device__ __forceinline__ float* el_record(const ElArgs& g, int64_t chunk, int slot) {
-  return g.part + (chunk * EL_SLOTS + slot) * g.pstride;
-}
-
-// launch 1: one wave per chunk of EL_CHUNK walked edges; the piece of every long row inside the chunk -> one partial record
+// launch 1: one wave per chunk of walked edges; the piece of every long row inside the chunk -> one partial record
 template <int OP, int LPR, int VEC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void el_long_kernel(ElArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const int64_t c0 = (int64_t)blockIdx.x * EL_CHUNK;
-  const int64_t c1 = c0 + EL_CHUNK < g.nnz ? c0 + EL_CHUNK : g.nnz;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const LaneCols<VEC> lc = lane_cols<LPR, VEC>(g.rs);
   const int lph = g.rs.lph < 64 ? g.rs.lph : 64;
-  const int r_first = g.rc[c0].x, r_last = g.rc[c1 - 1].x;
-  for (int r = r_first; r <= r_last; ++r) {            // (uniform in the wave)
-    const int64_t start = g.rowptr[r], end = g.rowptr[r + 1];
-    if (end - start <= EL_LONG) continue;
-    const int64_t e0 = start > c0 ? start : c0, e1 = end < c1 ? end : c1;
+  for_long_rows(g.rowptr, g.rc[ch.c0].x, g.rc[ch.c1 - 1].x, ch, [&](int r, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
     ElOwner<VEC> own;
     el_load_owner<OP, VEC>(g, lc, r, lph, own);
     ElState<VEC> st;
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void el
       el_merge<OP, VEC>(st, o);
     }
     if (grp == 0) {
-      float* p = el_record<VEC>(g, blockIdx.x, el_piece_slot(start, c0));
+      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         if (!lc.valid[v]) continue;
@@ -233,7 +216,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void el
         }
       }
     }
-  }
+  });
 }
 
 // launch 2: one lane group per row (column)
@@ -252,9 +235,9 @@ __global__ __launch_bounds__(256) void el_row_kernel(ElArgs g) {
   ElState<VEC> st;
   el_init<OP, VEC>(st);
   const bool single = OP != EL_COLS && deg == 1;       // att = 1: u is not read
-  if (deg > EL_LONG) {
-    for (int64_t b = start / EL_CHUNK; b <= (end - 1) / EL_CHUNK; ++b) {
-      const float* p = el_record<VEC>(g, b, el_piece_slot(start, b * EL_CHUNK));
+  if (deg > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
       ElState<VEC> o;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
@@ -264,7 +247,7 @@ __global__ __launch_bounds__(256) void el_row_kernel(ElArgs g) {
         o.z[v] = p[rs.R + H + lc.head[v]];
       }
       el_merge<OP, VEC>(st, o);
-    }
+    });
   } else if (!single) {
     for (int64_t e = start; e < end; ++e) el_edge<OP, VEC>(g, lc, own, e, lph, st);
   }
@@ -341,7 +324,7 @@ template <int OP>
 static void el_launch(const ElArgs& g, hipStream_t st) {
   int lpr, vec;
   pick_lanes(g.rs, &lpr, &vec);
-  const unsigned chunks = (unsigned)cdiv(g.nnz, EL_CHUNK);
+  const unsigned chunks = (unsigned)long_chunks(g.nnz);
   const unsigned blocks = (unsigned)cdiv(g.n, 4 * (64 / lpr));
   PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((el_long_kernel<OP, LPR, VEC>), dim3(chunks), dim3(64), 0, st, g));
   PYGAT_DISPATCH_LANES(lpr, vec, hipLaunchKernelGGL((el_row_kernel<OP, LPR, VEC>), dim3(blocks), dim3(256), 0, st, g));
@@ -400,7 +383,7 @@ extern "C" int pygat_gat_edge_workspace_bytes(int64_t nnz, int H, int Fo, size_t
   const int Fp = padded_width(Fo);
   PYGAT_REQUIRE(bytes, "gat_edge_workspace_bytes: null bytes");
   PYGAT_REQUIRE(nnz > 0 && H > 0 && Fp > 0, "gat_edge_workspace_bytes: nnz=%lld, H=%d or F'=%d out of range", (long long)nnz, H, Fo);
-  *bytes = (size_t)(cdiv(nnz, EL_CHUNK) * EL_SLOTS * el_pstride(H, Fp)) * sizeof(float);
+  *bytes = (size_t)(long_records(nnz) * el_pstride(H, Fp)) * sizeof(float);
   return PYGAT_OK;
 }
 

@@ -10,18 +10,14 @@
 // inside one head -- and CW = 1 for any other F (F = 1 and F = 7 are the reference's own uses; at most 4 floats per lane there, a
 // wider row is walked in windows of 256 floats, grid dimension y).  A wave carries 64 / LPR rows, and
 // every lane group loads the rows of up to four entries before it adds them, in entry order: several gathers in flight per wave.
-// A row of more than SP_LONG entries would serialise on its lane group: a first launch cuts the entry array into chunks of
-// SP_CHUNK entries, one wave per chunk -- its lane groups walk the piece of every long row that meets the chunk entry-interleaved,
-// are added in a fixed butterfly and leave one partial record per (chunk, piece) -- and the row's lane group adds the records in
-// chunk order.  No float atomics, every sum in a fixed order: two runs give the same bits.  A row without entries gets exact zeros.
-#include "common.h"
+// A long row goes through partial records (the rule of long_rows.h), one wave per chunk: its lane groups walk the piece of a long
+// row entry-interleaved and are added in a fixed butterfly; a record is the row's H * F sums, and records add.  No float atomics,
+// every sum in a fixed order: two runs give the same bits.  A row without entries gets exact zeros.
+#include "long_rows.h"
 #include <string.h>
 
 namespace pygat {
 
-constexpr int SP_CHUNK = 2048;                      // entries per chunk of the long-row launch
-constexpr int SP_LONG = 512;                        // rows of more entries go through partial records
-constexpr int SP_SLOTS = SP_CHUNK / SP_LONG + 1;    // long rows that meet one chunk: one running in, four that start in it
 constexpr int SP_MAX_ROW = 1024;                    // floats per row, H * F
 constexpr unsigned SP_SDDMM_MAX_BLOCKS = 1u << 20;  // the entry-parallel launch strides over the rest
 
@@ -32,7 +28,7 @@ struct SpArgs {
   const float *val, *b;
   int64_t ldb, ldo;
   float* out;
-  float* part;                 // [chunks x SP_SLOTS x pstride]
+  float* part;                 // [long_records(nnz) x pstride]
   int64_t pstride;             // H * F rounded up to 4 floats
 };
 
@@ -112,60 +108,34 @@ __device__ __forceinline__ void sp_walk(const SpArgs& g, const SpLane<VEC>& ln, 
   for (; e < e1; e += step) sp_entries<CW, VEC, 1>(g, ln, e, step, acc);
 }
 
-__device__ __forceinline__ int sp_piece_slot(int64_t start, int64_t chunk_first) {
-  return start < chunk_first ? 0 : 1 + (int)((start - chunk_first) / SP_LONG);
-}
-__device__ __forceinline__ float* sp_record(const SpArgs& g, int64_t chunk, int slot) {
-  return g.part + (chunk * SP_SLOTS + slot) * g.pstride;
-}
-// the row that holds entry e: the last r with rowptr[r] <= e (rows without entries are passed over)
-__device__ __forceinline__ int sp_row_of(const int32_t* rowptr, int n, int64_t e) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (rowptr[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// launch 1: one wave per chunk of SP_CHUNK entries; the piece of every long row inside the chunk -> one partial record
+// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record
 template <int CW, int LPR, int VEC>
 __global__ __launch_bounds__(64) void sp_long_kernel(SpArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const int64_t c0 = (int64_t)blockIdx.x * SP_CHUNK;
-  const int64_t c1 = c0 + SP_CHUNK < g.nnz ? c0 + SP_CHUNK : g.nnz;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const SpLane<VEC> ln = sp_lane<CW, LPR, VEC>(g);
-  const int64_t r_first = sp_row_of(g.rowptr, g.n, c0), r_last = sp_row_of(g.rowptr, g.n, c1 - 1);
-  for (int64_t base = r_first; base <= r_last; base += 64) {   // 64 rows screened per step, a lane each
-    const int64_t r = base + lane;
-    const bool lng = r <= r_last && g.rowptr[r + 1] - g.rowptr[r] > SP_LONG;
-    unsigned long long todo = __ballot(lng);
-    while (todo) {                                             // (uniform in the wave)
-      const int64_t row = base + (__ffsll((long long)todo) - 1);
-      todo &= todo - 1;
-      const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-      const int64_t e0 = start > c0 ? start : c0, e1 = end < c1 ? end : c1;
-      float acc[VEC][CW];
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    float acc[VEC][CW];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v)
+#pragma unroll
+      for (int k = 0; k < CW; ++k) acc[v][k] = 0.f;
+    sp_walk<CW, VEC>(g, ln, e0 + grp, e1, EPW, acc);
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
       for (int v = 0; v < VEC; ++v)
 #pragma unroll
-        for (int k = 0; k < CW; ++k) acc[v][k] = 0.f;
-      sp_walk<CW, VEC>(g, ln, e0 + grp, e1, EPW, acc);
+        for (int k = 0; k < CW; ++k) acc[v][k] += __shfl_xor(acc[v][k], off);
+    if (grp == 0) {
+      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
 #pragma unroll
-      for (int off = LPR; off < 64; off <<= 1)                 // lane groups of the wave, a fixed butterfly
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-#pragma unroll
-          for (int k = 0; k < CW; ++k) acc[v][k] += __shfl_xor(acc[v][k], off);
-      if (grp == 0) {
-        float* p = sp_record(g, blockIdx.x, sp_piece_slot(start, c0));
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (sp_valid<LPR, VEC>(g, v)) sp_store<CW>(p + ln.ofs[v], acc[v]);
-      }
+      for (int v = 0; v < VEC; ++v)
+        if (sp_valid<LPR, VEC>(g, v)) sp_store<CW>(p + ln.ofs[v], acc[v]);
     }
-  }
+  });
 }
 
 // launch 2: one lane group per row
@@ -182,9 +152,9 @@ __global__ __launch_bounds__(256) void sp_row_kernel(SpArgs g) {
   for (int v = 0; v < VEC; ++v)
 #pragma unroll
     for (int k = 0; k < CW; ++k) acc[v][k] = 0.f;
-  if (end - start > SP_LONG) {
-    for (int64_t c = start / SP_CHUNK; c <= (end - 1) / SP_CHUNK; ++c) {
-      const float* p = sp_record(g, c, sp_piece_slot(start, c * SP_CHUNK));
+  if (end - start > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         float w[CW];
@@ -192,7 +162,7 @@ __global__ __launch_bounds__(256) void sp_row_kernel(SpArgs g) {
 #pragma unroll
         for (int k = 0; k < CW; ++k) acc[v][k] += w[k];
       }
-    }
+    });
   } else {
     sp_walk<CW, VEC>(g, ln, start, end, 1, acc);
   }
@@ -309,8 +279,7 @@ extern "C" int pygat_spmm_workspace_bytes(int64_t nnz, int H, int F, size_t* byt
   PYGAT_REQUIRE(bytes, "spmm_workspace_bytes: null bytes");
   const int rc = sp_check_shape("spmm_workspace_bytes", nnz, H, F);
   if (rc != PYGAT_OK) return rc;
-  const int64_t chunks = nnz > 0 ? cdiv(nnz, SP_CHUNK) : 1;
-  *bytes = (size_t)(chunks * SP_SLOTS * sp_pstride(H, F)) * sizeof(float);
+  *bytes = (size_t)(long_records(nnz) * sp_pstride(H, F)) * sizeof(float);
   return PYGAT_OK;
 }
 
@@ -333,7 +302,7 @@ extern "C" int pygat_spmm_forward(int n_rows, int64_t nnz, const int32_t* rowptr
   sp_pick(H, F, vec16, &cw, &lpr, &vec, &g.NCH, &windows);
   g.n = n_rows; g.H = H; g.F = F; g.nnz = nnz; g.rowptr = rowptr; g.col = col; g.perm = perm; g.val = val; g.b = b;
   g.ldb = ldb; g.ldo = ldo; g.out = out; g.part = static_cast<float*>(ws); g.pstride = sp_pstride(H, F);
-  const unsigned chunks = (unsigned)cdiv(nnz, SP_CHUNK);
+  const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
   if (chunks)

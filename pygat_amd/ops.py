@@ -1123,7 +1123,7 @@ class AlphaGradState:
         A = A.contiguous().float()
         dev, f32 = t.device, torch.float32
         rec = torch.empty(n, H, 4, dtype=f32, device=dev)
-        part = torch.empty(-(-g.nnz // 2048) * 5 * H * 3, dtype=f32, device=dev)
+        part = torch.empty(_lib.alpha_grad_workspace_bytes(g.nnz, H) // 4, dtype=f32, device=dev)
         ds2 = torch.empty(n, H, dtype=f32, device=dev)
         dt2 = torch.empty(n, H, dtype=f32, device=dev)
         f, b = g.fwd, g.bwd

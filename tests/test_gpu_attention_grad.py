@@ -11,6 +11,7 @@ import torch
 
 import parity
 from alpha_grad_case import kink_count, level_ref, src_of
+from long_row_cases import nine_hubs, three_chunk_hub
 from tail_case import _iso_csr
 from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _force, _graph, _hub_graph, _params
 
@@ -22,6 +23,8 @@ ASYM_SEED = {(1, 7): 7, (8, 16): 7, (4, 64): 7}
 ROUTE_SEED, MODEL_SEED, DROPOUT_SEED, SPARSE_SEED = 21, 4, 10, 31
 ODD_SEED = {(3, 8): 308, (6, 16): 616}
 MODEL_INT_SEED = 1
+LONG_ROW_CASES = {"nine_hubs-8x16": (nine_hubs, (8, 16), 816), "nine_hubs-3x8": (nine_hubs, (3, 8), 308),
+                  "three_chunk_hub-8x16": (three_chunk_hub, (8, 16), 817)}
 ROUTE_N = 9000
 
 
@@ -116,6 +119,19 @@ def test_heads_not_a_power_of_two(shape):
     rowptr, col = _asym_graph()
     x, W, a, S = _params(len(rowptr) - 1, 48, H, Fo, seed=ODD_SEED[shape])
     _check(f"grad asym {shape}", rowptr, col, x, W, a, S, False, nan_single=True)
+
+
+@pytest.mark.parametrize("case", list(LONG_ROW_CASES))
+def test_long_row_slots_and_chunks(case):
+    """The long-row rule of csrc/long_rows.h beyond one hub: nine_hubs fills every slot of a chunk in the row and the column pass
+    (3 x 8: the shuffle-loop head_sum inside the long launch), three_chunk_hub merges a row's records from three chunks.  Two runs
+    give the same bits."""
+    pattern, (H, Fo), seed = LONG_ROW_CASES[case]
+    rowptr, col = pattern()
+    x, W, a, _ = _params(len(rowptr) - 1, 48, H, Fo, seed=seed)
+    runs = [_check(f"grad {case}", rowptr, col, x, W, a, None, True) for _ in range(2)]
+    for u, v in zip(*runs):
+        assert torch.equal(u, v)
 
 
 @pytest.mark.parametrize("shape", [(1, 7), (8, 16), (4, 64)], ids=["1x7", "8x16", "4x64"])

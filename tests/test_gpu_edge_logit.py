@@ -17,6 +17,7 @@ from alpha_grad_case import kink_count as plain_kink_count
 from alpha_grad_case import level_ref as plain_ref
 from alpha_grad_case import src_of
 from edge_logit_case import edge_logits, kink_count, level_ref
+from long_row_cases import nine_hubs, three_chunk_hub
 from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _graph, _hub_graph, _params
 
 pytestmark = pytest.mark.gpu
@@ -27,6 +28,9 @@ ODD_SEED = {(3, 8): 308, (6, 16): 616}
 ODD_ASYM_SEED = {(3, 8): 308, (6, 16): 616}
 ASYM_SEED = {(1, 7): 7, (8, 16): 7, (4, 64): 7}
 ZERO_SEED, MASK_SEED, MODEL_SEED = 816, 816, 5
+# pattern, (H, F'), concat, skip, seed
+LONG_ROW_CASES = {"nine_hubs-8x16-concat": (nine_hubs, (8, 16), True, False, 816), "nine_hubs-4x64-mean-skip": (nine_hubs, (4, 64), False, True, 464),
+                  "three_chunk_hub-8x16-concat": (three_chunk_hub, (8, 16), True, False, 816)}
 
 
 def _leaves(x, W, a, S, u, x_grad=True):
@@ -118,6 +122,22 @@ def test_heads_that_do_not_divide_64(shape):
     rowptr, col = _asym_graph()
     x, W, a, S = _params(len(rowptr) - 1, 48, H, Fo, seed=ODD_ASYM_SEED[shape])
     _check(f"edge asym {shape}", rowptr, col, x, W, a, S, edge_logits(len(col), H, ODD_ASYM_SEED[shape] + 1), False)
+
+
+@pytest.mark.parametrize("case", list(LONG_ROW_CASES))
+def test_long_row_slots_and_chunks(case):
+    """The long-row rule of csrc/long_rows.h beyond one hub, in all three passes (both patterns are symmetric): nine_hubs fills
+    every slot of a chunk, three_chunk_hub merges a row's records from three chunks.  Two runs give the same bits."""
+    pattern, (H, Fo), concat, skip, seed = LONG_ROW_CASES[case]
+    rowptr, col = pattern()
+    graph = _graph(rowptr, col)
+    x, W, a, S = _params(len(rowptr) - 1, 48, H, Fo, seed=seed)
+    u = edge_logits(len(col), H, seed + 1)
+    runs = [_check(f"edge {case}", rowptr, col, x, W, a, S if skip else None, u, concat, graph=graph) for _ in range(2)]
+    (g1, o1, _), (g2, o2, _) = runs
+    assert torch.equal(o1, o2)
+    for p, q in zip(g1, g2):
+        assert torch.equal(p, q)
 
 
 @pytest.mark.parametrize("shape", [(1, 7), (8, 16), (4, 64)], ids=["1x7", "8x16", "4x64"])

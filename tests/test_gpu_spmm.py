@@ -15,6 +15,7 @@ import torch
 
 import parity
 from alpha_grad_case import kink_count, level_ref
+from long_row_cases import nine_hubs, three_chunk_hub
 from spmm_case import coo_of, f32, normal, softmax_values, spmm_ref
 from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _graph, _hub_graph, _params
 
@@ -80,10 +81,7 @@ def _asym_coo():
 
 
 def _big_hub_coo():
-    """4 500 nodes, node 7 linked to 4 200 others: a row and a column of three 2048-entry chunks."""
-    from oracle import gat_oracle as O
-    rowptr, col = O.random_symmetric_csr(4500, 4, 9, hub=(7, 4200))
-    assert int(np.diff(rowptr).max()) >= 4097
+    rowptr, col = three_chunk_hub()
     return coo_of(rowptr, col) + (len(rowptr) - 1,)
 
 
@@ -172,6 +170,21 @@ def test_rows_and_columns_of_several_chunks():
     row, col, N = _big_hub_coo()
     _check("three chunks 8x16", row, col, (N, N), *_inputs(row, N, N, 8, 16, seed=600))
     _check("three chunks 1x7", row, col, (N, N), *_inputs(row, N, N, 1, 7, seed=601, heads=False))
+
+
+@pytest.mark.parametrize("shape", [(8, 16), (1, 7)], ids=["8x16", "1x7"])
+def test_every_slot_of_a_chunk(shape):
+    """long_row_cases.nine_hubs: nine rows (and columns) of 521 entries back to back fill slots 1-4, 0-4 and 0-1 of three chunks,
+    in the forward and in db; 1 x 7 without a head axis.  Two runs give the same bits."""
+    import pygat_amd as pg
+    H, F = shape
+    rowptr, col = nine_hubs()
+    row, col, N = coo_of(rowptr, col) + (len(rowptr) - 1,)
+    pattern = pg.EdgePattern.from_indices(torch.stack([row, col]).to(DEV), (N, N))
+    v, b, G = _inputs(row, N, N, H, F, seed=1200 + H * F, heads=H > 1)
+    first = _check(f"nine hubs {shape}", row, col, (N, N), v, b, G, pattern=pattern)
+    for p, q in zip(first, _device_run(pattern, v, b, G)):
+        assert torch.equal(p, q)
 
 
 def test_graph_pattern_matches_indices():
