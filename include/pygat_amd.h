@@ -596,6 +596,32 @@ int pygat_spmm_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int
 int pygat_spmm_grad_values(int64_t nnz, const int32_t* edge_rc, int H, int F, const float* G, int64_t ldg,
                            const float* b, int64_t ldb, float* dval, void* stream);
 
+/* ------------------------------------------------ K18: a row softmax over per-entry logits as an op of its own (csrc/k18_edge_softmax.hip)
+ * Additive under ABI 16 (no existing entry point changes).  The reference's layers.py:145-150,160 (attention dropout off) for H heads:
+ * with i_k the group of entry k -- its row (side 0) or its column (side 1) --
+ *   rows        m[i, h] = max_{k in group i} l[k, h],  Z[i, h] = sum_{k in group i} exp(l[k, h] - m[i, h])
+ *   apply       alpha[k, h] = exp(l[k, h] - m[i_k, h]) / Z[i_k, h]
+ *   grad_rows   c[i, h] = sum_{k in group i} alpha[k, h] G[k, h]
+ *   grad_apply  dl[k, h] = alpha[k, h] (G[k, h] - c[i_k, h])
+ * logits, alpha, G, dlogits are [nnz x H] in the CALLER's entry order.  rowptr [n_rows + 1] and perm [nnz] are the CSR of the grouping
+ * side: perm[k] = the caller's entry index of CSR position k (NULL: k itself); pass the column-sorted pattern and its n_cols to group by
+ * column.  The entry-parallel passes read the group of entry k from half `side` of edge_rc [nnz][2] = (row, col).  m, Z, c are
+ * [n_rows x H]; a group without entries gets m = Z = c = 0.  A group of one entry gets alpha = 1.0 and dl = 0.0 exactly.  Logits are
+ * finite floats of any magnitude.  Limits, refused with PYGAT_EINVAL: 1 <= H <= 64, 0 <= nnz < 2^31, side 0 or 1, n_rows < 0 or
+ * n_rows == 0 with entries, null pointers (perm excepted; the message names the pointer); nnz == 0 is a successful no-op.  perm / edge_rc are NOT range-checked: the caller validates its pattern once.
+ * ws >= the size pygat_edge_softmax_workspace_bytes reports = 5 records of 2 H floats per 2048-entry chunk, 16-byte aligned, the caller's
+ * (both group passes may share it): the partial (m, Z) or c records of the long rows, merged in chunk order (csrc/long_rows.h).  fp32, no
+ * float atomics, fixed summation order: bitwise reproducible.  Nothing allocates or synchronises. */
+int pygat_edge_softmax_workspace_bytes(int64_t nnz, int H, size_t* bytes);   /* an error code like the launchers */
+int pygat_edge_softmax_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* perm, int H,
+                            const float* logits, float* m, float* Z, void* ws, void* stream);
+int pygat_edge_softmax_apply(int64_t nnz, const int32_t* edge_rc, int side, int H, const float* logits,
+                             const float* m, const float* Z, float* alpha, void* stream);
+int pygat_edge_softmax_grad_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* perm, int H,
+                                 const float* alpha, const float* G, float* c, void* ws, void* stream);
+int pygat_edge_softmax_grad_apply(int64_t nnz, const int32_t* edge_rc, int side, int H, const float* alpha,
+                                  const float* G, const float* c, float* dlogits, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

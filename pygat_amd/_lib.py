@@ -48,6 +48,8 @@ SYMBOLS = [
     "pygat_gat_edge_backward_cols",
     "pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16",
     "pygat_spmm_workspace_bytes", "pygat_spmm_forward", "pygat_spmm_grad_values",
+    "pygat_edge_softmax_workspace_bytes", "pygat_edge_softmax_rows", "pygat_edge_softmax_apply", "pygat_edge_softmax_grad_rows",
+    "pygat_edge_softmax_grad_apply",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -163,6 +165,11 @@ def _load():
     lib.pygat_spmm_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
     lib.pygat_spmm_forward.argtypes = [i, i64, p, p, p, i, i, p, p, i64, p, i64, p, p]
     lib.pygat_spmm_grad_values.argtypes = [i64, p, i, i, p, i64, p, i64, p, p]
+    lib.pygat_edge_softmax_workspace_bytes.argtypes = [i64, i, C.POINTER(sz)]
+    lib.pygat_edge_softmax_rows.argtypes = [i, i64, p, p, i, p, p, p, p, p]
+    lib.pygat_edge_softmax_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
+    lib.pygat_edge_softmax_grad_rows.argtypes = [i, i64, p, p, i, p, p, p, p, p]
+    lib.pygat_edge_softmax_grad_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
@@ -244,6 +251,13 @@ def spmm_workspace_bytes(nnz: int, H: int, F: int) -> int:
     """Partial records of the long rows of pygat_spmm_forward (pygat_spmm_workspace_bytes)."""
     n = C.c_size_t(0)
     check(lib.pygat_spmm_workspace_bytes(int(nnz), int(H), int(F), C.byref(n)), "spmm_workspace_bytes")
+    return n.value
+
+
+def edge_softmax_workspace_bytes(nnz: int, H: int) -> int:
+    """Partial records of the long rows of pygat_edge_softmax_rows / _grad_rows (pygat_edge_softmax_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_edge_softmax_workspace_bytes(int(nnz), int(H), C.byref(n)), "edge_softmax_workspace_bytes")
     return n.value
 
 

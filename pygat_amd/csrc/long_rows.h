@@ -1,4 +1,4 @@
-// The long-row rule of the kernels that walk a CSR one lane group (K15, K17) or one wave (K14) per row.  A row of more than
+// The long-row rule of the kernels that walk a CSR one lane group (K15, K17, K18) or one wave (K14) per row.  A row of more than
 // LONG_ROW entries would serialise on its owner, so it is summed in two launches.  Launch 1 cuts the ENTRY array into chunks of
 // LONG_CHUNK entries, one work-group per chunk, which sums the piece of every long row that meets its chunk into partial record
 // chunk * LONG_SLOTS + slot.  At most LONG_SLOTS long rows meet a chunk: one that runs in from the chunk before (slot 0) and
