@@ -710,7 +710,8 @@ int pygat_elu_logsoftmax_nll_backward(int n, int C, const float* out, int64_t ld
  *   pygat_wgrad_sparse     dW_h = scale * (X .* m_h)^T dWh_h, dWskip_h = ... Gp_h   written as [H x Fin x F'] directly
  * p = 0: no dropout (m = 1, scale = 1).  p > 0: per-head input dropout with the decisions of pygat_dropout_bits -- drawn
  * from (seed, stream_id) per non-zero, or read from explicit `bits` [n x Fin] (H <= 8) -- and scale = 1 / (1 - p); s must
- * be NULL then (scores come from the masked Wh, pygat_attn_scores).  At most 512 output columns (2 R + H). */
+ * be NULL then (scores come from the masked Wh, pygat_attn_scores).  p outside [0, 1] (NaN included) is refused.  At most
+ * 512 output columns (2 R + H). */
 int pygat_project_sparse(int n, int Fin, int H, int Fo, const int32_t* rowptr, const int32_t* col, const float* val,
                          const float* Wcat, int64_t ldw, float p, const void* seed, int stream_id, const unsigned char* bits,
                          float* Wh, float* Sk, float* s, void* stream);

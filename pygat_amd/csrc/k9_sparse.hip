@@ -201,6 +201,8 @@ static int sp_setup(SpArgs* a, const char* what, int n, int Fin, int H, int Fo, 
   a->n = n; a->Fin = Fin; a->H = H; a->Fo = Fo; a->Fp = Fp; a->R = H * Fp; a->has_skip = skip ? 1 : 0; a->with_s = with_s ? 1 : 0;
   a->ncols = a->R * (skip ? 2 : 1) + (with_s ? H : 0);
   a->ptr = ptr; a->idx = idx; a->val = val; a->bits = bits;
+  // (a negative or NaN p used to fall through `p > 0` and run as "no dropout")
+  if (!(p >= 0.f && p <= 1.f)) { set_error("%s: p=%g outside [0,1]", what, (double)p); return PYGAT_EINVAL; }
   a->masked = p > 0.f ? 1 : 0;
   if (a->ncols > 64 * SP_CPL) { set_error("%s: %d output columns exceed %d", what, a->ncols, 64 * SP_CPL); return PYGAT_EINVAL; }
   if (a->masked) {
@@ -260,9 +262,10 @@ extern "C" int pygat_wgrad_sparse(int n, int Fin, int H, int Fo, int nseg, const
   SpArgs a;
   int rc = sp_setup(&a, "wgrad_sparse", n, Fin, H, Fo, colseg, row, val, p, seed, stream_id, bits, Gp != nullptr, false);
   if (rc) return rc;
+  // the size guard first: sizes just under the bound can then be shown to pass it without tables (tests/test_sparse_features_abi.py)
+  PYGAT_REQUIRE(sp_fits_32bit(n, a.R) && (!Gp || sp_fits_32bit(n, ldg)), "wgrad_sparse: the gradient tables exceed 4 GiB (n=%d)", n);
   PYGAT_REQUIRE(nseg >= Fin && seg_col && seg_begin && seg_end && ws && dWh && dW && (!Gp || (dWskip && ldg >= a.R)),
                 "wgrad_sparse: bad arguments");
-  PYGAT_REQUIRE(sp_fits_32bit(n, a.R) && (!Gp || sp_fits_32bit(n, ldg)), "wgrad_sparse: the gradient tables exceed 4 GiB (n=%d)", n);
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
   PYGAT_SP_DISPATCH(sparse_wgrad_kernel, dim3((unsigned)cdiv(nseg, 4)), nseg, seg_col, seg_begin, seg_end, dWh, Gp, ldg, part);

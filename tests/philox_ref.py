@@ -73,7 +73,7 @@ def flat_mask(seed, stream, count, p):
     return _scaled(_flat_keep(seed, stream, count, p), p)
 
 
-def _head_keep(seed, stream, n, Fin, H, p):
+def head_keep(seed, stream, n, Fin, H, p):
     """bool [H, n, Fin]: head h keeps x[i, k]."""
     i, k = np.meshgrid(np.arange(n, dtype=np.uint64), np.arange(Fin, dtype=np.uint64), indexing="ij")
     thresh = np.uint32(threshold(p)[0])
@@ -90,7 +90,7 @@ def head_bits(seed, stream, n, Fin, H, p):
     """uint8 [n, Fin], bit h = head h keeps x[i, k] (H <= 8): the bytes pygat_dropout_bits writes."""
     if not 1 <= H <= 8:
         raise ValueError("head_bits: a byte holds 8 heads")
-    keep = _head_keep(seed, stream, n, Fin, H, p)
+    keep = head_keep(seed, stream, n, Fin, H, p)
     bits = np.zeros((n, Fin), dtype=np.uint8)
     for h in range(H):
         bits |= keep[h].astype(np.uint8) << np.uint8(h)
@@ -113,7 +113,7 @@ def level_masks(seed, p, H, N, Fin, Fo, Fp, E, layout):
     PADDED head-interleaved table [N, H*Fp], the attention mask over [E, H] in the graph's forward CSR edge order."""
     from pygat_amd.dropout import STREAM_X, STREAM_WH, STREAM_ATT
     if layout == "bits":
-        x = _scaled(_head_keep(seed, STREAM_X, N, Fin, H, p), p)
+        x = _scaled(head_keep(seed, STREAM_X, N, Fin, H, p), p)
     elif layout == "wide":
         x = wide_mask(seed, STREAM_X, N, Fin, H, p)
     else:

@@ -261,6 +261,8 @@ CASES = {
     "forced":   (8, 200, 8, False, True, "wide", 5),              # FORCE_WIDE
     "sparse8":  (8, 300, 8, False, True, "sparse", 4),
     "sparse4":  (4, 129, 16, True, False, "sparse", 6),
+    "sparse8x16s": (8, 200, 16, True, True, "sparse", 9),         # 256 masked columns: four per lane (k9_sparse.hip)
+    "sparse8x32s": (8, 200, 32, True, True, "sparse", 5),         # 512 masked columns: eight per lane
 }
 DATA_SEED = {("mfma8", 0.1): 5}       # where a case's seed puts a logit near the kink at another dropout rate
 RUNS = ([(name, 0.6, None) for name in CASES] + [("mfma8", 0.1, None), ("wide9", 0.1, None)]
