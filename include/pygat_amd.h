@@ -622,6 +622,34 @@ int pygat_edge_softmax_grad_rows(int n_rows, int64_t nnz, const int32_t* rowptr,
 int pygat_edge_softmax_grad_apply(int64_t nnz, const int32_t* edge_rc, int side, int H, const float* alpha,
                                   const float* G, const float* c, float* dlogits, void* stream);
 
+/* ------------------------------------------------ K19: fused dot-product attention over an edge pattern (csrc/k19_dot_attention.hip)
+ * Additive under ABI 16 (no existing entry point changes).  For H heads, over a CSR pattern (rowptr [n_rows + 1], col [nnz]):
+ *   forward        s[e, h] = scale <q[i, h], k[j, h]> for entry e = (i, j);  out[i, h, :] = sum_{e in row i} softmax_row(s)[e, h] v[j, h, :]
+ *                  in one pass (an online softmax: nothing per entry is written);  m[i, h] = max_e s[e, h],  Z[i, h] = sum_e exp(s[e, h] -
+ *                  m[i, h]), [n_rows x H], always written: with out they are all backward_rows needs.
+ *   backward_rows  D[i, h] = <G[i, h], out[i, h]>,  p = exp(s - m[i, h]) / Z[i, h],  ds = scale p (<G[i, h], v[j, h]> - D[i, h]);
+ *                  dq[i, h, :] = sum_{e in row i} ds k[j, h, :];  P[e, h] = p and S[e, h] = ds, [nnz x H] in the CALLER's entry order
+ *                  (perm[k] = the caller's entry index of CSR position k, NULL: k itself).  The column side is K17 on the transposed
+ *                  pattern: dk = pygat_spmm_forward(val = S, b = q), dv = pygat_spmm_forward(val = P, b = G).
+ * Rows of q / out / G / dq (n_rows of them) and of k / v are H*F floats, heads side by side, NOT padded, 16-byte aligned, with row
+ * strides >= H*F that are multiples of 4 floats.  Repeated (row, col) pairs are separate entries.  A row without entries gets out = m = Z
+ * = dq = 0 exactly and its G row is not read; a row of one entry (i, j) gets out_i = v_j bit for bit, p = 1 and ds = dq_i = 0 exactly.
+ * Limits, refused with PYGAT_EINVAL before anything is launched: 1 <= H <= 64, F a power of two in 4..256 (zero-padding the columns of
+ * q, k and v to the next allowed F leaves the first F columns of the result unchanged), H*F <= 1024, 0 <= nnz < 2^31, null or misaligned
+ * tables (the message names the argument), short strides.  col / perm are NOT range-checked: the caller validates its pattern once.
+ * ws >= the size pygat_dot_attn_workspace_bytes reports = 5 records of H*F + 2 H floats (rounded up to 4) per 2048-entry chunk,
+ * 16-byte aligned, the caller's (both launchers may share it): the partial (acc, m, Z) or dq records of the long rows, merged in chunk
+ * order (csrc/long_rows.h).  fp32, no float atomics, fixed summation order: bitwise reproducible.  Nothing allocates or synchronises. */
+int pygat_dot_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes);   /* an error code like the launchers */
+int pygat_dot_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float scale,
+                                const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                      int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                      const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m, const float* Z,
+                                      const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, void* ws,
+                                      void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

@@ -50,6 +50,7 @@ SYMBOLS = [
     "pygat_spmm_workspace_bytes", "pygat_spmm_forward", "pygat_spmm_grad_values",
     "pygat_edge_softmax_workspace_bytes", "pygat_edge_softmax_rows", "pygat_edge_softmax_apply", "pygat_edge_softmax_grad_rows",
     "pygat_edge_softmax_grad_apply",
+    "pygat_dot_attn_workspace_bytes", "pygat_dot_attn_forward", "pygat_dot_attn_backward_rows",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -170,6 +171,10 @@ def _load():
     lib.pygat_edge_softmax_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
     lib.pygat_edge_softmax_grad_rows.argtypes = [i, i64, p, p, i, p, p, p, p, p]
     lib.pygat_edge_softmax_grad_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
+    lib.pygat_dot_attn_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
+    lib.pygat_dot_attn_forward.argtypes = [i, i64, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, p, p, p]
+    lib.pygat_dot_attn_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, p, p, i64, p, i64, p,
+                                                 p, p, p]
     u32 = C.c_uint32
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
@@ -258,6 +263,13 @@ def edge_softmax_workspace_bytes(nnz: int, H: int) -> int:
     """Partial records of the long rows of pygat_edge_softmax_rows / _grad_rows (pygat_edge_softmax_workspace_bytes)."""
     n = C.c_size_t(0)
     check(lib.pygat_edge_softmax_workspace_bytes(int(nnz), int(H), C.byref(n)), "edge_softmax_workspace_bytes")
+    return n.value
+
+
+def dot_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
+    """Partial records of the long rows of pygat_dot_attn_forward / _backward_rows (pygat_dot_attn_workspace_bytes)."""
+    n = C.c_size_t(0)
+    check(lib.pygat_dot_attn_workspace_bytes(int(nnz), int(H), int(F), C.byref(n)), "dot_attn_workspace_bytes")
     return n.value
 
 

@@ -1,0 +1,569 @@
+// K19 -- dot_attention: softmax_j(scale q_i . k_j)-weighted sums of v_j over the entries of every row of a sparse pattern, for H heads
+// at once, in one pass, and the row side of its gradient.
+//   forward        s[e, h] = scale <q[i, h], k[j, h]>,  out[i, h] = sum_{e = (i, j)} softmax_row(s)[e, h] v[j, h];  m, Z [n_rows x H] = the
+//                  row's maximum and sum of exp(s - m): with out, all the backward keeps -- nothing per entry
+//   backward_rows  D[i, h] = <G[i, h], out[i, h]>,  p = exp(s - m[i, h]) / Z[i, h],  ds = scale p (<G[i, h], v[j, h]> - D[i, h]),
+//                  dq[i, h] = sum_e ds k[j, h];  P[e, h] = p and S[e, h] = ds at the CALLER's entry index (perm), for the column side:
+//                  dk = spmm^T(S, q), dv = spmm^T(P, G) are two pygat_spmm_forward launches on the transposed pattern (K17, unchanged)
+// Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  Lane mapping as K17's CW = 4 path: a group of LPR
+// lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v.  F / 4 is a power of two, so the chunks of
+// a head sit on LH = F / 4 adjacent lanes of one v, and a head's dot product is a butterfly over them; every lane of a head ends with the
+// same s, m and Z.  q_i is loaded once per row.  Per entry k_j and v_j are gathered, several entries in flight (da_unroll), and folded
+// into an online (m, Z, acc) state per head with one __expf per (entry, head) (K18's es_fold).  A long row goes through partial
+// records (the rule of long_rows.h), one wave per chunk: its lane groups walk the piece entry-interleaved and are merged maximum
+// first -- rescale once, then a fixed butterfly -- and records merge in chunk order by the same rule.  A record is (acc[H F], m[H],
+// Z[H]) forward and the dq row backward.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.  A row
+// without entries gets out = m = Z = dq = 0 exactly; a row of one entry (i, j) gets out_i = v_j bit for bit, p = 1 and ds = dq_i = 0.
+#include "long_rows.h"
+#include <float.h>
+#include <string.h>
+
+namespace pygat {
+
+constexpr int DA_MAX_ROW = 1024;               // floats per row, H * F
+constexpr float DA_SEED = -FLT_MAX;            // running-max seed: finite, so no difference of two maxima is a NaN
+
+struct DaArgs {
+  int n, H, F, NCH, LH;        // rows of the walked pattern; heads; width of a head; chunks of 4 floats per row; lanes per head
+  int64_t nnz;
+  const int32_t *rowptr, *col, *perm;
+  const float *q, *k, *v;
+  int64_t ldq, ldk, ldv;
+  float scale;
+  float* out;                  // forward: written; backward: read
+  int64_t ldo;
+  float *m, *Z;                // [n x H]  forward: written; backward: read
+  const float* G;              // backward only from here
+  int64_t ldg;
+  float* dq;
+  int64_t lddq;
+  float *P, *S;                // [nnz x H], the caller's entry order
+  float* part;                 // [long_records(nnz) x pstride]
+  int64_t pstride;             // H * F + 2 H rounded up to 4 floats
+};
+
+static inline int64_t da_pstride(int H, int F) { return ((int64_t)H * F + 2 * H + 3) & ~(int64_t)3; }
+
+// entries whose k and v rows a lane group has in flight before it folds them (registers: U * VEC * 8).  The forward affords more than
+// the backward, which holds q, G and dq of its row besides: at 8 x 64 (two chunks per lane) a build with 4 entries in both was 0.6 ms
+// faster in the forward and 1.5 ms slower in the backward than one with 2 in both
+__host__ __device__ constexpr int da_unroll(bool bwd, int vec) { return bwd ? (vec == 1 ? 4 : (vec == 2 ? 2 : 1)) : (vec <= 2 ? 4 : 2); }
+
+template <int VEC>
+struct DaLane {
+  int ofs[VEC];      // float offset of the lane's chunk inside a row (0 when the chunk lies beyond the row)
+  int head[VEC];
+  unsigned ok;       // bit v: the chunk lies inside the row
+  unsigned lead;     // bit v: ... and is the first of its head (the lane that stores the head's scalars)
+};
+
+template <int LPR, int VEC>
+__device__ __forceinline__ DaLane<VEC> da_lane(const DaArgs& g) {
+  DaLane<VEC> ln;
+  ln.ok = ln.lead = 0;
+  const int c0 = (threadIdx.x & 63) & (LPR - 1);
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    const int c = c0 + 64 * v;
+    const bool in = c < g.NCH;
+    ln.ofs[v] = in ? 4 * c : 0;
+    ln.head[v] = ln.ofs[v] / g.F;
+    if (in) ln.ok |= 1u << v;
+    if (in && (c & (g.LH - 1)) == 0) ln.lead |= 1u << v;
+  }
+  return ln;
+}
+
+// sum over the lh adjacent lanes of a head (lh a power of two <= LPR): group_sum_rt without the steps a lane shape cannot take
+template <int LPR>
+__device__ __forceinline__ float da_head_sum(float x, int lh) {
+  if constexpr (LPR >= 64) return group_sum_rt(x, lh);
+  if constexpr (LPR >= 2) if (lh >= 2) x += dpp_mov<0xB1>(x);
+  if constexpr (LPR >= 4) if (lh >= 4) x += dpp_mov<0x4E>(x);
+  if constexpr (LPR >= 8) if (lh >= 8) x += dpp_mov<0x141>(x);
+  if constexpr (LPR >= 16) if (lh >= 16) x += dpp_mov<0x140>(x);
+  if constexpr (LPR >= 32) if (lh >= 32) x += __shfl_xor(x, 16);
+  return x;
+}
+
+__device__ __forceinline__ float4 da_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void da_axpy(float4& y, float a, const float4& x) {
+  y.x = fmaf(a, x.x, y.x); y.y = fmaf(a, x.y, y.y); y.z = fmaf(a, x.z, y.z); y.w = fmaf(a, x.w, y.w);
+}
+__device__ __forceinline__ void da_add(float4& y, const float4& x) { y.x += x.x; y.y += x.y; y.z += x.z; y.w += x.w; }
+__device__ __forceinline__ void da_scale(float4& y, float a) { y.x *= a; y.y *= a; y.z *= a; y.w *= a; }
+__device__ __forceinline__ float4 da_shfl_xor(const float4& x, int off) {
+  return make_float4(__shfl_xor(x.x, off), __shfl_xor(x.y, off), __shfl_xor(x.z, off), __shfl_xor(x.w, off));
+}
+
+template <int VEC>
+__device__ __forceinline__ void da_load_row(const float* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) w[v] = ld4(p + ln.ofs[v]);
+}
+template <int VEC>
+__device__ __forceinline__ void da_store_row(float* p, const DaLane<VEC>& ln, const float4 (&w)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v)
+    if (ln.ok >> v & 1) st4(p + ln.ofs[v], w[v]);
+}
+
+// the score of one entry: one rounding of the product, so the forward and the backward see the same bits
+template <int LPR>
+__device__ __forceinline__ float da_score(const DaArgs& g, const float4& q, const float4& k) {
+  return __fmul_rn(g.scale, da_head_sum<LPR>(dot4(q, k), g.LH));
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ forward
+template <int VEC>
+struct DaState {
+  float m[VEC], z[VEC];
+  float4 acc[VEC];
+};
+template <int VEC>
+__device__ __forceinline__ void da_init(DaState<VEC>& st) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) { st.m[v] = DA_SEED; st.z[v] = 0.f; st.acc[v] = da_zero4(); }
+}
+
+// online softmax state of one head and the lane's part of its weighted sum, one __expf per (entry, head) (K18's es_fold)
+__device__ __forceinline__ void da_fold(float& m, float& z, float4& acc, float s, const float4& w) {
+  const float d = s - m;
+  const float ex = __expf(-fabsf(d));
+  const bool up = d > 0.f;
+  const float r = up ? ex : 1.f, p = up ? 1.f : ex;
+  z = fmaf(z, r, p);
+  acc.x = fmaf(acc.x, r, p * w.x); acc.y = fmaf(acc.y, r, p * w.y); acc.z = fmaf(acc.z, r, p * w.z); acc.w = fmaf(acc.w, r, p * w.w);
+  m = up ? s : m;
+}
+
+// (m, z, acc) <- (m, z, acc) (+) (m2, z2, acc2), the earlier entries on the left
+__device__ __forceinline__ void da_merge(float& m, float& z, float4& acc, float m2, float z2, const float4& acc2) {
+  const float mn = fmaxf(m, m2);
+  const float f1 = __expf(m - mn), f2 = __expf(m2 - mn);
+  z = z * f1 + z2 * f2;
+  acc.x = acc.x * f1 + acc2.x * f2; acc.y = acc.y * f1 + acc2.y * f2; acc.z = acc.z * f1 + acc2.z * f2; acc.w = acc.w * f1 + acc2.w * f2;
+  m = mn;
+}
+
+// U gathered entries: the k and v rows of columns src[0..U), loaded before any is used
+template <int VEC, int U>
+struct DaRows {
+  float4 k[U][VEC], v[U][VEC];
+};
+template <int VEC, int U>
+__device__ __forceinline__ void da_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], DaRows<VEC, U>& w) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    da_load_row<VEC>(g.k + (int64_t)src[u] * g.ldk, ln, w.k[u]);
+    da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+  }
+}
+
+template <int LPR, int VEC, int U>
+__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[VEC], const DaRows<VEC, U>& w, DaState<VEC>& st) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) da_fold(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), w.v[u][v]);
+}
+
+// the entries e0, e0 + step, ... < e1 of one row, folded in that order, U at a time: the column indices of the next U are asked for
+// before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather
+template <int LPR, int VEC, int U>
+__device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
+                                            int64_t step, DaState<VEC>& st) {
+  int64_t e = e0;
+  if constexpr (U > 1) {
+    int32_t src[U];
+    bool full = e + (U - 1) * step < e1;
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) src[u] = g.col[e + u * step];
+    }
+    while (full) {
+      DaRows<VEC, U> w;
+      da_gather<VEC, U>(g, ln, src, w);
+      e += U * step;
+      full = e + (U - 1) * step < e1;
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) src[u] = g.col[e + u * step];
+      }
+      da_fwd_fold<LPR, VEC, U>(g, q, w, st);
+    }
+  }
+  for (; e < e1; e += step) {
+    const int32_t src[1] = {g.col[e]};
+    DaRows<VEC, 1> w;
+    da_gather<VEC, 1>(g, ln, src, w);
+    da_fwd_fold<LPR, VEC, 1>(g, q, w, st);
+  }
+}
+
+// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
+template <int LPR, int VEC>
+__global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int HF = g.H * g.F;
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    float4 q[VEC];
+    da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
+    DaState<VEC> st;
+    da_init<VEC>(st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC)>(g, ln, q, e0 + grp, e1, EPW, st);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
+      float mx = st.m[v];
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+      const float f = __expf(st.m[v] - mx);                    // (a lane group without entries: 0 x 0)
+      st.z[v] *= f;
+      da_scale(st.acc[v], f);
+      st.m[v] = mx;
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1) {
+        st.z[v] += __shfl_xor(st.z[v], off);
+        da_add(st.acc[v], da_shfl_xor(st.acc[v], off));
+      }
+    }
+    if (grp == 0) {
+      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
+      da_store_row<VEC>(p, ln, st.acc);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        if (ln.lead >> v & 1) { p[HF + ln.head[v]] = st.m[v]; p[HF + g.H + ln.head[v]] = st.z[v]; }
+    }
+  });
+}
+
+// launch 2: one lane group per row
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
+  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
+  const int HF = g.H * g.F;
+  DaState<VEC> st;
+  da_init<VEC>(st);
+  if (end - start > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        da_merge(st.m[v], st.z[v], st.acc[v], p[HF + ln.head[v]], p[HF + g.H + ln.head[v]], ld4(p + ln.ofs[v]));
+    });
+  } else if (end > start) {
+    float4 q[VEC];
+    da_load_row<VEC>(g.q + row * g.ldq, ln, q);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC)>(g, ln, q, start, end, 1, st);
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (!(ln.ok >> v & 1)) continue;
+    const bool any = end > start;
+    const float z = st.z[v];
+    const float4 a = st.acc[v];
+    st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
+    if (ln.lead >> v & 1) {
+      g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
+      g.Z[row * g.H + ln.head[v]] = z;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- backward, row side
+template <int VEC>
+struct DaRow {                 // what the backward holds of its row
+  float4 q[VEC], G[VEC];
+  float m[VEC], rz[VEC], D[VEC];
+};
+
+template <int LPR, int VEC>
+__device__ __forceinline__ void da_bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, DaRow<VEC>& r) {
+  float4 o[VEC];
+  da_load_row<VEC>(g.q + row * g.ldq, ln, r.q);
+  da_load_row<VEC>(g.G + row * g.ldg, ln, r.G);
+  da_load_row<VEC>(g.out + row * g.ldo, ln, o);
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    r.m[v] = g.m[row * g.H + ln.head[v]];
+    r.rz[v] = 1.f / g.Z[row * g.H + ln.head[v]];
+    r.D[v] = da_head_sum<LPR>(dot4(r.G[v], o[v]), g.LH);
+  }
+}
+
+// the caller's entry index (x H) of CSR position pos
+__device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { return (g.perm ? (int64_t)g.perm[pos] : pos) * g.H; }
+
+template <int LPR, int VEC, int U>
+__device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, const DaRows<VEC, U>& w,
+                                            const int64_t (&ent)[U], float4 (&dq)[VEC]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const float s = da_score<LPR>(g, r.q[v], w.k[u][v]);
+      const float p = __expf(s - r.m[v]) * r.rz[v];
+      const float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+      const float ds = g.scale * p * (dp - r.D[v]);
+      da_axpy(dq[v], ds, w.k[u][v]);
+      if (ln.lead >> v & 1) { g.P[ent[u] + ln.head[v]] = p; g.S[ent[u] + ln.head[v]] = ds; }
+    }
+}
+
+// as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic
+template <int LPR, int VEC, int U>
+__device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, int64_t e0, int64_t e1,
+                                            int64_t step, float4 (&dq)[VEC]) {
+  int64_t e = e0;
+  if constexpr (U > 1) {
+    int32_t src[U];
+    int64_t ent[U], ent_next[U];
+    bool full = e + (U - 1) * step < e1;
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) { src[u] = g.col[e + u * step]; ent_next[u] = da_entry(g, e + u * step); }
+    }
+    while (full) {
+      DaRows<VEC, U> w;
+      da_gather<VEC, U>(g, ln, src, w);
+#pragma unroll
+      for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+      e += U * step;
+      full = e + (U - 1) * step < e1;
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) { src[u] = g.col[e + u * step]; ent_next[u] = da_entry(g, e + u * step); }
+      }
+      da_bwd_fold<LPR, VEC, U>(g, ln, r, w, ent, dq);
+    }
+  }
+  for (; e < e1; e += step) {
+    const int32_t src[1] = {g.col[e]};
+    const int64_t ent[1] = {da_entry(g, e)};
+    DaRows<VEC, 1> w;
+    da_gather<VEC, 1>(g, ln, src, w);
+    da_bwd_fold<LPR, VEC, 1>(g, ln, r, w, ent, dq);
+  }
+}
+
+// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
+template <int LPR, int VEC>
+__global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    DaRow<VEC> r;
+    da_bwd_load<LPR, VEC>(g, ln, row, r);
+    float4 dq[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC)>(g, ln, r, e0 + grp, e1, EPW, dq);
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) da_add(dq[v], da_shfl_xor(dq[v], off));
+    if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dq);
+  });
+}
+
+// launch 2: one lane group per row
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
+  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
+  float4 dq[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
+  if (end - start > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) da_add(dq[v], ld4(p + ln.ofs[v]));
+    });
+  } else if (end > start) {                                    // (a row without entries: its G row is not read)
+    DaRow<VEC> r;
+    da_bwd_load<LPR, VEC>(g, ln, row, r);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC)>(g, ln, r, start, end, 1, dq);
+  }
+  da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
+}
+
+// (LPR, VEC) of a row of H * F floats = nch chunks of 4
+static inline void da_pick(int H, int F, int* lpr, int* vec, int* nch) {
+  *nch = H * F / 4;
+  if (*nch <= 64) {
+    int l = 1;
+    while (l < *nch) l <<= 1;
+    *lpr = l; *vec = 1;
+  } else {
+    *lpr = 64; *vec = (*nch + 63) / 64;
+  }
+}
+
+#define PYGAT_DA_DISPATCH(LPRV, VECV, ...)                                  \
+  do {                                                                       \
+    if ((VECV) == 1) {                                                       \
+      switch (LPRV) {                                                        \
+        case 1: { constexpr int LPR = 1, VEC = 1; __VA_ARGS__; } break;      \
+        case 2: { constexpr int LPR = 2, VEC = 1; __VA_ARGS__; } break;      \
+        case 4: { constexpr int LPR = 4, VEC = 1; __VA_ARGS__; } break;      \
+        case 8: { constexpr int LPR = 8, VEC = 1; __VA_ARGS__; } break;      \
+        case 16: { constexpr int LPR = 16, VEC = 1; __VA_ARGS__; } break;    \
+        case 32: { constexpr int LPR = 32, VEC = 1; __VA_ARGS__; } break;    \
+        default: { constexpr int LPR = 64, VEC = 1; __VA_ARGS__; } break;    \
+      }                                                                      \
+    } else if ((VECV) == 2) { constexpr int LPR = 64, VEC = 2; __VA_ARGS__; } \
+    else if ((VECV) == 3) { constexpr int LPR = 64, VEC = 3; __VA_ARGS__; }  \
+    else { constexpr int LPR = 64, VEC = 4; __VA_ARGS__; }                   \
+  } while (0)
+
+static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
+  const void* f = nullptr;
+  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC>)
+                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC>))
+                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC>)
+                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC>)));
+  return f;
+}
+
+// pygat_kernel_footprint: k19_{fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH)
+int footprint_k19(const char* name, int* regs, int* scratch) {
+  const void* fn = nullptr;
+  char dir[8] = "", kind[8] = "", rest = 0;
+  int lpr = 0, vec = 0;
+  if (sscanf(name, "k19_%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 && lpr <= 64 &&
+      (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) && (!strcmp(kind, "long") || !strcmp(kind, "row")) &&
+      (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
+    fn = da_kernel_ptr(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
+  if (!fn) {
+    set_error("kernel_footprint: unknown kernel '%s' (k19_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
+    return PYGAT_EINVAL;
+  }
+  return kernel_footprint_of(fn, regs, scratch);
+}
+
+#define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
+
+static int da_check_shape(const char* what, int64_t nnz, int H, int F) {
+  PYGAT_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31), "%s: nnz %lld outside [0, 2^31) (int32 entry indexing)", what, (long long)nnz);
+  PYGAT_REQUIRE(H >= 1 && H <= 64, "%s: H=%d heads outside [1, 64]", what, H);
+  PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (" DA_PAD_HINT ")",
+                what, F);
+  PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
+  return PYGAT_OK;
+}
+
+// a row table: non-null, 16-byte aligned, its stride a multiple of 4 floats and at least H x F
+#define DA_TABLE(what, name, ptr, ld, HF)                                                                              \
+  do {                                                                                                                 \
+    PYGAT_REQUIRE(ptr, "%s: null %s", what, name);                                                                     \
+    PYGAT_REQUIRE(aligned16(ptr), "%s: %s must be 16-byte aligned", what, name);                                       \
+    PYGAT_REQUIRE((ld) >= (HF) && (ld) % 4 == 0, "%s: the row stride of %s, %lld, must be a multiple of 4 and at least H x F = %d", \
+                  what, name, (long long)(ld), (int)(HF));                                                             \
+  } while (0)
+
+static int da_check_common(const char* what, int n_rows, int64_t nnz, int H, int F, const int32_t* rowptr, const int32_t* col,
+                           const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* out,
+                           int64_t ldo, const float* m, const float* Z, const void* ws) {
+  const int rc = da_check_shape(what, nnz, H, F);
+  if (rc != PYGAT_OK) return rc;
+  PYGAT_REQUIRE(n_rows >= 0, "%s: n_rows=%d", what, n_rows);
+  PYGAT_REQUIRE(n_rows > 0 || nnz == 0, "%s: n_rows=0 with nnz=%lld entries", what, (long long)nnz);
+  const int HF = H * F;
+  PYGAT_REQUIRE(rowptr, "%s: null rowptr", what);
+  PYGAT_REQUIRE(nnz == 0 || col, "%s: null col", what);
+  DA_TABLE(what, "q", q, ldq, HF);
+  DA_TABLE(what, "k", k, ldk, HF);
+  DA_TABLE(what, "v", v, ldv, HF);
+  DA_TABLE(what, "out", out, ldo, HF);
+  PYGAT_REQUIRE(m, "%s: null m", what);
+  PYGAT_REQUIRE(Z, "%s: null Z", what);
+  PYGAT_REQUIRE(ws, "%s: null workspace", what);
+  PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
+  return PYGAT_OK;
+}
+
+static void da_fill(DaArgs& g, int n_rows, int64_t nnz, int H, int F, const int32_t* rowptr, const int32_t* col, float scale,
+                    const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out, int64_t ldo,
+                    float* m, float* Z, void* ws) {
+  memset(&g, 0, sizeof(g));
+  g.n = n_rows; g.H = H; g.F = F; g.NCH = H * F / 4; g.LH = F / 4; g.nnz = nnz; g.rowptr = rowptr; g.col = col; g.scale = scale;
+  g.q = q; g.ldq = ldq; g.k = k; g.ldk = ldk; g.v = v; g.ldv = ldv; g.out = out; g.ldo = ldo; g.m = m; g.Z = Z;
+  g.part = static_cast<float*>(ws); g.pstride = da_pstride(H, F);
+}
+
+}  // namespace pygat
+
+using namespace pygat;
+
+extern "C" int pygat_dot_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes) {
+  PYGAT_REQUIRE(bytes, "dot_attn_workspace_bytes: null bytes");
+  const int rc = da_check_shape("dot_attn_workspace_bytes", nnz, H, F);
+  if (rc != PYGAT_OK) return rc;
+  *bytes = (size_t)(long_records(nnz) * da_pstride(H, F)) * sizeof(float);
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_dot_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float scale,
+                                           const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                           float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  const char* what = "dot_attn_forward";
+  const int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  if (rc != PYGAT_OK) return rc;
+  if (n_rows == 0) return PYGAT_OK;
+  DaArgs g;
+  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  int lpr, vec, nch;
+  da_pick(H, F, &lpr, &vec, &nch);
+  const unsigned chunks = (unsigned)long_chunks(nnz);
+  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
+  hipStream_t st = (hipStream_t)stream;
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC>), dim3(blocks), dim3(256), 0, st, g));
+  PYGAT_CHECK_LAUNCH(what);
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                                 int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                                 const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m,
+                                                 const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P,
+                                                 float* S, void* ws, void* stream) {
+  const char* what = "dot_attn_backward_rows";
+  const int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  if (rc != PYGAT_OK) return rc;
+  DA_TABLE(what, "G", G, ldg, H * F);
+  DA_TABLE(what, "dq", dq, lddq, H * F);
+  PYGAT_REQUIRE(nnz == 0 || P, "%s: null P", what);
+  PYGAT_REQUIRE(nnz == 0 || S, "%s: null S", what);
+  if (n_rows == 0) return PYGAT_OK;
+  DaArgs g;
+  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, const_cast<float*>(out), ldo, const_cast<float*>(m),
+          const_cast<float*>(Z), ws);
+  g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
+  int lpr, vec, nch;
+  da_pick(H, F, &lpr, &vec, &nch);
+  const unsigned chunks = (unsigned)long_chunks(nnz);
+  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
+  hipStream_t st = (hipStream_t)stream;
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC>), dim3(blocks), dim3(256), 0, st, g));
+  PYGAT_CHECK_LAUNCH(what);
+  return PYGAT_OK;
+}

@@ -1,0 +1,187 @@
+"""Dot-product attention over the entries of a sparse pattern -- the hot path of graph-transformer layers (TransformerConv / UniMP) -- and
+its score as an op of its own.
+
+  edge_dot       u[e, h] = scale * <q[row_e, h], k[col_e, h]>                 the SDDMM of csrc/k17_spmm.hip with a public face
+  dot_attention  out[i, h, :] = sum over the entries e = (i, j) of row i of  softmax_row(scale * q_i . k_j)[e, h] * v[j, h, :]
+                 fused, on the K19 kernels (csrc/k19_dot_attention.hip): an online softmax per row, nothing written per entry
+
+    pattern = graph.edge_pattern()                       # or EdgePattern.from_indices(indices [2, E], (n_rows, n_cols))
+    out = dot_attention(pattern, q, k, v)                # q [n_rows, H, F]; k, v [n_cols, H, F]; scale = 1 / sqrt(F)
+    out = spmm(pattern, edge_softmax(pattern, edge_dot(pattern, q, k, scale)), v)       # the same, from parts, with [E, H] tensors
+
+A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the
+pattern rectangular.  To attend over columns instead of rows, build the pattern from swapped indices.  Both ops are differentiable
+in every tensor.  The backward of dot_attention keeps out and (m, Z) per row; its two per-entry tensors P and S ([E, H] each) live
+only inside backward, between the row pass and the two transposed SpMMs that form dk and dv.  fp32, no float atomics, a fixed
+summation order: two runs give the same bits.  Nothing is read back to the host.  There is no CPU path and no fallback to torch.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from ._lib import lib, check
+from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
+
+MIN_F, MAX_F = 4, 256      # a head's width in dot_attention: a power of two in this range (csrc/k19_dot_attention.hip)
+
+_PAD_HINT = ("zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged "
+             "(pass scale yourself: the default follows the padded F)")
+
+
+def _tables(op: str, pattern, q, others):
+    """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns."""
+    if not isinstance(pattern, EdgePattern):
+        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    named = (("q", q, pattern.n_rows, "rows"),) + tuple((name, t, pattern.n_cols, "columns") for name, t in others)
+    for name, t, _, _ in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"pygat_amd {op}: {name} must be float32, not {t.dtype}")
+        if t.device != pattern.device:
+            raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}")
+    if q.dim() not in (2, 3):
+        raise ValueError(f"pygat_amd {op}: q [n_rows, F] or [n_rows, H, F] expected, got {tuple(q.shape)}")
+    for name, t in others:
+        if t.dim() != q.dim() or t.shape[1:] != q.shape[1:]:
+            raise ValueError(f"pygat_amd {op}: {name} {tuple(t.shape)} does not match q {tuple(q.shape)}: the same number of heads "
+                             f"and the same F expected")
+    for name, t, rows, side in named:
+        if t.shape[0] != rows:
+            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+    H, F = (1, int(q.shape[1])) if q.dim() == 2 else (int(q.shape[1]), int(q.shape[2]))
+    return H, F, q.dim() == 2
+
+
+# ------------------------------------------------------------------------------------------------------------------------ edge_dot
+def _edge_dot_shapes(pattern, q, k):
+    H, F, flat = _tables("edge_dot", pattern, q, (("k", k),))
+    if not (1 <= H <= MAX_HEADS) or F < 1 or H * F > MAX_ROW_FLOATS:
+        raise ValueError(f"pygat_amd edge_dot: H = {H} heads of F = {F} columns: the limits are 1 <= H <= {MAX_HEADS}, F >= 1 and "
+                         f"H * F <= {MAX_ROW_FLOATS} floats per row")
+    return H, F, flat
+
+
+def _sddmm(pattern: EdgePattern, H: int, F: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """u [E, H], u[e, h] = <a[row_e, h], b[col_e, h]>: one pygat_spmm_grad_values launch with G := a."""
+    u = torch.empty(pattern.nnz, H, dtype=torch.float32, device=a.device)
+    if pattern.nnz:
+        with torch.cuda.device(a.device):
+            check(lib.pygat_spmm_grad_values(pattern.nnz, _ptr(pattern.edge_rc), H, F, _ptr(a), H * F, _ptr(b), H * F, _ptr(u),
+                                             _stream()), "spmm_grad_values")
+    return u
+
+
+class _EdgeDotFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, q, k, scale):
+        H, F, flat = _edge_dot_shapes(pattern, q, k)
+        u = _sddmm(pattern, H, F, q.detach().contiguous(), k.detach().contiguous())
+        if scale != 1.0:
+            u.mul_(scale)
+        ctx.pattern, ctx.scale, ctx.hf = pattern, scale, (H, F)
+        ctx.save_for_backward(q, k)
+        return u.view(pattern.nnz) if flat else u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        q, k = ctx.saved_tensors
+        pattern, (H, F) = ctx.pattern, ctx.hf
+        if g.dtype != torch.float32:
+            raise ValueError(f"pygat_amd edge_dot: the gradient of the output must be float32, not {g.dtype}")
+        dq = dk = None
+        gs = (g if ctx.scale == 1.0 else g * ctx.scale).contiguous().view(pattern.nnz, H)
+        if ctx.needs_input_grad[1]:
+            dq = _launch_spmm(pattern.n_rows, pattern.nnz, pattern.rowptr, pattern.col, pattern.perm, H, F, gs,
+                              k.detach().contiguous()).view(q.shape)
+        if ctx.needs_input_grad[2]:
+            rowptr_t, row_t, perm_t = pattern.transposed()
+            dk = _launch_spmm(pattern.n_cols, pattern.nnz, rowptr_t, row_t, perm_t, H, F, gs, q.detach().contiguous()).view(k.shape)
+        return None, dq, dk, None
+
+
+def edge_dot(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """u [E, H] (q [n_rows, H, F], k [n_cols, H, F]) or u [E] (q [n_rows, F], k [n_cols, F]): u[e] = scale * <q[row_e], k[col_e]> per
+    head, in the caller's entry order, as spmm's values.  Differentiable in q and k.  float32 GPU tensors; H <= 64, H * F <= 1024,
+    any F >= 1."""
+    return _EdgeDotFn.apply(pattern, q, k, float(scale))
+
+
+# ------------------------------------------------------------------------------------------------------------------- dot_attention
+def _attention_shapes(pattern, q, k, v):
+    H, F, flat = _tables("dot_attention", pattern, q, (("k", k), ("v", v)))
+    if not (1 <= H <= MAX_HEADS):
+        raise ValueError(f"pygat_amd dot_attention: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
+    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
+        raise ValueError(f"pygat_amd dot_attention: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
+    if H * F > MAX_ROW_FLOATS:
+        raise ValueError(f"pygat_amd dot_attention: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
+                         f"{_PAD_HINT}")
+    return H, F, flat
+
+
+def _workspace(nnz: int, H: int, F: int, device) -> torch.Tensor:
+    return torch.empty(_lib.dot_attn_workspace_bytes(nnz, H, F), dtype=torch.uint8, device=device)
+
+
+class _DotAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, q, k, v, scale):
+        H, F, _ = _attention_shapes(pattern, q, k, v)
+        scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
+        qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        n, HF = pattern.n_rows, H * F
+        with torch.cuda.device(qc.device):
+            out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
+            m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
+            ws = _workspace(pattern.nnz, H, F, qc.device)
+            check(lib.pygat_dot_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, scale, _ptr(qc), HF,
+                                             _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
+                  "dot_attn_forward")
+        out = out.view(q.shape)
+        ctx.pattern, ctx.scale, ctx.hf = pattern, scale, (H, F)
+        ctx.save_for_backward(q, k, v, out, m, Z)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        q, k, v, out, m, Z = ctx.saved_tensors
+        pattern, scale, (H, F) = ctx.pattern, ctx.scale, ctx.hf
+        if G.dtype != torch.float32:
+            raise ValueError(f"pygat_amd dot_attention: the gradient of the output must be float32, not {G.dtype}")
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None
+        n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
+        qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        Gc = G.contiguous().view(n, HF)
+        with torch.cuda.device(qc.device):
+            dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
+            P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
+            ws = _workspace(nnz, H, F, qc.device)
+            check(lib.pygat_dot_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
+                                                   _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
+                                                   _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
+                  "dot_attn_backward_rows")
+        dk = dv = None
+        if need_k or need_v:
+            rowptr_t, row_t, perm_t = pattern.transposed()
+            if need_k:
+                dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
+            if need_v:
+                dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
+        return None, dq.view(q.shape) if need_q else None, dk, dv, None
+
+
+def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    """out like q ([n_rows, H, F], or [n_rows, F] with k, v [n_cols, F]): out[i] = sum over the entries (i, j) of row i of
+    softmax_j(scale * <q[i], k[j]>) * v[j], per head; scale defaults to 1 / sqrt(F).  A row without entries gets zeros.
+    Differentiable in q, k and v.  float32 GPU tensors; 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024."""
+    return _DotAttentionFn.apply(pattern, q, k, v, scale)

@@ -1,0 +1,209 @@
+#!/usr/bin/env python3
+"""What pygat_amd.dot_attention costs at config 5 (R-MAT 2^20 nodes, 10 760 610 entries; pygat_amd.rmat, the graph of bench.py) against
+the same result from the three ops it fuses -- edge_dot (pygat_spmm_grad_values), edge_softmax (K18) and spmm (pygat_spmm_forward) --
+at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone and forward + backward:
+
+    python tools/dot_attention_bench.py [--shapes 8x16,8x64] [--rounds 5] [--steps 10] [--warmup 10] [--out profiles/dot_attention_bench.jsonl]
+    rocprofv3 --kernel-trace --stats -d DIR -o da -- python tools/dot_attention_bench.py --child --forward-only --shapes 8x64 --out DIR/run.jsonl
+
+The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
+run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
+the same of the other.  Reported per contender: the median over all rounds x steps timed calls (at least 50) and the spread of the
+rounds' medians (largest minus smallest): a difference below that spread is not a difference.  The composition is given q already
+multiplied by the scale, so it runs the parent's kernels and nothing else.
+
+Before timing, both contenders' outputs are priced on the same seeded inputs by the rule of tests/parity.py against an fp64
+computation on the CPU, on a sample of rows (the row of most entries among them): the whole [E, H, F] product does not fit an fp64
+CPU run.  Algorithmic bytes are computed from the shapes (E entries, N rows, M columns, R = H F floats per row), `*_bytes` below.
+Recorded, not gated.  One JSON object per shape, appended."""
+import argparse
+import json
+import math
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SAMPLE_ROWS = 1024
+
+
+def fused_forward_bytes(E, N, M, H, F):
+    """Per entry: the k and v rows and the column index.  Per row: q read, out, m and Z written, the row pointer."""
+    R = H * F
+    return E * (2 * R * 4 + 4) + N * (2 * R * 4 + 2 * H * 4 + 4)
+
+
+def composed_forward_bytes(E, N, M, H, F):
+    """SDDMM: the q and k rows and the (row, col) pair per entry, u written.  K18: u read by the row pass and again by the entry pass
+    with the pair, alpha written; m and Z per row.  SpMM: alpha, the column index and the v row per entry, out per row."""
+    R = H * F
+    sddmm = E * (2 * R * 4 + 8 + H * 4)
+    softmax = E * (3 * H * 4 + 8) + N * (2 * 2 * H * 4 + 4)
+    spmm = E * (H * 4 + 4 + R * 4) + N * (R * 4 + 4)
+    return sddmm + softmax + spmm
+
+
+def fused_backward_bytes(E, N, M, H, F):
+    """Row pass: the k and v rows and the column index per entry, P and S written; q, G, out, m, Z read and dq written per row.
+    Column side, two SpMMs on the transposed pattern: S (P) with the row index and the permutation entry and the q (G) row per entry,
+    dk (dv) per column."""
+    R = H * F
+    rows = E * (2 * R * 4 + 4 + 2 * H * 4) + N * (4 * R * 4 + 2 * H * 4 + 4)
+    cols = 2 * (E * (H * 4 + 8 + R * 4) + M * (R * 4 + 4))
+    return rows + cols
+
+
+def composed_backward_bytes(E, N, M, H, F):
+    """SpMM's backward: an SDDMM over G and v (dalpha written) and the transposed SpMM of alpha and G (dv).  K18's backward: alpha and
+    dalpha read by both passes, dlogits written, c per row.  edge_dot's backward: the SpMM of dlogits and k (dq) and the transposed SpMM of
+    dlogits and q (dk)."""
+    R = H * F
+    spmm_b = E * (2 * R * 4 + 8 + H * 4) + E * (H * 4 + 8 + R * 4) + M * (R * 4 + 4)
+    softmax_b = E * (5 * H * 4 + 8) + N * (2 * H * 4 + 4)
+    dot_b = E * (H * 4 + 4 + R * 4) + N * (R * 4 + 4) + E * (H * 4 + 8 + R * 4) + M * (R * 4 + 4)
+    return spmm_b + softmax_b + dot_b
+
+
+def timed_round(fn, steps):
+    """-> the ms of `steps` calls, each between two events."""
+    import torch
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) for a, b in ev]
+
+
+def alternate(contenders, rounds, steps, warmup):
+    """{name: fn} -> {name: (median ms of all timed calls, spread of the rounds' medians)}."""
+    for fn in contenders.values():
+        for _ in range(warmup):
+            fn()
+    times = {name: [] for name in contenders}
+    for _ in range(rounds):
+        for name, fn in contenders.items():
+            times[name].append(timed_round(fn, steps))
+    out = {}
+    for name, per_round in times.items():
+        medians = [statistics.median(r) for r in per_round]
+        out[name] = (statistics.median([t for r in per_round for t in r]), max(medians) - min(medians))
+    return out
+
+
+def sampled_reference(rp, col, rows, q, k, v, scale, dtype):
+    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j, times v_j."""
+    import torch
+    deg = rp[rows + 1] - rp[rows]
+    idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
+    sub = torch.repeat_interleave(torch.arange(rows.numel()), deg)
+    cols, inv = torch.unique(col[idx], return_inverse=True)
+    qs, ks, vs = q[rows].cpu().to(dtype), k[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
+    s = (qs[sub] * ks[inv]).sum(-1) * scale
+    m = torch.full(qs.shape[:2], -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
+    p = torch.exp(s - m[sub])
+    alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
+    return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vs[inv])
+
+
+def measure(args):
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("dot_attention_bench: needs a GPU (a time taken anywhere else says nothing)")
+    import pygat_amd as pg
+    from pygat_amd.rmat import rmat_csr_numpy
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import parity                                                     # the one tolerance rule (tests/parity.py)
+    dev = torch.device("cuda", 0)
+    rp, col = rmat_csr_numpy(args.scale, args.draws, seed=1)
+    graph = pg.CSRGraph(torch.from_numpy(rp).to(dev), torch.from_numpy(col).to(dev))
+    pattern = graph.edge_pattern()
+    pattern.transposed()
+    N, E = graph.n, graph.nnz
+    rp_t, col_t = torch.from_numpy(rp).long(), torch.from_numpy(col).long()
+    deg = rp_t[1:] - rp_t[:-1]
+    picked = torch.randperm(N, generator=torch.Generator().manual_seed(3))[:SAMPLE_ROWS]
+    rows = torch.unique(torch.cat([picked, torch.argmax(deg)[None]]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        scale = 1.0 / math.sqrt(F)
+        g = torch.Generator(device=dev).manual_seed(2)
+        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
+        qs = q * scale
+
+        def fused(*leaves):
+            return pg.dot_attention(pattern, *leaves, scale)
+
+        def composed(qs_, k_, v_):
+            return pg.spmm(pattern, pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_)), v_)
+
+        def forward_of(fn, leaves):
+            def run():
+                with torch.no_grad():
+                    return fn(*leaves)
+            return run
+
+        def both_of(fn, leaves):
+            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
+
+            def run():
+                return torch.autograd.grad(fn(*leaves), leaves, G)
+            return run
+
+        # the same seeded inputs, both contenders priced on the sampled rows
+        out_f, out_c = forward_of(fused, (q, k, v))(), forward_of(composed, (qs, k, v))()
+        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64)
+        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32)
+        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused out", ref32)
+        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed out", ref32)
+        res = {"device": torch.cuda.get_device_name(0), "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E,
+               "H": H, "F": F, "scale": scale, "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup,
+               "checked_rows": int(rows.numel()), "longest_checked_row": int(deg[rows].max()),
+               "out_err_fused": err_f, "out_err_composed": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
+               "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
+               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F),
+               "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F), "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F)}
+        del out_f, out_c
+        fwd = alternate({"fused": forward_of(fused, (q, k, v)), "composed": forward_of(composed, (qs, k, v))}, args.rounds, args.steps,
+                        args.warmup)
+        legs = [("forward", fwd)]
+        if not args.forward_only:
+            legs.append(("forward_backward", alternate({"fused": both_of(fused, (q, k, v)), "composed": both_of(composed, (qs, k, v))},
+                                                       args.rounds, args.steps, args.warmup)))
+        for what, r in legs:
+            for name in ("fused", "composed"):
+                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+            res[f"{what}_speedup"] = res[f"composed_{what}_ms"] / res[f"fused_{what}_ms"]
+        with open(args.out, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+        del q, k, v, G, qs
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="8x16,8x64")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10, help="timed calls per round and contender")
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--forward-only", action="store_true", help="skip the forward + backward leg (a kernel trace of the forward alone)")
+    ap.add_argument("--scale", type=int, default=20)
+    ap.add_argument("--draws", type=int, default=5_000_000)
+    ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dot_attention_bench.jsonl"))
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return measure(args)
+    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
+    sys.exit(subprocess.call(cmd))
+
+
+if __name__ == "__main__":
+    main()
