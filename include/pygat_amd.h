@@ -649,6 +649,26 @@ int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr,
                                       const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m, const float* Z,
                                       const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, void* ws,
                                       void* stream);
+/* The same two with a per-entry term on the score (the BIAS instantiations of the K19 kernels), additive under ABI 16:
+ *   s[e, h] = scale <q[i, h], k[j, h]> + bias[c(e) * (bias_head_stride ? H : 1) + h * bias_head_stride],
+ * c(e) the CALLER's entry index of CSR position e (perm[e]; perm may be null: the position itself), as P and S are addressed.
+ * bias_head_stride 1: bias [nnz x H]; 0: bias [nnz], one value per entry shared by the heads.  Both launchers take the softmax's
+ * difference as (scale <q, k>) - (m - bias), the expression of the pair above with the bias on the maximum's side: under a bias of zeros
+ * out, dq, P and S are theirs bit for bit.  m and Z are those of the biased scores.  bias is read with 4-byte loads (no alignment beyond 4
+ * bytes), must be finite and is not checked; a large negative finite value (-9e15) masks an entry exactly -- p = 0, no share of out,
+ * exact zeros in dq, P, S and dbias -- while its row keeps an unmasked entry.  backward_rows also forms dbias[c(e), h] = p (<G[i, h],
+ * v[j, h]> - D[i, h]), always [nnz x H] (the gradient of a [nnz] bias is its sum over h, the caller's), stored only where dbias is not
+ * null; dq, P and S keep their formulas and, under a bias of zeros, their bits.  Refusals as above after the launcher's own name;
+ * besides: a null bias with nnz > 0, a bias_head_stride other than 0 or 1.  The workspace and its size query are unchanged. */
+int pygat_dot_attn_bias_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                     int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                     int64_t ldv, const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m,
+                                     float* Z, void* ws, void* stream);
+int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                           int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                           const float* v, int64_t ldv, const float* bias, int bias_head_stride, const float* out,
+                                           int64_t ldo, const float* m, const float* Z, const float* G, int64_t ldg, float* dq,
+                                           int64_t lddq, float* P, float* S, float* dbias, void* ws, void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

@@ -14,6 +14,12 @@
 // first -- rescale once, then a fixed butterfly -- and records merge in chunk order by the same rule.  A record is (acc[H F], m[H],
 // Z[H]) forward and the dq row backward.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.  A row
 // without entries gets out = m = Z = dq = 0 exactly; a row of one entry (i, j) gets out_i = v_j bit for bit, p = 1 and ds = dq_i = 0.
+// BIAS (a compile-time flag of the four kernels; pygat_dot_attn_bias_*): s[e, h] + bias[c(e), h] is what the softmax runs over, c(e)
+// the CALLER's entry index (perm), the bias [nnz x H] or [nnz] (a head stride of 0).  One more 4-byte load per (entry, head) and walk,
+// prefetched a batch ahead like the column indices; the backward also forms T = p (<G_i, v_j> - D_i), the gradient of the bias, beside
+// ds and stores it where it is asked for.  m and Z are those of the biased scores.  A bias of zeros changes no bit of out, dq, P or S; a
+// large negative finite bias (-9e15) gives p = 0 exactly while the row keeps another entry.  A row of one entry still gets out_i = v_j
+// and ds = T = dq_i = 0 exactly, p = 1 to rounding.
 #include "long_rows.h"
 #include <float.h>
 #include <string.h>
@@ -40,6 +46,10 @@ struct DaArgs {
   float *P, *S;                // [nnz x H], the caller's entry order
   float* part;                 // [long_records(nnz) x pstride]
   int64_t pstride;             // H * F + 2 H rounded up to 4 floats
+  const float* bias;           // BIAS kernels only from here: bias[entry * bstride + head * bhs] at the CALLER's entry index (perm)
+  int64_t bstride;             // H for a [nnz x H] bias, 1 for a [nnz] one shared by the heads
+  int bhs;                     // 1 | 0
+  float* dbias;                // [nnz x H], the caller's entry order; null: not asked for
 };
 
 static inline int64_t da_pstride(int H, int F) { return ((int64_t)H * F + 2 * H + 3) & ~(int64_t)3; }
@@ -114,6 +124,34 @@ __device__ __forceinline__ float da_score(const DaArgs& g, const float4& q, cons
   return __fmul_rn(g.scale, da_head_sum<LPR>(dot4(q, k), g.LH));
 }
 
+// the caller's entry index of CSR position pos, without a branch: a pattern without a permutation reads col[pos] in perm's place
+// (the line its walk has just asked for) and keeps pos.  As a branch around the load this put an s_waitcnt vmcnt(0) behind every
+// gather of the prefetching walk, which then waited for the gather, then for the indices (8 x 16 forward 6.64 ms against 3.68 ms
+// without a bias)
+// without a bias).  The loaded word is kept as it comes and turned into the index only where it is used, a batch later: taking the
+// choice at once made the walk wait for the word, and with it for the gather issued before it
+__device__ __forceinline__ int32_t da_eid_raw(const DaArgs& g, int64_t pos) { return (g.perm ? g.perm : g.col)[pos]; }
+__device__ __forceinline__ int32_t da_eid(const DaArgs& g, int32_t raw, int64_t pos) { return g.perm ? raw : (int32_t)pos; }
+template <int U>
+__device__ __forceinline__ void da_eids(const DaArgs& g, const int32_t (&raw)[U], int64_t e, int64_t step, int32_t (&eid)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) eid[u] = da_eid(g, raw[u], e + u * step);
+}
+
+// BIAS: the per-entry terms of U entries, one 4-byte load per (entry, chunk): every lane of a head asks for the same address, one
+// transaction (a lane past the row asks for head 0's)
+template <int VEC, int U, bool BIAS>
+struct DaBias {
+  float b[BIAS ? U : 1][BIAS ? VEC : 1];
+};
+template <int VEC, int U>
+__device__ __forceinline__ void da_bias_load(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&eid)[U], DaBias<VEC, U, true>& bs) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) bs.b[u][v] = g.bias[(int64_t)eid[u] * g.bstride + ln.head[v] * g.bhs];
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ forward
 template <int VEC>
 struct DaState {
@@ -135,6 +173,19 @@ __device__ __forceinline__ void da_fold(float& m, float& z, float4& acc, float s
   z = fmaf(z, r, p);
   acc.x = fmaf(acc.x, r, p * w.x); acc.y = fmaf(acc.y, r, p * w.y); acc.z = fmaf(acc.z, r, p * w.z); acc.w = fmaf(acc.w, r, p * w.w);
   m = up ? s : m;
+}
+
+// BIAS: the same fold of the score s + b.  The bias goes to the maximum's side of the difference, (s) - (m - b), and leaves the
+// expression s - m of da_fold as it is: under b = 0 both compile to the same operations on the same values (m - 0 is m), whether or
+// not the compiler contracts the product inside s into that difference -- it does -- so a bias of zeros changes no bit
+__device__ __forceinline__ void da_fold_b(float& m, float& z, float4& acc, float s, float b, const float4& w) {
+  const float d = s - (m - b);
+  const float ex = __expf(-fabsf(d));
+  const bool up = d > 0.f;
+  const float r = up ? ex : 1.f, p = up ? 1.f : ex;
+  z = fmaf(z, r, p);
+  acc.x = fmaf(acc.x, r, p * w.x); acc.y = fmaf(acc.y, r, p * w.y); acc.z = fmaf(acc.z, r, p * w.z); acc.w = fmaf(acc.w, r, p * w.w);
+  m = up ? __fadd_rn(s, b) : m;
 }
 
 // (m, z, acc) <- (m, z, acc) (+) (m2, z2, acc2), the earlier entries on the left
@@ -160,26 +211,38 @@ __device__ __forceinline__ void da_gather(const DaArgs& g, const DaLane<VEC>& ln
   }
 }
 
-template <int LPR, int VEC, int U>
-__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[VEC], const DaRows<VEC, U>& w, DaState<VEC>& st) {
+template <int LPR, int VEC, int U, bool BIAS>
+__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[VEC], const DaRows<VEC, U>& w,
+                                            const DaBias<VEC, U, BIAS>& bs, DaState<VEC>& st) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) da_fold(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), w.v[u][v]);
+    for (int v = 0; v < VEC; ++v) {
+      if constexpr (BIAS) da_fold_b(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), bs.b[u][v], w.v[u][v]);
+      else da_fold(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), w.v[u][v]);
+    }
 }
 
 // the entries e0, e0 + step, ... < e1 of one row, folded in that order, U at a time: the column indices of the next U are asked for
-// before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather
-template <int LPR, int VEC, int U>
+// before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather.  BIAS: the next
+// batch's entry indices travel with its column indices, and its bias values are asked for once this batch is folded -- ahead of the
+// next gather, so they are there when it is -- an iteration still waits for one gather
+template <int LPR, int VEC, int U, bool BIAS>
 __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
                                             int64_t step, DaState<VEC>& st) {
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
+    [[maybe_unused]] int32_t raw[U], eid[U];
+    DaBias<VEC, U, BIAS> bs;
     bool full = e + (U - 1) * step < e1;
     if (full) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) src[u] = g.col[e + u * step];
+      for (int u = 0; u < U; ++u) {
+        src[u] = g.col[e + u * step];
+        if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+      }
+      if constexpr (BIAS) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
     }
     while (full) {
       DaRows<VEC, U> w;
@@ -188,21 +251,31 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
       full = e + (U - 1) * step < e1;
       if (full) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) src[u] = g.col[e + u * step];
+        for (int u = 0; u < U; ++u) {
+          src[u] = g.col[e + u * step];
+          if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+        }
       }
-      da_fwd_fold<LPR, VEC, U>(g, q, w, st);
+      da_fwd_fold<LPR, VEC, U, BIAS>(g, q, w, bs, st);
+      if constexpr (BIAS)
+        if (full) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
     }
   }
   for (; e < e1; e += step) {
     const int32_t src[1] = {g.col[e]};
+    DaBias<VEC, 1, BIAS> bs;
+    if constexpr (BIAS) {
+      const int32_t eid[1] = {da_eid(g, da_eid_raw(g, e), e)};
+      da_bias_load<VEC, 1>(g, ln, eid, bs);
+    }
     DaRows<VEC, 1> w;
     da_gather<VEC, 1>(g, ln, src, w);
-    da_fwd_fold<LPR, VEC, 1>(g, q, w, st);
+    da_fwd_fold<LPR, VEC, 1, BIAS>(g, q, w, bs, st);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool BIAS>
 __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -215,7 +288,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
     DaState<VEC> st;
     da_init<VEC>(st);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC)>(g, ln, q, e0 + grp, e1, EPW, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS>(g, ln, q, e0 + grp, e1, EPW, st);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
       float mx = st.m[v];
@@ -242,7 +315,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool BIAS>
 __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -263,7 +336,7 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   } else if (end > start) {
     float4 q[VEC];
     da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC)>(g, ln, q, start, end, 1, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS>(g, ln, q, start, end, 1, st);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
@@ -303,60 +376,95 @@ __device__ __forceinline__ void da_bwd_load(const DaArgs& g, const DaLane<VEC>& 
 // the caller's entry index (x H) of CSR position pos
 __device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { return (g.perm ? (int64_t)g.perm[pos] : pos) * g.H; }
 
-template <int LPR, int VEC, int U>
+// BIAS: T = p (<G_i, v_j> - D_i), the gradient of the bias, formed beside ds -- ds itself is the unbiased kernel's expression, so a
+// bias of zeros leaves the bits of S, dq and dk alone -- and stored where it is asked for
+template <int LPR, int VEC, int U, bool BIAS>
 __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, const DaRows<VEC, U>& w,
-                                            const int64_t (&ent)[U], float4 (&dq)[VEC]) {
+                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, float4 (&dq)[VEC]) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       const float s = da_score<LPR>(g, r.q[v], w.k[u][v]);
-      const float p = __expf(s - r.m[v]) * r.rz[v];
+      float p;
+      if constexpr (BIAS) p = __expf(s - (r.m[v] - bs.b[u][v])) * r.rz[v];      // (as da_fold_b: s - m with the bias on m's side)
+      else p = __expf(s - r.m[v]) * r.rz[v];
       const float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
       const float ds = g.scale * p * (dp - r.D[v]);
       da_axpy(dq[v], ds, w.k[u][v]);
-      if (ln.lead >> v & 1) { g.P[ent[u] + ln.head[v]] = p; g.S[ent[u] + ln.head[v]] = ds; }
+      if (ln.lead >> v & 1) {
+        g.P[ent[u] + ln.head[v]] = p;
+        g.S[ent[u] + ln.head[v]] = ds;
+        if constexpr (BIAS)
+          if (g.dbias) g.dbias[ent[u] + ln.head[v]] = p * (dp - r.D[v]);
+      }
     }
 }
 
-// as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic
-template <int LPR, int VEC, int U>
+// as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic; BIAS: its bias values are
+// asked for once this batch is folded, ahead of the next gather
+template <int LPR, int VEC, int U, bool BIAS>
 __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, int64_t e0, int64_t e1,
                                             int64_t step, float4 (&dq)[VEC]) {
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
-    int64_t ent[U], ent_next[U];
+    int64_t ent[U];
+    [[maybe_unused]] int64_t ent_next[U];
+    [[maybe_unused]] int32_t raw[U], eid[U];
+    DaBias<VEC, U, BIAS> bs;
     bool full = e + (U - 1) * step < e1;
     if (full) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) { src[u] = g.col[e + u * step]; ent_next[u] = da_entry(g, e + u * step); }
+      for (int u = 0; u < U; ++u) {
+        src[u] = g.col[e + u * step];
+        if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+        else ent_next[u] = da_entry(g, e + u * step);
+      }
+      if constexpr (BIAS) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
     }
     while (full) {
       DaRows<VEC, U> w;
       da_gather<VEC, U>(g, ln, src, w);
+      if constexpr (!BIAS) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+      }
       e += U * step;
       full = e + (U - 1) * step < e1;
       if (full) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) { src[u] = g.col[e + u * step]; ent_next[u] = da_entry(g, e + u * step); }
+        for (int u = 0; u < U; ++u) {
+          src[u] = g.col[e + u * step];
+          if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+          else ent_next[u] = da_entry(g, e + u * step);
+        }
       }
-      da_bwd_fold<LPR, VEC, U>(g, ln, r, w, ent, dq);
+      if constexpr (BIAS) {                                      // (this batch's entry indices: formed after the last fold, not yet replaced)
+#pragma unroll
+        for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
+      }
+      da_bwd_fold<LPR, VEC, U, BIAS>(g, ln, r, w, ent, bs, dq);
+      if constexpr (BIAS)
+        if (full) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
     }
   }
   for (; e < e1; e += step) {
     const int32_t src[1] = {g.col[e]};
     const int64_t ent[1] = {da_entry(g, e)};
+    DaBias<VEC, 1, BIAS> bs;
+    if constexpr (BIAS) {
+      const int32_t eid[1] = {da_eid(g, da_eid_raw(g, e), e)};
+      da_bias_load<VEC, 1>(g, ln, eid, bs);
+    }
     DaRows<VEC, 1> w;
     da_gather<VEC, 1>(g, ln, src, w);
-    da_bwd_fold<LPR, VEC, 1>(g, ln, r, w, ent, dq);
+    da_bwd_fold<LPR, VEC, 1, BIAS>(g, ln, r, w, ent, bs, dq);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool BIAS>
 __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -369,7 +477,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
     float4 dq[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC)>(g, ln, r, e0 + grp, e1, EPW, dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS>(g, ln, r, e0 + grp, e1, EPW, dq);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
@@ -379,7 +487,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool BIAS>
 __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -399,7 +507,7 @@ __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   } else if (end > start) {                                    // (a row without entries: its G row is not read)
     DaRow<VEC> r;
     da_bwd_load<LPR, VEC>(g, ln, row, r);
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC)>(g, ln, r, start, end, 1, dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS>(g, ln, r, start, end, 1, dq);
   }
   da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
 }
@@ -433,30 +541,35 @@ static inline void da_pick(int H, int F, int* lpr, int* vec, int* nch) {
     else { constexpr int LPR = 64, VEC = 4; __VA_ARGS__; }                   \
   } while (0)
 
+template <bool BIAS>
 static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
   const void* f = nullptr;
-  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC>)
-                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC>))
-                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC>)
-                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC>)));
+  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS>)
+                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS>))
+                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS>)
+                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS>)));
   return f;
 }
 
-// pygat_kernel_footprint: k19_{fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH)
-int footprint_k19(const char* name, int* regs, int* scratch) {
+// pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH)
+static int da_footprint(const char* name, const char* prefix, bool bias, int* regs, int* scratch) {
   const void* fn = nullptr;
   char dir[8] = "", kind[8] = "", rest = 0;
   int lpr = 0, vec = 0;
-  if (sscanf(name, "k19_%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 && lpr <= 64 &&
-      (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) && (!strcmp(kind, "long") || !strcmp(kind, "row")) &&
-      (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
-    fn = da_kernel_ptr(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
+  const size_t np = strlen(prefix);
+  if (!strncmp(name, prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
+      lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) &&
+      (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
+    fn = bias ? da_kernel_ptr<true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
+              : da_kernel_ptr<false>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (k19_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
+    set_error("kernel_footprint: unknown kernel '%s' (%s{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name, prefix);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
 }
+int footprint_k19(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19_", false, regs, scratch); }
+int footprint_k19b(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19b_", true, regs, scratch); }
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
 
@@ -520,24 +633,78 @@ extern "C" int pygat_dot_attn_workspace_bytes(int64_t nnz, int H, int F, size_t*
   return PYGAT_OK;
 }
 
-extern "C" int pygat_dot_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float scale,
-                                           const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-                                           float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
-  const char* what = "dot_attn_forward";
-  const int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+// the per-entry term of the BIAS launchers: non-null where there are entries (4-byte loads: no alignment asked for), a head stride of 1
+// ([nnz x H]) or 0 ([nnz], shared by the heads)
+static int da_check_bias(const char* what, int64_t nnz, const float* bias, int bias_head_stride) {
+  PYGAT_REQUIRE(nnz == 0 || bias, "%s: null bias", what);
+  PYGAT_REQUIRE(bias_head_stride == 0 || bias_head_stride == 1, "%s: bias_head_stride=%d, 1 (bias [nnz x H]) or 0 (bias [nnz], shared by "
+                "the heads) expected", what, bias_head_stride);
+  return PYGAT_OK;
+}
+
+template <bool BIAS>
+static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                      int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                      const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
   if (rc != PYGAT_OK) return rc;
+  if constexpr (BIAS) {
+    rc = da_check_bias(what, nnz, bias, bias_head_stride);
+    if (rc != PYGAT_OK) return rc;
+  }
   if (n_rows == 0) return PYGAT_OK;
   DaArgs g;
   da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  if constexpr (BIAS) { g.perm = perm; g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
+}
+
+template <bool BIAS>
+static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                            int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                            int64_t ldv, const float* bias, int bias_head_stride, const float* out, int64_t ldo, const float* m,
+                            const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias,
+                            void* ws, void* stream) {
+  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  if (rc != PYGAT_OK) return rc;
+  DA_TABLE(what, "G", G, ldg, H * F);
+  DA_TABLE(what, "dq", dq, lddq, H * F);
+  PYGAT_REQUIRE(nnz == 0 || P, "%s: null P", what);
+  PYGAT_REQUIRE(nnz == 0 || S, "%s: null S", what);
+  if constexpr (BIAS) {
+    rc = da_check_bias(what, nnz, bias, bias_head_stride);
+    if (rc != PYGAT_OK) return rc;
+  }
+  if (n_rows == 0) return PYGAT_OK;
+  DaArgs g;
+  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, const_cast<float*>(out), ldo, const_cast<float*>(m),
+          const_cast<float*>(Z), ws);
+  g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
+  if constexpr (BIAS) { g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; g.dbias = dbias; }
+  int lpr, vec, nch;
+  da_pick(H, F, &lpr, &vec, &nch);
+  const unsigned chunks = (unsigned)long_chunks(nnz);
+  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
+  hipStream_t st = (hipStream_t)stream;
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS>), dim3(blocks), dim3(256), 0, st, g));
+  PYGAT_CHECK_LAUNCH(what);
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_dot_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float scale,
+                                           const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                           float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  return da_forward<false>("dot_attn_forward", n_rows, nnz, rowptr, col, nullptr, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out,
+                           ldo, m, Z, ws, stream);
 }
 
 extern "C" int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
@@ -545,25 +712,25 @@ extern "C" int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32
                                                  const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m,
                                                  const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P,
                                                  float* S, void* ws, void* stream) {
-  const char* what = "dot_attn_backward_rows";
-  const int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
-  if (rc != PYGAT_OK) return rc;
-  DA_TABLE(what, "G", G, ldg, H * F);
-  DA_TABLE(what, "dq", dq, lddq, H * F);
-  PYGAT_REQUIRE(nnz == 0 || P, "%s: null P", what);
-  PYGAT_REQUIRE(nnz == 0 || S, "%s: null S", what);
-  if (n_rows == 0) return PYGAT_OK;
-  DaArgs g;
-  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, const_cast<float*>(out), ldo, const_cast<float*>(m),
-          const_cast<float*>(Z), ws);
-  g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
-  int lpr, vec, nch;
-  da_pick(H, F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(nnz);
-  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
-  hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC>), dim3(blocks), dim3(256), 0, st, g));
-  PYGAT_CHECK_LAUNCH(what);
-  return PYGAT_OK;
+  return da_backward_rows<false>("dot_attn_backward_rows", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr,
+                                 1, out, ldo, m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream);
+}
+
+// the same two with a per-entry term on the score: s[e, h] = scale <q_i, k_j> + bias[entry(e), h bias_head_stride]
+extern "C" int pygat_dot_attn_bias_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                                int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                                const float* v, int64_t ldv, const float* bias, int bias_head_stride, float* out,
+                                                int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  return da_forward<true>("dot_attn_bias_forward", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
+                          bias_head_stride, out, ldo, m, Z, ws, stream);
+}
+
+extern "C" int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                                                      const int32_t* perm, int H, int F, float scale, const float* q, int64_t ldq,
+                                                      const float* k, int64_t ldk, const float* v, int64_t ldv, const float* bias,
+                                                      int bias_head_stride, const float* out, int64_t ldo, const float* m,
+                                                      const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P,
+                                                      float* S, float* dbias, void* ws, void* stream) {
+  return da_backward_rows<true>("dot_attn_bias_backward_rows", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv,
+                                bias, bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream);
 }

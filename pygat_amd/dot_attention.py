@@ -8,6 +8,7 @@ its score as an op of its own.
     pattern = graph.edge_pattern()                       # or EdgePattern.from_indices(indices [2, E], (n_rows, n_cols))
     out = dot_attention(pattern, q, k, v)                # q [n_rows, H, F]; k, v [n_cols, H, F]; scale = 1 / sqrt(F)
     out = spmm(pattern, edge_softmax(pattern, edge_dot(pattern, q, k, scale)), v)       # the same, from parts, with [E, H] tensors
+    out = dot_attention(pattern, q, k, v, bias=emb(edge_type))    # a per-entry term on the score, [E, H] or [E]; differentiable too
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the
 pattern rectangular.  To attend over columns instead of rows, build the pattern from swapped indices.  Both ops are differentiable
@@ -126,14 +127,40 @@ def _attention_shapes(pattern, q, k, v):
     return H, F, flat
 
 
+def _bias_tensor(pattern, bias):
+    """The refusals of `bias` that do not depend on q, k and v."""
+    if not isinstance(pattern, EdgePattern):
+        raise ValueError("pygat_amd dot_attention: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    if not isinstance(bias, torch.Tensor) or not bias.is_cuda:
+        raise ValueError("pygat_amd dot_attention: bias must be a tensor on the GPU (there is no CPU path)")
+    if bias.dtype != torch.float32:
+        raise ValueError(f"pygat_amd dot_attention: bias must be float32, not {bias.dtype}")
+    if bias.device != pattern.device:
+        raise ValueError(f"pygat_amd dot_attention: bias lives on {bias.device}, the pattern on {pattern.device}")
+
+
+def _bias_head_stride(pattern, bias, H: int, flat: bool) -> int:
+    """1: one value per entry and head ([E, H]; [E] where q, k and v have no head axis); 0: one per entry, shared by the heads."""
+    E = pattern.nnz
+    if tuple(bias.shape) == (E,):
+        return 1 if flat else 0
+    if not flat and tuple(bias.shape) == (E, H):
+        return 1
+    want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
+    raise ValueError(f"pygat_amd dot_attention: bias {want} expected for E = {E} entries and H = {H} heads, got {tuple(bias.shape)}")
+
+
 def _workspace(nnz: int, H: int, F: int, device) -> torch.Tensor:
     return torch.empty(_lib.dot_attn_workspace_bytes(nnz, H, F), dtype=torch.uint8, device=device)
 
 
 class _DotAttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pattern, q, k, v, scale):
-        H, F, _ = _attention_shapes(pattern, q, k, v)
+    def forward(ctx, pattern, q, k, v, scale, bias):
+        if bias is not None:
+            _bias_tensor(pattern, bias)
+        H, F, flat = _attention_shapes(pattern, q, k, v)
+        bhs = None if bias is None else _bias_head_stride(pattern, bias, H, flat)
         scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
         qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
         n, HF = pattern.n_rows, H * F
@@ -141,35 +168,53 @@ class _DotAttentionFn(torch.autograd.Function):
             out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
             m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
             ws = _workspace(pattern.nnz, H, F, qc.device)
-            check(lib.pygat_dot_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, scale, _ptr(qc), HF,
-                                             _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
-                  "dot_attn_forward")
+            if bias is None:
+                check(lib.pygat_dot_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, scale, _ptr(qc), HF,
+                                                 _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
+                      "dot_attn_forward")
+            else:
+                bc = bias.detach().contiguous()
+                check(lib.pygat_dot_attn_bias_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
+                                                      scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out), HF,
+                                                      _ptr(m), _ptr(Z), _ptr(ws), _stream()), "dot_attn_bias_forward")
         out = out.view(q.shape)
-        ctx.pattern, ctx.scale, ctx.hf = pattern, scale, (H, F)
-        ctx.save_for_backward(q, k, v, out, m, Z)
+        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs = pattern, scale, (H, F), bhs
+        ctx.save_for_backward(q, k, v, out, m, Z, bias)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        q, k, v, out, m, Z = ctx.saved_tensors
-        pattern, scale, (H, F) = ctx.pattern, ctx.scale, ctx.hf
+        q, k, v, out, m, Z, bias = ctx.saved_tensors
+        pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
         if G.dtype != torch.float32:
             raise ValueError(f"pygat_amd dot_attention: the gradient of the output must be float32, not {G.dtype}")
         need_q, need_k, need_v = ctx.needs_input_grad[1:4]
-        if not (need_q or need_k or need_v):
-            return None, None, None, None, None
+        need_b = bias is not None and ctx.needs_input_grad[5]
+        if not (need_q or need_k or need_v or need_b):
+            return None, None, None, None, None, None
         n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
         qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
         Gc = G.contiguous().view(n, HF)
+        db = None
         with torch.cuda.device(qc.device):
             dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
             ws = _workspace(nnz, H, F, qc.device)
-            check(lib.pygat_dot_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
-                                                   _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
-                                                   _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
-                  "dot_attn_backward_rows")
+            if bias is None:
+                check(lib.pygat_dot_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
+                                                       _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
+                                                       _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
+                      "dot_attn_backward_rows")
+            else:
+                bc = bias.detach().contiguous()
+                db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
+                check(lib.pygat_dot_attn_bias_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
+                                                            scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out),
+                                                            HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S),
+                                                            _ptr(db), _ptr(ws), _stream()), "dot_attn_bias_backward_rows")
+                if need_b:                      # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
+                    db = db.sum(1) if bhs == 0 else db.view(bias.shape)
         dk = dv = None
         if need_k or need_v:
             rowptr_t, row_t, perm_t = pattern.transposed()
@@ -177,11 +222,17 @@ class _DotAttentionFn(torch.autograd.Function):
                 dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
             if need_v:
                 dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
-        return None, dq.view(q.shape) if need_q else None, dk, dv, None
+        return None, dq.view(q.shape) if need_q else None, dk, dv, None, db
 
 
-def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out like q ([n_rows, H, F], or [n_rows, F] with k, v [n_cols, F]): out[i] = sum over the entries (i, j) of row i of
-    softmax_j(scale * <q[i], k[j]>) * v[j], per head; scale defaults to 1 / sqrt(F).  A row without entries gets zeros.
-    Differentiable in q, k and v.  float32 GPU tensors; 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024."""
-    return _DotAttentionFn.apply(pattern, q, k, v, scale)
+    softmax_j(scale * <q[i], k[j]> + bias[e]) * v[j], per head; scale defaults to 1 / sqrt(F).  A row without entries gets zeros.
+    bias (optional): a per-entry term on the score, at the caller's entry index -- [E, H], or [E] for one value per entry shared by
+    the heads (and where q, k and v have no head axis) -- taken into the softmax as (scale * <q, k>) - (m - bias), m the running
+    maximum, so a bias of zeros changes no bit of the result.  Its values must be finite (nothing is read back to check them); a large negative finite one such as -9e15 masks an entry exactly: its
+    coefficient, its share of out and every gradient that passes through it are exact zeros, provided the row keeps at least one
+    unmasked entry.  Differentiable in q, k, v and bias (the gradient of a [E] bias is the sum over the heads).  float32 GPU tensors;
+    1 <= H <= 64, F a power of two in 4..256, H * F <= 1024."""
+    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias)

@@ -5,6 +5,7 @@ at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone 
 
     python tools/dot_attention_bench.py [--shapes 8x16,8x64] [--rounds 5] [--steps 10] [--warmup 10] [--out profiles/dot_attention_bench.jsonl]
     rocprofv3 --kernel-trace --stats -d DIR -o da -- python tools/dot_attention_bench.py --child --forward-only --shapes 8x64 --out DIR/run.jsonl
+    python tools/dot_attention_bench.py --bias [...]       # the per-entry bias: three contenders -> profiles/dot_attention_bias_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
@@ -15,7 +16,13 @@ multiplied by the scale, so it runs the parent's kernels and nothing else.
 Before timing, both contenders' outputs are priced on the same seeded inputs by the rule of tests/parity.py against an fp64
 computation on the CPU, on a sample of rows (the row of most entries among them): the whole [E, H, F] product does not fit an fp64
 CPU run.  Algorithmic bytes are computed from the shapes (E entries, N rows, M columns, R = H F floats per row), `*_bytes` below.
-Recorded, not gated.  One JSON object per shape, appended."""
+Recorded, not gated.  One JSON object per shape, appended.
+
+--bias measures dot_attention's per-entry bias instead: in the one child process it alternates the fused op with an N(0, 1) [E, H] bias
+that requires a gradient, the composition spmm(edge_softmax(edge_dot(q, k) + bias), v) with the same bias, and the fused op without
+a bias, prices the first two on the sampled rows against the fp64 computation with the bias on the scores, and prints the byte
+model's expectation of what the bias adds to the fused forward (4 H bytes per entry, 4 more where the pattern carries a
+permutation; the bench's pattern carries none) beside the measured increment."""
 import argparse
 import json
 import math
@@ -67,6 +74,16 @@ def composed_backward_bytes(E, N, M, H, F):
     return spmm_b + softmax_b + dot_b
 
 
+def bias_forward_bytes(E, H, perm):
+    """What a [E, H] bias adds to the fused forward: its values, and the entry index where the pattern carries a permutation."""
+    return E * (4 * H + (4 if perm else 0))
+
+
+def bias_backward_bytes(E, H, perm):
+    """... and to the row pass of the backward: the values read, their gradient written (the entry index is read there anyway)."""
+    return E * 8 * H
+
+
 def timed_round(fn, steps):
     """-> the ms of `steps` calls, each between two events."""
     import torch
@@ -95,8 +112,9 @@ def alternate(contenders, rounds, steps, warmup):
     return out
 
 
-def sampled_reference(rp, col, rows, q, k, v, scale, dtype):
-    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j, times v_j."""
+def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None):
+    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j (+ bias [E, H], at the
+    CSR position), times v_j."""
     import torch
     deg = rp[rows + 1] - rp[rows]
     idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
@@ -104,10 +122,80 @@ def sampled_reference(rp, col, rows, q, k, v, scale, dtype):
     cols, inv = torch.unique(col[idx], return_inverse=True)
     qs, ks, vs = q[rows].cpu().to(dtype), k[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
     s = (qs[sub] * ks[inv]).sum(-1) * scale
+    if bias is not None:
+        s = s + bias[idx.to(bias.device)].cpu().to(dtype)
     m = torch.full(qs.shape[:2], -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
     p = torch.exp(s - m[sub])
     alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
     return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vs[inv])
+
+
+def measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
+    """--bias: fused with a bias, the composition with the same bias, fused without one; one JSON object per shape."""
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        scale = 1.0 / math.sqrt(F)
+        g = torch.Generator(device=dev).manual_seed(2)
+        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
+        bias = torch.randn(E, H, generator=g, device=dev)
+        qs = q * scale
+
+        def fused_bias(q_, k_, v_, b_):
+            return pg.dot_attention(pattern, q_, k_, v_, scale, b_)
+
+        def composed_bias(qs_, k_, v_, b_):
+            return pg.spmm(pattern, pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_) + b_), v_)
+
+        def fused(q_, k_, v_):
+            return pg.dot_attention(pattern, q_, k_, v_, scale)
+
+        def forward_of(fn, leaves):
+            def run():
+                with torch.no_grad():
+                    return fn(*leaves)
+            return run
+
+        def both_of(fn, leaves):
+            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
+
+            def run():
+                return torch.autograd.grad(fn(*leaves), leaves, G)
+            return run
+
+        out_f, out_c = forward_of(fused_bias, (q, k, v, bias))(), forward_of(composed_bias, (qs, k, v, bias))()
+        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, bias)
+        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, bias)
+        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, bias: out", ref32)
+        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, bias: out", ref32)
+        perm = pattern.perm is not None
+        res = {"bench": "dot_attention --bias", "device": torch.cuda.get_device_name(0),
+               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
+               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+               "longest_checked_row": int(deg[rows].max()), "out_err_fused_bias": err_f, "out_err_composed_bias": err_c,
+               "out_err_fp32_reference": parity.err(ref32, ref64), "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F),
+               "bias_forward_bytes": bias_forward_bytes(E, H, perm), "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F),
+               "bias_backward_bytes": bias_backward_bytes(E, H, perm)}
+        res["bias_forward_expected_increment"] = res["bias_forward_bytes"] / res["fused_forward_bytes"]
+        del out_f, out_c
+        legs = [("forward", alternate({"fused_bias": forward_of(fused_bias, (q, k, v, bias)),
+                                       "composed_bias": forward_of(composed_bias, (qs, k, v, bias)),
+                                       "fused": forward_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup))]
+        if not args.forward_only:
+            legs.append(("forward_backward", alternate({"fused_bias": both_of(fused_bias, (q, k, v, bias)),
+                                                        "composed_bias": both_of(composed_bias, (qs, k, v, bias)),
+                                                        "fused": both_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup)))
+        for what, r in legs:
+            for name in ("fused_bias", "composed_bias", "fused"):
+                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+            res[f"{what}_speedup"] = res[f"composed_bias_{what}_ms"] / res[f"fused_bias_{what}_ms"]
+            res[f"bias_{what}_measured_increment"] = res[f"fused_bias_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+        with open(args.out, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+        print(f"{shape}: the byte model expects the bias to add {100 * res['bias_forward_expected_increment']:.1f} % to the fused "
+              f"forward; measured {100 * res['bias_forward_measured_increment']:.1f} %", flush=True)
+        del q, k, v, G, qs, bias
+        torch.cuda.empty_cache()
 
 
 def measure(args):
@@ -129,6 +217,8 @@ def measure(args):
     picked = torch.randperm(N, generator=torch.Generator().manual_seed(3))[:SAMPLE_ROWS]
     rows = torch.unique(torch.cat([picked, torch.argmax(deg)[None]]))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.bias:
+        return measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     for shape in args.shapes.split(","):
         H, F = (int(x) for x in shape.split("x"))
         scale = 1.0 / math.sqrt(F)
@@ -196,9 +286,12 @@ def main():
     ap.add_argument("--scale", type=int, default=20)
     ap.add_argument("--draws", type=int, default=5_000_000)
     ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dot_attention_bench.jsonl"))
+    ap.add_argument("--bias", action="store_true", help="measure the per-entry bias: fused with a bias, the composition with it, fused without")
+    ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl, or profiles/dot_attention_bias_bench.jsonl with --bias")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bench.jsonl")
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
