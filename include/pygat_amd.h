@@ -669,6 +669,17 @@ int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const int32_t* ro
                                            const float* v, int64_t ldv, const float* bias, int bias_head_stride, const float* out,
                                            int64_t ldo, const float* m, const float* Z, const float* G, int64_t ldg, float* dq,
                                            int64_t lddq, float* P, float* S, float* dbias, void* ws, void* stream);
+/* The forward on bf16 k and v tables, for inference (the bf16-table instantiations of the two K19 forward kernels), additive under
+ * ABI 16.  k and v are rows of H*F bf16 values, 8-byte aligned, ldk and ldv in ELEMENTS, >= H*F and multiples of 4; q, out and ws as
+ * above (fp32, 16 bytes).  A lane's chunk is the same 4 row elements as in the fp32 kernels, one 8-byte load widened in registers, and
+ * everything after the load is theirs: out is pygat_dot_attn_forward's (pygat_dot_attn_bias_forward's) on the widened tables bit for
+ * bit, at 4 H*F + 4 gathered bytes per entry instead of 8 H*F + 4.  bias may be null: no bias, perm and bias_head_stride are then
+ * not looked at; otherwise as in pygat_dot_attn_bias_forward.  m and Z are not written: there is no backward on bf16 tables.
+ * Refusals as above after the launcher's own name.  The workspace and its size query are unchanged. */
+int pygat_dot_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                     int F, float scale, const float* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                     int64_t ldv, const float* bias, int bias_head_stride, float* out, int64_t ldo, void* ws,
+                                     void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

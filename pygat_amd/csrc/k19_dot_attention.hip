@@ -20,6 +20,10 @@
 // ds and stores it where it is asked for.  m and Z are those of the biased scores.  A bias of zeros changes no bit of out, dq, P or S; a
 // large negative finite bias (-9e15) gives p = 0 exactly while the row keeps another entry.  A row of one entry still gets out_i = v_j
 // and ds = T = dq_i = 0 exactly, p = 1 to rounding.
+// bf16 tables (a table-type parameter T of the two forward kernels; pygat_dot_attn_bf16_forward, inference only): k and v are rows of
+// H*F bf16 values.  The lane mapping is the fp32 one -- a lane's chunk is still 4 consecutive row elements, now one 8-byte load, widened
+// in registers (a bf16 is the high half of an fp32) -- and everything after the load sees the fp32 kernels' values in their order, so the
+// result is that of the fp32 kernels on the widened tables bit for bit.  Those instantiations write neither m nor Z (nothing reads them).
 #include "long_rows.h"
 #include <float.h>
 #include <string.h>
@@ -110,6 +114,17 @@ template <int VEC>
 __device__ __forceinline__ void da_load_row(const float* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
 #pragma unroll
   for (int v = 0; v < VEC; ++v) w[v] = ld4(p + ln.ofs[v]);
+}
+// a bf16 table: the same 4 row elements per chunk in one 8-byte load, widened exactly (element 0 is the low half of the first word)
+typedef unsigned short da_bf16;
+template <int VEC>
+__device__ __forceinline__ void da_load_row(const da_bf16* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    const uint2 r = *reinterpret_cast<const uint2*>(p + ln.ofs[v]);
+    w[v] = make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
+                       __uint_as_float(r.y & 0xffff0000u));
+  }
 }
 template <int VEC>
 __device__ __forceinline__ void da_store_row(float* p, const DaLane<VEC>& ln, const float4 (&w)[VEC]) {
@@ -202,12 +217,14 @@ template <int VEC, int U>
 struct DaRows {
   float4 k[U][VEC], v[U][VEC];
 };
-template <int VEC, int U>
+// T: the element type of the k and v tables (float, or da_bf16 in the inference forward: g.k and g.v then point at bf16 rows, ldk and
+// ldv counting elements all the same)
+template <int VEC, int U, typename T = float>
 __device__ __forceinline__ void da_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], DaRows<VEC, U>& w) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    da_load_row<VEC>(g.k + (int64_t)src[u] * g.ldk, ln, w.k[u]);
-    da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+    da_load_row<VEC>(reinterpret_cast<const T*>(g.k) + (int64_t)src[u] * g.ldk, ln, w.k[u]);
+    da_load_row<VEC>(reinterpret_cast<const T*>(g.v) + (int64_t)src[u] * g.ldv, ln, w.v[u]);
   }
 }
 
@@ -227,7 +244,7 @@ __device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[V
 // before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather.  BIAS: the next
 // batch's entry indices travel with its column indices, and its bias values are asked for once this batch is folded -- ahead of the
 // next gather, so they are there when it is -- an iteration still waits for one gather
-template <int LPR, int VEC, int U, bool BIAS>
+template <int LPR, int VEC, int U, bool BIAS, typename T>
 __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
                                             int64_t step, DaState<VEC>& st) {
   int64_t e = e0;
@@ -246,7 +263,7 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
     }
     while (full) {
       DaRows<VEC, U> w;
-      da_gather<VEC, U>(g, ln, src, w);
+      da_gather<VEC, U, T>(g, ln, src, w);
       e += U * step;
       full = e + (U - 1) * step < e1;
       if (full) {
@@ -269,13 +286,13 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
       da_bias_load<VEC, 1>(g, ln, eid, bs);
     }
     DaRows<VEC, 1> w;
-    da_gather<VEC, 1>(g, ln, src, w);
+    da_gather<VEC, 1, T>(g, ln, src, w);
     da_fwd_fold<LPR, VEC, 1, BIAS>(g, q, w, bs, st);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool BIAS>
+template <int LPR, int VEC, bool BIAS, typename T = float>
 __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -288,7 +305,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
     DaState<VEC> st;
     da_init<VEC>(st);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS>(g, ln, q, e0 + grp, e1, EPW, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T>(g, ln, q, e0 + grp, e1, EPW, st);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
       float mx = st.m[v];
@@ -314,9 +331,10 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
   });
 }
 
-// launch 2: one lane group per row
-template <int LPR, int VEC, bool BIAS>
+// launch 2: one lane group per row.  m and Z are what a backward reads: the bf16-table kernels, which have none, do not write them
+template <int LPR, int VEC, bool BIAS, typename T = float>
 __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
+  constexpr bool KEEP_MZ = sizeof(T) == sizeof(float);
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
@@ -336,7 +354,7 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   } else if (end > start) {
     float4 q[VEC];
     da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS>(g, ln, q, start, end, 1, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T>(g, ln, q, start, end, 1, st);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
@@ -345,10 +363,11 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
     const float z = st.z[v];
     const float4 a = st.acc[v];
     st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
-    if (ln.lead >> v & 1) {
-      g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
-      g.Z[row * g.H + ln.head[v]] = z;
-    }
+    if constexpr (KEEP_MZ)
+      if (ln.lead >> v & 1) {
+        g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
+        g.Z[row * g.H + ln.head[v]] = z;
+      }
   }
 }
 
@@ -551,25 +570,41 @@ static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
   return f;
 }
 
-// pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH)
-static int da_footprint(const char* name, const char* prefix, bool bias, int* regs, int* scratch) {
+// the bf16-table instantiations: the forward only
+template <bool BIAS>
+static const void* da_bf16_kernel_ptr(bool lng, int lpr, int vec) {
+  const void* f = nullptr;
+  PYGAT_DA_DISPATCH(lpr, vec, f = lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, da_bf16>)
+                                      : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, da_bf16>));
+  return f;
+}
+
+// pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH), and the
+// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>
+static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch) {
   const void* fn = nullptr;
   char dir[8] = "", kind[8] = "", rest = 0;
   int lpr = 0, vec = 0;
   const size_t np = strlen(prefix);
   if (!strncmp(name, prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
-      lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) &&
-      (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
-    fn = bias ? da_kernel_ptr<true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
-              : da_kernel_ptr<false>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
+      lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || (!bf16 && !strcmp(dir, "bwd"))) &&
+      (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4))) {
+    if (bf16)
+      fn = bias ? da_bf16_kernel_ptr<true>(!strcmp(kind, "long"), lpr, vec) : da_bf16_kernel_ptr<false>(!strcmp(kind, "long"), lpr, vec);
+    else
+      fn = bias ? da_kernel_ptr<true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
+                : da_kernel_ptr<false>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
+  }
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (%s{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name, prefix);
+    set_error("kernel_footprint: unknown kernel '%s' (%s{%s}_{long,row}_l<LPR>v<VEC>)", name, prefix, bf16 ? "fwd" : "fwd,bwd");
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
 }
-int footprint_k19(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19_", false, regs, scratch); }
-int footprint_k19b(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19b_", true, regs, scratch); }
+int footprint_k19(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19_", false, false, regs, scratch); }
+int footprint_k19b(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19b_", true, false, regs, scratch); }
+int footprint_k19h(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19h_", false, true, regs, scratch); }
+int footprint_k19hb(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19hb_", true, true, regs, scratch); }
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
 
@@ -582,18 +617,21 @@ static int da_check_shape(const char* what, int64_t nnz, int H, int F) {
   return PYGAT_OK;
 }
 
-// a row table: non-null, 16-byte aligned, its stride a multiple of 4 floats and at least H x F
-#define DA_TABLE(what, name, ptr, ld, HF)                                                                              \
+// a row table: non-null, aligned to a lane's chunk of 4 elements (16 bytes of floats, 8 of bf16), its stride a multiple of 4 elements
+// and at least H x F
+#define DA_TABLE_ALIGNED(what, name, ptr, ld, HF, align)                                                               \
   do {                                                                                                                 \
     PYGAT_REQUIRE(ptr, "%s: null %s", what, name);                                                                     \
-    PYGAT_REQUIRE(aligned16(ptr), "%s: %s must be 16-byte aligned", what, name);                                       \
+    PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & ((align) - 1u)) == 0, "%s: %s must be %d-byte aligned", what, name, (int)(align)); \
     PYGAT_REQUIRE((ld) >= (HF) && (ld) % 4 == 0, "%s: the row stride of %s, %lld, must be a multiple of 4 and at least H x F = %d", \
                   what, name, (long long)(ld), (int)(HF));                                                             \
   } while (0)
+#define DA_TABLE(what, name, ptr, ld, HF) DA_TABLE_ALIGNED(what, name, ptr, ld, HF, 16)
 
+// kv_bytes: the size of an element of k and v (4, or 2: bf16 tables); keep_mz: the launcher writes or reads m and Z
 static int da_check_common(const char* what, int n_rows, int64_t nnz, int H, int F, const int32_t* rowptr, const int32_t* col,
-                           const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* out,
-                           int64_t ldo, const float* m, const float* Z, const void* ws) {
+                           const float* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const float* out,
+                           int64_t ldo, const float* m, const float* Z, const void* ws, int kv_bytes = 4, bool keep_mz = true) {
   const int rc = da_check_shape(what, nnz, H, F);
   if (rc != PYGAT_OK) return rc;
   PYGAT_REQUIRE(n_rows >= 0, "%s: n_rows=%d", what, n_rows);
@@ -602,11 +640,11 @@ static int da_check_common(const char* what, int n_rows, int64_t nnz, int H, int
   PYGAT_REQUIRE(rowptr, "%s: null rowptr", what);
   PYGAT_REQUIRE(nnz == 0 || col, "%s: null col", what);
   DA_TABLE(what, "q", q, ldq, HF);
-  DA_TABLE(what, "k", k, ldk, HF);
-  DA_TABLE(what, "v", v, ldv, HF);
+  DA_TABLE_ALIGNED(what, "k", k, ldk, HF, 4 * kv_bytes);
+  DA_TABLE_ALIGNED(what, "v", v, ldv, HF, 4 * kv_bytes);
   DA_TABLE(what, "out", out, ldo, HF);
-  PYGAT_REQUIRE(m, "%s: null m", what);
-  PYGAT_REQUIRE(Z, "%s: null Z", what);
+  PYGAT_REQUIRE(m || !keep_mz, "%s: null m", what);
+  PYGAT_REQUIRE(Z || !keep_mz, "%s: null Z", what);
   PYGAT_REQUIRE(ws, "%s: null workspace", what);
   PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
   return PYGAT_OK;
@@ -642,11 +680,13 @@ static int da_check_bias(const char* what, int64_t nnz, const float* bias, int b
   return PYGAT_OK;
 }
 
-template <bool BIAS>
+// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z
+template <bool BIAS, typename T = float>
 static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
-                      int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                      int F, float scale, const float* q, int64_t ldq, const T* k, int64_t ldk, const T* v, int64_t ldv,
                       const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
-  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws, (int)sizeof(T),
+                           sizeof(T) == sizeof(float));
   if (rc != PYGAT_OK) return rc;
   if constexpr (BIAS) {
     rc = da_check_bias(what, nnz, bias, bias_head_stride);
@@ -654,15 +694,16 @@ static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* 
   }
   if (n_rows == 0) return PYGAT_OK;
   DaArgs g;
-  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v),
+          ldv, out, ldo, m, Z, ws);
   if constexpr (BIAS) { g.perm = perm; g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -723,6 +764,19 @@ extern "C" int pygat_dot_attn_bias_forward(int n_rows, int64_t nnz, const int32_
                                                 int64_t ldo, float* m, float* Z, void* ws, void* stream) {
   return da_forward<true>("dot_attn_bias_forward", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
                           bias_head_stride, out, ldo, m, Z, ws, stream);
+}
+
+// the inference forward on bf16 k and v tables (8-byte aligned rows, strides in elements); a null bias: the kernels without BIAS
+extern "C" int pygat_dot_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                                int H, int F, float scale, const float* q, int64_t ldq, const void* k, int64_t ldk,
+                                                const void* v, int64_t ldv, const float* bias, int bias_head_stride, float* out,
+                                                int64_t ldo, void* ws, void* stream) {
+  const da_bf16 *kh = static_cast<const da_bf16*>(k), *vh = static_cast<const da_bf16*>(v);
+  if (bias)
+    return da_forward<true, da_bf16>("dot_attn_bf16_forward", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, kh, ldk, vh, ldv, bias,
+                                     bias_head_stride, out, ldo, nullptr, nullptr, ws, stream);
+  return da_forward<false, da_bf16>("dot_attn_bf16_forward", n_rows, nnz, rowptr, col, nullptr, H, F, scale, q, ldq, kh, ldk, vh, ldv,
+                                    nullptr, 1, out, ldo, nullptr, nullptr, ws, stream);
 }
 
 extern "C" int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,

@@ -9,12 +9,16 @@ its score as an op of its own.
     out = dot_attention(pattern, q, k, v)                # q [n_rows, H, F]; k, v [n_cols, H, F]; scale = 1 / sqrt(F)
     out = spmm(pattern, edge_softmax(pattern, edge_dot(pattern, q, k, scale)), v)       # the same, from parts, with [E, H] tensors
     out = dot_attention(pattern, q, k, v, bias=emb(edge_type))    # a per-entry term on the score, [E, H] or [E]; differentiable too
+    with torch.no_grad():                                         # inference: bf16 tables, made once -- half the gathered bytes, the
+        out = dot_attention(pattern, q, k16, v16)                 # bits of dot_attention(pattern, q, k16.float(), v16.float())
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the
 pattern rectangular.  To attend over columns instead of rows, build the pattern from swapped indices.  Both ops are differentiable
 in every tensor.  The backward of dot_attention keeps out and (m, Z) per row; its two per-entry tensors P and S ([E, H] each) live
 only inside backward, between the row pass and the two transposed SpMMs that form dk and dv.  fp32, no float atomics, a fixed
 summation order: two runs give the same bits.  Nothing is read back to the host.  There is no CPU path and no fallback to torch.
+dot_attention also takes k and v as bfloat16 tables for inference (the bf16-table instantiations of the K19 forward kernels): no
+backward, no fp32 copy of either table, the float32 op's result on the widened tables bit for bit.  edge_dot stays float32 only.
 """
 from __future__ import annotations
 
@@ -34,15 +38,19 @@ _PAD_HINT = ("zero-padding the columns of q, k and v to the next allowed F leave
              "(pass scale yourself: the default follows the padded F)")
 
 
-def _tables(op: str, pattern, q, others):
-    """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns."""
+def _tables(op: str, pattern, q, others, bf16_others: bool = False):
+    """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns,
+    float32 like q, or bfloat16 where bf16_others (dot_attention's inference forward)."""
     if not isinstance(pattern, EdgePattern):
         raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
     named = (("q", q, pattern.n_rows, "rows"),) + tuple((name, t, pattern.n_cols, "columns") for name, t in others)
     for name, t, _, _ in named:
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path)")
-        if t.dtype != torch.float32:
+        if bf16_others and name != "q":
+            if t.dtype != torch.bfloat16:
+                raise ValueError(f"pygat_amd {op}: {name} must be bfloat16 like the other table, not {t.dtype}")
+        elif t.dtype != torch.float32:
             raise ValueError(f"pygat_amd {op}: {name} must be float32, not {t.dtype}")
         if t.device != pattern.device:
             raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}")
@@ -115,8 +123,8 @@ def edge_dot(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, scale: floa
 
 
 # ------------------------------------------------------------------------------------------------------------------- dot_attention
-def _attention_shapes(pattern, q, k, v):
-    H, F, flat = _tables("dot_attention", pattern, q, (("k", k), ("v", v)))
+def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False):
+    H, F, flat = _tables("dot_attention", pattern, q, (("k", k), ("v", v)), bf16_tables)
     if not (1 <= H <= MAX_HEADS):
         raise ValueError(f"pygat_amd dot_attention: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
     if not (MIN_F <= F <= MAX_F) or F & (F - 1):
@@ -225,6 +233,41 @@ class _DotAttentionFn(torch.autograd.Function):
         return None, dq.view(q.shape) if need_q else None, dk, dv, None, db
 
 
+def _bf16_tables(k, v) -> bool:
+    """k and v are both bfloat16 (the inference forward); one of them alone is refused."""
+    kb, vb = (isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (k, v))
+    if kb != vb:
+        kd, vd = (getattr(t, "dtype", type(t).__name__) for t in (k, v))
+        raise ValueError(f"pygat_amd dot_attention: k is {kd} and v is {vd}: the inference forward takes both k and v as bfloat16 "
+                         f"tables (k.bfloat16(), v.bfloat16()); otherwise both are float32")
+    return kb
+
+
+def _dot_attention_bf16(pattern, q, k, v, scale, bias):
+    """The inference forward on bfloat16 k and v: one pygat_dot_attn_bf16_forward launch on the tables as they are -- nothing is
+    widened, nothing is kept for a backward."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (q, k, v, bias)):
+        raise ValueError("pygat_amd dot_attention: bfloat16 k and v are for inference (there is no backward through them): call it "
+                         "under torch.no_grad(), or pass float32 tables")
+    if bias is not None:
+        _bias_tensor(pattern, bias)
+    H, F, flat = _attention_shapes(pattern, q, k, v, bf16_tables=True)
+    bhs = 1 if bias is None else _bias_head_stride(pattern, bias, H, flat)
+    scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
+    n, HF = pattern.n_rows, H * F
+    if pattern.nnz == 0:                        # every row is without entries
+        return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+    qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+    bc = None if bias is None else bias.detach().contiguous()
+    with torch.cuda.device(qc.device):
+        out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
+        ws = _workspace(pattern.nnz, H, F, qc.device)
+        check(lib.pygat_dot_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
+                                              _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out), HF, _ptr(ws),
+                                              _stream()), "dot_attn_bf16_forward")
+    return out.view(q.shape)
+
+
 def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
                   bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out like q ([n_rows, H, F], or [n_rows, F] with k, v [n_cols, F]): out[i] = sum over the entries (i, j) of row i of
@@ -234,5 +277,11 @@ def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: tor
     maximum, so a bias of zeros changes no bit of the result.  Its values must be finite (nothing is read back to check them); a large negative finite one such as -9e15 masks an entry exactly: its
     coefficient, its share of out and every gradient that passes through it are exact zeros, provided the row keeps at least one
     unmasked entry.  Differentiable in q, k, v and bias (the gradient of a [E] bias is the sum over the heads).  float32 GPU tensors;
-    1 <= H <= 64, F a power of two in 4..256, H * F <= 1024."""
+    1 <= H <= 64, F a power of two in 4..256, H * F <= 1024.
+    Inference on bfloat16 tables: k and v may both be torch.bfloat16 (made once, e.g. k.bfloat16(); q, bias and the result stay
+    float32).  The result is that of the float32 op on k.float() and v.float(), bit for bit -- the rows are widened in registers and
+    all arithmetic stays fp32 -- at half the gathered bytes and half the memory of the two tables.  There is no backward: with grad
+    mode on and a tensor that requires grad it raises; call it under torch.no_grad(), or pass float32 tables."""
+    if _bf16_tables(k, v):
+        return _dot_attention_bf16(pattern, q, k, v, scale, bias)
     return _DotAttentionFn.apply(pattern, q, k, v, scale, bias)

@@ -6,6 +6,7 @@ at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone 
     python tools/dot_attention_bench.py [--shapes 8x16,8x64] [--rounds 5] [--steps 10] [--warmup 10] [--out profiles/dot_attention_bench.jsonl]
     rocprofv3 --kernel-trace --stats -d DIR -o da -- python tools/dot_attention_bench.py --child --forward-only --shapes 8x64 --out DIR/run.jsonl
     python tools/dot_attention_bench.py --bias [...]       # the per-entry bias: three contenders -> profiles/dot_attention_bias_bench.jsonl
+    python tools/dot_attention_bench.py --kv-bf16 [...]    # bf16 k and v tables: fp32 against bf16 forward -> profiles/dot_attention_bf16_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
@@ -22,7 +23,13 @@ Recorded, not gated.  One JSON object per shape, appended.
 that requires a gradient, the composition spmm(edge_softmax(edge_dot(q, k) + bias), v) with the same bias, and the fused op without
 a bias, prices the first two on the sampled rows against the fp64 computation with the bias on the scores, and prints the byte
 model's expectation of what the bias adds to the fused forward (4 H bytes per entry, 4 more where the pattern carries a
-permutation; the bench's pattern carries none) beside the measured increment."""
+permutation; the bench's pattern carries none) beside the measured increment.
+
+--kv-bf16 measures the inference forward on bfloat16 k and v tables (forward only): in the one child process it alternates the fused
+forward on float32 tables with the fused forward on bfloat16 tables.  Both are fed the same values -- N(0, 1) draws rounded to
+bfloat16, and those widened to float32 -- so the two outputs are compared with torch.equal here; the bfloat16 one is priced on the
+sampled rows as above.  Recorded per shape: both medians with their spreads, their ratio, and the byte model's ratio beside it
+((4 R + 4) / (8 R + 4) per entry, and with the per-row traffic) -> profiles/dot_attention_bf16_bench.jsonl."""
 import argparse
 import json
 import math
@@ -41,6 +48,13 @@ def fused_forward_bytes(E, N, M, H, F):
     """Per entry: the k and v rows and the column index.  Per row: q read, out, m and Z written, the row pointer."""
     R = H * F
     return E * (2 * R * 4 + 4) + N * (2 * R * 4 + 2 * H * 4 + 4)
+
+
+def bf16_forward_bytes(E, N, M, H, F):
+    """bfloat16 k and v tables (inference).  Per entry: the two rows at 2 bytes a value and the column index.  Per row: q read and out
+    written in float32, the row pointer; m and Z are not written."""
+    R = H * F
+    return E * (2 * R * 2 + 4) + N * (2 * R * 4 + 4)
 
 
 def composed_forward_bytes(E, N, M, H, F):
@@ -198,6 +212,55 @@ def measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, 
         torch.cuda.empty_cache()
 
 
+def measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
+    """--kv-bf16: the fused forward on float32 tables against the fused forward on bfloat16 tables; one JSON object per shape."""
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        R = H * F
+        scale = 1.0 / math.sqrt(F)
+        g = torch.Generator(device=dev).manual_seed(2)
+        q = torch.randn(N, H, F, generator=g, device=dev)
+        k16, v16 = (torch.randn(N, H, F, generator=g, device=dev).bfloat16() for _ in range(2))
+        kw, vw = k16.float(), v16.float()                           # the same values, widened: what the float32 contender is fed
+
+        def run_fp32():
+            with torch.no_grad():
+                return pg.dot_attention(pattern, q, kw, vw, scale)
+
+        def run_bf16():
+            with torch.no_grad():
+                return pg.dot_attention(pattern, q, k16, v16, scale)
+
+        out_w, out_h = run_fp32(), run_bf16()
+        equal = bool(torch.equal(out_w, out_h))
+        ref64 = sampled_reference(rp_t, col_t, rows, q, kw, vw, scale, torch.float64)
+        ref32 = sampled_reference(rp_t, col_t, rows, q, kw, vw, scale, torch.float32)
+        err_h = parity.close_fwd(out_h[rows.to(dev)], ref64, f"{shape} fused, bf16 tables: out", ref32)
+        res = {"bench": "dot_attention --kv-bf16", "device": torch.cuda.get_device_name(0),
+               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
+               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+               "longest_checked_row": int(deg[rows].max()), "out_bf16_equals_out_fp32_on_widened_tables": equal,
+               "out_err_fused_bf16": err_h, "out_err_fp32_reference": parity.err(ref32, ref64),
+               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F),
+               "byte_model_ratio_per_entry": (4 * R + 4) / (8 * R + 4)}
+        res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
+        del out_w, out_h
+        r = alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
+        for name in ("fused_fp32", "fused_bf16"):
+            res[f"{name}_forward_ms"], res[f"{name}_forward_spread_ms"] = r[name]
+        res["measured_ratio"] = res["fused_bf16_forward_ms"] / res["fused_fp32_forward_ms"]
+        res["faster_by_more_than_the_spread"] = (res["fused_fp32_forward_ms"] - res["fused_bf16_forward_ms"]
+                                                 > max(res["fused_fp32_forward_spread_ms"], res["fused_bf16_forward_spread_ms"]))
+        with open(args.out, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+        print(f"{shape}: bf16 tables take {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
+              f"{res['byte_model_ratio']:.3f} ({res['byte_model_ratio_per_entry']:.3f} per entry); outputs "
+              f"{'bit-equal' if equal else 'DIFFER'}", flush=True)
+        del q, k16, v16, kw, vw
+        torch.cuda.empty_cache()
+
+
 def measure(args):
     import torch
     if not torch.cuda.is_available():
@@ -219,6 +282,8 @@ def measure(args):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if args.bias:
         return measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
+    if args.kv_bf16:
+        return measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     for shape in args.shapes.split(","):
         H, F = (int(x) for x in shape.split("x"))
         scale = 1.0 / math.sqrt(F)
@@ -287,11 +352,17 @@ def main():
     ap.add_argument("--draws", type=int, default=5_000_000)
     ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
     ap.add_argument("--bias", action="store_true", help="measure the per-entry bias: fused with a bias, the composition with it, fused without")
-    ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl, or profiles/dot_attention_bias_bench.jsonl with --bias")
+    ap.add_argument("--kv-bf16", action="store_true", help="measure bfloat16 k and v tables: the fused forward on float32 tables "
+                    "against the fused forward on bfloat16 tables (forward only)")
+    ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl; profiles/dot_attention_bias_bench.jsonl with --bias, "
+                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.bias and args.kv_bf16:
+        ap.error("--bias and --kv-bf16 are separate measurements")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bench.jsonl")
+        name = "dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bf16_bench.jsonl" if args.kv_bf16 else "dot_attention_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
