@@ -680,6 +680,30 @@ int pygat_dot_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, 
                                      int F, float scale, const float* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
                                      int64_t ldv, const float* bias, int bias_head_stride, float* out, int64_t ldo, void* ws,
                                      void* stream);
+/* The bias pair with seeded dropout of the softmax coefficients, for training (the DROP instantiations of the four fp32 K19 kernels),
+ * additive under ABI 16:
+ *   out[i, h, :] = sum_{e in row i} alpha[e, h] mask[c(e), h] v[j, h, :],   alpha = softmax_row(scale <q, k> + bias) over ALL entries of
+ * the row -- a dropped entry stays in the denominator; m and Z are the undropped softmax's -- mask in {0, 1 / (1 - p)}, c(e) the CALLER's
+ * entry index (perm[e]; perm may be null: the position itself).  mask[c, h] is element idx = c H + h of the flat layout of
+ * pygat_dropout_mask: word (idx & 3) of Philox-4x32-10(counter = (idx >> 2 low word, idx >> 2 high word, stream_id, 0xFFFFFFFF), key =
+ * *seed), kept iff word < the threshold of p; pygat_dropout_mask(nnz H, p, seed, stream_id, ...) writes the same table.  The decision is
+ * drawn in registers in the forward and again in backward_rows: no mask is stored.  seed is a uint64 in DEVICE memory, read by the
+ * kernels (nothing is read back; a captured graph replays with the seed found there).  backward_rows: D = <G, out>, ds = scale p (mask
+ * <G, v> - D), dbias = p (mask <G, v> - D), P := p mask and S := ds, so dk = pygat_spmm_forward(val = S, b = q) and dv =
+ * pygat_spmm_forward(val = P, b = G) as above.  bias may be null: no bias, bias_head_stride is then not looked at (dbias is not
+ * written).  A row of one entry gets out_i = mask v_j bit for bit; a row whose entries are all dropped, and every row at p = 1, exact
+ * zeros.  Refusals as for the bias pair after the launcher's own name; besides: a null or misaligned (8 bytes) seed, p outside [0, 1]
+ * (a NaN included).  Both launchers must be given the same p, seed value and stream_id.  The workspace and its size query are unchanged. */
+int pygat_dot_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                   int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                   int64_t ldv, const float* bias, int bias_head_stride, float p, const void* seed,
+                                   uint32_t stream_id, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                         int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                         const float* v, int64_t ldv, const float* bias, int bias_head_stride, float p,
+                                         const void* seed, uint32_t stream_id, const float* out, int64_t ldo, const float* m,
+                                         const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S,
+                                         float* dbias, void* ws, void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

@@ -24,7 +24,20 @@
 // H*F bf16 values.  The lane mapping is the fp32 one -- a lane's chunk is still 4 consecutive row elements, now one 8-byte load, widened
 // in registers (a bf16 is the high half of an fp32) -- and everything after the load sees the fp32 kernels' values in their order, so the
 // result is that of the fp32 kernels on the widened tables bit for bit.  Those instantiations write neither m nor Z (nothing reads them).
+// DROP (a compile-time flag of the four fp32 kernels, beside BIAS; pygat_dot_attn_dropout_*): seeded dropout of the coefficients,
+// out[i, h] = sum_e alpha[e, h] mask[c(e), h] v[j, h] with mask in {0, 1 / (1 - p)}, drawn in registers in the forward and again in the
+// backward: no mask tensor exists.  mask[c, h] is element c H + h of the flat layout of k7_dropout.hip's mask kernel (rng.h): word
+// (idx & 3) of Philox-4x32-10(counter = (idx >> 2 low, idx >> 2 high, stream_id, 0xFFFFFFFF), key = *seed) < thresh keeps, so
+// pygat_dropout_mask(nnz H, p, seed, stream_id) writes the same table.  The entry index is the one the BIAS path already carries a
+// batch ahead; the LH lanes of a head, which would draw the same word, share a batch's entries among them and exchange the decisions
+// (da_keep_batch): ceil(U / LH) Philox calls per (batch, chunk) and lane, one per entry in the remainder loop.  m and Z are the
+// undropped softmax's -- a dropped entry stays in the denominator -- and only (p mask) v goes into acc; record merges and long-row
+// pieces are as without DROP.  Backward: D = <G_i, out_i> as before (out is the dropped sum), ds = scale p (mask <G_i, v_j> - D),
+// T = p (mask <G_i, v_j> - D), and P := p mask, so dv = spmm^T(P, G) needs no change.  A row of one entry gets out_i = mask v_j bit for
+// bit; a row whose entries are all dropped, and every row under p = 1, exact zeros.  The instruction streams of the kernels without
+// DROP are what they were before the flag.
 #include "long_rows.h"
+#include "rng.h"
 #include <float.h>
 #include <string.h>
 
@@ -54,6 +67,7 @@ struct DaArgs {
   int64_t bstride;             // H for a [nnz x H] bias, 1 for a [nnz] one shared by the heads
   int bhs;                     // 1 | 0
   float* dbias;                // [nnz x H], the caller's entry order; null: not asked for
+  DropRng rng;                 // DROP kernels only: the seed (device memory), stream id, keep threshold and 1 / keep of the mask
 };
 
 static inline int64_t da_pstride(int H, int F) { return ((int64_t)H * F + 2 * H + 3) & ~(int64_t)3; }
@@ -167,6 +181,51 @@ __device__ __forceinline__ void da_bias_load(const DaArgs& g, const DaLane<VEC>&
     for (int v = 0; v < VEC; ++v) bs.b[u][v] = g.bias[(int64_t)eid[u] * g.bstride + ln.head[v] * g.bhs];
 }
 
+// DROP: the key of the row's draws, read once per kernel, and the keep factor (0 or 1 / (1 - p)) of flat mask element idx = c(e) H + h
+template <bool DROP>
+__device__ __forceinline__ uint2 da_key(const DaArgs& g) {
+  if constexpr (!DROP) return make_uint2(0u, 0u);
+  else {
+    const uint64_t seed = *g.rng.seed;
+    return make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  }
+}
+__device__ __forceinline__ float da_keep(const DaArgs& g, uint2 key, int64_t idx) {
+  const uint64_t q4 = (uint64_t)idx >> 2;
+  const uint4 w = philox4x32_10(make_uint4((uint32_t)q4, (uint32_t)(q4 >> 32), g.rng.stream_id, 0xFFFFFFFFu), key);
+  return word_of(w, (int)(idx & 3)) < g.rng.thresh ? g.rng.scale : 0.f;
+}
+// ... of a batch of U entries, base[u] = c(e_u) H.  The LH lanes of a head would all draw the same word for an entry, so they share the
+// batch instead: in a round, lane i of the head draws for entry t0 + i, and the head's lanes read each other's factor, one __shfl per
+// (entry, chunk): ceil(U / LH) Philox calls per lane and chunk, not U (a lane's place in its head is the same for all its chunks: 64 is
+// a multiple of LH; the lanes of a real head are all inside the row).  The rounds are a loop on purpose: unrolled, it is U copies of
+// the ten rounds
+template <int VEC, int U>
+__device__ __forceinline__ void da_keep_batch(const DaArgs& g, const DaLane<VEC>& ln, uint2 key, const int64_t (&base)[U],
+                                              float (&keep)[U][VEC]) {
+  if constexpr (U == 1) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) keep[0][v] = da_keep(g, key, base[0] + ln.head[v]);
+  } else {
+    const int li = (threadIdx.x & 63) & (g.LH - 1);
+#pragma unroll 1
+    for (int t0 = 0; t0 < U; t0 += g.LH) {
+      int64_t b = base[U - 1];                                   // (a lane past the batch draws for its last entry; nobody reads it)
+#pragma unroll
+      for (int u = 0; u < U - 1; ++u) b = t0 + li == u ? base[u] : b;
+      float mine[VEC];
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) mine[v] = da_keep(g, key, b + ln.head[v]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (u >= t0 && u < t0 + g.LH) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) keep[u][v] = __shfl(mine[v], u - t0, g.LH);
+        }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------ forward
 template <int VEC>
 struct DaState {
@@ -203,6 +262,19 @@ __device__ __forceinline__ void da_fold_b(float& m, float& z, float4& acc, float
   m = up ? __fadd_rn(s, b) : m;
 }
 
+// DROP: the fold of da_fold (da_fold_b under BIAS) with (p keep) v into acc; z takes p whole: a dropped entry stays in the denominator
+template <bool BIAS>
+__device__ __forceinline__ void da_fold_drop(float& m, float& z, float4& acc, float s, float b, float keep, const float4& w) {
+  const float d = BIAS ? s - (m - b) : s - m;
+  const float ex = __expf(-fabsf(d));
+  const bool up = d > 0.f;
+  const float r = up ? ex : 1.f, p = up ? 1.f : ex;
+  const float pk = p * keep;
+  z = fmaf(z, r, p);
+  acc.x = fmaf(acc.x, r, pk * w.x); acc.y = fmaf(acc.y, r, pk * w.y); acc.z = fmaf(acc.z, r, pk * w.z); acc.w = fmaf(acc.w, r, pk * w.w);
+  m = up ? (BIAS ? __fadd_rn(s, b) : s) : m;
+}
+
 // (m, z, acc) <- (m, z, acc) (+) (m2, z2, acc2), the earlier entries on the left
 __device__ __forceinline__ void da_merge(float& m, float& z, float4& acc, float m2, float z2, const float4& acc2) {
   const float mn = fmaxf(m, m2);
@@ -228,14 +300,25 @@ __device__ __forceinline__ void da_gather(const DaArgs& g, const DaLane<VEC>& ln
   }
 }
 
-template <int LPR, int VEC, int U, bool BIAS>
-__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[VEC], const DaRows<VEC, U>& w,
-                                            const DaBias<VEC, U, BIAS>& bs, DaState<VEC>& st) {
+// eid (BIAS | DROP) and key (DROP): the caller's entry indices of the batch and the key of its draws
+template <int LPR, int VEC, int U, bool BIAS, bool DROP>
+__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], const DaRows<VEC, U>& w,
+                                            const DaBias<VEC, U, BIAS>& bs, const int32_t (&eid)[U], uint2 key, DaState<VEC>& st) {
+  [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+  if constexpr (DROP) {
+    int64_t base[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) base[u] = (int64_t)eid[u] * g.H;
+    da_keep_batch<VEC, U>(g, ln, key, base, keep);
+  }
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      if constexpr (BIAS) da_fold_b(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), bs.b[u][v], w.v[u][v]);
+      if constexpr (DROP)
+        da_fold_drop<BIAS>(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), BIAS ? bs.b[u][v] : 0.f,
+                           keep[u][v], w.v[u][v]);
+      else if constexpr (BIAS) da_fold_b(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), bs.b[u][v], w.v[u][v]);
       else da_fold(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), w.v[u][v]);
     }
 }
@@ -243,10 +326,12 @@ __device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const float4 (&q)[V
 // the entries e0, e0 + step, ... < e1 of one row, folded in that order, U at a time: the column indices of the next U are asked for
 // before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather.  BIAS: the next
 // batch's entry indices travel with its column indices, and its bias values are asked for once this batch is folded -- ahead of the
-// next gather, so they are there when it is -- an iteration still waits for one gather
-template <int LPR, int VEC, int U, bool BIAS, typename T>
+// next gather, so they are there when it is -- an iteration still waits for one gather.  DROP: the entry indices travel the same way,
+// with or without a bias
+template <int LPR, int VEC, int U, bool BIAS, typename T, bool DROP>
 __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
-                                            int64_t step, DaState<VEC>& st) {
+                                            int64_t step, uint2 key, DaState<VEC>& st) {
+  constexpr bool EID = BIAS || DROP;
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
@@ -257,9 +342,10 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         src[u] = g.col[e + u * step];
-        if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+        if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
       }
-      if constexpr (BIAS) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
+      if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
+      if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
     }
     while (full) {
       DaRows<VEC, U> w;
@@ -270,31 +356,35 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
-          if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
         }
       }
-      da_fwd_fold<LPR, VEC, U, BIAS>(g, q, w, bs, st);
-      if constexpr (BIAS)
-        if (full) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
+      da_fwd_fold<LPR, VEC, U, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);    // (eid: this batch's, not yet replaced)
+      if constexpr (EID)
+        if (full) {
+          da_eids<U>(g, raw, e, step, eid);
+          if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
+        }
     }
   }
   for (; e < e1; e += step) {
     const int32_t src[1] = {g.col[e]};
     DaBias<VEC, 1, BIAS> bs;
-    if constexpr (BIAS) {
-      const int32_t eid[1] = {da_eid(g, da_eid_raw(g, e), e)};
-      da_bias_load<VEC, 1>(g, ln, eid, bs);
-    }
+    [[maybe_unused]] int32_t eid[1] = {0};
+    if constexpr (EID) eid[0] = da_eid(g, da_eid_raw(g, e), e);
+    if constexpr (BIAS) da_bias_load<VEC, 1>(g, ln, eid, bs);
     DaRows<VEC, 1> w;
     da_gather<VEC, 1, T>(g, ln, src, w);
-    da_fwd_fold<LPR, VEC, 1, BIAS>(g, q, w, bs, st);
+    da_fwd_fold<LPR, VEC, 1, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool BIAS, typename T = float>
+template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false>
 __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
+  static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
   constexpr int EPW = 64 / LPR;
+  const uint2 key = da_key<DROP>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
@@ -305,7 +395,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
     DaState<VEC> st;
     da_init<VEC>(st);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T>(g, ln, q, e0 + grp, e1, EPW, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP>(g, ln, q, e0 + grp, e1, EPW, key, st);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
       float mx = st.m[v];
@@ -332,8 +422,9 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row.  m and Z are what a backward reads: the bf16-table kernels, which have none, do not write them
-template <int LPR, int VEC, bool BIAS, typename T = float>
+template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false>
 __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
+  static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
   constexpr bool KEEP_MZ = sizeof(T) == sizeof(float);
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -354,7 +445,7 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   } else if (end > start) {
     float4 q[VEC];
     da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T>(g, ln, q, start, end, 1, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP>(g, ln, q, start, end, 1, da_key<DROP>(g), st);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
@@ -397,9 +488,14 @@ __device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { retu
 
 // BIAS: T = p (<G_i, v_j> - D_i), the gradient of the bias, formed beside ds -- ds itself is the unbiased kernel's expression, so a
 // bias of zeros leaves the bits of S, dq and dk alone -- and stored where it is asked for
-template <int LPR, int VEC, int U, bool BIAS>
+// DROP: the batch's keep factors are drawn again (ent[u] + head is an entry's flat mask index); an entry's multiplies <G_i, v_j> --
+// D_i = <G_i, out_i> is the row term of the dropped sum already -- and the stored P is p keep, what the transposed SpMM of dv
+// multiplies G with
+template <int LPR, int VEC, int U, bool BIAS, bool DROP>
 __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, const DaRows<VEC, U>& w,
-                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, float4 (&dq)[VEC]) {
+                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, uint2 key, float4 (&dq)[VEC]) {
+  [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+  if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -408,11 +504,16 @@ __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& 
       float p;
       if constexpr (BIAS) p = __expf(s - (r.m[v] - bs.b[u][v])) * r.rz[v];      // (as da_fold_b: s - m with the bias on m's side)
       else p = __expf(s - r.m[v]) * r.rz[v];
-      const float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+      float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+      float pk = p;
+      if constexpr (DROP) {
+        dp *= keep[u][v];
+        pk *= keep[u][v];
+      }
       const float ds = g.scale * p * (dp - r.D[v]);
       da_axpy(dq[v], ds, w.k[u][v]);
       if (ln.lead >> v & 1) {
-        g.P[ent[u] + ln.head[v]] = p;
+        g.P[ent[u] + ln.head[v]] = pk;
         g.S[ent[u] + ln.head[v]] = ds;
         if constexpr (BIAS)
           if (g.dbias) g.dbias[ent[u] + ln.head[v]] = p * (dp - r.D[v]);
@@ -421,10 +522,11 @@ __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& 
 }
 
 // as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic; BIAS: its bias values are
-// asked for once this batch is folded, ahead of the next gather
-template <int LPR, int VEC, int U, bool BIAS>
+// asked for once this batch is folded, ahead of the next gather; DROP: the entry indices travel as under BIAS, with or without one
+template <int LPR, int VEC, int U, bool BIAS, bool DROP>
 __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, int64_t e0, int64_t e1,
-                                            int64_t step, float4 (&dq)[VEC]) {
+                                            int64_t step, uint2 key, float4 (&dq)[VEC]) {
+  constexpr bool EID = BIAS || DROP;
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
@@ -437,15 +539,16 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         src[u] = g.col[e + u * step];
-        if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+        if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
         else ent_next[u] = da_entry(g, e + u * step);
       }
-      if constexpr (BIAS) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
+      if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
+      if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
     }
     while (full) {
       DaRows<VEC, U> w;
       da_gather<VEC, U>(g, ln, src, w);
-      if constexpr (!BIAS) {
+      if constexpr (!EID) {
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
       }
@@ -455,17 +558,20 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
-          if constexpr (BIAS) raw[u] = da_eid_raw(g, e + u * step);
+          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
           else ent_next[u] = da_entry(g, e + u * step);
         }
       }
-      if constexpr (BIAS) {                                      // (this batch's entry indices: formed after the last fold, not yet replaced)
+      if constexpr (EID) {                                       // (this batch's entry indices: formed after the last fold, not yet replaced)
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
       }
-      da_bwd_fold<LPR, VEC, U, BIAS>(g, ln, r, w, ent, bs, dq);
-      if constexpr (BIAS)
-        if (full) { da_eids<U>(g, raw, e, step, eid); da_bias_load<VEC, U>(g, ln, eid, bs); }
+      da_bwd_fold<LPR, VEC, U, BIAS, DROP>(g, ln, r, w, ent, bs, key, dq);
+      if constexpr (EID)
+        if (full) {
+          da_eids<U>(g, raw, e, step, eid);
+          if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
+        }
     }
   }
   for (; e < e1; e += step) {
@@ -478,14 +584,15 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
     }
     DaRows<VEC, 1> w;
     da_gather<VEC, 1>(g, ln, src, w);
-    da_bwd_fold<LPR, VEC, 1, BIAS>(g, ln, r, w, ent, bs, dq);
+    da_bwd_fold<LPR, VEC, 1, BIAS, DROP>(g, ln, r, w, ent, bs, key, dq);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
-template <int LPR, int VEC, bool BIAS>
+template <int LPR, int VEC, bool BIAS, bool DROP = false>
 __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
+  const uint2 key = da_key<DROP>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
@@ -496,7 +603,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
     float4 dq[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS>(g, ln, r, e0 + grp, e1, EPW, dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP>(g, ln, r, e0 + grp, e1, EPW, key, dq);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
@@ -506,7 +613,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC, bool BIAS>
+template <int LPR, int VEC, bool BIAS, bool DROP = false>
 __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -526,7 +633,7 @@ __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   } else if (end > start) {                                    // (a row without entries: its G row is not read)
     DaRow<VEC> r;
     da_bwd_load<LPR, VEC>(g, ln, row, r);
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS>(g, ln, r, start, end, 1, dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP>(g, ln, r, start, end, 1, da_key<DROP>(g), dq);
   }
   da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
 }
@@ -560,13 +667,13 @@ static inline void da_pick(int H, int F, int* lpr, int* vec, int* nch) {
     else { constexpr int LPR = 64, VEC = 4; __VA_ARGS__; }                   \
   } while (0)
 
-template <bool BIAS>
+template <bool BIAS, bool DROP = false>
 static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
   const void* f = nullptr;
-  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS>)
-                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS>))
-                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS>)
-                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS>)));
+  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS, DROP>)
+                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS, DROP>))
+                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, float, DROP>)
+                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, float, DROP>)));
   return f;
 }
 
@@ -580,8 +687,8 @@ static const void* da_bf16_kernel_ptr(bool lng, int lpr, int vec) {
 }
 
 // pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH), and the
-// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>
-static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch) {
+// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>; k19d_ | k19db_ (BIAS): the DROP instantiations of the first two
+static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch, bool drop = false) {
   const void* fn = nullptr;
   char dir[8] = "", kind[8] = "", rest = 0;
   int lpr = 0, vec = 0;
@@ -591,6 +698,9 @@ static int da_footprint(const char* name, const char* prefix, bool bias, bool bf
       (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4))) {
     if (bf16)
       fn = bias ? da_bf16_kernel_ptr<true>(!strcmp(kind, "long"), lpr, vec) : da_bf16_kernel_ptr<false>(!strcmp(kind, "long"), lpr, vec);
+    else if (drop)
+      fn = bias ? da_kernel_ptr<true, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
+                : da_kernel_ptr<false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
     else
       fn = bias ? da_kernel_ptr<true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
                 : da_kernel_ptr<false>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
@@ -605,6 +715,8 @@ int footprint_k19(const char* name, int* regs, int* scratch) { return da_footpri
 int footprint_k19b(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19b_", true, false, regs, scratch); }
 int footprint_k19h(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19h_", false, true, regs, scratch); }
 int footprint_k19hb(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19hb_", true, true, regs, scratch); }
+int footprint_k19d(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19d_", false, false, regs, scratch, true); }
+int footprint_k19db(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19db_", true, false, regs, scratch, true); }
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
 
@@ -680,11 +792,25 @@ static int da_check_bias(const char* what, int64_t nnz, const float* bias, int b
   return PYGAT_OK;
 }
 
-// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z
-template <bool BIAS, typename T = float>
+// the mask of the DROP launchers: the seed, a uint64 in device memory (8-byte loads), and p in [0, 1] (a NaN is outside)
+struct DaDrop {
+  float p;
+  const void* seed;
+  uint32_t stream_id;
+};
+static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
+  PYGAT_REQUIRE(d.seed, "%s: null seed", what);
+  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(d.seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
+  PYGAT_REQUIRE(make_rng(d.p, d.seed, d.stream_id, rng), "%s: p=%g outside [0, 1]", what, (double)d.p);
+  return PYGAT_OK;
+}
+
+// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z.  DROP: drop names the mask
+template <bool BIAS, typename T = float, bool DROP = false>
 static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
                       int F, float scale, const float* q, int64_t ldq, const T* k, int64_t ldk, const T* v, int64_t ldv,
-                      const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+                      const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream,
+                      const DaDrop* drop = nullptr) {
   int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws, (int)sizeof(T),
                            sizeof(T) == sizeof(float));
   if (rc != PYGAT_OK) return rc;
@@ -692,28 +818,34 @@ static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* 
     rc = da_check_bias(what, nnz, bias, bias_head_stride);
     if (rc != PYGAT_OK) return rc;
   }
+  DropRng rng;
+  if constexpr (DROP) {
+    rc = da_check_drop(what, *drop, &rng);
+    if (rc != PYGAT_OK) return rc;
+  }
   if (n_rows == 0) return PYGAT_OK;
   DaArgs g;
   da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v),
           ldv, out, ldo, m, Z, ws);
   if constexpr (BIAS) { g.perm = perm; g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; }
+  if constexpr (DROP) { g.perm = perm; g.rng = rng; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T, DROP>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T, DROP>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
 
-template <bool BIAS>
+template <bool BIAS, bool DROP = false>
 static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
                             int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                             int64_t ldv, const float* bias, int bias_head_stride, const float* out, int64_t ldo, const float* m,
                             const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias,
-                            void* ws, void* stream) {
+                            void* ws, void* stream, const DaDrop* drop = nullptr) {
   int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
   if (rc != PYGAT_OK) return rc;
   DA_TABLE(what, "G", G, ldg, H * F);
@@ -724,19 +856,25 @@ static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int
     rc = da_check_bias(what, nnz, bias, bias_head_stride);
     if (rc != PYGAT_OK) return rc;
   }
+  DropRng rng;
+  if constexpr (DROP) {
+    rc = da_check_drop(what, *drop, &rng);
+    if (rc != PYGAT_OK) return rc;
+  }
   if (n_rows == 0) return PYGAT_OK;
   DaArgs g;
   da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, const_cast<float*>(out), ldo, const_cast<float*>(m),
           const_cast<float*>(Z), ws);
   g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
+  if constexpr (DROP) g.rng = rng;
   if constexpr (BIAS) { g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; g.dbias = dbias; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS, DROP>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS, DROP>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -787,4 +925,37 @@ extern "C" int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const 
                                                       float* S, float* dbias, void* ws, void* stream) {
   return da_backward_rows<true>("dot_attn_bias_backward_rows", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv,
                                 bias, bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream);
+}
+
+// the bias pair with seeded dropout of the coefficients (the DROP instantiations): out = sum_e alpha mask v, mask[c(e), h] element
+// c(e) H + h of the flat layout pygat_dropout_mask(nnz H, p, seed, stream_id) writes, drawn in registers in both passes.  A null bias: no
+// bias, bias_head_stride is then not looked at
+extern "C" int pygat_dot_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                              int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                              const float* v, int64_t ldv, const float* bias, int bias_head_stride, float p,
+                                              const void* seed, uint32_t stream_id, float* out, int64_t ldo, float* m, float* Z,
+                                              void* ws, void* stream) {
+  const char* what = "dot_attn_dropout_forward";
+  const DaDrop drop = {p, seed, stream_id};
+  if (bias)
+    return da_forward<true, float, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
+                                         bias_head_stride, out, ldo, m, Z, ws, stream, &drop);
+  return da_forward<false, float, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out, ldo,
+                                        m, Z, ws, stream, &drop);
+}
+
+extern "C" int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                                                    const int32_t* perm, int H, int F, float scale, const float* q, int64_t ldq,
+                                                    const float* k, int64_t ldk, const float* v, int64_t ldv, const float* bias,
+                                                    int bias_head_stride, float p, const void* seed, uint32_t stream_id,
+                                                    const float* out, int64_t ldo, const float* m, const float* Z, const float* G,
+                                                    int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias, void* ws,
+                                                    void* stream) {
+  const char* what = "dot_attn_dropout_backward_rows";
+  const DaDrop drop = {p, seed, stream_id};
+  if (bias)
+    return da_backward_rows<true, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
+                                        bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream, &drop);
+  return da_backward_rows<false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out, ldo,
+                                       m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream, &drop);
 }

@@ -11,6 +11,8 @@ its score as an op of its own.
     out = dot_attention(pattern, q, k, v, bias=emb(edge_type))    # a per-entry term on the score, [E, H] or [E]; differentiable too
     with torch.no_grad():                                         # inference: bf16 tables, made once -- half the gathered bytes, the
         out = dot_attention(pattern, q, k16, v16)                 # bits of dot_attention(pattern, q, k16.float(), v16.float())
+    out = dot_attention_dropout(pattern, q, k, v, p, bias=b, training=self.training)    # training: dropout p on the coefficients, after
+                                                                  # the softmax, drawn in the kernels from a seed on the device
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the
 pattern rectangular.  To attend over columns instead of rows, build the pattern from swapped indices.  Both ops are differentiable
@@ -30,6 +32,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
+from .dropout import STREAM_ATT
 from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
 
 MIN_F, MAX_F = 4, 256      # a head's width in dot_attention: a power of two in this range (csrc/k19_dot_attention.hip)
@@ -123,31 +126,31 @@ def edge_dot(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, scale: floa
 
 
 # ------------------------------------------------------------------------------------------------------------------- dot_attention
-def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False):
-    H, F, flat = _tables("dot_attention", pattern, q, (("k", k), ("v", v)), bf16_tables)
+def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False, op: str = "dot_attention"):
+    H, F, flat = _tables(op, pattern, q, (("k", k), ("v", v)), bf16_tables)
     if not (1 <= H <= MAX_HEADS):
-        raise ValueError(f"pygat_amd dot_attention: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
+        raise ValueError(f"pygat_amd {op}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
     if not (MIN_F <= F <= MAX_F) or F & (F - 1):
-        raise ValueError(f"pygat_amd dot_attention: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
+        raise ValueError(f"pygat_amd {op}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
     if H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd dot_attention: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
+        raise ValueError(f"pygat_amd {op}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
                          f"{_PAD_HINT}")
     return H, F, flat
 
 
-def _bias_tensor(pattern, bias):
+def _bias_tensor(pattern, bias, op: str = "dot_attention"):
     """The refusals of `bias` that do not depend on q, k and v."""
     if not isinstance(pattern, EdgePattern):
-        raise ValueError("pygat_amd dot_attention: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
     if not isinstance(bias, torch.Tensor) or not bias.is_cuda:
-        raise ValueError("pygat_amd dot_attention: bias must be a tensor on the GPU (there is no CPU path)")
+        raise ValueError(f"pygat_amd {op}: bias must be a tensor on the GPU (there is no CPU path)")
     if bias.dtype != torch.float32:
-        raise ValueError(f"pygat_amd dot_attention: bias must be float32, not {bias.dtype}")
+        raise ValueError(f"pygat_amd {op}: bias must be float32, not {bias.dtype}")
     if bias.device != pattern.device:
-        raise ValueError(f"pygat_amd dot_attention: bias lives on {bias.device}, the pattern on {pattern.device}")
+        raise ValueError(f"pygat_amd {op}: bias lives on {bias.device}, the pattern on {pattern.device}")
 
 
-def _bias_head_stride(pattern, bias, H: int, flat: bool) -> int:
+def _bias_head_stride(pattern, bias, H: int, flat: bool, op: str = "dot_attention") -> int:
     """1: one value per entry and head ([E, H]; [E] where q, k and v have no head axis); 0: one per entry, shared by the heads."""
     E = pattern.nnz
     if tuple(bias.shape) == (E,):
@@ -155,7 +158,15 @@ def _bias_head_stride(pattern, bias, H: int, flat: bool) -> int:
     if not flat and tuple(bias.shape) == (E, H):
         return 1
     want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
-    raise ValueError(f"pygat_amd dot_attention: bias {want} expected for E = {E} entries and H = {H} heads, got {tuple(bias.shape)}")
+    raise ValueError(f"pygat_amd {op}: bias {want} expected for E = {E} entries and H = {H} heads, got {tuple(bias.shape)}")
+
+
+def _checked(op: str, pattern, q, k, v, bias):
+    """Every refusal of the float32 op that looks at the pattern and the tensors -> (H, F, no head axis, the bias's head stride | None)."""
+    if bias is not None:
+        _bias_tensor(pattern, bias, op)
+    H, F, flat = _attention_shapes(pattern, q, k, v, op=op)
+    return H, F, flat, None if bias is None else _bias_head_stride(pattern, bias, H, flat, op)
 
 
 def _workspace(nnz: int, H: int, F: int, device) -> torch.Tensor:
@@ -163,20 +174,31 @@ def _workspace(nnz: int, H: int, F: int, device) -> torch.Tensor:
 
 
 class _DotAttentionFn(torch.autograd.Function):
+    """drop: None (dot_attention) or (p, seed) (dot_attention_dropout: the mask of the coefficients, drawn in the kernels of both
+    passes from the int64 [1] seed tensor on the device)."""
+
     @staticmethod
-    def forward(ctx, pattern, q, k, v, scale, bias):
-        if bias is not None:
-            _bias_tensor(pattern, bias)
-        H, F, flat = _attention_shapes(pattern, q, k, v)
-        bhs = None if bias is None else _bias_head_stride(pattern, bias, H, flat)
+    def forward(ctx, pattern, q, k, v, scale, bias, drop):
+        op = "dot_attention" if drop is None else "dot_attention_dropout"
+        H, F, flat, bhs = _checked(op, pattern, q, k, v, bias)
         scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
         qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
         n, HF = pattern.n_rows, H * F
+        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs, ctx.op, ctx.p = pattern, scale, (H, F), bhs, op, None if drop is None else drop[0]
+        if drop is not None and pattern.nnz == 0:                  # every row is without entries: zeros, and nothing is launched
+            ctx.save_for_backward(q, k, v, None, None, None, bias, None)
+            return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
         with torch.cuda.device(qc.device):
             out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
             m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
             ws = _workspace(pattern.nnz, H, F, qc.device)
-            if bias is None:
+            if drop is not None:
+                bc = None if bias is None else bias.detach().contiguous()
+                check(lib.pygat_dot_attn_dropout_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H,
+                                                         F, scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs or 0, drop[0],
+                                                         _ptr(drop[1]), STREAM_ATT, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws),
+                                                         _stream()), "dot_attn_dropout_forward")
+            elif bias is None:
                 check(lib.pygat_dot_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, scale, _ptr(qc), HF,
                                                  _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
                       "dot_attn_forward")
@@ -186,22 +208,24 @@ class _DotAttentionFn(torch.autograd.Function):
                                                       scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out), HF,
                                                       _ptr(m), _ptr(Z), _ptr(ws), _stream()), "dot_attn_bias_forward")
         out = out.view(q.shape)
-        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs = pattern, scale, (H, F), bhs
-        ctx.save_for_backward(q, k, v, out, m, Z, bias)
+        ctx.save_for_backward(q, k, v, out, m, Z, bias, None if drop is None else drop[1])
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        q, k, v, out, m, Z, bias = ctx.saved_tensors
+        q, k, v, out, m, Z, bias, seed = ctx.saved_tensors
         pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
         if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd dot_attention: the gradient of the output must be float32, not {G.dtype}")
+            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_q, need_k, need_v = ctx.needs_input_grad[1:4]
         need_b = bias is not None and ctx.needs_input_grad[5]
         if not (need_q or need_k or need_v or need_b):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
+        if out is None:                                            # dot_attention_dropout without entries: zeros, nothing launched
+            return (None,) + tuple(torch.zeros_like(t) if need else None for t, need in
+                                   ((q, need_q), (k, need_k), (v, need_v))) + (None, torch.zeros_like(bias) if need_b else None, None)
         qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
         Gc = G.contiguous().view(n, HF)
         db = None
@@ -209,7 +233,15 @@ class _DotAttentionFn(torch.autograd.Function):
             dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
             ws = _workspace(nnz, H, F, qc.device)
-            if bias is None:
+            if seed is not None:
+                bc = None if bias is None else bias.detach().contiguous()
+                db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
+                check(lib.pygat_dot_attn_dropout_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
+                                                               scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs or 0,
+                                                               ctx.p, _ptr(seed), STREAM_ATT, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc),
+                                                               HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(db), _ptr(ws), _stream()),
+                      "dot_attn_dropout_backward_rows")
+            elif bias is None:
                 check(lib.pygat_dot_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
                                                        _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
                                                        _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
@@ -221,8 +253,8 @@ class _DotAttentionFn(torch.autograd.Function):
                                                             scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out),
                                                             HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S),
                                                             _ptr(db), _ptr(ws), _stream()), "dot_attn_bias_backward_rows")
-                if need_b:                      # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
-                    db = db.sum(1) if bhs == 0 else db.view(bias.shape)
+            if need_b:                          # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
+                db = db.sum(1) if bhs == 0 else db.view(bias.shape)
         dk = dv = None
         if need_k or need_v:
             rowptr_t, row_t, perm_t = pattern.transposed()
@@ -230,7 +262,7 @@ class _DotAttentionFn(torch.autograd.Function):
                 dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
             if need_v:
                 dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
-        return None, dq.view(q.shape) if need_q else None, dk, dv, None, db
+        return None, dq.view(q.shape) if need_q else None, dk, dv, None, db, None
 
 
 def _bf16_tables(k, v) -> bool:
@@ -284,4 +316,64 @@ def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: tor
     mode on and a tensor that requires grad it raises; call it under torch.no_grad(), or pass float32 tables."""
     if _bf16_tables(k, v):
         return _dot_attention_bf16(pattern, q, k, v, scale, bias)
-    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias)
+    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias, None)
+
+
+# ----------------------------------------------------------------------------------------------------------- dot_attention_dropout
+def _drop_p(op: str, p) -> float:
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:          # (a NaN is outside)
+        raise ValueError(f"pygat_amd {op}: p = {p!r}: a dropout probability in [0, 1] expected")
+    return float(p)
+
+
+def _drop_seed(op: str, pattern, seed):
+    if not isinstance(pattern, EdgePattern):
+        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or tuple(seed.shape) != (1,) or seed.device != pattern.device:
+        got = f"{seed.dtype} {tuple(seed.shape)} on {seed.device}" if isinstance(seed, torch.Tensor) else type(seed).__name__
+        raise ValueError(f"pygat_amd {op}: seed must be an int64 tensor of shape [1] on the pattern's device {pattern.device} (the "
+                         f"kernels read it there, so a captured graph replays with the value it finds), got {got}")
+    return seed.contiguous()
+
+
+def attention_dropout_mask(pattern: EdgePattern, H: int, p: float, seed: torch.Tensor) -> torch.Tensor:
+    """The mask dot_attention_dropout(pattern, ..., p, seed=seed) draws in its kernels, as a tensor: [E, H] float32, 0 or 1 / (1 - p),
+    row e the caller's entry e -- one pygat_dropout_mask launch over E * H elements (stream STREAM_ATT of the seed).  For tests and for
+    composing the op from parts: spmm(pattern, edge_softmax(pattern, scores) * attention_dropout_mask(pattern, H, p, seed), v)."""
+    op = "attention_dropout_mask"
+    p, seed = _drop_p(op, p), _drop_seed(op, pattern, seed)
+    if isinstance(H, bool) or not isinstance(H, int) or not 1 <= H <= MAX_HEADS:
+        raise ValueError(f"pygat_amd {op}: H = {H!r} heads: the limits are 1 <= H <= {MAX_HEADS}")
+    mask = torch.empty(pattern.nnz, H, dtype=torch.float32, device=pattern.device)
+    if pattern.nnz:
+        with torch.cuda.device(pattern.device):
+            check(lib.pygat_dropout_mask(pattern.nnz * H, p, _ptr(seed), STREAM_ATT, _ptr(mask), _stream()), "dropout_mask")
+    return mask
+
+
+def dot_attention_dropout(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: float,
+                          scale: Optional[float] = None, bias: Optional[torch.Tensor] = None, *, seed: Optional[torch.Tensor] = None,
+                          generator=None, training: bool = True) -> torch.Tensor:
+    """dot_attention with dropout p on the attention coefficients, as a graph-transformer layer trains (F.dropout on alpha):
+    out[i] = sum over the entries e = (i, j) of row i of  softmax_row(scale * <q[i], k[j]> + bias)[e] * mask[e] * v[j], per head, mask
+    in {0, 1 / (1 - p)}.  The softmax runs over all entries of the row -- a dropped entry keeps its share of the denominator -- so this
+    is dropout after the softmax, not masking before it.  Fused on the DROP instantiations of the K19 kernels: the decision for (entry,
+    head) is drawn in registers (Philox-4x32-10) in the forward and again in the backward, and no [E, H] tensor exists outside backward.
+    seed: an int64 [1] tensor on the pattern's device, read by the kernels (refill it in place between replays of a captured graph);
+    None draws one with torch.randint(0, 2**62, ..., generator=generator).  The mask is attention_dropout_mask(pattern, H, p, seed), at
+    the caller's entry index; the same seed gives the same bits.  training=False or p == 0 is dot_attention itself; p == 1 gives zeros.
+    Differentiable in q, k, v and bias.  float32 GPU tensors with dot_attention's limits; bfloat16 tables are refused (they are for
+    inference)."""
+    op = "dot_attention_dropout"
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (k, v)):
+        raise ValueError(f"pygat_amd {op}: k and v must be float32: there is no training path on bfloat16 tables (they are for "
+                         f"dot_attention's inference forward)")
+    p = _drop_p(op, p)
+    if seed is not None:
+        seed = _drop_seed(op, pattern, seed)
+    _checked(op, pattern, q, k, v, bias)                           # (refusals under this op's name, before anything touches the device)
+    if not training or p == 0.0:
+        return dot_attention(pattern, q, k, v, scale, bias)
+    if seed is None:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
+    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias, (p, seed))

@@ -7,6 +7,7 @@ at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone 
     rocprofv3 --kernel-trace --stats -d DIR -o da -- python tools/dot_attention_bench.py --child --forward-only --shapes 8x64 --out DIR/run.jsonl
     python tools/dot_attention_bench.py --bias [...]       # the per-entry bias: three contenders -> profiles/dot_attention_bias_bench.jsonl
     python tools/dot_attention_bench.py --kv-bf16 [...]    # bf16 k and v tables: fp32 against bf16 forward -> profiles/dot_attention_bf16_bench.jsonl
+    python tools/dot_attention_bench.py --dropout [...]    # seeded attention dropout: three contenders -> profiles/dot_attention_dropout_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
@@ -29,7 +30,14 @@ permutation; the bench's pattern carries none) beside the measured increment.
 forward on float32 tables with the fused forward on bfloat16 tables.  Both are fed the same values -- N(0, 1) draws rounded to
 bfloat16, and those widened to float32 -- so the two outputs are compared with torch.equal here; the bfloat16 one is priced on the
 sampled rows as above.  Recorded per shape: both medians with their spreads, their ratio, and the byte model's ratio beside it
-((4 R + 4) / (8 R + 4) per entry, and with the per-row traffic) -> profiles/dot_attention_bf16_bench.jsonl."""
+((4 R + 4) / (8 R + 4) per entry, and with the per-row traffic) -> profiles/dot_attention_bf16_bench.jsonl.
+
+--dropout measures dot_attention_dropout at p = 0.5: in the one child process it alternates the fused op with dropout, the fused op
+without it (dot_attention), and the composition spmm(edge_softmax(edge_dot(q, k)) * attention_dropout_mask(pattern, H, p, seed), v)
+with the same seed, which writes and reads the mask as a [E, H] tensor.  The first and the last are priced on the sampled rows against
+the fp64 computation under the mask attention_dropout_mask writes (that it is the mask of tests/philox_ref.py is the tests' business).
+The fused op's bytes are those without dropout -- the decisions are drawn in registers -- so what the measured increment over the
+fused op without dropout shows is arithmetic: ten Philox rounds per (entry, head chunk) and lane."""
 import argparse
 import json
 import math
@@ -126,9 +134,9 @@ def alternate(contenders, rounds, steps, warmup):
     return out
 
 
-def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None):
+def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None, mask=None):
     """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j (+ bias [E, H], at the
-    CSR position), times v_j."""
+    CSR position), times mask [E, H] (pre-scaled, after the softmax) where given, times v_j."""
     import torch
     deg = rp[rows + 1] - rp[rows]
     idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
@@ -141,6 +149,8 @@ def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None):
     m = torch.full(qs.shape[:2], -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
     p = torch.exp(s - m[sub])
     alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
+    if mask is not None:
+        alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
     return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vs[inv])
 
 
@@ -261,6 +271,75 @@ def measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, de
         torch.cuda.empty_cache()
 
 
+def measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
+    """--dropout: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object per shape."""
+    p = 0.5
+    seed = torch.tensor([20240607], dtype=torch.int64, device=dev)
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        scale = 1.0 / math.sqrt(F)
+        g = torch.Generator(device=dev).manual_seed(2)
+        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
+        qs = q * scale
+
+        def fused_dropout(q_, k_, v_):
+            return pg.dot_attention_dropout(pattern, q_, k_, v_, p, scale, seed=seed)
+
+        def composed_dropout(qs_, k_, v_):
+            alpha = pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_))
+            return pg.spmm(pattern, alpha * pg.attention_dropout_mask(pattern, H, p, seed), v_)
+
+        def fused(q_, k_, v_):
+            return pg.dot_attention(pattern, q_, k_, v_, scale)
+
+        def forward_of(fn, leaves):
+            def run():
+                with torch.no_grad():
+                    return fn(*leaves)
+            return run
+
+        def both_of(fn, leaves):
+            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
+
+            def run():
+                return torch.autograd.grad(fn(*leaves), leaves, G)
+            return run
+
+        out_f, out_c = forward_of(fused_dropout, (q, k, v))(), forward_of(composed_dropout, (qs, k, v))()
+        mask = pg.attention_dropout_mask(pattern, H, p, seed)
+        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, mask=mask)
+        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, mask=mask)
+        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, dropout: out", ref32)
+        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, dropout: out", ref32)
+        res = {"bench": "dot_attention --dropout", "device": torch.cuda.get_device_name(0), "p": p,
+               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
+               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+               "longest_checked_row": int(deg[rows].max()), "kept_fraction": float((mask != 0).float().mean()),
+               "out_err_fused_dropout": err_f, "out_err_composed_dropout": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
+               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F),
+               "mask_tensor_bytes": E * H * 4}
+        del out_f, out_c, mask
+        legs = [("forward", alternate({"fused_dropout": forward_of(fused_dropout, (q, k, v)),
+                                       "composed_dropout": forward_of(composed_dropout, (qs, k, v)),
+                                       "fused": forward_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup))]
+        if not args.forward_only:
+            legs.append(("forward_backward", alternate({"fused_dropout": both_of(fused_dropout, (q, k, v)),
+                                                        "composed_dropout": both_of(composed_dropout, (qs, k, v)),
+                                                        "fused": both_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup)))
+        for what, r in legs:
+            for name in ("fused_dropout", "composed_dropout", "fused"):
+                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+            res[f"{what}_speedup"] = res[f"composed_dropout_{what}_ms"] / res[f"fused_dropout_{what}_ms"]
+            res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+        with open(args.out, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+        print(f"{shape}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged bytes; "
+              f"the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
+        del q, k, v, G, qs
+        torch.cuda.empty_cache()
+
+
 def measure(args):
     import torch
     if not torch.cuda.is_available():
@@ -284,6 +363,8 @@ def measure(args):
         return measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     if args.kv_bf16:
         return measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
+    if args.dropout:
+        return measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     for shape in args.shapes.split(","):
         H, F = (int(x) for x in shape.split("x"))
         scale = 1.0 / math.sqrt(F)
@@ -354,14 +435,17 @@ def main():
     ap.add_argument("--bias", action="store_true", help="measure the per-entry bias: fused with a bias, the composition with it, fused without")
     ap.add_argument("--kv-bf16", action="store_true", help="measure bfloat16 k and v tables: the fused forward on float32 tables "
                     "against the fused forward on bfloat16 tables (forward only)")
+    ap.add_argument("--dropout", action="store_true", help="measure seeded attention dropout at p = 0.5: fused with dropout, fused "
+                    "without, the composition with the mask as a tensor")
     ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl; profiles/dot_attention_bias_bench.jsonl with --bias, "
-                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16")
+                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16, profiles/dot_attention_dropout_bench.jsonl with --dropout")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.bias and args.kv_bf16:
-        ap.error("--bias and --kv-bf16 are separate measurements")
+    if args.bias + args.kv_bf16 + args.dropout > 1:
+        ap.error("--bias, --kv-bf16 and --dropout are separate measurements")
     if args.out is None:
-        name = "dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bf16_bench.jsonl" if args.kv_bf16 else "dot_attention_bench.jsonl"
+        name = ("dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bf16_bench.jsonl" if args.kv_bf16 else
+                "dot_attention_dropout_bench.jsonl" if args.dropout else "dot_attention_bench.jsonl")
         args.out = os.path.join(ROOT, "profiles", name)
     if args.child:
         return measure(args)
