@@ -70,7 +70,7 @@ int pygat_device_name(char* host_buf, int len);
 /* Registers per lane and scratch bytes per lane of a tuned kernel as the LOADED code object reports them (hipFuncGetAttributes):
  * "k2_headline" (fused forward, 8 heads x 16, training), "k4_headline_da" (column pass with the a-gradient sums), "tn_x3w"
  * (streamed-K weight gradient), "x3gw" (general split-bf16 GEMM), "k1_x3_tail" (the headline projection with the
- * self-loop-only tail's output folded in, ABI 15).  The attention kernels were tuned at four waves per SIMD
+ * self-loop-only tail's output folded in, ABI 15), "tn_x3w_tail" (the weight gradient that forms the tail's dWh rows).  The attention kernels were tuned at four waves per SIMD
  * without scratch; `amdgpu_waves_per_eu` makes the compiler spill rather than fail, so tests/test_gpu_properties.py asks. */
 int pygat_kernel_footprint(const char* kernel, int* num_regs, int* scratch_bytes);
 
@@ -420,6 +420,19 @@ int pygat_wgrad(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, cons
 int pygat_wgrad_blocked(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, const pygat_col_blocks* x_blk,
                         const float* dWh, const float* ds, const float* a_pad, float* dW, int split_k, void* ws,
                         int h_first, int h_count, int gemm_mode, void* stream);
+
+/* The weight gradient of a level whose self-loop-only tail [row_first, n) has NO dWh rows (additive under ABI 16): the streamed-K
+ * split kernel reads dWh for the rows before row_first and forms the tail's rows itself, dWh_k = G_u ELU'(y_u) with u =
+ * user_row[k] (NULL: k) -- pygat_gat_backward_tail's value, by the same single multiply; flags: PYGAT_F_ELU or 0 -- so the tail's
+ * rows of dWh are neither written nor read (they may hold anything).  Same slabs, products and reduce as pygat_wgrad_blocked:
+ * dW has the bits of pygat_gat_backward_tail + pygat_wgrad_blocked.  Workspace and split_k as there (no ds, all heads).
+ * Returns 0 when it ran, 1 when NOT TAKEN -- nothing was launched, the caller runs that pair instead: whenever
+ * pygat_wgrad_blocked would not run the streamed-K split kernel with its dW-writing reduce (fp32-mfma mode, a column-blocked X,
+ * split_k <= 1, n < 4096, Fin or H F' <= 64 or not multiples of 4, operands or rows not 16-byte aligned), F' != Fp,
+ * PYGAT_F_SKIP in flags, or a slab of more rows than the kernel's row-id table holds (about 16 000).  Negative: an error. */
+int pygat_wgrad_tail_blocked(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, const pygat_col_blocks* x_blk,
+                             const float* dWh, float* dW, int split_k, void* ws, int row_first, int flags, const float* G,
+                             const float* y, const int32_t* user_row, int gemm_mode, void* stream);
 
 /* Self-loop-only nodes (ABI 14; csrc/k12_tail.hip).  A node whose only neighbour is itself has alpha_ii = 1: its forward is
  * h'_i = ELU(Wh_i (+ skip_i)), its backward dWh_i = Gp_i, ds_i = dt_i = 0 (layers.py:146-170 / 81-90 with one edge).  In a

@@ -34,7 +34,7 @@ SYMBOLS = [
     "pygat_abi_version", "pygat_last_error", "pygat_padded_width", "pygat_device_count",
     "pygat_device_name", "pygat_kernel_footprint", "pygat_default_gemm_mode", "pygat_dense_row_counts", "pygat_scan_workspace_bytes",
     "pygat_exclusive_scan_i32", "pygat_dense_fill_cols", "pygat_csr_symmetric_perm",
-    "pygat_gemm_workspace_bytes", "pygat_gemm_f32", "pygat_gemm_f32_blocked", "pygat_project_blocked", "pygat_wgrad_blocked", "pygat_pack_params", "pygat_pack_params_heads", "pygat_stack_heads", "pygat_stack_heads_padded", "pygat_project", "pygat_attn_scores",
+    "pygat_gemm_workspace_bytes", "pygat_gemm_f32", "pygat_gemm_f32_blocked", "pygat_project_blocked", "pygat_wgrad_blocked", "pygat_wgrad_tail_blocked", "pygat_pack_params", "pygat_pack_params_heads", "pygat_stack_heads", "pygat_stack_heads_padded", "pygat_project", "pygat_attn_scores",
     "pygat_unpack_wgrad",
     "pygat_edge_pairs", "pygat_slot_bounds", "pygat_slot_meta", "pygat_partials_bytes", "pygat_head_group", "pygat_gat_forward", "pygat_gat_forward_phases_ok", "pygat_gat_forward_tail", "pygat_gat_backward_col_tail", "pygat_gat_backward_tail", "pygat_project_tail_blocked", "pygat_head_mean",
     "pygat_gat_backward_prepare", "pygat_gat_backward_row", "pygat_gat_backward_col", "pygat_gat_backward_rowsum",
@@ -112,6 +112,7 @@ def _load():
     lib.pygat_gemm_f32_blocked.argtypes = [i, i, i, i, i64, p, i64, CB, p, i64, C.POINTER(OutSegments), CB, i, i, p, i, p]
     lib.pygat_project_blocked.argtypes = [i, i, i, i, p, i64, CB, p, i64, p, p, p, p, i, p, i, p]
     lib.pygat_wgrad_blocked.argtypes = [i, i, i, i, p, i64, CB, p, p, p, p, i, p, i, i, i, p]
+    lib.pygat_wgrad_tail_blocked.argtypes = [i, i, i, i, p, i64, CB, p, p, i, p, i, i, p, p, p, i, p]
     lib.pygat_pack_params.argtypes = [i, i, i, p, p, p, p, i64, p, p]
     lib.pygat_pack_params_heads.argtypes = [i, i, i, p, p, p, p, i64, p, p]
     lib.pygat_stack_heads.argtypes = [i, i64, i, i64, p, p, p, p, p, p, p]

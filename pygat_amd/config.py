@@ -47,6 +47,7 @@ class Config:
     renumber: bool                        # PYGAT_RENUMBER=0         large first levels in the caller's node order (no internal degree order)
     tail: bool                            # PYGAT_TAIL=0             self-loop-only nodes through the fused kernels like every other row
     tail_fused: bool                      # PYGAT_TAIL_FUSED=0       that tail through its own streams instead of the projection / dW GEMMs
+    tail_wgrad_min_bytes: int             # PYGAT_TAIL_WGRAD_MIN_BYTES  table size from which the dW GEMM forms the tail's dWh rows itself
 
     @staticmethod
     def from_env() -> "Config":
@@ -67,6 +68,7 @@ class Config:
             renumber=_flag("PYGAT_RENUMBER", True),
             tail=_flag("PYGAT_TAIL", True),
             tail_fused=_flag("PYGAT_TAIL_FUSED", True),
+            tail_wgrad_min_bytes=int(os.environ.get("PYGAT_TAIL_WGRAD_MIN_BYTES", 32 << 20)),
         )
 
     def describe(self) -> dict:

@@ -48,6 +48,7 @@ extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* sc
   if (!strcmp(kernel, "tn_x3w")) return pygat::footprint_gemm_x3(0, num_regs, scratch_bytes);
   if (!strcmp(kernel, "x3gw")) return pygat::footprint_gemm_x3(1, num_regs, scratch_bytes);
   if (!strcmp(kernel, "k1_x3_tail")) return pygat::footprint_gemm_x3(2, num_regs, scratch_bytes);
+  if (!strcmp(kernel, "tn_x3w_tail")) return pygat::footprint_gemm_x3(3, num_regs, scratch_bytes);
   static const char* const k14[] = {"k14_rows_long", "k14_cols_long", "k14_rows_wave", "k14_cols_wave", "k14_apply"};
   for (int w = 0; w < 5; ++w)
     if (!strcmp(kernel, k14[w])) return pygat::footprint_k14(w, num_regs, scratch_bytes);

@@ -798,8 +798,45 @@ __device__ __forceinline__ f32x4 mfma16_bf16(const TA_& a, const TB_& b, f32x4 c
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_tw[];   // [2 * TNW_STAGE]: 96 KB, one work-group per CU
+// TL (pygat_wgrad_tail_blocked): the B rows k >= row_first -- the self-loop-only tail of a degree-ordered level -- are FORMED here,
+// dWh_k = G_u ELU'(y_u) with u = urow[k] (NULL: k), by the one multiply of bwd_tail_item (tail_stream.h): the tail's dWh rows are
+// neither written by a stream nor read back.  Rows k < row_first read B = dWh[k] as ever.
+//   * the row ids of the work-group's slab go into LDS once, behind the two stages (u for a tail row, -1 for a row before the
+//     tail; clamped like the loads: 4 (k_per_split + 128) bytes), and the loader takes them with a ds_read one step ahead of the
+//     loads that use them -- a global load of urow inside the ring would sit in the same in-order vmcnt queue as the three-deep
+//     prefetch, and the wave would drain the ring to form its next addresses;
+//   * every row loads (value, factor source) through two SELECTED pointers -- a tail row (G[u], y[u]), a row before it
+//     (dWh[k], a row of 1.0f: factor 1, g * 1 = g bitwise) -- so the loop has no branch (the joins of one would cost the
+//     prefetch: see above), the ring stays three steps deep, and the slab that straddles row_first needs nothing of its own;
+//   * slabs, zeroed steps, the nine products and their order are untouched: dW has the bits of stream + plain kernel.
+struct TnTailArgs {
+  TnArgs t;             // (t.B = dWh: read for the rows before row_first only)
+  int64_t row_first;
+  const float* G;       // [. x N] caller-order rows, row stride ldg; y the same
+  const float* y;
+  int64_t ldg;
+  const int32_t* urow;  // table row -> caller row, or nullptr
+  int elu;
+};
+struct TnOnes {
+  float v[128];
+  constexpr TnOnes() : v{} { for (int i = 0; i < 128; ++i) v[i] = 1.f; }
+};
+__device__ const TnOnes tnw_ones{};   // the factor source of a row before the tail (one column tile wide)
+__device__ __forceinline__ const TnArgs& tn_args_of(const TnArgs& a) { return a; }
+__device__ __forceinline__ const TnArgs& tn_args_of(const TnTailArgs& a) { return a.t; }
+
+// a * b rounded to fp32, whatever consumes it (the empty asm hides the product from the contraction into an FMA)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+template <bool TL>
+__global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(std::conditional_t<TL, TnTailArgs, TnArgs> ga) {
+  const TnArgs& g = tn_args_of(ga);
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_tw[];   // [2 * TNW_STAGE]: 96 KB, one work-group per CU (TL: + the row ids)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fi = lane & 15, fq = lane >> 4;
   const int m0 = blockIdx.y * 128, n0 = blockIdx.z * 128;
@@ -813,14 +850,60 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
   // image position of this thread's k pair in column 4 c4 + COL: slice pr >> 2 rotated by (column >> 1) & 3, dword pr & 3
   uint32_t* const wbase = lds_tw + (4 * c4) * TNW_RS + (pr & 3);
   const int wq = pr >> 2, wrot = 2 * (c4 & 1);      // ((4 c4 + COL) >> 1) & 3 = (2 (c4 & 1) + (COL >> 1)) & 3
+  // TL: the ids of the step about to be loaded (read from LDS one step earlier) and the tables of the tail rows, as byte
+  // addresses: a row's two addresses are base + row * stride with base, row and stride SELECTED (cheap operands: hipcc turns a
+  // select between two address computations into a branch, and a select between a kernel argument and the row of ones into
+  // a flat load) and the loads go through the global address space explicitly
+  int id0 = 0, id1 = 0;
+  const int* ids = reinterpret_cast<const int*>(lds_tw + 2 * TNW_STAGE) + 2 * pr;
+  uint64_t ag = 0, ay = 0, ab = 0, aone = 0;
+  uint32_t sg = 0, sb = 0;
+  bool no_elu = true;
+  (void)id0; (void)id1; (void)ids; (void)ag; (void)ay; (void)ab; (void)aone; (void)sg; (void)sb; (void)no_elu;
+  typedef const __attribute__((address_space(1))) f32x4* gptr4;   // (a native vector: float4 is a class, and has no copy from address space 1)
+  if constexpr (TL) {
+    const int cg = (n0 + 4 * c4 + 3 < g.N) ? n0 + 4 * c4 : 0;
+    ag = (uint64_t)(uintptr_t)(ga.G + cg); ay = (uint64_t)(uintptr_t)(ga.y + cg); ab = (uint64_t)(uintptr_t)lb;
+    aone = (uint64_t)(uintptr_t)(tnw_ones.v + 4 * c4);
+    sg = (uint32_t)ga.ldg * 4u; sb = (uint32_t)g.ldb * 4u; no_elu = !ga.elu;
+    int* idw = reinterpret_cast<int*>(lds_tw + 2 * TNW_STAGE);
+    const int nid = (int)g.k_per_split + 128;
+    for (int j = tid; j < nid; j += 512) {
+      const int64_t k = kbeg + j < kend ? kbeg + j : kend - 1;
+      idw[j] = k >= ga.row_first ? (ga.urow ? ga.urow[k] : (int)k) : -1;
+    }
+    __syncthreads();
+    const int2 v__ = *reinterpret_cast<const int2*>(ids);
+    id0 = v__.x; id1 = v__.y;
+  }
+#define PYGAT_TWL_ROW(ID, KROW, DSTB, DSTY)                                                   \
+  {                                                                                           \
+    const bool t__ = (ID) >= 0;                                                               \
+    const uint32_t r__ = t__ ? (uint32_t)(ID) : (uint32_t)(KROW);                             \
+    const uint64_t pb__ = (t__ ? ag : ab) + (uint64_t)r__ * (t__ ? sg : sb);                  \
+    const uint64_t py__ = (t__ ? ay : aone) + (uint64_t)r__ * (t__ ? sg : 0u);                \
+    const f32x4 vb__ = *reinterpret_cast<gptr4>(pb__), vy__ = *reinterpret_cast<gptr4>(py__);   \
+    DSTB = make_float4(vb__[0], vb__[1], vb__[2], vb__[3]); DSTY = make_float4(vy__[0], vy__[1], vy__[2], vy__[3]);   \
+  }
 #define PYGAT_TWL_LOAD(R, STEP)                                                               \
   {                                                                                           \
     const int64_t k__ = kbeg + 32 * (int64_t)(STEP) + 2 * pr;   /* (steps past the slab: row kend - 1, zeroed) */ \
     const int64_t k0__ = k__ < kend ? k__ : kend - 1, k1__ = k__ + 1 < kend ? k__ + 1 : kend - 1;   \
     R##a0 = ld4(la + k0__ * g.lda); R##a1 = ld4(la + k1__ * g.lda);                           \
-    R##b0 = ld4(lb + k0__ * g.ldb); R##b1 = ld4(lb + k1__ * g.ldb);                           \
+    if constexpr (TL) {                                                                       \
+      PYGAT_TWL_ROW(id0, k0__, R##b0, R##y0)                                                  \
+      PYGAT_TWL_ROW(id1, k1__, R##b1, R##y1)                                                  \
+      const int2 v__ = *reinterpret_cast<const int2*>(ids + 32 * ((STEP) + 1));               \
+      id0 = v__.x; id1 = v__.y;                                                               \
+    } else {                                                                                  \
+      R##b0 = ld4(lb + k0__ * g.ldb); R##b1 = ld4(lb + k1__ * g.ldb);                         \
+    }                                                                                         \
     R##z0 = k__ < kend ? 1.f : 0.f; R##z1 = k__ + 1 < kend ? 1.f : 0.f;                       \
   }
+  // TL: the factor ELU'(y) = (y > 0 ? 1 : y + 1) of bwd_tail_item, 1 without PYGAT_F_ELU (and from the row of ones).  The
+  // product goes through mul_rounded: left to contraction, hipcc fuses it into the split's first subtraction (fma(g, f, -hi)),
+  // and the pieces then add up to the EXACT product instead of the rounded one the stream stores -- dW a few ulps off it.
+#define PYGAT_TWL_FAC(Y) (((Y) > 0.f || no_elu) ? 1.f : (Y) + 1.f)
 #define PYGAT_TWL_PUT(IMGBASE, X0, X1, COL)                                                   \
   {                                                                                           \
     uint32_t h__, m__, l__;                                                                   \
@@ -831,7 +914,8 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
 #define PYGAT_TWL_PUTA(R, STAGE, C, CMP)                                                       \
   PYGAT_TWL_PUT(lds_tw + (STAGE) * TNW_STAGE, R##a0.CMP * R##z0, R##a1.CMP * R##z1, C)
 #define PYGAT_TWL_PUTB(R, STAGE, C, CMP)                                                       \
-  PYGAT_TWL_PUT(lds_tw + (STAGE) * TNW_STAGE + 3 * TNW_IMG, R##b0.CMP, R##b1.CMP, C)
+  if constexpr (TL) PYGAT_TWL_PUT(lds_tw + (STAGE) * TNW_STAGE + 3 * TNW_IMG, mul_rounded(R##b0.CMP, PYGAT_TWL_FAC(R##y0.CMP)), mul_rounded(R##b1.CMP, PYGAT_TWL_FAC(R##y1.CMP)), C) \
+  else PYGAT_TWL_PUT(lds_tw + (STAGE) * TNW_STAGE + 3 * TNW_IMG, R##b0.CMP, R##b1.CMP, C)
 #define PYGAT_TWL_SPLIT(R, STAGE)                                                             \
   PYGAT_TWL_PUTA(R, STAGE, 0, x) PYGAT_TWL_PUTA(R, STAGE, 1, y) PYGAT_TWL_PUTA(R, STAGE, 2, z) PYGAT_TWL_PUTA(R, STAGE, 3, w) \
   PYGAT_TWL_PUTB(R, STAGE, 0, x) PYGAT_TWL_PUTB(R, STAGE, 1, y) PYGAT_TWL_PUTB(R, STAGE, 2, z) PYGAT_TWL_PUTB(R, STAGE, 3, w)
@@ -863,6 +947,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
   // instructions, 3 LDS writes) between them
 #define PYGAT_TWL_GROUP(TM, TN, PUT0)                                                         \
   {                                                                                           \
+    constexpr int vpm__ = (TL && (TM) == 1) ? 3 : 2;   /* (TL: a B eighth carries the two factors too, ~19 VALU) */ \
     PUT0                                                                                      \
     f32x4 c__ = acc[TM][TN];                                                                  \
     c__ = mfma16_bf16(fqa[TM][2], fqb[TN][2], c__); c__ = mfma16_bf16(fqa[TM][2], fqb[TN][1], c__);   \
@@ -873,7 +958,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
     acc[TM][TN] = c__;                                                                        \
     _Pragma("unroll") for (int m__ = 0; m__ < 9; ++m__) {                                     \
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                      \
-      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                                      \
+      __builtin_amdgcn_sched_group_barrier(0x002, vpm__, 0);                                  \
       if (m__ >= 3 && m__ < 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);             \
     }                                                                                         \
     __builtin_amdgcn_sched_barrier(0);                                                        \
@@ -892,6 +977,7 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
   }
   float4 r0a0, r0a1, r0b0, r0b1, r1a0, r1a1, r1b0, r1b1, r2a0, r2a1, r2b0, r2b1;
   float r0z0, r0z1, r1z0, r1z1, r2z0, r2z1;
+  float4 r0y0, r0y1, r1y0, r1y1, r2y0, r2y1;   // (TL only)
   PYGAT_TWL_LOAD(r0, 0)
   __builtin_amdgcn_sched_barrier(0);   // (issue order = wait order)
   PYGAT_TWL_LOAD(r1, 1)
@@ -906,6 +992,8 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
     PYGAT_TWL_STEP(r0, r2, i + 2)
   }
 #undef PYGAT_TWL_LOAD
+#undef PYGAT_TWL_ROW
+#undef PYGAT_TWL_FAC
 #undef PYGAT_TWL_PUT
 #undef PYGAT_TWL_SPLIT
 #undef PYGAT_TWL_GROUP
@@ -930,9 +1018,12 @@ __global__ __launch_bounds__(512) void gemm_tn_x3w_kernel(TnArgs g) {
     }
 }
 
-int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st) {
+// tl: the tail fields of the TL kernel (tl->t is filled here), or nullptr
+static int launch_tn_x3w(const TnArgs& g, int splits, hipStream_t st, const TnTailArgs* tl) {
   if (g.B2 || g.M <= 64 || g.N <= 64 || (g.k_per_split % 16) != 0) return 0;
   if (!aligned16(g.A) || !aligned16(g.B) || (g.lda % 4) != 0 || (g.ldb % 4) != 0 || (g.M % 4) != 0 || (g.N % 4) != 0) return 0;
+  // (TL forms byte offsets as 32-bit row x 32-bit stride)
+  if (tl && (!aligned16(tl->G) || !aligned16(tl->y) || (tl->ldg % 4) != 0 || tl->ldg >= (1 << 29) || g.ldb >= (1 << 29) || g.K > INT32_MAX)) return 0;
   int dev = -1;
   (void)hipGetDevice(&dev);
   // one 8-wave work-group per CU: at most 256 of them, slabs of whole loop turns (three 32-k steps)
@@ -943,12 +1034,27 @@ int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st) {
   gw.k_per_split = cdiv(cdiv(g.K, sw), 96) * 96;
   sw = (int)cdiv(g.K, gw.k_per_split);
   constexpr size_t ldsw = 2 * TNW_STAGE * sizeof(uint32_t);
-  static bool attr_w[64] = {};   // per device: the attribute belongs to the device's code object
-  if (dev < 0 || dev >= 64 || !attr_w[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-    if (dev >= 0 && dev < 64) attr_w[dev] = true;
+  const dim3 grid((unsigned)sw, (unsigned)cdiv(g.M, 128), (unsigned)cdiv(g.N, 128));
+  if (tl) {
+    // the slab's row ids beside the two stages: a slab of more rows than the LDS holds keeps the stream + the plain kernel
+    const size_t ldst = ldsw + (size_t)(gw.k_per_split + 128) * sizeof(int32_t);
+    if (ldst > 160 * 1024) return 0;
+    TnTailArgs gt = *tl;
+    gt.t = gw;
+    static bool attr_t[64] = {};
+    if (dev < 0 || dev >= 64 || !attr_t[dev]) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (dev >= 0 && dev < 64) attr_t[dev] = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_x3w_kernel<true>, grid, dim3(512), ldst, st, gt);
+  } else {
+    static bool attr_w[64] = {};   // per device: the attribute belongs to the device's code object
+    if (dev < 0 || dev >= 64 || !attr_w[dev]) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
+      if (dev >= 0 && dev < 64) attr_w[dev] = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_x3w_kernel<false>, grid, dim3(512), ldsw, st, gw);
   }
-  hipLaunchKernelGGL(gemm_tn_x3w_kernel, dim3((unsigned)sw, (unsigned)cdiv(g.M, 128), (unsigned)cdiv(g.N, 128)), dim3(512), ldsw, st, gw);
   hipError_t ew = hipGetLastError();
   if (ew != hipSuccess) {
     set_error("gemm_tn_x3w: %s", hipGetErrorString(ew));
@@ -956,6 +1062,12 @@ int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st) {
   }
   return sw;
 }
+
+int try_gemm_tn_x3(const TnArgs& g, int splits, hipStream_t st) { return launch_tn_x3w(g, splits, st, nullptr); }
+
+// (k1_gemm.hip) the weight gradient's reduce: slab sums in slab order, stored as dW [H x Fin x F']
+__global__ void wgrad_splitk_reduce_kernel(int Fin, int H, int Fo, int Fp, int splits, const float* __restrict__ ws,
+                                           float* __restrict__ dW);
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same pipeline for ANY operand layout: C[M x N] = op(A) op(B) with every product formed from the exact three-way
@@ -1256,13 +1368,48 @@ int try_gemm_x3g(int transA, int transB, int M, int N, int64_t K, const float* A
 }
 
 int footprint_gemm_x3(int which, int* regs, int* scratch) {
-  const void* fn = which == 0 ? reinterpret_cast<const void*>(&gemm_tn_x3w_kernel)
+  const void* fn = which == 0 ? reinterpret_cast<const void*>(&gemm_tn_x3w_kernel<false>)
                  : which == 1 ? reinterpret_cast<const void*>(&gemm_x3gw_kernel<true, false>)
+                 : which == 3 ? reinterpret_cast<const void*>(&gemm_tn_x3w_kernel<true>)   // weight gradient forming the tail's dWh rows
                               : reinterpret_cast<const void*>(&gemm_smallk_x3_kernel<false, 4, 16, 2, 2>);   // projection + tail output
   return kernel_footprint_of(fn, regs, scratch);
 }
 
 }  // namespace pygat
+
+// dW = X^T dWh of a level whose self-loop-only tail [row_first, n) has NO dWh rows: the streamed-K split kernel forms them from
+// G / y (gemm_tn_x3w_kernel<true>).  0: done; 1: not taken, nothing launched (the caller runs pygat_gat_backward_tail +
+// pygat_wgrad_blocked) -- whenever pygat_wgrad_blocked would not run that kernel with its dW-writing reduce.
+extern "C" int pygat_wgrad_tail_blocked(int n, int Fin, int H, int Fo, const float* X, int64_t ldx, const pygat_col_blocks* x_blk,
+                                        const float* dWh, float* dW, int split_k, void* ws, int row_first, int flags,
+                                        const float* G, const float* y, const int32_t* user_row, int gemm_mode, void* stream) {
+  using namespace pygat;
+  const int Fp = padded_width(Fo);
+  PYGAT_REQUIRE(gemm_mode >= PYGAT_GEMM_DEFAULT && gemm_mode <= PYGAT_GEMM_FP32_MFMA, "wgrad_tail: unknown product mode %d", gemm_mode);
+  PYGAT_REQUIRE(n > 0 && Fin > 0 && H > 0 && Fp > 0 && X && dWh && dW && ws && G && y && ldx >= (col_blocks_on(x_blk) ? x_blk->w : Fin),
+                "wgrad_tail: bad arguments");
+  PYGAT_REQUIRE(row_first >= 0 && row_first < n, "wgrad_tail: tail [%d, %d) outside the rows", row_first, n);
+  const int R = H * Fp;
+  // what keeps pygat_wgrad_blocked off the streamed-K split kernel (k1_gemm.hip; try_gemm_tn_stream), and what the tail rows need
+  if (!gemm_split(gemm_mode) || col_blocks_on(x_blk) || split_k <= 1 || Fo != Fp || (flags & PYGAT_F_SKIP)) return 1;
+  if (n < 4096 || (int64_t)Fin * R > 512 * 512) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int ldc = R + ((H + 3) / 4) * 4;
+  float* slabs = (float*)ws + (size_t)Fin * ldc;   // (the workspace layout of pygat_wgrad_blocked)
+  TnArgs g;
+  g.M = Fin; g.N = R; g.K = n; g.A = X; g.lda = ldx; g.B = dWh; g.ldb = R; g.ws = slabs;
+  g.N1 = R; g.B2 = nullptr; g.ldb2 = 0;
+  g.k_per_split = cdiv(cdiv((int64_t)n, split_k), 48) * 48;
+  TnTailArgs tl;
+  tl.t = g; tl.row_first = row_first; tl.G = G; tl.y = y; tl.ldg = R; tl.urow = user_row; tl.elu = (flags & PYGAT_F_ELU) ? 1 : 0;
+  const int r = launch_tn_x3w(g, (int)cdiv((int64_t)n, g.k_per_split), st, &tl);
+  if (r < 0) return r;
+  if (r == 0) return 1;
+  hipLaunchKernelGGL(wgrad_splitk_reduce_kernel, dim3((unsigned)cdiv((int64_t)Fin * R, 64)), dim3(512), 0, st, Fin, H, Fo, Fp, r,
+                     (const float*)slabs, dW);
+  PYGAT_CHECK_LAUNCH("wgrad_tail(reduce)");
+  return PYGAT_OK;
+}
 
 #if (PYGAT_DIAG_K1 & 16)
 // diagnostic builds only: copies the stamps the last streamed-A GEMM launch left (device-synchronising); tools/k1_stamps.py

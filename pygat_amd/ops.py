@@ -121,9 +121,12 @@ TAIL_MIN_SHARE = 0.05
 # output ELU(Wh_i) at its user row instead of Wh_i (pygat_project_tail_blocked) -- the tail's Wh rows are neither written nor
 # read.  Bitwise the same results.  Split-bf16 mode, no skip projection, F' = Fp, an ordinary x, and nothing in the backward
 # reading the tail's Wh rows (the a-gradient folded into the column pass).  Measured at config 5 (profiles/INDEX.md, tail):
-# projection 229 -> 254 us, the 125 us stream gone.  (The backward's dWh rows formed inside the weight gradient from G / y was
-# built and measured too: the streamed-K kernel went from 244 to 453 us, more than the 151 us stream it replaced -- the G / y
-# rows are gathers at the caller's rows -- so the backward keeps its stream.)  TAIL_FUSED = False / PYGAT_TAIL_FUSED=0 keeps the
+# projection 229 -> 254 us, the 125 us stream gone.  (The backward's dWh rows formed inside the weight gradient from G / y: a
+# first build took the streamed-K kernel from 244 to 453 us, more than the 151 us stream it replaced
+# (profiles/tail_bwd_wgrad_negative.txt).  Not because the G / y rows are gathers -- inside the tail user_row is increasing, and
+# the stream reads the same rows at 5.7 TB/s -- but because of its loader: row ids fetched by global loads in the prefetch ring's
+# own vmcnt queue, and selects between address computations that hipcc turns into branches, whose joins drain the ring.  With the
+# ids in LDS and a branch-free loader it pays: TAIL_WGRAD_MIN_BYTES below.)  TAIL_FUSED = False / PYGAT_TAIL_FUSED=0 keeps the
 # forward stream too.
 TAIL_FUSED = _config.tail_fused
 # The backward's tail stream and the column pass's cut-row fix-up in ONE launch (pygat_gat_backward_col_finish: the fix-up's
@@ -132,6 +135,13 @@ TAIL_FUSED = _config.tail_fused
 # ten thousand cut rows) that hides beside the stream.  Below it the level keeps the two launches -- a fix-up of a few
 # work-groups has nothing to hide, and the call sequence of small levels is what the tail tests pin.
 COL_FINISH_MIN_BYTES = 32 << 20
+# No backward tail stream at all (pygat_wgrad_tail_blocked, csrc/k1_gemm_x3.hip gemm_tn_x3w_kernel<true>): on tables of
+# TAIL_WGRAD_MIN_BYTES and more the weight-gradient GEMM forms the tail's B rows G_u ELU'(out_u) itself, with the stream's one
+# multiply, and the tail's dWh, ds and dt rows are neither written nor read: prepare -> column pass (main + its own fix-up) ->
+# a-gradient fold -> weight gradient.  Bitwise the stream's dW.  Only where nothing else reads those rows (no input gradient, no
+# skip projection, da folded in the column pass, dense x, no loss through alpha); the entry answers "not taken" for what its kernel
+# does not run (product mode, a blocked x, F' != Fp, ...) and the level then streams the tail after all.  PYGAT_TAIL_WGRAD_MIN_BYTES.
+TAIL_WGRAD_MIN_BYTES = _config.tail_wgrad_min_bytes
 
 
 def head_group(N: int, H: int, Fo: int) -> int:
@@ -928,8 +938,13 @@ def _level_backward(ctx, G, A=None):
                                                  ds.data_ptr() if rowlocal else None, hb, hr, hgw, _ptr(getattr(ctx, "user_row", None)), st),
                       "gat_backward_prepare")
         two_gather = ctx.flavour == "two-gather"
+        # no tail stream at all (TAIL_WGRAD_MIN_BYTES): the weight gradient forms the tail's dWh rows itself, where it is the
+        # only reader of the tail's dWh, ds and dt rows -- no input gradient, da folded in the column pass (cut rows only, all
+        # before the tail), dense x, no loss through alpha
+        tail_wgrad = (rowlocal and fused_tail and not ranged and L.N * L.R * 4 >= TAIL_WGRAD_MIN_BYTES and ctx.need[1]
+                      and not ctx.need[0] and da_part is not None and A is None and getattr(ctx, "xs", None) is None)
         # the tail's stream in the launch of the column pass's fix-up (COL_FINISH_MIN_BYTES)
-        col_finish = (rowlocal and fused_tail and not ranged and L.N * L.R * 4 >= COL_FINISH_MIN_BYTES
+        col_finish = (rowlocal and fused_tail and not ranged and not tail_wgrad and L.N * L.R * 4 >= COL_FINISH_MIN_BYTES
                       and lib.pygat_gat_backward_col_phases_ok(gT, H, Fo, hgw) == 1)
         if col_finish:
             with _span("k4_backward_col"):
@@ -947,7 +962,9 @@ def _level_backward(ctx, G, A=None):
                                                  a_pad.data_ptr(), GR.data_ptr(), None, ds.data_ptr(),
                                                  dWh.data_ptr(), dt.data_ptr(), None, part.data_ptr(), _ptr(da_part), hb, hr, hgw, st),
                       "gat_backward_col")
-                if fused_tail:           # the self-loop-only rows: dWh_j = G_u ELU'(out_u), ds_j = dt_j = 0 (csrc/k12_tail.hip)
+                if tail_wgrad:           # the self-loop-only rows: formed inside the weight gradient (pygat_wgrad_tail_blocked)
+                    pass
+                elif fused_tail:         # ... dWh_j = G_u ELU'(out_u), ds_j = dt_j = 0 (csrc/k12_tail.hip)
                     check(lib.pygat_gat_backward_tail(tail[0], L.N - tail[0], H, Fo, ctx.flags, G.data_ptr(), y.data_ptr(),
                                                       _ptr(getattr(ctx, "user_row", None)), dWh.data_ptr(), 0, 0, ds.data_ptr(), dt.data_ptr(), st),
                           "gat_backward_tail")
@@ -1035,9 +1052,20 @@ def _level_backward(ctx, G, A=None):
             wsw = torch.empty(lib.pygat_wgrad_workspace_bytes(L.Fin, H, Fo, split_k) // 4, dtype=f32, device=dev)
             dW = (torch.zeros if ranged else torch.empty)(H, L.Fin, Fo, dtype=f32, device=dev)
             with _span("k5_wgrad"):
-                check(lib.pygat_wgrad_blocked(L.N, L.Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), dWh.data_ptr(),
-                                              ds.data_ptr() if fold_ds else None, a_pad.data_ptr(), dW.data_ptr(), split_k,
-                                              wsw.data_ptr(), hb, hr, GEMM_MODES[L.mode], st), "wgrad")
+                if tail_wgrad:
+                    rc = lib.pygat_wgrad_tail_blocked(L.N, L.Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), dWh.data_ptr(), dW.data_ptr(),
+                                                      split_k, wsw.data_ptr(), tail[0], ctx.flags, G.data_ptr(), y.data_ptr(),
+                                                      _ptr(getattr(ctx, "user_row", None)), GEMM_MODES[L.mode], st)
+                    if rc == 1:          # not taken (product mode, blocked x, F' != Fp, ...): the stream after all, then the plain GEMM
+                        check(lib.pygat_gat_backward_tail(tail[0], L.N - tail[0], H, Fo, ctx.flags, G.data_ptr(), y.data_ptr(),
+                                                          _ptr(getattr(ctx, "user_row", None)), dWh.data_ptr(), 0, 0, ds.data_ptr(), dt.data_ptr(), st),
+                              "gat_backward_tail")
+                    else:
+                        check(rc, "wgrad_tail")
+                if not tail_wgrad or rc == 1:
+                    check(lib.pygat_wgrad_blocked(L.N, L.Fin, H, Fo, x.data_ptr(), L.ldx, L.xb(), dWh.data_ptr(),
+                                                  ds.data_ptr() if fold_ds else None, a_pad.data_ptr(), dW.data_ptr(), split_k,
+                                                  wsw.data_ptr(), hb, hr, GEMM_MODES[L.mode], st), "wgrad")
         if L.skip and ctx.need[3] and not sparse_w:
             dSc = torch.empty(L.Fin, L.R, dtype=f32, device=dev)
             for c0, w, g0 in L.gp_windows():
