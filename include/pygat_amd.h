@@ -717,6 +717,32 @@ int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t*
                                          const void* seed, uint32_t stream_id, const float* out, int64_t ldo, const float* m,
                                          const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S,
                                          float* dbias, void* ws, void* stream);
+/* The bias pair with a feature row per entry on the key and the value side (the EDGE instantiations of the four fp32 K19 kernels),
+ * additive under ABI 16:
+ *   s[e, h] = scale <q[i, h], k[j, h] + ee[c(e), h]> + bias,   out[i, h, :] = sum_{e in row i} softmax_row(s)[e, h] (v[j, h, :] + ee[c(e), h, :]),
+ * ee = the argument e, [nnz x H*F] floats, a row table like k and v (16-byte aligned, lde >= H*F and a multiple of 4), c(e) the CALLER's
+ * entry index of CSR position e (perm[e]; perm may be null: the position itself).  A lane reads its 16 bytes of the entry's row with the
+ * k and v rows of the entry.  kk = k_j + ee_c and vv = v_j + ee_c are one rounded add per element, formed the same way by both
+ * launchers, and everything after sees kk and vv where the pairs above see k_j and v_j: with ee = 0, out, dq, P and S have their
+ * values.  backward_rows: dp = <G_i, vv>, D = <G_i, out_i>, ds = scale p (dp - D), dq_i = sum_e ds kk, P := p and S := ds, so dk =
+ * pygat_spmm_forward(val = S, b = q) and dv = pygat_spmm_forward(val = P, b = G) as above, and the gradient of ee, row-local:
+ * de[c(e), h, :] = ds q[i, h, :] + p G[i, h, :], [nnz x H*F] with row stride ldde, a row table like e.  Every row of de is written
+ * exactly once (an entry belongs to one row, in a long row to one piece): nothing is zeroed or accumulated.  de may be null: not asked
+ * for, ldde is then not looked at.  bias may be null: no bias, bias_head_stride is then not looked at (dbias is not written);
+ * otherwise as in the bias pair, dbias = p (dp - D).  A row of one entry (i, j) gets out_i = v_j + ee_c and de_c = G_i bit for bit, p
+ * = 1 and ds = dq_i = 0 exactly; a masked entry (bias -9e15) gets an all-zero row of de.  Refusals as for the bias pair after the
+ * launcher's own name; besides: a null e with nnz > 0, a misaligned e or de, a short or odd lde or ldde.  The workspace and its size
+ * query are unchanged. */
+int pygat_dot_attn_edge_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                int64_t ldv, const float* e, int64_t lde, const float* bias, int bias_head_stride, float* out,
+                                int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_dot_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                      int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                      const float* v, int64_t ldv, const float* e, int64_t lde, const float* bias,
+                                      int bias_head_stride, const float* out, int64_t ldo, const float* m, const float* Z,
+                                      const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* de,
+                                      int64_t ldde, float* dbias, void* ws, void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

@@ -53,6 +53,7 @@ SYMBOLS = [
     "pygat_dot_attn_workspace_bytes", "pygat_dot_attn_forward", "pygat_dot_attn_backward_rows",
     "pygat_dot_attn_bias_forward", "pygat_dot_attn_bias_backward_rows", "pygat_dot_attn_bf16_forward",
     "pygat_dot_attn_dropout_forward", "pygat_dot_attn_dropout_backward_rows",
+    "pygat_dot_attn_edge_forward", "pygat_dot_attn_edge_backward_rows",
     "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
     "pygat_unpack_blockdiag",
     "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
@@ -186,6 +187,9 @@ def _load():
     lib.pygat_dot_attn_dropout_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, f, p, u32, p, i64, p, p, p, p]
     lib.pygat_dot_attn_dropout_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, f, p, u32, p, i64, p, p,
                                                          p, i64, p, i64, p, p, p, p, p]
+    lib.pygat_dot_attn_edge_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p, p]
+    lib.pygat_dot_attn_edge_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p,
+                                                      i64, p, i64, p, p, p, i64, p, p, p]
     lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
     lib.pygat_wgrad_workspace_bytes.restype = sz
     lib.pygat_wgrad.argtypes = [i, i, i, i, p, i64, p, p, p, p, i, p, i, i, i, p]

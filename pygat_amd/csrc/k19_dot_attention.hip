@@ -36,6 +36,16 @@
 // T = p (mask <G_i, v_j> - D), and P := p mask, so dv = spmm^T(P, G) needs no change.  A row of one entry gets out_i = mask v_j bit for
 // bit; a row whose entries are all dropped, and every row under p = 1, exact zeros.  The instruction streams of the kernels without
 // DROP are what they were before the flag.
+// EDGE (a compile-time flag of the four fp32 kernels, beside BIAS, never with DROP or bf16 tables; pygat_dot_attn_edge_*): a row of H*F
+// floats per entry on both sides, s[e, h] = scale <q[i, h], k[j, h] + e[c(e), h]> (+ bias) and out[i, h] = sum_e alpha[e, h] (v[j, h] +
+// e[c(e), h]), c(e) the CALLER's entry index, carried a batch ahead as under BIAS.  A lane's chunk of the e row is the 4 elements of its
+// chunk of k and v, one more 16-byte load per (entry, chunk), asked for with the gather of its batch.  kk = k_j + e and vv = v_j + e are
+// one rounded add per element, formed the same way in both passes; everything after sees kk and vv where it saw k_j and v_j, so e = 0
+// leaves out, dq, P and S at the values of the kernels without EDGE.  Backward: dp = <G_i, vv>, dq_i += ds kk, and the gradient of e is
+// row-local, de[c(e)] = ds q_i + p G_i, a 16-byte store per lane and entry where de is asked for: an entry belongs to one row (in a
+// long row to one piece), so every row of de is written exactly once and nothing is zeroed.  Records and the workspace are unchanged.
+// A row of one entry (i, j) gets out_i = v_j + e_c and de_c = G_i bit for bit.  The instruction streams of the kernels without EDGE
+// are what they were before the flag.
 #include "long_rows.h"
 #include "rng.h"
 #include <float.h>
@@ -68,6 +78,10 @@ struct DaArgs {
   int bhs;                     // 1 | 0
   float* dbias;                // [nnz x H], the caller's entry order; null: not asked for
   DropRng rng;                 // DROP kernels only: the seed (device memory), stream id, keep threshold and 1 / keep of the mask
+  const float* e;              // EDGE kernels only from here: the entry's row e + entry * lde at the CALLER's entry index (perm)
+  int64_t lde;
+  float* de;                   // [nnz x ldde], the caller's entry order; null: not asked for
+  int64_t ldde;
 };
 
 static inline int64_t da_pstride(int H, int F) { return ((int64_t)H * F + 2 * H + 3) & ~(int64_t)3; }
@@ -300,6 +314,29 @@ __device__ __forceinline__ void da_gather(const DaArgs& g, const DaLane<VEC>& ln
   }
 }
 
+// EDGE: the e rows of U entries at the caller's entry indices eid[0..U), asked for right behind the gather of their batch, and
+// kk = k_j + e, vv = v_j + e in the gathered rows' place: one rounded add per element, the same in the forward and the backward
+template <int VEC, int U, bool EDGE>
+struct DaEdgeRows {
+  float4 e[EDGE ? U : 1][EDGE ? VEC : 1];
+};
+template <int VEC, int U>
+__device__ __forceinline__ void da_gather_edge(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&eid)[U],
+                                               DaEdgeRows<VEC, U, true>& we) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) da_load_row<VEC>(g.e + (int64_t)eid[u] * g.lde, ln, we.e[u]);
+}
+__device__ __forceinline__ void da_add_rn(float4& y, const float4& x) {
+  y.x = __fadd_rn(y.x, x.x); y.y = __fadd_rn(y.y, x.y); y.z = __fadd_rn(y.z, x.z); y.w = __fadd_rn(y.w, x.w);
+}
+template <int VEC, int U>
+__device__ __forceinline__ void da_edge_add(DaRows<VEC, U>& w, const DaEdgeRows<VEC, U, true>& we) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) { da_add_rn(w.k[u][v], we.e[u][v]); da_add_rn(w.v[u][v], we.e[u][v]); }
+}
+
 // eid (BIAS | DROP) and key (DROP): the caller's entry indices of the batch and the key of its draws
 template <int LPR, int VEC, int U, bool BIAS, bool DROP>
 __device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], const DaRows<VEC, U>& w,
@@ -327,11 +364,11 @@ __device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const DaLane<VEC>& 
 // before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather.  BIAS: the next
 // batch's entry indices travel with its column indices, and its bias values are asked for once this batch is folded -- ahead of the
 // next gather, so they are there when it is -- an iteration still waits for one gather.  DROP: the entry indices travel the same way,
-// with or without a bias
-template <int LPR, int VEC, int U, bool BIAS, typename T, bool DROP>
+// with or without a bias.  EDGE: the same entry indices place the batch's e rows, asked for right behind its gather
+template <int LPR, int VEC, int U, bool BIAS, typename T, bool DROP, bool EDGE = false>
 __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
                                             int64_t step, uint2 key, DaState<VEC>& st) {
-  constexpr bool EID = BIAS || DROP;
+  constexpr bool EID = BIAS || DROP || EDGE;
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
@@ -350,6 +387,8 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
     while (full) {
       DaRows<VEC, U> w;
       da_gather<VEC, U, T>(g, ln, src, w);
+      [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
+      if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
       e += U * step;
       full = e + (U - 1) * step < e1;
       if (full) {
@@ -359,6 +398,7 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
           if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
         }
       }
+      if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
       da_fwd_fold<LPR, VEC, U, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);    // (eid: this batch's, not yet replaced)
       if constexpr (EID)
         if (full) {
@@ -375,14 +415,20 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
     if constexpr (BIAS) da_bias_load<VEC, 1>(g, ln, eid, bs);
     DaRows<VEC, 1> w;
     da_gather<VEC, 1, T>(g, ln, src, w);
+    if constexpr (EDGE) {
+      DaEdgeRows<VEC, 1, true> we;
+      da_gather_edge<VEC, 1>(g, ln, eid, we);
+      da_edge_add<VEC, 1>(w, we);
+    }
     da_fwd_fold<LPR, VEC, 1, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false>
+template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
   static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
+  static_assert(!EDGE || (!DROP && sizeof(T) == sizeof(float)), "per-entry rows: fp32 tables, no dropout");
   constexpr int EPW = 64 / LPR;
   const uint2 key = da_key<DROP>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -395,7 +441,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
     DaState<VEC> st;
     da_init<VEC>(st);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP>(g, ln, q, e0 + grp, e1, EPW, key, st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP, EDGE>(g, ln, q, e0 + grp, e1, EPW, key, st);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
       float mx = st.m[v];
@@ -422,9 +468,10 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row.  m and Z are what a backward reads: the bf16-table kernels, which have none, do not write them
-template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false>
+template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
+  static_assert(!EDGE || (!DROP && sizeof(T) == sizeof(float)), "per-entry rows: fp32 tables, no dropout");
   constexpr bool KEEP_MZ = sizeof(T) == sizeof(float);
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -445,7 +492,7 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   } else if (end > start) {
     float4 q[VEC];
     da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP>(g, ln, q, start, end, 1, da_key<DROP>(g), st);
+    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP, EDGE>(g, ln, q, start, end, 1, da_key<DROP>(g), st);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
@@ -491,9 +538,14 @@ __device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { retu
 // DROP: the batch's keep factors are drawn again (ent[u] + head is an entry's flat mask index); an entry's multiplies <G_i, v_j> --
 // D_i = <G_i, out_i> is the row term of the dropped sum already -- and the stored P is p keep, what the transposed SpMM of dv
 // multiplies G with
-template <int LPR, int VEC, int U, bool BIAS, bool DROP>
+// EDGE: w holds kk and vv; every lane also stores its chunk of de[c(e)] = ds q_i + p G_i where de is asked for (eid: the batch's
+// entry indices, looked at under EDGE alone).  lone (EDGE alone): the entry is the only one of its row, whose coefficient is 1 by
+// definition and goes into de as that, so de_c = G_i bit for bit: the p formed here is exp(scale <q, kk> - m) with the product
+// contracted into the difference, m the rounded product, and may come out an ulp above 1 where the scale is no power of two
+template <int LPR, int VEC, int U, bool BIAS, bool DROP, bool EDGE = false>
 __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, const DaRows<VEC, U>& w,
-                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, uint2 key, float4 (&dq)[VEC]) {
+                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, uint2 key, float4 (&dq)[VEC],
+                                            [[maybe_unused]] const int32_t (&eid)[U], [[maybe_unused]] bool lone = false) {
   [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
   if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
@@ -518,15 +570,24 @@ __device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& 
         if constexpr (BIAS)
           if (g.dbias) g.dbias[ent[u] + ln.head[v]] = p * (dp - r.D[v]);
       }
+      if constexpr (EDGE)
+        if (g.de && (ln.ok >> v & 1)) {
+          const float4 &qi = r.q[v], &Gi = r.G[v];
+          const float pe = lone ? 1.f : p;
+          st4(g.de + (int64_t)eid[u] * g.ldde + ln.ofs[v],
+              make_float4(fmaf(ds, qi.x, pe * Gi.x), fmaf(ds, qi.y, pe * Gi.y), fmaf(ds, qi.z, pe * Gi.z), fmaf(ds, qi.w, pe * Gi.w)));
+        }
     }
 }
 
 // as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic; BIAS: its bias values are
-// asked for once this batch is folded, ahead of the next gather; DROP: the entry indices travel as under BIAS, with or without one
-template <int LPR, int VEC, int U, bool BIAS, bool DROP>
+// asked for once this batch is folded, ahead of the next gather; DROP: the entry indices travel as under BIAS, with or without one;
+// EDGE: they also place the batch's e rows, asked for right behind its gather, and its rows of de; lone: the walk is over a row of one
+// entry (the row kernel says so; a piece of a long row never is)
+template <int LPR, int VEC, int U, bool BIAS, bool DROP, bool EDGE = false>
 __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, int64_t e0, int64_t e1,
-                                            int64_t step, uint2 key, float4 (&dq)[VEC]) {
-  constexpr bool EID = BIAS || DROP;
+                                            int64_t step, uint2 key, float4 (&dq)[VEC], [[maybe_unused]] bool lone = false) {
+  constexpr bool EID = BIAS || DROP || EDGE;
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
@@ -548,6 +609,8 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
     while (full) {
       DaRows<VEC, U> w;
       da_gather<VEC, U>(g, ln, src, w);
+      [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
+      if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
       if constexpr (!EID) {
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
@@ -566,7 +629,8 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
       }
-      da_bwd_fold<LPR, VEC, U, BIAS, DROP>(g, ln, r, w, ent, bs, key, dq);
+      if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
+      da_bwd_fold<LPR, VEC, U, BIAS, DROP, EDGE>(g, ln, r, w, ent, bs, key, dq, eid);
       if constexpr (EID)
         if (full) {
           da_eids<U>(g, raw, e, step, eid);
@@ -584,13 +648,21 @@ __device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& 
     }
     DaRows<VEC, 1> w;
     da_gather<VEC, 1>(g, ln, src, w);
-    da_bwd_fold<LPR, VEC, 1, BIAS, DROP>(g, ln, r, w, ent, bs, key, dq);
+    [[maybe_unused]] int32_t eide[1] = {0};
+    if constexpr (EDGE) {
+      eide[0] = da_eid(g, da_eid_raw(g, e), e);
+      DaEdgeRows<VEC, 1, true> we;
+      da_gather_edge<VEC, 1>(g, ln, eide, we);
+      da_edge_add<VEC, 1>(w, we);
+    }
+    da_bwd_fold<LPR, VEC, 1, BIAS, DROP, EDGE>(g, ln, r, w, ent, bs, key, dq, eide, lone);
   }
 }
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
-template <int LPR, int VEC, bool BIAS, bool DROP = false>
+template <int LPR, int VEC, bool BIAS, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
+  static_assert(!(EDGE && DROP), "per-entry rows: no dropout");
   constexpr int EPW = 64 / LPR;
   const uint2 key = da_key<DROP>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -603,7 +675,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
     float4 dq[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP>(g, ln, r, e0 + grp, e1, EPW, key, dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP, EDGE>(g, ln, r, e0 + grp, e1, EPW, key, dq);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
@@ -613,8 +685,9 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC, bool BIAS, bool DROP = false>
+template <int LPR, int VEC, bool BIAS, bool DROP = false, bool EDGE = false>
 __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
+  static_assert(!(EDGE && DROP), "per-entry rows: no dropout");
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
@@ -633,7 +706,8 @@ __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   } else if (end > start) {                                    // (a row without entries: its G row is not read)
     DaRow<VEC> r;
     da_bwd_load<LPR, VEC>(g, ln, row, r);
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP>(g, ln, r, start, end, 1, da_key<DROP>(g), dq);
+    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP, EDGE>(g, ln, r, start, end, 1, da_key<DROP>(g), dq,
+                                                                            EDGE && end - start == 1);
   }
   da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
 }
@@ -667,13 +741,13 @@ static inline void da_pick(int H, int F, int* lpr, int* vec, int* nch) {
     else { constexpr int LPR = 64, VEC = 4; __VA_ARGS__; }                   \
   } while (0)
 
-template <bool BIAS, bool DROP = false>
+template <bool BIAS, bool DROP = false, bool EDGE = false>
 static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
   const void* f = nullptr;
-  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS, DROP>)
-                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS, DROP>))
-                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, float, DROP>)
-                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, float, DROP>)));
+  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS, DROP, EDGE>)
+                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS, DROP, EDGE>))
+                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, float, DROP, EDGE>)
+                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, float, DROP, EDGE>)));
   return f;
 }
 
@@ -687,8 +761,10 @@ static const void* da_bf16_kernel_ptr(bool lng, int lpr, int vec) {
 }
 
 // pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH), and the
-// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>; k19d_ | k19db_ (BIAS): the DROP instantiations of the first two
-static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch, bool drop = false) {
+// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>; k19d_ | k19db_ (BIAS): the DROP instantiations of the first two;
+// k19e_ | k19eb_ (BIAS): their EDGE instantiations
+static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch, bool drop = false,
+                        bool edge = false) {
   const void* fn = nullptr;
   char dir[8] = "", kind[8] = "", rest = 0;
   int lpr = 0, vec = 0;
@@ -698,6 +774,9 @@ static int da_footprint(const char* name, const char* prefix, bool bias, bool bf
       (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4))) {
     if (bf16)
       fn = bias ? da_bf16_kernel_ptr<true>(!strcmp(kind, "long"), lpr, vec) : da_bf16_kernel_ptr<false>(!strcmp(kind, "long"), lpr, vec);
+    else if (edge)
+      fn = bias ? da_kernel_ptr<true, false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
+                : da_kernel_ptr<false, false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
     else if (drop)
       fn = bias ? da_kernel_ptr<true, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
                 : da_kernel_ptr<false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
@@ -717,6 +796,12 @@ int footprint_k19h(const char* name, int* regs, int* scratch) { return da_footpr
 int footprint_k19hb(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19hb_", true, true, regs, scratch); }
 int footprint_k19d(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19d_", false, false, regs, scratch, true); }
 int footprint_k19db(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19db_", true, false, regs, scratch, true); }
+int footprint_k19e(const char* name, int* regs, int* scratch) {
+  return da_footprint(name, "k19e_", false, false, regs, scratch, false, true);
+}
+int footprint_k19eb(const char* name, int* regs, int* scratch) {
+  return da_footprint(name, "k19eb_", true, false, regs, scratch, false, true);
+}
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
 
@@ -805,15 +890,34 @@ static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
   return PYGAT_OK;
 }
 
-// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z.  DROP: drop names the mask
-template <bool BIAS, typename T = float, bool DROP = false>
+// the per-entry rows of the EDGE launchers: e, and de where it is asked for, are row tables like k and v, [nnz x H*F] at the caller's
+// entry index; e is non-null where there are entries
+struct DaEdge {
+  const float* e;
+  int64_t lde;
+  float* de;                   // backward only; null: not asked for
+  int64_t ldde;
+};
+static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed) {
+  if (nnz > 0 || ed.e) DA_TABLE(what, "e", ed.e, ed.lde, HF);
+  if (ed.de) DA_TABLE(what, "de", ed.de, ed.ldde, HF);
+  return PYGAT_OK;
+}
+
+// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z.  DROP: drop names the mask.  EDGE: edge
+// names the per-entry rows
+template <bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
 static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
                       int F, float scale, const float* q, int64_t ldq, const T* k, int64_t ldk, const T* v, int64_t ldv,
                       const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream,
-                      const DaDrop* drop = nullptr) {
+                      const DaDrop* drop = nullptr, const DaEdge* edge = nullptr) {
   int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws, (int)sizeof(T),
                            sizeof(T) == sizeof(float));
   if (rc != PYGAT_OK) return rc;
+  if constexpr (EDGE) {
+    rc = da_check_edge(what, nnz, H * F, *edge);
+    if (rc != PYGAT_OK) return rc;
+  }
   if constexpr (BIAS) {
     rc = da_check_bias(what, nnz, bias, bias_head_stride);
     if (rc != PYGAT_OK) return rc;
@@ -829,29 +933,34 @@ static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* 
           ldv, out, ldo, m, Z, ws);
   if constexpr (BIAS) { g.perm = perm; g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; }
   if constexpr (DROP) { g.perm = perm; g.rng = rng; }
+  if constexpr (EDGE) { g.perm = perm; g.e = edge->e; g.lde = edge->lde; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T, DROP>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T, DROP>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T, DROP, EDGE>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T, DROP, EDGE>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
 
-template <bool BIAS, bool DROP = false>
+template <bool BIAS, bool DROP = false, bool EDGE = false>
 static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
                             int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                             int64_t ldv, const float* bias, int bias_head_stride, const float* out, int64_t ldo, const float* m,
                             const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias,
-                            void* ws, void* stream, const DaDrop* drop = nullptr) {
+                            void* ws, void* stream, const DaDrop* drop = nullptr, const DaEdge* edge = nullptr) {
   int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
   if (rc != PYGAT_OK) return rc;
   DA_TABLE(what, "G", G, ldg, H * F);
   DA_TABLE(what, "dq", dq, lddq, H * F);
   PYGAT_REQUIRE(nnz == 0 || P, "%s: null P", what);
   PYGAT_REQUIRE(nnz == 0 || S, "%s: null S", what);
+  if constexpr (EDGE) {
+    rc = da_check_edge(what, nnz, H * F, *edge);
+    if (rc != PYGAT_OK) return rc;
+  }
   if constexpr (BIAS) {
     rc = da_check_bias(what, nnz, bias, bias_head_stride);
     if (rc != PYGAT_OK) return rc;
@@ -867,14 +976,15 @@ static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int
           const_cast<float*>(Z), ws);
   g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
   if constexpr (DROP) g.rng = rng;
+  if constexpr (EDGE) { g.e = edge->e; g.lde = edge->lde; g.de = edge->de; g.ldde = edge->ldde; }
   if constexpr (BIAS) { g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; g.dbias = dbias; }
   int lpr, vec, nch;
   da_pick(H, F, &lpr, &vec, &nch);
   const unsigned chunks = (unsigned)long_chunks(nnz);
   const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
   hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS, DROP>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS, DROP>), dim3(blocks), dim3(256), 0, st, g));
+  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS, DROP, EDGE>), dim3(chunks), dim3(64), 0, st, g));
+  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS, DROP, EDGE>), dim3(blocks), dim3(256), 0, st, g));
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -958,4 +1068,36 @@ extern "C" int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, con
                                         bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream, &drop);
   return da_backward_rows<false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out, ldo,
                                        m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream, &drop);
+}
+
+// the bias pair with a row of H*F floats per entry on both sides (the EDGE instantiations): s = scale <q_i, k_j + e_c> + bias,
+// out_i = sum alpha (v_j + e_c), c the caller's entry index; backward_rows also forms de[c] = ds q_i + p G_i where de is not null.
+// A null bias: no bias, bias_head_stride is then not looked at
+extern "C" int pygat_dot_attn_edge_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                           int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                           const float* v, int64_t ldv, const float* e, int64_t lde, const float* bias,
+                                           int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  const char* what = "dot_attn_edge_forward";
+  const DaEdge edge = {e, lde, nullptr, 0};
+  if (bias)
+    return da_forward<true, float, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
+                                                bias_head_stride, out, ldo, m, Z, ws, stream, nullptr, &edge);
+  return da_forward<false, float, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1,
+                                               out, ldo, m, Z, ws, stream, nullptr, &edge);
+}
+
+extern "C" int pygat_dot_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                                                 const int32_t* perm, int H, int F, float scale, const float* q, int64_t ldq,
+                                                 const float* k, int64_t ldk, const float* v, int64_t ldv, const float* e, int64_t lde,
+                                                 const float* bias, int bias_head_stride, const float* out, int64_t ldo,
+                                                 const float* m, const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq,
+                                                 float* P, float* S, float* de, int64_t ldde, float* dbias, void* ws, void* stream) {
+  const char* what = "dot_attn_edge_backward_rows";
+  const DaEdge edge = {e, lde, de, ldde};
+  if (bias)
+    return da_backward_rows<true, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
+                                               bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream, nullptr,
+                                               &edge);
+  return da_backward_rows<false, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out,
+                                              ldo, m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream, nullptr, &edge);
 }

@@ -13,6 +13,8 @@ its score as an op of its own.
         out = dot_attention(pattern, q, k16, v16)                 # bits of dot_attention(pattern, q, k16.float(), v16.float())
     out = dot_attention_dropout(pattern, q, k, v, p, bias=b, training=self.training)    # training: dropout p on the coefficients, after
                                                                   # the softmax, drawn in the kernels from a seed on the device
+    out = dot_attention_edge(pattern, q, k, v, e, bias=b)         # edge features: e [E, H, F] joins k[col] in the score and v[col] in
+                                                                  # the sum (the EDGE instantiations); differentiable in e too
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the
 pattern rectangular.  To attend over columns instead of rows, build the pattern from swapped indices.  Both ops are differentiable
@@ -377,3 +379,114 @@ def dot_attention_dropout(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor
     if seed is None:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
     return _DotAttentionFn.apply(pattern, q, k, v, scale, bias, (p, seed))
+
+
+# -------------------------------------------------------------------------------------------------------------- dot_attention_edge
+_EDGE_OP = "dot_attention_edge"
+
+
+def _edge_tensor(pattern, e, op: str = _EDGE_OP):
+    """The refusals of `e` that do not depend on q, k and v."""
+    want = "e [E, H, F] (or [E, F] without a head axis), a row per entry at the caller's entry index, expected"
+    if not isinstance(pattern, EdgePattern):
+        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    if not isinstance(e, torch.Tensor) or not e.is_cuda:
+        raise ValueError(f"pygat_amd {op}: e must be a tensor on the GPU (there is no CPU path); {want}")
+    if e.dtype != torch.float32:
+        raise ValueError(f"pygat_amd {op}: e must be float32, not {e.dtype}; {want}")
+    if e.device != pattern.device:
+        raise ValueError(f"pygat_amd {op}: e lives on {e.device}, the pattern on {pattern.device}; {want}")
+
+
+def _edge_shape(pattern, e, q, op: str = _EDGE_OP):
+    want = (pattern.nnz,) + tuple(q.shape[1:])
+    if tuple(e.shape) != want:
+        raise ValueError(f"pygat_amd {op}: e {list(want)} expected for E = {pattern.nnz} entries and q {tuple(q.shape)} -- (E,) + "
+                         f"q.shape[1:], a row per entry -- got {tuple(e.shape)}")
+
+
+class _DotAttentionEdgeFn(torch.autograd.Function):
+    """dot_attention_edge: _DotAttentionFn's skeleton on the EDGE instantiations, with e [E, H, F] beside k and v and its gradient de
+    written by the row pass of the backward."""
+
+    @staticmethod
+    def forward(ctx, pattern, q, k, v, e, scale, bias):
+        op = _EDGE_OP
+        _edge_tensor(pattern, e, op)
+        H, F, flat, bhs = _checked(op, pattern, q, k, v, bias)
+        _edge_shape(pattern, e, q, op)
+        scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
+        n, HF = pattern.n_rows, H * F
+        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs = pattern, scale, (H, F), bhs
+        if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
+            ctx.save_for_backward(q, k, v, e, None, None, None, bias)
+            return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+        qc, kc, vc, ec = (t.detach().contiguous() for t in (q, k, v, e))
+        bc = None if bias is None else bias.detach().contiguous()
+        with torch.cuda.device(qc.device):
+            out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
+            m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
+            ws = _workspace(pattern.nnz, H, F, qc.device)
+            check(lib.pygat_dot_attn_edge_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
+                                                  scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(ec), HF, _ptr(bc), bhs or 0,
+                                                  _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()), "dot_attn_edge_forward")
+        out = out.view(q.shape)
+        ctx.save_for_backward(q, k, v, e, out, m, Z, bias)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        q, k, v, e, out, m, Z, bias = ctx.saved_tensors
+        pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
+        if G.dtype != torch.float32:
+            raise ValueError(f"pygat_amd {_EDGE_OP}: the gradient of the output must be float32, not {G.dtype}")
+        need_q, need_k, need_v, need_e = ctx.needs_input_grad[1:5]
+        need_b = bias is not None and ctx.needs_input_grad[6]
+        if not (need_q or need_k or need_v or need_e or need_b):
+            return None, None, None, None, None, None, None
+        n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
+        if out is None:                                            # no entries: zeros, nothing launched
+            return (None,) + tuple(torch.zeros_like(t) if need else None for t, need in
+                                   ((q, need_q), (k, need_k), (v, need_v), (e, need_e))) + (None, torch.zeros_like(bias) if need_b else None)
+        qc, kc, vc, ec = (t.detach().contiguous() for t in (q, k, v, e))
+        bc = None if bias is None else bias.detach().contiguous()
+        Gc = G.contiguous().view(n, HF)
+        with torch.cuda.device(qc.device):
+            dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
+            P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
+            de = torch.empty(nnz, HF, dtype=torch.float32, device=qc.device) if need_e else None      # (every row is written once)
+            db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
+            ws = _workspace(nnz, H, F, qc.device)
+            check(lib.pygat_dot_attn_edge_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
+                                                        _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(ec), HF, _ptr(bc), bhs or 0,
+                                                        _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S),
+                                                        _ptr(de), HF, _ptr(db), _ptr(ws), _stream()), "dot_attn_edge_backward_rows")
+            if need_b:                          # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
+                db = db.sum(1) if bhs == 0 else db.view(bias.shape)
+        dk = dv = None
+        if need_k or need_v:
+            rowptr_t, row_t, perm_t = pattern.transposed()
+            if need_k:
+                dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
+            if need_v:
+                dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
+        return None, dq.view(q.shape) if need_q else None, dk, dv, de.view(e.shape) if need_e else None, None, db
+
+
+def dot_attention_edge(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tensor,
+                       scale: Optional[float] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dot_attention with a feature row per entry on the key and the value side, as a graph-transformer layer uses its edge features
+    (TransformerConv with edge_dim: e = lin_edge(edge_attr).view(E, H, F)):
+    out[i] = sum over the entries c = (i, j) of row i of  softmax_j(scale * <q[i], k[j] + e[c]> + bias[c]) * (v[j] + e[c]), per head.
+    e is [E, H, F] ([E, F] where q, k and v have no head axis) at the caller's entry index, as bias and spmm's values; scale and bias
+    are dot_attention's.  Fused on the EDGE instantiations of the K19 kernels: a lane reads its 16 bytes of the e row with the k and v
+    rows of the entry, k[j] + e[c] and v[j] + e[c] are one rounded add per element in both passes -- e = 0 gives dot_attention's
+    values -- and the gradient of e, de[c] = ds * q[i] + alpha * G[i], is written by the row pass of the backward, once per entry: no
+    transposed pass, no atomics, two runs give the same bits.  Differentiable in q, k, v, e and bias; when e does not require grad,
+    no [E, H, F] tensor is made in backward.  A row without entries gets zeros; a row of one entry (i, j) gets v[j] + e[c] bit for bit.
+    float32 GPU tensors with dot_attention's limits (1 <= H <= 64, F a power of two in 4..256, H * F <= 1024); bfloat16 k, v or e are
+    refused: there is no inference variant and no dropout variant of this op."""
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (k, v, e)):
+        raise ValueError(f"pygat_amd {_EDGE_OP}: k, v and e must be float32: bfloat16 tables are for dot_attention's inference forward")
+    return _DotAttentionEdgeFn.apply(pattern, q, k, v, e, scale, bias)

@@ -8,6 +8,7 @@ at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone 
     python tools/dot_attention_bench.py --bias [...]       # the per-entry bias: three contenders -> profiles/dot_attention_bias_bench.jsonl
     python tools/dot_attention_bench.py --kv-bf16 [...]    # bf16 k and v tables: fp32 against bf16 forward -> profiles/dot_attention_bf16_bench.jsonl
     python tools/dot_attention_bench.py --dropout [...]    # seeded attention dropout: three contenders -> profiles/dot_attention_dropout_bench.jsonl
+    python tools/dot_attention_bench.py --edge [...]       # per-entry key and value features: fused against the chain of parts -> profiles/dot_attention_edge_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
@@ -37,7 +38,14 @@ without it (dot_attention), and the composition spmm(edge_softmax(edge_dot(q, k)
 with the same seed, which writes and reads the mask as a [E, H] tensor.  The first and the last are priced on the sampled rows against
 the fp64 computation under the mask attention_dropout_mask writes (that it is the mask of tests/philox_ref.py is the tests' business).
 The fused op's bytes are those without dropout -- the decisions are drawn in registers -- so what the measured increment over the
-fused op without dropout shows is arithmetic: ten Philox rounds per (entry, head chunk) and lane."""
+fused op without dropout shows is arithmetic: ten Philox rounds per (entry, head chunk) and lane.
+
+--edge measures dot_attention_edge: in the one child process it alternates the fused op, with an N(0, 1) e [E, H, F] that requires a
+gradient, and the chain of parts a user writes without it -- edge_dot(q, k, scale) + scale * (q[row] * e).sum(-1), edge_softmax,
+spmm(alpha, v) + zeros.index_add(0, row, alpha[..., None] * e) -- and prices both on the sampled rows against the fp64 computation
+with e on both sides.  e alone is E H F 4 bytes (5.5 GB at 8x16, 22 GB at 8x64) and de the same again; the chain holds several
+tensors of that size at once.  Free device memory is asked for first: a contender that does not fit is left out and the record
+says so (`skipped`), a shape where not even the fused op fits is skipped whole; the tool does not fail over it."""
 import argparse
 import json
 import math
@@ -106,6 +114,37 @@ def bias_backward_bytes(E, H, perm):
     return E * 8 * H
 
 
+def edge_forward_bytes(E, H, F, perm):
+    """What e adds to the fused forward: its row per entry, and the entry index where the pattern carries a permutation."""
+    return E * (4 * H * F + (4 if perm else 0))
+
+
+def edge_backward_bytes(E, H, F, perm):
+    """... and to the row pass of the backward: the row read again and its gradient written (the entry index is read there anyway)."""
+    return E * 8 * H * F
+
+
+def chain_edge_forward_bytes(E, N, H, F):
+    """What e adds to the composition's forward, counted in torch's elementwise passes.  Key side: q[row] gathered and written, the
+    product with e read twice and written, its sum over F read, the [E, H] result scaled and added to edge_dot's.  Value side:
+    alpha e formed (e read, the product written), read again by index_add and added to [N, R] zeros with float atomics, and the sum
+    with spmm's out."""
+    R = H * F
+    key = E * (R * 4 + 8 + R * 4) + E * (3 * R * 4) + E * (R * 4 + H * 4) + E * (5 * H * 4)
+    value = E * (H * 4 + 2 * R * 4) + E * (R * 4 + 8 + 2 * R * 4) + N * (R * 4) + N * (3 * R * 4)
+    return key + value
+
+
+def chain_edge_backward_bytes(E, N, H, F):
+    """... and to its backward, at least: G[row] gathered and written for the scatter; d(alpha e) = that times e and alpha (e and
+    G[row] read twice, [E, R] and its sum over F written); the key-side product's two factors' gradients (g e and g q[row]: two
+    reads and a write each), the scatter of the first into dq with float atomics, and the sum of the two parts of de."""
+    R = H * F
+    value = E * (2 * R * 4 + 8) + E * (3 * R * 4 + H * 4) + E * (R * 4 + H * 4 + R * 4)
+    key = 2 * E * (2 * R * 4 + H * 4) + E * (R * 4 + 8 + 2 * R * 4) + E * (3 * R * 4)
+    return value + key
+
+
 def timed_round(fn, steps):
     """-> the ms of `steps` calls, each between two events."""
     import torch
@@ -134,16 +173,21 @@ def alternate(contenders, rounds, steps, warmup):
     return out
 
 
-def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None, mask=None):
+def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None, mask=None, edge=None):
     """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j (+ bias [E, H], at the
-    CSR position), times mask [E, H] (pre-scaled, after the softmax) where given, times v_j."""
+    CSR position), times mask [E, H] (pre-scaled, after the softmax) where given, times v_j.  edge [E, H, F], at the CSR position:
+    added to k_j and to v_j."""
     import torch
     deg = rp[rows + 1] - rp[rows]
     idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
     sub = torch.repeat_interleave(torch.arange(rows.numel()), deg)
     cols, inv = torch.unique(col[idx], return_inverse=True)
     qs, ks, vs = q[rows].cpu().to(dtype), k[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
-    s = (qs[sub] * ks[inv]).sum(-1) * scale
+    kk, vv = ks[inv], vs[inv]
+    if edge is not None:
+        es = edge[idx.to(edge.device)].cpu().to(dtype)
+        kk, vv = kk + es, vv + es
+    s = (qs[sub] * kk).sum(-1) * scale
     if bias is not None:
         s = s + bias[idx.to(bias.device)].cpu().to(dtype)
     m = torch.full(qs.shape[:2], -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
@@ -151,7 +195,7 @@ def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None, mask=None
     alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
     if mask is not None:
         alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
-    return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vs[inv])
+    return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vv)
 
 
 def measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
@@ -340,6 +384,99 @@ def measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, de
         torch.cuda.empty_cache()
 
 
+def measure_edge(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
+    """--edge: dot_attention_edge against the chain of parts; one JSON object per shape, a shape or a contender that does not fit the
+    free device memory left out and named in the record."""
+    row = pattern.edge_rc[:, 0].long()
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        scale = 1.0 / math.sqrt(F)
+        e_bytes = E * H * F * 4
+        torch.cuda.empty_cache()
+        free = torch.cuda.mem_get_info(dev)[0]
+        # e, de and a margin for the fused op; the chain holds q[row], two products, their gradients and autograd's saved copies besides
+        need = {"fused_edge": 3 * e_bytes + (2 << 30), "composed_edge": 12 * e_bytes + (2 << 30)}
+        fits = [name for name in need if need[name] <= free]
+        res = {"bench": "dot_attention --edge", "device": torch.cuda.get_device_name(0),
+               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
+               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "e_bytes": e_bytes,
+               "free_device_bytes": free, "needed_device_bytes": need,
+               "skipped": {name: f"needs {need[name]} bytes of device memory, {free} are free" for name in need if name not in fits}}
+        if "fused_edge" not in fits:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(res) + "\n")
+            print(json.dumps(res), flush=True)
+            print(f"{shape}: skipped, e alone is {e_bytes / 1e9:.1f} GB and {free / 1e9:.1f} GB are free", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(2)
+        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
+        e = torch.randn(E, H, F, generator=g, device=dev)
+
+        def fused_edge(q_, k_, v_, e_):
+            return pg.dot_attention_edge(pattern, q_, k_, v_, e_, scale)
+
+        def composed_edge(q_, k_, v_, e_):
+            s = pg.edge_dot(pattern, q_, k_, scale) + scale * (q_[row] * e_).sum(-1)
+            alpha = pg.edge_softmax(pattern, s)
+            return pg.spmm(pattern, alpha, v_) + torch.zeros_like(q_).index_add(0, row, alpha[..., None] * e_)
+
+        fns = {"fused_edge": fused_edge, "composed_edge": composed_edge}
+
+        def forward_of(fn):
+            def run():
+                with torch.no_grad():
+                    return fn(q, k, v, e)
+            return run
+
+        def both_of(fn):
+            leaves = [t.detach().requires_grad_(True) for t in (q, k, v, e)]      # (fresh leaves on the same memory: no second e)
+
+            def run():
+                return torch.autograd.grad(fn(*leaves), leaves, G)
+            return run
+
+        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, edge=e)
+        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, edge=e)
+        res.update({"checked_rows": int(rows.numel()), "longest_checked_row": int(deg[rows].max()),
+                    "out_err_fp32_reference": parity.err(ref32, ref64)})
+        for name in list(fits):
+            try:                                                    # (the estimate above is one: what does not fit after all is left out too)
+                out = forward_of(fns[name])()
+                res[f"out_err_{name}"] = parity.close_fwd(out[rows.to(dev)], ref64, f"{shape} {name}: out", ref32)
+                del out
+                if not args.forward_only:
+                    both_of(fns[name])()
+            except torch.cuda.OutOfMemoryError as err:
+                fits.remove(name)
+                res["skipped"][name] = "out of device memory in a trial call: " + str(err).split("\n")[0]
+            torch.cuda.empty_cache()
+        if not fits:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(res) + "\n")
+            print(json.dumps(res), flush=True)
+            continue
+        perm = pattern.perm is not None
+        res.update({"fused_forward_bytes": fused_forward_bytes(E, N, N, H, F) + edge_forward_bytes(E, H, F, perm),
+                    "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F) + edge_backward_bytes(E, H, F, perm),
+                    "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F) + chain_edge_forward_bytes(E, N, H, F),
+                    "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F) + chain_edge_backward_bytes(E, N, H, F)})
+        legs = [("forward", alternate({name: forward_of(fns[name]) for name in fits}, args.rounds, args.steps, args.warmup))]
+        if not args.forward_only:
+            legs.append(("forward_backward", alternate({name: both_of(fns[name]) for name in fits}, args.rounds, args.steps,
+                                                       args.warmup)))
+        for what, r in legs:
+            for name in fits:
+                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+            if "composed_edge" in fits:
+                res[f"{what}_speedup"] = res[f"composed_edge_{what}_ms"] / res[f"fused_edge_{what}_ms"]
+        res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+        del q, k, v, G, e
+        torch.cuda.empty_cache()
+
+
 def measure(args):
     import torch
     if not torch.cuda.is_available():
@@ -365,6 +502,8 @@ def measure(args):
         return measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     if args.dropout:
         return measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
+    if args.edge:
+        return measure_edge(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
     for shape in args.shapes.split(","):
         H, F = (int(x) for x in shape.split("x"))
         scale = 1.0 / math.sqrt(F)
@@ -437,15 +576,19 @@ def main():
                     "against the fused forward on bfloat16 tables (forward only)")
     ap.add_argument("--dropout", action="store_true", help="measure seeded attention dropout at p = 0.5: fused with dropout, fused "
                     "without, the composition with the mask as a tensor")
+    ap.add_argument("--edge", action="store_true", help="measure dot_attention_edge, per-entry key and value features: the fused op "
+                    "against the chain of parts; a shape or contender that does not fit the free device memory is skipped")
     ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl; profiles/dot_attention_bias_bench.jsonl with --bias, "
-                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16, profiles/dot_attention_dropout_bench.jsonl with --dropout")
+                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16, profiles/dot_attention_dropout_bench.jsonl with --dropout, "
+                    "profiles/dot_attention_edge_bench.jsonl with --edge")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.bias + args.kv_bf16 + args.dropout > 1:
-        ap.error("--bias, --kv-bf16 and --dropout are separate measurements")
+    if args.bias + args.kv_bf16 + args.dropout + args.edge > 1:
+        ap.error("--bias, --kv-bf16, --dropout and --edge are separate measurements")
     if args.out is None:
         name = ("dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bf16_bench.jsonl" if args.kv_bf16 else
-                "dot_attention_dropout_bench.jsonl" if args.dropout else "dot_attention_bench.jsonl")
+                "dot_attention_dropout_bench.jsonl" if args.dropout else "dot_attention_edge_bench.jsonl" if args.edge else
+                "dot_attention_bench.jsonl")
         args.out = os.path.join(ROOT, "profiles", name)
     if args.child:
         return measure(args)
