@@ -34,13 +34,6 @@ int footprint_k16(const char* name, int* regs, int* scratch);
 int footprint_k17(const char* name, int* regs, int* scratch);
 int footprint_k18(const char* name, int* regs, int* scratch);
 int footprint_k19(const char* name, int* regs, int* scratch);
-int footprint_k19b(const char* name, int* regs, int* scratch);
-int footprint_k19h(const char* name, int* regs, int* scratch);
-int footprint_k19hb(const char* name, int* regs, int* scratch);
-int footprint_k19d(const char* name, int* regs, int* scratch);
-int footprint_k19db(const char* name, int* regs, int* scratch);
-int footprint_k19e(const char* name, int* regs, int* scratch);
-int footprint_k19eb(const char* name, int* regs, int* scratch);
 }  // namespace pygat
 
 extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* scratch_bytes) {
@@ -58,14 +51,7 @@ extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* sc
   if (!strncmp(kernel, "k16_", 4)) return pygat::footprint_k16(kernel, num_regs, scratch_bytes);
   if (!strncmp(kernel, "k17_", 4)) return pygat::footprint_k17(kernel, num_regs, scratch_bytes);
   if (!strncmp(kernel, "k18_", 4)) return pygat::footprint_k18(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19_", 4)) return pygat::footprint_k19(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19b_", 5)) return pygat::footprint_k19b(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19h_", 5)) return pygat::footprint_k19h(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19hb_", 6)) return pygat::footprint_k19hb(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19d_", 5)) return pygat::footprint_k19d(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19db_", 6)) return pygat::footprint_k19db(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19e_", 5)) return pygat::footprint_k19e(kernel, num_regs, scratch_bytes);
-  if (!strncmp(kernel, "k19eb_", 6)) return pygat::footprint_k19eb(kernel, num_regs, scratch_bytes);
+  if (!strncmp(kernel, "k19", 3)) return pygat::footprint_k19(kernel, num_regs, scratch_bytes);      // (every variant's prefix)
   pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw, k1_x3_tail, k14_rows_long, "
                    "k14_cols_long, k14_rows_wave, k14_cols_wave, k14_apply)", kernel);
   return PYGAT_EINVAL;

@@ -1,60 +1,72 @@
-// K19 -- dot_attention: softmax_j(scale q_i . k_j)-weighted sums of v_j over the entries of every row of a sparse pattern, for H heads
-// at once, in one pass, and the row side of its gradient.
-//   forward        s[e, h] = scale <q[i, h], k[j, h]>,  out[i, h] = sum_{e = (i, j)} softmax_row(s)[e, h] v[j, h];  m, Z [n_rows x H] = the
-//                  row's maximum and sum of exp(s - m): with out, all the backward keeps -- nothing per entry
-//   backward_rows  D[i, h] = <G[i, h], out[i, h]>,  p = exp(s - m[i, h]) / Z[i, h],  ds = scale p (<G[i, h], v[j, h]> - D[i, h]),
-//                  dq[i, h] = sum_e ds k[j, h];  P[e, h] = p and S[e, h] = ds at the CALLER's entry index (perm), for the column side:
-//                  dk = spmm^T(S, q), dv = spmm^T(P, G) are two pygat_spmm_forward launches on the transposed pattern (K17, unchanged)
-// Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  Lane mapping as K17's CW = 4 path: a group of LPR
-// lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v.  F / 4 is a power of two, so the chunks of
-// a head sit on LH = F / 4 adjacent lanes of one v, and a head's dot product is a butterfly over them; every lane of a head ends with the
-// same s, m and Z.  q_i is loaded once per row.  Per entry k_j and v_j are gathered, several entries in flight (da_unroll), and folded
-// into an online (m, Z, acc) state per head with one __expf per (entry, head) (K18's es_fold).  A long row goes through partial
-// records (the rule of long_rows.h), one wave per chunk: its lane groups walk the piece entry-interleaved and are merged maximum
-// first -- rescale once, then a fixed butterfly -- and records merge in chunk order by the same rule.  A record is (acc[H F], m[H],
-// Z[H]) forward and the dq row backward.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.  A row
-// without entries gets out = m = Z = dq = 0 exactly; a row of one entry (i, j) gets out_i = v_j bit for bit, p = 1 and ds = dq_i = 0.
-// BIAS (a compile-time flag of the four kernels; pygat_dot_attn_bias_*): s[e, h] + bias[c(e), h] is what the softmax runs over, c(e)
-// the CALLER's entry index (perm), the bias [nnz x H] or [nnz] (a head stride of 0).  One more 4-byte load per (entry, head) and walk,
-// prefetched a batch ahead like the column indices; the backward also forms T = p (<G_i, v_j> - D_i), the gradient of the bias, beside
-// ds and stores it where it is asked for.  m and Z are those of the biased scores.  A bias of zeros changes no bit of out, dq, P or S; a
-// large negative finite bias (-9e15) gives p = 0 exactly while the row keeps another entry.  A row of one entry still gets out_i = v_j
-// and ds = T = dq_i = 0 exactly, p = 1 to rounding.
-// bf16 tables (a table-type parameter T of the two forward kernels; pygat_dot_attn_bf16_forward, inference only): k and v are rows of
-// H*F bf16 values.  The lane mapping is the fp32 one -- a lane's chunk is still 4 consecutive row elements, now one 8-byte load, widened
-// in registers (a bf16 is the high half of an fp32) -- and everything after the load sees the fp32 kernels' values in their order, so the
-// result is that of the fp32 kernels on the widened tables bit for bit.  Those instantiations write neither m nor Z (nothing reads them).
-// DROP (a compile-time flag of the four fp32 kernels, beside BIAS; pygat_dot_attn_dropout_*): seeded dropout of the coefficients,
-// out[i, h] = sum_e alpha[e, h] mask[c(e), h] v[j, h] with mask in {0, 1 / (1 - p)}, drawn in registers in the forward and again in the
-// backward: no mask tensor exists.  mask[c, h] is element c H + h of the flat layout of k7_dropout.hip's mask kernel (rng.h): word
-// (idx & 3) of Philox-4x32-10(counter = (idx >> 2 low, idx >> 2 high, stream_id, 0xFFFFFFFF), key = *seed) < thresh keeps, so
-// pygat_dropout_mask(nnz H, p, seed, stream_id) writes the same table.  The entry index is the one the BIAS path already carries a
-// batch ahead; the LH lanes of a head, which would draw the same word, share a batch's entries among them and exchange the decisions
-// (da_keep_batch): ceil(U / LH) Philox calls per (batch, chunk) and lane, one per entry in the remainder loop.  m and Z are the
-// undropped softmax's -- a dropped entry stays in the denominator -- and only (p mask) v goes into acc; record merges and long-row
-// pieces are as without DROP.  Backward: D = <G_i, out_i> as before (out is the dropped sum), ds = scale p (mask <G_i, v_j> - D),
-// T = p (mask <G_i, v_j> - D), and P := p mask, so dv = spmm^T(P, G) needs no change.  A row of one entry gets out_i = mask v_j bit for
-// bit; a row whose entries are all dropped, and every row under p = 1, exact zeros.  The instruction streams of the kernels without
-// DROP are what they were before the flag.
-// EDGE (a compile-time flag of the four fp32 kernels, beside BIAS, never with DROP or bf16 tables; pygat_dot_attn_edge_*): a row of H*F
-// floats per entry on both sides, s[e, h] = scale <q[i, h], k[j, h] + e[c(e), h]> (+ bias) and out[i, h] = sum_e alpha[e, h] (v[j, h] +
-// e[c(e), h]), c(e) the CALLER's entry index, carried a batch ahead as under BIAS.  A lane's chunk of the e row is the 4 elements of its
-// chunk of k and v, one more 16-byte load per (entry, chunk), asked for with the gather of its batch.  kk = k_j + e and vv = v_j + e are
-// one rounded add per element, formed the same way in both passes; everything after sees kk and vv where it saw k_j and v_j, so e = 0
-// leaves out, dq, P and S at the values of the kernels without EDGE.  Backward: dp = <G_i, vv>, dq_i += ds kk, and the gradient of e is
-// row-local, de[c(e)] = ds q_i + p G_i, a 16-byte store per lane and entry where de is asked for: an entry belongs to one row (in a
-// long row to one piece), so every row of de is written exactly once and nothing is zeroed.  Records and the workspace are unchanged.
-// A row of one entry (i, j) gets out_i = v_j + e_c and de_c = G_i bit for bit.  The instruction streams of the kernels without EDGE
-// are what they were before the flag.
+// K19 -- dot_attention: softmax-weighted sums of value rows over the entries of every row of a sparse pattern, for H heads at once, in
+// one pass, and the row side of its gradient.  One kernel family: four kernels (forward | backward) x (long | row), instantiated per
+// lane shape and per variant, a set of compile-time flags (DA_BIAS, DA_DROP, DA_EDGE, DA_BF16).
+//
+// Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h:
+//   kk = k[j, h],  vv = v[j, h];                       EDGE: kk = k[j, h] + e[c, h], vv = v[j, h] + e[c, h], one rounded add per element,
+//                                                      formed the same way in both passes
+//   s = scale <q[i, h], kk>                            one rounding of the product, the same bits in both passes;  BIAS: the softmax runs
+//                                                      over s + bias[c, h] (bias [nnz x H], or [nnz] with a head stride of 0), taken as
+//                                                      s - (m - b): the bias goes to the maximum's side, so b = 0 is the plain expression
+//   p = exp(s - m[i, h]) / Z[i, h]                     m, Z [n_rows x H]: the row's maximum and sum of exp(s - m), of the biased scores
+//                                                      under BIAS and always of the undropped softmax
+//   out[i, h] = sum_e p vv                             DROP: sum_e p mask[c, h] vv, mask in {0, 1 / (1 - p)}: a dropped entry stays in Z
+//   backward_rows:  D = <G[i, h], out[i, h]>,  dp = <G[i, h], vv>  (DROP: mask dp),  ds = scale p (dp - D),  dq[i, h] = sum_e ds kk,
+//     P[c, h] = p (DROP: p mask) and S[c, h] = ds for the column side: dk = spmm^T(S, q) and dv = spmm^T(P, G) are two
+//     pygat_spmm_forward launches on the transposed pattern (K17);  BIAS: T = p (dp - D), the gradient of the bias, stored at [c, h]
+//     where it is asked for (ds stays the expression without a bias);  EDGE: de[c] = ds q[i] + p G[i], a 16-byte store per lane and
+//     entry where it is asked for -- an entry belongs to one row (in a long row to one piece), so every row of de is written exactly
+//     once and nothing is zeroed.
+//   The forward keeps out, m and Z, all the backward reads -- nothing per entry.  DROP draws its mask in registers in both passes, no
+//   mask tensor exists: mask[c, h] is element c H + h of the flat layout of k7_dropout.hip's mask kernel (rng.h): word (idx & 3) of
+//   Philox-4x32-10(counter = (idx >> 2 low, idx >> 2 high, stream_id, 0xFFFFFFFF), key = *seed) < thresh keeps, so
+//   pygat_dropout_mask(nnz H, p, seed, stream_id) writes the same table.  The LH lanes of a head share a batch's draws (da_keep_batch).
+//   BF16 (forward only, inference): k and v are rows of H*F bf16 values, a lane's chunk one 8-byte load widened in registers (a bf16
+//   is the high half of an fp32); everything after the load sees the fp32 kernels' values in their order.  Neither m nor Z is written.
+//   EDGE goes with neither DROP nor BF16, DROP not with BF16; BIAS goes with each.
+//
+// Lane mapping.  Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  As K17's CW = 4 path: a group of
+// LPR lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v.  F / 4 is a power of two, so the
+// chunks of a head sit on LH = F / 4 adjacent lanes of one v, and a head's dot product is a butterfly over them; every lane of a head
+// ends with the same s, m and Z.  q_i is loaded once per row.  Per entry k_j and v_j (and the e row) are gathered, several entries in
+// flight (da_unroll), the indices and bias values of the next batch asked for under this batch's arithmetic (da_walk), and folded
+// into an online (m, Z, acc) state per head with one __expf per (entry, head) (da_fold; K18's es_fold).
+//
+// Long rows go through partial records (the rule of long_rows.h), one wave per chunk: its lane groups walk the piece
+// entry-interleaved and are merged maximum first -- rescale once, then a fixed butterfly -- and records merge in chunk order by the
+// same rule.  A record is (acc[H F], m[H], Z[H]) forward and the dq row backward, whatever the variant.
+//
+// Exactness.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.
+//   a row without entries   out = m = Z = dq = 0 exactly
+//   a row of one entry      out_i = v_j bit for bit, p = 1 and ds = dq_i = 0;  BIAS: the same, T = 0, p = 1 to rounding;  DROP: out_i =
+//                           mask v_j bit for bit;  EDGE: out_i = v_j + e_c and de_c = G_i bit for bit
+//   a bias of zeros         changes no bit of out, dq, P or S; a large negative finite bias (-9e15) gives p = 0 exactly while the row
+//                           keeps another entry
+//   e = 0                   leaves out, dq, P and S at the values of the kernels without EDGE
+//   all entries dropped     (and every row under p = 1) exact zeros
+//   bf16 tables             the result of the fp32 kernels on the widened tables bit for bit
+// A flag that is off leaves no trace in a kernel: the instantiations without it are instruction for instruction what they would be
+// if the flag did not exist (profiles/k19_refactor_isa.txt).
 #include "long_rows.h"
 #include "rng.h"
 #include <float.h>
 #include <string.h>
+#include <type_traits>
 
 namespace pygat {
 
 constexpr int DA_MAX_ROW = 1024;               // floats per row, H * F
 constexpr float DA_SEED = -FLT_MAX;            // running-max seed: finite, so no difference of two maxima is a NaN
+
+// a variant: the set of its flags, the template parameter V of everything below that depends on one
+enum : unsigned { DA_BIAS = 1, DA_DROP = 2, DA_EDGE = 4, DA_BF16 = 8 };
+constexpr bool da_has(unsigned v, unsigned flag) { return (v & flag) != 0; }
+// the caller's entry index c(e) travels with the walk
+constexpr bool da_eid_walk(unsigned v) { return da_has(v, DA_BIAS | DA_DROP | DA_EDGE); }
+// the kernels that exist: bf16 tables are for inference (no dropout, no backward), per-entry rows go with fp32 tables and no dropout
+constexpr bool da_exists(unsigned v, bool bwd) {
+  return v < 16 && !(da_has(v, DA_EDGE) && da_has(v, DA_DROP | DA_BF16)) && !(da_has(v, DA_BF16) && (bwd || da_has(v, DA_DROP)));
+}
 
 struct DaArgs {
   int n, H, F, NCH, LH;        // rows of the walked pattern; heads; width of a head; chunks of 4 floats per row; lanes per head
@@ -240,50 +252,19 @@ __device__ __forceinline__ void da_keep_batch(const DaArgs& g, const DaLane<VEC>
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------------------ forward
-template <int VEC>
-struct DaState {
-  float m[VEC], z[VEC];
-  float4 acc[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ void da_init(DaState<VEC>& st) {
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) { st.m[v] = DA_SEED; st.z[v] = 0.f; st.acc[v] = da_zero4(); }
-}
-
-// online softmax state of one head and the lane's part of its weighted sum, one __expf per (entry, head) (K18's es_fold)
-__device__ __forceinline__ void da_fold(float& m, float& z, float4& acc, float s, const float4& w) {
-  const float d = s - m;
-  const float ex = __expf(-fabsf(d));
-  const bool up = d > 0.f;
-  const float r = up ? ex : 1.f, p = up ? 1.f : ex;
-  z = fmaf(z, r, p);
-  acc.x = fmaf(acc.x, r, p * w.x); acc.y = fmaf(acc.y, r, p * w.y); acc.z = fmaf(acc.z, r, p * w.z); acc.w = fmaf(acc.w, r, p * w.w);
-  m = up ? s : m;
-}
-
-// BIAS: the same fold of the score s + b.  The bias goes to the maximum's side of the difference, (s) - (m - b), and leaves the
-// expression s - m of da_fold as it is: under b = 0 both compile to the same operations on the same values (m - 0 is m), whether or
-// not the compiler contracts the product inside s into that difference -- it does -- so a bias of zeros changes no bit
-__device__ __forceinline__ void da_fold_b(float& m, float& z, float4& acc, float s, float b, const float4& w) {
-  const float d = s - (m - b);
-  const float ex = __expf(-fabsf(d));
-  const bool up = d > 0.f;
-  const float r = up ? ex : 1.f, p = up ? 1.f : ex;
-  z = fmaf(z, r, p);
-  acc.x = fmaf(acc.x, r, p * w.x); acc.y = fmaf(acc.y, r, p * w.y); acc.z = fmaf(acc.z, r, p * w.z); acc.w = fmaf(acc.w, r, p * w.w);
-  m = up ? __fadd_rn(s, b) : m;
-}
-
-// DROP: the fold of da_fold (da_fold_b under BIAS) with (p keep) v into acc; z takes p whole: a dropped entry stays in the denominator
-template <bool BIAS>
-__device__ __forceinline__ void da_fold_drop(float& m, float& z, float4& acc, float s, float b, float keep, const float4& w) {
+// ----------------------------------------------------------------------------------------------------------- the fold and the walk
+// online softmax state of one head and the lane's part of its weighted sum, one __expf per (entry, head) (K18's es_fold).
+// BIAS: the fold of the score s + b.  The bias goes to the maximum's side of the difference, (s) - (m - b), and leaves the expression
+// s - m as it is: under b = 0 both compile to the same operations on the same values (m - 0 is m), whether or not the compiler
+// contracts the product inside s into that difference -- it does -- so a bias of zeros changes no bit.
+// DROP: (p keep) v goes into acc; z takes p whole: a dropped entry stays in the denominator.  (b, keep: 0 and 1 without the flag)
+template <bool BIAS, bool DROP>
+__device__ __forceinline__ void da_fold(float& m, float& z, float4& acc, float s, float b, float keep, const float4& w) {
   const float d = BIAS ? s - (m - b) : s - m;
   const float ex = __expf(-fabsf(d));
   const bool up = d > 0.f;
   const float r = up ? ex : 1.f, p = up ? 1.f : ex;
-  const float pk = p * keep;
+  const float pk = DROP ? p * keep : p;
   z = fmaf(z, r, p);
   acc.x = fmaf(acc.x, r, pk * w.x); acc.y = fmaf(acc.y, r, pk * w.y); acc.z = fmaf(acc.z, r, pk * w.z); acc.w = fmaf(acc.w, r, pk * w.w);
   m = up ? (BIAS ? __fadd_rn(s, b) : s) : m;
@@ -337,41 +318,34 @@ __device__ __forceinline__ void da_edge_add(DaRows<VEC, U>& w, const DaEdgeRows<
     for (int v = 0; v < VEC; ++v) { da_add_rn(w.k[u][v], we.e[u][v]); da_add_rn(w.v[u][v], we.e[u][v]); }
 }
 
-// eid (BIAS | DROP) and key (DROP): the caller's entry indices of the batch and the key of its draws
-template <int LPR, int VEC, int U, bool BIAS, bool DROP>
-__device__ __forceinline__ void da_fwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], const DaRows<VEC, U>& w,
-                                            const DaBias<VEC, U, BIAS>& bs, const int32_t (&eid)[U], uint2 key, DaState<VEC>& st) {
-  [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
-  if constexpr (DROP) {
-    int64_t base[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) base[u] = (int64_t)eid[u] * g.H;
-    da_keep_batch<VEC, U>(g, ln, key, base, keep);
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      if constexpr (DROP)
-        da_fold_drop<BIAS>(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), BIAS ? bs.b[u][v] : 0.f,
-                           keep[u][v], w.v[u][v]);
-      else if constexpr (BIAS) da_fold_b(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), bs.b[u][v], w.v[u][v]);
-      else da_fold(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), w.v[u][v]);
-    }
-}
+// the caller's entry index (x H) of CSR position pos, as the backward without a flag forms it: with the load, no word carried
+__device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { return (g.perm ? (int64_t)g.perm[pos] : pos) * g.H; }
 
-// the entries e0, e0 + step, ... < e1 of one row, folded in that order, U at a time: the column indices of the next U are asked for
-// before this batch's rows are used, so an iteration waits for one gather, not for an index and then a gather.  BIAS: the next
-// batch's entry indices travel with its column indices, and its bias values are asked for once this batch is folded -- ahead of the
-// next gather, so they are there when it is -- an iteration still waits for one gather.  DROP: the entry indices travel the same way,
-// with or without a bias.  EDGE: the same entry indices place the batch's e rows, asked for right behind its gather
-template <int LPR, int VEC, int U, bool BIAS, typename T, bool DROP, bool EDGE = false>
-__device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const float4 (&q)[VEC], int64_t e0, int64_t e1,
-                                            int64_t step, uint2 key, DaState<VEC>& st) {
-  constexpr bool EID = BIAS || DROP || EDGE;
+// The walk of both passes: the entries e0, e0 + step, ... < e1 of one row, handed to Fold::fold in that order, U at a time and then one
+// at a time.  w: the gathered k and v rows (kk and vv under EDGE); bs: the bias values; eid: the caller's entry indices (where the
+// variant carries them, da_eid_walk); ent: eid x H (BWD); key (DROP): the key of the row's draws; ctx: what the pass keeps of its row,
+// handed through; U = da_unroll.  Fold is DaFwdFold or DaBwdFold, a type and not a closure, key travels by value, and the kernels
+// call da_walk themselves: a closure, a key behind a reference or one more function between a kernel and its walk all gave the same
+// instructions in another order.
+// The order of the loads is the kernels' speed.  The column indices of the next U entries are asked for before this batch's rows are
+// used, so an iteration waits for one gather, not for an index and then a gather.  Where the variant carries entry indices, the next
+// batch's travel with its column indices as loaded words (da_eid_raw) and become indices only after this batch's fold; BIAS: the
+// next batch's bias values are asked for then, ahead of the next gather, so they are there when it is -- an iteration still waits for
+// one gather.  EDGE: the same entry indices place the batch's e rows, asked for right behind its gather, and its rows of de.
+// The backward without a flag needs the entry index only for its stores and forms it whole (da_entry) a batch ahead.
+// One at a time, the backward forms what it needs where it needs it: ent by da_entry, eid ahead of the bias load (BIAS) and again
+// behind the gather (EDGE); one index for all of them is fewer instructions, and changes those of every flagged backward kernel.
+// lone (the backward row kernel under EDGE says so; a piece of a long row never is): the walk is over a row of one entry
+template <int VEC, unsigned V, bool BWD, typename Fold, typename... Ctx>
+__device__ __forceinline__ void da_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool lone,
+                                        uint2 key, Ctx&... ctx) {
+  constexpr int U = da_unroll(BWD, VEC);
+  constexpr bool BIAS = da_has(V, DA_BIAS), EDGE = da_has(V, DA_EDGE), EID = da_eid_walk(V);
+  using T = std::conditional_t<da_has(V, DA_BF16), da_bf16, float>;      // the element type of the k and v tables
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
+    [[maybe_unused]] int64_t ent[U], ent_next[U];
     [[maybe_unused]] int32_t raw[U], eid[U];
     DaBias<VEC, U, BIAS> bs;
     bool full = e + (U - 1) * step < e1;
@@ -380,6 +354,7 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
       for (int u = 0; u < U; ++u) {
         src[u] = g.col[e + u * step];
         if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
+        else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
       }
       if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
       if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
@@ -389,6 +364,10 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
       da_gather<VEC, U, T>(g, ln, src, w);
       [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
       if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
+      if constexpr (BWD && !EID) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+      }
       e += U * step;
       full = e + (U - 1) * step < e1;
       if (full) {
@@ -396,10 +375,15 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
           if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
+          else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
         }
       }
+      if constexpr (BWD && EID) {                                  // (eid: this batch's, formed after the last fold, not yet replaced)
+#pragma unroll
+        for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
+      }
       if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
-      da_fwd_fold<LPR, VEC, U, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);    // (eid: this batch's, not yet replaced)
+      Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, false);
       if constexpr (EID)
         if (full) {
           da_eids<U>(g, raw, e, step, eid);
@@ -409,28 +393,66 @@ __device__ __forceinline__ void da_fwd_walk(const DaArgs& g, const DaLane<VEC>& 
   }
   for (; e < e1; e += step) {
     const int32_t src[1] = {g.col[e]};
-    DaBias<VEC, 1, BIAS> bs;
+    [[maybe_unused]] int64_t ent[1] = {0};
     [[maybe_unused]] int32_t eid[1] = {0};
-    if constexpr (EID) eid[0] = da_eid(g, da_eid_raw(g, e), e);
+    if constexpr (BWD) ent[0] = da_entry(g, e);
+    if constexpr (BWD ? BIAS : EID) eid[0] = da_eid(g, da_eid_raw(g, e), e);
+    DaBias<VEC, 1, BIAS> bs;
     if constexpr (BIAS) da_bias_load<VEC, 1>(g, ln, eid, bs);
     DaRows<VEC, 1> w;
     da_gather<VEC, 1, T>(g, ln, src, w);
     if constexpr (EDGE) {
+      if constexpr (BWD) eid[0] = da_eid(g, da_eid_raw(g, e), e);
       DaEdgeRows<VEC, 1, true> we;
       da_gather_edge<VEC, 1>(g, ln, eid, we);
       da_edge_add<VEC, 1>(w, we);
     }
-    da_fwd_fold<LPR, VEC, 1, BIAS, DROP>(g, ln, q, w, bs, eid, key, st);
+    Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, lone);
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------ forward
+template <int VEC>
+struct DaState {
+  float m[VEC], z[VEC];
+  float4 acc[VEC];
+};
+template <int VEC>
+__device__ __forceinline__ void da_init(DaState<VEC>& st) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) { st.m[v] = DA_SEED; st.z[v] = 0.f; st.acc[v] = da_zero4(); }
+}
+
+// the forward's fold of a batch; ctx: q_i and the row's state.  eid is looked at under DROP alone, ent and lone not at all
+template <int LPR, int VEC, unsigned V>
+struct DaFwdFold {
+  template <int U>
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, uint2 key, const float4 (&q)[VEC],
+                                              DaState<VEC>& st, const DaRows<VEC, U>& w, const int64_t (&)[U],
+                                              const DaBias<VEC, U, da_has(V, DA_BIAS)>& bs, const int32_t (&eid)[U], bool) {
+    constexpr bool BIAS = da_has(V, DA_BIAS), DROP = da_has(V, DA_DROP);
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) {
+      int64_t base[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) base[u] = (int64_t)eid[u] * g.H;
+      da_keep_batch<VEC, U>(g, ln, key, base, keep);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        da_fold<BIAS, DROP>(st.m[v], st.z[v], st.acc[v], da_score<LPR>(g, q[v], w.k[u][v]), BIAS ? bs.b[u][v] : 0.f,
+                            DROP ? keep[u][v] : 1.f, w.v[u][v]);
+  }
+};
+
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
+template <int LPR, int VEC, unsigned V>
 __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
-  static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
-  static_assert(!EDGE || (!DROP && sizeof(T) == sizeof(float)), "per-entry rows: fp32 tables, no dropout");
+  static_assert(da_exists(V, false), "no dropout on bf16 tables (they are for inference); per-entry rows: fp32 tables, no dropout");
   constexpr int EPW = 64 / LPR;
-  const uint2 key = da_key<DROP>(g);
+  const uint2 key = da_key<da_has(V, DA_DROP)>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
@@ -441,7 +463,7 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
     DaState<VEC> st;
     da_init<VEC>(st);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP, EDGE>(g, ln, q, e0 + grp, e1, EPW, key, st);
+    da_walk<VEC, V, false, DaFwdFold<LPR, VEC, V>>(g, ln, e0 + grp, e1, EPW, false, key, q, st);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
       float mx = st.m[v];
@@ -468,11 +490,10 @@ __global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row.  m and Z are what a backward reads: the bf16-table kernels, which have none, do not write them
-template <int LPR, int VEC, bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
+template <int LPR, int VEC, unsigned V>
 __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
-  static_assert(!DROP || sizeof(T) == sizeof(float), "no dropout on bf16 tables: they are for inference");
-  static_assert(!EDGE || (!DROP && sizeof(T) == sizeof(float)), "per-entry rows: fp32 tables, no dropout");
-  constexpr bool KEEP_MZ = sizeof(T) == sizeof(float);
+  static_assert(da_exists(V, false), "no dropout on bf16 tables (they are for inference); per-entry rows: fp32 tables, no dropout");
+  constexpr bool KEEP_MZ = !da_has(V, DA_BF16);
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
@@ -492,7 +513,7 @@ __global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
   } else if (end > start) {
     float4 q[VEC];
     da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_fwd_walk<LPR, VEC, da_unroll(false, VEC), BIAS, T, DROP, EDGE>(g, ln, q, start, end, 1, da_key<DROP>(g), st);
+    da_walk<VEC, V, false, DaFwdFold<LPR, VEC, V>>(g, ln, start, end, 1, false, da_key<da_has(V, DA_DROP)>(g), q, st);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
@@ -530,9 +551,7 @@ __device__ __forceinline__ void da_bwd_load(const DaArgs& g, const DaLane<VEC>& 
   }
 }
 
-// the caller's entry index (x H) of CSR position pos
-__device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { return (g.perm ? (int64_t)g.perm[pos] : pos) * g.H; }
-
+// the backward's fold of a batch; ctx: the row (DaRow) and its dq
 // BIAS: T = p (<G_i, v_j> - D_i), the gradient of the bias, formed beside ds -- ds itself is the unbiased kernel's expression, so a
 // bias of zeros leaves the bits of S, dq and dk alone -- and stored where it is asked for
 // DROP: the batch's keep factors are drawn again (ent[u] + head is an entry's flat mask index); an entry's multiplies <G_i, v_j> --
@@ -542,129 +561,55 @@ __device__ __forceinline__ int64_t da_entry(const DaArgs& g, int64_t pos) { retu
 // entry indices, looked at under EDGE alone).  lone (EDGE alone): the entry is the only one of its row, whose coefficient is 1 by
 // definition and goes into de as that, so de_c = G_i bit for bit: the p formed here is exp(scale <q, kk> - m) with the product
 // contracted into the difference, m the rounded product, and may come out an ulp above 1 where the scale is no power of two
-template <int LPR, int VEC, int U, bool BIAS, bool DROP, bool EDGE = false>
-__device__ __forceinline__ void da_bwd_fold(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, const DaRows<VEC, U>& w,
-                                            const int64_t (&ent)[U], const DaBias<VEC, U, BIAS>& bs, uint2 key, float4 (&dq)[VEC],
-                                            [[maybe_unused]] const int32_t (&eid)[U], [[maybe_unused]] bool lone = false) {
-  [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
-  if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
+template <int LPR, int VEC, unsigned V>
+struct DaBwdFold {
+  template <int U>
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, uint2 key, const DaRow<VEC>& r,
+                                              float4 (&dq)[VEC], const DaRows<VEC, U>& w, const int64_t (&ent)[U],
+                                              const DaBias<VEC, U, da_has(V, DA_BIAS)>& bs, [[maybe_unused]] const int32_t (&eid)[U],
+                                              [[maybe_unused]] bool lone) {
+    constexpr bool BIAS = da_has(V, DA_BIAS), DROP = da_has(V, DA_DROP), EDGE = da_has(V, DA_EDGE);
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
-  for (int u = 0; u < U; ++u)
+    for (int u = 0; u < U; ++u)
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const float s = da_score<LPR>(g, r.q[v], w.k[u][v]);
-      float p;
-      if constexpr (BIAS) p = __expf(s - (r.m[v] - bs.b[u][v])) * r.rz[v];      // (as da_fold_b: s - m with the bias on m's side)
-      else p = __expf(s - r.m[v]) * r.rz[v];
-      float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
-      float pk = p;
-      if constexpr (DROP) {
-        dp *= keep[u][v];
-        pk *= keep[u][v];
-      }
-      const float ds = g.scale * p * (dp - r.D[v]);
-      da_axpy(dq[v], ds, w.k[u][v]);
-      if (ln.lead >> v & 1) {
-        g.P[ent[u] + ln.head[v]] = pk;
-        g.S[ent[u] + ln.head[v]] = ds;
-        if constexpr (BIAS)
-          if (g.dbias) g.dbias[ent[u] + ln.head[v]] = p * (dp - r.D[v]);
-      }
-      if constexpr (EDGE)
-        if (g.de && (ln.ok >> v & 1)) {
-          const float4 &qi = r.q[v], &Gi = r.G[v];
-          const float pe = lone ? 1.f : p;
-          st4(g.de + (int64_t)eid[u] * g.ldde + ln.ofs[v],
-              make_float4(fmaf(ds, qi.x, pe * Gi.x), fmaf(ds, qi.y, pe * Gi.y), fmaf(ds, qi.z, pe * Gi.z), fmaf(ds, qi.w, pe * Gi.w)));
+      for (int v = 0; v < VEC; ++v) {
+        const float s = da_score<LPR>(g, r.q[v], w.k[u][v]);
+        float p;
+        if constexpr (BIAS) p = __expf(s - (r.m[v] - bs.b[u][v])) * r.rz[v];      // (as da_fold: s - m with the bias on m's side)
+        else p = __expf(s - r.m[v]) * r.rz[v];
+        float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+        float pk = p;
+        if constexpr (DROP) {
+          dp *= keep[u][v];
+          pk *= keep[u][v];
         }
-    }
-}
-
-// as da_fwd_walk: the next batch's column and entry indices are in flight under this batch's arithmetic; BIAS: its bias values are
-// asked for once this batch is folded, ahead of the next gather; DROP: the entry indices travel as under BIAS, with or without one;
-// EDGE: they also place the batch's e rows, asked for right behind its gather, and its rows of de; lone: the walk is over a row of one
-// entry (the row kernel says so; a piece of a long row never is)
-template <int LPR, int VEC, int U, bool BIAS, bool DROP, bool EDGE = false>
-__device__ __forceinline__ void da_bwd_walk(const DaArgs& g, const DaLane<VEC>& ln, const DaRow<VEC>& r, int64_t e0, int64_t e1,
-                                            int64_t step, uint2 key, float4 (&dq)[VEC], [[maybe_unused]] bool lone = false) {
-  constexpr bool EID = BIAS || DROP || EDGE;
-  int64_t e = e0;
-  if constexpr (U > 1) {
-    int32_t src[U];
-    int64_t ent[U];
-    [[maybe_unused]] int64_t ent_next[U];
-    [[maybe_unused]] int32_t raw[U], eid[U];
-    DaBias<VEC, U, BIAS> bs;
-    bool full = e + (U - 1) * step < e1;
-    if (full) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        src[u] = g.col[e + u * step];
-        if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
-        else ent_next[u] = da_entry(g, e + u * step);
-      }
-      if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
-      if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
-    }
-    while (full) {
-      DaRows<VEC, U> w;
-      da_gather<VEC, U>(g, ln, src, w);
-      [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
-      if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
-      if constexpr (!EID) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
-      }
-      e += U * step;
-      full = e + (U - 1) * step < e1;
-      if (full) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          src[u] = g.col[e + u * step];
-          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
-          else ent_next[u] = da_entry(g, e + u * step);
+        const float ds = g.scale * p * (dp - r.D[v]);
+        da_axpy(dq[v], ds, w.k[u][v]);
+        if (ln.lead >> v & 1) {
+          g.P[ent[u] + ln.head[v]] = pk;
+          g.S[ent[u] + ln.head[v]] = ds;
+          if constexpr (BIAS)
+            if (g.dbias) g.dbias[ent[u] + ln.head[v]] = p * (dp - r.D[v]);
         }
+        if constexpr (EDGE)
+          if (g.de && (ln.ok >> v & 1)) {
+            const float4 &qi = r.q[v], &Gi = r.G[v];
+            const float pe = lone ? 1.f : p;
+            st4(g.de + (int64_t)eid[u] * g.ldde + ln.ofs[v],
+                make_float4(fmaf(ds, qi.x, pe * Gi.x), fmaf(ds, qi.y, pe * Gi.y), fmaf(ds, qi.z, pe * Gi.z), fmaf(ds, qi.w, pe * Gi.w)));
+          }
       }
-      if constexpr (EID) {                                       // (this batch's entry indices: formed after the last fold, not yet replaced)
-#pragma unroll
-        for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
-      }
-      if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
-      da_bwd_fold<LPR, VEC, U, BIAS, DROP, EDGE>(g, ln, r, w, ent, bs, key, dq, eid);
-      if constexpr (EID)
-        if (full) {
-          da_eids<U>(g, raw, e, step, eid);
-          if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
-        }
-    }
   }
-  for (; e < e1; e += step) {
-    const int32_t src[1] = {g.col[e]};
-    const int64_t ent[1] = {da_entry(g, e)};
-    DaBias<VEC, 1, BIAS> bs;
-    if constexpr (BIAS) {
-      const int32_t eid[1] = {da_eid(g, da_eid_raw(g, e), e)};
-      da_bias_load<VEC, 1>(g, ln, eid, bs);
-    }
-    DaRows<VEC, 1> w;
-    da_gather<VEC, 1>(g, ln, src, w);
-    [[maybe_unused]] int32_t eide[1] = {0};
-    if constexpr (EDGE) {
-      eide[0] = da_eid(g, da_eid_raw(g, e), e);
-      DaEdgeRows<VEC, 1, true> we;
-      da_gather_edge<VEC, 1>(g, ln, eide, we);
-      da_edge_add<VEC, 1>(w, we);
-    }
-    da_bwd_fold<LPR, VEC, 1, BIAS, DROP, EDGE>(g, ln, r, w, ent, bs, key, dq, eide, lone);
-  }
-}
+};
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
-template <int LPR, int VEC, bool BIAS, bool DROP = false, bool EDGE = false>
+template <int LPR, int VEC, unsigned V>
 __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
-  static_assert(!(EDGE && DROP), "per-entry rows: no dropout");
+  static_assert(da_exists(V, true), "no backward on bf16 tables; per-entry rows: no dropout");
   constexpr int EPW = 64 / LPR;
-  const uint2 key = da_key<DROP>(g);
+  const uint2 key = da_key<da_has(V, DA_DROP)>(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
@@ -675,7 +620,7 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
     float4 dq[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP, EDGE>(g, ln, r, e0 + grp, e1, EPW, key, dq);
+    da_walk<VEC, V, true, DaBwdFold<LPR, VEC, V>>(g, ln, e0 + grp, e1, EPW, false, key, r, dq);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
@@ -685,9 +630,9 @@ __global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC, bool BIAS, bool DROP = false, bool EDGE = false>
+template <int LPR, int VEC, unsigned V>
 __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
-  static_assert(!(EDGE && DROP), "per-entry rows: no dropout");
+  static_assert(da_exists(V, true), "no backward on bf16 tables; per-entry rows: no dropout");
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
@@ -706,8 +651,8 @@ __global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
   } else if (end > start) {                                    // (a row without entries: its G row is not read)
     DaRow<VEC> r;
     da_bwd_load<LPR, VEC>(g, ln, row, r);
-    da_bwd_walk<LPR, VEC, da_unroll(true, VEC), BIAS, DROP, EDGE>(g, ln, r, start, end, 1, da_key<DROP>(g), dq,
-                                                                            EDGE && end - start == 1);
+    da_walk<VEC, V, true, DaBwdFold<LPR, VEC, V>>(g, ln, start, end, 1, da_has(V, DA_EDGE) && end - start == 1,
+                                                  da_key<da_has(V, DA_DROP)>(g), r, dq);
   }
   da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
 }
@@ -741,66 +686,57 @@ static inline void da_pick(int H, int F, int* lpr, int* vec, int* nch) {
     else { constexpr int LPR = 64, VEC = 4; __VA_ARGS__; }                   \
   } while (0)
 
-template <bool BIAS, bool DROP = false, bool EDGE = false>
-static const void* da_kernel_ptr(bool bwd, bool lng, int lpr, int vec) {
-  const void* f = nullptr;
-  PYGAT_DA_DISPATCH(lpr, vec, f = bwd ? (lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, BIAS, DROP, EDGE>)
-                                             : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, BIAS, DROP, EDGE>))
-                                      : (lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, float, DROP, EDGE>)
-                                             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, float, DROP, EDGE>)));
-  return f;
+// the table of the family: (variant, forward | backward, long | row, lane shape) -> the kernel; null where there is none.  What a
+// launcher starts and what pygat_kernel_footprint reports on both come from here
+template <int LPR, int VEC, unsigned V>
+static const void* da_kernel_at(bool bwd, bool lng) {
+  if constexpr (da_exists(V, true)) {
+    if (bwd) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, V>)
+                        : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, V>);
+  } else if (bwd) return nullptr;
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, V>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, V>);
+}
+template <unsigned V>
+static const void* da_kernel_of(bool bwd, bool lng, int lpr, int vec) {
+  PYGAT_DA_DISPATCH(lpr, vec, return (da_kernel_at<LPR, VEC, V>(bwd, lng)));
+  return nullptr;
+}
+static const void* da_kernel(unsigned variant, bool bwd, bool lng, int lpr, int vec) {
+  switch (variant) {
+    case 0: return da_kernel_of<0>(bwd, lng, lpr, vec);
+    case DA_BIAS: return da_kernel_of<DA_BIAS>(bwd, lng, lpr, vec);
+    case DA_BF16: return da_kernel_of<DA_BF16>(bwd, lng, lpr, vec);
+    case DA_BF16 | DA_BIAS: return da_kernel_of<DA_BF16 | DA_BIAS>(bwd, lng, lpr, vec);
+    case DA_DROP: return da_kernel_of<DA_DROP>(bwd, lng, lpr, vec);
+    case DA_DROP | DA_BIAS: return da_kernel_of<DA_DROP | DA_BIAS>(bwd, lng, lpr, vec);
+    case DA_EDGE: return da_kernel_of<DA_EDGE>(bwd, lng, lpr, vec);
+    case DA_EDGE | DA_BIAS: return da_kernel_of<DA_EDGE | DA_BIAS>(bwd, lng, lpr, vec);
+  }
+  return nullptr;
 }
 
-// the bf16-table instantiations: the forward only
-template <bool BIAS>
-static const void* da_bf16_kernel_ptr(bool lng, int lpr, int vec) {
-  const void* f = nullptr;
-  PYGAT_DA_DISPATCH(lpr, vec, f = lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, BIAS, da_bf16>)
-                                      : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, BIAS, da_bf16>));
-  return f;
-}
-
-// pygat_kernel_footprint: k19_ | k19b_ (BIAS) {fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH), and the
-// bf16-table kernels k19h_ | k19hb_ (BIAS) fwd_{long,row}_l<LPR>v<VEC>; k19d_ | k19db_ (BIAS): the DROP instantiations of the first two;
-// k19e_ | k19eb_ (BIAS): their EDGE instantiations
-static int da_footprint(const char* name, const char* prefix, bool bias, bool bf16, int* regs, int* scratch, bool drop = false,
-                        bool edge = false) {
+// pygat_kernel_footprint: <prefix>{fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); the prefix names the
+// variant: k19_, k19b_ (BIAS), k19h_, k19hb_ (bf16 tables: fwd only), k19d_, k19db_ (DROP), k19e_, k19eb_ (EDGE)
+int footprint_k19(const char* name, int* regs, int* scratch) {
+  static const struct { const char* prefix; unsigned variant; } names[] = {
+      {"k19_", 0}, {"k19b_", DA_BIAS}, {"k19h_", DA_BF16}, {"k19hb_", DA_BF16 | DA_BIAS},
+      {"k19d_", DA_DROP}, {"k19db_", DA_DROP | DA_BIAS}, {"k19e_", DA_EDGE}, {"k19eb_", DA_EDGE | DA_BIAS}};
   const void* fn = nullptr;
-  char dir[8] = "", kind[8] = "", rest = 0;
-  int lpr = 0, vec = 0;
-  const size_t np = strlen(prefix);
-  if (!strncmp(name, prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
-      lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || (!bf16 && !strcmp(dir, "bwd"))) &&
-      (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4))) {
-    if (bf16)
-      fn = bias ? da_bf16_kernel_ptr<true>(!strcmp(kind, "long"), lpr, vec) : da_bf16_kernel_ptr<false>(!strcmp(kind, "long"), lpr, vec);
-    else if (edge)
-      fn = bias ? da_kernel_ptr<true, false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
-                : da_kernel_ptr<false, false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
-    else if (drop)
-      fn = bias ? da_kernel_ptr<true, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
-                : da_kernel_ptr<false, true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
-    else
-      fn = bias ? da_kernel_ptr<true>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec)
-                : da_kernel_ptr<false>(!strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
+  for (const auto& nm : names) {
+    char dir[8] = "", kind[8] = "", rest = 0;
+    int lpr = 0, vec = 0;
+    const size_t np = strlen(nm.prefix);
+    if (!strncmp(name, nm.prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
+        lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) &&
+        (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
+      fn = da_kernel(nm.variant, !strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
   }
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (%s{%s}_{long,row}_l<LPR>v<VEC>)", name, prefix, bf16 ? "fwd" : "fwd,bwd");
+    set_error("kernel_footprint: unknown kernel '%s' (k19{,b,h,hb,d,db,e,eb}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>; k19h*: fwd only)", name);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
-}
-int footprint_k19(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19_", false, false, regs, scratch); }
-int footprint_k19b(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19b_", true, false, regs, scratch); }
-int footprint_k19h(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19h_", false, true, regs, scratch); }
-int footprint_k19hb(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19hb_", true, true, regs, scratch); }
-int footprint_k19d(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19d_", false, false, regs, scratch, true); }
-int footprint_k19db(const char* name, int* regs, int* scratch) { return da_footprint(name, "k19db_", true, false, regs, scratch, true); }
-int footprint_k19e(const char* name, int* regs, int* scratch) {
-  return da_footprint(name, "k19e_", false, false, regs, scratch, false, true);
-}
-int footprint_k19eb(const char* name, int* regs, int* scratch) {
-  return da_footprint(name, "k19eb_", true, false, regs, scratch, false, true);
 }
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
@@ -845,15 +781,6 @@ static int da_check_common(const char* what, int n_rows, int64_t nnz, int H, int
   PYGAT_REQUIRE(ws, "%s: null workspace", what);
   PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
   return PYGAT_OK;
-}
-
-static void da_fill(DaArgs& g, int n_rows, int64_t nnz, int H, int F, const int32_t* rowptr, const int32_t* col, float scale,
-                    const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out, int64_t ldo,
-                    float* m, float* Z, void* ws) {
-  memset(&g, 0, sizeof(g));
-  g.n = n_rows; g.H = H; g.F = F; g.NCH = H * F / 4; g.LH = F / 4; g.nnz = nnz; g.rowptr = rowptr; g.col = col; g.scale = scale;
-  g.q = q; g.ldq = ldq; g.k = k; g.ldk = ldk; g.v = v; g.ldv = ldv; g.out = out; g.ldo = ldo; g.m = m; g.Z = Z;
-  g.part = static_cast<float*>(ws); g.pstride = da_pstride(H, F);
 }
 
 }  // namespace pygat
@@ -904,87 +831,87 @@ static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed
   return PYGAT_OK;
 }
 
-// T: the element type of k and v; da_bf16 is the inference forward, which keeps no m and Z.  DROP: drop names the mask.  EDGE: edge
-// names the per-entry rows
-template <bool BIAS, typename T = float, bool DROP = false, bool EDGE = false>
-static int da_forward(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
-                      int F, float scale, const float* q, int64_t ldq, const T* k, int64_t ldk, const T* v, int64_t ldv,
-                      const float* bias, int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream,
-                      const DaDrop* drop = nullptr, const DaEdge* edge = nullptr) {
-  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws, (int)sizeof(T),
-                           sizeof(T) == sizeof(float));
-  if (rc != PYGAT_OK) return rc;
-  if constexpr (EDGE) {
-    rc = da_check_edge(what, nnz, H * F, *edge);
-    if (rc != PYGAT_OK) return rc;
-  }
-  if constexpr (BIAS) {
-    rc = da_check_bias(what, nnz, bias, bias_head_stride);
-    if (rc != PYGAT_OK) return rc;
-  }
-  DropRng rng;
-  if constexpr (DROP) {
-    rc = da_check_drop(what, *drop, &rng);
-    if (rc != PYGAT_OK) return rc;
-  }
-  if (n_rows == 0) return PYGAT_OK;
-  DaArgs g;
-  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, reinterpret_cast<const float*>(k), ldk, reinterpret_cast<const float*>(v),
-          ldv, out, ldo, m, Z, ws);
-  if constexpr (BIAS) { g.perm = perm; g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; }
-  if constexpr (DROP) { g.perm = perm; g.rng = rng; }
-  if constexpr (EDGE) { g.perm = perm; g.e = edge->e; g.lde = edge->lde; }
-  int lpr, vec, nch;
-  da_pick(H, F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(nnz);
-  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
-  hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_long_kernel<LPR, VEC, BIAS, T, DROP, EDGE>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_fwd_row_kernel<LPR, VEC, BIAS, T, DROP, EDGE>), dim3(blocks), dim3(256), 0, st, g));
-  PYGAT_CHECK_LAUNCH(what);
-  return PYGAT_OK;
-}
+// what an entry point asks for: its name, the variant and the pass, and every argument under the name include/pygat_amd.h gives it.
+// k and v are float or bf16 rows by the variant; out, m and Z are written by the forward and read by the backward; what a variant or a
+// pass does not have stays zero
+struct DaCall {
+  const char* what;
+  unsigned variant;
+  bool bwd;
+  int n_rows;
+  int64_t nnz;
+  const int32_t *rowptr, *col, *perm;
+  int H, F;
+  float scale;
+  const float* q;
+  int64_t ldq;
+  const void *k, *v;
+  int64_t ldk, ldv;
+  float* out;
+  int64_t ldo;
+  float *m, *Z;
+  void *ws, *stream;
+  const float* bias;           // DA_BIAS
+  int bias_head_stride;
+  float* dbias;                // ... backward; null: not asked for
+  DaDrop drop;                 // DA_DROP
+  DaEdge edge;                 // DA_EDGE
+  const float* G;              // backward only from here
+  int64_t ldg;
+  float* dq;
+  int64_t lddq;
+  float *P, *S;
+};
+// the arguments all nine entry points have, from the entry point's own parameters
+#define DA_CALL(c, name, var, back)                                                                                                 \
+  DaCall c = {};                                                                                                                    \
+  c.what = name; c.variant = var; c.bwd = back; c.n_rows = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.H = H; c.F = F;  \
+  c.scale = scale; c.q = q; c.ldq = ldq; c.k = k; c.ldk = ldk; c.v = v; c.ldv = ldv; c.out = const_cast<float*>(out); c.ldo = ldo; \
+  c.ws = ws; c.stream = stream
+// ... and those of the backward's
+#define DA_CALL_BWD(c) \
+  c.perm = perm; c.m = const_cast<float*>(m); c.Z = const_cast<float*>(Z); c.G = G; c.ldg = ldg; c.dq = dq; c.lddq = lddq; c.P = P; c.S = S
+// a null bias at an entry point that takes one or none: the variant without BIAS; bias_head_stride is then not looked at
+static inline unsigned da_with_bias(unsigned variant, const float* bias) { return bias ? variant | DA_BIAS : variant; }
 
-template <bool BIAS, bool DROP = false, bool EDGE = false>
-static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
-                            int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
-                            int64_t ldv, const float* bias, int bias_head_stride, const float* out, int64_t ldo, const float* m,
-                            const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias,
-                            void* ws, void* stream, const DaDrop* drop = nullptr, const DaEdge* edge = nullptr) {
-  int rc = da_check_common(what, n_rows, nnz, H, F, rowptr, col, q, ldq, k, ldk, v, ldv, out, ldo, m, Z, ws);
+// every launcher: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
+static int da_launch(const DaCall& c) {
+  const char* what = c.what;
+  const bool bias = da_has(c.variant, DA_BIAS), drop = da_has(c.variant, DA_DROP), edge = da_has(c.variant, DA_EDGE),
+             bf16 = da_has(c.variant, DA_BF16);
+  const int HF = c.H * c.F;
+  int rc = da_check_common(what, c.n_rows, c.nnz, c.H, c.F, c.rowptr, c.col, c.q, c.ldq, c.k, c.ldk, c.v, c.ldv, c.out, c.ldo, c.m, c.Z,
+                           c.ws, bf16 ? 2 : 4, !bf16);
   if (rc != PYGAT_OK) return rc;
-  DA_TABLE(what, "G", G, ldg, H * F);
-  DA_TABLE(what, "dq", dq, lddq, H * F);
-  PYGAT_REQUIRE(nnz == 0 || P, "%s: null P", what);
-  PYGAT_REQUIRE(nnz == 0 || S, "%s: null S", what);
-  if constexpr (EDGE) {
-    rc = da_check_edge(what, nnz, H * F, *edge);
-    if (rc != PYGAT_OK) return rc;
+  if (c.bwd) {
+    DA_TABLE(what, "G", c.G, c.ldg, HF);
+    DA_TABLE(what, "dq", c.dq, c.lddq, HF);
+    PYGAT_REQUIRE(c.nnz == 0 || c.P, "%s: null P", what);
+    PYGAT_REQUIRE(c.nnz == 0 || c.S, "%s: null S", what);
   }
-  if constexpr (BIAS) {
-    rc = da_check_bias(what, nnz, bias, bias_head_stride);
-    if (rc != PYGAT_OK) return rc;
-  }
+  if (edge && (rc = da_check_edge(what, c.nnz, HF, c.edge)) != PYGAT_OK) return rc;
+  if (bias && (rc = da_check_bias(what, c.nnz, c.bias, c.bias_head_stride)) != PYGAT_OK) return rc;
   DropRng rng;
-  if constexpr (DROP) {
-    rc = da_check_drop(what, *drop, &rng);
-    if (rc != PYGAT_OK) return rc;
-  }
-  if (n_rows == 0) return PYGAT_OK;
+  if (drop && (rc = da_check_drop(what, c.drop, &rng)) != PYGAT_OK) return rc;
+  if (c.n_rows == 0) return PYGAT_OK;
   DaArgs g;
-  da_fill(g, n_rows, nnz, H, F, rowptr, col, scale, q, ldq, k, ldk, v, ldv, const_cast<float*>(out), ldo, const_cast<float*>(m),
-          const_cast<float*>(Z), ws);
-  g.perm = perm; g.G = G; g.ldg = ldg; g.dq = dq; g.lddq = lddq; g.P = P; g.S = S;
-  if constexpr (DROP) g.rng = rng;
-  if constexpr (EDGE) { g.e = edge->e; g.lde = edge->lde; g.de = edge->de; g.ldde = edge->ldde; }
-  if constexpr (BIAS) { g.bias = bias; g.bhs = bias_head_stride; g.bstride = bias_head_stride ? H : 1; g.dbias = dbias; }
+  memset(&g, 0, sizeof(g));
+  g.n = c.n_rows; g.H = c.H; g.F = c.F; g.NCH = HF / 4; g.LH = c.F / 4; g.nnz = c.nnz; g.rowptr = c.rowptr; g.col = c.col; g.scale = c.scale;
+  g.q = c.q; g.ldq = c.ldq; g.k = static_cast<const float*>(c.k); g.ldk = c.ldk; g.v = static_cast<const float*>(c.v); g.ldv = c.ldv;
+  g.out = c.out; g.ldo = c.ldo; g.m = c.m; g.Z = c.Z; g.part = static_cast<float*>(c.ws); g.pstride = da_pstride(c.H, c.F);
+  if (c.bwd || da_eid_walk(c.variant)) g.perm = c.perm;           // (the forward without a flag walks in CSR order alone)
+  if (c.bwd) { g.G = c.G; g.ldg = c.ldg; g.dq = c.dq; g.lddq = c.lddq; g.P = c.P; g.S = c.S; }
+  if (bias) { g.bias = c.bias; g.bhs = c.bias_head_stride; g.bstride = c.bias_head_stride ? c.H : 1; g.dbias = c.dbias; }
+  if (drop) g.rng = rng;
+  if (edge) { g.e = c.edge.e; g.lde = c.edge.lde; g.de = c.edge.de; g.ldde = c.edge.ldde; }
   int lpr, vec, nch;
-  da_pick(H, F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(nnz);
-  const unsigned blocks = (unsigned)cdiv(n_rows, 4 * (64 / lpr));
-  hipStream_t st = (hipStream_t)stream;
-  if (chunks) PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_long_kernel<LPR, VEC, BIAS, DROP, EDGE>), dim3(chunks), dim3(64), 0, st, g));
-  PYGAT_DA_DISPATCH(lpr, vec, hipLaunchKernelGGL((da_bwd_row_kernel<LPR, VEC, BIAS, DROP, EDGE>), dim3(blocks), dim3(256), 0, st, g));
+  da_pick(c.H, c.F, &lpr, &vec, &nch);
+  const unsigned chunks = (unsigned)long_chunks(c.nnz);
+  const unsigned blocks = (unsigned)cdiv(c.n_rows, 4 * (64 / lpr));
+  hipStream_t st = (hipStream_t)c.stream;
+  void* args[] = {&g};
+  if (chunks) (void)hipLaunchKernel(da_kernel(c.variant, c.bwd, true, lpr, vec), dim3(chunks), dim3(64), args, 0, st);
+  (void)hipLaunchKernel(da_kernel(c.variant, c.bwd, false, lpr, vec), dim3(blocks), dim3(256), args, 0, st);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -992,8 +919,9 @@ static int da_backward_rows(const char* what, int n_rows, int64_t nnz, const int
 extern "C" int pygat_dot_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float scale,
                                            const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                                            float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
-  return da_forward<false>("dot_attn_forward", n_rows, nnz, rowptr, col, nullptr, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out,
-                           ldo, m, Z, ws, stream);
+  DA_CALL(c, "dot_attn_forward", 0, false);
+  c.m = m; c.Z = Z;
+  return da_launch(c);
 }
 
 extern "C" int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
@@ -1001,8 +929,9 @@ extern "C" int pygat_dot_attn_backward_rows(int n_rows, int64_t nnz, const int32
                                                  const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m,
                                                  const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P,
                                                  float* S, void* ws, void* stream) {
-  return da_backward_rows<false>("dot_attn_backward_rows", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr,
-                                 1, out, ldo, m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream);
+  DA_CALL(c, "dot_attn_backward_rows", 0, true);
+  DA_CALL_BWD(c);
+  return da_launch(c);
 }
 
 // the same two with a per-entry term on the score: s[e, h] = scale <q_i, k_j> + bias[entry(e), h bias_head_stride]
@@ -1010,8 +939,9 @@ extern "C" int pygat_dot_attn_bias_forward(int n_rows, int64_t nnz, const int32_
                                                 int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
                                                 const float* v, int64_t ldv, const float* bias, int bias_head_stride, float* out,
                                                 int64_t ldo, float* m, float* Z, void* ws, void* stream) {
-  return da_forward<true>("dot_attn_bias_forward", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
-                          bias_head_stride, out, ldo, m, Z, ws, stream);
+  DA_CALL(c, "dot_attn_bias_forward", DA_BIAS, false);
+  c.perm = perm; c.m = m; c.Z = Z; c.bias = bias; c.bias_head_stride = bias_head_stride;
+  return da_launch(c);
 }
 
 // the inference forward on bf16 k and v tables (8-byte aligned rows, strides in elements); a null bias: the kernels without BIAS
@@ -1019,12 +949,9 @@ extern "C" int pygat_dot_attn_bf16_forward(int n_rows, int64_t nnz, const int32_
                                                 int H, int F, float scale, const float* q, int64_t ldq, const void* k, int64_t ldk,
                                                 const void* v, int64_t ldv, const float* bias, int bias_head_stride, float* out,
                                                 int64_t ldo, void* ws, void* stream) {
-  const da_bf16 *kh = static_cast<const da_bf16*>(k), *vh = static_cast<const da_bf16*>(v);
-  if (bias)
-    return da_forward<true, da_bf16>("dot_attn_bf16_forward", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, kh, ldk, vh, ldv, bias,
-                                     bias_head_stride, out, ldo, nullptr, nullptr, ws, stream);
-  return da_forward<false, da_bf16>("dot_attn_bf16_forward", n_rows, nnz, rowptr, col, nullptr, H, F, scale, q, ldq, kh, ldk, vh, ldv,
-                                    nullptr, 1, out, ldo, nullptr, nullptr, ws, stream);
+  DA_CALL(c, "dot_attn_bf16_forward", da_with_bias(DA_BF16, bias), false);
+  c.perm = perm; c.bias = bias; c.bias_head_stride = bias_head_stride;
+  return da_launch(c);
 }
 
 extern "C" int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
@@ -1033,8 +960,10 @@ extern "C" int pygat_dot_attn_bias_backward_rows(int n_rows, int64_t nnz, const 
                                                       int bias_head_stride, const float* out, int64_t ldo, const float* m,
                                                       const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq, float* P,
                                                       float* S, float* dbias, void* ws, void* stream) {
-  return da_backward_rows<true>("dot_attn_bias_backward_rows", n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv,
-                                bias, bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream);
+  DA_CALL(c, "dot_attn_bias_backward_rows", DA_BIAS, true);
+  DA_CALL_BWD(c);
+  c.bias = bias; c.bias_head_stride = bias_head_stride; c.dbias = dbias;
+  return da_launch(c);
 }
 
 // the bias pair with seeded dropout of the coefficients (the DROP instantiations): out = sum_e alpha mask v, mask[c(e), h] element
@@ -1045,13 +974,9 @@ extern "C" int pygat_dot_attn_dropout_forward(int n_rows, int64_t nnz, const int
                                               const float* v, int64_t ldv, const float* bias, int bias_head_stride, float p,
                                               const void* seed, uint32_t stream_id, float* out, int64_t ldo, float* m, float* Z,
                                               void* ws, void* stream) {
-  const char* what = "dot_attn_dropout_forward";
-  const DaDrop drop = {p, seed, stream_id};
-  if (bias)
-    return da_forward<true, float, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
-                                         bias_head_stride, out, ldo, m, Z, ws, stream, &drop);
-  return da_forward<false, float, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out, ldo,
-                                        m, Z, ws, stream, &drop);
+  DA_CALL(c, "dot_attn_dropout_forward", da_with_bias(DA_DROP, bias), false);
+  c.perm = perm; c.m = m; c.Z = Z; c.bias = bias; c.bias_head_stride = bias_head_stride; c.drop = {p, seed, stream_id};
+  return da_launch(c);
 }
 
 extern "C" int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
@@ -1061,13 +986,10 @@ extern "C" int pygat_dot_attn_dropout_backward_rows(int n_rows, int64_t nnz, con
                                                     const float* out, int64_t ldo, const float* m, const float* Z, const float* G,
                                                     int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* dbias, void* ws,
                                                     void* stream) {
-  const char* what = "dot_attn_dropout_backward_rows";
-  const DaDrop drop = {p, seed, stream_id};
-  if (bias)
-    return da_backward_rows<true, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
-                                        bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream, &drop);
-  return da_backward_rows<false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out, ldo,
-                                       m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream, &drop);
+  DA_CALL(c, "dot_attn_dropout_backward_rows", da_with_bias(DA_DROP, bias), true);
+  DA_CALL_BWD(c);
+  c.bias = bias; c.bias_head_stride = bias_head_stride; c.dbias = dbias; c.drop = {p, seed, stream_id};
+  return da_launch(c);
 }
 
 // the bias pair with a row of H*F floats per entry on both sides (the EDGE instantiations): s = scale <q_i, k_j + e_c> + bias,
@@ -1077,13 +999,9 @@ extern "C" int pygat_dot_attn_edge_forward(int n_rows, int64_t nnz, const int32_
                                            int H, int F, float scale, const float* q, int64_t ldq, const float* k, int64_t ldk,
                                            const float* v, int64_t ldv, const float* e, int64_t lde, const float* bias,
                                            int bias_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
-  const char* what = "dot_attn_edge_forward";
-  const DaEdge edge = {e, lde, nullptr, 0};
-  if (bias)
-    return da_forward<true, float, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
-                                                bias_head_stride, out, ldo, m, Z, ws, stream, nullptr, &edge);
-  return da_forward<false, float, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1,
-                                               out, ldo, m, Z, ws, stream, nullptr, &edge);
+  DA_CALL(c, "dot_attn_edge_forward", da_with_bias(DA_EDGE, bias), false);
+  c.perm = perm; c.m = m; c.Z = Z; c.bias = bias; c.bias_head_stride = bias_head_stride; c.edge = {e, lde, nullptr, 0};
+  return da_launch(c);
 }
 
 extern "C" int pygat_dot_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
@@ -1092,12 +1010,8 @@ extern "C" int pygat_dot_attn_edge_backward_rows(int n_rows, int64_t nnz, const 
                                                  const float* bias, int bias_head_stride, const float* out, int64_t ldo,
                                                  const float* m, const float* Z, const float* G, int64_t ldg, float* dq, int64_t lddq,
                                                  float* P, float* S, float* de, int64_t ldde, float* dbias, void* ws, void* stream) {
-  const char* what = "dot_attn_edge_backward_rows";
-  const DaEdge edge = {e, lde, de, ldde};
-  if (bias)
-    return da_backward_rows<true, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, bias,
-                                               bias_head_stride, out, ldo, m, Z, G, ldg, dq, lddq, P, S, dbias, ws, stream, nullptr,
-                                               &edge);
-  return da_backward_rows<false, false, true>(what, n_rows, nnz, rowptr, col, perm, H, F, scale, q, ldq, k, ldk, v, ldv, nullptr, 1, out,
-                                              ldo, m, Z, G, ldg, dq, lddq, P, S, nullptr, ws, stream, nullptr, &edge);
+  DA_CALL(c, "dot_attn_edge_backward_rows", da_with_bias(DA_EDGE, bias), true);
+  DA_CALL_BWD(c);
+  c.bias = bias; c.bias_head_stride = bias_head_stride; c.dbias = dbias; c.edge = {e, lde, de, ldde};
+  return da_launch(c);
 }

@@ -43,22 +43,31 @@ _PAD_HINT = ("zero-padding the columns of q, k and v to the next allowed F leave
              "(pass scale yourself: the default follows the padded F)")
 
 
+def _require_pattern(op: str, pattern):
+    if not isinstance(pattern, EdgePattern):
+        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+
+
+def _require_tensor(op: str, pattern, name: str, t, dtype=torch.float32, want: str = ""):
+    """The refusals of one tensor (q, k, v, bias, e) that look at nothing but it and the pattern: a tensor on the GPU, of `dtype`
+    (float32, or bfloat16: k and v in dot_attention's inference forward), on the pattern's device.  want: what the message adds."""
+    _require_pattern(op, pattern)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path){want}")
+    if t.dtype != dtype:
+        like = "float32" if dtype == torch.float32 else "bfloat16 like the other table"
+        raise ValueError(f"pygat_amd {op}: {name} must be {like}, not {t.dtype}{want}")
+    if t.device != pattern.device:
+        raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}{want}")
+
+
 def _tables(op: str, pattern, q, others, bf16_others: bool = False):
     """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns,
     float32 like q, or bfloat16 where bf16_others (dot_attention's inference forward)."""
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    _require_pattern(op, pattern)
     named = (("q", q, pattern.n_rows, "rows"),) + tuple((name, t, pattern.n_cols, "columns") for name, t in others)
     for name, t, _, _ in named:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path)")
-        if bf16_others and name != "q":
-            if t.dtype != torch.bfloat16:
-                raise ValueError(f"pygat_amd {op}: {name} must be bfloat16 like the other table, not {t.dtype}")
-        elif t.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {op}: {name} must be float32, not {t.dtype}")
-        if t.device != pattern.device:
-            raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}")
+        _require_tensor(op, pattern, name, t, torch.bfloat16 if bf16_others and name != "q" else torch.float32)
     if q.dim() not in (2, 3):
         raise ValueError(f"pygat_amd {op}: q [n_rows, F] or [n_rows, H, F] expected, got {tuple(q.shape)}")
     for name, t in others:
@@ -140,18 +149,6 @@ def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False, op: str = "do
     return H, F, flat
 
 
-def _bias_tensor(pattern, bias, op: str = "dot_attention"):
-    """The refusals of `bias` that do not depend on q, k and v."""
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
-    if not isinstance(bias, torch.Tensor) or not bias.is_cuda:
-        raise ValueError(f"pygat_amd {op}: bias must be a tensor on the GPU (there is no CPU path)")
-    if bias.dtype != torch.float32:
-        raise ValueError(f"pygat_amd {op}: bias must be float32, not {bias.dtype}")
-    if bias.device != pattern.device:
-        raise ValueError(f"pygat_amd {op}: bias lives on {bias.device}, the pattern on {pattern.device}")
-
-
 def _bias_head_stride(pattern, bias, H: int, flat: bool, op: str = "dot_attention") -> int:
     """1: one value per entry and head ([E, H]; [E] where q, k and v have no head axis); 0: one per entry, shared by the heads."""
     E = pattern.nnz
@@ -163,98 +160,106 @@ def _bias_head_stride(pattern, bias, H: int, flat: bool, op: str = "dot_attentio
     raise ValueError(f"pygat_amd {op}: bias {want} expected for E = {E} entries and H = {H} heads, got {tuple(bias.shape)}")
 
 
-def _checked(op: str, pattern, q, k, v, bias):
-    """Every refusal of the float32 op that looks at the pattern and the tensors -> (H, F, no head axis, the bias's head stride | None)."""
+_E_WANT = "; e [E, H, F] (or [E, F] without a head axis), a row per entry at the caller's entry index, expected"
+
+
+def _checked(op: str, pattern, q, k, v, bias, e=None, bf16_tables: bool = False):
+    """Every refusal that looks at the pattern and the tensors, those of e and bias alone first -> (H, F, no head axis, the bias's
+    head stride | None)."""
+    if e is not None:
+        _require_tensor(op, pattern, "e", e, want=_E_WANT)
     if bias is not None:
-        _bias_tensor(pattern, bias, op)
-    H, F, flat = _attention_shapes(pattern, q, k, v, op=op)
-    return H, F, flat, None if bias is None else _bias_head_stride(pattern, bias, H, flat, op)
+        _require_tensor(op, pattern, "bias", bias)
+    H, F, flat = _attention_shapes(pattern, q, k, v, bf16_tables, op)
+    bhs = None if bias is None else _bias_head_stride(pattern, bias, H, flat, op)
+    if e is not None and tuple(e.shape) != (pattern.nnz,) + tuple(q.shape[1:]):
+        raise ValueError(f"pygat_amd {op}: e {[pattern.nnz] + list(q.shape[1:])} expected for E = {pattern.nnz} entries and q "
+                         f"{tuple(q.shape)} -- (E,) + q.shape[1:], a row per entry -- got {tuple(e.shape)}")
+    return H, F, flat, bhs
 
 
-def _workspace(nnz: int, H: int, F: int, device) -> torch.Tensor:
-    return torch.empty(_lib.dot_attn_workspace_bytes(nnz, H, F), dtype=torch.uint8, device=device)
+def _launch(pattern, which: str, H: int, F: int, scale: float, qc, kc, vc, ec, bc, bhs, drop, rest, bf16: bool = False):
+    """One K19 launcher call, `which` "forward" or "backward_rows", at the entry point of what is present -- bf16 tables, e rows, a
+    dropout (p, seed), a bias, or none of them -- on its argument list: the pattern's arrays, the three tables, the groups of e, bias
+    and dropout, then `rest`, the pass's own arguments up to the workspace."""
+    kind = "bf16_" if bf16 else "edge_" if ec is not None else "dropout_" if drop is not None else "bias_" if bc is not None else ""
+    HF = H * F
+    args = (pattern.n_rows, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col))
+    if kind or which != "forward":                                 # (the forward without a flag walks in CSR order alone)
+        args += (_ptr(pattern.perm),)
+    args += (H, F, scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF)
+    if ec is not None:
+        args += (_ptr(ec), HF)
+    if kind:
+        args += (_ptr(bc), bhs or 0)
+    if drop is not None:
+        args += (drop[0], _ptr(drop[1]), STREAM_ATT)
+    ws = torch.empty(_lib.dot_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=qc.device)
+    check(getattr(lib, f"pygat_dot_attn_{kind}{which}")(*args, *rest, _ptr(ws), _stream()), f"dot_attn_{kind}{which}")
+
+
+def _forward(pattern, H: int, F: int, scale: float, q, k, v, e, bias, bhs, drop, bf16: bool = False):
+    """The forward launch on the tensors as they are -> (out [n_rows, H * F], m, Z), m and Z [n_rows, H] what a backward reads (None
+    on bf16 tables: nothing is kept for one)."""
+    qc, kc, vc, ec, bc = (None if t is None else t.detach().contiguous() for t in (q, k, v, e, bias))
+    n, dev = pattern.n_rows, qc.device
+    with torch.cuda.device(dev):
+        out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
+        m, Z = (None, None) if bf16 else (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
+        _launch(pattern, "forward", H, F, scale, qc, kc, vc, ec, bc, bhs, drop,
+                (_ptr(out), H * F) + (() if bf16 else (_ptr(m), _ptr(Z))), bf16)
+    return out, m, Z
 
 
 class _DotAttentionFn(torch.autograd.Function):
-    """drop: None (dot_attention) or (p, seed) (dot_attention_dropout: the mask of the coefficients, drawn in the kernels of both
-    passes from the int64 [1] seed tensor on the device)."""
+    """dot_attention, dot_attention_dropout and dot_attention_edge.  e: None or the [E, H, F] rows of dot_attention_edge; drop: None or
+    (p, seed) of dot_attention_dropout: the mask of the coefficients, drawn in the kernels of both passes from the int64 [1] seed
+    tensor on the device."""
 
     @staticmethod
-    def forward(ctx, pattern, q, k, v, scale, bias, drop):
-        op = "dot_attention" if drop is None else "dot_attention_dropout"
-        H, F, flat, bhs = _checked(op, pattern, q, k, v, bias)
+    def forward(ctx, pattern, q, k, v, e, scale, bias, drop):
+        op = "dot_attention_edge" if e is not None else "dot_attention" if drop is None else "dot_attention_dropout"
+        H, F, flat, bhs = _checked(op, pattern, q, k, v, bias, e)
         scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
-        qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
-        n, HF = pattern.n_rows, H * F
-        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs, ctx.op, ctx.p = pattern, scale, (H, F), bhs, op, None if drop is None else drop[0]
-        if drop is not None and pattern.nnz == 0:                  # every row is without entries: zeros, and nothing is launched
-            ctx.save_for_backward(q, k, v, None, None, None, bias, None)
+        p, seed = (None, None) if drop is None else drop
+        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs, ctx.op, ctx.p = pattern, scale, (H, F), bhs, op, p
+        if pattern.nnz == 0 and op != "dot_attention":             # every row is without entries: zeros, and nothing is launched
+            ctx.save_for_backward(q, k, v, e, None, None, None, bias, None)
             return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
-        with torch.cuda.device(qc.device):
-            out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
-            m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
-            ws = _workspace(pattern.nnz, H, F, qc.device)
-            if drop is not None:
-                bc = None if bias is None else bias.detach().contiguous()
-                check(lib.pygat_dot_attn_dropout_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H,
-                                                         F, scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs or 0, drop[0],
-                                                         _ptr(drop[1]), STREAM_ATT, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws),
-                                                         _stream()), "dot_attn_dropout_forward")
-            elif bias is None:
-                check(lib.pygat_dot_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, scale, _ptr(qc), HF,
-                                                 _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
-                      "dot_attn_forward")
-            else:
-                bc = bias.detach().contiguous()
-                check(lib.pygat_dot_attn_bias_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
-                                                      scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out), HF,
-                                                      _ptr(m), _ptr(Z), _ptr(ws), _stream()), "dot_attn_bias_forward")
+        out, m, Z = _forward(pattern, H, F, scale, q, k, v, e, bias, bhs, drop)
         out = out.view(q.shape)
-        ctx.save_for_backward(q, k, v, out, m, Z, bias, None if drop is None else drop[1])
+        ctx.save_for_backward(q, k, v, e, out, m, Z, bias, seed)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        q, k, v, out, m, Z, bias, seed = ctx.saved_tensors
+        q, k, v, e, out, m, Z, bias, seed = ctx.saved_tensors
         pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
         if G.dtype != torch.float32:
             raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_q, need_k, need_v = ctx.needs_input_grad[1:4]
-        need_b = bias is not None and ctx.needs_input_grad[5]
-        if not (need_q or need_k or need_v or need_b):
-            return None, None, None, None, None, None, None
+        need_e, need_b = e is not None and ctx.needs_input_grad[4], bias is not None and ctx.needs_input_grad[6]
+        if not (need_q or need_k or need_v or need_e or need_b):
+            return (None,) * 8
+        if out is None:                                            # no entries: zeros, nothing launched
+            zq, zk, zv, ze, zb = (torch.zeros_like(t) if need else None for t, need in
+                                  ((q, need_q), (k, need_k), (v, need_v), (e, need_e), (bias, need_b)))
+            return None, zq, zk, zv, ze, None, zb, None
         n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
-        if out is None:                                            # dot_attention_dropout without entries: zeros, nothing launched
-            return (None,) + tuple(torch.zeros_like(t) if need else None for t, need in
-                                   ((q, need_q), (k, need_k), (v, need_v))) + (None, torch.zeros_like(bias) if need_b else None, None)
-        qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        qc, kc, vc, ec, bc = (None if t is None else t.detach().contiguous() for t in (q, k, v, e, bias))
         Gc = G.contiguous().view(n, HF)
-        db = None
         with torch.cuda.device(qc.device):
             dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
-            ws = _workspace(nnz, H, F, qc.device)
-            if seed is not None:
-                bc = None if bias is None else bias.detach().contiguous()
-                db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
-                check(lib.pygat_dot_attn_dropout_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
-                                                               scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs or 0,
-                                                               ctx.p, _ptr(seed), STREAM_ATT, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc),
-                                                               HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(db), _ptr(ws), _stream()),
-                      "dot_attn_dropout_backward_rows")
-            elif bias is None:
-                check(lib.pygat_dot_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
-                                                       _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
-                                                       _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
-                      "dot_attn_backward_rows")
-            else:
-                bc = bias.detach().contiguous()
-                db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
-                check(lib.pygat_dot_attn_bias_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
-                                                            scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out),
-                                                            HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S),
-                                                            _ptr(db), _ptr(ws), _stream()), "dot_attn_bias_backward_rows")
+            de = torch.empty(nnz, HF, dtype=torch.float32, device=qc.device) if need_e else None      # (every row is written once)
+            db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
+            rest = (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S))
+            if e is not None:
+                rest += (_ptr(de), HF)
+            if e is not None or bias is not None or seed is not None:      # (every entry point but the one without a flag)
+                rest += (_ptr(db),)
+            _launch(pattern, "backward_rows", H, F, scale, qc, kc, vc, ec, bc, bhs, None if seed is None else (ctx.p, seed), rest)
             if need_b:                          # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
                 db = db.sum(1) if bhs == 0 else db.view(bias.shape)
         dk = dv = None
@@ -264,7 +269,7 @@ class _DotAttentionFn(torch.autograd.Function):
                 dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
             if need_v:
                 dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
-        return None, dq.view(q.shape) if need_q else None, dk, dv, None, db, None
+        return None, dq.view(q.shape) if need_q else None, dk, dv, de.view(e.shape) if need_e else None, None, db, None
 
 
 def _bf16_tables(k, v) -> bool:
@@ -283,23 +288,11 @@ def _dot_attention_bf16(pattern, q, k, v, scale, bias):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (q, k, v, bias)):
         raise ValueError("pygat_amd dot_attention: bfloat16 k and v are for inference (there is no backward through them): call it "
                          "under torch.no_grad(), or pass float32 tables")
-    if bias is not None:
-        _bias_tensor(pattern, bias)
-    H, F, flat = _attention_shapes(pattern, q, k, v, bf16_tables=True)
-    bhs = 1 if bias is None else _bias_head_stride(pattern, bias, H, flat)
+    H, F, flat, bhs = _checked("dot_attention", pattern, q, k, v, bias, bf16_tables=True)
     scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
-    n, HF = pattern.n_rows, H * F
     if pattern.nnz == 0:                        # every row is without entries
         return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
-    qc, kc, vc = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
-    bc = None if bias is None else bias.detach().contiguous()
-    with torch.cuda.device(qc.device):
-        out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
-        ws = _workspace(pattern.nnz, H, F, qc.device)
-        check(lib.pygat_dot_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
-                                              _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(bc), bhs, _ptr(out), HF, _ptr(ws),
-                                              _stream()), "dot_attn_bf16_forward")
-    return out.view(q.shape)
+    return _forward(pattern, H, F, scale, q, k, v, None, bias, 1 if bias is None else bhs, None, bf16=True)[0].view(q.shape)
 
 
 def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
@@ -318,7 +311,7 @@ def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: tor
     mode on and a tensor that requires grad it raises; call it under torch.no_grad(), or pass float32 tables."""
     if _bf16_tables(k, v):
         return _dot_attention_bf16(pattern, q, k, v, scale, bias)
-    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias, None)
+    return _DotAttentionFn.apply(pattern, q, k, v, None, scale, bias, None)
 
 
 # ----------------------------------------------------------------------------------------------------------- dot_attention_dropout
@@ -329,8 +322,7 @@ def _drop_p(op: str, p) -> float:
 
 
 def _drop_seed(op: str, pattern, seed):
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    _require_pattern(op, pattern)
     if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or tuple(seed.shape) != (1,) or seed.device != pattern.device:
         got = f"{seed.dtype} {tuple(seed.shape)} on {seed.device}" if isinstance(seed, torch.Tensor) else type(seed).__name__
         raise ValueError(f"pygat_amd {op}: seed must be an int64 tensor of shape [1] on the pattern's device {pattern.device} (the "
@@ -378,102 +370,10 @@ def dot_attention_dropout(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor
         return dot_attention(pattern, q, k, v, scale, bias)
     if seed is None:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
-    return _DotAttentionFn.apply(pattern, q, k, v, scale, bias, (p, seed))
+    return _DotAttentionFn.apply(pattern, q, k, v, None, scale, bias, (p, seed))
 
 
 # -------------------------------------------------------------------------------------------------------------- dot_attention_edge
-_EDGE_OP = "dot_attention_edge"
-
-
-def _edge_tensor(pattern, e, op: str = _EDGE_OP):
-    """The refusals of `e` that do not depend on q, k and v."""
-    want = "e [E, H, F] (or [E, F] without a head axis), a row per entry at the caller's entry index, expected"
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
-    if not isinstance(e, torch.Tensor) or not e.is_cuda:
-        raise ValueError(f"pygat_amd {op}: e must be a tensor on the GPU (there is no CPU path); {want}")
-    if e.dtype != torch.float32:
-        raise ValueError(f"pygat_amd {op}: e must be float32, not {e.dtype}; {want}")
-    if e.device != pattern.device:
-        raise ValueError(f"pygat_amd {op}: e lives on {e.device}, the pattern on {pattern.device}; {want}")
-
-
-def _edge_shape(pattern, e, q, op: str = _EDGE_OP):
-    want = (pattern.nnz,) + tuple(q.shape[1:])
-    if tuple(e.shape) != want:
-        raise ValueError(f"pygat_amd {op}: e {list(want)} expected for E = {pattern.nnz} entries and q {tuple(q.shape)} -- (E,) + "
-                         f"q.shape[1:], a row per entry -- got {tuple(e.shape)}")
-
-
-class _DotAttentionEdgeFn(torch.autograd.Function):
-    """dot_attention_edge: _DotAttentionFn's skeleton on the EDGE instantiations, with e [E, H, F] beside k and v and its gradient de
-    written by the row pass of the backward."""
-
-    @staticmethod
-    def forward(ctx, pattern, q, k, v, e, scale, bias):
-        op = _EDGE_OP
-        _edge_tensor(pattern, e, op)
-        H, F, flat, bhs = _checked(op, pattern, q, k, v, bias)
-        _edge_shape(pattern, e, q, op)
-        scale = 1.0 / math.sqrt(F) if scale is None else float(scale)
-        n, HF = pattern.n_rows, H * F
-        ctx.pattern, ctx.scale, ctx.hf, ctx.bhs = pattern, scale, (H, F), bhs
-        if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
-            ctx.save_for_backward(q, k, v, e, None, None, None, bias)
-            return torch.zeros(q.shape, dtype=torch.float32, device=q.device)
-        qc, kc, vc, ec = (t.detach().contiguous() for t in (q, k, v, e))
-        bc = None if bias is None else bias.detach().contiguous()
-        with torch.cuda.device(qc.device):
-            out = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
-            m, Z = torch.empty(n, H, dtype=torch.float32, device=qc.device), torch.empty(n, H, dtype=torch.float32, device=qc.device)
-            ws = _workspace(pattern.nnz, H, F, qc.device)
-            check(lib.pygat_dot_attn_edge_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F,
-                                                  scale, _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(ec), HF, _ptr(bc), bhs or 0,
-                                                  _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()), "dot_attn_edge_forward")
-        out = out.view(q.shape)
-        ctx.save_for_backward(q, k, v, e, out, m, Z, bias)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        q, k, v, e, out, m, Z, bias = ctx.saved_tensors
-        pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
-        if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {_EDGE_OP}: the gradient of the output must be float32, not {G.dtype}")
-        need_q, need_k, need_v, need_e = ctx.needs_input_grad[1:5]
-        need_b = bias is not None and ctx.needs_input_grad[6]
-        if not (need_q or need_k or need_v or need_e or need_b):
-            return None, None, None, None, None, None, None
-        n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
-        if out is None:                                            # no entries: zeros, nothing launched
-            return (None,) + tuple(torch.zeros_like(t) if need else None for t, need in
-                                   ((q, need_q), (k, need_k), (v, need_v), (e, need_e))) + (None, torch.zeros_like(bias) if need_b else None)
-        qc, kc, vc, ec = (t.detach().contiguous() for t in (q, k, v, e))
-        bc = None if bias is None else bias.detach().contiguous()
-        Gc = G.contiguous().view(n, HF)
-        with torch.cuda.device(qc.device):
-            dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
-            P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
-            de = torch.empty(nnz, HF, dtype=torch.float32, device=qc.device) if need_e else None      # (every row is written once)
-            db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
-            ws = _workspace(nnz, H, F, qc.device)
-            check(lib.pygat_dot_attn_edge_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, scale,
-                                                        _ptr(qc), HF, _ptr(kc), HF, _ptr(vc), HF, _ptr(ec), HF, _ptr(bc), bhs or 0,
-                                                        _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S),
-                                                        _ptr(de), HF, _ptr(db), _ptr(ws), _stream()), "dot_attn_edge_backward_rows")
-            if need_b:                          # [E, H] -> the bias's own shape: a [E] bias shared by H heads gets the sum over them
-                db = db.sum(1) if bhs == 0 else db.view(bias.shape)
-        dk = dv = None
-        if need_k or need_v:
-            rowptr_t, row_t, perm_t = pattern.transposed()
-            if need_k:
-                dk = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, S, qc.view(n, HF)).view(k.shape)
-            if need_v:
-                dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
-        return None, dq.view(q.shape) if need_q else None, dk, dv, de.view(e.shape) if need_e else None, None, db
-
-
 def dot_attention_edge(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tensor,
                        scale: Optional[float] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dot_attention with a feature row per entry on the key and the value side, as a graph-transformer layer uses its edge features
@@ -487,6 +387,8 @@ def dot_attention_edge(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v
     no [E, H, F] tensor is made in backward.  A row without entries gets zeros; a row of one entry (i, j) gets v[j] + e[c] bit for bit.
     float32 GPU tensors with dot_attention's limits (1 <= H <= 64, F a power of two in 4..256, H * F <= 1024); bfloat16 k, v or e are
     refused: there is no inference variant and no dropout variant of this op."""
+    op = "dot_attention_edge"
     if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (k, v, e)):
-        raise ValueError(f"pygat_amd {_EDGE_OP}: k, v and e must be float32: bfloat16 tables are for dot_attention's inference forward")
-    return _DotAttentionEdgeFn.apply(pattern, q, k, v, e, scale, bias)
+        raise ValueError(f"pygat_amd {op}: k, v and e must be float32: bfloat16 tables are for dot_attention's inference forward")
+    _require_tensor(op, pattern, "e", e, want=_E_WANT)             # (a None here would be dot_attention)
+    return _DotAttentionFn.apply(pattern, q, k, v, e, scale, bias, None)

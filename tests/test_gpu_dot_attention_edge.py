@@ -297,7 +297,7 @@ def test_refusals(monkeypatch):
     out = pg.dot_attention_edge(pattern, *leaves)
     del seen[:]
     with pytest.raises(ValueError, match="dot_attention_edge.*float32"):
-        mod._DotAttentionEdgeFn.backward(out.grad_fn, torch.ones(N, 4, 16, device=DEV, dtype=torch.float64))
+        mod._DotAttentionFn.backward(out.grad_fn, torch.ones(N, 4, 16, device=DEV, dtype=torch.float64))
     assert seen == []
 
 
