@@ -1,4 +1,8 @@
-"""ctypes binding of libpygat_amd.so (the C ABI in include/pygat_amd.h).
+"""ctypes binding of libpygat_amd.so, taken from the one declaration of its C ABI: include/pygat_amd.h.
+
+The header is read when this module is imported; every entry point's restype / argtypes, the struct mirrors and the
+constants below come from it, so a new entry point is declared once, there.  The header is plain C (no macros in
+declarations, no function pointers, no varargs); parse_header refuses anything it does not understand rather than guess.
 
 There is NO fallback: if the HIP library is missing or does not export the
 expected symbols, importing this module raises.  PyTorch is used by the callers
@@ -8,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 # torch FIRST: it brings its own HIP runtime (torch/lib/libamdhip64.so); libpygat_amd.so must bind to that one.  Loaded
 # before torch, the library pulls in /opt/rocm/lib/libamdhip64.so.7 instead, the process then holds two HIP runtimes and
@@ -17,71 +22,163 @@ import torch  # noqa: F401,E402
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpygat_amd.so")
+# the library is loaded in-tree and never installed: the header it was built from lies beside the package
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pygat_amd.h")
 # development aid (tools/build_variant.sh, same-lease A/B runs): another build of the same library.  Still a HIP library or
-# nothing -- the symbol check below applies to it as well.
+# nothing -- it is bound from this tree's header, and the ABI-version check below refuses a stale one.
 from .config import config as _config  # noqa: E402
 if _config.lib_path:
     LIB_PATH = os.path.abspath(_config.lib_path)
 
-ABI_VERSION = 16
-F_ELU = 1
-F_SKIP = 2
-F_MAIN_ONLY = 4
-F_FIXUP_ONLY = 8
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float,
+           "double": C.c_double, "size_t": C.c_size_t}
+# pointers that are not plain addresses to ctypes; a `const pygat_<struct>*` is a POINTER of its mirror, every other one a c_void_p
+POINTERS = {"size_t*": C.POINTER(C.c_size_t), "int*": C.POINTER(C.c_int), "char*": C.c_char_p, "const char*": C.c_char_p}
+_POINTEES = set(SCALARS) | {"void", "char", "unsigned char"}
 
-# every entry point declared in include/pygat_amd.h
-SYMBOLS = [
-    "pygat_abi_version", "pygat_last_error", "pygat_padded_width", "pygat_device_count",
-    "pygat_device_name", "pygat_kernel_footprint", "pygat_default_gemm_mode", "pygat_dense_row_counts", "pygat_scan_workspace_bytes",
-    "pygat_exclusive_scan_i32", "pygat_dense_fill_cols", "pygat_csr_symmetric_perm",
-    "pygat_gemm_workspace_bytes", "pygat_gemm_f32", "pygat_gemm_f32_blocked", "pygat_project_blocked", "pygat_wgrad_blocked", "pygat_wgrad_tail_blocked", "pygat_pack_params", "pygat_pack_params_heads", "pygat_stack_heads", "pygat_stack_heads_padded", "pygat_project", "pygat_attn_scores",
-    "pygat_unpack_wgrad",
-    "pygat_edge_pairs", "pygat_slot_bounds", "pygat_slot_meta", "pygat_partials_bytes", "pygat_head_group", "pygat_gat_forward", "pygat_gat_forward_phases_ok", "pygat_gat_forward_tail", "pygat_gat_backward_col_tail", "pygat_gat_backward_tail", "pygat_project_tail_blocked", "pygat_head_mean",
-    "pygat_gat_backward_prepare", "pygat_gat_backward_row", "pygat_gat_backward_col", "pygat_gat_backward_rowsum",
-    "pygat_gat_backward_col_da_bytes", "pygat_a_grad_fold",
-    "pygat_gat_backward_col_phases_ok", "pygat_gat_backward_col_phase", "pygat_gat_backward_col_finish",
-    "pygat_agrad_workspace_bytes", "pygat_a_grad", "pygat_wgrad_workspace_bytes", "pygat_wgrad",
-    "pygat_gatv2_forward", "pygat_gatv2_backward_prepare", "pygat_gatv2_workspace_bytes", "pygat_gatv2_backward",
-    "pygat_gat_attention", "pygat_gatv2_attention",
-    "pygat_alpha_grad_workspace_bytes", "pygat_alpha_grad_rows", "pygat_alpha_grad_cols", "pygat_alpha_grad_apply",
-    "pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
-    "pygat_gat_edge_backward_cols",
-    "pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16",
-    "pygat_spmm_workspace_bytes", "pygat_spmm_forward", "pygat_spmm_grad_values",
-    "pygat_edge_softmax_workspace_bytes", "pygat_edge_softmax_rows", "pygat_edge_softmax_apply", "pygat_edge_softmax_grad_rows",
-    "pygat_edge_softmax_grad_apply",
-    "pygat_dot_attn_workspace_bytes", "pygat_dot_attn_forward", "pygat_dot_attn_backward_rows",
-    "pygat_dot_attn_bias_forward", "pygat_dot_attn_bias_backward_rows", "pygat_dot_attn_bf16_forward",
-    "pygat_dot_attn_dropout_forward", "pygat_dot_attn_dropout_backward_rows",
-    "pygat_dot_attn_edge_forward", "pygat_dot_attn_edge_backward_rows",
-    "pygat_dropout_mask", "pygat_dropout_mask2", "pygat_dropout_expand", "pygat_dropout_head_sum", "pygat_pack_blockdiag",
-    "pygat_unpack_blockdiag",
-    "pygat_headmask_supported", "pygat_dropout_bits", "pygat_project_dropout_workspace_bytes", "pygat_project_dropout",
-    "pygat_wgrad_dropout_workspace_bytes",
-    "pygat_wgrad_dropout", "pygat_dropout_head_sum_bits",
-    "pygat_nll_workspace_bytes", "pygat_elu_logsoftmax_nll", "pygat_elu_logsoftmax_nll_backward",
-    "pygat_project_sparse", "pygat_wgrad_sparse", "pygat_wgrad_sparse_workspace_bytes", "pygat_dropout_narrow", "pygat_dx_dropout", "pygat_adam_step", "pygat_bce_workspace_bytes", "pygat_bce_with_logits", "pygat_bce_with_logits_backward",
-]
 
-MAX_ADAM_TENSORS = 48    # PYGAT_ADAM_MAX_TENSORS
-MAX_SEGMENTS = 4    # PYGAT_MAX_SEGMENTS
+class HeaderError(ValueError):
+    """A declaration of the header that parse_header does not understand."""
+
+
+def _spelling(text: str, where: str, structs) -> str:
+    """`const  float *const*` -> `const float* const*`; refuses anything that is not a known scalar or a pointer to a known type."""
+    if not re.fullmatch(r"[\w\s*]+", text):
+        raise HeaderError(f"{where}: cannot read the type in `{text.strip()}`")
+    t = re.sub(r" \*", "*", " ".join(re.findall(r"\w+|\*", text)))
+    base = re.sub(r"^const ", "", t.split("*")[0])
+    if not (t in SCALARS or ("*" in t and (base in _POINTEES or base in structs))):
+        raise HeaderError(f"{where}: unknown type `{t}`")
+    return t
+
+
+def parse_header(text: str):
+    """The C ABI declared by the text of include/pygat_amd.h, as (consts, structs, funcs):
+    consts   {name: int} of every `#define PYGAT_X <int>` and every `PYGAT_X = <int>` of an enum;
+    structs  {name: [(type, field, array extent or None), ...]} of every `typedef struct { ... } name;`, fields in order;
+    funcs    {name: (return type, [(type, parameter), ...])} of every `ret pygat_name(params);`, in order.
+    Types are C spellings with single spaces and `*` bound to the left (`const float* const*`).  Raises HeaderError, naming
+    the declaration, for whatever it cannot read: nothing is skipped and no type is guessed."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", "", text, flags=re.S)      # extern "C" { and its }
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#define[ \t]+(PYGAT_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def enum(m):
+        for entry in filter(None, map(str.strip, m[1].split(","))):
+            e = re.fullmatch(r"(PYGAT_\w+)\s*=\s*(-?\d+)", entry)
+            if not e:
+                raise HeaderError(f"enum entry `{entry}`: expected PYGAT_NAME = <integer>")
+            consts[e[1]] = int(e[2])
+        return ""
+    text = re.sub(r"\benum\s*\{(.*?)\}\s*;", enum, text, flags=re.S)
+
+    def extent(expr, where):
+        e = re.fullmatch(r"(?:(\d+)|(\w+)(?:\s*\+\s*(\d+))?)", expr.strip())
+        if not e or (e[2] and e[2] not in consts):
+            raise HeaderError(f"{where}: cannot resolve the extent [{expr}]")
+        return int(e[1]) if e[1] else consts[e[2]] + int(e[3] or 0)
+
+    structs = {}
+
+    def struct(m):
+        name, fields = m[2], []
+        for decl in filter(None, map(str.strip, m[1].split(";"))):
+            f = re.fullmatch(r"(.*?)(\w+)\s*(?:\[(.*)\])?", decl, flags=re.S)
+            where = f"{name}.{f[2]}" if f else name
+            if not f:
+                raise HeaderError(f"{where}: cannot read the field `{decl}`")
+            fields.append((_spelling(f[1], where, structs), f[2], None if f[3] is None else extent(f[3], where)))
+        structs[name] = fields
+        return ""
+    text = re.sub(r"\btypedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+
+    funcs = {}
+    for decl in filter(None, map(str.strip, text.split(";"))):
+        f = re.fullmatch(r"(.*?)\b(pygat_\w+)\s*\((.*)\)", decl, flags=re.S)
+        if not f:
+            named = re.search(r"\bpygat_\w+", decl)
+            raise HeaderError(f"{named[0] if named else decl[:60]!r}: not a function declaration `ret pygat_name(params)`")
+        name, params = f[2], f[3].strip()
+        if "(" in params or "..." in params:
+            raise HeaderError(f"{name}: function-pointer and variadic parameters are not supported")
+        args = []
+        for k, param in enumerate([] if params == "void" else params.split(",")):
+            p = re.fullmatch(r"(.*?)(\w+)\s*", param, flags=re.S)
+            if not p:
+                raise HeaderError(f"{name}: cannot read parameter {k} `{param.strip()}`")
+            args.append((_spelling(p[1], f"{name}({p[2]})", structs), p[2]))
+        funcs[name] = (_spelling(f[1], f"{name} (return type)", structs), args)
+    skipped = set(re.findall(r"\b(pygat_\w+)\s*\(", text)) - set(funcs)
+    if skipped:
+        raise HeaderError(f"{sorted(skipped)}: named before `(` but not parsed as functions")
+    return consts, structs, funcs
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f"pygat_amd: {HEADER_PATH} not found. The binding is read from the C header of the tree the package "
+                          f"lies in; the package is used in-tree and not installed without it.")
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except HeaderError as e:
+        raise ImportError(f"pygat_amd: {HEADER_PATH}: {e}") from e
+
+
+_CONSTS, _STRUCTS, _FUNCS = _read_header()
+SYMBOLS = list(_FUNCS)          # every entry point declared in include/pygat_amd.h
+
+ABI_VERSION = _CONSTS["PYGAT_ABI_VERSION"]
+EINVAL = _CONSTS["PYGAT_EINVAL"]
+F_ELU = _CONSTS["PYGAT_F_ELU"]
+F_SKIP = _CONSTS["PYGAT_F_SKIP"]
+F_MAIN_ONLY = _CONSTS["PYGAT_F_MAIN_ONLY"]
+F_FIXUP_ONLY = _CONSTS["PYGAT_F_FIXUP_ONLY"]
+GEMM_DEFAULT = _CONSTS["PYGAT_GEMM_DEFAULT"]
+GEMM_SPLIT_BF16 = _CONSTS["PYGAT_GEMM_SPLIT_BF16"]
+GEMM_FP32_MFMA = _CONSTS["PYGAT_GEMM_FP32_MFMA"]
+MAX_SEGMENTS = _CONSTS["PYGAT_MAX_SEGMENTS"]
+MAX_HEADS_TABLE = _CONSTS["PYGAT_MAX_HEADS_TABLE"]
+MAX_ADAM_TENSORS = _CONSTS["PYGAT_ADAM_MAX_TENSORS"]
+ADAM_STATE_BYTES = _CONSTS["PYGAT_ADAM_STATE_BYTES"]
+
+
+def _fields(struct: str):
+    """_fields_ of a struct of the header: a pointer field is an address, an array field element type * extent."""
+    fields = []
+    for t, name, extent in _STRUCTS[struct]:
+        ct = C.c_void_p if "*" in t else SCALARS[t]
+        fields.append((name, ct if extent is None else ct * extent))
+    return fields
 
 
 class OutSegments(C.Structure):
-    _fields_ = [("nseg", C.c_int), ("col_start", C.c_int32 * (MAX_SEGMENTS + 1)), ("ptr", C.c_void_p * MAX_SEGMENTS),
-                ("ld", C.c_int64 * MAX_SEGMENTS)]
+    _fields_ = _fields("pygat_out_segments")
 
 
 class ColBlocks(C.Structure):
     """pygat_col_blocks: a [rows x cols] matrix stored as cols / w blocks of [rows x w], `stride` floats apart."""
-    _fields_ = [("w", C.c_int), ("stride", C.c_int64)]
+    _fields_ = _fields("pygat_col_blocks")
 
 
 class Graph(C.Structure):
-    _fields_ = [("n", C.c_int), ("nnz", C.c_int64), ("rowptr", C.c_void_p), ("edge_rc", C.c_void_p),
-                ("slot_edges", C.c_int), ("slot_begin", C.c_void_p), ("cut_rows", C.c_void_p),
-                ("n_cut", C.c_int), ("n_cut_wide", C.c_int), ("slot_first", C.c_int64), ("slot_count", C.c_int64),
-                ("slot_meta", C.c_void_p), ("slot_order", C.c_void_p), ("user_row", C.c_void_p)]
+    _fields_ = _fields("pygat_graph")
+
+
+_MIRRORS = {"pygat_out_segments": OutSegments, "pygat_col_blocks": ColBlocks, "pygat_graph": Graph}
+
+
+def _ctype(t: str):
+    """The ctypes type of a parameter or return type as parse_header spells it."""
+    if t in SCALARS or t in POINTERS:
+        return SCALARS.get(t) or POINTERS[t]
+    pointee = re.sub(r"^const ", "", t.split("*")[0])
+    if pointee in _STRUCTS:
+        if t != f"const {pointee}*" or pointee not in _MIRRORS:
+            raise ImportError(f"pygat_amd: {HEADER_PATH}: no ctypes mirror for `{t}`")
+        return C.POINTER(_MIRRORS[pointee])
+    return C.c_void_p
 
 
 def _load():
@@ -93,140 +190,9 @@ def _load():
     missing = [s for s in SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise ImportError(f"pygat_amd: {LIB_PATH} lacks symbols {missing}")
-    p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
-    lib.pygat_abi_version.restype = i
-    lib.pygat_last_error.restype = C.c_char_p
-    lib.pygat_padded_width.argtypes = [i]
-    lib.pygat_device_name.argtypes = [C.c_char_p, i]
-    lib.pygat_kernel_footprint.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.pygat_default_gemm_mode.argtypes = []
-    lib.pygat_dense_row_counts.argtypes = [p, i, i64, i, p, p]
-    lib.pygat_scan_workspace_bytes.argtypes = [i64]
-    lib.pygat_scan_workspace_bytes.restype = sz
-    lib.pygat_exclusive_scan_i32.argtypes = [p, i64, p, p, p]
-    lib.pygat_dense_fill_cols.argtypes = [p, i, i64, i, p, p, p]
-    lib.pygat_csr_symmetric_perm.argtypes = [i, p, p, p, p, p]
-    lib.pygat_gemm_workspace_bytes.argtypes = [i, i, i]
-    lib.pygat_gemm_workspace_bytes.restype = sz
-    lib.pygat_gemm_f32.argtypes = [i, i, i, i, i64, p, i64, p, i64, C.POINTER(OutSegments), i, i, p, i, p]
-    CB = C.POINTER(ColBlocks)
-    lib.pygat_gemm_f32_blocked.argtypes = [i, i, i, i, i64, p, i64, CB, p, i64, C.POINTER(OutSegments), CB, i, i, p, i, p]
-    lib.pygat_project_blocked.argtypes = [i, i, i, i, p, i64, CB, p, i64, p, p, p, p, i, p, i, p]
-    lib.pygat_wgrad_blocked.argtypes = [i, i, i, i, p, i64, CB, p, p, p, p, i, p, i, i, i, p]
-    lib.pygat_wgrad_tail_blocked.argtypes = [i, i, i, i, p, i64, CB, p, p, i, p, i, i, p, p, p, i, p]
-    lib.pygat_pack_params.argtypes = [i, i, i, p, p, p, p, i64, p, p]
-    lib.pygat_pack_params_heads.argtypes = [i, i, i, p, p, p, p, i64, p, p]
-    lib.pygat_stack_heads.argtypes = [i, i64, i, i64, p, p, p, p, p, p, p]
-    lib.pygat_stack_heads_padded.argtypes = [i, i64, i64, i, i64, i64, p, p, p, p, p, p, p]
-    lib.pygat_unpack_wgrad.argtypes = [i, i, i, p, i64, i, p, p]
-    lib.pygat_attn_scores.argtypes = [i, i, i, p, p, p, p, p, p]
-    lib.pygat_project.argtypes = [i, i, i, i, p, i64, p, i64, p, p, p, p, i, p, i, p]
-    lib.pygat_edge_pairs.argtypes = [i, p, p, p, p]
-    lib.pygat_slot_bounds.argtypes = [i, i64, p, p, i, p, p]
-    lib.pygat_slot_meta.argtypes = [i, i64, p, p, i, p, p, p]
-    lib.pygat_partials_bytes.argtypes = [i64, i, i, i]
-    lib.pygat_partials_bytes.restype = sz
-    lib.pygat_head_group.argtypes = [i, i, i]
-    lib.pygat_head_group.restype = i
-    lib.pygat_gat_forward.argtypes = [C.POINTER(Graph), i, i, f, i, p, p, p, p, p, p, p, p, p, p, p, p, p]
-    lib.pygat_gat_forward_phases_ok.argtypes = [i, i, i]
-    lib.pygat_gat_forward_tail.argtypes = [i, i, i, i, i, p, i64, p, p, p, p, p, p, p]
-    lib.pygat_gat_backward_col_tail.argtypes = [i, i, i, i, p, p, p, p]
-    lib.pygat_gat_backward_tail.argtypes = [i, i, i, i, i, p, p, p, p, i64, i, p, p, p]
-    lib.pygat_project_tail_blocked.argtypes = [i, i, i, i, p, i64, CB, p, i64, p, p, p, i, p, i, i, p, p, i, p]
-    lib.pygat_head_mean.argtypes = [i, i, i, p, p, p, p]
-    lib.pygat_gat_backward_prepare.argtypes = [i, i, i, i, i, p, p, p, p, p, p, p, p, p, f, p, i, i, i, p, p]
-    lib.pygat_gat_backward_row.argtypes = [C.POINTER(Graph), i, i, f, p, p, p, p, p, p, i, i, i, p]
-    lib.pygat_gat_backward_col.argtypes = [C.POINTER(Graph), p, i, i, f, p, p, p, p, p, p, p, p, p, p, i, i, i, p]
-    lib.pygat_gat_backward_col_da_bytes.argtypes = [C.POINTER(Graph), i, i, i]
-    lib.pygat_gat_backward_col_da_bytes.restype = sz
-    lib.pygat_gat_backward_col_phases_ok.argtypes = [C.POINTER(Graph), i, i, i]
-    lib.pygat_gat_backward_col_phase.argtypes = [C.POINTER(Graph), p, i, i, f, p, p, p, p, p, p, p, p, p, p, i, i, i, i, p]
-    lib.pygat_gat_backward_col_finish.argtypes = [C.POINTER(Graph), i, i, p, p, p, p, p, i, i, i, i, p, p, p, p]
-    lib.pygat_a_grad_fold.argtypes = [C.POINTER(Graph), i, i, p, p, p, p, p, p, i, p]
-    lib.pygat_gat_backward_rowsum.argtypes = [C.POINTER(Graph), p, i, i, p, p, p, i, i, p]
-    lib.pygat_agrad_workspace_bytes.argtypes = [i, i]
-    lib.pygat_agrad_workspace_bytes.restype = sz
-    lib.pygat_a_grad.argtypes = [i, i, i, p, p, p, p, p, p, p, p, i, i, p]
-    lib.pygat_gatv2_forward.argtypes = [C.POINTER(Graph), i, i, f, i, p, p, p, p, p, p, p, p, p, p]
-    lib.pygat_gatv2_backward_prepare.argtypes = [i, i, i, i, i, p, p, p, p, p, p, p, p, p]
-    lib.pygat_gatv2_workspace_bytes.argtypes = [i64, i, i, i]
-    lib.pygat_gatv2_workspace_bytes.restype = sz
-    lib.pygat_gatv2_backward.argtypes = [C.POINTER(Graph), C.POINTER(Graph), p, p, i, i, f, p, p, p, p, p, p, p, p]
-    lib.pygat_gat_attention.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, p, p, p, i, p, p, p]
-    lib.pygat_gatv2_attention.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p]
-    lib.pygat_alpha_grad_workspace_bytes.argtypes = [i64, i, C.POINTER(sz)]
-    lib.pygat_alpha_grad_rows.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p]
-    lib.pygat_alpha_grad_cols.argtypes = [i, i64, p, p, p, p, i, i, f, p, p, p, p, p, p]
-    lib.pygat_alpha_grad_apply.argtypes = [i, i, i, p, p, p, p, p]
-    lib.pygat_gat_edge_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
-    lib.pygat_gat_edge_forward.argtypes = [i, i64, p, p, i, i, f, i, p, p, p, p, p, i64, p, p, p, p, p, p]
-    lib.pygat_gat_edge_alpha.argtypes = [i, i64, p, i, f, p, p, p, p, p, i64, p, p]
-    lib.pygat_gat_edge_backward_rows.argtypes = [i, i64, p, p, i, i, f, i, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
-    lib.pygat_gat_edge_backward_cols.argtypes = [i, i64, p, p, p, i, i, f, p, p, p, p, p, i64, p, p, p, p, p, p, p, p]
-    lib.pygat_gat_bf16_workspace_bytes.argtypes = [i64, i, i, i, C.POINTER(sz)]
-    lib.pygat_gat_pack_bf16.argtypes = [i, i, i, p, i64, p, p, p, p]
-    lib.pygat_gat_forward_bf16.argtypes = [C.POINTER(Graph), i, i, f, i, p, p, p, p, p, p, i, p, p]
-    lib.pygat_spmm_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
-    lib.pygat_spmm_forward.argtypes = [i, i64, p, p, p, i, i, p, p, i64, p, i64, p, p]
-    lib.pygat_spmm_grad_values.argtypes = [i64, p, i, i, p, i64, p, i64, p, p]
-    lib.pygat_edge_softmax_workspace_bytes.argtypes = [i64, i, C.POINTER(sz)]
-    lib.pygat_edge_softmax_rows.argtypes = [i, i64, p, p, i, p, p, p, p, p]
-    lib.pygat_edge_softmax_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
-    lib.pygat_edge_softmax_grad_rows.argtypes = [i, i64, p, p, i, p, p, p, p, p]
-    lib.pygat_edge_softmax_grad_apply.argtypes = [i64, p, i, i, p, p, p, p, p]
-    lib.pygat_dot_attn_workspace_bytes.argtypes = [i64, i, i, C.POINTER(sz)]
-    lib.pygat_dot_attn_forward.argtypes = [i, i64, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, p, p, p]
-    lib.pygat_dot_attn_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, p, p, i64, p, i64, p,
-                                                 p, p, p]
-    lib.pygat_dot_attn_bias_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p, p]
-    lib.pygat_dot_attn_bias_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p, i64, p,
-                                                      i64, p, p, p, p, p]
-    lib.pygat_dot_attn_bf16_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, p, i64, p, p]
-    u32 = C.c_uint32
-    lib.pygat_dot_attn_dropout_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, f, p, u32, p, i64, p, p, p, p]
-    lib.pygat_dot_attn_dropout_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i, f, p, u32, p, i64, p, p,
-                                                         p, i64, p, i64, p, p, p, p, p]
-    lib.pygat_dot_attn_edge_forward.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p, p]
-    lib.pygat_dot_attn_edge_backward_rows.argtypes = [i, i64, p, p, p, i, i, f, p, i64, p, i64, p, i64, p, i64, p, i, p, i64, p, p, p,
-                                                      i64, p, i64, p, p, p, i64, p, p, p]
-    lib.pygat_wgrad_workspace_bytes.argtypes = [i, i, i, i]
-    lib.pygat_wgrad_workspace_bytes.restype = sz
-    lib.pygat_wgrad.argtypes = [i, i, i, i, p, i64, p, p, p, p, i, p, i, i, i, p]
-    lib.pygat_dropout_mask.argtypes = [i64, f, p, u32, p, p]
-    lib.pygat_dropout_mask2.argtypes = [f, p, i64, u32, p, i64, u32, p, p]
-    lib.pygat_dropout_expand.argtypes = [i, i, i, p, i64, p, f, p, u32, p, i64, p]
-    lib.pygat_dropout_head_sum.argtypes = [i, i, i, p, i64, p, f, p, u32, p, i64, i, p]
-    lib.pygat_pack_blockdiag.argtypes = [i, i, i, p, p, p, i64, p]
-    lib.pygat_unpack_blockdiag.argtypes = [i, i, i, p, i64, i, p, p]
-    lib.pygat_headmask_supported.argtypes = [i, i, i]
-    lib.pygat_dropout_bits.argtypes = [i, i, i, f, p, i, p, p]
-    lib.pygat_project_dropout_workspace_bytes.argtypes = [i, i, i, i, i]
-    lib.pygat_project_dropout_workspace_bytes.restype = sz
-    lib.pygat_project_dropout.argtypes = [i, i, i, i, p, i64, p, f, p, i64, p, p, i, p, p]
-    lib.pygat_wgrad_dropout_workspace_bytes.argtypes = [i, i, i, i, i]
-    lib.pygat_wgrad_dropout_workspace_bytes.restype = sz
-    lib.pygat_wgrad_dropout.argtypes = [i, i, i, i, p, i64, p, f, p, p, i64, p, i, p, p]
-    lib.pygat_dropout_head_sum_bits.argtypes = [i, i, i, p, i64, p, f, p, i64, i, p]
-    lib.pygat_project_sparse.argtypes = [i, i, i, i, p, p, p, p, i64, f, p, i, p, p, p, p, p]
-    lib.pygat_wgrad_sparse.argtypes = [i, i, i, i, i, p, p, p, p, p, p, f, p, i, p, p, p, i64, p, p, p, p]
-    lib.pygat_wgrad_sparse_workspace_bytes.argtypes = [i, i, i, i]
-    lib.pygat_dropout_narrow.argtypes = [i, i, i, i]
-    lib.pygat_bce_workspace_bytes.argtypes = [i64]
-    lib.pygat_bce_workspace_bytes.restype = sz
-    lib.pygat_bce_with_logits.argtypes = [i64, p, p, p, p, p]
-    lib.pygat_bce_with_logits_backward.argtypes = [i64, p, p, p, p, p]
-    lib.pygat_adam_step.argtypes = [i, p, p, p, p, p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, p, p]
-    lib.pygat_dx_dropout.argtypes = [i, i, i, i, p, p, i64, p, f, p, i64, p, i64, i, p]
-    lib.pygat_wgrad_sparse_workspace_bytes.restype = sz
-    lib.pygat_nll_workspace_bytes.argtypes = [i]
-    lib.pygat_nll_workspace_bytes.restype = sz
-    lib.pygat_elu_logsoftmax_nll.argtypes = [i, i, p, i64, p, p, p, p, p]
-    lib.pygat_elu_logsoftmax_nll_backward.argtypes = [i, i, p, i64, p, p, p, p, i64, p]
-    for s in SYMBOLS:
-        fn = getattr(lib, s)
-        if fn.restype is C.c_int or s in ("pygat_abi_version", "pygat_padded_width", "pygat_device_count", "pygat_default_gemm_mode"):
-            fn.restype = i
+    for name, (ret, params) in _FUNCS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _ctype(ret), [_ctype(t) for t, _ in params]
     if lib.pygat_abi_version() != ABI_VERSION:
         raise ImportError(f"pygat_amd: ABI version {lib.pygat_abi_version()} != {ABI_VERSION}")
     return lib
@@ -240,51 +206,46 @@ def check(rc: int, what: str = "") -> None:
     if rc == 0:
         return
     msg = lib.pygat_last_error().decode(errors="replace")
-    if rc == -1:
+    if rc == EINVAL:
         raise ValueError(f"pygat_amd {what}: {msg}")
     raise RuntimeError(f"pygat_amd {what}: {msg} (code {rc})")
 
 
+def _workspace_bytes(what: str, *sizes) -> int:
+    """A size query that answers through its last argument: pygat_<what>(sizes..., size_t* bytes)."""
+    n = C.c_size_t(0)
+    check(getattr(lib, "pygat_" + what)(*map(int, sizes), C.byref(n)), what)
+    return n.value
+
+
 def alpha_grad_workspace_bytes(nnz: int, H: int) -> int:
     """Partial records of the long rows of pygat_alpha_grad_rows / _cols (pygat_alpha_grad_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_alpha_grad_workspace_bytes(int(nnz), int(H), C.byref(n)), "alpha_grad_workspace_bytes")
-    return n.value
+    return _workspace_bytes("alpha_grad_workspace_bytes", nnz, H)
 
 
 def edge_workspace_bytes(nnz: int, H: int, f_out: int) -> int:
     """Scratch of the edge-logit passes (pygat_gat_edge_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_gat_edge_workspace_bytes(int(nnz), int(H), int(f_out), C.byref(n)), "gat_edge_workspace_bytes")
-    return n.value
+    return _workspace_bytes("gat_edge_workspace_bytes", nnz, H, f_out)
 
 
 def bf16_workspace_bytes(nnz: int, slot_edges: int, H: int, f_out: int) -> int:
     """Partial records of the bf16-table forward (pygat_gat_bf16_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_gat_bf16_workspace_bytes(int(nnz), int(slot_edges), int(H), int(f_out), C.byref(n)), "gat_bf16_workspace_bytes")
-    return n.value
+    return _workspace_bytes("gat_bf16_workspace_bytes", nnz, slot_edges, H, f_out)
 
 
 def spmm_workspace_bytes(nnz: int, H: int, F: int) -> int:
     """Partial records of the long rows of pygat_spmm_forward (pygat_spmm_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_spmm_workspace_bytes(int(nnz), int(H), int(F), C.byref(n)), "spmm_workspace_bytes")
-    return n.value
+    return _workspace_bytes("spmm_workspace_bytes", nnz, H, F)
 
 
 def edge_softmax_workspace_bytes(nnz: int, H: int) -> int:
     """Partial records of the long rows of pygat_edge_softmax_rows / _grad_rows (pygat_edge_softmax_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_edge_softmax_workspace_bytes(int(nnz), int(H), C.byref(n)), "edge_softmax_workspace_bytes")
-    return n.value
+    return _workspace_bytes("edge_softmax_workspace_bytes", nnz, H)
 
 
 def dot_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
     """Partial records of the long rows of pygat_dot_attn_forward / _backward_rows (pygat_dot_attn_workspace_bytes)."""
-    n = C.c_size_t(0)
-    check(lib.pygat_dot_attn_workspace_bytes(int(nnz), int(H), int(F), C.byref(n)), "dot_attn_workspace_bytes")
-    return n.value
+    return _workspace_bytes("dot_attn_workspace_bytes", nnz, H, F)
 
 
 def padded_width(f_out: int) -> int:

@@ -246,15 +246,15 @@ def _split_k(M: int, N: int, K: int, streamed_k: bool = False, mode: Optional[st
     return max(1, min(256, 1024 // tiles, K // 256, max(by_traffic, want))) if tiles < 1024 else 1
 
 
-GEMM_MODES = {"split-bf16": 0, "fp32-mfma": 1}     # PYGAT_GEMM_SPLIT_BF16 / PYGAT_GEMM_FP32_MFMA
+GEMM_MODES = {"split-bf16": _lib.GEMM_SPLIT_BF16, "fp32-mfma": _lib.GEMM_FP32_MFMA}
 _mode_tls = threading.local()                        # the calling thread's choice; None = the library's default
 
 
 def _mode_code(mode: Optional[str] = None) -> int:
     """The `gemm_mode` argument of a C call: an explicit name, else this thread's set_gemm_mode choice, else
-    PYGAT_GEMM_DEFAULT (-1: split-bf16 unless PYGAT_GEMM_F32=1 was in the environment when the library was loaded)."""
+    PYGAT_GEMM_DEFAULT (split-bf16 unless PYGAT_GEMM_F32=1 was in the environment when the library was loaded)."""
     mode = mode or getattr(_mode_tls, "mode", None)
-    return -1 if mode is None else GEMM_MODES[mode]
+    return _lib.GEMM_DEFAULT if mode is None else GEMM_MODES[mode]
 
 
 def set_gemm_mode(mode: Optional[str]) -> None:
@@ -657,7 +657,7 @@ def no_table_dtype(table_dtype, what: str) -> None:
 
 
 PAD_K = _config.pad_k     # development knob: 0 = run odd input widths as they are
-MAX_HEAD_TABLE = 16     # PYGAT_MAX_HEADS_TABLE: heads whose parameter pointers travel as kernel arguments
+MAX_HEAD_TABLE = _lib.MAX_HEADS_TABLE     # heads whose parameter pointers travel as kernel arguments
 
 
 class GATLevelHeadsFn(torch.autograd.Function):

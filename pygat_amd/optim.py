@@ -11,7 +11,7 @@ from typing import Iterable
 
 import torch
 
-from ._lib import lib, check, MAX_ADAM_TENSORS
+from ._lib import lib, check, ADAM_STATE_BYTES, MAX_ADAM_TENSORS
 
 
 class Adam(torch.optim.Optimizer):
@@ -36,7 +36,7 @@ class Adam(torch.optim.Optimizer):
                 if "exp_avg" not in st:
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            chunks = [(ps[i:i + MAX_ADAM_TENSORS], torch.zeros(6, dtype=torch.int32, device=ps[0].device))     # PYGAT_ADAM_STATE_BYTES
+            chunks = [(ps[i:i + MAX_ADAM_TENSORS], torch.zeros(ADAM_STATE_BYTES // 4, dtype=torch.int32, device=ps[0].device))
                       for i in range(0, len(ps), MAX_ADAM_TENSORS)] if ps else []
             loaded = (self._loaded_steps or {}).pop(gi, None)
             if loaded is not None:

@@ -225,3 +225,105 @@ def test_python_switches_are_read_once_in_one_place():
     assert not offenders, offenders
     from pygat_amd.config import Config, config
     assert config.describe().keys() == Config.from_env().describe().keys() and config.dist_chunks >= 1
+
+
+# ---- the binding is read from the header (pygat_amd/_lib.py parse_header): literal expectations, written out here ----
+
+SIZE_T_FUNCTIONS = {"pygat_scan_workspace_bytes", "pygat_gemm_workspace_bytes", "pygat_partials_bytes",
+                    "pygat_gat_backward_col_da_bytes", "pygat_agrad_workspace_bytes", "pygat_wgrad_workspace_bytes",
+                    "pygat_gatv2_workspace_bytes", "pygat_project_dropout_workspace_bytes",
+                    "pygat_wgrad_dropout_workspace_bytes", "pygat_nll_workspace_bytes", "pygat_wgrad_sparse_workspace_bytes",
+                    "pygat_bce_workspace_bytes"}
+
+
+def test_hard_declarations_bind_as_written(lib):
+    """Declarations a loose reader would get wrong: pointer-to-pointer and const pointers, host int* / char* arguments,
+    struct pointers, unsigned char*, the non-int return types."""
+    L, p, i, d = lib.lib, C.c_void_p, C.c_int, C.c_double
+    assert L.pygat_adam_step.argtypes == [i, p, p, p, p, p, d, d, d, d, d, p, p]
+    assert L.pygat_kernel_footprint.argtypes == [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    assert L.pygat_device_name.argtypes == [C.c_char_p, C.c_int]
+    assert L.pygat_gat_forward.argtypes[0] is C.POINTER(lib.Graph)
+    blocked = L.pygat_gemm_f32_blocked.argtypes
+    assert blocked[7] is C.POINTER(lib.ColBlocks) and blocked[11] is C.POINTER(lib.ColBlocks)
+    assert blocked[10] is C.POINTER(lib.OutSegments)
+    assert [t for t in blocked if t not in (i, C.c_int64, p)] == [blocked[7], blocked[10], blocked[11]]
+    assert L.pygat_dropout_bits.argtypes == [i, i, i, C.c_float, p, i, p, p]          # unsigned char* bits: an address
+    assert L.pygat_last_error.restype is C.c_char_p
+    assert {n for n in lib.SYMBOLS if getattr(L, n).restype is C.c_size_t} == SIZE_T_FUNCTIONS
+    assert all(getattr(L, n).restype is C.c_int for n in lib.SYMBOLS if n not in SIZE_T_FUNCTIONS | {"pygat_last_error"})
+    for n in ("pygat_abi_version", "pygat_last_error", "pygat_device_count"):          # declared (void)
+        assert getattr(L, n).argtypes == []
+
+
+def test_struct_mirrors_follow_the_header(lib):
+    assert [f for f, _ in lib.Graph._fields_] == [
+        "n", "nnz", "rowptr", "edge_rc", "slot_edges", "slot_begin", "cut_rows", "n_cut", "n_cut_wide", "slot_first",
+        "slot_count", "slot_meta", "slot_order", "user_row"]
+    assert [t for _, t in lib.Graph._fields_] == [
+        C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert lib.OutSegments._fields_ == [("nseg", C.c_int), ("col_start", C.c_int32 * 5), ("ptr", C.c_void_p * 4),
+                                        ("ld", C.c_int64 * 4)]
+    assert lib.ColBlocks._fields_ == [("w", C.c_int), ("stride", C.c_int64)]
+    g = lib.Graph(3, 7, None, None, 64)                  # positional construction in header order
+    assert (g.n, g.nnz, g.slot_edges, g.user_row) == (3, 7, 64, None)
+
+
+def test_constants_keep_their_values(lib):
+    from pygat_amd import ops
+    consts = lib.parse_header(open(os.path.join(ROOT, "include", "pygat_amd.h")).read())[0]
+    assert consts == {"PYGAT_ABI_VERSION": 16, "PYGAT_OK": 0, "PYGAT_EINVAL": -1, "PYGAT_EHIP": -2, "PYGAT_ENODEV": -3,
+                      "PYGAT_F_ELU": 1, "PYGAT_F_SKIP": 2, "PYGAT_F_MAIN_ONLY": 4, "PYGAT_F_FIXUP_ONLY": 8,
+                      "PYGAT_GEMM_DEFAULT": -1, "PYGAT_GEMM_SPLIT_BF16": 0, "PYGAT_GEMM_FP32_MFMA": 1,
+                      "PYGAT_MAX_SEGMENTS": 4, "PYGAT_MAX_HEADS_TABLE": 16, "PYGAT_ADAM_MAX_TENSORS": 48,
+                      "PYGAT_ADAM_STATE_BYTES": 24}
+    assert (lib.ABI_VERSION, lib.F_ELU, lib.F_SKIP, lib.F_MAIN_ONLY, lib.F_FIXUP_ONLY) == (16, 1, 2, 4, 8)
+    assert (lib.MAX_SEGMENTS, lib.MAX_ADAM_TENSORS, lib.ADAM_STATE_BYTES // 4, lib.EINVAL) == (4, 48, 6, -1)
+    assert ops.MAX_HEAD_TABLE == 16 and ops.GEMM_MODES == {"split-bf16": 0, "fp32-mfma": 1}
+    assert ops._mode_code("fp32-mfma") == 1 and lib.GEMM_DEFAULT == -1
+
+
+GOOD_HEADER = """
+#define PYGAT_N 2
+enum { PYGAT_A = 1, PYGAT_B = -3 };
+typedef struct { int n; const float* rows[PYGAT_N + 1]; int64_t ld[PYGAT_N]; int32_t tag[3]; } pygat_t;
+/* a comment naming pygat_ghost(int) declares nothing */
+int pygat_one(void);
+size_t pygat_two(const pygat_t* t, const float* const* W,
+                 unsigned char *bits, int64_t n, void* stream);
+"""
+
+
+def test_parser_reads_exactly_what_is_declared(lib):
+    consts, structs, funcs = lib.parse_header(GOOD_HEADER)
+    assert consts == {"PYGAT_N": 2, "PYGAT_A": 1, "PYGAT_B": -3}
+    assert structs == {"pygat_t": [("int", "n", None), ("const float*", "rows", 3), ("int64_t", "ld", 2), ("int32_t", "tag", 3)]}
+    assert funcs == {"pygat_one": ("int", []),
+                     "pygat_two": ("size_t", [("const pygat_t*", "t"), ("const float* const*", "W"), ("unsigned char*", "bits"),
+                                              ("int64_t", "n"), ("void*", "stream")])}
+    assert list(funcs) == ["pygat_one", "pygat_two"]
+
+
+@pytest.mark.parametrize("decl, name", [
+    ("int pygat_x(long q);", "pygat_x"),                                          # a scalar type the rule does not cover
+    ("int pygat_x(int n, long* q);", "pygat_x"),                                  # ... nor a pointer to one
+    ("int pygat_cb(int n, void (*done)(int), void* stream);", "pygat_cb"),        # function pointer
+    ("int pygat_va(const char* fmt, ...);", "pygat_va"),                          # varargs
+    ("typedef struct { int n; float* ptr[PYGAT_NOWHERE]; } pygat_s;", "pygat_s"),  # extent that resolves to nothing
+    ("typedef struct { int n; float* ptr[2 * PYGAT_N]; } pygat_s;", "pygat_s"),    # an expression outside the rule
+    ("typedef struct { long n; } pygat_s;", "pygat_s"),                           # unknown field type
+    ("long pygat_r(int n);", "pygat_r"),                                          # unknown return type
+    ("int pygat_arr(int n[4]);", "pygat_arr"),                                    # array parameter
+    ("static inline int pygat_body(int n) { return n; }", "pygat_body"),          # a definition, not a declaration
+], ids=["scalar", "pointee", "function-pointer", "varargs", "extent-name", "extent-expr", "field", "return", "array",
+        "definition"])
+def test_parser_refuses_what_it_cannot_read(lib, decl, name):
+    with pytest.raises(lib.HeaderError, match=name):
+        lib.parse_header(GOOD_HEADER + decl + "\n")
+
+
+def test_parser_skips_no_name_of_the_header(lib):
+    funcs = lib.parse_header(open(os.path.join(ROOT, "include", "pygat_amd.h")).read())[2]
+    assert set(header_functions()) <= set(funcs) and len(funcs) == len(header_functions())
+    assert list(funcs) == lib.SYMBOLS
