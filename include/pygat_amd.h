@@ -744,6 +744,46 @@ int pygat_dot_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* ro
                                       const float* G, int64_t ldg, float* dq, int64_t lddq, float* P, float* S, float* de,
                                       int64_t ldde, float* dbias, void* ws, void* stream);
 
+/* ------------------------------------------------ K20: the GAT score fused over an edge pattern (csrc/k20_additive_attention.hip)
+ * Additive under ABI 16 (no existing entry point changes).  For H heads, over a CSR pattern (rowptr [n_rows + 1], col [nnz]) whose row
+ * side and column side are different tables, s_dst [n_rows x H] and s_src [n_cols x H] (dense, 4-byte loads) and v [n_cols x H*F]:
+ *   forward        z[e, h] = s_dst[i, h] + s_src[j, h] for entry e = (i, j), one rounded add;  with edge_logit: z = (s_dst[i, h] +
+ *                  s_src[j, h]) + edge_logit[c(e) * (logit_head_stride ? H : 1) + h * logit_head_stride], two rounded adds in this
+ *                  order, c(e) the CALLER's entry index of CSR position e (perm[e]; perm may be null: the position itself);
+ *                  l = z > 0 ? z : negative_slope z;  out[i, h, :] = sum_{e in row i} softmax_row(l)[e, h] v[j, h, :] in one pass (an
+ *                  online softmax: nothing per entry is written);  m[i, h] = max_e l[e, h],  Z[i, h] = sum_e exp(l[e, h] - m[i, h]),
+ *                  [n_rows x H], always written: with out they are all backward_rows needs.
+ *   backward_rows  D[i, h] = <G[i, h], out[i, h]>,  p = exp(l - m[i, h]) / Z[i, h],  dz = p (<G[i, h], v[j, h]> - D[i, h]) (z > 0 ? 1 :
+ *                  negative_slope);  ds_dst[i, h] = sum_{e in row i} dz, [n_rows x H];  P[c(e), h] = p and S[c(e), h] = dz, [nnz x H] in
+ *                  the CALLER's entry order.  S is the gradient of edge_logit ([nnz x H]; of a [nnz] one its sum over h, the
+ *                  caller's).  The column side is K17 on the transposed pattern: dv = pygat_spmm_forward(val = P, b = G), ds_src =
+ *                  pygat_spmm_forward(val = S, b = ones [n_rows x H x 1]).
+ * edge_logit == NULL selects the kernels without the term: they carry no entry index through their walk, the forward does not read
+ * perm, and logit_head_stride is not looked at; perm may be null then, and for a pattern in CSR order.  logit_head_stride 1:
+ * edge_logit [nnz x H]; 0: [nnz], one value per entry shared by the heads.  An edge_logit of zeros changes no bit of out, ds_dst, P or S.
+ * Its values must be finite and are not checked; a large negative finite one (-9e15) masks an entry exactly -- p = 0, no share of out,
+ * exact zeros in P and S -- while its row keeps another entry and negative_slope > 0 (at slope 0, l = 0: no mask).
+ * Rows of v / out / G are H*F floats, heads side by side, NOT padded, 16-byte aligned, with row strides >= H*F that are multiples of 4
+ * floats.  Repeated (row, col) pairs are separate entries.  A row without entries gets out = m = Z = ds_dst = 0 exactly and its G row is
+ * not read; a row of one entry (i, j) gets out_i = v_j bit for bit and dz = 0 exactly.  Limits, refused with PYGAT_EINVAL before
+ * anything is launched: 1 <= H <= 64, F a power of two in 4..256 (zero-padding the columns of v to the next allowed F leaves the
+ * first F columns of the result unchanged), H*F <= 1024, 0 <= nnz < 2^31, a negative_slope that is not finite, null or misaligned
+ * tables (the message names the argument), short strides, a logit_head_stride other than 0 or 1.  col / perm are NOT range-checked.
+ * ws >= the size pygat_add_attn_workspace_bytes reports = 5 records of H*F + 2 H floats (rounded up to 4) per 2048-entry chunk,
+ * 16-byte aligned, the caller's (both launchers may share it): the partial (acc, m, Z) records, or the H sums of dz, of the long rows,
+ * merged in chunk order (csrc/long_rows.h).  fp32, no float atomics, fixed summation order: bitwise reproducible.  Nothing allocates or
+ * synchronises. */
+int pygat_add_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes);   /* an error code like the launchers */
+int pygat_add_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H, int F,
+                           float negative_slope, const float* s_dst, const float* s_src, const float* v, int64_t ldv,
+                           const float* edge_logit, int logit_head_stride, float* out, int64_t ldo, float* m, float* Z, void* ws,
+                           void* stream);
+int pygat_add_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                 int F, float negative_slope, const float* s_dst, const float* s_src, const float* v, int64_t ldv,
+                                 const float* edge_logit, int logit_head_stride, const float* out, int64_t ldo, const float* m,
+                                 const float* Z, const float* G, int64_t ldg, float* ds_dst, float* P, float* S, void* ws,
+                                 void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

@@ -248,6 +248,11 @@ def dot_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
     return _workspace_bytes("dot_attn_workspace_bytes", nnz, H, F)
 
 
+def add_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
+    """Partial records of the long rows of pygat_add_attn_forward / _backward_rows (pygat_add_attn_workspace_bytes)."""
+    return _workspace_bytes("add_attn_workspace_bytes", nnz, H, F)
+
+
 def padded_width(f_out: int) -> int:
     fp = lib.pygat_padded_width(int(f_out))
     if fp == 0:

@@ -1,0 +1,168 @@
+"""The GAT score over the entries of a sparse pattern whose two sides are different tables -- a sampled block of a large graph
+(destination nodes x sampled sources), attention from one node set to another, a GAT head inside a model built from the pattern ops.
+
+  additive_attention  out[i, h, :] = sum over the entries e = (i, j) of row i of
+                      softmax_row(LeakyReLU(s_dst[i, h] + s_src[j, h] (+ edge_logit[e, h])))[e, h] * v[j, h, :]
+                      fused, on the K20 kernels (csrc/k20_additive_attention.hip): an online softmax per row, nothing written per entry
+
+    pattern = EdgePattern.from_indices(indices [2, E], (n_dst, n_src))      # or graph.edge_pattern()
+    out = additive_attention(pattern, s_dst, s_src, v)                      # s_dst [n_dst, H], s_src [n_src, H], v [n_src, H, F]
+    out = spmm(pattern, edge_softmax(pattern, F.leaky_relu(s_dst[row] + s_src[col], 0.2)), v)      # the same, from parts
+    out = additive_attention(pattern, s_dst, s_src, v, 0.2, edge_logit=emb(edge_type))             # gat_level's edge_logit, [E, H] | [E]
+
+A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the pattern
+rectangular.  Differentiable in every tensor.  The backward keeps out and (m, Z) per row; its two per-entry tensors P and S ([E, H]
+each) live only inside backward, between the row pass and the transposed SpMMs that form dv and ds_src.  fp32, no float atomics, a
+fixed summation order: two runs give the same bits.  Nothing is read back to the host.  There is no CPU path and no fallback to torch.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from ._lib import lib, check
+from .dot_attention import MIN_F, MAX_F, _require_pattern, _require_tensor
+from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
+
+_OP = "additive_attention"
+_PAD_HINT = ("zero-padding the columns of v to the next allowed F leaves the first F columns of the result unchanged (no scale "
+             "depends on F)")
+
+
+def _slope(negative_slope) -> float:
+    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
+        raise ValueError(f"pygat_amd {_OP}: negative_slope = {negative_slope!r}: a finite float expected")
+    return float(negative_slope)
+
+
+def _checked(pattern, s_dst, s_src, v, edge_logit):
+    """Every refusal that looks at the pattern and the tensors, those of edge_logit alone first -> (H, F, no head axis, the logit's
+    head stride | None)."""
+    if edge_logit is not None:
+        _require_tensor(_OP, pattern, "edge_logit", edge_logit)
+    _require_pattern(_OP, pattern)
+    for name, t in (("s_dst", s_dst), ("s_src", s_src), ("v", v)):
+        _require_tensor(_OP, pattern, name, t)
+    named = (("s_dst", s_dst, pattern.n_rows, "rows"), ("s_src", s_src, pattern.n_cols, "columns"), ("v", v, pattern.n_cols, "columns"))
+    if s_dst.dim() not in (1, 2):
+        raise ValueError(f"pygat_amd {_OP}: s_dst [n_rows] or [n_rows, H] expected, got {tuple(s_dst.shape)}")
+    if s_src.dim() != s_dst.dim() or s_src.shape[1:] != s_dst.shape[1:]:
+        raise ValueError(f"pygat_amd {_OP}: s_src {tuple(s_src.shape)} does not match s_dst {tuple(s_dst.shape)}: the same number of "
+                         f"heads expected")
+    if v.dim() != s_dst.dim() + 1 or v.shape[1:-1] != s_dst.shape[1:]:
+        raise ValueError(f"pygat_amd {_OP}: v {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: v [n_cols, F] with s_dst "
+                         f"[n_rows], or v [n_cols, H, F] with s_dst [n_rows, H] and the same number of heads, expected")
+    for name, t, rows, side in named:
+        if t.shape[0] != rows:
+            raise ValueError(f"pygat_amd {_OP}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+    flat = s_dst.dim() == 1
+    H, F = (1 if flat else int(s_dst.shape[1])), int(v.shape[-1])
+    if not (1 <= H <= MAX_HEADS):
+        raise ValueError(f"pygat_amd {_OP}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
+    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
+        raise ValueError(f"pygat_amd {_OP}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
+    if H * F > MAX_ROW_FLOATS:
+        raise ValueError(f"pygat_amd {_OP}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
+                         f"{_PAD_HINT}")
+    return H, F, flat, None if edge_logit is None else _logit_head_stride(pattern, edge_logit, H, flat)
+
+
+def _logit_head_stride(pattern, edge_logit, H: int, flat: bool) -> int:
+    """1: one value per entry and head ([E, H]; [E] where the tensors have no head axis); 0: one per entry, shared by the heads."""
+    E = pattern.nnz
+    if tuple(edge_logit.shape) == (E,):
+        return 1 if flat else 0
+    if not flat and tuple(edge_logit.shape) == (E, H):
+        return 1
+    want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
+    raise ValueError(f"pygat_amd {_OP}: edge_logit {want} expected for E = {E} entries and H = {H} heads, got "
+                     f"{tuple(edge_logit.shape)}")
+
+
+def _launch(pattern, which: str, H: int, F: int, slope: float, sd, ss, vc, uc, uhs, rest):
+    """One K20 launcher call, `which` "forward" or "backward_rows": the pattern's arrays, the three tables, the logit (None: the
+    kernels without the term, which need no permutation in the forward), then `rest`, the pass's own arguments up to the workspace."""
+    ws = torch.empty(_lib.add_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=vc.device)
+    check(getattr(lib, f"pygat_add_attn_{which}")(pattern.n_rows, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col),
+                                                   _ptr(pattern.perm), H, F, slope, _ptr(sd), _ptr(ss), _ptr(vc), H * F, _ptr(uc),
+                                                   uhs or 0, *rest, _ptr(ws), _stream()), f"add_attn_{which}")
+
+
+class _AdditiveAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pattern, s_dst, s_src, v, slope, edge_logit):
+        H, F, flat, uhs = _checked(pattern, s_dst, s_src, v, edge_logit)
+        ctx.pattern, ctx.slope, ctx.hf, ctx.uhs = pattern, slope, (H, F), uhs
+        if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
+            ctx.save_for_backward(s_dst, s_src, v, edge_logit, None, None, None)
+            return torch.zeros((pattern.n_rows,) + tuple(v.shape[1:]), dtype=torch.float32, device=v.device)
+        sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
+        n, dev = pattern.n_rows, vc.device
+        with torch.cuda.device(dev):
+            out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
+            m, Z = (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
+            _launch(pattern, "forward", H, F, slope, sd, ss, vc, uc, uhs, (_ptr(out), H * F, _ptr(m), _ptr(Z)))
+        out = out.view((n,) + tuple(v.shape[1:]))
+        ctx.save_for_backward(s_dst, s_src, v, edge_logit, out, m, Z)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        s_dst, s_src, v, edge_logit, out, m, Z = ctx.saved_tensors
+        pattern, slope, (H, F), uhs = ctx.pattern, ctx.slope, ctx.hf, ctx.uhs
+        if G.dtype != torch.float32:
+            raise ValueError(f"pygat_amd {_OP}: the gradient of the output must be float32, not {G.dtype}")
+        need_d, need_s, need_v = ctx.needs_input_grad[1:4]
+        need_u = edge_logit is not None and ctx.needs_input_grad[5]
+        if not (need_d or need_s or need_v or need_u):
+            return (None,) * 6
+        if out is None:                                            # no entries: zeros, nothing launched
+            zd, zs, zv, zu = (torch.zeros_like(t) if need else None for t, need in
+                              ((s_dst, need_d), (s_src, need_s), (v, need_v), (edge_logit, need_u)))
+            return None, zd, zs, zv, None, zu
+        n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, v.device
+        sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
+        Gc = G.contiguous().view(n, HF)
+        with torch.cuda.device(dev):
+            dd = torch.empty(n, H, dtype=torch.float32, device=dev)
+            P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            _launch(pattern, "backward_rows", H, F, slope, sd, ss, vc, uc, uhs,
+                    (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), _ptr(P), _ptr(S)))
+            du = None
+            if need_u:                          # S is the gradient of an [E, H] logit; an [E] one shared by H heads gets the sum over them
+                du = S.sum(1) if uhs == 0 else S.view(edge_logit.shape)
+            ds = dv = None
+            if need_s or need_v:
+                rowptr_t, row_t, perm_t = pattern.transposed()
+                if need_s:                      # the column sums of S: K17's F = 1 path against a table of ones
+                    ones = torch.ones(n, H, dtype=torch.float32, device=dev)
+                    ds = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, 1, S, ones).view(s_src.shape)
+                if need_v:
+                    dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
+        return None, dd.view(s_dst.shape) if need_d else None, ds, dv, None, du
+
+
+def additive_attention(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.Tensor, v: torch.Tensor, negative_slope: float = 0.2,
+                       edge_logit: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [n_rows, H, F] (s_dst [n_rows, H], s_src [n_cols, H], v [n_cols, H, F]) or out [n_rows, F] (s_dst [n_rows], s_src [n_cols],
+    v [n_cols, F]): out[i] = sum over the entries (i, j) of row i of softmax_j(LeakyReLU(s_dst[i] + s_src[j] + edge_logit[e])) * v[j],
+    per head -- the attention of a GAT level with the row side and the column side as different tables (for a level on one node set:
+    s_dst = Wh . a_dst, s_src = Wh . a_src, v = Wh).  z = (s_dst[i] + s_src[j]) + edge_logit[e] is two rounded adds in this order;
+    LeakyReLU has the slope negative_slope (a finite float) for z <= 0, and its derivative at z == 0 is negative_slope, as torch's.
+    A row without entries gets zeros; a pattern without entries launches nothing.
+    edge_logit (optional): a per-entry term in front of the LeakyReLU, gat_level's edge_logit, at the caller's entry index -- [E, H], or
+    [E] for one value per entry shared by the heads (and where the tensors have no head axis).  A logit of zeros changes no bit of the
+    result.  Its values must be finite (nothing is read back to check them); a large negative finite one such as -9e15 masks an entry
+    exactly -- its coefficient, its share of out and every gradient that passes through it are exact zeros -- provided the row keeps at
+    least one unmasked entry and negative_slope > 0.  It does not mask at negative_slope == 0: LeakyReLU then sends every negative z to 0.
+    Differentiable in s_dst, s_src, v and edge_logit (the gradient of an [E] logit is the sum over the heads); a gradient that is not
+    asked for costs no launch.  float32 GPU tensors on the pattern's device; 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024;
+    for another F zero-pad the columns of v: the first F columns of the result are unchanged.
+    Not provided: dropout on the coefficients, bfloat16 tables, a fused column pass (dv and ds_src are two K17 launches on the
+    transposed pattern)."""
+    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, _slope(negative_slope), edge_logit)
