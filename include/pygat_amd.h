@@ -784,6 +784,49 @@ int pygat_add_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr,
                                  const float* Z, const float* G, int64_t ldg, float* ds_dst, float* P, float* S, void* ws,
                                  void* stream);
 
+/* ------------------------------------------------ K21: the GATv2 score fused over an edge pattern (csrc/k21_gatv2_attention.hip)
+ * Additive under ABI 16 (no existing entry point changes).  For H heads, over a CSR pattern (rowptr [n_rows + 1], col [nnz]) whose row
+ * side and column side are different tables, x_dst [n_rows x H*F] and x_src [n_cols x H*F], an attention vector a [H x F] (dense)
+ * and a value table v [n_cols x H*F]; v == NULL: v is x_src, the gathered row serves the score and the sum (one gather per entry):
+ *   forward        t[f] = x_dst[i, h, f] + x_src[j, h, f] for entry e = (i, j), one rounded add;  g[f] = t[f] > 0 ? t[f] :
+ *                  negative_slope t[f];  s[e, h] = sum_f a[h, f] g[f] in a fixed order;  out[i, h, :] = sum_{e in row i}
+ *                  softmax_row(s)[e, h] v[j, h, :] in one pass (an online softmax: nothing per entry is written);  m[i, h] = max_e
+ *                  s[e, h],  Z[i, h] = sum_e exp(s[e, h] - m[i, h]), [n_rows x H], always written: with out they are all the backward needs.
+ *   backward_rows  D[i, h] = <G[i, h], out[i, h]>,  p = exp(s - m[i, h]) / Z[i, h],  S = p (<G[i, h], v[j, h]> - D[i, h]);
+ *                  dx_dst[i, h, f] = sum_{e in row i} S a[h, f] (t[f] > 0 ? 1 : negative_slope);  P[c(e), h] = p and S[c(e), h] = S,
+ *                  [nnz x H] in the CALLER's entry order, c(e) = perm[e] (perm may be null: the position itself).
+ *   backward_cols  on the transposed pattern (rowptr_t [n_cols + 1], row_t [nnz], perm_t [nnz] | null), S as backward_rows left it:
+ *                  dx_src[j, h, f] = sum_{e in column j} S[c(e), h] a[h, f] (t[f] > 0 ? 1 : negative_slope);  da[h, f] = sum over
+ *                  ALL entries of S[c(e), h] g[f], reduced from per-wave records in a fixed order.  Both are always written.
+ *   dv = pygat_spmm_forward(val = P, b = G) on the transposed pattern (K17), the caller's launch; with v == NULL the caller adds it
+ *   to dx_src.
+ * Rows of x_dst / x_src / v / out / G / dx_dst / dx_src are H*F floats, heads side by side, NOT padded, 16-byte aligned, with row
+ * strides >= H*F that are multiples of 4 floats; a and da are 16-byte aligned.  Repeated (row, col) pairs are separate entries.  A
+ * row without entries gets out = m = Z = dx_dst = 0 exactly and its G row is not read; a column without entries gets dx_src = 0; a
+ * row of one entry (i, j) gets out_i = v_j bit for bit and S = 0 exactly.  Limits, refused with PYGAT_EINVAL before anything is
+ * launched: 1 <= H <= 64, F a power of two in 4..256 (zero-padding the columns of x_dst, x_src, a and v to the next allowed F leaves
+ * the first F columns of the result unchanged: zero columns of a add nothing to a score), H*F <= 1024, 0 <= nnz < 2^31, a
+ * negative_slope that is not finite, null or misaligned tables (the message names the argument), short strides.  col / perm are NOT
+ * range-checked.  ws >= the size pygat_v2_attn_workspace_bytes reports, 16-byte aligned, the caller's (the three launchers may share
+ * it): 5 records of H*F + 2 H floats (rounded up to 4) per 2048-entry chunk -- the partial (acc, m, Z) records, or the H*F sums of
+ * dx, of the long rows and long columns, merged in chunk order (csrc/long_rows.h) -- and the da records of backward_cols: H*F floats,
+ * five per 2048-entry chunk (one of the long-column kernel, four of the column kernel, whose work-groups take a chunk's columns
+ * each; four for a pattern without entries) and one per partial sum of the reduce (128).  fp32, no float
+ * atomics, no LDS, fixed summation order: bitwise reproducible.  Nothing allocates or synchronises. */
+int pygat_v2_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes);   /* an error code like the launchers */
+int pygat_v2_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float negative_slope,
+                          const float* x_dst, int64_t ldd, const float* x_src, int64_t lds, const float* a, const float* v,
+                          int64_t ldv, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_v2_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds,
+                                const float* a, const float* v, int64_t ldv, const float* out, int64_t ldo, const float* m,
+                                const float* Z, const float* G, int64_t ldg, float* dx_dst, int64_t lddx, float* P, float* S,
+                                void* ws, void* stream);
+int pygat_v2_attn_backward_cols(int n_cols, int64_t nnz, const int32_t* rowptr_t, const int32_t* row_t, const int32_t* perm_t,
+                                int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                int64_t lds, const float* a, const float* S, float* dx_src, int64_t lddx, float* da, void* ws,
+                                void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

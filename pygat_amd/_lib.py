@@ -253,6 +253,12 @@ def add_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
     return _workspace_bytes("add_attn_workspace_bytes", nnz, H, F)
 
 
+def v2_attn_workspace_bytes(nnz: int, H: int, F: int) -> int:
+    """Partial records of the long rows and columns and the da records of pygat_v2_attn_forward / _backward_rows / _backward_cols
+    (pygat_v2_attn_workspace_bytes)."""
+    return _workspace_bytes("v2_attn_workspace_bytes", nnz, H, F)
+
+
 def padded_width(f_out: int) -> int:
     fp = lib.pygat_padded_width(int(f_out))
     if fp == 0:

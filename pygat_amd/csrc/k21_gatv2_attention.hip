@@ -1,0 +1,712 @@
+// K21 -- gatv2_attention: the GATv2 score a . LeakyReLU(x_dst_i + x_src_j) over the entries of every row of a sparse pattern whose row
+// side and column side are different tables, for H heads at once, in one pass, and both sides of its gradient.  One kernel family in
+// the shape of K19 and K20: (forward | backward rows | backward columns) x (long | row), instantiated per lane shape; the two row
+// passes also per SHARED, the compile-time flag of v == x_src; and the two kernels of the staged reduce of da.
+//
+// Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h, feature f:
+//   t[f] = x_dst[i, h, f] + x_src[j, h, f]             one rounded add
+//   g[f] = t[f] > 0 ? t[f] : slope t[f]                one rounded product
+//   s    = sum_f a[h, f] g[f]                          a fixed order: the lane's four elements (dot4), then the head's butterfly
+//                                                      (da_head_sum) -- the same bits in the forward and in the backward
+//   p    = exp(s - m[i, h]) / Z[i, h]                  m, Z [n_rows x H]: the row's maximum of s and its sum of exp(s - m)
+//   out[i, h, :] = sum_e p v[j, h, :]                  SHARED: v is x_src, the gathered row serves both, one gather per entry
+//   backward_rows:  D = <G[i, h], out[i, h]>,  dp = <G[i, h], v[j, h]>,  S = p (dp - D),
+//     dx_dst[i, h, f] = sum_e S a[h, f] g'(t[f])  (g' = 1 for t > 0, else the slope: the slope at t == 0, as torch), held in registers
+//     and written once per row,  P[c, h] = p and S[c, h] = S for the column side.
+//   backward_cols, on the transposed pattern: column j holds x_src[j] and a, gathers x_dst[i] and S[c] per entry:
+//     dx_src[j, h, f] = sum_e S a[h, f] g'(t[f]),  da[h, f] = sum over all entries of S g(t[f]).
+//   dv = spmm^T(P, G) is K17 on the transposed pattern, the caller's launch.
+//   The forward keeps out, m and Z, all the backward reads -- nothing per entry.
+//
+// Lane mapping: K19's (da_lanes.h).  Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  A group of LPR
+// lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane; the chunks of a head sit on LH = F / 4 adjacent lanes of one
+// chunk slot.  The walked side's own row and the lane's chunk of a are loaded once per row; per entry a lane loads its 16 bytes of the
+// gathered row (and of v_j without SHARED; the S scalars of its heads in the column pass), several entries in flight (v2_unroll), the
+// indices of the next batch asked for under this batch's arithmetic (v2_walk, after K19's da_walk).  One __expf per (entry, head)
+// goes into the online (m, Z, acc) state (da_fold).
+//
+// Long rows (and long columns) go through partial records (the rule of long_rows.h), one wave per chunk: its lane groups walk the
+// piece entry-interleaved and are merged by a fixed butterfly (the forward: maximum first, one rescale), and records merge in chunk
+// order.  A record is (acc[H F], m[H], Z[H]) forward and the H F sums of dx backward.
+//
+// da.  The column pass keeps the lane's chunk of da in registers, as a compensated sum (v2_da_add).  A work-group of the column
+// kernel takes the columns that BEGIN inside one 2048-entry chunk of the transposed entry array (a column without entries begins
+// where the next one does) -- work-groups of about equal work whatever the degrees are, which a fixed share of the columns is not:
+// on an R-MAT graph the heavy columns sit a power of two apart -- so a wave leaves ONE record of H F floats for all its columns, the
+// butterfly of its lane groups; a wave of the long-column kernel leaves one per chunk.  Two small kernels add the records in a
+// fixed order (V2_DA_STAGE partial sums, then their sum, compensated too), as the GATv2 level's da reduce does.  No LDS anywhere.
+//
+// Exactness.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.
+//   a row without entries   out = m = Z = dx_dst = 0 exactly; a column without entries dx_src = 0
+//   a row of one entry      out_i = v_j bit for bit and S = 0 exactly: D and dp are formed by the same routine on the same bits
+//   SHARED                  the same operations on the same values as the kernels without the flag fed a copy of x_src
+#include "da_lanes.h"
+#include <math.h>
+#include <string.h>
+
+namespace pygat {
+
+// The kernels take K19's argument block (DaArgs, da_lanes.h), so that its lane mapping and entry-index helpers serve as they stand:
+//   row passes:   q = x_dst (ldq),  k = x_src (ldk),  v (ldv; SHARED: not looked at),  bias = a [H x F],  scale = the negative slope,
+//                 dq = dx_dst (lddq)
+//   column pass:  the walked pattern is the transposed one: q = x_src (the walked side),  k = x_dst (the gathered side),  bias = a,
+//                 S read at the caller's entry index,  dq = dx_src,  de = the da records of the long-column kernel (one per chunk),
+//                 dbias = those of the column kernel (one per wave),  ldde = H F
+constexpr int V2_DA_STAGE = 128;               // partial sums between the da records and da
+
+// entries in flight: da_unroll's values
+__host__ __device__ constexpr int v2_unroll(bool bwd, int vec) { return da_unroll(bwd, vec); }
+
+__device__ __forceinline__ float4 v2_t(const float4& x, const float4& y) {
+  return make_float4(__fadd_rn(x.x, y.x), __fadd_rn(x.y, y.y), __fadd_rn(x.z, y.z), __fadd_rn(x.w, y.w));
+}
+__device__ __forceinline__ float v2_leaky1(float t, float slope) { return t > 0.f ? t : __fmul_rn(slope, t); }
+__device__ __forceinline__ float4 v2_leaky(const float4& t, float slope) {
+  return make_float4(v2_leaky1(t.x, slope), v2_leaky1(t.y, slope), v2_leaky1(t.z, slope), v2_leaky1(t.w, slope));
+}
+// y += c a g'(t)
+__device__ __forceinline__ void v2_dside(float4& y, float c, const float4& a, const float4& t, float slope) {
+  const float cs = c * slope;
+  y.x = fmaf(t.x > 0.f ? c : cs, a.x, y.x); y.y = fmaf(t.y > 0.f ? c : cs, a.y, y.y);
+  y.z = fmaf(t.z > 0.f ? c : cs, a.z, y.z); y.w = fmaf(t.w > 0.f ? c : cs, a.w, y.w);
+}
+// s += x with the rounding error of the sum carried in c (Kahan), every operation a rounded one in this order; s - c is the sum
+__device__ __forceinline__ void v2_kahan(float& s, float& c, float x) {
+  const float y = __fsub_rn(x, c), t = __fadd_rn(s, y);
+  c = __fsub_rn(__fsub_rn(t, s), y);
+  s = t;
+}
+// da += S g, compensated: da is a sum over ALL entries, which torch forms pairwise; a plain chain over a hub column of 699 entries at
+// one lane group per wave missed four times an fp32 torch run's own error by a few per cent at F = 64 and 256
+__device__ __forceinline__ void v2_da_add(float4& s, float4& c, float S, const float4& g) {
+  v2_kahan(s.x, c.x, __fmul_rn(S, g.x)); v2_kahan(s.y, c.y, __fmul_rn(S, g.y));
+  v2_kahan(s.z, c.z, __fmul_rn(S, g.z)); v2_kahan(s.w, c.w, __fmul_rn(S, g.w));
+}
+// the score of one (entry, chunk slot) from t: every lane of the head gets the head's
+template <int LPR>
+__device__ __forceinline__ float v2_score(const DaArgs& g, const float4& a, const float4& t) {
+  return da_head_sum<LPR>(dot4(a, v2_leaky(t, g.scale)), g.LH);
+}
+
+// U gathered entries, loaded before any is used.  MODE 0: forward, 1: backward rows (x = x_src[j]; v = v[j] without SHARED), 2: the
+// column pass (x = x_dst[i]; s = S[c, head of the chunk slot])
+template <int VEC, int U, int MODE, bool SHARED>
+struct V2Rows {
+  static constexpr bool SEP = MODE != 2 && !SHARED;
+  float4 x[U][VEC];
+  float4 v[SEP ? U : 1][SEP ? VEC : 1];
+  float s[MODE == 2 ? U : 1][MODE == 2 ? VEC : 1];
+  __device__ __forceinline__ const float4& val(int u, int c) const {
+    if constexpr (SEP) return v[u][c];
+    else return x[u][c];
+  }
+};
+template <int VEC, int U, int MODE, bool SHARED>
+__device__ __forceinline__ void v2_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], const int64_t (&ent)[U],
+                                          V2Rows<VEC, U, MODE, SHARED>& w) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    da_load_row<VEC>(g.k + (int64_t)src[u] * g.ldk, ln, w.x[u]);
+    if constexpr (MODE != 2 && !SHARED) da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+    if constexpr (MODE == 2) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) w.s[u][v] = g.S[ent[u] + ln.head[v]];
+    }
+  }
+}
+
+// The walk of all three passes, after K19's da_walk: the entries e0, e0 + step, ... < e1 of one row, handed to Fold::fold in that
+// order, U at a time and then one at a time.  The indices of the next U entries -- the other side's row and, in the backward passes,
+// the caller's entry index (da_entry) -- are asked for before this batch's gather is used, so an iteration waits for one gather, not
+// for an index and then a gather.  The forward carries no entry index and does not touch perm.
+template <int VEC, int MODE, bool SHARED, typename Fold, typename... Ctx>
+__device__ __forceinline__ void v2_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, Ctx&... ctx) {
+  constexpr int U = v2_unroll(MODE != 0, VEC);
+  int64_t e = e0;
+  if constexpr (U > 1) {
+    int32_t src[U];
+    int64_t ent[U], ent_next[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ent[u] = ent_next[u] = 0;
+    bool full = e + (U - 1) * step < e1;
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        src[u] = g.col[e + u * step];
+        if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+      }
+    }
+    while (full) {
+      if constexpr (MODE != 0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+      }
+      V2Rows<VEC, U, MODE, SHARED> w;
+      v2_gather<VEC, U, MODE, SHARED>(g, ln, src, ent, w);
+      e += U * step;
+      full = e + (U - 1) * step < e1;
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          src[u] = g.col[e + u * step];
+          if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+        }
+      }
+      Fold::fold(g, ln, ctx..., w, ent);
+    }
+  }
+  for (; e < e1; e += step) {
+    const int32_t src[1] = {g.col[e]};
+    int64_t ent[1] = {0};
+    if constexpr (MODE != 0) ent[0] = da_entry(g, e);
+    V2Rows<VEC, 1, MODE, SHARED> w;
+    v2_gather<VEC, 1, MODE, SHARED>(g, ln, src, ent, w);
+    Fold::fold(g, ln, ctx..., w, ent);
+  }
+}
+
+// what every pass holds of the walked side: its own row (x_dst[i]; x_src[j] in the column pass) and the lane's chunks of a
+template <int VEC>
+struct V2Own {
+  float4 x[VEC], a[VEC];
+};
+
+// ------------------------------------------------------------------------------------------------------------------------ forward
+template <int LPR, int VEC, bool SHARED>
+struct V2FwdFold {
+  template <int U>
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, const V2Own<VEC>& r, DaState<VEC>& st,
+                                              const V2Rows<VEC, U, 0, SHARED>& w, const int64_t (&)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const float s = v2_score<LPR>(g, r.a[v], v2_t(r.x[v], w.x[u][v]));
+        da_fold<false, false>(st.m[v], st.z[v], st.acc[v], s, 0.f, 1.f, w.val(u, v));
+      }
+  }
+};
+
+// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
+template <int LPR, int VEC, bool SHARED>
+__global__ __launch_bounds__(64) void v2_fwd_long_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int HF = g.H * g.F;
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    V2Own<VEC> r;
+    da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, r.x);
+    da_load_row<VEC>(g.bias, ln, r.a);
+    DaState<VEC> st;
+    da_init<VEC>(st);
+    v2_walk<VEC, 0, SHARED, V2FwdFold<LPR, VEC, SHARED>>(g, ln, e0 + grp, e1, EPW, r, st);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
+      float mx = st.m[v];
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+      const float f = __expf(st.m[v] - mx);                    // (a lane group without entries: 0 x 0)
+      st.z[v] *= f;
+      da_scale(st.acc[v], f);
+      st.m[v] = mx;
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1) {
+        st.z[v] += __shfl_xor(st.z[v], off);
+        da_add(st.acc[v], da_shfl_xor(st.acc[v], off));
+      }
+    }
+    if (grp == 0) {
+      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
+      da_store_row<VEC>(p, ln, st.acc);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        if (ln.lead >> v & 1) { p[HF + ln.head[v]] = st.m[v]; p[HF + g.H + ln.head[v]] = st.z[v]; }
+    }
+  });
+}
+
+// launch 2: one lane group per row
+template <int LPR, int VEC, bool SHARED>
+__global__ __launch_bounds__(256) void v2_fwd_row_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
+  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
+  const int HF = g.H * g.F;
+  DaState<VEC> st;
+  da_init<VEC>(st);
+  if (end - start > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        da_merge(st.m[v], st.z[v], st.acc[v], p[HF + ln.head[v]], p[HF + g.H + ln.head[v]], ld4(p + ln.ofs[v]));
+    });
+  } else if (end > start) {
+    V2Own<VEC> r;
+    da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
+    da_load_row<VEC>(g.bias, ln, r.a);
+    v2_walk<VEC, 0, SHARED, V2FwdFold<LPR, VEC, SHARED>>(g, ln, start, end, 1, r, st);
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (!(ln.ok >> v & 1)) continue;
+    const bool any = end > start;
+    const float z = st.z[v];
+    const float4 a = st.acc[v];
+    st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
+    if (ln.lead >> v & 1) {
+      g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
+      g.Z[row * g.H + ln.head[v]] = z;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- backward, row side
+template <int VEC>
+struct V2BwdRow {              // what the backward holds of its row
+  V2Own<VEC> own;
+  float4 G[VEC];
+  float m[VEC], rz[VEC], D[VEC];
+};
+
+template <int LPR, int VEC>
+__device__ __forceinline__ void v2_bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, V2BwdRow<VEC>& r) {
+  float4 o[VEC];
+  da_load_row<VEC>(g.q + row * g.ldq, ln, r.own.x);
+  da_load_row<VEC>(g.bias, ln, r.own.a);
+  da_load_row<VEC>(g.G + row * g.ldg, ln, r.G);
+  da_load_row<VEC>(g.out + row * g.ldo, ln, o);
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    r.m[v] = g.m[row * g.H + ln.head[v]];
+    r.rz[v] = 1.f / g.Z[row * g.H + ln.head[v]];
+    r.D[v] = da_head_sum<LPR>(dot4(r.G[v], o[v]), g.LH);
+  }
+}
+
+// the backward's fold of a batch; ctx: the row (V2BwdRow) and the lane's chunks of dx_dst.  In a row of one entry out_i is v_j bit for
+// bit, so dp and D are one routine on the same bits and S is an exact zero
+template <int LPR, int VEC, bool SHARED>
+struct V2BwdFold {
+  template <int U>
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, const V2BwdRow<VEC>& r, float4 (&dx)[VEC],
+                                              const V2Rows<VEC, U, 1, SHARED>& w, const int64_t (&ent)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const float4 t = v2_t(r.own.x[v], w.x[u][v]);
+        const float s = v2_score<LPR>(g, r.own.a[v], t);
+        const float p = __expf(s - r.m[v]) * r.rz[v];
+        const float dp = da_head_sum<LPR>(dot4(r.G[v], w.val(u, v)), g.LH);
+        const float S = p * (dp - r.D[v]);
+        v2_dside(dx[v], S, r.own.a[v], t, g.scale);
+        if (ln.lead >> v & 1) {
+          g.P[ent[u] + ln.head[v]] = p;
+          g.S[ent[u] + ln.head[v]] = S;
+        }
+      }
+  }
+};
+
+template <int VEC>
+__device__ __forceinline__ void v2_zero(float4 (&x)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) x[v] = da_zero4();
+}
+// the lane groups of a wave, a fixed butterfly
+template <int LPR, int VEC>
+__device__ __forceinline__ void v2_wave_sum(float4 (&x)[VEC]) {
+#pragma unroll
+  for (int off = LPR; off < 64; off <<= 1)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) da_add(x[v], da_shfl_xor(x[v], off));
+}
+
+// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the H F sums of dx_dst
+template <int LPR, int VEC, bool SHARED>
+__global__ __launch_bounds__(64) void v2_bwd_long_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    V2BwdRow<VEC> r;
+    v2_bwd_load<LPR, VEC>(g, ln, row, r);
+    float4 dx[VEC];
+    v2_zero<VEC>(dx);
+    v2_walk<VEC, 1, SHARED, V2BwdFold<LPR, VEC, SHARED>>(g, ln, e0 + grp, e1, EPW, r, dx);
+    v2_wave_sum<LPR, VEC>(dx);
+    if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dx);
+  });
+}
+
+// launch 2: one lane group per row
+template <int LPR, int VEC, bool SHARED>
+__global__ __launch_bounds__(256) void v2_bwd_row_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
+  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
+  float4 dx[VEC];
+  v2_zero<VEC>(dx);
+  if (end - start > LONG_ROW) {
+    for_long_records(start, end, [&](int64_t rec) {
+      const float* p = g.part + rec * g.pstride;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) da_add(dx[v], ld4(p + ln.ofs[v]));
+    });
+  } else if (end > start) {                                    // (a row without entries: its G row is not read)
+    V2BwdRow<VEC> r;
+    v2_bwd_load<LPR, VEC>(g, ln, row, r);
+    v2_walk<VEC, 1, SHARED, V2BwdFold<LPR, VEC, SHARED>>(g, ln, start, end, 1, r, dx);
+  }
+  da_store_row<VEC>(g.dq + row * g.lddq, ln, dx);
+}
+
+// ---------------------------------------------------------------------------------------------------------- backward, column side
+// the column pass's fold of a batch; ctx: the column's own row and a (V2Own), the lane's chunks of dx_src, of da and of da's
+// compensation
+template <int VEC>
+struct V2ColFold {
+  template <int U>
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, const V2Own<VEC>& r, float4 (&dx)[VEC],
+                                              float4 (&da)[VEC], float4 (&dc)[VEC], const V2Rows<VEC, U, 2, false>& w,
+                                              const int64_t (&)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const float4 t = v2_t(w.x[u][v], r.x[v]);              // x_dst[i] + x_src[j], the row pass's t
+        const float S = w.s[u][v];
+        v2_dside(dx[v], S, r.a[v], t, g.scale);
+        v2_da_add(da[v], dc[v], S, v2_leaky(t, g.scale));
+      }
+  }
+};
+
+// s <- s - c, the compensated sum, before the lane groups of a wave are added
+template <int VEC>
+__device__ __forceinline__ void v2_settle(float4 (&s)[VEC], const float4 (&c)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) { s[v].x -= c[v].x; s[v].y -= c[v].y; s[v].z -= c[v].z; s[v].w -= c[v].w; }
+}
+
+// launch 1: one wave per chunk of the transposed pattern; the piece of every long column inside the chunk -> one partial record, the
+// H F sums of dx_src; the wave's da of all its pieces -> da record `chunk`
+template <int LPR, int VEC>
+__global__ __launch_bounds__(64) void v2_col_long_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR;
+  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  float4 da[VEC], dc[VEC];
+  v2_zero<VEC>(da);
+  v2_zero<VEC>(dc);
+  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
+                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
+    V2Own<VEC> r;
+    da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, r.x);
+    da_load_row<VEC>(g.bias, ln, r.a);
+    float4 dx[VEC];
+    v2_zero<VEC>(dx);
+    v2_walk<VEC, 2, false, V2ColFold<VEC>>(g, ln, e0 + grp, e1, EPW, r, dx, da, dc);
+    v2_wave_sum<LPR, VEC>(dx);
+    if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dx);
+  });
+  v2_settle<VEC>(da, dc);
+  v2_wave_sum<LPR, VEC>(da);
+  if (grp == 0) da_store_row<VEC>(g.de + (int64_t)blockIdx.x * g.ldde, ln, da);
+}
+
+// the first c in [0, n] with rowptr[c] >= x (x <= rowptr[n])
+__device__ __forceinline__ int v2_first_at(const int32_t* rowptr, int n, int64_t x) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (rowptr[mid] >= x) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// launch 2: one work-group per chunk of LONG_CHUNK entries: the columns that begin inside the chunk (the last work-group: from its
+// chunk on, the columns without entries at the end among them), a lane group every (lane groups of the work-group)-th of them, so a
+// wave's da stays in registers over all its columns and leaves one record
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
+  constexpr int EPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / LPR;
+  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
+  V2Own<VEC> r;
+  da_load_row<VEC>(g.bias, ln, r.a);
+  float4 da[VEC], dc[VEC];
+  v2_zero<VEC>(da);
+  v2_zero<VEC>(dc);
+  const int64_t x0 = (int64_t)blockIdx.x * LONG_CHUNK;
+  const int c0 = v2_first_at(g.rowptr, g.n, x0);
+  const int c1 = blockIdx.x + 1 == gridDim.x ? g.n : v2_first_at(g.rowptr, g.n, x0 + LONG_CHUNK);
+  for (int64_t base = c0 + wave * EPW; base < c1; base += 4 * EPW) {                              // (uniform in the wave)
+    const int64_t row = base + grp;
+    if (row >= c1) continue;                                   // (whole lane groups; nothing inside the loop crosses a group)
+    const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
+    float4 dx[VEC];
+    v2_zero<VEC>(dx);
+    if (end - start > LONG_ROW) {                              // (its da went into the long-column kernel's records)
+      for_long_records(start, end, [&](int64_t rec) {
+        const float* p = g.part + rec * g.pstride;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) da_add(dx[v], ld4(p + ln.ofs[v]));
+      });
+    } else if (end > start) {
+      da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
+      v2_walk<VEC, 2, false, V2ColFold<VEC>>(g, ln, start, end, 1, r, dx, da, dc);
+    }
+    da_store_row<VEC>(g.dq + row * g.lddq, ln, dx);
+  }
+  v2_settle<VEC>(da, dc);
+  v2_wave_sum<LPR, VEC>(da);
+  if (grp == 0) da_store_row<VEC>(g.dbias + ((int64_t)blockIdx.x * 4 + wave) * g.ldde, ln, da);
+}
+
+// the da records -> da, two launches in a fixed order: V2_DA_STAGE work-groups, each the sum of every V2_DA_STAGE-th record; then
+// their sum.  Both sums are compensated (Kahan, in fp32, every operation a rounded one in this order): da is a sum over ALL entries
+// whose partial sums reach the size of the result long before the end, and a plain chain of 128 such steps alone cost more than the
+// whole of the rest (hub pattern, 4 x 64: 1.3e-4 on |da| = 201 against 3.3e-5 of an fp32 torch run)
+__global__ __launch_bounds__(256) void v2_da_stage_kernel(int R, int nrec, const float* __restrict__ part, float* __restrict__ out2) {
+  for (int c = threadIdx.x; c < R; c += 256) {
+    float acc = 0.f, comp = 0.f;
+    int b = blockIdx.x;
+    for (; b + 3 * V2_DA_STAGE < nrec; b += 4 * V2_DA_STAGE) {
+      const float x0 = part[(int64_t)b * R + c], x1 = part[(int64_t)(b + V2_DA_STAGE) * R + c];
+      const float x2 = part[(int64_t)(b + 2 * V2_DA_STAGE) * R + c], x3 = part[(int64_t)(b + 3 * V2_DA_STAGE) * R + c];
+      v2_kahan(acc, comp, x0); v2_kahan(acc, comp, x1); v2_kahan(acc, comp, x2); v2_kahan(acc, comp, x3);
+    }
+    for (; b < nrec; b += V2_DA_STAGE) v2_kahan(acc, comp, part[(int64_t)b * R + c]);
+    out2[(int64_t)blockIdx.x * R + c] = acc;
+  }
+}
+__global__ __launch_bounds__(256) void v2_da_final_kernel(int R, const float* __restrict__ part, float* __restrict__ da) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= R) return;
+  float acc = 0.f, comp = 0.f;
+  for (int b = 0; b < V2_DA_STAGE; ++b) v2_kahan(acc, comp, part[(int64_t)b * R + c]);
+  da[c] = acc;
+}
+
+// the table of the family: (SHARED, forward | backward rows | columns, long | row, lane shape) -> the kernel.  What a launcher starts
+// and what pygat_kernel_footprint reports on both come from here.  pass: 0 forward, 1 backward rows, 2 columns (no SHARED variant)
+template <int LPR, int VEC, bool SHARED>
+static const void* v2_kernel_at(int pass, bool lng) {
+  if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC>)
+                            : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC>);
+  if (pass == 1) return lng ? reinterpret_cast<const void*>(&v2_bwd_long_kernel<LPR, VEC, SHARED>)
+                            : reinterpret_cast<const void*>(&v2_bwd_row_kernel<LPR, VEC, SHARED>);
+  return lng ? reinterpret_cast<const void*>(&v2_fwd_long_kernel<LPR, VEC, SHARED>)
+             : reinterpret_cast<const void*>(&v2_fwd_row_kernel<LPR, VEC, SHARED>);
+}
+static const void* v2_kernel(bool shared, int pass, bool lng, int lpr, int vec) {
+  if (shared) PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, true>(pass, lng)));
+  else PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, false>(pass, lng)));
+  return nullptr;
+}
+
+// pygat_kernel_footprint: <prefix>{fwd,bwd,col}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k21_: a v table of its
+// own, k21s_: SHARED (fwd and bwd only: the column pass has one variant, under k21_); k21_da_stage, k21_da_final: the reduce of da
+int footprint_k21(const char* name, int* regs, int* scratch) {
+  static const struct { const char* prefix; bool shared; } names[] = {{"k21_", false}, {"k21s_", true}};
+  const void* fn = nullptr;
+  if (!strcmp(name, "k21_da_stage")) fn = reinterpret_cast<const void*>(&v2_da_stage_kernel);
+  if (!strcmp(name, "k21_da_final")) fn = reinterpret_cast<const void*>(&v2_da_final_kernel);
+  for (const auto& nm : names) {
+    char dir[8] = "", kind[8] = "", rest = 0;
+    int lpr = 0, vec = 0;
+    const size_t np = strlen(nm.prefix);
+    if (!fn && !strncmp(name, nm.prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 &&
+        lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 &&
+        (!strcmp(dir, "fwd") || !strcmp(dir, "bwd") || (!strcmp(dir, "col") && !nm.shared)) &&
+        (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
+      fn = v2_kernel(nm.shared, !strcmp(dir, "fwd") ? 0 : (!strcmp(dir, "bwd") ? 1 : 2), !strcmp(kind, "long"), lpr, vec);
+  }
+  if (!fn) {
+    set_error("kernel_footprint: unknown kernel '%s' (k21{,s}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, k21_col_{long,row}_l<LPR>v<VEC>, "
+              "k21_da_stage, k21_da_final)", name);
+    return PYGAT_EINVAL;
+  }
+  return kernel_footprint_of(fn, regs, scratch);
+}
+
+#define V2_PAD_HINT "zero-padding the columns of x_dst, x_src, a and v to the next allowed F leaves the first F columns of the result " \
+                    "unchanged: zero columns of a add nothing to a score"
+
+static int v2_check_shape(const char* what, int64_t nnz, int H, int F) {
+  PYGAT_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31), "%s: nnz %lld outside [0, 2^31) (int32 entry indexing)", what, (long long)nnz);
+  PYGAT_REQUIRE(H >= 1 && H <= 64, "%s: H=%d heads outside [1, 64]", what, H);
+  PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (" V2_PAD_HINT ")",
+                what, F);
+  PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
+  return PYGAT_OK;
+}
+
+// the workspace, in floats: the long-row records of a pass (every pass starts at the front), then the da records -- one per chunk of
+// the long-column kernel, then one per wave of the column kernel, four to a chunk -- then the staged partial sums
+static inline int64_t v2_part_floats(int64_t nnz, int H, int F) { return long_records(nnz) * da_pstride(H, F); }
+// (the column kernel's grid: a work-group per chunk of entries, one for a pattern without entries)
+static inline int64_t v2_col_blocks(int64_t nnz) { return nnz > 0 ? long_chunks(nnz) : 1; }
+static inline int64_t v2_da_records(int64_t nnz) { return long_chunks(nnz) + 4 * v2_col_blocks(nnz); }
+static inline int64_t v2_ws_floats(int64_t nnz, int H, int F) {
+  return v2_part_floats(nnz, H, F) + (v2_da_records(nnz) + V2_DA_STAGE) * (int64_t)H * F;
+}
+
+// what an entry point asks for, every argument under the name include/pygat_amd.h gives it; pass 0 forward, 1 backward rows, 2
+// backward columns (there n, rowptr, col, perm are n_cols, rowptr_t, row_t, perm_t); what a pass does not have stays zero
+struct V2Call {
+  const char* what;
+  int pass;
+  int n;
+  int64_t nnz;
+  const int32_t *rowptr, *col, *perm;
+  int H, F;
+  float negative_slope;
+  const float *x_dst, *x_src, *a, *v;
+  int64_t ldd, lds, ldv;
+  float* out;
+  int64_t ldo;
+  float *m, *Z;
+  const float* G;
+  int64_t ldg;
+  float* dx;                   // dx_dst | dx_src
+  int64_t lddx;
+  float *P, *S, *da;
+  void *ws, *stream;
+};
+
+// all three launchers: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
+static int v2_launch(const V2Call& c) {
+  const char* what = c.what;
+  const bool cols = c.pass == 2;
+  const int rc = v2_check_shape(what, c.nnz, c.H, c.F);
+  if (rc != PYGAT_OK) return rc;
+  PYGAT_REQUIRE(isfinite(c.negative_slope), "%s: negative_slope=%g, a finite slope expected", what, (double)c.negative_slope);
+  const char* nname = cols ? "n_cols" : "n_rows";
+  PYGAT_REQUIRE(c.n >= 0, "%s: %s=%d", what, nname, c.n);
+  PYGAT_REQUIRE(c.n > 0 || c.nnz == 0, "%s: %s=0 with nnz=%lld entries", what, nname, (long long)c.nnz);
+  const int HF = c.H * c.F;
+  PYGAT_REQUIRE(c.rowptr, "%s: null %s", what, cols ? "rowptr_t" : "rowptr");
+  PYGAT_REQUIRE(c.nnz == 0 || c.col, "%s: null %s", what, cols ? "row_t" : "col");
+  DA_TABLE(what, "x_dst", c.x_dst, c.ldd, HF);
+  DA_TABLE(what, "x_src", c.x_src, c.lds, HF);
+  PYGAT_REQUIRE(c.a, "%s: null a", what);
+  PYGAT_REQUIRE(aligned16(c.a), "%s: a must be 16-byte aligned", what);
+  if (!cols) {
+    if (c.v) DA_TABLE(what, "v", c.v, c.ldv, HF);              // (null: v is x_src, the SHARED kernels)
+    DA_TABLE(what, "out", c.out, c.ldo, HF);
+    PYGAT_REQUIRE(c.m, "%s: null m", what);
+    PYGAT_REQUIRE(c.Z, "%s: null Z", what);
+  }
+  PYGAT_REQUIRE(c.ws, "%s: null workspace", what);
+  PYGAT_REQUIRE(aligned16(c.ws), "%s: the workspace must be 16-byte aligned", what);
+  if (c.pass == 1) {
+    DA_TABLE(what, "G", c.G, c.ldg, HF);
+    DA_TABLE(what, "dx_dst", c.dx, c.lddx, HF);
+    PYGAT_REQUIRE(c.nnz == 0 || c.P, "%s: null P", what);
+    PYGAT_REQUIRE(c.nnz == 0 || c.S, "%s: null S", what);
+  }
+  if (cols) {
+    PYGAT_REQUIRE(c.nnz == 0 || c.S, "%s: null S", what);
+    DA_TABLE(what, "dx_src", c.dx, c.lddx, HF);
+    PYGAT_REQUIRE(c.da, "%s: null da", what);
+    PYGAT_REQUIRE(aligned16(c.da), "%s: da must be 16-byte aligned", what);
+  }
+  if (c.n == 0) return PYGAT_OK;
+  DaArgs g;
+  memset(&g, 0, sizeof(g));
+  g.n = c.n; g.H = c.H; g.F = c.F; g.NCH = HF / 4; g.LH = c.F / 4; g.nnz = c.nnz; g.rowptr = c.rowptr; g.col = c.col;
+  g.scale = c.negative_slope; g.bias = c.a; g.part = static_cast<float*>(c.ws); g.pstride = da_pstride(c.H, c.F);
+  if (cols) { g.q = c.x_src; g.ldq = c.lds; g.k = c.x_dst; g.ldk = c.ldd; }
+  else {
+    g.q = c.x_dst; g.ldq = c.ldd; g.k = c.x_src; g.ldk = c.lds; g.v = c.v; g.ldv = c.ldv;
+    g.out = c.out; g.ldo = c.ldo; g.m = c.m; g.Z = c.Z;
+  }
+  if (c.pass != 0) { g.perm = c.perm; g.dq = c.dx; g.lddq = c.lddx; g.S = c.S; }   // (the forward walks in CSR order alone)
+  if (c.pass == 1) { g.G = c.G; g.ldg = c.ldg; g.P = c.P; }
+  int lpr, vec, nch;
+  da_pick(c.H, c.F, &lpr, &vec, &nch);
+  const unsigned chunks = (unsigned)long_chunks(c.nnz);
+  unsigned blocks = (unsigned)cdiv(c.n, 4 * (64 / lpr));
+  float* stage = nullptr;
+  if (cols) {
+    blocks = (unsigned)v2_col_blocks(c.nnz);
+    g.ldde = HF;
+    g.de = g.part + v2_part_floats(c.nnz, c.H, c.F);
+    g.dbias = g.de + (int64_t)chunks * HF;
+    stage = g.de + v2_da_records(c.nnz) * HF;
+  }
+  hipStream_t st = (hipStream_t)c.stream;
+  void* args[] = {&g};
+  const bool shared = !cols && !c.v;
+  if (chunks) (void)hipLaunchKernel(v2_kernel(shared, c.pass, true, lpr, vec), dim3(chunks), dim3(64), args, 0, st);
+  (void)hipLaunchKernel(v2_kernel(shared, c.pass, false, lpr, vec), dim3(blocks), dim3(256), args, 0, st);
+  if (cols) {
+    const int nrec = (int)(chunks + 4 * blocks);
+    hipLaunchKernelGGL(v2_da_stage_kernel, dim3(V2_DA_STAGE), dim3(256), 0, st, HF, nrec, (const float*)g.de, stage);
+    hipLaunchKernelGGL(v2_da_final_kernel, dim3((unsigned)cdiv(HF, 256)), dim3(256), 0, st, HF, (const float*)stage, c.da);
+  }
+  PYGAT_CHECK_LAUNCH(what);
+  return PYGAT_OK;
+}
+
+}  // namespace pygat
+
+using namespace pygat;
+
+extern "C" int pygat_v2_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes) {
+  PYGAT_REQUIRE(bytes, "v2_attn_workspace_bytes: null bytes");
+  const int rc = v2_check_shape("v2_attn_workspace_bytes", nnz, H, F);
+  if (rc != PYGAT_OK) return rc;
+  *bytes = (size_t)v2_ws_floats(nnz, H, F) * sizeof(float);
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_v2_attn_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F,
+                                     float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds,
+                                     const float* a, const float* v, int64_t ldv, float* out, int64_t ldo, float* m, float* Z, void* ws,
+                                     void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.H = H; c.F = F;
+  c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
+  c.out = out; c.ldo = ldo; c.m = m; c.Z = Z; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                           int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                           int64_t lds, const float* a, const float* v, int64_t ldv, const float* out, int64_t ldo,
+                                           const float* m, const float* Z, const float* G, int64_t ldg, float* dx_dst, int64_t lddx,
+                                           float* P, float* S, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_backward_rows"; c.pass = 1; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
+  c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v;
+  c.ldv = ldv; c.out = const_cast<float*>(out); c.ldo = ldo; c.m = const_cast<float*>(m); c.Z = const_cast<float*>(Z); c.G = G;
+  c.ldg = ldg; c.dx = dx_dst; c.lddx = lddx; c.P = P; c.S = S; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_backward_cols(int n_cols, int64_t nnz, const int32_t* rowptr_t, const int32_t* row_t,
+                                           const int32_t* perm_t, int H, int F, float negative_slope, const float* x_dst, int64_t ldd,
+                                           const float* x_src, int64_t lds, const float* a, const float* S, float* dx_src,
+                                           int64_t lddx, float* da, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_backward_cols"; c.pass = 2; c.n = n_cols; c.nnz = nnz; c.rowptr = rowptr_t; c.col = row_t; c.perm = perm_t;
+  c.H = H; c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a;
+  c.S = const_cast<float*>(S); c.dx = dx_src; c.lddx = lddx; c.da = da; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}

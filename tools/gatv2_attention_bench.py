@@ -1,0 +1,214 @@
+#!/usr/bin/env python3
+"""What pygat_amd.gatv2_attention costs at config 5 (R-MAT 2^20 nodes, 10 760 610 entries; pygat_amd.rmat, the graph of bench.py)
+against the same result from the parts it fuses -- two torch gathers and their sum, leaky_relu, the product with a and its sum over the
+features, edge_softmax (K18) and spmm (pygat_spmm_forward) -- at H x F = 8x16 and 8x64, N(0, 1) tensors, slope 0.2, with v shared
+(v=None: v is x_src) and with a v table of its own, the forward alone and forward + backward:
+
+    python tools/gatv2_attention_bench.py [--shapes 8x16,8x64] [--values shared,separate] [--rounds 5] [--steps 10] [--warmup 10]
+                                          [--out profiles/gatv2_attention_bench.jsonl]
+
+The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
+run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
+round times `steps` calls of one contender, each between two HIP events, then the same of the other.  Reported per contender: the
+median over all rounds x steps timed calls (at least 50) and the spread of the rounds' medians: a difference below that spread is
+not a difference.  The composition is the baseline: it runs kernels and torch ops that exist without K21, on the same build.
+
+Before timing, both contenders' outputs are priced on the same seeded inputs by the rule of tests/parity.py against an fp64
+computation on the CPU, on a sample of rows (the row of most entries among them).  Algorithmic bytes are computed from the shapes (E
+entries, N rows, M columns, H heads, R = H F floats per row), `*_bytes` below; `*_roof_ms` is their time at 8 TB/s, and
+`*_roof_fraction` that over the measured time: the whole op's share of the HBM roof on the byte model, not a kernel's.  Recorded, not
+gated.  One JSON object per (shape, value table), appended."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+SAMPLE_ROWS = 1024
+HBM_BYTES_PER_S = 8e12
+SECTOR = 32          # bytes: the granularity at which the H floats of S[c] are counted
+
+
+def sectors(nbytes):
+    return -(-nbytes // SECTOR) * SECTOR
+
+
+def fused_forward_bytes(E, N, M, H, F, shared):
+    """Per entry: the column index and the x_src row (shared: that is the value row too; separate: the v row besides).  Per row:
+    x_dst read, out, m and Z written, the row pointer."""
+    R = H * F
+    return E * (4 + (1 if shared else 2) * 4 * R) + N * (2 * 4 * R + 2 * 4 * H + 4)
+
+
+def fused_backward_bytes(E, N, M, H, F, shared, perm=False):
+    """Row pass: the forward's reads per entry (and the entry index where the pattern carries a permutation), P and S written; x_dst,
+    G, out, m, Z read and dx_dst written per row.  Column pass on the transposed pattern: the row index, the entry index, the x_dst
+    row and S at sector granularity per entry; x_src read and dx_src written per column (the da records are a few MB).  dv, K17 on
+    the transposed pattern: P with the two indices and the G row per entry, dv per column; shared: the sum of dx_src's two parts."""
+    R = H * F
+    rows = E * (4 + (1 if shared else 2) * 4 * R + 2 * 4 * H + (4 if perm else 0)) + N * (4 * 4 * R + 2 * 4 * H + 4)
+    cols = E * (8 + 4 * R + sectors(4 * H)) + M * (2 * 4 * R + 4)
+    dv = E * (4 * H + 8 + 4 * R) + M * (4 * R + 4) + (M * 3 * 4 * R if shared else 0)
+    return rows + cols + dv
+
+
+def composed_forward_bytes(E, N, M, H, F):
+    """The two gathers (an int64 index and a row read, [E, R] written, each), their sum (two reads and a write), leaky_relu and the
+    product with a (a read and a write each), the sum over the features ([E, R] read, [E, H] written).  K18: the scores read by the
+    row pass and again by the entry pass with the (row, col) pair, alpha written; m and Z per row.  SpMM: alpha, the column index and
+    the v row per entry, out per row."""
+    R = H * F
+    score = 2 * E * (8 + 2 * 4 * R) + E * 3 * 4 * R + 2 * E * 2 * 4 * R + E * (4 * R + 4 * H)
+    softmax = E * (3 * 4 * H + 8) + N * (2 * 2 * 4 * H + 4)
+    spmm = E * (4 * H + 4 + 4 * R) + N * (4 * R + 4)
+    return score + softmax + spmm
+
+
+def composed_backward_bytes(E, N, M, H, F):
+    """SpMM's backward: an SDDMM over G and v (dalpha written) and the transposed SpMM of alpha and G (dv).  K18's backward: alpha and
+    dalpha read by both passes, dscores written, c per row.  The sum's backward broadcasts ([E, H] read, [E, R] written); the
+    product's gives da ([E, R] read twice, reduced) and the gradient of leaky_relu's output (two reads and a write); leaky_relu's
+    backward (two reads and a write); the two gathers' backwards: [E, R] and an int64 index read and added into [N, R] and [M, R]
+    tables that were zeroed first."""
+    R = H * F
+    spmm_b = E * (2 * 4 * R + 8 + 4 * H) + E * (4 * H + 8 + 4 * R) + M * (4 * R + 4)
+    softmax_b = E * (5 * 4 * H + 8) + N * (2 * 4 * H + 4)
+    score_b = E * (4 * H + 4 * R) + E * 2 * 4 * R + 2 * E * 3 * 4 * R + 2 * E * (8 + 3 * 4 * R) + (N + M) * 4 * R
+    return spmm_b + softmax_b + score_b
+
+
+def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype):
+    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of a . leaky_relu(x_dst_i + x_src_j), times
+    v_j; the rows a few hundred at a time, so that no [entries, H, F] tensor grows beyond them."""
+    import torch
+    ad = a.cpu().to(dtype)
+    outs = []
+    for part in torch.split(rows, 256):
+        deg = rp[part + 1] - rp[part]
+        idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in part.tolist()])
+        sub = torch.repeat_interleave(torch.arange(part.numel()), deg)
+        cols, inv = torch.unique(col[idx], return_inverse=True)
+        xd, xs, vs = x_dst[part].cpu().to(dtype), x_src[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
+        s = (ad * torch.nn.functional.leaky_relu(xd[sub] + xs[inv], slope)).sum(-1)
+        m = torch.full((part.numel(), s.shape[1]), -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
+        p = torch.exp(s - m[sub])
+        alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
+        outs.append(torch.zeros(part.numel(), v.shape[1], v.shape[2], dtype=dtype).index_add(0, sub, alpha[:, :, None] * vs[inv]))
+    return torch.cat(outs)
+
+
+def measure(args):
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("gatv2_attention_bench: needs a GPU (a time taken anywhere else says nothing)")
+    import pygat_amd as pg
+    from pygat_amd.rmat import rmat_csr_numpy
+    from dot_attention_bench import alternate                        # the one timing routine of these tools
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import parity                                                     # the one tolerance rule (tests/parity.py)
+    dev = torch.device("cuda", 0)
+    rp, col = rmat_csr_numpy(args.scale, args.draws, seed=1)
+    graph = pg.CSRGraph(torch.from_numpy(rp).to(dev), torch.from_numpy(col).to(dev))
+    pattern = graph.edge_pattern()
+    pattern.transposed()
+    N, E = graph.n, graph.nnz
+    row_d, col_d = pattern.edge_rc[:, 0].long(), pattern.edge_rc[:, 1].long()
+    rp_t, col_t = torch.from_numpy(rp).long(), torch.from_numpy(col).long()
+    deg = rp_t[1:] - rp_t[:-1]
+    picked = torch.randperm(N, generator=torch.Generator().manual_seed(3))[:SAMPLE_ROWS]
+    rows = torch.unique(torch.cat([picked, torch.argmax(deg)[None]]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    slope, perm = 0.2, pattern.perm is not None
+    for shape in args.shapes.split(","):
+        H, F = (int(x) for x in shape.split("x"))
+        for values in args.values.split(","):
+            shared = values == "shared"
+            g = torch.Generator(device=dev).manual_seed(2)
+            x_dst, x_src = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(2))
+            a = torch.randn(H, F, generator=g, device=dev)
+            G = torch.randn(N, H, F, generator=g, device=dev)
+            leaves = (x_dst, x_src, a) + (() if shared else (torch.randn(N, H, F, generator=g, device=dev),))
+
+            def fused(xd, xs, a_, v_=None):
+                return pg.gatv2_attention(pattern, xd, xs, a_, v_, slope)
+
+            def composed(xd, xs, a_, v_=None):
+                e = (a_ * torch.nn.functional.leaky_relu(xd[row_d] + xs[col_d], slope)).sum(-1)
+                return pg.spmm(pattern, pg.edge_softmax(pattern, e), xs if v_ is None else v_)
+
+            def forward_of(fn):
+                def run():
+                    with torch.no_grad():
+                        return fn(*leaves)
+                return run
+
+            def both_of(fn):
+                mine = [t.detach().clone().requires_grad_(True) for t in leaves]
+
+                def run():
+                    return torch.autograd.grad(fn(*mine), mine, G)
+                return run
+
+            # the same seeded inputs, both contenders priced on the sampled rows
+            out_f, out_c = forward_of(fused)(), forward_of(composed)()
+            v = leaves[-1] if not shared else x_src
+            ref64 = sampled_reference(rp_t, col_t, rows, x_dst, x_src, a, v, slope, torch.float64)
+            ref32 = sampled_reference(rp_t, col_t, rows, x_dst, x_src, a, v, slope, torch.float32)
+            err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} {values} fused out", ref32)
+            err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} {values} composed out", ref32)
+            res = {"bench": "gatv2_attention", "values": values, "device": torch.cuda.get_device_name(0),
+                   "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
+                   "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+                   "longest_checked_row": int(deg[rows].max()), "out_err_fused": err_f, "out_err_composed": err_c,
+                   "out_err_fp32_reference": parity.err(ref32, ref64), "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
+                   "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, shared),
+                   "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F),
+                   "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, shared, perm),
+                   "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F)}
+            del out_f, out_c
+            legs = [("forward", alternate({"fused": forward_of(fused), "composed": forward_of(composed)}, args.rounds, args.steps,
+                                          args.warmup))]
+            if not args.forward_only:
+                legs.append(("forward_backward", alternate({"fused": both_of(fused), "composed": both_of(composed)}, args.rounds,
+                                                           args.steps, args.warmup)))
+            for what, r in legs:
+                for name in ("fused", "composed"):
+                    res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+                res[f"{what}_speedup"] = res[f"composed_{what}_ms"] / res[f"fused_{what}_ms"]
+                model = res["fused_forward_bytes"] + (res["fused_backward_bytes"] if what == "forward_backward" else 0)
+                res[f"fused_{what}_roof_ms"] = 1e3 * model / HBM_BYTES_PER_S
+                res[f"fused_{what}_roof_fraction"] = res[f"fused_{what}_roof_ms"] / res[f"fused_{what}_ms"]
+            res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+            with open(args.out, "a") as f:
+                f.write(json.dumps(res) + "\n")
+            print(json.dumps(res), flush=True)
+            del x_dst, x_src, a, G, leaves, v
+            torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="8x16,8x64")
+    ap.add_argument("--values", default="shared,separate", help="shared: v=None, v is x_src; separate: a v table of its own")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10, help="timed calls per round and contender")
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--forward-only", action="store_true", help="skip the forward + backward leg")
+    ap.add_argument("--scale", type=int, default=20)
+    ap.add_argument("--draws", type=int, default=5_000_000)
+    ap.add_argument("--limit", type=int, default=540, help="seconds the measuring child may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gatv2_attention_bench.jsonl"))
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return measure(args)
+    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
+    sys.exit(subprocess.call(cmd))
+
+
+if __name__ == "__main__":
+    main()
