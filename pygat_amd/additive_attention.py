@@ -17,7 +17,6 @@ fixed summation order: two runs give the same bits.  Nothing is read back to the
 """
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
@@ -25,18 +24,12 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import MIN_F, MAX_F, _require_pattern, _require_tensor
-from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
+from .dot_attention import _require_heads, _require_pattern, _require_tensor, _slope
+from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "additive_attention"
 _PAD_HINT = ("zero-padding the columns of v to the next allowed F leaves the first F columns of the result unchanged (no scale "
              "depends on F)")
-
-
-def _slope(negative_slope) -> float:
-    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
-        raise ValueError(f"pygat_amd {_OP}: negative_slope = {negative_slope!r}: a finite float expected")
-    return float(negative_slope)
 
 
 def _checked(pattern, s_dst, s_src, v, edge_logit):
@@ -61,13 +54,7 @@ def _checked(pattern, s_dst, s_src, v, edge_logit):
             raise ValueError(f"pygat_amd {_OP}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
     flat = s_dst.dim() == 1
     H, F = (1 if flat else int(s_dst.shape[1])), int(v.shape[-1])
-    if not (1 <= H <= MAX_HEADS):
-        raise ValueError(f"pygat_amd {_OP}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
-    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
-        raise ValueError(f"pygat_amd {_OP}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
-    if H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd {_OP}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
-                         f"{_PAD_HINT}")
+    _require_heads(_OP, H, F, _PAD_HINT)
     return H, F, flat, None if edge_logit is None else _logit_head_stride(pattern, edge_logit, H, flat)
 
 
@@ -165,4 +152,4 @@ def additive_attention(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.T
     for another F zero-pad the columns of v: the first F columns of the result are unchanged.
     Not provided: dropout on the coefficients, bfloat16 tables, a fused column pass (dv and ds_src are two K17 launches on the
     transposed pattern)."""
-    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, _slope(negative_slope), edge_logit)
+    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, _slope(_OP, negative_slope), edge_logit)

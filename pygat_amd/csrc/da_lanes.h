@@ -1,8 +1,9 @@
-// What the two fused attention families over an edge pattern share: K19 (k19_dot_attention.hip, the dot-product score) and K20
-// (k20_additive_attention.hip, the GAT score).  The kernel arguments, the lane mapping of a row of H*F floats, the online softmax
-// fold of one head and the merge of two partial records, the caller's entry index of a CSR position, the per-entry scalar term, the
-// lane-shape dispatch and the table checks of the launchers.  Moved here from k19_dot_attention.hip as it stood; K19's device code is
-// the same before and after (profiles/k20_k19_unchanged.txt).  Each family's walk, folds and kernels are its own.
+// The lanes of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip, the dot-product score), K20
+// (k20_additive_attention.hip, the GAT score) and K21 (k21_gatv2_attention.hip, the GATv2 score).  The kernel arguments, the lane
+// mapping of a row of H*F floats, the online softmax fold of one head and the merge of two partial records, the caller's entry index
+// of a CSR position, the per-entry scalar term, the lane-shape dispatch and the table checks of the launchers.  Moved here from
+// k19_dot_attention.hip as it stood; K19's device code is the same before and after (profiles/k20_k19_unchanged.txt).  The kernels
+// built on these, one copy for the three families, and the launcher tail: da_family.h.  A family's walk and folds are its own.
 #pragma once
 #include "long_rows.h"
 #include "rng.h"

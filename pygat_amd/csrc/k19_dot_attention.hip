@@ -29,7 +29,7 @@
 // LPR lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v.  F / 4 is a power of two, so the
 // chunks of a head sit on LH = F / 4 adjacent lanes of one v, and a head's dot product is a butterfly over them; every lane of a head
 // ends with the same s, m and Z.  q_i is loaded once per row.  Per entry k_j and v_j (and the e row) are gathered, several entries in
-// flight (da_unroll), the indices and bias values of the next batch asked for under this batch's arithmetic (da_walk), and folded
+// flight (da_unroll), the indices and bias values of the next batch asked for under this batch's arithmetic (DaFam::walk), and folded
 // into an online (m, Z, acc) state per head with one __expf per (entry, head) (da_fold; K18's es_fold).
 //
 // Long rows go through partial records (the rule of long_rows.h), one wave per chunk: its lane groups walk the piece
@@ -47,10 +47,10 @@
 //   bf16 tables             the result of the fp32 kernels on the widened tables bit for bit
 // A flag that is off leaves no trace in a kernel: the instantiations without it are instruction for instruction what they would be
 // if the flag did not exist (profiles/k19_refactor_isa.txt).
-// The kernel arguments, the lane mapping, the fold of one head, the record merge and the lane-shape dispatch are da_lanes.h's, shared
-// with K20 (k20_additive_attention.hip).
-#include "da_lanes.h"
-#include <string.h>
+// The kernel arguments, the lane mapping, the fold of one head, the record merge and the lane-shape dispatch are da_lanes.h's; the
+// four kernels themselves, the shape check, the kernel-name parser and the launch of a pair are da_family.h's, instantiated on DaFam
+// below.  Both are shared with K20 (k20_additive_attention.hip) and K21 (k21_gatv2_attention.hip).
+#include "da_family.h"
 #include <type_traits>
 
 namespace pygat {
@@ -169,96 +169,6 @@ __device__ __forceinline__ void da_edge_add(DaRows<VEC, U>& w, const DaEdgeRows<
     for (int v = 0; v < VEC; ++v) { da_add_rn(w.k[u][v], we.e[u][v]); da_add_rn(w.v[u][v], we.e[u][v]); }
 }
 
-// The walk of both passes: the entries e0, e0 + step, ... < e1 of one row, handed to Fold::fold in that order, U at a time and then one
-// at a time.  w: the gathered k and v rows (kk and vv under EDGE); bs: the bias values; eid: the caller's entry indices (where the
-// variant carries them, da_eid_walk); ent: eid x H (BWD); key (DROP): the key of the row's draws; ctx: what the pass keeps of its row,
-// handed through; U = da_unroll.  Fold is DaFwdFold or DaBwdFold, a type and not a closure, key travels by value, and the kernels
-// call da_walk themselves: a closure, a key behind a reference or one more function between a kernel and its walk all gave the same
-// instructions in another order.
-// The order of the loads is the kernels' speed.  The column indices of the next U entries are asked for before this batch's rows are
-// used, so an iteration waits for one gather, not for an index and then a gather.  Where the variant carries entry indices, the next
-// batch's travel with its column indices as loaded words (da_eid_raw) and become indices only after this batch's fold; BIAS: the
-// next batch's bias values are asked for then, ahead of the next gather, so they are there when it is -- an iteration still waits for
-// one gather.  EDGE: the same entry indices place the batch's e rows, asked for right behind its gather, and its rows of de.
-// The backward without a flag needs the entry index only for its stores and forms it whole (da_entry) a batch ahead.
-// One at a time, the backward forms what it needs where it needs it: ent by da_entry, eid ahead of the bias load (BIAS) and again
-// behind the gather (EDGE); one index for all of them is fewer instructions, and changes those of every flagged backward kernel.
-// lone (the backward row kernel under EDGE says so; a piece of a long row never is): the walk is over a row of one entry
-template <int VEC, unsigned V, bool BWD, typename Fold, typename... Ctx>
-__device__ __forceinline__ void da_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool lone,
-                                        uint2 key, Ctx&... ctx) {
-  constexpr int U = da_unroll(BWD, VEC);
-  constexpr bool BIAS = da_has(V, DA_BIAS), EDGE = da_has(V, DA_EDGE), EID = da_eid_walk(V);
-  using T = std::conditional_t<da_has(V, DA_BF16), da_bf16, float>;      // the element type of the k and v tables
-  int64_t e = e0;
-  if constexpr (U > 1) {
-    int32_t src[U];
-    [[maybe_unused]] int64_t ent[U], ent_next[U];
-    [[maybe_unused]] int32_t raw[U], eid[U];
-    DaBias<VEC, U, BIAS> bs;
-    bool full = e + (U - 1) * step < e1;
-    if (full) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        src[u] = g.col[e + u * step];
-        if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
-        else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
-      }
-      if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
-      if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
-    }
-    while (full) {
-      DaRows<VEC, U> w;
-      da_gather<VEC, U, T>(g, ln, src, w);
-      [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
-      if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
-      if constexpr (BWD && !EID) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
-      }
-      e += U * step;
-      full = e + (U - 1) * step < e1;
-      if (full) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          src[u] = g.col[e + u * step];
-          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
-          else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
-        }
-      }
-      if constexpr (BWD && EID) {                                  // (eid: this batch's, formed after the last fold, not yet replaced)
-#pragma unroll
-        for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
-      }
-      if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
-      Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, false);
-      if constexpr (EID)
-        if (full) {
-          da_eids<U>(g, raw, e, step, eid);
-          if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
-        }
-    }
-  }
-  for (; e < e1; e += step) {
-    const int32_t src[1] = {g.col[e]};
-    [[maybe_unused]] int64_t ent[1] = {0};
-    [[maybe_unused]] int32_t eid[1] = {0};
-    if constexpr (BWD) ent[0] = da_entry(g, e);
-    if constexpr (BWD ? BIAS : EID) eid[0] = da_eid(g, da_eid_raw(g, e), e);
-    DaBias<VEC, 1, BIAS> bs;
-    if constexpr (BIAS) da_bias_load<VEC, 1>(g, ln, eid, bs);
-    DaRows<VEC, 1> w;
-    da_gather<VEC, 1, T>(g, ln, src, w);
-    if constexpr (EDGE) {
-      if constexpr (BWD) eid[0] = da_eid(g, da_eid_raw(g, e), e);
-      DaEdgeRows<VEC, 1, true> we;
-      da_gather_edge<VEC, 1>(g, ln, eid, we);
-      da_edge_add<VEC, 1>(w, we);
-    }
-    Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, lone);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------ forward
 // the forward's fold of a batch; ctx: q_i and the row's state.  eid is looked at under DROP alone, ent and lone not at all
 template <int LPR, int VEC, unsigned V>
@@ -284,109 +194,11 @@ struct DaFwdFold {
   }
 };
 
-// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, unsigned V>
-__global__ __launch_bounds__(64) void da_fwd_long_kernel(DaArgs g) {
-  static_assert(da_exists(V, false), "no dropout on bf16 tables (they are for inference); per-entry rows: fp32 tables, no dropout");
-  constexpr int EPW = 64 / LPR;
-  const uint2 key = da_key<da_has(V, DA_DROP)>(g);
-  const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int HF = g.H * g.F;
-  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
-                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
-    float4 q[VEC];
-    da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, q);
-    DaState<VEC> st;
-    da_init<VEC>(st);
-    da_walk<VEC, V, false, DaFwdFold<LPR, VEC, V>>(g, ln, e0 + grp, e1, EPW, false, key, q, st);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
-      float mx = st.m[v];
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-      const float f = __expf(st.m[v] - mx);                    // (a lane group without entries: 0 x 0)
-      st.z[v] *= f;
-      da_scale(st.acc[v], f);
-      st.m[v] = mx;
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) {
-        st.z[v] += __shfl_xor(st.z[v], off);
-        da_add(st.acc[v], da_shfl_xor(st.acc[v], off));
-      }
-    }
-    if (grp == 0) {
-      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
-      da_store_row<VEC>(p, ln, st.acc);
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        if (ln.lead >> v & 1) { p[HF + ln.head[v]] = st.m[v]; p[HF + g.H + ln.head[v]] = st.z[v]; }
-    }
-  });
-}
-
-// launch 2: one lane group per row.  m and Z are what a backward reads: the bf16-table kernels, which have none, do not write them
-template <int LPR, int VEC, unsigned V>
-__global__ __launch_bounds__(256) void da_fwd_row_kernel(DaArgs g) {
-  static_assert(da_exists(V, false), "no dropout on bf16 tables (they are for inference); per-entry rows: fp32 tables, no dropout");
-  constexpr bool KEEP_MZ = !da_has(V, DA_BF16);
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
-  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-  const int HF = g.H * g.F;
-  DaState<VEC> st;
-  da_init<VEC>(st);
-  if (end - start > LONG_ROW) {
-    for_long_records(start, end, [&](int64_t rec) {
-      const float* p = g.part + rec * g.pstride;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        da_merge(st.m[v], st.z[v], st.acc[v], p[HF + ln.head[v]], p[HF + g.H + ln.head[v]], ld4(p + ln.ofs[v]));
-    });
-  } else if (end > start) {
-    float4 q[VEC];
-    da_load_row<VEC>(g.q + row * g.ldq, ln, q);
-    da_walk<VEC, V, false, DaFwdFold<LPR, VEC, V>>(g, ln, start, end, 1, false, da_key<da_has(V, DA_DROP)>(g), q, st);
-  }
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    if (!(ln.ok >> v & 1)) continue;
-    const bool any = end > start;
-    const float z = st.z[v];
-    const float4 a = st.acc[v];
-    st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
-    if constexpr (KEEP_MZ)
-      if (ln.lead >> v & 1) {
-        g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
-        g.Z[row * g.H + ln.head[v]] = z;
-      }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------- backward, row side
 template <int VEC>
-struct DaRow {                 // what the backward holds of its row
-  float4 q[VEC], G[VEC];
-  float m[VEC], rz[VEC], D[VEC];
+struct DaRow : DaGrad<VEC> {   // what the backward holds of its row
+  float4 q[VEC];
 };
-
-template <int LPR, int VEC>
-__device__ __forceinline__ void da_bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, DaRow<VEC>& r) {
-  float4 o[VEC];
-  da_load_row<VEC>(g.q + row * g.ldq, ln, r.q);
-  da_load_row<VEC>(g.G + row * g.ldg, ln, r.G);
-  da_load_row<VEC>(g.out + row * g.ldo, ln, o);
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    r.m[v] = g.m[row * g.H + ln.head[v]];
-    r.rz[v] = 1.f / g.Z[row * g.H + ln.head[v]];
-    r.D[v] = da_head_sum<LPR>(dot4(r.G[v], o[v]), g.LH);
-  }
-}
 
 // the backward's fold of a batch; ctx: the row (DaRow) and its dq
 // BIAS: T = p (<G_i, v_j> - D_i), the gradient of the bias, formed beside ds -- ds itself is the unbiased kernel's expression, so a
@@ -441,69 +253,129 @@ struct DaBwdFold {
   }
 };
 
-// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the dq row
-template <int LPR, int VEC, unsigned V>
-__global__ __launch_bounds__(64) void da_bwd_long_kernel(DaArgs g) {
-  static_assert(da_exists(V, true), "no backward on bf16 tables; per-entry rows: no dropout");
-  constexpr int EPW = 64 / LPR;
-  const uint2 key = da_key<da_has(V, DA_DROP)>(g);
-  const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
-                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
-    DaRow<VEC> r;
-    da_bwd_load<LPR, VEC>(g, ln, row, r);
-    float4 dq[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-    da_walk<VEC, V, true, DaBwdFold<LPR, VEC, V>>(g, ln, e0 + grp, e1, EPW, false, key, r, dq);
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) da_add(dq[v], da_shfl_xor(dq[v], off));
-    if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dq);
-  });
-}
-
-// launch 2: one lane group per row
-template <int LPR, int VEC, unsigned V>
-__global__ __launch_bounds__(256) void da_bwd_row_kernel(DaArgs g) {
-  static_assert(da_exists(V, true), "no backward on bf16 tables; per-entry rows: no dropout");
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
-  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-  float4 dq[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) dq[v] = da_zero4();
-  if (end - start > LONG_ROW) {
-    for_long_records(start, end, [&](int64_t rec) {
-      const float* p = g.part + rec * g.pstride;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) da_add(dq[v], ld4(p + ln.ofs[v]));
-    });
-  } else if (end > start) {                                    // (a row without entries: its G row is not read)
-    DaRow<VEC> r;
-    da_bwd_load<LPR, VEC>(g, ln, row, r);
-    da_walk<VEC, V, true, DaBwdFold<LPR, VEC, V>>(g, ln, start, end, 1, da_has(V, DA_EDGE) && end - start == 1,
-                                                  da_key<da_has(V, DA_DROP)>(g), r, dq);
+// the family: what the kernels of da_family.h hold of a row and how they walk it, per variant.  m and Z are what a backward reads: the
+// bf16-table kernels, which have none, do not write them.  lone: see walk
+template <unsigned V>
+struct DaFam {
+  static constexpr bool KEEP_MZ = !da_has(V, DA_BF16);
+  template <int VEC> using Own = float4[VEC];                  // q_i
+  template <int VEC> using Row = DaRow<VEC>;
+  __device__ __forceinline__ static uint2 key(const DaArgs& g) { return da_key<da_has(V, DA_DROP)>(g); }
+  __device__ __forceinline__ static bool lone(int64_t start, int64_t end) { return da_has(V, DA_EDGE) && end - start == 1; }
+  template <int VEC>
+  __device__ __forceinline__ static void load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, float4 (&q)[VEC]) {
+    da_load_row<VEC>(g.q + row * g.ldq, ln, q);
   }
-  da_store_row<VEC>(g.dq + row * g.lddq, ln, dq);
-}
+  template <int LPR, int VEC>
+  __device__ __forceinline__ static void bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, DaRow<VEC>& r) {
+    load<VEC>(g, ln, row, r.q);
+    da_grad_load<LPR, VEC>(g, ln, row, r);
+  }
+  // The walk of both passes (PASS 0 forward, 1 backward): the entries e0, e0 + step, ... < e1 of one row, handed to Fold::fold in that
+  // order, U at a time and then one at a time.  w: the gathered k and v rows (kk and vv under EDGE); bs: the bias values; eid: the
+  // caller's entry indices (where the variant carries them, da_eid_walk); ent: eid x H (BWD); key (DROP): the key of the row's draws;
+  // ctx: what the pass keeps of its row, handed through; U = da_unroll.  Fold is DaFwdFold or DaBwdFold, a type and not a closure, key
+  // travels by value, and the kernels of da_family.h call this member themselves: a closure, a key behind a reference or one more
+  // function between a kernel and its walk all gave the same instructions in another order.
+  // The order of the loads is the kernels' speed.  The column indices of the next U entries are asked for before this batch's rows are
+  // used, so an iteration waits for one gather, not for an index and then a gather.  Where the variant carries entry indices, the next
+  // batch's travel with its column indices as loaded words (da_eid_raw) and become indices only after this batch's fold; BIAS: the
+  // next batch's bias values are asked for then, ahead of the next gather, so they are there when it is -- an iteration still waits for
+  // one gather.  EDGE: the same entry indices place the batch's e rows, asked for right behind its gather, and its rows of de.
+  // The backward without a flag needs the entry index only for its stores and forms it whole (da_entry) a batch ahead.
+  // One at a time, the backward forms what it needs where it needs it: ent by da_entry, eid ahead of the bias load (BIAS) and again
+  // behind the gather (EDGE); one index for all of them is fewer instructions, and changes those of every flagged backward kernel.
+  // lone (the backward row kernel under EDGE says so; a piece of a long row never is): the walk is over a row of one entry
+  template <int LPR, int VEC, int PASS, typename... Ctx>
+  __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool lone,
+                                              uint2 key, Ctx&... ctx) {
+    constexpr bool BWD = PASS == 1;
+    static_assert(da_exists(V, BWD), "bf16 tables are for inference: no dropout, no backward; per-entry rows: fp32 tables, no dropout");
+    using Fold = std::conditional_t<BWD, DaBwdFold<LPR, VEC, V>, DaFwdFold<LPR, VEC, V>>;
+    constexpr int U = da_unroll(BWD, VEC);
+    constexpr bool BIAS = da_has(V, DA_BIAS), EDGE = da_has(V, DA_EDGE), EID = da_eid_walk(V);
+    using T = std::conditional_t<da_has(V, DA_BF16), da_bf16, float>;      // the element type of the k and v tables
+    int64_t e = e0;
+    if constexpr (U > 1) {
+      int32_t src[U];
+      [[maybe_unused]] int64_t ent[U], ent_next[U];
+      [[maybe_unused]] int32_t raw[U], eid[U];
+      DaBias<VEC, U, BIAS> bs;
+      bool full = e + (U - 1) * step < e1;
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          src[u] = g.col[e + u * step];
+          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
+          else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
+        }
+        if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
+        if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
+      }
+      while (full) {
+        DaRows<VEC, U> w;
+        da_gather<VEC, U, T>(g, ln, src, w);
+        [[maybe_unused]] DaEdgeRows<VEC, U, EDGE> we;
+        if constexpr (EDGE) da_gather_edge<VEC, U>(g, ln, eid, we);
+        if constexpr (BWD && !EID) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+        }
+        e += U * step;
+        full = e + (U - 1) * step < e1;
+        if (full) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            src[u] = g.col[e + u * step];
+            if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
+            else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
+          }
+        }
+        if constexpr (BWD && EID) {                                  // (eid: this batch's, formed after the last fold, not yet replaced)
+#pragma unroll
+          for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
+        }
+        if constexpr (EDGE) da_edge_add<VEC, U>(w, we);
+        Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, false);
+        if constexpr (EID)
+          if (full) {
+            da_eids<U>(g, raw, e, step, eid);
+            if constexpr (BIAS) da_bias_load<VEC, U>(g, ln, eid, bs);
+          }
+      }
+    }
+    for (; e < e1; e += step) {
+      const int32_t src[1] = {g.col[e]};
+      [[maybe_unused]] int64_t ent[1] = {0};
+      [[maybe_unused]] int32_t eid[1] = {0};
+      if constexpr (BWD) ent[0] = da_entry(g, e);
+      if constexpr (BWD ? BIAS : EID) eid[0] = da_eid(g, da_eid_raw(g, e), e);
+      DaBias<VEC, 1, BIAS> bs;
+      if constexpr (BIAS) da_bias_load<VEC, 1>(g, ln, eid, bs);
+      DaRows<VEC, 1> w;
+      da_gather<VEC, 1, T>(g, ln, src, w);
+      if constexpr (EDGE) {
+        if constexpr (BWD) eid[0] = da_eid(g, da_eid_raw(g, e), e);
+        DaEdgeRows<VEC, 1, true> we;
+        da_gather_edge<VEC, 1>(g, ln, eid, we);
+        da_edge_add<VEC, 1>(w, we);
+      }
+      Fold::fold(g, ln, key, ctx..., w, ent, bs, eid, lone);
+    }
+  }
+};
 
-// the table of the family (lane shapes: da_pick and PYGAT_DA_DISPATCH of da_lanes.h): (variant, forward | backward, long | row, lane shape) -> the kernel; null where there is none.  What a
-// launcher starts and what pygat_kernel_footprint reports on both come from here
+// the table of the family (lane shapes: da_pick and PYGAT_DA_DISPATCH of da_lanes.h): (variant, forward | backward, long | row, lane
+// shape) -> the kernel of da_family.h on DaFam<variant>; null where there is none.  What a launcher starts and what
+// pygat_kernel_footprint reports on both come from here
 template <int LPR, int VEC, unsigned V>
 static const void* da_kernel_at(bool bwd, bool lng) {
   if constexpr (da_exists(V, true)) {
-    if (bwd) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<LPR, VEC, V>)
-                        : reinterpret_cast<const void*>(&da_bwd_row_kernel<LPR, VEC, V>);
+    if (bwd) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<DaFam<V>, LPR, VEC>)
+                        : reinterpret_cast<const void*>(&da_bwd_row_kernel<DaFam<V>, LPR, VEC>);
   } else if (bwd) return nullptr;
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<LPR, VEC, V>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<LPR, VEC, V>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<DaFam<V>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<DaFam<V>, LPR, VEC>);
 }
 template <unsigned V>
 static const void* da_kernel_of(bool bwd, bool lng, int lpr, int vec) {
@@ -531,15 +403,9 @@ int footprint_k19(const char* name, int* regs, int* scratch) {
       {"k19_", 0}, {"k19b_", DA_BIAS}, {"k19h_", DA_BF16}, {"k19hb_", DA_BF16 | DA_BIAS},
       {"k19d_", DA_DROP}, {"k19db_", DA_DROP | DA_BIAS}, {"k19e_", DA_EDGE}, {"k19eb_", DA_EDGE | DA_BIAS}};
   const void* fn = nullptr;
-  for (const auto& nm : names) {
-    char dir[8] = "", kind[8] = "", rest = 0;
-    int lpr = 0, vec = 0;
-    const size_t np = strlen(nm.prefix);
-    if (!strncmp(name, nm.prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
-        lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) &&
-        (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
-      fn = da_kernel(nm.variant, !strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
-  }
+  DaKernelName k;
+  for (const auto& nm : names)
+    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1) fn = da_kernel(nm.variant, k.pass == 1, k.lng, k.lpr, k.vec);
   if (!fn) {
     set_error("kernel_footprint: unknown kernel '%s' (k19{,b,h,hb,d,db,e,eb}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>; k19h*: fwd only)", name);
     return PYGAT_EINVAL;
@@ -549,20 +415,11 @@ int footprint_k19(const char* name, int* regs, int* scratch) {
 
 #define DA_PAD_HINT "zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged"
 
-static int da_check_shape(const char* what, int64_t nnz, int H, int F) {
-  PYGAT_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31), "%s: nnz %lld outside [0, 2^31) (int32 entry indexing)", what, (long long)nnz);
-  PYGAT_REQUIRE(H >= 1 && H <= 64, "%s: H=%d heads outside [1, 64]", what, H);
-  PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (" DA_PAD_HINT ")",
-                what, F);
-  PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
-  return PYGAT_OK;
-}
-
 // kv_bytes: the size of an element of k and v (4, or 2: bf16 tables); keep_mz: the launcher writes or reads m and Z
 static int da_check_common(const char* what, int n_rows, int64_t nnz, int H, int F, const int32_t* rowptr, const int32_t* col,
                            const float* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const float* out,
                            int64_t ldo, const float* m, const float* Z, const void* ws, int kv_bytes = 4, bool keep_mz = true) {
-  const int rc = da_check_shape(what, nnz, H, F);
+  const int rc = da_check_shape(what, nnz, H, F, DA_PAD_HINT);
   if (rc != PYGAT_OK) return rc;
   PYGAT_REQUIRE(n_rows >= 0, "%s: n_rows=%d", what, n_rows);
   PYGAT_REQUIRE(n_rows > 0 || nnz == 0, "%s: n_rows=0 with nnz=%lld entries", what, (long long)nnz);
@@ -586,9 +443,9 @@ using namespace pygat;
 
 extern "C" int pygat_dot_attn_workspace_bytes(int64_t nnz, int H, int F, size_t* bytes) {
   PYGAT_REQUIRE(bytes, "dot_attn_workspace_bytes: null bytes");
-  const int rc = da_check_shape("dot_attn_workspace_bytes", nnz, H, F);
+  const int rc = da_check_shape("dot_attn_workspace_bytes", nnz, H, F, DA_PAD_HINT);
   if (rc != PYGAT_OK) return rc;
-  *bytes = (size_t)(long_records(nnz) * da_pstride(H, F)) * sizeof(float);
+  *bytes = (size_t)da_part_floats(nnz, H, F) * sizeof(float);
   return PYGAT_OK;
 }
 
@@ -701,14 +558,9 @@ static int da_launch(const DaCall& c) {
   if (bias) { g.bias = c.bias; g.bhs = c.bias_head_stride; g.bstride = c.bias_head_stride ? c.H : 1; g.dbias = c.dbias; }
   if (drop) g.rng = rng;
   if (edge) { g.e = c.edge.e; g.lde = c.edge.lde; g.de = c.edge.de; g.ldde = c.edge.ldde; }
-  int lpr, vec, nch;
-  da_pick(c.H, c.F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(c.nnz);
-  const unsigned blocks = (unsigned)cdiv(c.n_rows, 4 * (64 / lpr));
-  hipStream_t st = (hipStream_t)c.stream;
-  void* args[] = {&g};
-  if (chunks) (void)hipLaunchKernel(da_kernel(c.variant, c.bwd, true, lpr, vec), dim3(chunks), dim3(64), args, 0, st);
-  (void)hipLaunchKernel(da_kernel(c.variant, c.bwd, false, lpr, vec), dim3(blocks), dim3(256), args, 0, st);
+  const DaGrid gd = da_grid(c.n_rows, c.nnz, c.H, c.F);
+  da_launch_pair(da_kernel(c.variant, c.bwd, true, gd.lpr, gd.vec), da_kernel(c.variant, c.bwd, false, gd.lpr, gd.vec), g, gd.chunks,
+                 gd.blocks, c.stream);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }

@@ -1,7 +1,8 @@
 // K20 -- additive_attention: the GAT score over the entries of every row of a sparse pattern whose row side and column side are
 // different tables, for H heads at once, in one pass, and the row side of its gradient.  One kernel family in K19's shape: four
 // kernels (forward | backward rows) x (long | row), instantiated per lane shape and per LOGIT, the compile-time flag of the per-entry
-// term.
+// term.  The forward pair is da_family.h's, shared with K19 and K21, on AaFam below; the backward pair, whose row gradient is one
+// scalar per head and not a row of H*F floats, is written here.
 //
 // Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h:
 //   z = s_dst[i, h] + s_src[j, h]                      one rounded add;  LOGIT: z = (s_dst[i, h] + s_src[j, h]) + u[c, h], two rounded
@@ -35,9 +36,8 @@
 //   a row of one entry      out_i = v_j bit for bit and dz = 0 exactly: D and dp are formed by the same routine on the same bits
 //   u = 0                   changes no bit of out, ds_dst, P or S against the kernels without LOGIT (x + 0 is x)
 //   a large negative finite u (-9e15) gives p = 0 exactly while the row keeps another entry and slope > 0 (at slope 0 l is 0: no mask)
-#include "da_lanes.h"
+#include "da_family.h"
 #include <math.h>
-#include <string.h>
 
 namespace pygat {
 
@@ -166,104 +166,34 @@ struct AaFwdFold {
   }
 };
 
-// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool LOGIT>
-__global__ __launch_bounds__(64) void aa_fwd_long_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int HF = g.H * g.F;
-  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
-                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
-    float sd[VEC];
+// the family: what the forward kernels of da_family.h hold of a row and how they walk it, per LOGIT.  walk forwards to aa_walk, which
+// the backward kernels below call themselves: as the family's member, K21's way, it moved the LOGIT forward at 64 lanes a row
+template <bool LOGIT>
+struct AaFam {
+  static constexpr bool KEEP_MZ = true;
+  template <int VEC> using Own = float[VEC];                   // s_dst of the row, per chunk slot
+  __device__ __forceinline__ static DaNoKey key(const DaArgs&) { return {}; }
+  template <int VEC>
+  __device__ __forceinline__ static void load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, float (&sd)[VEC]) {
     aa_load_sd<VEC>(g, ln, row, sd);
-    DaState<VEC> st;
-    da_init<VEC>(st);
-    aa_walk<VEC, LOGIT, false, AaFwdFold<VEC, LOGIT>>(g, ln, e0 + grp, e1, EPW, sd, st);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
-      float mx = st.m[v];
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-      const float f = __expf(st.m[v] - mx);                    // (a lane group without entries: 0 x 0)
-      st.z[v] *= f;
-      da_scale(st.acc[v], f);
-      st.m[v] = mx;
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) {
-        st.z[v] += __shfl_xor(st.z[v], off);
-        da_add(st.acc[v], da_shfl_xor(st.acc[v], off));
-      }
-    }
-    if (grp == 0) {
-      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
-      da_store_row<VEC>(p, ln, st.acc);
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        if (ln.lead >> v & 1) { p[HF + ln.head[v]] = st.m[v]; p[HF + g.H + ln.head[v]] = st.z[v]; }
-    }
-  });
-}
-
-// launch 2: one lane group per row
-template <int LPR, int VEC, bool LOGIT>
-__global__ __launch_bounds__(256) void aa_fwd_row_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
-  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-  const int HF = g.H * g.F;
-  DaState<VEC> st;
-  da_init<VEC>(st);
-  if (end - start > LONG_ROW) {
-    for_long_records(start, end, [&](int64_t rec) {
-      const float* p = g.part + rec * g.pstride;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        da_merge(st.m[v], st.z[v], st.acc[v], p[HF + ln.head[v]], p[HF + g.H + ln.head[v]], ld4(p + ln.ofs[v]));
-    });
-  } else if (end > start) {
-    float sd[VEC];
-    aa_load_sd<VEC>(g, ln, row, sd);
-    aa_walk<VEC, LOGIT, false, AaFwdFold<VEC, LOGIT>>(g, ln, start, end, 1, sd, st);
   }
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    if (!(ln.ok >> v & 1)) continue;
-    const bool any = end > start;
-    const float z = st.z[v];
-    const float4 a = st.acc[v];
-    st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
-    if (ln.lead >> v & 1) {
-      g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
-      g.Z[row * g.H + ln.head[v]] = z;
-    }
+  template <int LPR, int VEC, int PASS>
+  __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool, DaNoKey,
+                                              const float (&sd)[VEC], DaState<VEC>& st) {
+    aa_walk<VEC, LOGIT, false, AaFwdFold<VEC, LOGIT>>(g, ln, e0, e1, step, sd, st);
   }
-}
+};
 
 // ------------------------------------------------------------------------------------------------------------- backward, row side
 template <int VEC>
-struct AaRow {                 // what the backward holds of its row
+struct AaRow : DaGrad<VEC> {   // what the backward holds of its row
   float sd[VEC];
-  float4 G[VEC];
-  float m[VEC], rz[VEC], D[VEC];
 };
 
 template <int LPR, int VEC>
 __device__ __forceinline__ void aa_bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, AaRow<VEC>& r) {
-  float4 o[VEC];
   aa_load_sd<VEC>(g, ln, row, r.sd);
-  da_load_row<VEC>(g.G + row * g.ldg, ln, r.G);
-  da_load_row<VEC>(g.out + row * g.ldo, ln, o);
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    r.m[v] = g.m[row * g.H + ln.head[v]];
-    r.rz[v] = 1.f / g.Z[row * g.H + ln.head[v]];
-    r.D[v] = da_head_sum<LPR>(dot4(r.G[v], o[v]), g.LH);
-  }
+  da_grad_load<LPR, VEC>(g, ln, row, r);
 }
 
 // the backward's fold of a batch; ctx: the row (AaRow) and the sums of dz of its heads, one per chunk slot (every lane of a head holds
@@ -352,8 +282,8 @@ template <int LPR, int VEC, bool LOGIT>
 static const void* aa_kernel_at(bool bwd, bool lng) {
   if (bwd) return lng ? reinterpret_cast<const void*>(&aa_bwd_long_kernel<LPR, VEC, LOGIT>)
                       : reinterpret_cast<const void*>(&aa_bwd_row_kernel<LPR, VEC, LOGIT>);
-  return lng ? reinterpret_cast<const void*>(&aa_fwd_long_kernel<LPR, VEC, LOGIT>)
-             : reinterpret_cast<const void*>(&aa_fwd_row_kernel<LPR, VEC, LOGIT>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<AaFam<LOGIT>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<AaFam<LOGIT>, LPR, VEC>);
 }
 static const void* aa_kernel(bool logit, bool bwd, bool lng, int lpr, int vec) {
   if (logit) PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, true>(bwd, lng)));
@@ -366,15 +296,9 @@ static const void* aa_kernel(bool logit, bool bwd, bool lng, int lpr, int vec) {
 int footprint_k20(const char* name, int* regs, int* scratch) {
   static const struct { const char* prefix; bool logit; } names[] = {{"k20_", false}, {"k20u_", true}};
   const void* fn = nullptr;
-  for (const auto& nm : names) {
-    char dir[8] = "", kind[8] = "", rest = 0;
-    int lpr = 0, vec = 0;
-    const size_t np = strlen(nm.prefix);
-    if (!strncmp(name, nm.prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 && lpr >= 1 &&
-        lpr <= 64 && (lpr & (lpr - 1)) == 0 && (!strcmp(dir, "fwd") || !strcmp(dir, "bwd")) &&
-        (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
-      fn = aa_kernel(nm.logit, !strcmp(dir, "bwd"), !strcmp(kind, "long"), lpr, vec);
-  }
+  DaKernelName k;
+  for (const auto& nm : names)
+    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1) fn = aa_kernel(nm.logit, k.pass == 1, k.lng, k.lpr, k.vec);
   if (!fn) {
     set_error("kernel_footprint: unknown kernel '%s' (k20{,u}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
     return PYGAT_EINVAL;
@@ -384,14 +308,7 @@ int footprint_k20(const char* name, int* regs, int* scratch) {
 
 #define AA_PAD_HINT "zero-padding the columns of v to the next allowed F leaves the first F columns of the result unchanged"
 
-static int aa_check_shape(const char* what, int64_t nnz, int H, int F) {
-  PYGAT_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31), "%s: nnz %lld outside [0, 2^31) (int32 entry indexing)", what, (long long)nnz);
-  PYGAT_REQUIRE(H >= 1 && H <= 64, "%s: H=%d heads outside [1, 64]", what, H);
-  PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (" AA_PAD_HINT ")",
-                what, F);
-  PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
-  return PYGAT_OK;
-}
+static int aa_check_shape(const char* what, int64_t nnz, int H, int F) { return da_check_shape(what, nnz, H, F, AA_PAD_HINT); }
 
 // what an entry point asks for, every argument under the name include/pygat_amd.h gives it; out, m and Z are written by the forward
 // and read by the backward; what the forward does not have stays zero
@@ -453,14 +370,9 @@ static int aa_launch(const AaCall& c) {
   if (c.bwd || logit) g.perm = c.perm;                            // (the forward without a logit walks in CSR order alone)
   if (c.bwd) { g.G = c.G; g.ldg = c.ldg; g.dq = c.ds_dst; g.lddq = c.H; g.P = c.P; g.S = c.S; }
   if (logit) { g.bias = c.edge_logit; g.bhs = c.logit_head_stride; g.bstride = c.logit_head_stride ? c.H : 1; }
-  int lpr, vec, nch;
-  da_pick(c.H, c.F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(c.nnz);
-  const unsigned blocks = (unsigned)cdiv(c.n_rows, 4 * (64 / lpr));
-  hipStream_t st = (hipStream_t)c.stream;
-  void* args[] = {&g};
-  if (chunks) (void)hipLaunchKernel(aa_kernel(logit, c.bwd, true, lpr, vec), dim3(chunks), dim3(64), args, 0, st);
-  (void)hipLaunchKernel(aa_kernel(logit, c.bwd, false, lpr, vec), dim3(blocks), dim3(256), args, 0, st);
+  const DaGrid gd = da_grid(c.n_rows, c.nnz, c.H, c.F);
+  da_launch_pair(aa_kernel(logit, c.bwd, true, gd.lpr, gd.vec), aa_kernel(logit, c.bwd, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks,
+                 c.stream);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -473,7 +385,7 @@ extern "C" int pygat_add_attn_workspace_bytes(int64_t nnz, int H, int F, size_t*
   PYGAT_REQUIRE(bytes, "add_attn_workspace_bytes: null bytes");
   const int rc = aa_check_shape("add_attn_workspace_bytes", nnz, H, F);
   if (rc != PYGAT_OK) return rc;
-  *bytes = (size_t)(long_records(nnz) * da_pstride(H, F)) * sizeof(float);
+  *bytes = (size_t)da_part_floats(nnz, H, F) * sizeof(float);
   return PYGAT_OK;
 }
 

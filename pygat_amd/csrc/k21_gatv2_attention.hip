@@ -1,7 +1,8 @@
 // K21 -- gatv2_attention: the GATv2 score a . LeakyReLU(x_dst_i + x_src_j) over the entries of every row of a sparse pattern whose row
 // side and column side are different tables, for H heads at once, in one pass, and both sides of its gradient.  One kernel family in
 // the shape of K19 and K20: (forward | backward rows | backward columns) x (long | row), instantiated per lane shape; the two row
-// passes also per SHARED, the compile-time flag of v == x_src; and the two kernels of the staged reduce of da.
+// passes also per SHARED, the compile-time flag of v == x_src; and the two kernels of the staged reduce of da.  The kernels of the two
+// row passes are da_family.h's, shared with K19 and K20, on V2Fam below; the column pass and the reduce of da are written here.
 //
 // Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h, feature f:
 //   t[f] = x_dst[i, h, f] + x_src[j, h, f]             one rounded add
@@ -22,7 +23,7 @@
 // lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane; the chunks of a head sit on LH = F / 4 adjacent lanes of one
 // chunk slot.  The walked side's own row and the lane's chunk of a are loaded once per row; per entry a lane loads its 16 bytes of the
 // gathered row (and of v_j without SHARED; the S scalars of its heads in the column pass), several entries in flight (v2_unroll), the
-// indices of the next batch asked for under this batch's arithmetic (v2_walk, after K19's da_walk).  One __expf per (entry, head)
+// indices of the next batch asked for under this batch's arithmetic (V2Fam::walk, after K19's).  One __expf per (entry, head)
 // goes into the online (m, Z, acc) state (da_fold).
 //
 // Long rows (and long columns) go through partial records (the rule of long_rows.h), one wave per chunk: its lane groups walk the
@@ -40,9 +41,9 @@
 //   a row without entries   out = m = Z = dx_dst = 0 exactly; a column without entries dx_src = 0
 //   a row of one entry      out_i = v_j bit for bit and S = 0 exactly: D and dp are formed by the same routine on the same bits
 //   SHARED                  the same operations on the same values as the kernels without the flag fed a copy of x_src
-#include "da_lanes.h"
+#include "da_family.h"
 #include <math.h>
-#include <string.h>
+#include <type_traits>
 
 namespace pygat {
 
@@ -115,56 +116,6 @@ __device__ __forceinline__ void v2_gather(const DaArgs& g, const DaLane<VEC>& ln
   }
 }
 
-// The walk of all three passes, after K19's da_walk: the entries e0, e0 + step, ... < e1 of one row, handed to Fold::fold in that
-// order, U at a time and then one at a time.  The indices of the next U entries -- the other side's row and, in the backward passes,
-// the caller's entry index (da_entry) -- are asked for before this batch's gather is used, so an iteration waits for one gather, not
-// for an index and then a gather.  The forward carries no entry index and does not touch perm.
-template <int VEC, int MODE, bool SHARED, typename Fold, typename... Ctx>
-__device__ __forceinline__ void v2_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, Ctx&... ctx) {
-  constexpr int U = v2_unroll(MODE != 0, VEC);
-  int64_t e = e0;
-  if constexpr (U > 1) {
-    int32_t src[U];
-    int64_t ent[U], ent_next[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) ent[u] = ent_next[u] = 0;
-    bool full = e + (U - 1) * step < e1;
-    if (full) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        src[u] = g.col[e + u * step];
-        if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
-      }
-    }
-    while (full) {
-      if constexpr (MODE != 0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
-      }
-      V2Rows<VEC, U, MODE, SHARED> w;
-      v2_gather<VEC, U, MODE, SHARED>(g, ln, src, ent, w);
-      e += U * step;
-      full = e + (U - 1) * step < e1;
-      if (full) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          src[u] = g.col[e + u * step];
-          if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
-        }
-      }
-      Fold::fold(g, ln, ctx..., w, ent);
-    }
-  }
-  for (; e < e1; e += step) {
-    const int32_t src[1] = {g.col[e]};
-    int64_t ent[1] = {0};
-    if constexpr (MODE != 0) ent[0] = da_entry(g, e);
-    V2Rows<VEC, 1, MODE, SHARED> w;
-    v2_gather<VEC, 1, MODE, SHARED>(g, ln, src, ent, w);
-    Fold::fold(g, ln, ctx..., w, ent);
-  }
-}
-
 // what every pass holds of the walked side: its own row (x_dst[i]; x_src[j] in the column pass) and the lane's chunks of a
 template <int VEC>
 struct V2Own {
@@ -187,108 +138,11 @@ struct V2FwdFold {
   }
 };
 
-// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record (acc, m, Z)
-template <int LPR, int VEC, bool SHARED>
-__global__ __launch_bounds__(64) void v2_fwd_long_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int HF = g.H * g.F;
-  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
-                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
-    V2Own<VEC> r;
-    da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, r.x);
-    da_load_row<VEC>(g.bias, ln, r.a);
-    DaState<VEC> st;
-    da_init<VEC>(st);
-    v2_walk<VEC, 0, SHARED, V2FwdFold<LPR, VEC, SHARED>>(g, ln, e0 + grp, e1, EPW, r, st);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {                            // lane groups of the wave: the maximum first, one rescale, a fixed butterfly
-      float mx = st.m[v];
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-      const float f = __expf(st.m[v] - mx);                    // (a lane group without entries: 0 x 0)
-      st.z[v] *= f;
-      da_scale(st.acc[v], f);
-      st.m[v] = mx;
-#pragma unroll
-      for (int off = LPR; off < 64; off <<= 1) {
-        st.z[v] += __shfl_xor(st.z[v], off);
-        da_add(st.acc[v], da_shfl_xor(st.acc[v], off));
-      }
-    }
-    if (grp == 0) {
-      float* p = g.part + long_record(blockIdx.x, slot) * g.pstride;
-      da_store_row<VEC>(p, ln, st.acc);
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        if (ln.lead >> v & 1) { p[HF + ln.head[v]] = st.m[v]; p[HF + g.H + ln.head[v]] = st.z[v]; }
-    }
-  });
-}
-
-// launch 2: one lane group per row
-template <int LPR, int VEC, bool SHARED>
-__global__ __launch_bounds__(256) void v2_fwd_row_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
-  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-  const int HF = g.H * g.F;
-  DaState<VEC> st;
-  da_init<VEC>(st);
-  if (end - start > LONG_ROW) {
-    for_long_records(start, end, [&](int64_t rec) {
-      const float* p = g.part + rec * g.pstride;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v)
-        da_merge(st.m[v], st.z[v], st.acc[v], p[HF + ln.head[v]], p[HF + g.H + ln.head[v]], ld4(p + ln.ofs[v]));
-    });
-  } else if (end > start) {
-    V2Own<VEC> r;
-    da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
-    da_load_row<VEC>(g.bias, ln, r.a);
-    v2_walk<VEC, 0, SHARED, V2FwdFold<LPR, VEC, SHARED>>(g, ln, start, end, 1, r, st);
-  }
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    if (!(ln.ok >> v & 1)) continue;
-    const bool any = end > start;
-    const float z = st.z[v];
-    const float4 a = st.acc[v];
-    st4(g.out + row * g.ldo + ln.ofs[v], any ? make_float4(a.x / z, a.y / z, a.z / z, a.w / z) : da_zero4());
-    if (ln.lead >> v & 1) {
-      g.m[row * g.H + ln.head[v]] = any ? st.m[v] : 0.f;
-      g.Z[row * g.H + ln.head[v]] = z;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------- backward, row side
 template <int VEC>
-struct V2BwdRow {              // what the backward holds of its row
+struct V2BwdRow : DaGrad<VEC> {   // what the backward holds of its row
   V2Own<VEC> own;
-  float4 G[VEC];
-  float m[VEC], rz[VEC], D[VEC];
 };
-
-template <int LPR, int VEC>
-__device__ __forceinline__ void v2_bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, V2BwdRow<VEC>& r) {
-  float4 o[VEC];
-  da_load_row<VEC>(g.q + row * g.ldq, ln, r.own.x);
-  da_load_row<VEC>(g.bias, ln, r.own.a);
-  da_load_row<VEC>(g.G + row * g.ldg, ln, r.G);
-  da_load_row<VEC>(g.out + row * g.ldo, ln, o);
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    r.m[v] = g.m[row * g.H + ln.head[v]];
-    r.rz[v] = 1.f / g.Z[row * g.H + ln.head[v]];
-    r.D[v] = da_head_sum<LPR>(dot4(r.G[v], o[v]), g.LH);
-  }
-}
 
 // the backward's fold of a batch; ctx: the row (V2BwdRow) and the lane's chunks of dx_dst.  In a row of one entry out_i is v_j bit for
 // bit, so dp and D are one routine on the same bits and S is an exact zero
@@ -316,62 +170,79 @@ struct V2BwdFold {
 };
 
 template <int VEC>
-__device__ __forceinline__ void v2_zero(float4 (&x)[VEC]) {
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) x[v] = da_zero4();
-}
-// the lane groups of a wave, a fixed butterfly
-template <int LPR, int VEC>
-__device__ __forceinline__ void v2_wave_sum(float4 (&x)[VEC]) {
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1)
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) da_add(x[v], da_shfl_xor(x[v], off));
-}
+struct V2ColFold;
 
-// launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the H F sums of dx_dst
-template <int LPR, int VEC, bool SHARED>
-__global__ __launch_bounds__(64) void v2_bwd_long_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, grp = lane / LPR;
-  const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
-                [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
-    V2BwdRow<VEC> r;
-    v2_bwd_load<LPR, VEC>(g, ln, row, r);
-    float4 dx[VEC];
-    v2_zero<VEC>(dx);
-    v2_walk<VEC, 1, SHARED, V2BwdFold<LPR, VEC, SHARED>>(g, ln, e0 + grp, e1, EPW, r, dx);
-    v2_wave_sum<LPR, VEC>(dx);
-    if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dx);
-  });
-}
-
-// launch 2: one lane group per row
-template <int LPR, int VEC, bool SHARED>
-__global__ __launch_bounds__(256) void v2_bwd_row_kernel(DaArgs g) {
-  constexpr int EPW = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW + lane / LPR;
-  if (row >= g.n) return;                                      // (whole lane groups; nothing below crosses a group)
-  const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
-  const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
-  float4 dx[VEC];
-  v2_zero<VEC>(dx);
-  if (end - start > LONG_ROW) {
-    for_long_records(start, end, [&](int64_t rec) {
-      const float* p = g.part + rec * g.pstride;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) da_add(dx[v], ld4(p + ln.ofs[v]));
-    });
-  } else if (end > start) {                                    // (a row without entries: its G row is not read)
-    V2BwdRow<VEC> r;
-    v2_bwd_load<LPR, VEC>(g, ln, row, r);
-    v2_walk<VEC, 1, SHARED, V2BwdFold<LPR, VEC, SHARED>>(g, ln, start, end, 1, r, dx);
+// the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED (the column pass: without)
+template <bool SHARED>
+struct V2Fam {
+  static constexpr bool KEEP_MZ = true;
+  template <int VEC> using Own = V2Own<VEC>;
+  template <int VEC> using Row = V2BwdRow<VEC>;
+  __device__ __forceinline__ static DaNoKey key(const DaArgs&) { return {}; }
+  __device__ __forceinline__ static bool lone(int64_t, int64_t) { return false; }
+  template <int VEC>
+  __device__ __forceinline__ static void load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, V2Own<VEC>& r) {
+    da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
+    da_load_row<VEC>(g.bias, ln, r.a);
   }
-  da_store_row<VEC>(g.dq + row * g.lddq, ln, dx);
-}
+  // The walk of all three passes, after K19's: the entries e0, e0 + step, ... < e1 of one row, handed to the pass's fold in that
+  // order, U at a time and then one at a time.  The indices of the next U entries -- the other side's row and, in the backward passes,
+  // the caller's entry index (da_entry) -- are asked for before this batch's gather is used, so an iteration waits for one gather, not
+  // for an index and then a gather.  The forward carries no entry index and does not touch perm.
+  template <int LPR, int VEC, int MODE, typename... Ctx>
+  __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
+                                                DaNoKey, Ctx&... ctx) {
+    using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED>,
+                                    std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED>, V2ColFold<VEC>>>;
+    constexpr int U = v2_unroll(MODE != 0, VEC);
+    int64_t e = e0;
+    if constexpr (U > 1) {
+      int32_t src[U];
+      int64_t ent[U], ent_next[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) ent[u] = ent_next[u] = 0;
+      bool full = e + (U - 1) * step < e1;
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          src[u] = g.col[e + u * step];
+          if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+        }
+      }
+      while (full) {
+        if constexpr (MODE != 0) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
+        }
+        V2Rows<VEC, U, MODE, SHARED> w;
+        v2_gather<VEC, U, MODE, SHARED>(g, ln, src, ent, w);
+        e += U * step;
+        full = e + (U - 1) * step < e1;
+        if (full) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            src[u] = g.col[e + u * step];
+            if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+          }
+        }
+        Fold::fold(g, ln, ctx..., w, ent);
+      }
+    }
+    for (; e < e1; e += step) {
+      const int32_t src[1] = {g.col[e]};
+      int64_t ent[1] = {0};
+      if constexpr (MODE != 0) ent[0] = da_entry(g, e);
+      V2Rows<VEC, 1, MODE, SHARED> w;
+      v2_gather<VEC, 1, MODE, SHARED>(g, ln, src, ent, w);
+      Fold::fold(g, ln, ctx..., w, ent);
+    }
+  }
+  template <int LPR, int VEC>
+  __device__ __forceinline__ static void bwd_load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, V2BwdRow<VEC>& r) {
+    load<VEC>(g, ln, row, r.own);
+    da_grad_load<LPR, VEC>(g, ln, row, r);
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------- backward, column side
 // the column pass's fold of a batch; ctx: the column's own row and a (V2Own), the lane's chunks of dx_src, of da and of da's
@@ -410,21 +281,21 @@ __global__ __launch_bounds__(64) void v2_col_long_kernel(DaArgs g) {
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
   float4 da[VEC], dc[VEC];
-  v2_zero<VEC>(da);
-  v2_zero<VEC>(dc);
+  da_zero_row<VEC>(da);
+  da_zero_row<VEC>(dc);
   for_long_rows(g.rowptr, row_of(g.rowptr, g.n, ch.c0), row_of(g.rowptr, g.n, ch.c1 - 1), ch,
                 [&](int row, int64_t, int64_t, int64_t e0, int64_t e1, int slot) {
     V2Own<VEC> r;
     da_load_row<VEC>(g.q + (int64_t)row * g.ldq, ln, r.x);
     da_load_row<VEC>(g.bias, ln, r.a);
     float4 dx[VEC];
-    v2_zero<VEC>(dx);
-    v2_walk<VEC, 2, false, V2ColFold<VEC>>(g, ln, e0 + grp, e1, EPW, r, dx, da, dc);
-    v2_wave_sum<LPR, VEC>(dx);
+    da_zero_row<VEC>(dx);
+    V2Fam<false>::walk<LPR, VEC, 2>(g, ln, e0 + grp, e1, EPW, false, DaNoKey{}, r, dx, da, dc);
+    da_wave_sum<LPR, VEC>(dx);
     if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dx);
   });
   v2_settle<VEC>(da, dc);
-  v2_wave_sum<LPR, VEC>(da);
+  da_wave_sum<LPR, VEC>(da);
   if (grp == 0) da_store_row<VEC>(g.de + (int64_t)blockIdx.x * g.ldde, ln, da);
 }
 
@@ -449,8 +320,8 @@ __global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
   V2Own<VEC> r;
   da_load_row<VEC>(g.bias, ln, r.a);
   float4 da[VEC], dc[VEC];
-  v2_zero<VEC>(da);
-  v2_zero<VEC>(dc);
+  da_zero_row<VEC>(da);
+  da_zero_row<VEC>(dc);
   const int64_t x0 = (int64_t)blockIdx.x * LONG_CHUNK;
   const int c0 = v2_first_at(g.rowptr, g.n, x0);
   const int c1 = blockIdx.x + 1 == gridDim.x ? g.n : v2_first_at(g.rowptr, g.n, x0 + LONG_CHUNK);
@@ -459,7 +330,7 @@ __global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
     if (row >= c1) continue;                                   // (whole lane groups; nothing inside the loop crosses a group)
     const int64_t start = g.rowptr[row], end = g.rowptr[row + 1];
     float4 dx[VEC];
-    v2_zero<VEC>(dx);
+    da_zero_row<VEC>(dx);
     if (end - start > LONG_ROW) {                              // (its da went into the long-column kernel's records)
       for_long_records(start, end, [&](int64_t rec) {
         const float* p = g.part + rec * g.pstride;
@@ -468,12 +339,12 @@ __global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
       });
     } else if (end > start) {
       da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
-      v2_walk<VEC, 2, false, V2ColFold<VEC>>(g, ln, start, end, 1, r, dx, da, dc);
+      V2Fam<false>::walk<LPR, VEC, 2>(g, ln, start, end, 1, false, DaNoKey{}, r, dx, da, dc);
     }
     da_store_row<VEC>(g.dq + row * g.lddq, ln, dx);
   }
   v2_settle<VEC>(da, dc);
-  v2_wave_sum<LPR, VEC>(da);
+  da_wave_sum<LPR, VEC>(da);
   if (grp == 0) da_store_row<VEC>(g.dbias + ((int64_t)blockIdx.x * 4 + wave) * g.ldde, ln, da);
 }
 
@@ -508,10 +379,10 @@ template <int LPR, int VEC, bool SHARED>
 static const void* v2_kernel_at(int pass, bool lng) {
   if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC>)
                             : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC>);
-  if (pass == 1) return lng ? reinterpret_cast<const void*>(&v2_bwd_long_kernel<LPR, VEC, SHARED>)
-                            : reinterpret_cast<const void*>(&v2_bwd_row_kernel<LPR, VEC, SHARED>);
-  return lng ? reinterpret_cast<const void*>(&v2_fwd_long_kernel<LPR, VEC, SHARED>)
-             : reinterpret_cast<const void*>(&v2_fwd_row_kernel<LPR, VEC, SHARED>);
+  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED>, LPR, VEC>)
+                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED>, LPR, VEC>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED>, LPR, VEC>);
 }
 static const void* v2_kernel(bool shared, int pass, bool lng, int lpr, int vec) {
   if (shared) PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, true>(pass, lng)));
@@ -526,16 +397,10 @@ int footprint_k21(const char* name, int* regs, int* scratch) {
   const void* fn = nullptr;
   if (!strcmp(name, "k21_da_stage")) fn = reinterpret_cast<const void*>(&v2_da_stage_kernel);
   if (!strcmp(name, "k21_da_final")) fn = reinterpret_cast<const void*>(&v2_da_final_kernel);
-  for (const auto& nm : names) {
-    char dir[8] = "", kind[8] = "", rest = 0;
-    int lpr = 0, vec = 0;
-    const size_t np = strlen(nm.prefix);
-    if (!fn && !strncmp(name, nm.prefix, np) && sscanf(name + np, "%3[a-z]_%4[a-z]_l%dv%d%c", dir, kind, &lpr, &vec, &rest) == 4 &&
-        lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 &&
-        (!strcmp(dir, "fwd") || !strcmp(dir, "bwd") || (!strcmp(dir, "col") && !nm.shared)) &&
-        (!strcmp(kind, "long") || !strcmp(kind, "row")) && (vec == 1 || (lpr == 64 && vec >= 2 && vec <= 4)))
-      fn = v2_kernel(nm.shared, !strcmp(dir, "fwd") ? 0 : (!strcmp(dir, "bwd") ? 1 : 2), !strcmp(kind, "long"), lpr, vec);
-  }
+  DaKernelName k;
+  for (const auto& nm : names)
+    if (!fn && da_parse_kernel_name(name, nm.prefix, &k) && (k.pass != 2 || !nm.shared))
+      fn = v2_kernel(nm.shared, k.pass, k.lng, k.lpr, k.vec);
   if (!fn) {
     set_error("kernel_footprint: unknown kernel '%s' (k21{,s}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, k21_col_{long,row}_l<LPR>v<VEC>, "
               "k21_da_stage, k21_da_final)", name);
@@ -547,23 +412,15 @@ int footprint_k21(const char* name, int* regs, int* scratch) {
 #define V2_PAD_HINT "zero-padding the columns of x_dst, x_src, a and v to the next allowed F leaves the first F columns of the result " \
                     "unchanged: zero columns of a add nothing to a score"
 
-static int v2_check_shape(const char* what, int64_t nnz, int H, int F) {
-  PYGAT_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31), "%s: nnz %lld outside [0, 2^31) (int32 entry indexing)", what, (long long)nnz);
-  PYGAT_REQUIRE(H >= 1 && H <= 64, "%s: H=%d heads outside [1, 64]", what, H);
-  PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (" V2_PAD_HINT ")",
-                what, F);
-  PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
-  return PYGAT_OK;
-}
+static int v2_check_shape(const char* what, int64_t nnz, int H, int F) { return da_check_shape(what, nnz, H, F, V2_PAD_HINT); }
 
 // the workspace, in floats: the long-row records of a pass (every pass starts at the front), then the da records -- one per chunk of
 // the long-column kernel, then one per wave of the column kernel, four to a chunk -- then the staged partial sums
-static inline int64_t v2_part_floats(int64_t nnz, int H, int F) { return long_records(nnz) * da_pstride(H, F); }
 // (the column kernel's grid: a work-group per chunk of entries, one for a pattern without entries)
 static inline int64_t v2_col_blocks(int64_t nnz) { return nnz > 0 ? long_chunks(nnz) : 1; }
 static inline int64_t v2_da_records(int64_t nnz) { return long_chunks(nnz) + 4 * v2_col_blocks(nnz); }
 static inline int64_t v2_ws_floats(int64_t nnz, int H, int F) {
-  return v2_part_floats(nnz, H, F) + (v2_da_records(nnz) + V2_DA_STAGE) * (int64_t)H * F;
+  return da_part_floats(nnz, H, F) + (v2_da_records(nnz) + V2_DA_STAGE) * (int64_t)H * F;
 }
 
 // what an entry point asks for, every argument under the name include/pygat_amd.h gives it; pass 0 forward, 1 backward rows, 2
@@ -638,25 +495,21 @@ static int v2_launch(const V2Call& c) {
   }
   if (c.pass != 0) { g.perm = c.perm; g.dq = c.dx; g.lddq = c.lddx; g.S = c.S; }   // (the forward walks in CSR order alone)
   if (c.pass == 1) { g.G = c.G; g.ldg = c.ldg; g.P = c.P; }
-  int lpr, vec, nch;
-  da_pick(c.H, c.F, &lpr, &vec, &nch);
-  const unsigned chunks = (unsigned)long_chunks(c.nnz);
-  unsigned blocks = (unsigned)cdiv(c.n, 4 * (64 / lpr));
+  DaGrid gd = da_grid(c.n, c.nnz, c.H, c.F);
   float* stage = nullptr;
   if (cols) {
-    blocks = (unsigned)v2_col_blocks(c.nnz);
+    gd.blocks = (unsigned)v2_col_blocks(c.nnz);
     g.ldde = HF;
-    g.de = g.part + v2_part_floats(c.nnz, c.H, c.F);
-    g.dbias = g.de + (int64_t)chunks * HF;
+    g.de = g.part + da_part_floats(c.nnz, c.H, c.F);
+    g.dbias = g.de + (int64_t)gd.chunks * HF;
     stage = g.de + v2_da_records(c.nnz) * HF;
   }
   hipStream_t st = (hipStream_t)c.stream;
-  void* args[] = {&g};
   const bool shared = !cols && !c.v;
-  if (chunks) (void)hipLaunchKernel(v2_kernel(shared, c.pass, true, lpr, vec), dim3(chunks), dim3(64), args, 0, st);
-  (void)hipLaunchKernel(v2_kernel(shared, c.pass, false, lpr, vec), dim3(blocks), dim3(256), args, 0, st);
+  da_launch_pair(v2_kernel(shared, c.pass, true, gd.lpr, gd.vec), v2_kernel(shared, c.pass, false, gd.lpr, gd.vec), g, gd.chunks,
+                 gd.blocks, c.stream);
   if (cols) {
-    const int nrec = (int)(chunks + 4 * blocks);
+    const int nrec = (int)(gd.chunks + 4 * gd.blocks);
     hipLaunchKernelGGL(v2_da_stage_kernel, dim3(V2_DA_STAGE), dim3(256), 0, st, HF, nrec, (const float*)g.de, stage);
     hipLaunchKernelGGL(v2_da_final_kernel, dim3((unsigned)cdiv(HF, 256)), dim3(256), 0, st, HF, (const float*)stage, c.da);
   }

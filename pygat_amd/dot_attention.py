@@ -61,6 +61,24 @@ def _require_tensor(op: str, pattern, name: str, t, dtype=torch.float32, want: s
         raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}{want}")
 
 
+def _require_heads(op: str, H: int, F: int, pad_hint: str):
+    """The row shapes the K19, K20 and K21 kernels take (csrc/da_family.h); pad_hint: how the op's caller reaches an allowed F."""
+    if not (1 <= H <= MAX_HEADS):
+        raise ValueError(f"pygat_amd {op}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
+    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
+        raise ValueError(f"pygat_amd {op}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {pad_hint}")
+    if H * F > MAX_ROW_FLOATS:
+        raise ValueError(f"pygat_amd {op}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
+                         f"{pad_hint}")
+
+
+def _slope(op: str, negative_slope) -> float:
+    """The negative slope of additive_attention's and gatv2_attention's LeakyReLU: a finite float."""
+    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
+        raise ValueError(f"pygat_amd {op}: negative_slope = {negative_slope!r}: a finite float expected")
+    return float(negative_slope)
+
+
 def _tables(op: str, pattern, q, others, bf16_others: bool = False):
     """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns,
     float32 like q, or bfloat16 where bf16_others (dot_attention's inference forward)."""
@@ -139,13 +157,7 @@ def edge_dot(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, scale: floa
 # ------------------------------------------------------------------------------------------------------------------- dot_attention
 def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False, op: str = "dot_attention"):
     H, F, flat = _tables(op, pattern, q, (("k", k), ("v", v)), bf16_tables)
-    if not (1 <= H <= MAX_HEADS):
-        raise ValueError(f"pygat_amd {op}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
-    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
-        raise ValueError(f"pygat_amd {op}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
-    if H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd {op}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
-                         f"{_PAD_HINT}")
+    _require_heads(op, H, F, _PAD_HINT)
     return H, F, flat
 
 

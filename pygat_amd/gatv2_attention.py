@@ -20,7 +20,6 @@ give the same bits.  Nothing is read back to the host.  There is no CPU path and
 """
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
@@ -28,18 +27,12 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import MIN_F, MAX_F, _require_pattern, _require_tensor
-from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
+from .dot_attention import _require_heads, _require_pattern, _require_tensor, _slope
+from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "gatv2_attention"
 _PAD_HINT = ("zero-pad the columns of all four tensors (x_dst, x_src, a and v) to the next allowed F: zero columns of a add nothing "
              "to a score, and the first F columns of the result are unchanged")
-
-
-def _slope(negative_slope) -> float:
-    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
-        raise ValueError(f"pygat_amd {_OP}: negative_slope = {negative_slope!r}: a finite float expected")
-    return float(negative_slope)
 
 
 def _checked(pattern, x_dst, x_src, a, v):
@@ -61,13 +54,7 @@ def _checked(pattern, x_dst, x_src, a, v):
         if t.shape[0] != rows:
             raise ValueError(f"pygat_amd {_OP}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
     H, F = (1 if x_dst.dim() == 2 else int(x_dst.shape[1])), int(x_dst.shape[-1])
-    if not (1 <= H <= MAX_HEADS):
-        raise ValueError(f"pygat_amd {_OP}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
-    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
-        raise ValueError(f"pygat_amd {_OP}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {_PAD_HINT}")
-    if H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd {_OP}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
-                         f"{_PAD_HINT}")
+    _require_heads(_OP, H, F, _PAD_HINT)
     return H, F
 
 
@@ -157,7 +144,7 @@ def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tens
     add nothing to a score.
     Not provided: a per-entry term or edge features, dropout on the coefficients, bfloat16 tables, the value product fused into the
     column pass (dv is a K17 launch on the transposed pattern)."""
-    slope = _slope(negative_slope)
+    slope = _slope(_OP, negative_slope)
     if v is None:
         return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src, slope, True)
     return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, v, slope, False)
