@@ -783,6 +783,34 @@ int pygat_add_attn_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr,
                                  const float* edge_logit, int logit_head_stride, const float* out, int64_t ldo, const float* m,
                                  const float* Z, const float* G, int64_t ldg, float* ds_dst, float* P, float* S, void* ws,
                                  void* stream);
+/* The K20 pair with seeded dropout of the softmax coefficients, for training (the DROP instantiations of the four K20 kernels), additive
+ * under ABI 16:
+ *   out[i, h, :] = sum_{e in row i} alpha[e, h] mask[c(e), h] v[j, h, :],   alpha = softmax_row(l) over ALL entries of the row -- a
+ * dropped entry stays in the denominator; m and Z are the undropped softmax's -- mask in {0, 1 / (1 - p)}, c(e) the CALLER's entry index
+ * (perm[e]; perm may be null: the position itself).  The mask is pygat_dot_attn_dropout_forward's: mask[c, h] is element idx = c H + h
+ * of the flat layout of pygat_dropout_mask, word (idx & 3) of Philox-4x32-10(counter = (idx >> 2 low word, idx >> 2 high word,
+ * stream_id, 0xFFFFFFFF), key = *seed), kept iff word < the threshold of p; pygat_dropout_mask(nnz H, p, seed, stream_id, ...) writes
+ * the same table, and one seed gives the same mask in K19, K20 and K21.  The decision is drawn in registers in the forward and again in
+ * backward_rows: no mask is stored.  Under dropout the walk carries the entry index in both passes, so the forward reads perm whether or
+ * not there is an edge_logit; without one it loads no logit.  seed is a uint64 in DEVICE memory, read by the kernels (nothing is read
+ * back; a captured graph replays with the seed found there).  backward_rows: D = <G, out>, dp = mask <G, v>, dz = p (dp - D) (z > 0 ?
+ * 1 : negative_slope), ds_dst = sum dz, P := p mask and S := dz, so dv = pygat_spmm_forward(val = P, b = G), ds_src =
+ * pygat_spmm_forward(val = S, b = ones) and S is the gradient of edge_logit as above.  edge_logit may be null: no term,
+ * logit_head_stride is then not looked at; an edge_logit of zeros changes no bit against the DROP kernels without it.  A row of one
+ * entry gets out_i = mask v_j bit for bit; its dz is an exact zero where the entry is dropped and where mask is a power of two (p =
+ * 0.5: mask dp and D are then the same bits), and otherwise the difference of two roundings, mask <G, v> against <G, mask v>: a few
+ * ulps of dp, not zero.  A row whose entries are all dropped, and every row at p = 1, get exact zeros in out.  Refusals as for the
+ * K20 pair after the launcher's own name; besides: a null or misaligned (8 bytes) seed, p outside [0, 1] (a NaN included).  Both
+ * launchers must be given the same p, seed value and stream_id.  The workspace is pygat_add_attn_workspace_bytes'. */
+int pygat_add_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                   int F, float negative_slope, const float* s_dst, const float* s_src, const float* v, int64_t ldv,
+                                   const float* edge_logit, int logit_head_stride, float p, const void* seed, uint32_t stream_id,
+                                   float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_add_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                         int H, int F, float negative_slope, const float* s_dst, const float* s_src, const float* v,
+                                         int64_t ldv, const float* edge_logit, int logit_head_stride, float p, const void* seed,
+                                         uint32_t stream_id, const float* out, int64_t ldo, const float* m, const float* Z,
+                                         const float* G, int64_t ldg, float* ds_dst, float* P, float* S, void* ws, void* stream);
 
 /* ------------------------------------------------ K21: the GATv2 score fused over an edge pattern (csrc/k21_gatv2_attention.hip)
  * Additive under ABI 16 (no existing entry point changes).  For H heads, over a CSR pattern (rowptr [n_rows + 1], col [nnz]) whose row
@@ -826,6 +854,31 @@ int pygat_v2_attn_backward_cols(int n_cols, int64_t nnz, const int32_t* rowptr_t
                                 int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
                                 int64_t lds, const float* a, const float* S, float* dx_src, int64_t lddx, float* da, void* ws,
                                 void* stream);
+/* The two K21 row passes with seeded dropout of the softmax coefficients, for training (the DROP instantiations of the forward and
+ * backward_rows kernels), additive under ABI 16:
+ *   out[i, h, :] = sum_{e in row i} alpha[e, h] mask[c(e), h] v[j, h, :],   alpha = softmax_row(s) over ALL entries of the row -- a
+ * dropped entry stays in the denominator; m and Z are the undropped softmax's -- mask in {0, 1 / (1 - p)}, the mask of
+ * pygat_dot_attn_dropout_forward and pygat_add_attn_dropout_forward: element c(e) H + h of the flat layout
+ * pygat_dropout_mask(nnz H, p, seed, stream_id, ...) writes, drawn in registers in the forward and again in backward_rows; no mask is
+ * stored.  c(e) is the CALLER's entry index, so the forward takes perm (after col; it may be null: the position itself), which
+ * pygat_v2_attn_forward never reads.  seed is a uint64 in DEVICE memory, read by the kernels.  backward_rows: D = <G, out>, S = p (mask
+ * <G, v> - D), dx_dst from S as above, P := p mask, so dv = pygat_spmm_forward(val = P, b = G).  pygat_v2_attn_backward_cols reads S
+ * alone: it is launched as it is and has no dropout variant.  v == NULL as above.  A row of one entry gets out_i = mask v_j bit for
+ * bit; its S is an exact zero where the entry is dropped and where mask is a power of two (p = 0.5), and otherwise the difference of
+ * two roundings, mask <G, v> against <G, mask v>: a few ulps of dp, not zero.  A row whose entries are all dropped, and every row at
+ * p = 1, get exact zeros in out.  Refusals as for the K21 launchers after the launcher's own name; besides: a null or misaligned (8
+ * bytes) seed, p outside [0, 1] (a NaN included).  Both launchers must be given the same p, seed value and stream_id.  The workspace
+ * is pygat_v2_attn_workspace_bytes'. */
+int pygat_v2_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                  int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds,
+                                  const float* a, const float* v, int64_t ldv, float p, const void* seed, uint32_t stream_id,
+                                  float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream);
+int pygat_v2_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                        int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                        int64_t lds, const float* a, const float* v, int64_t ldv, float p, const void* seed,
+                                        uint32_t stream_id, const float* out, int64_t ldo, const float* m, const float* Z,
+                                        const float* G, int64_t ldg, float* dx_dst, int64_t lddx, float* P, float* S, void* ws,
+                                        void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

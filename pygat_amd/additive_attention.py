@@ -9,6 +9,8 @@
     out = additive_attention(pattern, s_dst, s_src, v)                      # s_dst [n_dst, H], s_src [n_src, H], v [n_src, H, F]
     out = spmm(pattern, edge_softmax(pattern, F.leaky_relu(s_dst[row] + s_src[col], 0.2)), v)      # the same, from parts
     out = additive_attention(pattern, s_dst, s_src, v, 0.2, edge_logit=emb(edge_type))             # gat_level's edge_logit, [E, H] | [E]
+    out = additive_attention_dropout(pattern, s_dst, s_src, v, 0.6, training=self.training)        # training: dropout p on the coefficients,
+                                                                # after the softmax, drawn in the kernels from a seed on the device
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the pattern
 rectangular.  Differentiable in every tensor.  The backward keeps out and (m, Z) per row; its two per-entry tensors P and S ([E, H]
@@ -24,41 +26,43 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import _require_heads, _require_pattern, _require_tensor, _slope
+from .dot_attention import _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
+from .dropout import STREAM_ATT
 from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "additive_attention"
+_OP_DROP = "additive_attention_dropout"
 _PAD_HINT = ("zero-padding the columns of v to the next allowed F leaves the first F columns of the result unchanged (no scale "
              "depends on F)")
 
 
-def _checked(pattern, s_dst, s_src, v, edge_logit):
-    """Every refusal that looks at the pattern and the tensors, those of edge_logit alone first -> (H, F, no head axis, the logit's
-    head stride | None)."""
+def _checked(pattern, s_dst, s_src, v, edge_logit, op: str = _OP):
+    """Every refusal that looks at the pattern and the tensors, those of edge_logit alone first, under the op's name -> (H, F, no
+    head axis, the logit's head stride | None)."""
     if edge_logit is not None:
-        _require_tensor(_OP, pattern, "edge_logit", edge_logit)
-    _require_pattern(_OP, pattern)
+        _require_tensor(op, pattern, "edge_logit", edge_logit)
+    _require_pattern(op, pattern)
     for name, t in (("s_dst", s_dst), ("s_src", s_src), ("v", v)):
-        _require_tensor(_OP, pattern, name, t)
+        _require_tensor(op, pattern, name, t)
     named = (("s_dst", s_dst, pattern.n_rows, "rows"), ("s_src", s_src, pattern.n_cols, "columns"), ("v", v, pattern.n_cols, "columns"))
     if s_dst.dim() not in (1, 2):
-        raise ValueError(f"pygat_amd {_OP}: s_dst [n_rows] or [n_rows, H] expected, got {tuple(s_dst.shape)}")
+        raise ValueError(f"pygat_amd {op}: s_dst [n_rows] or [n_rows, H] expected, got {tuple(s_dst.shape)}")
     if s_src.dim() != s_dst.dim() or s_src.shape[1:] != s_dst.shape[1:]:
-        raise ValueError(f"pygat_amd {_OP}: s_src {tuple(s_src.shape)} does not match s_dst {tuple(s_dst.shape)}: the same number of "
+        raise ValueError(f"pygat_amd {op}: s_src {tuple(s_src.shape)} does not match s_dst {tuple(s_dst.shape)}: the same number of "
                          f"heads expected")
     if v.dim() != s_dst.dim() + 1 or v.shape[1:-1] != s_dst.shape[1:]:
-        raise ValueError(f"pygat_amd {_OP}: v {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: v [n_cols, F] with s_dst "
+        raise ValueError(f"pygat_amd {op}: v {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: v [n_cols, F] with s_dst "
                          f"[n_rows], or v [n_cols, H, F] with s_dst [n_rows, H] and the same number of heads, expected")
     for name, t, rows, side in named:
         if t.shape[0] != rows:
-            raise ValueError(f"pygat_amd {_OP}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
     flat = s_dst.dim() == 1
     H, F = (1 if flat else int(s_dst.shape[1])), int(v.shape[-1])
-    _require_heads(_OP, H, F, _PAD_HINT)
-    return H, F, flat, None if edge_logit is None else _logit_head_stride(pattern, edge_logit, H, flat)
+    _require_heads(op, H, F, _PAD_HINT)
+    return H, F, flat, None if edge_logit is None else _logit_head_stride(pattern, edge_logit, H, flat, op)
 
 
-def _logit_head_stride(pattern, edge_logit, H: int, flat: bool) -> int:
+def _logit_head_stride(pattern, edge_logit, H: int, flat: bool, op: str = _OP) -> int:
     """1: one value per entry and head ([E, H]; [E] where the tensors have no head axis); 0: one per entry, shared by the heads."""
     E = pattern.nnz
     if tuple(edge_logit.shape) == (E,):
@@ -66,59 +70,68 @@ def _logit_head_stride(pattern, edge_logit, H: int, flat: bool) -> int:
     if not flat and tuple(edge_logit.shape) == (E, H):
         return 1
     want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
-    raise ValueError(f"pygat_amd {_OP}: edge_logit {want} expected for E = {E} entries and H = {H} heads, got "
+    raise ValueError(f"pygat_amd {op}: edge_logit {want} expected for E = {E} entries and H = {H} heads, got "
                      f"{tuple(edge_logit.shape)}")
 
 
-def _launch(pattern, which: str, H: int, F: int, slope: float, sd, ss, vc, uc, uhs, rest):
-    """One K20 launcher call, `which` "forward" or "backward_rows": the pattern's arrays, the three tables, the logit (None: the
-    kernels without the term, which need no permutation in the forward), then `rest`, the pass's own arguments up to the workspace."""
+def _launch(pattern, which: str, H: int, F: int, slope: float, sd, ss, vc, uc, uhs, drop, rest):
+    """One K20 launcher call, `which` "forward" or "backward_rows", at the entry point of what is present -- a dropout (p, seed) or
+    none: the pattern's arrays, the three tables, the logit (None: the kernels without the term, which without dropout need no
+    permutation in the forward), the dropout group, then `rest`, the pass's own arguments up to the workspace."""
+    kind = "" if drop is None else "dropout_"
+    group = () if drop is None else (drop[0], _ptr(drop[1]), STREAM_ATT)
     ws = torch.empty(_lib.add_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=vc.device)
-    check(getattr(lib, f"pygat_add_attn_{which}")(pattern.n_rows, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col),
-                                                   _ptr(pattern.perm), H, F, slope, _ptr(sd), _ptr(ss), _ptr(vc), H * F, _ptr(uc),
-                                                   uhs or 0, *rest, _ptr(ws), _stream()), f"add_attn_{which}")
+    check(getattr(lib, f"pygat_add_attn_{kind}{which}")(pattern.n_rows, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col),
+                                                         _ptr(pattern.perm), H, F, slope, _ptr(sd), _ptr(ss), _ptr(vc), H * F,
+                                                         _ptr(uc), uhs or 0, *group, *rest, _ptr(ws), _stream()),
+          f"add_attn_{kind}{which}")
 
 
 class _AdditiveAttentionFn(torch.autograd.Function):
+    """additive_attention and additive_attention_dropout.  drop: None or (p, seed) of additive_attention_dropout: the mask of the
+    coefficients, drawn in the kernels of both passes from the int64 [1] seed tensor on the device."""
+
     @staticmethod
-    def forward(ctx, pattern, s_dst, s_src, v, slope, edge_logit):
-        H, F, flat, uhs = _checked(pattern, s_dst, s_src, v, edge_logit)
-        ctx.pattern, ctx.slope, ctx.hf, ctx.uhs = pattern, slope, (H, F), uhs
+    def forward(ctx, pattern, s_dst, s_src, v, slope, edge_logit, drop=None):
+        op = _OP if drop is None else _OP_DROP
+        H, F, flat, uhs = _checked(pattern, s_dst, s_src, v, edge_logit, op)
+        p, seed = (None, None) if drop is None else drop
+        ctx.pattern, ctx.slope, ctx.hf, ctx.uhs, ctx.op, ctx.p = pattern, slope, (H, F), uhs, op, p
         if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
-            ctx.save_for_backward(s_dst, s_src, v, edge_logit, None, None, None)
+            ctx.save_for_backward(s_dst, s_src, v, edge_logit, None, None, None, None)
             return torch.zeros((pattern.n_rows,) + tuple(v.shape[1:]), dtype=torch.float32, device=v.device)
         sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
         n, dev = pattern.n_rows, vc.device
         with torch.cuda.device(dev):
             out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
             m, Z = (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
-            _launch(pattern, "forward", H, F, slope, sd, ss, vc, uc, uhs, (_ptr(out), H * F, _ptr(m), _ptr(Z)))
+            _launch(pattern, "forward", H, F, slope, sd, ss, vc, uc, uhs, drop, (_ptr(out), H * F, _ptr(m), _ptr(Z)))
         out = out.view((n,) + tuple(v.shape[1:]))
-        ctx.save_for_backward(s_dst, s_src, v, edge_logit, out, m, Z)
+        ctx.save_for_backward(s_dst, s_src, v, edge_logit, out, m, Z, seed)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        s_dst, s_src, v, edge_logit, out, m, Z = ctx.saved_tensors
+        s_dst, s_src, v, edge_logit, out, m, Z, seed = ctx.saved_tensors
         pattern, slope, (H, F), uhs = ctx.pattern, ctx.slope, ctx.hf, ctx.uhs
         if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {_OP}: the gradient of the output must be float32, not {G.dtype}")
+            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_d, need_s, need_v = ctx.needs_input_grad[1:4]
         need_u = edge_logit is not None and ctx.needs_input_grad[5]
         if not (need_d or need_s or need_v or need_u):
-            return (None,) * 6
+            return (None,) * 7
         if out is None:                                            # no entries: zeros, nothing launched
             zd, zs, zv, zu = (torch.zeros_like(t) if need else None for t, need in
                               ((s_dst, need_d), (s_src, need_s), (v, need_v), (edge_logit, need_u)))
-            return None, zd, zs, zv, None, zu
+            return None, zd, zs, zv, None, zu, None
         n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, v.device
         sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
         Gc = G.contiguous().view(n, HF)
         with torch.cuda.device(dev):
             dd = torch.empty(n, H, dtype=torch.float32, device=dev)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
-            _launch(pattern, "backward_rows", H, F, slope, sd, ss, vc, uc, uhs,
+            _launch(pattern, "backward_rows", H, F, slope, sd, ss, vc, uc, uhs, None if seed is None else (ctx.p, seed),
                     (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), _ptr(P), _ptr(S)))
             du = None
             if need_u:                          # S is the gradient of an [E, H] logit; an [E] one shared by H heads gets the sum over them
@@ -131,7 +144,7 @@ class _AdditiveAttentionFn(torch.autograd.Function):
                     ds = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, 1, S, ones).view(s_src.shape)
                 if need_v:
                     dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
-        return None, dd.view(s_dst.shape) if need_d else None, ds, dv, None, du
+        return None, dd.view(s_dst.shape) if need_d else None, ds, dv, None, du, None
 
 
 def additive_attention(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.Tensor, v: torch.Tensor, negative_slope: float = 0.2,
@@ -150,6 +163,36 @@ def additive_attention(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.T
     Differentiable in s_dst, s_src, v and edge_logit (the gradient of an [E] logit is the sum over the heads); a gradient that is not
     asked for costs no launch.  float32 GPU tensors on the pattern's device; 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024;
     for another F zero-pad the columns of v: the first F columns of the result are unchanged.
-    Not provided: dropout on the coefficients, bfloat16 tables, a fused column pass (dv and ds_src are two K17 launches on the
-    transposed pattern)."""
+    Not provided: dropout on the coefficients (that is the sibling op's, additive_attention_dropout), bfloat16 tables, a
+    fused column pass (dv and ds_src are two K17 launches on the transposed pattern)."""
     return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, _slope(_OP, negative_slope), edge_logit)
+
+
+def additive_attention_dropout(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.Tensor, v: torch.Tensor, p: float,
+                               negative_slope: float = 0.2, edge_logit: Optional[torch.Tensor] = None, *,
+                               seed: Optional[torch.Tensor] = None, generator=None, training: bool = True) -> torch.Tensor:
+    """additive_attention with dropout p on the attention coefficients, as a GAT trains (the reference's dropout after the
+    normalisation, PyG's GATConv): out[i] = sum over the entries e = (i, j) of row i of
+    softmax_row(LeakyReLU(s_dst[i] + s_src[j] + edge_logit[e]))[e] * mask[e] * v[j], per head, mask in {0, 1 / (1 - p)}.  The softmax
+    runs over all entries of the row -- a dropped entry keeps its share of the denominator -- so this is dropout after the softmax, not
+    masking before it.  Fused on the DROP instantiations of the K20 kernels: the decision for (entry, head) is drawn in registers
+    (Philox-4x32-10) in the forward and again in the backward, and no [E, H] mask exists outside backward.
+    seed: an int64 [1] tensor on the pattern's device, read by the kernels (refill it in place between replays of a captured graph);
+    None draws one with torch.randint(0, 2**62, ..., generator=generator).  The mask is attention_dropout_mask(pattern, H, p, seed), at
+    the caller's entry index -- the mask dot_attention_dropout and gatv2_attention_dropout draw from the same seed; the same seed gives
+    the same bits.  training=False or p == 0 is additive_attention itself; p == 1 gives zeros; a row whose entries are all dropped
+    gets exact zeros.  Differentiable in s_dst, s_src, v and edge_logit; a gradient that is not asked for costs no launch.  float32 GPU
+    tensors with additive_attention's limits; bfloat16 tensors are refused."""
+    op = _OP_DROP
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (s_dst, s_src, v, edge_logit)):
+        raise ValueError(f"pygat_amd {op}: s_dst, s_src, v and edge_logit must be float32: there is no training path on bfloat16 "
+                         f"tensors")
+    p, slope = _drop_p(op, p), _slope(op, negative_slope)
+    if seed is not None:
+        seed = _drop_seed(op, pattern, seed)
+    _checked(pattern, s_dst, s_src, v, edge_logit, op)             # (refusals under this op's name, before anything touches the device)
+    if not training or p == 0.0:
+        return additive_attention(pattern, s_dst, s_src, v, slope, edge_logit)
+    if seed is None:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
+    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, slope, edge_logit, (p, seed))

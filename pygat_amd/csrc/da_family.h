@@ -1,13 +1,14 @@
 // The kernel skeleton and the launcher tail of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip), K20
 // (k20_additive_attention.hip) and K21 (k21_gatv2_attention.hip), on the lane mapping of da_lanes.h.  A pass is two kernels, a piece
 // kernel for the long rows (one wave per chunk, the rule of long_rows.h) and a row kernel; their bodies are here once, templated on
-// the family, a type (DaFam<variant>, AaFam<LOGIT>, V2Fam<SHARED>) that says what a lane group holds of its row and how it walks it:
+// the family, a type (DaFam<variant>, AaFam<LOGIT, DROP>, V2Fam<SHARED, DROP>) that says what a lane group holds of its row and how it
+// walks it:
 //   forward   Fam::Own<VEC>; Fam::load<VEC>(g, ln, row, own); Fam::KEEP_MZ
 //   backward  Fam::Row<VEC>, a DaGrad<VEC> and the row's own operand; Fam::bwd_load<LPR, VEC>(g, ln, row, r);
 //             Fam::lone(start, end) (the row is one entry and the family cares: K19 under EDGE)
 //   both      Fam::walk<LPR, VEC, PASS>(g, ln, e0, e1, step, lone, key, own | r, st | dx): the entries e0, e0 + step, ... < e1 folded
 //             in that order, PASS 0 forward, 1 backward;  Fam::key(g): what a kernel reads once for all its rows (K19: the key of
-//             the draws under DROP, zeros without; K20 and K21: a DaNoKey)
+//             the draws under DROP, zeros without; K20 and K21: the same key under DROP (da_key, da_lanes.h), a DaNoKey without)
 // The backward pair is that of the families whose row gradient is a row of H*F floats (K19's dq, K21's dx_dst); K20's, one scalar
 // per head and a record of H floats, is its own and shares da_grad_load alone: a trait for the accumulator would have been as long
 // as the two kernels it saves.
@@ -15,7 +16,8 @@
 // families 456 are instruction for instruction what they were when each family had its own copy, 6 the same instructions in another
 // order (profiles/da_family_isa.txt); helpers did not keep that.  What a kernel calls is the family's walk itself where that could be
 // had (K19, K21): with one forwarding function between the kernel and the walk, the backward kernels of both came out reordered.
-// Host side: the shape check, the parser of the kernel names pygat_kernel_footprint takes, the grids and the launch of a pair.
+// Host side: the shape check, the check of a DROP launcher's p and seed, the parser of the kernel names pygat_kernel_footprint takes,
+// the grids and the launch of a pair.
 #pragma once
 #include "da_lanes.h"
 #include <string.h>
@@ -199,6 +201,20 @@ static int da_check_shape(const char* what, int64_t nnz, int H, int F, const cha
   PYGAT_REQUIRE(F >= 4 && F <= 256 && (F & (F - 1)) == 0, "%s: F=%d, a head's width must be a power of two in 4..256 (%s)", what, F,
                 pad_hint);
   PYGAT_REQUIRE((int64_t)H * F <= DA_MAX_ROW, "%s: row too wide: H x F = %d x %d > %d floats", what, H, F, DA_MAX_ROW);
+  return PYGAT_OK;
+}
+
+// the mask of the DROP launchers of all three families: the seed, a uint64 in device memory (8-byte loads), and p in [0, 1] (a NaN is
+// outside)
+struct DaDrop {
+  float p;
+  const void* seed;
+  uint32_t stream_id;
+};
+static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
+  PYGAT_REQUIRE(d.seed, "%s: null seed", what);
+  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(d.seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
+  PYGAT_REQUIRE(make_rng(d.p, d.seed, d.stream_id, rng), "%s: p=%g outside [0, 1]", what, (double)d.p);
   return PYGAT_OK;
 }
 

@@ -1,7 +1,8 @@
 // The lanes of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip, the dot-product score), K20
 // (k20_additive_attention.hip, the GAT score) and K21 (k21_gatv2_attention.hip, the GATv2 score).  The kernel arguments, the lane
 // mapping of a row of H*F floats, the online softmax fold of one head and the merge of two partial records, the caller's entry index
-// of a CSR position, the per-entry scalar term, the lane-shape dispatch and the table checks of the launchers.  Moved here from
+// of a CSR position, the per-entry scalar term, the draws of the DROP instantiations (the seeded dropout of the coefficients, one copy
+// for the three families), the lane-shape dispatch and the table checks of the launchers.  Moved here from
 // k19_dot_attention.hip as it stood; K19's device code is the same before and after (profiles/k20_k19_unchanged.txt).  The kernels
 // built on these, one copy for the three families, and the launcher tail: da_family.h.  A family's walk and folds are its own.
 #pragma once
@@ -151,6 +152,52 @@ __device__ __forceinline__ void da_fold(float& m, float& z, float4& acc, float s
   z = fmaf(z, r, p);
   acc.x = fmaf(acc.x, r, pk * w.x); acc.y = fmaf(acc.y, r, pk * w.y); acc.z = fmaf(acc.z, r, pk * w.z); acc.w = fmaf(acc.w, r, pk * w.w);
   m = up ? (BIAS ? __fadd_rn(s, b) : s) : m;
+}
+
+// DROP (all three families): the key of the row's draws, read once per kernel, and the keep factor (0 or 1 / (1 - p)) of flat mask
+// element idx = c(e) H + h
+template <bool DROP>
+__device__ __forceinline__ uint2 da_key(const DaArgs& g) {
+  if constexpr (!DROP) return make_uint2(0u, 0u);
+  else {
+    const uint64_t seed = *g.rng.seed;
+    return make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  }
+}
+__device__ __forceinline__ float da_keep(const DaArgs& g, uint2 key, int64_t idx) {
+  const uint64_t q4 = (uint64_t)idx >> 2;
+  const uint4 w = philox4x32_10(make_uint4((uint32_t)q4, (uint32_t)(q4 >> 32), g.rng.stream_id, 0xFFFFFFFFu), key);
+  return word_of(w, (int)(idx & 3)) < g.rng.thresh ? g.rng.scale : 0.f;
+}
+// ... of a batch of U entries, base[u] = c(e_u) H.  The LH lanes of a head would all draw the same word for an entry, so they share the
+// batch instead: in a round, lane i of the head draws for entry t0 + i, and the head's lanes read each other's factor, one __shfl per
+// (entry, chunk): ceil(U / LH) Philox calls per lane and chunk, not U (a lane's place in its head is the same for all its chunks: 64 is
+// a multiple of LH; the lanes of a real head are all inside the row).  The rounds are a loop on purpose: unrolled, it is U copies of
+// the ten rounds
+template <int VEC, int U>
+__device__ __forceinline__ void da_keep_batch(const DaArgs& g, const DaLane<VEC>& ln, uint2 key, const int64_t (&base)[U],
+                                              float (&keep)[U][VEC]) {
+  if constexpr (U == 1) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) keep[0][v] = da_keep(g, key, base[0] + ln.head[v]);
+  } else {
+    const int li = (threadIdx.x & 63) & (g.LH - 1);
+#pragma unroll 1
+    for (int t0 = 0; t0 < U; t0 += g.LH) {
+      int64_t b = base[U - 1];                                   // (a lane past the batch draws for its last entry; nobody reads it)
+#pragma unroll
+      for (int u = 0; u < U - 1; ++u) b = t0 + li == u ? base[u] : b;
+      float mine[VEC];
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) mine[v] = da_keep(g, key, b + ln.head[v]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (u >= t0 && u < t0 + g.LH) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) keep[u][v] = __shfl(mine[v], u - t0, g.LH);
+        }
+    }
+  }
 }
 
 // (m, z, acc) <- (m, z, acc) (+) (m2, z2, acc2), the earlier entries on the left

@@ -83,50 +83,7 @@ __device__ __forceinline__ float da_score(const DaArgs& g, const float4& q, cons
   return __fmul_rn(g.scale, da_head_sum<LPR>(dot4(q, k), g.LH));
 }
 
-// DROP: the key of the row's draws, read once per kernel, and the keep factor (0 or 1 / (1 - p)) of flat mask element idx = c(e) H + h
-template <bool DROP>
-__device__ __forceinline__ uint2 da_key(const DaArgs& g) {
-  if constexpr (!DROP) return make_uint2(0u, 0u);
-  else {
-    const uint64_t seed = *g.rng.seed;
-    return make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
-  }
-}
-__device__ __forceinline__ float da_keep(const DaArgs& g, uint2 key, int64_t idx) {
-  const uint64_t q4 = (uint64_t)idx >> 2;
-  const uint4 w = philox4x32_10(make_uint4((uint32_t)q4, (uint32_t)(q4 >> 32), g.rng.stream_id, 0xFFFFFFFFu), key);
-  return word_of(w, (int)(idx & 3)) < g.rng.thresh ? g.rng.scale : 0.f;
-}
-// ... of a batch of U entries, base[u] = c(e_u) H.  The LH lanes of a head would all draw the same word for an entry, so they share the
-// batch instead: in a round, lane i of the head draws for entry t0 + i, and the head's lanes read each other's factor, one __shfl per
-// (entry, chunk): ceil(U / LH) Philox calls per lane and chunk, not U (a lane's place in its head is the same for all its chunks: 64 is
-// a multiple of LH; the lanes of a real head are all inside the row).  The rounds are a loop on purpose: unrolled, it is U copies of
-// the ten rounds
-template <int VEC, int U>
-__device__ __forceinline__ void da_keep_batch(const DaArgs& g, const DaLane<VEC>& ln, uint2 key, const int64_t (&base)[U],
-                                              float (&keep)[U][VEC]) {
-  if constexpr (U == 1) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) keep[0][v] = da_keep(g, key, base[0] + ln.head[v]);
-  } else {
-    const int li = (threadIdx.x & 63) & (g.LH - 1);
-#pragma unroll 1
-    for (int t0 = 0; t0 < U; t0 += g.LH) {
-      int64_t b = base[U - 1];                                   // (a lane past the batch draws for its last entry; nobody reads it)
-#pragma unroll
-      for (int u = 0; u < U - 1; ++u) b = t0 + li == u ? base[u] : b;
-      float mine[VEC];
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) mine[v] = da_keep(g, key, b + ln.head[v]);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (u >= t0 && u < t0 + g.LH) {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) keep[u][v] = __shfl(mine[v], u - t0, g.LH);
-        }
-    }
-  }
-}
+// (DROP: the key of the row's draws, da_key, and the keep factors of a batch, da_keep_batch: da_lanes.h, shared with K20 and K21)
 
 // ----------------------------------------------------------------------------------------------------------- the fold and the walk
 // (the fold of one head, da_fold, and the merge of two records, da_merge: da_lanes.h)
@@ -458,18 +415,7 @@ static int da_check_bias(const char* what, int64_t nnz, const float* bias, int b
   return PYGAT_OK;
 }
 
-// the mask of the DROP launchers: the seed, a uint64 in device memory (8-byte loads), and p in [0, 1] (a NaN is outside)
-struct DaDrop {
-  float p;
-  const void* seed;
-  uint32_t stream_id;
-};
-static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
-  PYGAT_REQUIRE(d.seed, "%s: null seed", what);
-  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(d.seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
-  PYGAT_REQUIRE(make_rng(d.p, d.seed, d.stream_id, rng), "%s: p=%g outside [0, 1]", what, (double)d.p);
-  return PYGAT_OK;
-}
+// (the mask of the DROP launchers, DaDrop and da_check_drop: da_family.h, shared with K20 and K21)
 
 // the per-entry rows of the EDGE launchers: e, and de where it is asked for, are row tables like k and v, [nnz x H*F] at the caller's
 // entry index; e is non-null where there are entries

@@ -1,8 +1,9 @@
 // K20 -- additive_attention: the GAT score over the entries of every row of a sparse pattern whose row side and column side are
 // different tables, for H heads at once, in one pass, and the row side of its gradient.  One kernel family in K19's shape: four
-// kernels (forward | backward rows) x (long | row), instantiated per lane shape and per LOGIT, the compile-time flag of the per-entry
-// term.  The forward pair is da_family.h's, shared with K19 and K21, on AaFam below; the backward pair, whose row gradient is one
-// scalar per head and not a row of H*F floats, is written here.
+// kernels (forward | backward rows) x (long | row), instantiated per lane shape, per LOGIT, the compile-time flag of the per-entry
+// term, and per DROP, that of the seeded dropout of the coefficients (additive_attention_dropout).  The forward pair is da_family.h's,
+// shared with K19 and K21, on AaFam below; the backward pair, whose row gradient is one scalar per head and not a row of H*F floats, is
+// written here.
 //
 // Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h:
 //   z = s_dst[i, h] + s_src[j, h]                      one rounded add;  LOGIT: z = (s_dst[i, h] + s_src[j, h]) + u[c, h], two rounded
@@ -17,6 +18,11 @@
 //     S[c, h] = dz for the column side: dv = spmm^T(P, G) and ds_src = spmm^T(S, ones[n_rows x H x 1]) are two pygat_spmm_forward
 //     launches on the transposed pattern (K17).  S is the gradient of u as it is.
 //   The forward keeps out, m and Z, all the backward reads -- nothing per entry.
+//   DROP: out[i, h] = sum_e p mask[c, h] v[j, h], mask in {0, 1 / (1 - p_drop)}: a dropped entry stays in Z, and m and Z are the
+//     undropped softmax's.  mask[c, h] is K19's: element c H + h of the flat layout of k7_dropout.hip's mask kernel on the launcher's
+//     stream id, drawn in registers in both passes (da_keep_batch, da_lanes.h) -- no mask tensor exists.  backward_rows: dp = mask <G, v>,
+//     T = p (dp - D), dz and ds_dst as above, P[c, h] = p mask, S[c, h] = dz.  The walk then carries c in both passes, on LOGIT's path,
+//     and the forward reads perm; without LOGIT it loads no logit.
 //
 // Lane mapping: K19's (da_lanes.h).  Rows of v, out and G are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.
 // A group of LPR lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v; the chunks of a head sit
@@ -33,17 +39,21 @@
 //
 // Exactness.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.
 //   a row without entries   out = m = Z = ds_dst = 0 exactly
-//   a row of one entry      out_i = v_j bit for bit and dz = 0 exactly: D and dp are formed by the same routine on the same bits
-//   u = 0                   changes no bit of out, ds_dst, P or S against the kernels without LOGIT (x + 0 is x)
+//   a row of one entry      out_i = v_j bit for bit and dz = 0 exactly: D and dp are formed by the same routine on the same bits;
+//                           DROP: out_i = mask v_j bit for bit; dz = 0 exactly where the entry is dropped or mask is a power of two,
+//                           otherwise mask <G, v> against <G, mask v>, two roundings apart
+//   all entries dropped     (and every row under p_drop = 1) exact zeros in out
+//   u = 0                   changes no bit of out, ds_dst, P or S against the kernels without LOGIT (x + 0 is x), with and without DROP
 //   a large negative finite u (-9e15) gives p = 0 exactly while the row keeps another entry and slope > 0 (at slope 0 l is 0: no mask)
 #include "da_family.h"
 #include <math.h>
+#include <type_traits>
 
 namespace pygat {
 
 // The kernels take K19's argument block (DaArgs, da_lanes.h), so that its lane mapping and entry-index helpers serve as they stand:
 //   q = s_dst [n x H] (ldq = H),  k = s_src [n_cols x H] (ldk = H),  scale = the negative slope,  bias / bstride / bhs = the logit u,
-//   dq = ds_dst [n x H].  dbias, rng, e and de are not looked at.
+//   dq = ds_dst [n x H],  rng = the mask of the DROP kernels.  dbias, e and de are not looked at.
 __device__ __forceinline__ float aa_leaky(float z, float slope) { return z > 0.f ? z : __fmul_rn(slope, z); }
 
 // U gathered entries: the s_src scalars (one per chunk slot) and the v rows of columns src[0..U), loaded before any is used
@@ -74,10 +84,14 @@ __device__ __forceinline__ float aa_z(float sd, float t, float u) {
 // iteration waits for one gather, not for an index and then a gather.  LOGIT: the next batch's entry indices travel with its column
 // indices as loaded words (da_eid_raw) and become indices only after this batch's fold, when the next batch's logits are asked for,
 // ahead of the next gather.  Without LOGIT the forward carries no entry index; the backward needs it only for its stores and forms it
-// whole (da_entry) a batch ahead.
-template <int VEC, bool LOGIT, bool BWD, typename Fold, typename... Ctx>
-__device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, Ctx&... ctx) {
+// whole (da_entry) a batch ahead.  DROP: the entry index places the draws, so it travels on LOGIT's path in BOTH passes (EID), the
+// forward's included, whether or not there is a logit to load; ent = eid x H is then formed in the forward too.  key: the key of the
+// draws under DROP (by value, K19's way), a DaNoKey without.
+template <int VEC, bool LOGIT, bool DROP, bool BWD, typename Fold, typename Key, typename... Ctx>
+__device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, Key key,
+                                        Ctx&... ctx) {
   constexpr int U = da_unroll(BWD, VEC);
+  constexpr bool EID = LOGIT || DROP;
   int64_t e = e0;
   if constexpr (U > 1) {
     int32_t src[U];
@@ -89,18 +103,16 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         src[u] = g.col[e + u * step];
-        if constexpr (LOGIT) raw[u] = da_eid_raw(g, e + u * step);
+        if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
         else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
       }
-      if constexpr (LOGIT) {
-        da_eids<U>(g, raw, e, step, eid);
-        da_bias_load<VEC, U>(g, ln, eid, bs);
-      }
+      if constexpr (EID) da_eids<U>(g, raw, e, step, eid);
+      if constexpr (LOGIT) da_bias_load<VEC, U>(g, ln, eid, bs);
     }
     while (full) {
       AaRows<VEC, U> w;
       aa_gather<VEC, U>(g, ln, src, w);
-      if constexpr (BWD && !LOGIT) {
+      if constexpr (BWD && !EID) {
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
       }
@@ -110,19 +122,19 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
-          if constexpr (LOGIT) raw[u] = da_eid_raw(g, e + u * step);
+          if constexpr (EID) raw[u] = da_eid_raw(g, e + u * step);
           else if constexpr (BWD) ent_next[u] = da_entry(g, e + u * step);
         }
       }
-      if constexpr (BWD && LOGIT) {                                // (eid: this batch's, formed after the last fold, not yet replaced)
+      if constexpr ((BWD || DROP) && EID) {                        // (eid: this batch's, formed after the last fold, not yet replaced)
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = (int64_t)eid[u] * g.H;
       }
-      Fold::fold(g, ln, ctx..., w, ent, bs);
-      if constexpr (LOGIT)
+      Fold::fold(g, ln, key, ctx..., w, ent, bs);
+      if constexpr (EID)
         if (full) {
           da_eids<U>(g, raw, e, step, eid);
-          da_bias_load<VEC, U>(g, ln, eid, bs);
+          if constexpr (LOGIT) da_bias_load<VEC, U>(g, ln, eid, bs);
         }
     }
   }
@@ -130,7 +142,7 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
     const int32_t src[1] = {g.col[e]};
     [[maybe_unused]] int64_t ent[1] = {0};
     [[maybe_unused]] int32_t eid[1] = {0};
-    if constexpr (BWD) ent[0] = da_entry(g, e);
+    if constexpr (BWD || DROP) ent[0] = da_entry(g, e);
     DaBias<VEC, 1, LOGIT> bs;
     if constexpr (LOGIT) {
       eid[0] = da_eid(g, da_eid_raw(g, e), e);
@@ -138,7 +150,7 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
     }
     AaRows<VEC, 1> w;
     aa_gather<VEC, 1>(g, ln, src, w);
-    Fold::fold(g, ln, ctx..., w, ent, bs);
+    Fold::fold(g, ln, key, ctx..., w, ent, bs);
   }
 }
 
@@ -150,37 +162,48 @@ __device__ __forceinline__ void aa_load_sd(const DaArgs& g, const DaLane<VEC>& l
   for (int v = 0; v < VEC; ++v) sd[v] = g.q[row * g.ldq + ln.head[v]];
 }
 
-// the forward's fold of a batch; ctx: s_dst of the row and the row's state.  ent is not looked at
-template <int VEC, bool LOGIT>
+// the key of a kernel's draws: K19's under DROP, nothing without
+template <bool DROP> using AaKey = std::conditional_t<DROP, uint2, DaNoKey>;
+
+// the forward's fold of a batch; ctx: s_dst of the row and the row's state.  ent is looked at under DROP alone: ent[u] + head is the
+// entry's flat mask index, and (p keep) v goes into acc while Z takes p whole (da_fold)
+template <int VEC, bool LOGIT, bool DROP>
 struct AaFwdFold {
   template <int U>
-  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, const float (&sd)[VEC], DaState<VEC>& st,
-                                              const AaRows<VEC, U>& w, const int64_t (&)[U], const DaBias<VEC, U, LOGIT>& bs) {
+  __device__ __forceinline__ static void fold(const DaArgs& g, [[maybe_unused]] const DaLane<VEC>& ln, [[maybe_unused]] AaKey<DROP> key,
+                                              const float (&sd)[VEC], DaState<VEC>& st, const AaRows<VEC, U>& w,
+                                              [[maybe_unused]] const int64_t (&ent)[U], const DaBias<VEC, U, LOGIT>& bs) {
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const float z = aa_z<LOGIT>(sd[v], w.t[u][v], LOGIT ? bs.b[u][v] : 0.f);
-        da_fold<false, false>(st.m[v], st.z[v], st.acc[v], aa_leaky(z, g.scale), 0.f, 1.f, w.v[u][v]);
+        da_fold<false, DROP>(st.m[v], st.z[v], st.acc[v], aa_leaky(z, g.scale), 0.f, DROP ? keep[u][v] : 1.f, w.v[u][v]);
       }
   }
 };
 
-// the family: what the forward kernels of da_family.h hold of a row and how they walk it, per LOGIT.  walk forwards to aa_walk, which
-// the backward kernels below call themselves: as the family's member, K21's way, it moved the LOGIT forward at 64 lanes a row
-template <bool LOGIT>
+// the family: what the forward kernels of da_family.h hold of a row and how they walk it, per LOGIT and DROP.  walk forwards to
+// aa_walk, which the backward kernels below call themselves: as the family's member, K21's way, it moved the LOGIT forward at 64
+// lanes a row
+template <bool LOGIT, bool DROP>
 struct AaFam {
   static constexpr bool KEEP_MZ = true;
   template <int VEC> using Own = float[VEC];                   // s_dst of the row, per chunk slot
-  __device__ __forceinline__ static DaNoKey key(const DaArgs&) { return {}; }
+  __device__ __forceinline__ static AaKey<DROP> key([[maybe_unused]] const DaArgs& g) {
+    if constexpr (DROP) return da_key<true>(g);
+    else return {};
+  }
   template <int VEC>
   __device__ __forceinline__ static void load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, float (&sd)[VEC]) {
     aa_load_sd<VEC>(g, ln, row, sd);
   }
   template <int LPR, int VEC, int PASS>
-  __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool, DaNoKey,
-                                              const float (&sd)[VEC], DaState<VEC>& st) {
-    aa_walk<VEC, LOGIT, false, AaFwdFold<VEC, LOGIT>>(g, ln, e0, e1, step, sd, st);
+  __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
+                                              AaKey<DROP> key, const float (&sd)[VEC], DaState<VEC>& st) {
+    aa_walk<VEC, LOGIT, DROP, false, AaFwdFold<VEC, LOGIT, DROP>>(g, ln, e0, e1, step, key, sd, st);
   }
 };
 
@@ -198,22 +221,34 @@ __device__ __forceinline__ void aa_bwd_load(const DaArgs& g, const DaLane<VEC>& 
 
 // the backward's fold of a batch; ctx: the row (AaRow) and the sums of dz of its heads, one per chunk slot (every lane of a head holds
 // the head's).  In a row of one entry out_i is v_j bit for bit, so dp and D are one routine on the same bits and dz is an exact zero
-template <int LPR, int VEC, bool LOGIT>
+// DROP: the batch's keep factors are drawn again, as K19's backward does (ent[u] + head is an entry's flat mask index); an entry's
+// multiplies <G_i, v_j> -- D_i = <G_i, out_i> is the row term of the dropped sum already -- and the stored P is p keep, what the
+// transposed SpMM of dv multiplies G with.  In a row of one entry out_i is keep v_j bit for bit; dz is an exact zero where the entry is
+// dropped and where keep is a power of two (p = 0.5: 2), and otherwise a rounding of keep dp against one of D
+template <int LPR, int VEC, bool LOGIT, bool DROP>
 struct AaBwdFold {
   template <int U>
-  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, const AaRow<VEC>& r, float (&ds)[VEC],
-                                              const AaRows<VEC, U>& w, const int64_t (&ent)[U], const DaBias<VEC, U, LOGIT>& bs) {
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, [[maybe_unused]] AaKey<DROP> key,
+                                              const AaRow<VEC>& r, float (&ds)[VEC], const AaRows<VEC, U>& w, const int64_t (&ent)[U],
+                                              const DaBias<VEC, U, LOGIT>& bs) {
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const float z = aa_z<LOGIT>(r.sd[v], w.t[u][v], LOGIT ? bs.b[u][v] : 0.f);
         const float p = __expf(aa_leaky(z, g.scale) - r.m[v]) * r.rz[v];
-        const float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+        float dp = da_head_sum<LPR>(dot4(r.G[v], w.v[u][v]), g.LH);
+        float pk = p;
+        if constexpr (DROP) {
+          dp *= keep[u][v];
+          pk *= keep[u][v];
+        }
         const float dz = p * (dp - r.D[v]) * (z > 0.f ? 1.f : g.scale);
         ds[v] += dz;
         if (ln.lead >> v & 1) {
-          g.P[ent[u] + ln.head[v]] = p;
+          g.P[ent[u] + ln.head[v]] = pk;
           g.S[ent[u] + ln.head[v]] = dz;
         }
       }
@@ -221,9 +256,10 @@ struct AaBwdFold {
 };
 
 // launch 1: one wave per chunk; the piece of every long row inside the chunk -> one partial record, the H sums of dz
-template <int LPR, int VEC, bool LOGIT>
+template <int LPR, int VEC, bool LOGIT, bool DROP>
 __global__ __launch_bounds__(64) void aa_bwd_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
+  const auto key = AaFam<LOGIT, DROP>::key(g);
   const int lane = threadIdx.x & 63, grp = lane / LPR;
   const LongChunk ch = long_chunk_span(blockIdx.x, g.nnz);
   const DaLane<VEC> ln = da_lane<LPR, VEC>(g);
@@ -234,7 +270,7 @@ __global__ __launch_bounds__(64) void aa_bwd_long_kernel(DaArgs g) {
     float ds[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) ds[v] = 0.f;
-    aa_walk<VEC, LOGIT, true, AaBwdFold<LPR, VEC, LOGIT>>(g, ln, e0 + grp, e1, EPW, r, ds);
+    aa_walk<VEC, LOGIT, DROP, true, AaBwdFold<LPR, VEC, LOGIT, DROP>>(g, ln, e0 + grp, e1, EPW, key, r, ds);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1)                   // lane groups of the wave, a fixed butterfly
 #pragma unroll
@@ -249,7 +285,7 @@ __global__ __launch_bounds__(64) void aa_bwd_long_kernel(DaArgs g) {
 }
 
 // launch 2: one lane group per row
-template <int LPR, int VEC, bool LOGIT>
+template <int LPR, int VEC, bool LOGIT, bool DROP>
 __global__ __launch_bounds__(256) void aa_bwd_row_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
@@ -269,38 +305,43 @@ __global__ __launch_bounds__(256) void aa_bwd_row_kernel(DaArgs g) {
   } else if (end > start) {                                    // (a row without entries: its G row is not read)
     AaRow<VEC> r;
     aa_bwd_load<LPR, VEC>(g, ln, row, r);
-    aa_walk<VEC, LOGIT, true, AaBwdFold<LPR, VEC, LOGIT>>(g, ln, start, end, 1, r, ds);
+    aa_walk<VEC, LOGIT, DROP, true, AaBwdFold<LPR, VEC, LOGIT, DROP>>(g, ln, start, end, 1, AaFam<LOGIT, DROP>::key(g), r, ds);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v)
     if (ln.lead >> v & 1) g.dq[row * g.lddq + ln.head[v]] = ds[v];
 }
 
-// the table of the family: (LOGIT, forward | backward, long | row, lane shape) -> the kernel.  What a launcher starts and what
+// the table of the family: (LOGIT, DROP, forward | backward, long | row, lane shape) -> the kernel.  What a launcher starts and what
 // pygat_kernel_footprint reports on both come from here
-template <int LPR, int VEC, bool LOGIT>
+template <int LPR, int VEC, bool LOGIT, bool DROP>
 static const void* aa_kernel_at(bool bwd, bool lng) {
-  if (bwd) return lng ? reinterpret_cast<const void*>(&aa_bwd_long_kernel<LPR, VEC, LOGIT>)
-                      : reinterpret_cast<const void*>(&aa_bwd_row_kernel<LPR, VEC, LOGIT>);
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<AaFam<LOGIT>, LPR, VEC>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<AaFam<LOGIT>, LPR, VEC>);
+  if (bwd) return lng ? reinterpret_cast<const void*>(&aa_bwd_long_kernel<LPR, VEC, LOGIT, DROP>)
+                      : reinterpret_cast<const void*>(&aa_bwd_row_kernel<LPR, VEC, LOGIT, DROP>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<AaFam<LOGIT, DROP>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<AaFam<LOGIT, DROP>, LPR, VEC>);
 }
-static const void* aa_kernel(bool logit, bool bwd, bool lng, int lpr, int vec) {
-  if (logit) PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, true>(bwd, lng)));
-  else PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, false>(bwd, lng)));
+template <bool LOGIT, bool DROP>
+static const void* aa_kernel_of(bool bwd, bool lng, int lpr, int vec) {
+  PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, LOGIT, DROP>(bwd, lng)));
   return nullptr;
+}
+static const void* aa_kernel(bool logit, bool drop, bool bwd, bool lng, int lpr, int vec) {
+  if (drop) return logit ? aa_kernel_of<true, true>(bwd, lng, lpr, vec) : aa_kernel_of<false, true>(bwd, lng, lpr, vec);
+  return logit ? aa_kernel_of<true, false>(bwd, lng, lpr, vec) : aa_kernel_of<false, false>(bwd, lng, lpr, vec);
 }
 
 // pygat_kernel_footprint: <prefix>{fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k20_: the kernels without
-// the flag, k20u_: LOGIT
+// a flag, k20u_: LOGIT, k20d_: DROP, k20du_: DROP and LOGIT
 int footprint_k20(const char* name, int* regs, int* scratch) {
-  static const struct { const char* prefix; bool logit; } names[] = {{"k20_", false}, {"k20u_", true}};
+  static const struct { const char* prefix; bool logit, drop; } names[] = {
+      {"k20_", false, false}, {"k20u_", true, false}, {"k20d_", false, true}, {"k20du_", true, true}};
   const void* fn = nullptr;
   DaKernelName k;
   for (const auto& nm : names)
-    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1) fn = aa_kernel(nm.logit, k.pass == 1, k.lng, k.lpr, k.vec);
+    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1) fn = aa_kernel(nm.logit, nm.drop, k.pass == 1, k.lng, k.lpr, k.vec);
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (k20{,u}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
+    set_error("kernel_footprint: unknown kernel '%s' (k20{,u,d,du}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
@@ -324,6 +365,8 @@ struct AaCall {
   int64_t ldv;
   const float* edge_logit;     // null: the kernels without LOGIT
   int logit_head_stride;
+  bool dropout;                // the DROP kernels, on the mask of drop
+  DaDrop drop;
   float* out;
   int64_t ldo;
   float *m, *Z;
@@ -361,18 +404,24 @@ static int aa_launch(const AaCall& c) {
   }
   PYGAT_REQUIRE(!logit || c.logit_head_stride == 0 || c.logit_head_stride == 1, "%s: logit_head_stride=%d, 1 (edge_logit [nnz x H]) or 0 "
                 "(edge_logit [nnz], shared by the heads) expected", what, c.logit_head_stride);
+  DropRng rng;
+  if (c.dropout) {
+    const int rd = da_check_drop(what, c.drop, &rng);
+    if (rd != PYGAT_OK) return rd;
+  }
   if (c.n_rows == 0) return PYGAT_OK;
   DaArgs g;
   memset(&g, 0, sizeof(g));
   g.n = c.n_rows; g.H = c.H; g.F = c.F; g.NCH = HF / 4; g.LH = c.F / 4; g.nnz = c.nnz; g.rowptr = c.rowptr; g.col = c.col;
   g.scale = c.negative_slope; g.q = c.s_dst; g.ldq = c.H; g.k = c.s_src; g.ldk = c.H; g.v = c.v; g.ldv = c.ldv;
   g.out = c.out; g.ldo = c.ldo; g.m = c.m; g.Z = c.Z; g.part = static_cast<float*>(c.ws); g.pstride = da_pstride(c.H, c.F);
-  if (c.bwd || logit) g.perm = c.perm;                            // (the forward without a logit walks in CSR order alone)
+  if (c.bwd || logit || c.dropout) g.perm = c.perm;               // (the forward without a flag walks in CSR order alone)
   if (c.bwd) { g.G = c.G; g.ldg = c.ldg; g.dq = c.ds_dst; g.lddq = c.H; g.P = c.P; g.S = c.S; }
   if (logit) { g.bias = c.edge_logit; g.bhs = c.logit_head_stride; g.bstride = c.logit_head_stride ? c.H : 1; }
+  if (c.dropout) g.rng = rng;
   const DaGrid gd = da_grid(c.n_rows, c.nnz, c.H, c.F);
-  da_launch_pair(aa_kernel(logit, c.bwd, true, gd.lpr, gd.vec), aa_kernel(logit, c.bwd, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks,
-                 c.stream);
+  da_launch_pair(aa_kernel(logit, c.dropout, c.bwd, true, gd.lpr, gd.vec), aa_kernel(logit, c.dropout, c.bwd, false, gd.lpr, gd.vec), g,
+                 gd.chunks, gd.blocks, c.stream);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -411,5 +460,30 @@ extern "C" int pygat_add_attn_backward_rows(int n_rows, int64_t nnz, const int32
                                             float* ds_dst, float* P, float* S, void* ws, void* stream) {
   AA_CALL(c, "add_attn_backward_rows", true);
   c.G = G; c.ldg = ldg; c.ds_dst = ds_dst; c.P = P; c.S = S;
+  return aa_launch(c);
+}
+
+// the same two with seeded dropout of the coefficients (the DROP instantiations): out = sum_e alpha mask v, mask[c(e), h] element
+// c(e) H + h of the flat layout pygat_dropout_mask(nnz H, p, seed, stream_id) writes, drawn in registers in both passes -- the mask of
+// pygat_dot_attn_dropout_forward.  A null edge_logit: no term, logit_head_stride is then not looked at
+extern "C" int pygat_add_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                              int H, int F, float negative_slope, const float* s_dst, const float* s_src,
+                                              const float* v, int64_t ldv, const float* edge_logit, int logit_head_stride, float p,
+                                              const void* seed, uint32_t stream_id, float* out, int64_t ldo, float* m, float* Z,
+                                              void* ws, void* stream) {
+  AA_CALL(c, "add_attn_dropout_forward", false);
+  c.dropout = true; c.drop = {p, seed, stream_id};
+  return aa_launch(c);
+}
+
+extern "C" int pygat_add_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                                                    const int32_t* perm, int H, int F, float negative_slope, const float* s_dst,
+                                                    const float* s_src, const float* v, int64_t ldv, const float* edge_logit,
+                                                    int logit_head_stride, float p, const void* seed, uint32_t stream_id,
+                                                    const float* out, int64_t ldo, const float* m, const float* Z, const float* G,
+                                                    int64_t ldg, float* ds_dst, float* P, float* S, void* ws, void* stream) {
+  AA_CALL(c, "add_attn_dropout_backward_rows", true);
+  c.G = G; c.ldg = ldg; c.ds_dst = ds_dst; c.P = P; c.S = S;
+  c.dropout = true; c.drop = {p, seed, stream_id};
   return aa_launch(c);
 }

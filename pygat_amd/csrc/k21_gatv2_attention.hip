@@ -1,7 +1,8 @@
 // K21 -- gatv2_attention: the GATv2 score a . LeakyReLU(x_dst_i + x_src_j) over the entries of every row of a sparse pattern whose row
 // side and column side are different tables, for H heads at once, in one pass, and both sides of its gradient.  One kernel family in
 // the shape of K19 and K20: (forward | backward rows | backward columns) x (long | row), instantiated per lane shape; the two row
-// passes also per SHARED, the compile-time flag of v == x_src; and the two kernels of the staged reduce of da.  The kernels of the two
+// passes also per SHARED, the compile-time flag of v == x_src, and per DROP, that of the seeded dropout of the coefficients
+// (gatv2_attention_dropout); and the two kernels of the staged reduce of da.  The kernels of the two
 // row passes are da_family.h's, shared with K19 and K20, on V2Fam below; the column pass and the reduce of da are written here.
 //
 // Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h, feature f:
@@ -18,6 +19,10 @@
 //     dx_src[j, h, f] = sum_e S a[h, f] g'(t[f]),  da[h, f] = sum over all entries of S g(t[f]).
 //   dv = spmm^T(P, G) is K17 on the transposed pattern, the caller's launch.
 //   The forward keeps out, m and Z, all the backward reads -- nothing per entry.
+//   DROP: out[i, h, :] = sum_e p mask[c, h] v[j, h, :], mask in {0, 1 / (1 - p_drop)}: a dropped entry stays in Z, and m and Z are the
+//     undropped softmax's.  mask[c, h] is K19's: element c H + h of the flat layout of k7_dropout.hip's mask kernel on the launcher's
+//     stream id, drawn in registers in both row passes (da_keep_batch, da_lanes.h) -- no mask tensor exists.  backward_rows: S = p (mask
+//     <G, v> - D), P[c, h] = p mask.  The forward then carries c and reads perm.  The column pass reads S alone: one variant serves both.
 //
 // Lane mapping: K19's (da_lanes.h).  Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  A group of LPR
 // lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane; the chunks of a head sit on LH = F / 4 adjacent lanes of one
@@ -39,7 +44,10 @@
 //
 // Exactness.  No LDS, no float atomics, every sum in a fixed order: two runs give the same bits.
 //   a row without entries   out = m = Z = dx_dst = 0 exactly; a column without entries dx_src = 0
-//   a row of one entry      out_i = v_j bit for bit and S = 0 exactly: D and dp are formed by the same routine on the same bits
+//   a row of one entry      out_i = v_j bit for bit and S = 0 exactly: D and dp are formed by the same routine on the same bits;
+//                           DROP: out_i = mask v_j bit for bit; S = 0 exactly where the entry is dropped or mask is a power of two,
+//                           otherwise mask <G, v> against <G, mask v>, two roundings apart
+//   all entries dropped     (and every row under p_drop = 1) exact zeros in out
 //   SHARED                  the same operations on the same values as the kernels without the flag fed a copy of x_src
 #include "da_family.h"
 #include <math.h>
@@ -122,18 +130,25 @@ struct V2Own {
   float4 x[VEC], a[VEC];
 };
 
+// the key of a kernel's draws: K19's under DROP, nothing without
+template <bool DROP> using V2Key = std::conditional_t<DROP, uint2, DaNoKey>;
+
 // ------------------------------------------------------------------------------------------------------------------------ forward
-template <int LPR, int VEC, bool SHARED>
+// ent is looked at under DROP alone: ent[u] + head is the entry's flat mask index, and (p keep) v goes into acc while Z takes p whole
+template <int LPR, int VEC, bool SHARED, bool DROP>
 struct V2FwdFold {
   template <int U>
-  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, const V2Own<VEC>& r, DaState<VEC>& st,
-                                              const V2Rows<VEC, U, 0, SHARED>& w, const int64_t (&)[U]) {
+  __device__ __forceinline__ static void fold(const DaArgs& g, [[maybe_unused]] const DaLane<VEC>& ln, [[maybe_unused]] V2Key<DROP> key,
+                                              const V2Own<VEC>& r, DaState<VEC>& st, const V2Rows<VEC, U, 0, SHARED>& w,
+                                              [[maybe_unused]] const int64_t (&ent)[U]) {
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const float s = v2_score<LPR>(g, r.a[v], v2_t(r.x[v], w.x[u][v]));
-        da_fold<false, false>(st.m[v], st.z[v], st.acc[v], s, 0.f, 1.f, w.val(u, v));
+        da_fold<false, DROP>(st.m[v], st.z[v], st.acc[v], s, 0.f, DROP ? keep[u][v] : 1.f, w.val(u, v));
       }
   }
 };
@@ -146,11 +161,18 @@ struct V2BwdRow : DaGrad<VEC> {   // what the backward holds of its row
 
 // the backward's fold of a batch; ctx: the row (V2BwdRow) and the lane's chunks of dx_dst.  In a row of one entry out_i is v_j bit for
 // bit, so dp and D are one routine on the same bits and S is an exact zero
-template <int LPR, int VEC, bool SHARED>
+// DROP: the batch's keep factors are drawn again, as K19's backward does; an entry's multiplies <G_i, v_j> -- D_i = <G_i, out_i> is the
+// row term of the dropped sum already -- and the stored P is p keep, what the transposed SpMM of dv multiplies G with; the column pass
+// reads S alone and is the same launch with and without dropout.  In a row of one entry out_i is keep v_j bit for bit; S is an exact
+// zero where the entry is dropped and where keep is a power of two, and otherwise a rounding of keep dp against one of D
+template <int LPR, int VEC, bool SHARED, bool DROP>
 struct V2BwdFold {
   template <int U>
-  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, const V2BwdRow<VEC>& r, float4 (&dx)[VEC],
-                                              const V2Rows<VEC, U, 1, SHARED>& w, const int64_t (&ent)[U]) {
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, [[maybe_unused]] V2Key<DROP> key,
+                                              const V2BwdRow<VEC>& r, float4 (&dx)[VEC], const V2Rows<VEC, U, 1, SHARED>& w,
+                                              const int64_t (&ent)[U]) {
+    [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
+    if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -158,11 +180,16 @@ struct V2BwdFold {
         const float4 t = v2_t(r.own.x[v], w.x[u][v]);
         const float s = v2_score<LPR>(g, r.own.a[v], t);
         const float p = __expf(s - r.m[v]) * r.rz[v];
-        const float dp = da_head_sum<LPR>(dot4(r.G[v], w.val(u, v)), g.LH);
+        float dp = da_head_sum<LPR>(dot4(r.G[v], w.val(u, v)), g.LH);
+        float pk = p;
+        if constexpr (DROP) {
+          dp *= keep[u][v];
+          pk *= keep[u][v];
+        }
         const float S = p * (dp - r.D[v]);
         v2_dside(dx[v], S, r.own.a[v], t, g.scale);
         if (ln.lead >> v & 1) {
-          g.P[ent[u] + ln.head[v]] = p;
+          g.P[ent[u] + ln.head[v]] = pk;
           g.S[ent[u] + ln.head[v]] = S;
         }
       }
@@ -172,13 +199,16 @@ struct V2BwdFold {
 template <int VEC>
 struct V2ColFold;
 
-// the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED (the column pass: without)
-template <bool SHARED>
+// the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED and DROP (the column pass: without either)
+template <bool SHARED, bool DROP = false>
 struct V2Fam {
   static constexpr bool KEEP_MZ = true;
   template <int VEC> using Own = V2Own<VEC>;
   template <int VEC> using Row = V2BwdRow<VEC>;
-  __device__ __forceinline__ static DaNoKey key(const DaArgs&) { return {}; }
+  __device__ __forceinline__ static V2Key<DROP> key([[maybe_unused]] const DaArgs& g) {
+    if constexpr (DROP) return da_key<true>(g);
+    else return {};
+  }
   __device__ __forceinline__ static bool lone(int64_t, int64_t) { return false; }
   template <int VEC>
   __device__ __forceinline__ static void load(const DaArgs& g, const DaLane<VEC>& ln, int64_t row, V2Own<VEC>& r) {
@@ -188,13 +218,16 @@ struct V2Fam {
   // The walk of all three passes, after K19's: the entries e0, e0 + step, ... < e1 of one row, handed to the pass's fold in that
   // order, U at a time and then one at a time.  The indices of the next U entries -- the other side's row and, in the backward passes,
   // the caller's entry index (da_entry) -- are asked for before this batch's gather is used, so an iteration waits for one gather, not
-  // for an index and then a gather.  The forward carries no entry index and does not touch perm.
+  // for an index and then a gather.  The forward carries no entry index and does not touch perm -- except under DROP, where the entry
+  // index places the draws: its forward forms it as the backward passes do (ENT).  key: the key of the draws under DROP, by value.
   template <int LPR, int VEC, int MODE, typename... Ctx>
   __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
-                                                DaNoKey, Ctx&... ctx) {
-    using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED>,
-                                    std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED>, V2ColFold<VEC>>>;
+                                                V2Key<DROP> key, Ctx&... ctx) {
+    static_assert(MODE != 2 || !DROP, "the column pass reads S alone: it has no DROP variant");
+    using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED, DROP>,
+                                    std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED, DROP>, V2ColFold<VEC>>>;
     constexpr int U = v2_unroll(MODE != 0, VEC);
+    constexpr bool ENT = MODE != 0 || DROP;
     int64_t e = e0;
     if constexpr (U > 1) {
       int32_t src[U];
@@ -206,11 +239,11 @@ struct V2Fam {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
-          if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+          if constexpr (ENT) ent_next[u] = da_entry(g, e + u * step);
         }
       }
       while (full) {
-        if constexpr (MODE != 0) {
+        if constexpr (ENT) {
 #pragma unroll
           for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
         }
@@ -222,19 +255,19 @@ struct V2Fam {
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             src[u] = g.col[e + u * step];
-            if constexpr (MODE != 0) ent_next[u] = da_entry(g, e + u * step);
+            if constexpr (ENT) ent_next[u] = da_entry(g, e + u * step);
           }
         }
-        Fold::fold(g, ln, ctx..., w, ent);
+        Fold::fold(g, ln, key, ctx..., w, ent);
       }
     }
     for (; e < e1; e += step) {
       const int32_t src[1] = {g.col[e]};
       int64_t ent[1] = {0};
-      if constexpr (MODE != 0) ent[0] = da_entry(g, e);
+      if constexpr (ENT) ent[0] = da_entry(g, e);
       V2Rows<VEC, 1, MODE, SHARED> w;
       v2_gather<VEC, 1, MODE, SHARED>(g, ln, src, ent, w);
-      Fold::fold(g, ln, ctx..., w, ent);
+      Fold::fold(g, ln, key, ctx..., w, ent);
     }
   }
   template <int LPR, int VEC>
@@ -250,7 +283,7 @@ struct V2Fam {
 template <int VEC>
 struct V2ColFold {
   template <int U>
-  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, const V2Own<VEC>& r, float4 (&dx)[VEC],
+  __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, DaNoKey, const V2Own<VEC>& r, float4 (&dx)[VEC],
                                               float4 (&da)[VEC], float4 (&dc)[VEC], const V2Rows<VEC, U, 2, false>& w,
                                               const int64_t (&)[U]) {
 #pragma unroll
@@ -375,34 +408,42 @@ __global__ __launch_bounds__(256) void v2_da_final_kernel(int R, const float* __
 
 // the table of the family: (SHARED, forward | backward rows | columns, long | row, lane shape) -> the kernel.  What a launcher starts
 // and what pygat_kernel_footprint reports on both come from here.  pass: 0 forward, 1 backward rows, 2 columns (no SHARED variant)
-template <int LPR, int VEC, bool SHARED>
+template <int LPR, int VEC, bool SHARED, bool DROP>
 static const void* v2_kernel_at(int pass, bool lng) {
   if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC>)
                             : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC>);
-  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED>, LPR, VEC>)
-                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED>, LPR, VEC>);
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED>, LPR, VEC>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED>, LPR, VEC>);
+  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED, DROP>, LPR, VEC>)
+                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED, DROP>, LPR, VEC>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED, DROP>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED, DROP>, LPR, VEC>);
 }
-static const void* v2_kernel(bool shared, int pass, bool lng, int lpr, int vec) {
-  if (shared) PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, true>(pass, lng)));
-  else PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, false>(pass, lng)));
+template <bool SHARED, bool DROP>
+static const void* v2_kernel_of(int pass, bool lng, int lpr, int vec) {
+  PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, SHARED, DROP>(pass, lng)));
   return nullptr;
+}
+// (the column pass has one variant: whatever is asked for, the kernels without a flag)
+static const void* v2_kernel(bool shared, bool drop, int pass, bool lng, int lpr, int vec) {
+  if (pass == 2) return v2_kernel_of<false, false>(pass, lng, lpr, vec);
+  if (drop) return shared ? v2_kernel_of<true, true>(pass, lng, lpr, vec) : v2_kernel_of<false, true>(pass, lng, lpr, vec);
+  return shared ? v2_kernel_of<true, false>(pass, lng, lpr, vec) : v2_kernel_of<false, false>(pass, lng, lpr, vec);
 }
 
 // pygat_kernel_footprint: <prefix>{fwd,bwd,col}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k21_: a v table of its
-// own, k21s_: SHARED (fwd and bwd only: the column pass has one variant, under k21_); k21_da_stage, k21_da_final: the reduce of da
+// own, k21s_: SHARED, k21d_: DROP, k21ds_: DROP and SHARED (fwd and bwd only: the column pass has one variant, under k21_);
+// k21_da_stage, k21_da_final: the reduce of da
 int footprint_k21(const char* name, int* regs, int* scratch) {
-  static const struct { const char* prefix; bool shared; } names[] = {{"k21_", false}, {"k21s_", true}};
+  static const struct { const char* prefix; bool shared, drop; } names[] = {
+      {"k21_", false, false}, {"k21s_", true, false}, {"k21d_", false, true}, {"k21ds_", true, true}};
   const void* fn = nullptr;
   if (!strcmp(name, "k21_da_stage")) fn = reinterpret_cast<const void*>(&v2_da_stage_kernel);
   if (!strcmp(name, "k21_da_final")) fn = reinterpret_cast<const void*>(&v2_da_final_kernel);
   DaKernelName k;
   for (const auto& nm : names)
-    if (!fn && da_parse_kernel_name(name, nm.prefix, &k) && (k.pass != 2 || !nm.shared))
-      fn = v2_kernel(nm.shared, k.pass, k.lng, k.lpr, k.vec);
+    if (!fn && da_parse_kernel_name(name, nm.prefix, &k) && (k.pass != 2 || !(nm.shared || nm.drop)))
+      fn = v2_kernel(nm.shared, nm.drop, k.pass, k.lng, k.lpr, k.vec);
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (k21{,s}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, k21_col_{long,row}_l<LPR>v<VEC>, "
+    set_error("kernel_footprint: unknown kernel '%s' (k21{,s,d,ds}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, k21_col_{long,row}_l<LPR>v<VEC>, "
               "k21_da_stage, k21_da_final)", name);
     return PYGAT_EINVAL;
   }
@@ -444,6 +485,8 @@ struct V2Call {
   int64_t lddx;
   float *P, *S, *da;
   void *ws, *stream;
+  bool dropout;                // the DROP kernels of the two row passes, on the mask of drop
+  DaDrop drop;
 };
 
 // all three launchers: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
@@ -483,6 +526,11 @@ static int v2_launch(const V2Call& c) {
     PYGAT_REQUIRE(c.da, "%s: null da", what);
     PYGAT_REQUIRE(aligned16(c.da), "%s: da must be 16-byte aligned", what);
   }
+  DropRng rng;
+  if (c.dropout) {
+    const int rd = da_check_drop(what, c.drop, &rng);
+    if (rd != PYGAT_OK) return rd;
+  }
   if (c.n == 0) return PYGAT_OK;
   DaArgs g;
   memset(&g, 0, sizeof(g));
@@ -495,6 +543,7 @@ static int v2_launch(const V2Call& c) {
   }
   if (c.pass != 0) { g.perm = c.perm; g.dq = c.dx; g.lddq = c.lddx; g.S = c.S; }   // (the forward walks in CSR order alone)
   if (c.pass == 1) { g.G = c.G; g.ldg = c.ldg; g.P = c.P; }
+  if (c.dropout) { g.perm = c.perm; g.rng = rng; }                                 // (... but for the draws: its entry index places them)
   DaGrid gd = da_grid(c.n, c.nnz, c.H, c.F);
   float* stage = nullptr;
   if (cols) {
@@ -506,8 +555,8 @@ static int v2_launch(const V2Call& c) {
   }
   hipStream_t st = (hipStream_t)c.stream;
   const bool shared = !cols && !c.v;
-  da_launch_pair(v2_kernel(shared, c.pass, true, gd.lpr, gd.vec), v2_kernel(shared, c.pass, false, gd.lpr, gd.vec), g, gd.chunks,
-                 gd.blocks, c.stream);
+  da_launch_pair(v2_kernel(shared, c.dropout, c.pass, true, gd.lpr, gd.vec), v2_kernel(shared, c.dropout, c.pass, false, gd.lpr, gd.vec),
+                 g, gd.chunks, gd.blocks, c.stream);
   if (cols) {
     const int nrec = (int)(gd.chunks + 4 * gd.blocks);
     hipLaunchKernelGGL(v2_da_stage_kernel, dim3(V2_DA_STAGE), dim3(256), 0, st, HF, nrec, (const float*)g.de, stage);
@@ -550,6 +599,36 @@ extern "C" int pygat_v2_attn_backward_rows(int n_rows, int64_t nnz, const int32_
   c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v;
   c.ldv = ldv; c.out = const_cast<float*>(out); c.ldo = ldo; c.m = const_cast<float*>(m); c.Z = const_cast<float*>(Z); c.G = G;
   c.ldg = ldg; c.dx = dx_dst; c.lddx = lddx; c.P = P; c.S = S; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}
+
+// the two row passes with seeded dropout of the coefficients (the DROP instantiations): out = sum_e alpha mask v, mask[c(e), h] element
+// c(e) H + h of the flat layout pygat_dropout_mask(nnz H, p, seed, stream_id) writes, drawn in registers in both passes -- the mask of
+// pygat_dot_attn_dropout_forward.  The forward takes perm: the entry index places the draws.  pygat_v2_attn_backward_cols reads S alone
+// and serves as it is
+extern "C" int pygat_v2_attn_dropout_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                             int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                             int64_t lds, const float* a, const float* v, int64_t ldv, float p, const void* seed,
+                                             uint32_t stream_id, float* out, int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_dropout_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
+  c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
+  c.out = out; c.ldo = ldo; c.m = m; c.Z = Z; c.ws = ws; c.stream = stream; c.dropout = true; c.drop = {p, seed, stream_id};
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                                                   const int32_t* perm, int H, int F, float negative_slope, const float* x_dst,
+                                                   int64_t ldd, const float* x_src, int64_t lds, const float* a, const float* v,
+                                                   int64_t ldv, float p, const void* seed, uint32_t stream_id, const float* out,
+                                                   int64_t ldo, const float* m, const float* Z, const float* G, int64_t ldg,
+                                                   float* dx_dst, int64_t lddx, float* P, float* S, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_dropout_backward_rows"; c.pass = 1; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm;
+  c.H = H; c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v;
+  c.ldv = ldv; c.out = const_cast<float*>(out); c.ldo = ldo; c.m = const_cast<float*>(m); c.Z = const_cast<float*>(Z); c.G = G;
+  c.ldg = ldg; c.dx = dx_dst; c.lddx = lddx; c.P = P; c.S = S; c.ws = ws; c.stream = stream; c.dropout = true;
+  c.drop = {p, seed, stream_id};
   return v2_launch(c);
 }
 

@@ -10,6 +10,8 @@
     out = gatv2_attention(pattern, Whi, Whj, a, v=Whi)                      # the reference's SpGraphAttentionLayerV2 (layers.py:270-300)
     e = (a * F.leaky_relu(x_dst[row] + x_src[col], 0.2)).sum(-1)            # the same from parts: an [E, H, F] tensor, kept for autograd
     out = spmm(pattern, edge_softmax(pattern, e), x_src)
+    out = gatv2_attention_dropout(pattern, x_dst, x_src, a, 0.6, training=self.training)    # training: dropout p on the coefficients, after
+                                                                # the softmax, drawn in the kernels from a seed on the device
 
 The nonlinearity sits inside the sum over the features, so the score needs a whole F-wide row per entry and cannot be written as
 additive_attention's sum of two per-node scalars.  A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate
@@ -27,34 +29,36 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import _require_heads, _require_pattern, _require_tensor, _slope
+from .dot_attention import _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
+from .dropout import STREAM_ATT
 from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "gatv2_attention"
+_OP_DROP = "gatv2_attention_dropout"
 _PAD_HINT = ("zero-pad the columns of all four tensors (x_dst, x_src, a and v) to the next allowed F: zero columns of a add nothing "
              "to a score, and the first F columns of the result are unchanged")
 
 
-def _checked(pattern, x_dst, x_src, a, v):
-    """Every refusal that looks at the pattern and the tensors -> (H, F)."""
-    _require_pattern(_OP, pattern)
+def _checked(pattern, x_dst, x_src, a, v, op: str = _OP):
+    """Every refusal that looks at the pattern and the tensors, under the op's name -> (H, F)."""
+    _require_pattern(op, pattern)
     for name, t in (("x_dst", x_dst), ("x_src", x_src), ("a", a), ("v", v)):
-        _require_tensor(_OP, pattern, name, t)
+        _require_tensor(op, pattern, name, t)
     if x_dst.dim() not in (2, 3):
-        raise ValueError(f"pygat_amd {_OP}: x_dst [n_rows, F] or [n_rows, H, F] expected, got {tuple(x_dst.shape)}")
+        raise ValueError(f"pygat_amd {op}: x_dst [n_rows, F] or [n_rows, H, F] expected, got {tuple(x_dst.shape)}")
     for name, t in (("x_src", x_src), ("v", v)):
         if t.dim() != x_dst.dim() or t.shape[1:] != x_dst.shape[1:]:
-            raise ValueError(f"pygat_amd {_OP}: {name} {tuple(t.shape)} does not match x_dst {tuple(x_dst.shape)}: the same number of "
+            raise ValueError(f"pygat_amd {op}: {name} {tuple(t.shape)} does not match x_dst {tuple(x_dst.shape)}: the same number of "
                              f"heads and the same width expected")
     if a.shape != x_dst.shape[1:]:
-        raise ValueError(f"pygat_amd {_OP}: a {tuple(a.shape)} does not match x_dst {tuple(x_dst.shape)}: a [F] with x_dst [n_rows, F], "
+        raise ValueError(f"pygat_amd {op}: a {tuple(a.shape)} does not match x_dst {tuple(x_dst.shape)}: a [F] with x_dst [n_rows, F], "
                          f"or a [H, F] with x_dst [n_rows, H, F], expected")
     for name, t, rows, side in (("x_dst", x_dst, pattern.n_rows, "rows"), ("x_src", x_src, pattern.n_cols, "columns"),
                                 ("v", v, pattern.n_cols, "columns")):
         if t.shape[0] != rows:
-            raise ValueError(f"pygat_amd {_OP}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
     H, F = (1 if x_dst.dim() == 2 else int(x_dst.shape[1])), int(x_dst.shape[-1])
-    _require_heads(_OP, H, F, _PAD_HINT)
+    _require_heads(op, H, F, _PAD_HINT)
     return H, F
 
 
@@ -63,15 +67,19 @@ def _workspace(pattern, H: int, F: int, dev):
 
 
 class _Gatv2AttentionFn(torch.autograd.Function):
-    """shared: v is x_src (the op's v=None).  The tensor arrives in both places all the same, so autograd adds the two parts of its
-    gradient -- the score's (the column pass) and the value's (the transposed SpMM) -- and the kernels get a null v."""
+    """gatv2_attention and gatv2_attention_dropout.  shared: v is x_src (the op's v=None).  The tensor arrives in both places all the
+    same, so autograd adds the two parts of its gradient -- the score's (the column pass) and the value's (the transposed SpMM) -- and
+    the kernels get a null v.  drop: None or (p, seed) of gatv2_attention_dropout: the mask of the coefficients, drawn in the kernels of
+    the two row passes from the int64 [1] seed tensor on the device; the column pass reads S alone and is the same launch."""
 
     @staticmethod
-    def forward(ctx, pattern, x_dst, x_src, a, v, slope, shared):
-        H, F = _checked(pattern, x_dst, x_src, a, v)
-        ctx.pattern, ctx.slope, ctx.hf, ctx.shared = pattern, slope, (H, F), shared
+    def forward(ctx, pattern, x_dst, x_src, a, v, slope, shared, drop=None):
+        op = _OP if drop is None else _OP_DROP
+        H, F = _checked(pattern, x_dst, x_src, a, v, op)
+        p, seed = (None, None) if drop is None else drop
+        ctx.pattern, ctx.slope, ctx.hf, ctx.shared, ctx.op, ctx.p = pattern, slope, (H, F), shared, op, p
         if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
-            ctx.save_for_backward(x_dst, x_src, a, v, None, None, None)
+            ctx.save_for_backward(x_dst, x_src, a, v, None, None, None, None)
             return torch.zeros_like(x_dst)
         xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src, a))
         vc = None if shared else v.detach().contiguous()
@@ -80,26 +88,31 @@ class _Gatv2AttentionFn(torch.autograd.Function):
             out = torch.empty(n, HF, dtype=torch.float32, device=dev)
             m, Z = (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
             ws = _workspace(pattern, H, F, dev)
-            check(lib.pygat_v2_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), H, F, slope, _ptr(xd), HF,
-                                            _ptr(xs), HF, _ptr(ac), _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream()),
-                  "v2_attn_forward")
+            tables = (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF)
+            rest = (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream())
+            if drop is None:                                       # (the forward without dropout walks in CSR order alone)
+                check(lib.pygat_v2_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), *tables, *rest),
+                      "v2_attn_forward")
+            else:
+                check(lib.pygat_v2_attn_dropout_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
+                                                        *tables, p, _ptr(seed), STREAM_ATT, *rest), "v2_attn_dropout_forward")
         out = out.view(x_dst.shape)
-        ctx.save_for_backward(x_dst, x_src, a, v, out, m, Z)
+        ctx.save_for_backward(x_dst, x_src, a, v, out, m, Z, seed)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        x_dst, x_src, a, v, out, m, Z = ctx.saved_tensors
+        x_dst, x_src, a, v, out, m, Z, seed = ctx.saved_tensors
         pattern, slope, (H, F), shared = ctx.pattern, ctx.slope, ctx.hf, ctx.shared
         if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {_OP}: the gradient of the output must be float32, not {G.dtype}")
+            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_d, need_s, need_a, need_v = ctx.needs_input_grad[1:5]
         if not (need_d or need_s or need_a or need_v):
-            return (None,) * 7
+            return (None,) * 8
         if out is None:                                            # no entries: zeros, nothing launched
             return (None,) + tuple(torch.zeros_like(t) if need else None
-                                   for t, need in ((x_dst, need_d), (x_src, need_s), (a, need_a), (v, need_v))) + (None, None)
+                                   for t, need in ((x_dst, need_d), (x_src, need_s), (a, need_a), (v, need_v))) + (None, None, None)
         n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, x_dst.device
         xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src, a))
         vc = None if shared else v.detach().contiguous()
@@ -108,10 +121,12 @@ class _Gatv2AttentionFn(torch.autograd.Function):
             dd = torch.empty(n, HF, dtype=torch.float32, device=dev)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
             ws = _workspace(pattern, H, F, dev)
-            check(lib.pygat_v2_attn_backward_rows(n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope,
-                                                  _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF, _ptr(out), HF, _ptr(m), _ptr(Z),
-                                                  _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S), _ptr(ws), _stream()),
-                  "v2_attn_backward_rows")
+            kind = "" if seed is None else "dropout_"
+            group = () if seed is None else (ctx.p, _ptr(seed), STREAM_ATT)
+            check(getattr(lib, f"pygat_v2_attn_{kind}backward_rows")(
+                n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac),
+                _ptr(vc), HF, *group, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S), _ptr(ws),
+                _stream()), f"v2_attn_{kind}backward_rows")
             ds = da = dv = None
             if need_s or need_a or need_v:
                 rowptr_t, row_t, perm_t = pattern.transposed()
@@ -124,7 +139,7 @@ class _Gatv2AttentionFn(torch.autograd.Function):
                 if need_v:
                     dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
         return (None, dd.view(x_dst.shape) if need_d else None, ds.view(x_src.shape) if need_s else None,
-                da.view(a.shape) if need_a else None, dv, None, None)
+                da.view(a.shape) if need_a else None, dv, None, None, None)
 
 
 def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tensor, a: torch.Tensor, v: Optional[torch.Tensor] = None,
@@ -142,9 +157,41 @@ def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tens
     share the column pass on the transposed pattern; dv is one K17 launch there.  float32 GPU tensors on the pattern's device;
     1 <= H <= 64, F a power of two in 4..256, H * F <= 1024; for another F zero-pad the columns of all four tensors: zero columns of a
     add nothing to a score.
-    Not provided: a per-entry term or edge features, dropout on the coefficients, bfloat16 tables, the value product fused into the
-    column pass (dv is a K17 launch on the transposed pattern)."""
+    Not provided: a per-entry term or edge features, dropout on the coefficients (that is the sibling op's,
+    gatv2_attention_dropout), bfloat16 tables, the value product fused into the column pass (dv is a K17 launch on the transposed
+    pattern)."""
     slope = _slope(_OP, negative_slope)
     if v is None:
         return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src, slope, True)
     return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, v, slope, False)
+
+
+def gatv2_attention_dropout(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tensor, a: torch.Tensor, p: float,
+                            v: Optional[torch.Tensor] = None, negative_slope: float = 0.2, *, seed: Optional[torch.Tensor] = None,
+                            generator=None, training: bool = True) -> torch.Tensor:
+    """gatv2_attention with dropout p on the attention coefficients, as a GATv2 trains (the reference's dropout after the
+    normalisation, PyG's GATv2Conv): out[i] = sum over the entries e = (i, j) of row i of
+    softmax_row(sum_f a[f] LeakyReLU(x_dst[i, f] + x_src[j, f]))[e] * mask[e] * v[j], per head, mask in {0, 1 / (1 - p)}.  The softmax
+    runs over all entries of the row -- a dropped entry keeps its share of the denominator -- so this is dropout after the softmax, not
+    masking before it.  Fused on the DROP instantiations of the two K21 row passes: the decision for (entry, head) is drawn in registers
+    (Philox-4x32-10) in the forward and again in the backward, and no [E, H] mask exists outside backward; the column pass (dx_src and
+    da) reads S alone and is gatv2_attention's.
+    seed: an int64 [1] tensor on the pattern's device, read by the kernels (refill it in place between replays of a captured graph);
+    None draws one with torch.randint(0, 2**62, ..., generator=generator).  The mask is attention_dropout_mask(pattern, H, p, seed), at
+    the caller's entry index -- the mask dot_attention_dropout and additive_attention_dropout draw from the same seed; the same seed
+    gives the same bits.  training=False or p == 0 is gatv2_attention itself; p == 1 gives zeros; a row whose entries are all dropped
+    gets exact zeros.  v=None: v is x_src, as in gatv2_attention.  Differentiable in x_dst, x_src, a and v; a gradient that is not asked
+    for costs no launch where a whole launch serves only it.  float32 GPU tensors with gatv2_attention's limits; bfloat16 tensors are
+    refused."""
+    op = _OP_DROP
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (x_dst, x_src, a, v)):
+        raise ValueError(f"pygat_amd {op}: x_dst, x_src, a and v must be float32: there is no training path on bfloat16 tensors")
+    p, slope = _drop_p(op, p), _slope(op, negative_slope)
+    if seed is not None:
+        seed = _drop_seed(op, pattern, seed)
+    _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op)      # (refusals under this op's name, before the device)
+    if not training or p == 0.0:
+        return gatv2_attention(pattern, x_dst, x_src, a, v, slope)
+    if seed is None:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
+    return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, (p, seed))

@@ -1,0 +1,372 @@
+"""pygat_amd.additive_attention_dropout (the DROP instantiations of csrc/k20_additive_attention.hip): additive_attention with seeded
+dropout on the softmax coefficients, the decision for (entry, head) drawn in the kernels of both passes -- out, ds_dst, ds_src, dv, du.
+
+Ground truth, the mask and the seeded cases live in additive_attention_dropout_case.py: torch autograd in fp64 on the CPU with the mask
+of tests/philox_ref.py, loss L = <out, G>, pricing by parity.check_autograd unchanged (out by close_fwd, every gradient by close_grad).
+Every case is rehearsed on the CPU, the fp32 ground-truth run standing in for the device, by
+tests/test_additive_attention_dropout_abi.py and passes there; no case is built here."""
+import copy
+import ctypes as C
+import importlib
+import itertools
+
+import pytest
+import torch
+
+import additive_attention_dropout_case as case
+from test_gpu_attention import DEV
+from test_gpu_dot_attention import _Spy, _pattern
+
+pytestmark = pytest.mark.gpu
+
+FWD, ROWS, SPMM = "pygat_add_attn_forward", "pygat_add_attn_backward_rows", "pygat_spmm_forward"
+DFWD, DROWS, MASK = "pygat_add_attn_dropout_forward", "pygat_add_attn_dropout_backward_rows", "pygat_dropout_mask"
+SHAPES = ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))
+K20D = [f"{fam}_{d}_{kind}_l{l}v{v}" for fam in ("k20d", "k20du") for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES]
+
+
+def _seed(value):
+    return torch.tensor([value], dtype=torch.int64, device=DEV)
+
+
+def _leaves(c):
+    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
+
+
+def _fused(pattern, c, seed=None):
+    import pygat_amd as pg
+    seed = _seed(c.seed) if seed is None else seed
+    return lambda s_dst, s_src, v, u=None: pg.additive_attention_dropout(pattern, s_dst, s_src, v, c.p, c.slope, u, seed=seed)
+
+
+def _from_parts(pattern, c, seed=None):
+    import pygat_amd as pg
+    seed = _seed(c.seed) if seed is None else seed
+    row, col = c.row.to(DEV), c.col.to(DEV)
+
+    def run(s_dst, s_src, v, u=None):
+        z = s_dst[row] + s_src[col]
+        if u is not None:
+            z = z + (u[:, None] if u.dim() < z.dim() else u)
+        alpha = pg.edge_softmax(pattern, torch.nn.functional.leaky_relu(z, c.slope))
+        return pg.spmm(pattern, alpha * pg.attention_dropout_mask(pattern, c.H, c.p, seed).view(alpha.shape), v)
+    return run
+
+
+def _device_run(pattern, c, fn=None, seed=None, leaves=None):
+    """-> (out, ds_dst, ds_src, dv[, du]) on the device."""
+    leaves = leaves or _leaves(c)
+    out = (fn or _fused)(pattern, c, seed)(*leaves)
+    assert out.dtype == torch.float32 and out.shape == c.G.shape and out.requires_grad
+    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+
+
+def _run_case(name):
+    c = case.cases()[name]
+    res = _device_run(_pattern(c), c)
+    c.price(*res)
+    c.check_all_dropped(res[0])
+    return (c,) + res
+
+
+def _spied(monkeypatch):
+    seen = []
+    for mod in ("pygat_amd.additive_attention", "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):
+        m = importlib.import_module(mod)
+        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------------------------ lane shapes
+@pytest.mark.parametrize("name", case.case_names("lanes-"))
+def test_lane_shapes(name):
+    """Every lane shape -- LPR 1..64, VEC 2, 3 and 4, tensors without a head axis -- at p = 0.5, with and without a permutation, without
+    a logit and with one ([E, H], and [E] shared by the heads): the four DROP kernels with and without LOGIT."""
+    _run_case(name)
+
+
+@pytest.mark.parametrize("name", case.case_names("long-"))
+def test_long_rows(name):
+    """Every slot of a chunk and a row of three chunks, scores of std 3, at p = 0.5 and 0.9: a mask drawn at the wrong entry index in
+    the long-row launch, or Z taken over the kept entries alone, moves out far beyond 1e-5."""
+    _run_case(name)
+
+
+@pytest.mark.parametrize("name", case.case_names("rect-") + case.case_names("repeats-") + case.case_names("gone-"))
+def test_unsorted_entries_and_rows_that_lose_every_entry(name):
+    """Unsorted entries (only the permutation finds an entry's decision), a rectangular pattern with empty rows, repeated (row, col)
+    pairs with a decision each; at p = 0.9, rows of two and more entries that lose all of them in a head are exact zeros there."""
+    c, out = _run_case(name)[:2]
+    if name.startswith("gone-"):
+        gone = c.all_dropped().to(DEV)
+        assert int(gone.sum()) >= 5 and float(out[gone].abs().max()) == 0.0
+        some_kept = ~c.all_dropped(min_entries=0).to(DEV)                       # (a row and head that keep at least one entry)
+        assert bool((out[some_kept].abs().amax(-1) > 0.0).all())
+
+
+# -------------------------------------------------------------------------------------------------------------- the mask, bit for bit
+@pytest.mark.parametrize("name", case.case_names("single-"))
+def test_the_mask_bit_for_bit(name):
+    """Exactly one entry per row, unsorted: every coefficient is 1, so out[i, h, :] == mask[e, h] * v[col_e, h, :] exactly, with the mask
+    of tests/philox_ref.py at the CALLER's entry index; attention_dropout_mask writes the same table on the device; ds_dst is exact
+    zeros (at p = 0.5 the factor 2 is exact in <G_i, out_i> as well)."""
+    import pygat_amd as pg
+    c, out, dd = _run_case(name)[:3]
+    mask = c.mask.to(DEV)
+    assert torch.equal(pg.attention_dropout_mask(_pattern(c), c.H, c.p, _seed(c.seed)), mask)
+    want = torch.zeros_like(out)
+    want[c.row.to(DEV)] = mask[:, :, None] * c.v.float().to(DEV)[c.col.to(DEV)]
+    assert torch.equal(out, want), "out_i == mask_e * v_j bit for bit"
+    assert bool((out == 0).any()) and bool((out != 0).any())
+    assert float(dd.abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------ composition
+@pytest.mark.parametrize("name", case.case_names("composed-"))
+def test_fused_against_the_composition(name):
+    """spmm(edge_softmax(leaky_relu(s_dst[row] + s_src[col] (+ u))) * attention_dropout_mask, v) on the device and the fused op: both
+    pass against the same fp64 run, out and every gradient.  The mask's bits through P: with G = 1, dv[j, h, :] = sum over the entries
+    of column j of P[e, h], a sum of terms >= 0 (p > 0: no score of these cases underflows), so it is an exact zero where, and only
+    where, the mask drops every entry of the column in that head."""
+    c = case.cases()[name]
+    pattern = _pattern(c)
+    c.price(*_device_run(pattern, c), what=name + " fused")
+    c.price(*_device_run(pattern, c, _from_parts), what=name + " from parts")
+    leaves = _leaves(c)
+    out = _fused(pattern, c)(*leaves)
+    dv = torch.autograd.grad(out, leaves[2], torch.ones_like(out))[0]
+    kept = torch.zeros(c.shape[1], c.H).index_add(0, c.col, (c.mask != 0).float())
+    assert torch.equal(dv[:, :, 0] == 0, (kept == 0).to(DEV)), "the exact zeros of P are the mask's"
+    filled = torch.bincount(c.col, minlength=c.shape[1]) > 0
+    assert bool((kept[filled] == 0).any()) and bool((kept[filled] != 0).any())
+
+
+@pytest.mark.parametrize("name", case.case_names("masked-"))
+def test_masked_entries_under_dropout(name):
+    """u = -9e15 on a third of the entries and dropout on top: priced as usual; du at the masked entries is 0.0 whether or not the
+    dropout keeps them."""
+    c, out, dd, ds, dv, du = _run_case(name)
+    c.check_masked(du)
+    assert float(du.abs().max()) > 0.0
+
+
+@pytest.mark.parametrize("name", case.case_names("zero-"))
+def test_a_logit_of_zeros_changes_no_bit(name):
+    """out, ds_dst, ds_src and dv under a logit of zeros and dropout are bit-equal to the DROP kernels without LOGIT on the same inputs
+    and the same seed."""
+    c, out, dd, ds, dv, du = _run_case(name)
+    want = _device_run(_pattern(c), c, leaves=_leaves(c)[:3])
+    for got, ref, what in zip((out, dd, ds, dv), want, ("out", "ds_dst", "ds_src", "dv")):
+        assert torch.equal(got, ref), (name, what)
+
+
+# ---------------------------------------------------------------------------------------------------------------- trivial paths
+def test_trivial_paths(monkeypatch):
+    """training=False and p = 0 are additive_attention itself, bit for bit, without a dropout launch; p = 1 gives zeros everywhere; p
+    next to 0 goes through the DROP kernels, keeps every entry with a factor of 1.0f, and is additive_attention bit for bit as well."""
+    import pygat_amd as pg
+    seen = _spied(monkeypatch)
+    for name in ("near0-hub-8x16-indices-plain", "near0-hub-12x64-graph-logit"):
+        c = case.cases()[name]
+        pattern = _pattern(c)
+        G = c.G.float().to(DEV)
+
+        def run(fn):
+            del seen[:]
+            leaves = _leaves(c)
+            out = fn(*leaves)
+            return (out.detach(),) + torch.autograd.grad(out, leaves, G), list(seen)
+        u_kw = (lambda lv: {} if c.u is None else {"edge_logit": lv[3]})
+        want, launched = run(lambda *lv: pg.additive_attention(pattern, *lv[:3], c.slope, **u_kw(lv)))
+        assert launched[:2] == [FWD, ROWS]
+        for kw in (dict(p=0.5, training=False), dict(p=0.0), dict(p=0.0, seed=_seed(5)), dict(p=0, training=False)):
+            got, seen_now = run(lambda *lv: pg.additive_attention_dropout(pattern, *lv[:3], kw["p"], c.slope, **u_kw(lv),
+                                                                         **{k: v for k, v in kw.items() if k != "p"}))
+            assert seen_now == launched and DFWD not in seen_now, (kw, seen_now)
+            assert all(torch.equal(a, b) for a, b in zip(got, want)), kw
+        got, seen_now = run(lambda *lv: pg.additive_attention_dropout(pattern, *lv[:3], 1.0, c.slope, **u_kw(lv), seed=_seed(c.seed)))
+        assert seen_now[:2] == [DFWD, DROWS]
+        assert all(float(t.abs().max()) == 0.0 for t in got), "p = 1: nothing is kept"
+        got, seen_now = run(lambda *lv: pg.additive_attention_dropout(pattern, *lv[:3], c.p, c.slope, **u_kw(lv), seed=_seed(c.seed)))
+        assert seen_now[:2] == [DFWD, DROWS]
+        c.price(*got)
+        assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, "every entry kept with a factor of 1")
+
+
+# ---------------------------------------------------------------------------------------------------------------- reproducible
+@pytest.mark.parametrize("name", case.case_names("twice-"))
+def test_same_seed_same_bits_new_seed_new_mask(name):
+    import pygat_amd as pg
+    c = case.cases()[name]
+    pattern = _pattern(c)
+    runs = [_device_run(pattern, c) for _ in range(2)]
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    c.price(*runs[0])
+    other = _device_run(pattern, c, seed=_seed(c.seed + 1))
+    assert not torch.equal(other[0], runs[0][0]) and not torch.equal(other[1], runs[0][1])
+    # without a seed: one is drawn from the generator -- the same generator state, the same bits
+    leaves = [t.detach() for t in _leaves(c)]
+    gen = torch.Generator(device=DEV)
+    outs = []
+    for s in (3, 3, 4):
+        gen.manual_seed(s)
+        outs.append(pg.additive_attention_dropout(pattern, *leaves[:3], c.p, c.slope, *leaves[3:], generator=gen))
+    assert torch.equal(outs[0], outs[1]) and not torch.equal(outs[0], outs[2])
+
+
+# ---------------------------------------------------------------------------------------------------------- launches and refusals
+def test_only_the_needed_launches(monkeypatch):
+    import pygat_amd as pg
+    seen = _spied(monkeypatch)
+    c = case.cases()["lanes-asym-8x16-indices-logit"]
+    G = c.G.float().to(DEV)
+    tensors = [t.float().to(DEV) for t in c.leaves]
+    seed = _seed(c.seed)
+    pattern = _pattern(c)
+    with torch.no_grad():
+        pg.additive_attention_dropout(pattern, *tensors[:3], 0.5, edge_logit=tensors[3], seed=seed)
+        pg.additive_attention_dropout(pattern, *tensors[:3], 0.5, seed=seed)
+    assert seen == [DFWD, DFWD] and not pattern.has_transpose
+    for needs in itertools.product((False, True), repeat=4):
+        if not any(needs):
+            continue
+        pattern = _pattern(c)                                       # (a fresh one: has it built its transpose?)
+        del seen[:]
+        leaves = [t.clone().requires_grad_(n) for t, n in zip(tensors, needs)]
+        out = pg.additive_attention_dropout(pattern, *leaves[:3], 0.5, c.slope, leaves[3], seed=seed)
+        wanted = [t for t, n in zip(leaves, needs) if n]
+        grads = torch.autograd.grad(out, wanted, G)
+        assert seen == [DFWD, DROWS] + [SPMM] * (needs[1] + needs[2]), (needs, seen)
+        assert pattern.has_transpose == (needs[1] or needs[2]), "neither ds_dst nor du builds the transpose"
+        assert all(g.shape == t.shape for g, t in zip(grads, wanted))
+    # no entries: zeros of the right shape, differentiable, and nothing launched at all
+    empty = pg.EdgePattern.from_indices(torch.zeros(2, 0, dtype=torch.int64, device=DEV), (5, 7))
+    sd, ss, v0 = (torch.randn(*dims, device=DEV, requires_grad=True) for dims in ((5, 2), (7, 2), (7, 2, 8)))
+    for shape in (None, (0, 2), (0,)):
+        u0 = None if shape is None else torch.zeros(shape, device=DEV, requires_grad=True)
+        leaves = [sd, ss, v0] + ([] if u0 is None else [u0])
+        del seen[:]
+        out = pg.additive_attention_dropout(empty, sd, ss, v0, 0.5, 0.2, u0, seed=seed)
+        grads = torch.autograd.grad(out, leaves, torch.ones_like(out))
+        assert out.shape == (5, 2, 8) and float(out.detach().abs().max()) == 0.0
+        assert all(g.shape == t.shape for g, t in zip(grads, leaves)) and all(float(g.abs().sum()) == 0.0 for g in grads)
+        assert seen == [] and not empty.has_transpose, seen
+
+
+def test_refusals(monkeypatch):
+    import pygat_amd as pg
+    seen = _spied(monkeypatch)
+    c = case.cases()["lanes-asym-8x16-indices-plain"]
+    pattern = _pattern(c)
+    N, E = c.shape[0], c.row.numel()
+
+    def t(*dims, **kw):
+        return torch.rand(*dims, device=DEV, **kw)
+    sd, ss, v = t(N, 4), t(N, 4), t(N, 4, 16)
+    seed = _seed(1)
+    elsewhere = copy.copy(pattern)
+    elsewhere.device = torch.device("cuda", 1)                    # (a pattern that says it lives on another device: no second GPU needed)
+    ok = (pattern, sd, ss, v, 0.5)
+    for args, kw, needle in ((((pattern, sd, ss, v.bfloat16(), 0.5)), {}, "no training path on bfloat16"),
+                             ((pattern, sd.bfloat16(), ss, v, 0.5), {}, "no training path on bfloat16"),
+                             ((pattern, sd, ss, v, 1.5), {}, "p = 1.5"), ((pattern, sd, ss, v, -0.5), {}, "p = -0.5"),
+                             ((pattern, sd, ss, v, float("nan")), {}, "p = nan"), ((pattern, sd, ss, v, 2.0), dict(training=False), "p = 2.0"),
+                             (ok, dict(seed=7), "seed must be an int64 tensor of shape [1]"),
+                             (ok, dict(seed=seed.int()), "got torch.int32 (1,)"),
+                             (ok, dict(seed=torch.zeros(2, dtype=torch.int64, device=DEV)), "got torch.int64 (2,)"),
+                             (ok, dict(seed=seed.cpu()), "on cpu"),
+                             ((pattern, sd, ss, v, 0.0), dict(seed=seed.cpu()), "on cpu"),
+                             ((elsewhere, sd, ss, v, 0.5), dict(seed=seed), "cuda:1"),
+                             (ok, dict(negative_slope=float("inf")), "negative_slope = inf"),
+                             ((object(), sd, ss, v, 0.5), {}, "EdgePattern"),
+                             ((pattern, sd.cpu(), ss, v, 0.5), {}, "s_dst must be a tensor on the GPU"),
+                             ((pattern, sd, ss, v.double(), 0.5), {}, "v must be float32"),
+                             ((pattern, sd, ss.half(), v, 0.5), {}, "s_src must be float32"),
+                             ((pattern, sd, ss, t(N, 4, 12), 0.5), {}, "F = 12"),
+                             ((pattern, t(N, 65), t(N, 65), t(N, 65, 4), 0.5), {}, "H = 65"),
+                             ((pattern, t(N, 8), t(N, 8), t(N, 8, 256), 0.5), {}, "H * F = 8 * 256 = 2048"),
+                             ((pattern, sd, ss, t(N + 1, 4, 16), 0.5), {}, f"v has {N + 1} rows but the pattern has {N} columns"),
+                             (ok, dict(edge_logit=t(E, 8)), f"got ({E}, 8)"),
+                             (ok, dict(edge_logit=t(E, 4).double()), "edge_logit must be float32"),
+                             ((pattern, sd, ss, v, 0.0), dict(edge_logit=t(E + 1)), f"got ({E + 1},)"),
+                             (ok, dict(edge_logit=t(E, 4).cpu(), training=False), "edge_logit must be a tensor on the GPU")):
+        with pytest.raises(ValueError, match="additive_attention_dropout: ") as err:
+            pg.additive_attention_dropout(*args, **kw)
+        assert needle in str(err.value), (needle, str(err.value))
+    assert seen == [] and not pattern.has_transpose
+    # an fp64 incoming gradient is refused under this op's name
+    mod = importlib.import_module("pygat_amd.additive_attention")
+    leaves = [x.clone().requires_grad_(True) for x in (sd, ss, v)]
+    out = pg.additive_attention_dropout(pattern, *leaves, 0.5, seed=seed)
+    del seen[:]
+    with pytest.raises(ValueError, match="additive_attention_dropout: the gradient of the output must be float32"):
+        mod._AdditiveAttentionFn.backward(out.grad_fn, torch.ones(N, 4, 16, device=DEV, dtype=torch.float64))
+    assert seen == []
+
+
+# ---------------------------------------------------------------------------------------------------------------- graph capture
+@pytest.mark.parametrize("name", case.case_names("capture-"))
+def test_capture_and_replay_with_a_refilled_seed(name):
+    """Forward and backward captured once under torch.cuda.graph, on one stream; the seed tensor is refilled in place between replays,
+    and every replay gives the eager result of its seed, bit for bit."""
+    import pygat_amd as pg
+    c = case.cases()[name]
+    pattern = _pattern(c)
+    seed = _seed(c.seed)
+    static = _leaves(c)
+    G = c.G.float().to(DEV)
+
+    def step():
+        out = pg.additive_attention_dropout(pattern, *static[:3], c.p, c.slope, *static[3:], seed=seed)
+        return (out,) + torch.autograd.grad(out, static, G)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):                                   # (warm-up off the default stream: the transpose is built here)
+        step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = step()
+    for value in (c.seed, c.seed + 1, c.seed):
+        seed.fill_(value)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = [t.clone() for t in captured]
+        eager = _device_run(pattern, c, seed=_seed(value))
+        for a, b, what in zip(got, eager, ["out"] + c.names):
+            assert torch.equal(a, b), (value, what)
+        if value == c.seed:
+            c.price(got[0], *got[1:])
+
+
+# ------------------------------------------------------------------------------------------------------------------ in a module
+@pytest.mark.parametrize("name", case.case_names("module-"))
+def test_a_bipartite_gat_layer_under_dropout(name):
+    """additive_attention_case's BipartiteGAT with additive_attention_dropout as `attend`: out and the gradients that reach x_src,
+    x_dst, W and a."""
+    import pygat_amd as pg
+    c = case.cases()[name]
+    pattern = _pattern(c)
+    seed = _seed(c.mask_seed)
+    module = c.module(lambda s_dst, s_src, v: pg.additive_attention_dropout(pattern, s_dst, s_src, v, c.p, c.slope, seed=seed)).to(DEV)
+    for n, w in zip(c.NAMES, c.weights):
+        assert torch.equal(module.get_parameter(n).detach().cpu().double(), w)
+    x_src, x_dst = (t.float().to(DEV).requires_grad_(True) for t in (c.x_src, c.x_dst))
+    out = module(x_src, x_dst)
+    out.sum().backward()
+    c.price(out.detach(), x_src.grad, x_dst.grad, *[module.get_parameter(n).grad for n in c.NAMES])
+
+
+# -------------------------------------------------------------------------------------------------------------------- footprint
+def test_dropout_kernels_have_no_scratch():
+    from pygat_amd._lib import lib
+    regs, scratch = C.c_int(-1), C.c_int(-1)
+    assert len(K20D) == 80
+    for name in K20D:
+        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
+        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
+    for bad in (b"k20d_fwd_row_l3v1", b"k20d_fwd_row_l32v2", b"k20du_fwd_row_l64v5", b"k20d_mid_row_l8v1", b"k20du_fwd_row_l8v1x", b"k20d_",
+                b"k20d", b"k20dfwd_row_l8v1", b"k20b_fwd_row_l8v1", b"k20ud_fwd_row_l8v1", b"k20d_col_row_l8v1"):
+        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad

@@ -5,6 +5,9 @@ against the same result from the parts it fuses -- two torch gathers and their s
 
     python tools/additive_attention_bench.py [--shapes 8x16,8x64] [--rounds 5] [--steps 10] [--warmup 10] [--out profiles/additive_attention_bench.jsonl]
     python tools/additive_attention_bench.py --logit [...]      # with an N(0, 1) [E, H] edge_logit that requires a gradient, on both sides
+    python tools/additive_attention_bench.py --dropout [...]    # additive_attention_dropout at p = 0.5: three contenders alternated --
+                                                                # fused with dropout, fused without, the composition with the mask as a
+                                                                # tensor -> profiles/additive_attention_dropout_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
@@ -77,9 +80,9 @@ def composed_backward_bytes(E, N, M, H, F, logit=False):
     return spmm_b + softmax_b + rest
 
 
-def sampled_reference(rp, col, rows, s_dst, s_src, v, slope, dtype, u=None):
+def sampled_reference(rp, col, rows, s_dst, s_src, v, slope, dtype, u=None, mask=None):
     """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of leaky_relu((s_dst_i + s_src_j) + u) (u [E, H],
-    at the CSR position), times v_j."""
+    at the CSR position), times mask (the dropout's, [E, H] at the CSR position, after the softmax), times v_j."""
     import torch
     deg = rp[rows + 1] - rp[rows]
     idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
@@ -93,6 +96,8 @@ def sampled_reference(rp, col, rows, s_dst, s_src, v, slope, dtype, u=None):
     m = torch.full(sd.shape, -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, l.shape[1]), l, "amax")
     p = torch.exp(l - m[sub])
     alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
+    if mask is not None:
+        alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
     return torch.zeros(rows.numel(), v.shape[1], v.shape[2], dtype=dtype).index_add(0, sub, alpha[:, :, None] * vs[inv])
 
 
@@ -147,6 +152,12 @@ def measure(args):
                 return torch.autograd.grad(fn(*mine), mine, G)
             return run
 
+        if args.dropout:
+            measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg,
+                            rows, perm, forward_of, both_of, fused)
+            del s_dst, s_src, v, G, leaves
+            torch.cuda.empty_cache()
+            continue
         # the same seeded inputs, both contenders priced on the sampled rows
         out_f, out_c = forward_of(fused)(), forward_of(composed)()
         ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float64, *leaves[3:])
@@ -182,6 +193,57 @@ def measure(args):
         torch.cuda.empty_cache()
 
 
+def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg, rows,
+                    perm, forward_of, both_of, fused):
+    """--dropout, one shape: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object.  The fused
+    op's algorithmic bytes are those without dropout -- the mask is drawn in registers -- but for the permutation entry the forward now
+    reads where the pattern carries one (4 bytes an entry; this graph's pattern carries none)."""
+    p = 0.5
+    seed = torch.tensor([20240607], dtype=torch.int64, device=dev)
+    N, E = pattern.n_rows, pattern.nnz
+
+    def fused_dropout(sd, ss, v_, u=None):
+        return pg.additive_attention_dropout(pattern, sd, ss, v_, p, slope, u, seed=seed)
+
+    def composed_dropout(sd, ss, v_, u=None):
+        z = sd[row_d] + ss[col_d]
+        if u is not None:
+            z = z + u
+        alpha = pg.edge_softmax(pattern, torch.nn.functional.leaky_relu(z, slope))
+        return pg.spmm(pattern, alpha * pg.attention_dropout_mask(pattern, H, p, seed), v_)
+
+    contenders = {"fused_dropout": fused_dropout, "composed_dropout": composed_dropout, "fused": fused}
+    out_f, out_c = forward_of(fused_dropout)(), forward_of(composed_dropout)()
+    mask = pg.attention_dropout_mask(pattern, H, p, seed)
+    ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float64, *leaves[3:4], mask=mask)
+    ref32 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float32, *leaves[3:4], mask=mask)
+    err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, dropout: out", ref32)
+    err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, dropout: out", ref32)
+    res = {"bench": "additive_attention --dropout" + (" --logit" if args.logit else ""), "device": torch.cuda.get_device_name(0), "p": p,
+           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
+           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+           "longest_checked_row": int(deg[rows].max()), "kept_fraction": float((mask != 0).float().mean()),
+           "out_err_fused_dropout": err_f, "out_err_composed_dropout": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
+           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, args.logit, perm),
+           "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, args.logit, perm),
+           "fused_dropout_extra_forward_bytes": 0 if args.logit or not perm else 4 * E, "mask_tensor_bytes": E * H * 4}
+    del out_f, out_c, mask
+    legs = [("forward", alternate({k: forward_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup))]
+    if not args.forward_only:
+        legs.append(("forward_backward", alternate({k: both_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup)))
+    for what, r in legs:
+        for name in contenders:
+            res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+        res[f"{what}_speedup"] = res[f"composed_dropout_{what}_ms"] / res[f"fused_dropout_{what}_ms"]
+        res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+    print(json.dumps(res), flush=True)
+    print(f"{shape}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged bytes; "
+          f"the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="8x16,8x64")
@@ -193,9 +255,13 @@ def main():
     ap.add_argument("--scale", type=int, default=20)
     ap.add_argument("--draws", type=int, default=5_000_000)
     ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "additive_attention_bench.jsonl"))
+    ap.add_argument("--dropout", action="store_true", help="additive_attention_dropout at p = 0.5 against the op without dropout and "
+                    "the composition with the mask as a tensor")
+    ap.add_argument("--out", default=None, help="profiles/additive_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "additive_attention_dropout_bench.jsonl" if args.dropout else "additive_attention_bench.jsonl")
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]

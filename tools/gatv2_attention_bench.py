@@ -81,9 +81,10 @@ def composed_backward_bytes(E, N, M, H, F):
     return spmm_b + softmax_b + score_b
 
 
-def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype):
+def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype, mask=None):
     """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of a . leaky_relu(x_dst_i + x_src_j), times
-    v_j; the rows a few hundred at a time, so that no [entries, H, F] tensor grows beyond them."""
+    mask (the dropout's, [E, H] at the CSR position, after the softmax), times v_j; the rows a few hundred at a time, so that no
+    [entries, H, F] tensor grows beyond them."""
     import torch
     ad = a.cpu().to(dtype)
     outs = []
@@ -97,6 +98,8 @@ def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype):
         m = torch.full((part.numel(), s.shape[1]), -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
         p = torch.exp(s - m[sub])
         alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
+        if mask is not None:
+            alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
         outs.append(torch.zeros(part.numel(), v.shape[1], v.shape[2], dtype=dtype).index_add(0, sub, alpha[:, :, None] * vs[inv]))
     return torch.cat(outs)
 
@@ -153,9 +156,15 @@ def measure(args):
                     return torch.autograd.grad(fn(*mine), mine, G)
                 return run
 
+            v = leaves[-1] if not shared else x_src
+            if args.dropout:
+                measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, row_d, col_d, rp_t,
+                                col_t, deg, rows, perm, forward_of, both_of, fused)
+                del x_dst, x_src, a, G, leaves, v
+                torch.cuda.empty_cache()
+                continue
             # the same seeded inputs, both contenders priced on the sampled rows
             out_f, out_c = forward_of(fused)(), forward_of(composed)()
-            v = leaves[-1] if not shared else x_src
             ref64 = sampled_reference(rp_t, col_t, rows, x_dst, x_src, a, v, slope, torch.float64)
             ref32 = sampled_reference(rp_t, col_t, rows, x_dst, x_src, a, v, slope, torch.float32)
             err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} {values} fused out", ref32)
@@ -190,6 +199,54 @@ def measure(args):
             torch.cuda.empty_cache()
 
 
+def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, row_d, col_d, rp_t, col_t, deg,
+                    rows, perm, forward_of, both_of, fused):
+    """--dropout, one shape and one kind of v: fused with dropout, fused without, the composition with the mask as a tensor; one JSON
+    object.  The fused op's algorithmic bytes are those without dropout -- the mask is drawn in registers -- but for the permutation
+    entry the forward now reads where the pattern carries one (4 bytes an entry; this graph's pattern carries none)."""
+    p = 0.5
+    seed = torch.tensor([20240607], dtype=torch.int64, device=dev)
+    N, E, shared = pattern.n_rows, pattern.nnz, values == "shared"
+
+    def fused_dropout(xd, xs, a_, v_=None):
+        return pg.gatv2_attention_dropout(pattern, xd, xs, a_, p, v_, slope, seed=seed)
+
+    def composed_dropout(xd, xs, a_, v_=None):
+        e = (a_ * torch.nn.functional.leaky_relu(xd[row_d] + xs[col_d], slope)).sum(-1)
+        return pg.spmm(pattern, pg.edge_softmax(pattern, e) * pg.attention_dropout_mask(pattern, H, p, seed), xs if v_ is None else v_)
+
+    contenders = {"fused_dropout": fused_dropout, "composed_dropout": composed_dropout, "fused": fused}
+    out_f, out_c = forward_of(fused_dropout)(), forward_of(composed_dropout)()
+    mask = pg.attention_dropout_mask(pattern, H, p, seed)
+    ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], v, slope, torch.float64, mask=mask)
+    ref32 = sampled_reference(rp_t, col_t, rows, *leaves[:3], v, slope, torch.float32, mask=mask)
+    err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} {values} fused, dropout: out", ref32)
+    err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} {values} composed, dropout: out", ref32)
+    res = {"bench": "gatv2_attention --dropout", "values": values, "device": torch.cuda.get_device_name(0), "p": p,
+           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
+           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+           "longest_checked_row": int(deg[rows].max()), "kept_fraction": float((mask != 0).float().mean()),
+           "out_err_fused_dropout": err_f, "out_err_composed_dropout": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
+           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, shared),
+           "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, shared, perm),
+           "fused_dropout_extra_forward_bytes": 4 * E if perm else 0, "mask_tensor_bytes": E * H * 4}
+    del out_f, out_c, mask
+    legs = [("forward", alternate({k: forward_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup))]
+    if not args.forward_only:
+        legs.append(("forward_backward", alternate({k: both_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup)))
+    for what, r in legs:
+        for name in contenders:
+            res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+        res[f"{what}_speedup"] = res[f"composed_dropout_{what}_ms"] / res[f"fused_dropout_{what}_ms"]
+        res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+    print(json.dumps(res), flush=True)
+    print(f"{shape} {values}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged "
+          f"bytes; the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="8x16,8x64")
@@ -201,9 +258,13 @@ def main():
     ap.add_argument("--scale", type=int, default=20)
     ap.add_argument("--draws", type=int, default=5_000_000)
     ap.add_argument("--limit", type=int, default=540, help="seconds the measuring child may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gatv2_attention_bench.jsonl"))
+    ap.add_argument("--dropout", action="store_true", help="gatv2_attention_dropout at p = 0.5 against the op without dropout and the "
+                    "composition with the mask as a tensor")
+    ap.add_argument("--out", default=None, help="profiles/gatv2_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "gatv2_attention_dropout_bench.jsonl" if args.dropout else "gatv2_attention_bench.jsonl")
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
