@@ -879,6 +879,34 @@ int pygat_v2_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t* 
                                         uint32_t stream_id, const float* out, int64_t ldo, const float* m, const float* Z,
                                         const float* G, int64_t ldg, float* dx_dst, int64_t lddx, float* P, float* S, void* ws,
                                         void* stream);
+/* The three K21 passes with a feature row per entry inside the score (the EDGE instantiations of the K21 kernels), additive under ABI
+ * 16:
+ *   t[f] = (x_dst[i, h, f] + x_src[j, h, f]) + ee[c(e), h, f], two rounded adds in this order, the same bits in all three launchers;
+ *   g, s, m, Z and out from t as above: ee enters the score alone, out stays the sum over v (PyG's GATv2Conv with edge_dim).
+ * ee = the argument e, [nnz x H*F] floats, a row table like x_src (16-byte aligned, lde >= H*F and a multiple of 4), c(e) the CALLER's
+ * entry index of CSR position e, so the forward takes perm (after col; it may be null: the position itself).  A lane reads its 16
+ * bytes of the entry's row with the gathered rows of the entry.  backward_rows: D, S, P and dx_dst as above, and the gradient of ee,
+ * row-local: de[c(e), h, f] = S a[h, f] (t[f] > 0 ? 1 : negative_slope), the term dx_dst sums over the row, [nnz x H*F] with row
+ * stride ldde, a row table like e.  Every row of de is written exactly once (an entry belongs to one row, in a long row to one
+ * piece): nothing is zeroed or accumulated, no atomics.  de may be null: not asked for, ldde is then not looked at.  backward_cols
+ * takes e beside S (perm_t places both) and forms dx_src and da from the same t; it does not write de.  v == NULL as above.  With ee =
+ * 0 every output has the bits of the launchers without it.  A row of one entry (i, j) gets out_i = v_j bit for bit, S = 0 exactly and
+ * an all-zero row of de.  There is no dropout variant.  Refusals as for the K21 launchers after the launcher's own name; besides: a
+ * null e with nnz > 0, a misaligned e or de, a short or odd lde or ldde, in the words of pygat_dot_attn_edge_forward.  The workspace
+ * and its size query are unchanged. */
+int pygat_v2_attn_edge_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H, int F,
+                               float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds, const float* a,
+                               const float* v, int64_t ldv, const float* e, int64_t lde, float* out, int64_t ldo, float* m, float* Z,
+                               void* ws, void* stream);
+int pygat_v2_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                     int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds,
+                                     const float* a, const float* v, int64_t ldv, const float* e, int64_t lde, const float* out,
+                                     int64_t ldo, const float* m, const float* Z, const float* G, int64_t ldg, float* dx_dst,
+                                     int64_t lddx, float* P, float* S, float* de, int64_t ldde, void* ws, void* stream);
+int pygat_v2_attn_edge_backward_cols(int n_cols, int64_t nnz, const int32_t* rowptr_t, const int32_t* row_t, const int32_t* perm_t,
+                                     int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                     int64_t lds, const float* a, const float* e, int64_t lde, const float* S, float* dx_src,
+                                     int64_t lddx, float* da, void* ws, void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

@@ -1,7 +1,7 @@
 // The kernel skeleton and the launcher tail of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip), K20
 // (k20_additive_attention.hip) and K21 (k21_gatv2_attention.hip), on the lane mapping of da_lanes.h.  A pass is two kernels, a piece
 // kernel for the long rows (one wave per chunk, the rule of long_rows.h) and a row kernel; their bodies are here once, templated on
-// the family, a type (DaFam<variant>, AaFam<LOGIT, DROP>, V2Fam<SHARED, DROP>) that says what a lane group holds of its row and how it
+// the family, a type (DaFam<variant>, AaFam<LOGIT, DROP>, V2Fam<SHARED, DROP, EDGE>) that says what a lane group holds of its row and how it
 // walks it:
 //   forward   Fam::Own<VEC>; Fam::load<VEC>(g, ln, row, own); Fam::KEEP_MZ
 //   backward  Fam::Row<VEC>, a DaGrad<VEC> and the row's own operand; Fam::bwd_load<LPR, VEC>(g, ln, row, r);
@@ -215,6 +215,20 @@ static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
   PYGAT_REQUIRE(d.seed, "%s: null seed", what);
   PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(d.seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
   PYGAT_REQUIRE(make_rng(d.p, d.seed, d.stream_id, rng), "%s: p=%g outside [0, 1]", what, (double)d.p);
+  return PYGAT_OK;
+}
+
+// the per-entry rows of the EDGE launchers of K19 and K21: e, and de where it is asked for, are row tables like the gathered ones,
+// [nnz x H*F] at the caller's entry index; e is non-null where there are entries
+struct DaEdge {
+  const float* e;
+  int64_t lde;
+  float* de;                   // backward rows only; null: not asked for
+  int64_t ldde;
+};
+static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed) {
+  if (nnz > 0 || ed.e) DA_TABLE(what, "e", ed.e, ed.lde, HF);
+  if (ed.de) DA_TABLE(what, "de", ed.de, ed.ldde, HF);
   return PYGAT_OK;
 }
 

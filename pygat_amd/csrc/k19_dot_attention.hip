@@ -417,19 +417,7 @@ static int da_check_bias(const char* what, int64_t nnz, const float* bias, int b
 
 // (the mask of the DROP launchers, DaDrop and da_check_drop: da_family.h, shared with K20 and K21)
 
-// the per-entry rows of the EDGE launchers: e, and de where it is asked for, are row tables like k and v, [nnz x H*F] at the caller's
-// entry index; e is non-null where there are entries
-struct DaEdge {
-  const float* e;
-  int64_t lde;
-  float* de;                   // backward only; null: not asked for
-  int64_t ldde;
-};
-static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed) {
-  if (nnz > 0 || ed.e) DA_TABLE(what, "e", ed.e, ed.lde, HF);
-  if (ed.de) DA_TABLE(what, "de", ed.de, ed.ldde, HF);
-  return PYGAT_OK;
-}
+// (the per-entry rows of the EDGE launchers, DaEdge and da_check_edge: da_family.h, shared with K21)
 
 // what an entry point asks for: its name, the variant and the pass, and every argument under the name include/pygat_amd.h gives it.
 // k and v are float or bf16 rows by the variant; out, m and Z are written by the forward and read by the backward; what a variant or a

@@ -2,7 +2,8 @@
 // side and column side are different tables, for H heads at once, in one pass, and both sides of its gradient.  One kernel family in
 // the shape of K19 and K20: (forward | backward rows | backward columns) x (long | row), instantiated per lane shape; the two row
 // passes also per SHARED, the compile-time flag of v == x_src, and per DROP, that of the seeded dropout of the coefficients
-// (gatv2_attention_dropout); and the two kernels of the staged reduce of da.  The kernels of the two
+// (gatv2_attention_dropout); all three passes per EDGE, that of a feature row per entry inside the score (gatv2_attention_edge); and
+// the two kernels of the staged reduce of da.  The kernels of the two
 // row passes are da_family.h's, shared with K19 and K20, on V2Fam below; the column pass and the reduce of da are written here.
 //
 // Arithmetic.  For an entry e = (i, j) of row i, c(e) its index in the CALLER's order (perm), per head h, feature f:
@@ -23,6 +24,16 @@
 //     undropped softmax's.  mask[c, h] is K19's: element c H + h of the flat layout of k7_dropout.hip's mask kernel on the launcher's
 //     stream id, drawn in registers in both row passes (da_keep_batch, da_lanes.h) -- no mask tensor exists.  backward_rows: S = p (mask
 //     <G, v> - D), P[c, h] = p mask.  The forward then carries c and reads perm.  The column pass reads S alone: one variant serves both.
+//   EDGE: t[f] = (x_dst[i, h, f] + x_src[j, h, f]) + e[c, h, f], two rounded adds in this order, the same bits in all three passes; e
+//     [nnz x H F] is a row table at the CALLER's entry index, and enters the score alone: out is the sum over v as before.  A lane asks
+//     for its 16 bytes of the entry's e row right behind the batch's gather (v2_gather), at the entry index the walk carries -- the
+//     forward carries it too and reads perm, as under DROP.  backward_rows: de[c, h, f] = S a[h, f] g'(t[f]), the term dx_dst sums over
+//     the row, stored by every lane once per entry (16 bytes) where de is asked for: an entry belongs to one row, in a long row to one
+//     piece, so nothing is zeroed or added and there are no atomics.  The column pass forms t with e[c] gathered beside x_dst[i] and
+//     S[c]: it has EDGE kernels of its own, which read g.e and g.lde alone -- DaArgs::de, dbias and ldde hold the da records there.
+//     e = 0: t + 0 is t bit for bit (an exact zero may change its sign, which LeakyReLU and its slope treat alike), so every output has
+//     gatv2_attention's bits.  EDGE goes with SHARED and not with DROP.  The unroll is da_unroll's at every lane shape: no EDGE kernel
+//     spills at it (the e rows are one more gathered row per entry, and the widest lane shapes hold one or two entries in flight).
 //
 // Lane mapping: K19's (da_lanes.h).  Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  A group of LPR
 // lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane; the chunks of a head sit on LH = F / 4 adjacent lanes of one
@@ -63,8 +74,8 @@ namespace pygat {
 //                 dbias = those of the column kernel (one per wave),  ldde = H F
 constexpr int V2_DA_STAGE = 128;               // partial sums between the da records and da
 
-// entries in flight: da_unroll's values
-__host__ __device__ constexpr int v2_unroll(bool bwd, int vec) { return da_unroll(bwd, vec); }
+// entries in flight: da_unroll's values, under EDGE too (no kernel of the family uses scratch at them)
+__host__ __device__ constexpr int v2_unroll(bool bwd, int vec, bool /*edge*/) { return da_unroll(bwd, vec); }
 
 __device__ __forceinline__ float4 v2_t(const float4& x, const float4& y) {
   return make_float4(__fadd_rn(x.x, y.x), __fadd_rn(x.y, y.y), __fadd_rn(x.z, y.z), __fadd_rn(x.w, y.w));
@@ -97,10 +108,30 @@ __device__ __forceinline__ float v2_score(const DaArgs& g, const float4& a, cons
   return da_head_sum<LPR>(dot4(a, v2_leaky(t, g.scale)), g.LH);
 }
 
+// the entry index a walk carries: c(e) H, the place of the entry's scalars (da_entry); under EDGE c(e) itself, which places the
+// entry's rows of e and de, and v2_scalars turns it into the place of the scalars
+template <bool EDGE>
+__device__ __forceinline__ int64_t v2_entry(const DaArgs& g, int64_t pos) {
+  if constexpr (EDGE) return g.perm ? (int64_t)g.perm[pos] : pos;
+  else return da_entry(g, pos);
+}
+template <bool EDGE>
+__device__ __forceinline__ int64_t v2_scalars(const DaArgs& g, int64_t ent) {
+  if constexpr (EDGE) return ent * g.H;
+  else return ent;
+}
+
 // U gathered entries, loaded before any is used.  MODE 0: forward, 1: backward rows (x = x_src[j]; v = v[j] without SHARED), 2: the
-// column pass (x = x_dst[i]; s = S[c, head of the chunk slot])
-template <int VEC, int U, int MODE, bool SHARED>
-struct V2Rows {
+// column pass (x = x_dst[i]; s = S[c, head of the chunk slot]).  EDGE: e = e[c], the entry's own row.  t: the argument of LeakyReLU
+// from the walked side's own row, x_dst + x_src first and e behind it in every pass
+template <int VEC, int U, bool EDGE>
+struct V2EdgeRows {
+  float4 e[U][VEC];
+};
+template <int VEC, int U>
+struct V2EdgeRows<VEC, U, false> {};         // (an empty base: without EDGE the struct is what it was)
+template <int VEC, int U, int MODE, bool SHARED, bool EDGE>
+struct V2Rows : V2EdgeRows<VEC, U, EDGE> {
   static constexpr bool SEP = MODE != 2 && !SHARED;
   float4 x[U][VEC];
   float4 v[SEP ? U : 1][SEP ? VEC : 1];
@@ -109,17 +140,23 @@ struct V2Rows {
     if constexpr (SEP) return v[u][c];
     else return x[u][c];
   }
+  __device__ __forceinline__ float4 t(const float4& own, int u, int c) const {
+    if constexpr (EDGE) return v2_t(MODE == 2 ? v2_t(x[u][c], own) : v2_t(own, x[u][c]), this->e[u][c]);
+    else if constexpr (MODE == 2) return v2_t(x[u][c], own);
+    else return v2_t(own, x[u][c]);
+  }
 };
-template <int VEC, int U, int MODE, bool SHARED>
+template <int VEC, int U, int MODE, bool SHARED, bool EDGE>
 __device__ __forceinline__ void v2_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], const int64_t (&ent)[U],
-                                          V2Rows<VEC, U, MODE, SHARED>& w) {
+                                          V2Rows<VEC, U, MODE, SHARED, EDGE>& w) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     da_load_row<VEC>(g.k + (int64_t)src[u] * g.ldk, ln, w.x[u]);
     if constexpr (MODE != 2 && !SHARED) da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+    if constexpr (EDGE) da_load_row<VEC>(g.e + ent[u] * g.lde, ln, w.e[u]);
     if constexpr (MODE == 2) {
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) w.s[u][v] = g.S[ent[u] + ln.head[v]];
+      for (int v = 0; v < VEC; ++v) w.s[u][v] = g.S[v2_scalars<EDGE>(g, ent[u]) + ln.head[v]];
     }
   }
 }
@@ -135,11 +172,12 @@ template <bool DROP> using V2Key = std::conditional_t<DROP, uint2, DaNoKey>;
 
 // ------------------------------------------------------------------------------------------------------------------------ forward
 // ent is looked at under DROP alone: ent[u] + head is the entry's flat mask index, and (p keep) v goes into acc while Z takes p whole
-template <int LPR, int VEC, bool SHARED, bool DROP>
+// (under EDGE the gather has used it already)
+template <int LPR, int VEC, bool SHARED, bool DROP, bool EDGE>
 struct V2FwdFold {
   template <int U>
   __device__ __forceinline__ static void fold(const DaArgs& g, [[maybe_unused]] const DaLane<VEC>& ln, [[maybe_unused]] V2Key<DROP> key,
-                                              const V2Own<VEC>& r, DaState<VEC>& st, const V2Rows<VEC, U, 0, SHARED>& w,
+                                              const V2Own<VEC>& r, DaState<VEC>& st, const V2Rows<VEC, U, 0, SHARED, EDGE>& w,
                                               [[maybe_unused]] const int64_t (&ent)[U]) {
     [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
     if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
@@ -147,7 +185,7 @@ struct V2FwdFold {
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        const float s = v2_score<LPR>(g, r.a[v], v2_t(r.x[v], w.x[u][v]));
+        const float s = v2_score<LPR>(g, r.a[v], w.t(r.x[v], u, v));
         da_fold<false, DROP>(st.m[v], st.z[v], st.acc[v], s, 0.f, DROP ? keep[u][v] : 1.f, w.val(u, v));
       }
   }
@@ -165,11 +203,13 @@ struct V2BwdRow : DaGrad<VEC> {   // what the backward holds of its row
 // row term of the dropped sum already -- and the stored P is p keep, what the transposed SpMM of dv multiplies G with; the column pass
 // reads S alone and is the same launch with and without dropout.  In a row of one entry out_i is keep v_j bit for bit; S is an exact
 // zero where the entry is dropped and where keep is a power of two, and otherwise a rounding of keep dp against one of D
-template <int LPR, int VEC, bool SHARED, bool DROP>
+// EDGE: ent[u] is c(e) itself; every lane also stores its chunk of de[c(e)] = S a g'(t), the term of dx_dst, where de is asked for.  In
+// a row of one entry S is an exact zero and so is the row of de
+template <int LPR, int VEC, bool SHARED, bool DROP, bool EDGE>
 struct V2BwdFold {
   template <int U>
   __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>& ln, [[maybe_unused]] V2Key<DROP> key,
-                                              const V2BwdRow<VEC>& r, float4 (&dx)[VEC], const V2Rows<VEC, U, 1, SHARED>& w,
+                                              const V2BwdRow<VEC>& r, float4 (&dx)[VEC], const V2Rows<VEC, U, 1, SHARED, EDGE>& w,
                                               const int64_t (&ent)[U]) {
     [[maybe_unused]] float keep[DROP ? U : 1][DROP ? VEC : 1];
     if constexpr (DROP) da_keep_batch<VEC, U>(g, ln, key, ent, keep);
@@ -177,7 +217,7 @@ struct V2BwdFold {
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        const float4 t = v2_t(r.own.x[v], w.x[u][v]);
+        const float4 t = w.t(r.own.x[v], u, v);
         const float s = v2_score<LPR>(g, r.own.a[v], t);
         const float p = __expf(s - r.m[v]) * r.rz[v];
         float dp = da_head_sum<LPR>(dot4(r.G[v], w.val(u, v)), g.LH);
@@ -189,19 +229,28 @@ struct V2BwdFold {
         const float S = p * (dp - r.D[v]);
         v2_dside(dx[v], S, r.own.a[v], t, g.scale);
         if (ln.lead >> v & 1) {
-          g.P[ent[u] + ln.head[v]] = pk;
-          g.S[ent[u] + ln.head[v]] = S;
+          g.P[v2_scalars<EDGE>(g, ent[u]) + ln.head[v]] = pk;
+          g.S[v2_scalars<EDGE>(g, ent[u]) + ln.head[v]] = S;
         }
+        if constexpr (EDGE)
+          if (g.de && (ln.ok >> v & 1)) {
+            const float4& a = r.own.a[v];
+            const float cs = S * g.scale;
+            st4(g.de + ent[u] * g.ldde + ln.ofs[v], make_float4((t.x > 0.f ? S : cs) * a.x, (t.y > 0.f ? S : cs) * a.y,
+                                                                (t.z > 0.f ? S : cs) * a.z, (t.w > 0.f ? S : cs) * a.w));
+          }
       }
   }
 };
 
-template <int VEC>
+template <int VEC, bool EDGE>
 struct V2ColFold;
 
-// the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED and DROP (the column pass: without either)
-template <bool SHARED, bool DROP = false>
+// the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED, DROP and EDGE (the column pass: per
+// EDGE alone)
+template <bool SHARED, bool DROP = false, bool EDGE = false>
 struct V2Fam {
+  static_assert(!(DROP && EDGE), "EDGE does not combine with DROP");
   static constexpr bool KEEP_MZ = true;
   template <int VEC> using Own = V2Own<VEC>;
   template <int VEC> using Row = V2BwdRow<VEC>;
@@ -219,15 +268,16 @@ struct V2Fam {
   // order, U at a time and then one at a time.  The indices of the next U entries -- the other side's row and, in the backward passes,
   // the caller's entry index (da_entry) -- are asked for before this batch's gather is used, so an iteration waits for one gather, not
   // for an index and then a gather.  The forward carries no entry index and does not touch perm -- except under DROP, where the entry
-  // index places the draws: its forward forms it as the backward passes do (ENT).  key: the key of the draws under DROP, by value.
+  // index places the draws, and under EDGE, where it places the e rows: its forward forms it as the backward passes do (ENT).  key:
+  // the key of the draws under DROP, by value.
   template <int LPR, int VEC, int MODE, typename... Ctx>
   __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
                                                 V2Key<DROP> key, Ctx&... ctx) {
     static_assert(MODE != 2 || !DROP, "the column pass reads S alone: it has no DROP variant");
-    using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED, DROP>,
-                                    std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED, DROP>, V2ColFold<VEC>>>;
-    constexpr int U = v2_unroll(MODE != 0, VEC);
-    constexpr bool ENT = MODE != 0 || DROP;
+    using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED, DROP, EDGE>,
+                                    std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED, DROP, EDGE>, V2ColFold<VEC, EDGE>>>;
+    constexpr int U = v2_unroll(MODE != 0, VEC, EDGE);
+    constexpr bool ENT = MODE != 0 || DROP || EDGE;
     int64_t e = e0;
     if constexpr (U > 1) {
       int32_t src[U];
@@ -239,7 +289,7 @@ struct V2Fam {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = g.col[e + u * step];
-          if constexpr (ENT) ent_next[u] = da_entry(g, e + u * step);
+          if constexpr (ENT) ent_next[u] = v2_entry<EDGE>(g, e + u * step);
         }
       }
       while (full) {
@@ -247,15 +297,15 @@ struct V2Fam {
 #pragma unroll
           for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
         }
-        V2Rows<VEC, U, MODE, SHARED> w;
-        v2_gather<VEC, U, MODE, SHARED>(g, ln, src, ent, w);
+        V2Rows<VEC, U, MODE, SHARED, EDGE> w;
+        v2_gather<VEC, U, MODE, SHARED, EDGE>(g, ln, src, ent, w);
         e += U * step;
         full = e + (U - 1) * step < e1;
         if (full) {
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             src[u] = g.col[e + u * step];
-            if constexpr (ENT) ent_next[u] = da_entry(g, e + u * step);
+            if constexpr (ENT) ent_next[u] = v2_entry<EDGE>(g, e + u * step);
           }
         }
         Fold::fold(g, ln, key, ctx..., w, ent);
@@ -264,9 +314,9 @@ struct V2Fam {
     for (; e < e1; e += step) {
       const int32_t src[1] = {g.col[e]};
       int64_t ent[1] = {0};
-      if constexpr (ENT) ent[0] = da_entry(g, e);
-      V2Rows<VEC, 1, MODE, SHARED> w;
-      v2_gather<VEC, 1, MODE, SHARED>(g, ln, src, ent, w);
+      if constexpr (ENT) ent[0] = v2_entry<EDGE>(g, e);
+      V2Rows<VEC, 1, MODE, SHARED, EDGE> w;
+      v2_gather<VEC, 1, MODE, SHARED, EDGE>(g, ln, src, ent, w);
       Fold::fold(g, ln, key, ctx..., w, ent);
     }
   }
@@ -279,18 +329,18 @@ struct V2Fam {
 
 // ---------------------------------------------------------------------------------------------------------- backward, column side
 // the column pass's fold of a batch; ctx: the column's own row and a (V2Own), the lane's chunks of dx_src, of da and of da's
-// compensation
-template <int VEC>
+// compensation.  EDGE: t is the row pass's, e[c] behind x_dst[i] + x_src[j]
+template <int VEC, bool EDGE>
 struct V2ColFold {
   template <int U>
   __device__ __forceinline__ static void fold(const DaArgs& g, const DaLane<VEC>&, DaNoKey, const V2Own<VEC>& r, float4 (&dx)[VEC],
-                                              float4 (&da)[VEC], float4 (&dc)[VEC], const V2Rows<VEC, U, 2, false>& w,
+                                              float4 (&da)[VEC], float4 (&dc)[VEC], const V2Rows<VEC, U, 2, false, EDGE>& w,
                                               const int64_t (&)[U]) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        const float4 t = v2_t(w.x[u][v], r.x[v]);              // x_dst[i] + x_src[j], the row pass's t
+        const float4 t = w.t(r.x[v], u, v);                    // x_dst[i] + x_src[j] (+ e[c]), the row pass's t
         const float S = w.s[u][v];
         v2_dside(dx[v], S, r.a[v], t, g.scale);
         v2_da_add(da[v], dc[v], S, v2_leaky(t, g.scale));
@@ -307,7 +357,7 @@ __device__ __forceinline__ void v2_settle(float4 (&s)[VEC], const float4 (&c)[VE
 
 // launch 1: one wave per chunk of the transposed pattern; the piece of every long column inside the chunk -> one partial record, the
 // H F sums of dx_src; the wave's da of all its pieces -> da record `chunk`
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool EDGE>
 __global__ __launch_bounds__(64) void v2_col_long_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, grp = lane / LPR;
@@ -323,7 +373,7 @@ __global__ __launch_bounds__(64) void v2_col_long_kernel(DaArgs g) {
     da_load_row<VEC>(g.bias, ln, r.a);
     float4 dx[VEC];
     da_zero_row<VEC>(dx);
-    V2Fam<false>::walk<LPR, VEC, 2>(g, ln, e0 + grp, e1, EPW, false, DaNoKey{}, r, dx, da, dc);
+    V2Fam<false, false, EDGE>::template walk<LPR, VEC, 2>(g, ln, e0 + grp, e1, EPW, false, DaNoKey{}, r, dx, da, dc);
     da_wave_sum<LPR, VEC>(dx);
     if (grp == 0) da_store_row<VEC>(g.part + long_record(blockIdx.x, slot) * g.pstride, ln, dx);
   });
@@ -345,7 +395,7 @@ __device__ __forceinline__ int v2_first_at(const int32_t* rowptr, int n, int64_t
 // launch 2: one work-group per chunk of LONG_CHUNK entries: the columns that begin inside the chunk (the last work-group: from its
 // chunk on, the columns without entries at the end among them), a lane group every (lane groups of the work-group)-th of them, so a
 // wave's da stays in registers over all its columns and leaves one record
-template <int LPR, int VEC>
+template <int LPR, int VEC, bool EDGE>
 __global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / LPR;
@@ -372,7 +422,7 @@ __global__ __launch_bounds__(256) void v2_col_row_kernel(DaArgs g) {
       });
     } else if (end > start) {
       da_load_row<VEC>(g.q + row * g.ldq, ln, r.x);
-      V2Fam<false>::walk<LPR, VEC, 2>(g, ln, start, end, 1, false, DaNoKey{}, r, dx, da, dc);
+      V2Fam<false, false, EDGE>::template walk<LPR, VEC, 2>(g, ln, start, end, 1, false, DaNoKey{}, r, dx, da, dc);
     }
     da_store_row<VEC>(g.dq + row * g.lddq, ln, dx);
   }
@@ -406,45 +456,48 @@ __global__ __launch_bounds__(256) void v2_da_final_kernel(int R, const float* __
   da[c] = acc;
 }
 
-// the table of the family: (SHARED, forward | backward rows | columns, long | row, lane shape) -> the kernel.  What a launcher starts
-// and what pygat_kernel_footprint reports on both come from here.  pass: 0 forward, 1 backward rows, 2 columns (no SHARED variant)
-template <int LPR, int VEC, bool SHARED, bool DROP>
+// the table of the family: (SHARED, DROP, EDGE, forward | backward rows | columns, long | row, lane shape) -> the kernel.  What a
+// launcher starts and what pygat_kernel_footprint reports on both come from here.  pass: 0 forward, 1 backward rows, 2 columns (per
+// EDGE alone)
+template <int LPR, int VEC, bool SHARED, bool DROP, bool EDGE>
 static const void* v2_kernel_at(int pass, bool lng) {
-  if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC>)
-                            : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC>);
-  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED, DROP>, LPR, VEC>)
-                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED, DROP>, LPR, VEC>);
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED, DROP>, LPR, VEC>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED, DROP>, LPR, VEC>);
+  if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC, EDGE>)
+                            : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC, EDGE>);
+  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>)
+                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>);
 }
-template <bool SHARED, bool DROP>
+template <bool SHARED, bool DROP, bool EDGE>
 static const void* v2_kernel_of(int pass, bool lng, int lpr, int vec) {
-  PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, SHARED, DROP>(pass, lng)));
+  PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, SHARED, DROP, EDGE>(pass, lng)));
   return nullptr;
 }
-// (the column pass has one variant: whatever is asked for, the kernels without a flag)
-static const void* v2_kernel(bool shared, bool drop, int pass, bool lng, int lpr, int vec) {
-  if (pass == 2) return v2_kernel_of<false, false>(pass, lng, lpr, vec);
-  if (drop) return shared ? v2_kernel_of<true, true>(pass, lng, lpr, vec) : v2_kernel_of<false, true>(pass, lng, lpr, vec);
-  return shared ? v2_kernel_of<true, false>(pass, lng, lpr, vec) : v2_kernel_of<false, false>(pass, lng, lpr, vec);
+// (the column pass has one variant per EDGE: whatever else is asked for, the kernels without SHARED and DROP; EDGE is without DROP)
+static const void* v2_kernel(bool shared, bool drop, bool edge, int pass, bool lng, int lpr, int vec) {
+  if (pass == 2) return edge ? v2_kernel_of<false, false, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, false>(pass, lng, lpr, vec);
+  if (edge) return shared ? v2_kernel_of<true, false, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, true>(pass, lng, lpr, vec);
+  if (drop) return shared ? v2_kernel_of<true, true, false>(pass, lng, lpr, vec) : v2_kernel_of<false, true, false>(pass, lng, lpr, vec);
+  return shared ? v2_kernel_of<true, false, false>(pass, lng, lpr, vec) : v2_kernel_of<false, false, false>(pass, lng, lpr, vec);
 }
 
 // pygat_kernel_footprint: <prefix>{fwd,bwd,col}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k21_: a v table of its
 // own, k21s_: SHARED, k21d_: DROP, k21ds_: DROP and SHARED (fwd and bwd only: the column pass has one variant, under k21_);
-// k21_da_stage, k21_da_final: the reduce of da
+// k21e_: EDGE, with a column pass of its own, k21es_: EDGE and SHARED (fwd and bwd only); k21_da_stage, k21_da_final: the reduce of da
 int footprint_k21(const char* name, int* regs, int* scratch) {
-  static const struct { const char* prefix; bool shared, drop; } names[] = {
-      {"k21_", false, false}, {"k21s_", true, false}, {"k21d_", false, true}, {"k21ds_", true, true}};
+  static const struct { const char* prefix; bool shared, drop, edge; } names[] = {
+      {"k21_", false, false, false}, {"k21s_", true, false, false}, {"k21d_", false, true, false}, {"k21ds_", true, true, false},
+      {"k21e_", false, false, true}, {"k21es_", true, false, true}};
   const void* fn = nullptr;
   if (!strcmp(name, "k21_da_stage")) fn = reinterpret_cast<const void*>(&v2_da_stage_kernel);
   if (!strcmp(name, "k21_da_final")) fn = reinterpret_cast<const void*>(&v2_da_final_kernel);
   DaKernelName k;
   for (const auto& nm : names)
     if (!fn && da_parse_kernel_name(name, nm.prefix, &k) && (k.pass != 2 || !(nm.shared || nm.drop)))
-      fn = v2_kernel(nm.shared, nm.drop, k.pass, k.lng, k.lpr, k.vec);
+      fn = v2_kernel(nm.shared, nm.drop, nm.edge, k.pass, k.lng, k.lpr, k.vec);
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (k21{,s,d,ds}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, k21_col_{long,row}_l<LPR>v<VEC>, "
-              "k21_da_stage, k21_da_final)", name);
+    set_error("kernel_footprint: unknown kernel '%s' (k21{,s,d,ds,e,es}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, "
+              "k21{,e}_col_{long,row}_l<LPR>v<VEC>, k21_da_stage, k21_da_final)", name);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
@@ -487,6 +540,8 @@ struct V2Call {
   void *ws, *stream;
   bool dropout;                // the DROP kernels of the two row passes, on the mask of drop
   DaDrop drop;
+  bool edge;                   // the EDGE kernels of all three passes, on the rows of ed (de: the row pass's alone)
+  DaEdge ed;
 };
 
 // all three launchers: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
@@ -526,6 +581,10 @@ static int v2_launch(const V2Call& c) {
     PYGAT_REQUIRE(c.da, "%s: null da", what);
     PYGAT_REQUIRE(aligned16(c.da), "%s: da must be 16-byte aligned", what);
   }
+  if (c.edge) {
+    const int re = da_check_edge(what, c.nnz, HF, c.ed);
+    if (re != PYGAT_OK) return re;
+  }
   DropRng rng;
   if (c.dropout) {
     const int rd = da_check_drop(what, c.drop, &rng);
@@ -544,6 +603,8 @@ static int v2_launch(const V2Call& c) {
   if (c.pass != 0) { g.perm = c.perm; g.dq = c.dx; g.lddq = c.lddx; g.S = c.S; }   // (the forward walks in CSR order alone)
   if (c.pass == 1) { g.G = c.G; g.ldg = c.ldg; g.P = c.P; }
   if (c.dropout) { g.perm = c.perm; g.rng = rng; }                                 // (... but for the draws: its entry index places them)
+  if (c.edge) { g.perm = c.perm; g.e = c.ed.e; g.lde = c.ed.lde; }                 // (... and for the e rows)
+  if (c.edge && c.pass == 1) { g.de = c.ed.de; g.ldde = c.ed.ldde; }               // (the column pass: de and ldde are the da records')
   DaGrid gd = da_grid(c.n, c.nnz, c.H, c.F);
   float* stage = nullptr;
   if (cols) {
@@ -555,8 +616,8 @@ static int v2_launch(const V2Call& c) {
   }
   hipStream_t st = (hipStream_t)c.stream;
   const bool shared = !cols && !c.v;
-  da_launch_pair(v2_kernel(shared, c.dropout, c.pass, true, gd.lpr, gd.vec), v2_kernel(shared, c.dropout, c.pass, false, gd.lpr, gd.vec),
-                 g, gd.chunks, gd.blocks, c.stream);
+  da_launch_pair(v2_kernel(shared, c.dropout, c.edge, c.pass, true, gd.lpr, gd.vec),
+                 v2_kernel(shared, c.dropout, c.edge, c.pass, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks, c.stream);
   if (cols) {
     const int nrec = (int)(gd.chunks + 4 * gd.blocks);
     hipLaunchKernelGGL(v2_da_stage_kernel, dim3(V2_DA_STAGE), dim3(256), 0, st, HF, nrec, (const float*)g.de, stage);
@@ -640,5 +701,45 @@ extern "C" int pygat_v2_attn_backward_cols(int n_cols, int64_t nnz, const int32_
   c.what = "v2_attn_backward_cols"; c.pass = 2; c.n = n_cols; c.nnz = nnz; c.rowptr = rowptr_t; c.col = row_t; c.perm = perm_t;
   c.H = H; c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a;
   c.S = const_cast<float*>(S); c.dx = dx_src; c.lddx = lddx; c.da = da; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}
+
+// all three passes with a feature row per entry inside the score (the EDGE instantiations): t = (x_dst_i + x_src_j) + e_c, e [nnz x
+// H*F] at the CALLER's entry index.  The forward takes perm: the entry index places the rows of e.  backward_rows writes de where it is
+// asked for (a null de: not asked for); backward_cols reads e beside S
+extern "C" int pygat_v2_attn_edge_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                          int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src, int64_t lds,
+                                          const float* a, const float* v, int64_t ldv, const float* e, int64_t lde, float* out,
+                                          int64_t ldo, float* m, float* Z, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_edge_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
+  c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
+  c.out = out; c.ldo = ldo; c.m = m; c.Z = Z; c.ws = ws; c.stream = stream; c.edge = true; c.ed = {e, lde, nullptr, 0};
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_edge_backward_rows(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                                int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
+                                                int64_t lds, const float* a, const float* v, int64_t ldv, const float* e, int64_t lde,
+                                                const float* out, int64_t ldo, const float* m, const float* Z, const float* G,
+                                                int64_t ldg, float* dx_dst, int64_t lddx, float* P, float* S, float* de, int64_t ldde,
+                                                void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_edge_backward_rows"; c.pass = 1; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
+  c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v;
+  c.ldv = ldv; c.out = const_cast<float*>(out); c.ldo = ldo; c.m = const_cast<float*>(m); c.Z = const_cast<float*>(Z); c.G = G;
+  c.ldg = ldg; c.dx = dx_dst; c.lddx = lddx; c.P = P; c.S = S; c.ws = ws; c.stream = stream; c.edge = true; c.ed = {e, lde, de, ldde};
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_edge_backward_cols(int n_cols, int64_t nnz, const int32_t* rowptr_t, const int32_t* row_t,
+                                                const int32_t* perm_t, int H, int F, float negative_slope, const float* x_dst,
+                                                int64_t ldd, const float* x_src, int64_t lds, const float* a, const float* e, int64_t lde,
+                                                const float* S, float* dx_src, int64_t lddx, float* da, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_edge_backward_cols"; c.pass = 2; c.n = n_cols; c.nnz = nnz; c.rowptr = rowptr_t; c.col = row_t; c.perm = perm_t;
+  c.H = H; c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a;
+  c.S = const_cast<float*>(S); c.dx = dx_src; c.lddx = lddx; c.da = da; c.ws = ws; c.stream = stream; c.edge = true;
+  c.ed = {e, lde, nullptr, 0};
   return v2_launch(c);
 }

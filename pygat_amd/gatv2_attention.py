@@ -12,6 +12,8 @@
     out = spmm(pattern, edge_softmax(pattern, e), x_src)
     out = gatv2_attention_dropout(pattern, x_dst, x_src, a, 0.6, training=self.training)    # training: dropout p on the coefficients, after
                                                                 # the softmax, drawn in the kernels from a seed on the device
+    out = gatv2_attention_edge(pattern, x_dst, x_src, a, lin_edge(edge_attr).view(E, H, F))    # edge features inside the score, before
+                                                                # LeakyReLU (PyG's GATv2Conv with edge_dim); differentiable in e too
 
 The nonlinearity sits inside the sum over the features, so the score needs a whole F-wide row per entry and cannot be written as
 additive_attention's sum of two per-node scalars.  A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate
@@ -29,12 +31,13 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
+from .dot_attention import _E_WANT, _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
 from .dropout import STREAM_ATT
 from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "gatv2_attention"
 _OP_DROP = "gatv2_attention_dropout"
+_OP_EDGE = "gatv2_attention_edge"
 _PAD_HINT = ("zero-pad the columns of all four tensors (x_dst, x_src, a and v) to the next allowed F: zero columns of a add nothing "
              "to a score, and the first F columns of the result are unchanged")
 
@@ -66,20 +69,41 @@ def _workspace(pattern, H: int, F: int, dev):
     return torch.empty(_lib.v2_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=dev)
 
 
+def _checked_e(pattern, x_dst, e, op: str = _OP_EDGE):
+    """The refusals of e's shape, after _checked: a row per entry, shaped like a row of x_dst."""
+    if tuple(e.shape) != (pattern.nnz,) + tuple(x_dst.shape[1:]):
+        raise ValueError(f"pygat_amd {op}: e {[pattern.nnz] + list(x_dst.shape[1:])} expected for E = {pattern.nnz} entries and x_dst "
+                         f"{tuple(x_dst.shape)} -- (E,) + x_dst.shape[1:], a row per entry -- got {tuple(e.shape)}")
+
+
+def _edge_rows(e, HF: int):
+    """e as the launchers take it -> (tensor, leading dimension): the tensor itself where its rows are H * F dense floats a multiple
+    of 4 floats apart and 16-byte aligned (a column slice of a wider tensor: no copy), a contiguous copy otherwise."""
+    e = e.detach()
+    inner = e.dim() == 2 or e.shape[1] == 1 or e.stride(1) == e.shape[2]
+    if e.shape[0] > 1 and e.stride(-1) == 1 and inner and e.stride(0) >= HF and e.stride(0) % 4 == 0 and e.data_ptr() % 16 == 0:
+        return e, e.stride(0)
+    return e.contiguous(), HF
+
+
 class _Gatv2AttentionFn(torch.autograd.Function):
-    """gatv2_attention and gatv2_attention_dropout.  shared: v is x_src (the op's v=None).  The tensor arrives in both places all the
-    same, so autograd adds the two parts of its gradient -- the score's (the column pass) and the value's (the transposed SpMM) -- and
-    the kernels get a null v.  drop: None or (p, seed) of gatv2_attention_dropout: the mask of the coefficients, drawn in the kernels of
-    the two row passes from the int64 [1] seed tensor on the device; the column pass reads S alone and is the same launch."""
+    """gatv2_attention, gatv2_attention_dropout and gatv2_attention_edge.  shared: v is x_src (the op's v=None).  The tensor arrives
+    in both places all the same, so autograd adds the two parts of its gradient -- the score's (the column pass) and the value's (the
+    transposed SpMM) -- and the kernels get a null v.  drop: None or (p, seed) of gatv2_attention_dropout: the mask of the coefficients,
+    drawn in the kernels of the two row passes from the int64 [1] seed tensor on the device; the column pass reads S alone and is the
+    same launch.  e: None or the [E, H, F] rows of gatv2_attention_edge, which all three passes read (the EDGE entry points); not with
+    drop."""
 
     @staticmethod
-    def forward(ctx, pattern, x_dst, x_src, a, v, slope, shared, drop=None):
-        op = _OP if drop is None else _OP_DROP
+    def forward(ctx, pattern, x_dst, x_src, a, v, slope, shared, drop=None, e=None):
+        op = _OP_EDGE if e is not None else _OP if drop is None else _OP_DROP
         H, F = _checked(pattern, x_dst, x_src, a, v, op)
+        if e is not None:
+            _checked_e(pattern, x_dst, e, op)
         p, seed = (None, None) if drop is None else drop
         ctx.pattern, ctx.slope, ctx.hf, ctx.shared, ctx.op, ctx.p = pattern, slope, (H, F), shared, op, p
         if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
-            ctx.save_for_backward(x_dst, x_src, a, v, None, None, None, None)
+            ctx.save_for_backward(x_dst, x_src, a, v, None, None, None, None, e)
             return torch.zeros_like(x_dst)
         xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src, a))
         vc = None if shared else v.detach().contiguous()
@@ -90,29 +114,35 @@ class _Gatv2AttentionFn(torch.autograd.Function):
             ws = _workspace(pattern, H, F, dev)
             tables = (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF)
             rest = (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream())
-            if drop is None:                                       # (the forward without dropout walks in CSR order alone)
+            if e is not None:                                      # (the entry index places the rows of e: perm)
+                ec, lde = _edge_rows(e, HF)
+                check(lib.pygat_v2_attn_edge_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
+                                                     *tables, _ptr(ec), lde, *rest), "v2_attn_edge_forward")
+            elif drop is None:                                     # (the forward without dropout walks in CSR order alone)
                 check(lib.pygat_v2_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), *tables, *rest),
                       "v2_attn_forward")
             else:
                 check(lib.pygat_v2_attn_dropout_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
                                                         *tables, p, _ptr(seed), STREAM_ATT, *rest), "v2_attn_dropout_forward")
         out = out.view(x_dst.shape)
-        ctx.save_for_backward(x_dst, x_src, a, v, out, m, Z, seed)
+        ctx.save_for_backward(x_dst, x_src, a, v, out, m, Z, seed, e)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        x_dst, x_src, a, v, out, m, Z, seed = ctx.saved_tensors
+        x_dst, x_src, a, v, out, m, Z, seed, e = ctx.saved_tensors
         pattern, slope, (H, F), shared = ctx.pattern, ctx.slope, ctx.hf, ctx.shared
         if G.dtype != torch.float32:
             raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_d, need_s, need_a, need_v = ctx.needs_input_grad[1:5]
-        if not (need_d or need_s or need_a or need_v):
-            return (None,) * 8
+        need_e = e is not None and ctx.needs_input_grad[8]
+        if not (need_d or need_s or need_a or need_v or need_e):
+            return (None,) * 9
         if out is None:                                            # no entries: zeros, nothing launched
             return (None,) + tuple(torch.zeros_like(t) if need else None
-                                   for t, need in ((x_dst, need_d), (x_src, need_s), (a, need_a), (v, need_v))) + (None, None, None)
+                                   for t, need in ((x_dst, need_d), (x_src, need_s), (a, need_a), (v, need_v))) + (
+                                       None, None, None, torch.zeros_like(e) if need_e else None)
         n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, x_dst.device
         xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src, a))
         vc = None if shared else v.detach().contiguous()
@@ -121,11 +151,15 @@ class _Gatv2AttentionFn(torch.autograd.Function):
             dd = torch.empty(n, HF, dtype=torch.float32, device=dev)
             P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
             ws = _workspace(pattern, H, F, dev)
-            kind = "" if seed is None else "dropout_"
-            group = () if seed is None else (ctx.p, _ptr(seed), STREAM_ATT)
+            kind = "edge_" if e is not None else "" if seed is None else "dropout_"
+            group, tail, de = () if seed is None else (ctx.p, _ptr(seed), STREAM_ATT), (), None
+            if e is not None:
+                ec, lde = _edge_rows(e, HF)
+                de = torch.empty(nnz, HF, dtype=torch.float32, device=dev) if need_e else None    # (every row is written once)
+                group, tail = (_ptr(ec), lde), (_ptr(de), HF)
             check(getattr(lib, f"pygat_v2_attn_{kind}backward_rows")(
                 n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac),
-                _ptr(vc), HF, *group, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S), _ptr(ws),
+                _ptr(vc), HF, *group, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S), *tail, _ptr(ws),
                 _stream()), f"v2_attn_{kind}backward_rows")
             ds = da = dv = None
             if need_s or need_a or need_v:
@@ -133,13 +167,14 @@ class _Gatv2AttentionFn(torch.autograd.Function):
                 if need_s or need_a:                # one pass forms both: the column's dx_src in registers, da from per-wave records
                     ds = torch.empty(pattern.n_cols, HF, dtype=torch.float32, device=dev)
                     da = torch.empty(HF, dtype=torch.float32, device=dev)
-                    check(lib.pygat_v2_attn_backward_cols(pattern.n_cols, nnz, _ptr(rowptr_t), _ptr(row_t), _ptr(perm_t), H, F, slope,
-                                                          _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(S), _ptr(ds), HF, _ptr(da),
-                                                          _ptr(ws), _stream()), "v2_attn_backward_cols")
+                    kind, group = ("edge_", (_ptr(ec), lde)) if e is not None else ("", ())
+                    check(getattr(lib, f"pygat_v2_attn_{kind}backward_cols")(
+                        pattern.n_cols, nnz, _ptr(rowptr_t), _ptr(row_t), _ptr(perm_t), H, F, slope, _ptr(xd), HF, _ptr(xs), HF,
+                        _ptr(ac), *group, _ptr(S), _ptr(ds), HF, _ptr(da), _ptr(ws), _stream()), f"v2_attn_{kind}backward_cols")
                 if need_v:
                     dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
         return (None, dd.view(x_dst.shape) if need_d else None, ds.view(x_src.shape) if need_s else None,
-                da.view(a.shape) if need_a else None, dv, None, None, None)
+                da.view(a.shape) if need_a else None, dv, None, None, None, de.view(e.shape) if need_e else None)
 
 
 def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tensor, a: torch.Tensor, v: Optional[torch.Tensor] = None,
@@ -157,7 +192,8 @@ def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tens
     share the column pass on the transposed pattern; dv is one K17 launch there.  float32 GPU tensors on the pattern's device;
     1 <= H <= 64, F a power of two in 4..256, H * F <= 1024; for another F zero-pad the columns of all four tensors: zero columns of a
     add nothing to a score.
-    Not provided: a per-entry term or edge features, dropout on the coefficients (that is the sibling op's,
+    Not provided: a per-entry term or edge features in this op (a feature row per entry inside the score is the sibling op's,
+    gatv2_attention_edge; a scalar term per entry is not provided), dropout on the coefficients (that is the sibling op's,
     gatv2_attention_dropout), bfloat16 tables, the value product fused into the column pass (dv is a K17 launch on the transposed
     pattern)."""
     slope = _slope(_OP, negative_slope)
@@ -195,3 +231,33 @@ def gatv2_attention_dropout(pattern: EdgePattern, x_dst: torch.Tensor, x_src: to
     if seed is None:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
     return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, (p, seed))
+
+
+def gatv2_attention_edge(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tensor, a: torch.Tensor, e: torch.Tensor,
+                         v: Optional[torch.Tensor] = None, negative_slope: float = 0.2) -> torch.Tensor:
+    """gatv2_attention with a feature row per entry inside the score, as a GATv2 uses its edge features (PyG's GATv2Conv with edge_dim:
+    e = lin_edge(edge_attr).view(E, H, F)): out[i] = sum over the entries c = (i, j) of row i of
+    softmax_j(sum_f a[f] LeakyReLU(x_dst[i, f] + x_src[j, f] + e[c, f])) * v[j], per head.  The nonlinearity sits inside the sum over
+    the features, so the edge term cannot be a scalar per entry as additive_attention's edge_logit is: it is a whole row, added before
+    LeakyReLU.  e enters the score only; the sum runs over v (x_src under v=None), as in PyG.
+    e is [E, H, F] ([E, F] where the tables have no head axis), float32, on the pattern's device, its rows at the caller's entry index
+    as spmm's values; a row-strided e -- a column slice of a wider tensor, the row stride a multiple of 4 floats and the first row
+    16-byte aligned -- is read in place by its leading dimension, without a copy.  t = (x_dst[i] + x_src[j]) + e[c] is two rounded
+    adds in this order in every pass, so e = 0 gives gatv2_attention's bits in out and every gradient.  Fused on the EDGE
+    instantiations of the K21 kernels: a lane reads its 16 bytes of the e row with the gathered rows of the entry, in the forward, the
+    row pass and the column pass; the gradient of e, de[c] = S[c] * a * LeakyReLU'(t), is written by the row pass, once per entry: no
+    atomics, two runs give the same bits.  Differentiable in x_dst, x_src, a, v and e; a gradient that is not asked for costs no
+    launch that serves only it: when e does not require grad no [E, H, F] tensor is made in backward, and without dx_src and da
+    there is no column pass.  A row without entries gets zeros; a row of one entry (i, j) gets v[j] bit for bit and an all-zero row of
+    de; a pattern without entries launches nothing.  float32 GPU tensors with gatv2_attention's limits (1 <= H <= 64, F a power of two
+    in 4..256, H * F <= 1024).
+    Not provided: dropout on the coefficients together with edge features, bfloat16 tables, e in the value sum, a scalar term per
+    entry, the value product fused into the column pass."""
+    op = _OP_EDGE
+    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (x_dst, x_src, a, v, e)):
+        raise ValueError(f"pygat_amd {op}: x_dst, x_src, a, v and e must be float32: there are no bfloat16 tables in this op")
+    slope = _slope(op, negative_slope)
+    _require_tensor(op, pattern, "e", e, want=_E_WANT)             # (a None here would be gatv2_attention)
+    _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op)
+    _checked_e(pattern, x_dst, e, op)
+    return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, None, e)

@@ -5,7 +5,7 @@ features, edge_softmax (K18) and spmm (pygat_spmm_forward) -- at H x F = 8x16 an
 (v=None: v is x_src) and with a v table of its own, the forward alone and forward + backward:
 
     python tools/gatv2_attention_bench.py [--shapes 8x16,8x64] [--values shared,separate] [--rounds 5] [--steps 10] [--warmup 10]
-                                          [--out profiles/gatv2_attention_bench.jsonl]
+                                          [--dropout | --edge] [--out profiles/gatv2_attention_bench.jsonl]
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
@@ -17,7 +17,12 @@ Before timing, both contenders' outputs are priced on the same seeded inputs by 
 computation on the CPU, on a sample of rows (the row of most entries among them).  Algorithmic bytes are computed from the shapes (E
 entries, N rows, M columns, H heads, R = H F floats per row), `*_bytes` below; `*_roof_ms` is their time at 8 TB/s, and
 `*_roof_fraction` that over the measured time: the whole op's share of the HBM roof on the byte model, not a kernel's.  Recorded, not
-gated.  One JSON object per (shape, value table), appended."""
+gated.  One JSON object per (shape, value table), appended.
+
+--edge measures pygat_amd.gatv2_attention_edge, e [E, H, F] ~ N(0, 1) inside the score, against the same composition with e added
+before leaky_relu, at 8x16 and 8x32 by default (an [E, R] tensor is 5.5 and 11 GB there; at 8x64 it is 22 GB, and the composition,
+which keeps some ten of them for autograd, runs only where the device has the room: otherwise the fused op is recorded alone and the
+line says so), into profiles/gatv2_attention_edge_bench.jsonl."""
 import argparse
 import json
 import os
@@ -81,10 +86,10 @@ def composed_backward_bytes(E, N, M, H, F):
     return spmm_b + softmax_b + score_b
 
 
-def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype, mask=None):
+def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype, mask=None, e=None):
     """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of a . leaky_relu(x_dst_i + x_src_j), times
     mask (the dropout's, [E, H] at the CSR position, after the softmax), times v_j; the rows a few hundred at a time, so that no
-    [entries, H, F] tensor grows beyond them."""
+    [entries, H, F] tensor grows beyond them.  e: the edge rows of --edge, [E, H, F] at the CSR position, added behind x_dst_i + x_src_j."""
     import torch
     ad = a.cpu().to(dtype)
     outs = []
@@ -94,7 +99,10 @@ def sampled_reference(rp, col, rows, x_dst, x_src, a, v, slope, dtype, mask=None
         sub = torch.repeat_interleave(torch.arange(part.numel()), deg)
         cols, inv = torch.unique(col[idx], return_inverse=True)
         xd, xs, vs = x_dst[part].cpu().to(dtype), x_src[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
-        s = (ad * torch.nn.functional.leaky_relu(xd[sub] + xs[inv], slope)).sum(-1)
+        t = xd[sub] + xs[inv]
+        if e is not None:
+            t = t + e[idx.to(e.device)].cpu().to(dtype)
+        s = (ad * torch.nn.functional.leaky_relu(t, slope)).sum(-1)
         m = torch.full((part.numel(), s.shape[1]), -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
         p = torch.exp(s - m[sub])
         alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
@@ -157,6 +165,12 @@ def measure(args):
                 return run
 
             v = leaves[-1] if not shared else x_src
+            if args.edge:
+                measure_edge(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, G, row_d, col_d, rp_t,
+                             col_t, deg, rows, perm)
+                del x_dst, x_src, a, G, leaves, v
+                torch.cuda.empty_cache()
+                continue
             if args.dropout:
                 measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, row_d, col_d, rp_t,
                                 col_t, deg, rows, perm, forward_of, both_of, fused)
@@ -247,9 +261,96 @@ def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, val
           f"bytes; the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
 
 
+def edge_bytes(E, H, F, perm=False):
+    """What e adds to the byte models, R = H F: the fused op reads the entry's e row once in each of its three passes (and the entry
+    index in the forward where the pattern carries a permutation) and writes de once; the composition has one more elementwise add in
+    its forward (two [E, R] reads and a write) and none in its backward: the add hands its incoming gradient on as de."""
+    R = H * F
+    return {"fused_forward": E * 4 * R + (4 * E if perm else 0), "fused_backward": 3 * E * 4 * R, "composed_forward": 3 * E * 4 * R,
+            "composed_backward": 0}
+
+
+def measure_edge(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, G, row_d, col_d, rp_t, col_t, deg,
+                 rows, perm):
+    """--edge, one shape and one kind of v: gatv2_attention_edge against the composition with e inside leaky_relu; one JSON object.
+    Every gradient is asked for, de among them."""
+    N, E, shared = pattern.n_rows, pattern.nnz, values == "shared"
+    R = H * F
+    e = torch.randn(E, H, F, generator=torch.Generator(device=dev).manual_seed(5), device=dev)
+    leaves = leaves + (e,)
+
+    def fused(xd, xs, a_, *rest):
+        return pg.gatv2_attention_edge(pattern, xd, xs, a_, rest[-1], None if shared else rest[0], slope)
+
+    def composed(xd, xs, a_, *rest):
+        s = (a_ * torch.nn.functional.leaky_relu(xd[row_d] + xs[col_d] + rest[-1], slope)).sum(-1)
+        return pg.spmm(pattern, pg.edge_softmax(pattern, s), xs if shared else rest[0])
+
+    def forward_of(fn):
+        def run():
+            with torch.no_grad():
+                return fn(*leaves)
+        return run
+
+    def both_of(fn):
+        mine = [t.detach().clone().requires_grad_(True) for t in leaves]
+
+        def run():
+            return torch.autograd.grad(fn(*mine), mine, G)
+        return run
+
+    # the composition keeps the two gathers, their sum, the sum with e, leaky_relu's output and the product for autograd, and its
+    # backward holds as many gradients at its peak: some fourteen [E, R] tensors with the two copies of e
+    free, _ = torch.cuda.mem_get_info(dev)
+    need = 14 * E * 4 * R
+    with_composed = need <= free
+    extra = edge_bytes(E, H, F, perm)
+    out_f = forward_of(fused)()
+    ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], v, slope, torch.float64, e=e)
+    ref32 = sampled_reference(rp_t, col_t, rows, *leaves[:3], v, slope, torch.float32, e=e)
+    res = {"bench": "gatv2_attention --edge", "values": values, "device": torch.cuda.get_device_name(0),
+           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
+           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+           "longest_checked_row": int(deg[rows].max()), "e_tensor_bytes": E * 4 * R,
+           "out_err_fused": parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} {values} fused, edge: out", ref32),
+           "out_err_fp32_reference": parity.err(ref32, ref64),
+           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, shared) + extra["fused_forward"],
+           "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, shared, perm) + extra["fused_backward"],
+           "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F) + extra["composed_forward"],
+           "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F) + extra["composed_backward"]}
+    contenders = {"fused": fused}
+    if with_composed:
+        out_c = forward_of(composed)()
+        res["out_err_composed"] = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} {values} composed, edge: out", ref32)
+        res["out_max_abs_fused_minus_composed"] = float((out_f - out_c).abs().max())
+        contenders["composed"] = composed
+        del out_c
+    else:
+        res["composed"] = (f"not run: some {need / 2 ** 30:.0f} GiB for its [E, R] tensors against {free / 2 ** 30:.0f} GiB free; "
+                           f"the fused op is recorded alone")
+    del out_f
+    legs = [("forward", alternate({k: forward_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup))]
+    if not args.forward_only:
+        legs.append(("forward_backward", alternate({k: both_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup)))
+    for what, r in legs:
+        for name in contenders:
+            res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
+        model = res["fused_forward_bytes"] + (res["fused_backward_bytes"] if what == "forward_backward" else 0)
+        other = res["composed_forward_bytes"] + (res["composed_backward_bytes"] if what == "forward_backward" else 0)
+        res[f"{what}_bytes_ratio_model"] = other / model
+        res[f"fused_{what}_roof_ms"] = 1e3 * model / HBM_BYTES_PER_S
+        res[f"fused_{what}_roof_fraction"] = res[f"fused_{what}_roof_ms"] / res[f"fused_{what}_ms"]
+        if with_composed:
+            res[f"{what}_speedup"] = res[f"composed_{what}_ms"] / res[f"fused_{what}_ms"]
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="8x16,8x64")
+    ap.add_argument("--shapes", default=None, help="8x16,8x64; under --edge 8x16,8x32")
     ap.add_argument("--values", default="shared,separate", help="shared: v=None, v is x_src; separate: a v table of its own")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10, help="timed calls per round and contender")
@@ -260,11 +361,20 @@ def main():
     ap.add_argument("--limit", type=int, default=540, help="seconds the measuring child may take")
     ap.add_argument("--dropout", action="store_true", help="gatv2_attention_dropout at p = 0.5 against the op without dropout and the "
                     "composition with the mask as a tensor")
-    ap.add_argument("--out", default=None, help="profiles/gatv2_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout")
+    ap.add_argument("--edge", action="store_true", help="gatv2_attention_edge, e [E, H, F] inside the score, against the composition "
+                    "with e added before leaky_relu")
+    ap.add_argument("--out", default=None, help="profiles/gatv2_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout, "
+                    "..._edge_bench.jsonl under --edge")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.edge and args.dropout:
+        ap.error("--edge and --dropout are two measurements: there is no op with both")
+    if args.shapes is None:
+        args.shapes = "8x16,8x32" if args.edge else "8x16,8x64"
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "gatv2_attention_dropout_bench.jsonl" if args.dropout else "gatv2_attention_bench.jsonl")
+        name = "gatv2_attention_edge_bench.jsonl" if args.edge else "gatv2_attention_dropout_bench.jsonl" if args.dropout else \
+            "gatv2_attention_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
