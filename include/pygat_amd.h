@@ -908,6 +908,29 @@ int pygat_v2_attn_edge_backward_cols(int n_cols, int64_t nnz, const int32_t* row
                                      int64_t lds, const float* a, const float* e, int64_t lde, const float* S, float* dx_src,
                                      int64_t lddx, float* da, void* ws, void* stream);
 
+/* ------------------------------------------------ K22: seeded neighbour sampling of a block (csrc/k22_sample.hip), additive under ABI 16
+ * The block the pattern ops above are fed with: n_dst destination nodes of the graph (n, nnz, rowptr, col: columns strictly increasing
+ * inside a row) x their sampled sources, written as a CSR directly -- no sort, all arithmetic integer, two runs give the same bits.
+ *   key(p) of the entry at CSR position p = word (p & 3) of Philox-4x32-10(counter (p >> 2, hop, 4, 0), key (seed lo, seed hi)); *seed
+ *     is a uint64 in DEVICE memory.  The key depends on the position only: not on dst, not on fanout.
+ *   row r = node dst[r] with positions [b, e): all of them if e - b <= fanout, else the fanout entries smallest in (key, p); kept
+ *     positions are stored ascending.  (fanout = INT32_MAX keeps whole rows.)
+ *   src_nodes = dst in the caller's order, then every other kept column once, ascending; an entry's local column is its index there.
+ * Outputs, all sized by the CALLER's upper bounds (nothing is read back in between): blk_rowptr [n_dst + 1]; blk_col [cap] local
+ * columns; edge_rc [cap x 2] (row, local column); edge_ids [cap] the graph's CSR position of every entry; src_nodes [src_cap];
+ * info [4] = (entries E, sources n_src, 1 if some dst[r] lies outside [0, n), 1 if some id repeats in dst).  cap >= min(n_dst *
+ * fanout, nnz) and src_cap >= n_dst + min(cap, n) hold every valid result; a row that would pass cap and a source that would pass
+ * src_cap are not written.  An id outside [0, n) is never used as an index: its row is empty.  With a flag raised the other outputs
+ * are not meaningful (after a repeat nothing is selected at all).
+ * ws >= pygat_sample_workspace_bytes(n, n_dst) bytes, 16-byte aligned, contents irrelevant: two n-sized int32 tables (the marker of
+ * the dst nodes, the marks of the kept columns), their scan, the per-row counts and the list of the long rows.
+ * Rows whose positions span at most 64 Philox calls (253 entries at any alignment) are selected by one wave with the keys in
+ * registers, longer ones by a work-group with a four-pass radix select (256-bin LDS histograms, keys recomputed per pass). */
+int pygat_sample_workspace_bytes(int n, int n_dst, size_t* bytes);
+int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst, int fanout,
+                       const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr, int32_t* blk_col,
+                       int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

@@ -1,5 +1,5 @@
 """The GAT score over the entries of a sparse pattern whose two sides are different tables -- a sampled block of a large graph
-(destination nodes x sampled sources), attention from one node set to another, a GAT head inside a model built from the pattern ops.
+(destination nodes x sampled sources: what pygat_amd.sample_neighbors returns), attention from one node set to another, a GAT head inside a model built from the pattern ops.
 
   additive_attention  out[i, h, :] = sum over the entries e = (i, j) of row i of
                       softmax_row(LeakyReLU(s_dst[i, h] + s_src[j, h] (+ edge_logit[e, h])))[e, h] * v[j, h, :]

@@ -1,0 +1,405 @@
+// K22 -- seeded neighbour sampling: the block (destination nodes x sampled sources) the pattern ops are fed with, written as a CSR
+// directly (gfx950).  include/pygat_amd.h states the semantics; tests/sampler_ref.py restates them in NumPy.
+//
+// Passes of pygat_sample_block, all on one stream, nothing read back in between:
+//   count     per dst row: range check, cnt = min(degree, fanout), marker[dst[r]] = r + 1, long-row flag, src_nodes[r] = dst[r]
+//   verify    marker[dst[r]] != r + 1 -> some id repeats (plain stores: whichever store won, one of the two rows sees a mismatch)
+//   scan x 2  cnt -> blk_rowptr; long-row flags -> positions in the list of long rows   (pygat_exclusive_scan_i32)
+//   list      the long rows in row order; info[0] = entries
+//   select    short rows (positions span <= 64 Philox calls): one wave per row, keys in registers, bitwise radix select by ballots;
+//             long rows: one work-group per row, four 8-bit radix passes over a 256-bin LDS histogram (integer LDS atomics), keys
+//             recomputed per pass.  Both end in sample_emit: the kept positions in ascending order through a prefix count, and a
+//             plain store of 1 at mark[column] of each.
+//   clear     mark[dst[r]] = 0
+//   scan      mark -> rank
+//   sources   src_nodes[n_dst + rank[j]] = j for marked j; info[1] = sources
+//   relabel   per entry: row by binary search in blk_rowptr, local column = dst position (marker) or n_dst + rank; edge_rc
+// The marker table is never cleared: marker[j] = m names a dst row only if 1 <= m <= n_dst and dst[m - 1] == j, which is checked.
+// Every loop runs over a row's positions or a list's length; all arithmetic is integer.
+#include "common.h"
+#include "rng.h"
+#include <string.h>
+
+namespace pygat {
+
+constexpr int SAMPLE_WAVE_QUADS = 64;     // a row whose positions span more Philox calls than this goes to a work-group
+constexpr int SAMPLE_LONG_BLOCKS = 1024;  // work-groups that walk the list of long rows
+
+// positions [b, e) of block row r in the graph; an id outside [0, n) is an empty row and is never used as an index
+__device__ __forceinline__ bool sample_row(int n, const int32_t* __restrict__ rowptr, const int64_t* __restrict__ dst, int r, int* b,
+                                           int* e) {
+  const int64_t id = dst[r];
+  *b = *e = 0;
+  if (id < 0 || id >= n) return false;
+  const int rb = rowptr[id], re = rowptr[id + 1];
+  if (re > rb) { *b = rb; *e = re; }
+  return true;
+}
+
+__device__ __forceinline__ int sample_quads(int b, int e) { return ((e - 1) >> 2) - (b >> 2) + 1; }   // e > b
+
+__global__ __launch_bounds__(256) void sample_count_kernel(int n, const int32_t* __restrict__ rowptr, int n_dst,
+                                                           const int64_t* __restrict__ dst, int fanout, int32_t* __restrict__ marker,
+                                                           int32_t* __restrict__ cnt, int32_t* __restrict__ lflag,
+                                                           int64_t* __restrict__ src_nodes, int32_t* __restrict__ info) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_dst) return;
+  int b, e;
+  if (sample_row(n, rowptr, dst, r, &b, &e)) marker[dst[r]] = r + 1;
+  else info[2] = 1;
+  const int d = e - b;
+  src_nodes[r] = dst[r];
+  cnt[r] = d < fanout ? d : fanout;
+  lflag[r] = (d > 0 && sample_quads(b, e) > SAMPLE_WAVE_QUADS) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void sample_verify_kernel(int n, int n_dst, const int64_t* __restrict__ dst,
+                                                            const int32_t* __restrict__ marker, int32_t* __restrict__ info) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_dst) return;
+  const int64_t id = dst[r];
+  if (id >= 0 && id < n && marker[id] != r + 1) info[3] = 1;
+}
+
+__global__ __launch_bounds__(256) void sample_list_kernel(int n_dst, const int32_t* __restrict__ lflag, const int32_t* __restrict__ lptr,
+                                                          const int32_t* __restrict__ blk_rowptr, int32_t* __restrict__ llist,
+                                                          int32_t* __restrict__ info) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) info[0] = blk_rowptr[n_dst];
+  if (r < n_dst && lflag[r]) llist[lptr[r]] = r;
+}
+
+// exclusive prefix of v over the THREADS (64: the wave; 256: the work-group, wsum = 4 ints of LDS) threads, and the total
+template <int THREADS>
+__device__ __forceinline__ int sample_scan(int v, int* total, int* wsum) {
+  const int lane = threadIdx.x & 63;
+  int x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int y = __shfl_up(x, off);
+    if (lane >= off) x += y;
+  }
+  if constexpr (THREADS == 64) {
+    *total = __shfl(x, 63);
+    return x - v;
+  } else {
+    const int w = threadIdx.x >> 6;
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < THREADS / 64; ++k) {
+      if (k < w) pre += wsum[k];
+      tot += wsum[k];
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + x - v;
+  }
+}
+
+// Writes the kept positions of the row [b, e) in ascending order at edge_ids[base ...] (at most `room` of them) and marks their
+// columns: all of them (`all`), or those with key < T and the first `ties` of those with key == T.  The index of an entry is the
+// number of kept entries in front of it, from one prefix count over (entries below T, entries equal to T) per THREADS Philox calls.
+template <int THREADS>
+__device__ __forceinline__ void sample_emit(uint64_t seed, uint32_t hop, int b, int e, bool all, uint32_t T, int ties, int64_t base,
+                                            int room, const int32_t* __restrict__ gcol, int64_t* __restrict__ edge_ids,
+                                            int32_t* __restrict__ mark, int* wsum) {
+  const int tid = THREADS == 64 ? (threadIdx.x & 63) : threadIdx.x;
+  const int qb = b >> 2, qe = (e - 1) >> 2;
+  int less_before = 0, eq_before = 0;
+  for (int q0 = qb; q0 <= qe; q0 += THREADS) {
+    const int q = q0 + tid;
+    unsigned lm = 0, em = 0;
+    if (q <= qe) {
+      uint4 w = make_uint4(0, 0, 0, 0);
+      if (!all) w = sample_keys4(seed, (uint32_t)q, hop);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t p = 4u * (uint32_t)q + j, key = word_of(w, j);
+        if (p >= (uint32_t)b && p < (uint32_t)e) {
+          if (all || key < T) lm |= 1u << j;
+          else if (key == T) em |= 1u << j;
+        }
+      }
+    }
+    int tot;
+    const int ex = sample_scan<THREADS>(__popc(lm) | (__popc(em) << 16), &tot, wsum);   // <= 4 THREADS <= 1024 each: no carry
+    int lb = less_before + (ex & 0xFFFF), eb = eq_before + (ex >> 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int idx = -1;
+      if ((lm >> j) & 1) { idx = lb + (eb < ties ? eb : ties); ++lb; }
+      else if ((em >> j) & 1) { if (eb < ties) idx = lb + eb; ++eb; }
+      if (idx >= 0 && idx < room) {
+        const uint32_t p = 4u * (uint32_t)q + j;
+        edge_ids[base + idx] = (int64_t)p;
+        mark[gcol[p]] = 1;
+      }
+    }
+    less_before += tot & 0xFFFF;
+    eq_before += tot >> 16;
+  }
+}
+
+// where block row r writes: false if nothing is to be written (a repeat in dst was seen, an empty row, or a range that does not
+// lie inside the caller's cap -- which no valid input produces)
+__device__ __forceinline__ bool sample_room(const int32_t* __restrict__ blk_rowptr, const int32_t* __restrict__ info, int r, int64_t cap,
+                                            int64_t* base, int* room) {
+  if (info[3]) return false;
+  const int bb = blk_rowptr[r], be = blk_rowptr[r + 1];
+  if (bb < 0 || be <= bb || (int64_t)be > cap) return false;
+  *base = bb; *room = be - bb;
+  return true;
+}
+
+// ---- short rows: one wave per row, the row's keys in registers (one Philox call per lane) ---------------------------------------
+__global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const int32_t* __restrict__ rowptr,
+                                                                 const int32_t* __restrict__ gcol, int n_dst,
+                                                                 const int64_t* __restrict__ dst, int fanout,
+                                                                 const uint64_t* __restrict__ seedp, uint32_t hop, int64_t cap,
+                                                                 const int32_t* __restrict__ blk_rowptr, int64_t* __restrict__ edge_ids,
+                                                                 int32_t* __restrict__ mark, const int32_t* __restrict__ info) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_dst) return;
+  int b, e, room;
+  int64_t base;
+  sample_row(n, rowptr, dst, r, &b, &e);
+  if (e <= b || sample_quads(b, e) > SAMPLE_WAVE_QUADS || !sample_room(blk_rowptr, info, r, cap, &base, &room)) return;
+  const uint64_t seed = seedp[0];
+  const bool all = e - b <= fanout;
+  uint32_t T = 0;
+  int kk = 0;
+  if (!all) {
+    const int q = (b >> 2) + lane;
+    const uint4 w4 = sample_keys4(seed, (uint32_t)q, hop);
+    uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+    unsigned cand = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t p = 4u * (uint32_t)q + j;
+      if (p >= (uint32_t)b && p < (uint32_t)e) cand |= 1u << j;
+    }
+    kk = fanout;                       // the rank sought among the candidates, 1-based
+    for (int bit = 31; bit >= 0; --bit) {
+      unsigned z = 0;
+      int c0 = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool zj = ((cand >> j) & 1) && !((w[j] >> bit) & 1);
+        c0 += __popcll(__ballot(zj));
+        z |= (zj ? 1u : 0u) << j;
+      }
+      if (kk <= c0) cand = z;
+      else { kk -= c0; T |= 1u << bit; cand &= ~z; }
+    }
+  }
+  sample_emit<64>(seed, hop, b, e, all, T, kk, base, room, gcol, edge_ids, mark, nullptr);
+}
+
+// ---- long rows: one work-group per row of the list, radix select over the 32-bit key in four 8-bit passes -------------------------
+__global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const int32_t* __restrict__ rowptr,
+                                                                  const int32_t* __restrict__ gcol, int n_dst,
+                                                                  const int64_t* __restrict__ dst, int fanout,
+                                                                  const uint64_t* __restrict__ seedp, uint32_t hop, int64_t cap,
+                                                                  const int32_t* __restrict__ blk_rowptr,
+                                                                  const int32_t* __restrict__ lptr, const int32_t* __restrict__ llist,
+                                                                  int64_t* __restrict__ edge_ids, int32_t* __restrict__ mark,
+                                                                  const int32_t* __restrict__ info) {
+  __shared__ int hist[256];
+  __shared__ int wsum[4];
+  __shared__ int sel[2];
+  const int tid = threadIdx.x;
+  const uint64_t seed = seedp[0];
+  int n_long = lptr[n_dst];
+  if (n_long > n_dst) n_long = n_dst;
+  for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
+    const int r = llist[x];
+    if (r < 0 || r >= n_dst) continue;
+    int b, e, room;
+    int64_t base;
+    sample_row(n, rowptr, dst, r, &b, &e);
+    if (e <= b || !sample_room(blk_rowptr, info, r, cap, &base, &room)) continue;
+    const bool all = e - b <= fanout;
+    uint32_t T = 0;
+    int kk = fanout;
+    if (!all) {
+      const int qb = b >> 2, qe = (e - 1) >> 2;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        hist[tid] = 0;
+        __syncthreads();
+        for (int q = qb + tid; q <= qe; q += 256) {
+          const uint4 w = sample_keys4(seed, (uint32_t)q, hop);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t p = 4u * (uint32_t)q + j, key = word_of(w, j);
+            const bool in = p >= (uint32_t)b && p < (uint32_t)e && (pass == 0 || ((key ^ T) >> (shift + 8)) == 0);
+            if (in) atomicAdd(&hist[(key >> shift) & 255u], 1);
+          }
+        }
+        __syncthreads();
+        const int h = hist[tid];
+        int tot;
+        const int ex = sample_scan<256>(h, &tot, wsum);
+        if (ex < kk && kk <= ex + h) { sel[0] = tid; sel[1] = kk - ex; }     // one bin holds the rank sought
+        __syncthreads();
+        T |= (uint32_t)sel[0] << shift;
+        kk = sel[1];
+        __syncthreads();
+      }
+    }
+    sample_emit<256>(seed, hop, b, e, all, T, kk, base, room, gcol, edge_ids, mark, wsum);
+  }
+}
+
+__global__ __launch_bounds__(256) void sample_clear_dst_kernel(int n, int n_dst, const int64_t* __restrict__ dst,
+                                                               int32_t* __restrict__ mark) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_dst) return;
+  const int64_t id = dst[r];
+  if (id >= 0 && id < n) mark[id] = 0;
+}
+
+__global__ __launch_bounds__(256) void sample_sources_kernel(int n, int n_dst, const int32_t* __restrict__ mark,
+                                                             const int32_t* __restrict__ rank, int64_t src_cap,
+                                                             int64_t* __restrict__ src_nodes, int32_t* __restrict__ info) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j == 0) info[1] = n_dst + rank[n];
+  if (j >= n || !mark[j]) return;
+  const int64_t pos = (int64_t)n_dst + rank[j];
+  if (pos < src_cap) src_nodes[pos] = j;
+}
+
+__global__ __launch_bounds__(256) void sample_relabel_kernel(int64_t nnz, const int32_t* __restrict__ gcol, int n_dst,
+                                                             const int64_t* __restrict__ dst, int64_t cap,
+                                                             const int32_t* __restrict__ blk_rowptr, const int32_t* __restrict__ marker,
+                                                             const int32_t* __restrict__ rank, const int64_t* __restrict__ edge_ids,
+                                                             int32_t* __restrict__ blk_col, int32_t* __restrict__ edge_rc,
+                                                             const int32_t* __restrict__ info) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (info[3] || k >= cap || k >= blk_rowptr[n_dst]) return;
+  int lo = 0, hi = n_dst;                 // the last row r with blk_rowptr[r] <= k (rows without entries in between are passed over)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk_rowptr[mid] <= k) lo = mid; else hi = mid;
+  }
+  const int64_t p = edge_ids[k];
+  int local = -1;
+  if (p >= 0 && p < nnz) {
+    const int j = gcol[p];
+    const int m = marker[j];
+    local = (m >= 1 && m <= n_dst && dst[m - 1] == j) ? m - 1 : n_dst + rank[j];
+  }
+  blk_col[k] = local;
+  edge_rc[2 * k] = lo;
+  edge_rc[2 * k + 1] = local;
+}
+
+// the workspace, in int32 units; every table starts at a multiple of 4
+struct SampleWs {
+  int64_t marker, mark, rank, cnt, lflag, lptr, llist, tiles, total;
+};
+static inline SampleWs sample_ws(int n, int n_dst) {
+  auto up = [](int64_t v) { return (v + 3) & ~(int64_t)3; };
+  SampleWs w;
+  int64_t at = 0;
+  w.marker = at; at += up(n);
+  w.mark = at; at += up(n);
+  w.rank = at; at += up((int64_t)n + 1);
+  w.cnt = at; at += up(n_dst);
+  w.lflag = at; at += up(n_dst);
+  w.lptr = at; at += up((int64_t)n_dst + 1);
+  w.llist = at; at += up(n_dst);
+  w.tiles = at; at += up((int64_t)(pygat_scan_workspace_bytes(n > n_dst ? n : n_dst) / sizeof(int32_t)));
+  w.total = at;
+  return w;
+}
+
+int footprint_k22(const char* name, int* regs, int* scratch) {
+  static const struct { const char* name; const void* fn; } names[] = {
+      {"k22_count", reinterpret_cast<const void*>(&sample_count_kernel)},
+      {"k22_verify", reinterpret_cast<const void*>(&sample_verify_kernel)},
+      {"k22_list", reinterpret_cast<const void*>(&sample_list_kernel)},
+      {"k22_select_wave", reinterpret_cast<const void*>(&sample_select_wave_kernel)},
+      {"k22_select_block", reinterpret_cast<const void*>(&sample_select_block_kernel)},
+      {"k22_clear_dst", reinterpret_cast<const void*>(&sample_clear_dst_kernel)},
+      {"k22_sources", reinterpret_cast<const void*>(&sample_sources_kernel)},
+      {"k22_relabel", reinterpret_cast<const void*>(&sample_relabel_kernel)}};
+  for (const auto& nm : names)
+    if (!strcmp(name, nm.name)) return kernel_footprint_of(nm.fn, regs, scratch);
+  set_error("kernel_footprint: unknown kernel '%s' (k22_count, k22_verify, k22_list, k22_select_wave, k22_select_block, k22_clear_dst, "
+            "k22_sources, k22_relabel)", name);
+  return PYGAT_EINVAL;
+}
+
+}  // namespace pygat
+
+using namespace pygat;
+
+extern "C" int pygat_sample_workspace_bytes(int n, int n_dst, size_t* bytes) {
+  PYGAT_REQUIRE(bytes, "sample_workspace_bytes: null bytes");
+  PYGAT_REQUIRE(n > 0 && n_dst > 0 && n_dst <= n, "sample_workspace_bytes: n=%d nodes, n_dst=%d: 1 <= n_dst <= n expected", n, n_dst);
+  *bytes = (size_t)sample_ws(n, n_dst).total * sizeof(int32_t);
+  return PYGAT_OK;
+}
+
+extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst,
+                                  int fanout, const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr,
+                                  int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws,
+                                  void* stream) {
+  const char* what = "sample_block";
+  PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
+                (long long)nnz);
+  PYGAT_REQUIRE(n_dst > 0 && n_dst <= n, "%s: n_dst=%d: 1 <= n_dst <= n = %d expected (distinct node ids)", what, n_dst, n);
+  PYGAT_REQUIRE(fanout > 0, "%s: fanout=%d: a fanout >= 1 expected (INT32_MAX keeps whole rows)", what, fanout);
+  const struct { const void* p; const char* name; } tables[] = {
+      {rowptr, "rowptr"}, {col, "col"}, {dst, "dst"}, {seed, "seed"}, {blk_rowptr, "blk_rowptr"}, {blk_col, "blk_col"},
+      {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {src_nodes, "src_nodes"}, {info, "info"}, {ws, "workspace"}};
+  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
+  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 7u) == 0 && (reinterpret_cast<uintptr_t>(edge_ids) & 7u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(src_nodes) & 7u) == 0, "%s: dst, edge_ids and src_nodes must be 8-byte aligned", what);
+  PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
+  PYGAT_REQUIRE(cap > 0 && cap < ((int64_t)1 << 31), "%s: cap=%lld: room for 1 <= cap < 2^31 entries expected", what, (long long)cap);
+  PYGAT_REQUIRE(src_cap >= n_dst, "%s: src_cap=%lld is below n_dst=%d", what, (long long)src_cap, n_dst);
+
+  const SampleWs w = sample_ws(n, n_dst);
+  int32_t* base = (int32_t*)ws;
+  int32_t *marker = base + w.marker, *mark = base + w.mark, *rank = base + w.rank, *cnt = base + w.cnt, *lflag = base + w.lflag,
+          *lptr = base + w.lptr, *llist = base + w.llist;
+  void* tiles = base + w.tiles;
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t* seedp = (const uint64_t*)seed;
+  const dim3 rows((unsigned)cdiv(n_dst, 256)), tpb(256);
+
+  hipError_t me = hipMemsetAsync(mark, 0, (size_t)n * sizeof(int32_t), st);
+  if (me == hipSuccess) me = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), st);
+  if (me != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: %s", what, hipGetErrorString(me));
+    return PYGAT_EHIP;
+  }
+  hipLaunchKernelGGL(sample_count_kernel, rows, tpb, 0, st, n, rowptr, n_dst, dst, fanout, marker, cnt, lflag, src_nodes, info);
+  hipLaunchKernelGGL(sample_verify_kernel, rows, tpb, 0, st, n, n_dst, dst, marker, info);
+  PYGAT_CHECK_LAUNCH(what);
+  int rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
+  if (rc != PYGAT_OK) return rc;
+  rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
+  if (rc != PYGAT_OK) return rc;
+  hipLaunchKernelGGL(sample_list_kernel, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
+  hipLaunchKernelGGL(sample_select_wave_kernel, dim3((unsigned)cdiv(n_dst, 4)), tpb, 0, st, n, rowptr, col, n_dst, dst, fanout, seedp,
+                     hop, cap, blk_rowptr, edge_ids, mark, info);
+  hipLaunchKernelGGL(sample_select_block_kernel, dim3((unsigned)(n_dst < SAMPLE_LONG_BLOCKS ? n_dst : SAMPLE_LONG_BLOCKS)), tpb, 0, st, n,
+                     rowptr, col, n_dst, dst, fanout, seedp, hop, cap, blk_rowptr, lptr, llist, edge_ids, mark, info);
+  hipLaunchKernelGGL(sample_clear_dst_kernel, rows, tpb, 0, st, n, n_dst, dst, mark);
+  PYGAT_CHECK_LAUNCH(what);
+  rc = pygat_exclusive_scan_i32(mark, n, rank, tiles, stream);
+  if (rc != PYGAT_OK) return rc;
+  hipLaunchKernelGGL(sample_sources_kernel, dim3((unsigned)cdiv(n, 256)), tpb, 0, st, n, n_dst, mark, rank, src_cap, src_nodes, info);
+  hipLaunchKernelGGL(sample_relabel_kernel, dim3((unsigned)cdiv(cap, 256)), tpb, 0, st, nnz, col, n_dst, dst, cap, blk_rowptr, marker,
+                     rank, edge_ids, blk_col, edge_rc, info);
+  PYGAT_CHECK_LAUNCH(what);
+  return PYGAT_OK;
+}

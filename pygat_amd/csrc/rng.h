@@ -9,6 +9,10 @@
 // tests/philox_ref.py restates the generator, the keep rule of make_rng and the layouts (the flat one of k7_dropout.hip's
 // mask kernels included) in NumPy, and tests/test_gpu_dropout_seeded.py compares the kernels with it bit for bit: a change
 // of a layout changes that file in the same commit.
+//   sample_keys4 the selection keys of the neighbour sampler (k22_sample.hip): key of the entry at CSR position p of the graph =
+//               word (p & 3) of Philox(counter = (p >> 2, hop, STREAM_SAMPLE = 4, 0), key = seed) -- four POSITIONS per call; the
+//               key depends on the position alone.  No other layout uses stream 4.  tests/sampler_ref.py restates it and
+//               tests/test_gpu_sample.py compares the sampled blocks with it entry for entry.
 #pragma once
 #include "common.h"
 
@@ -47,6 +51,12 @@ __device__ __forceinline__ uint4 draw_heads4(const DropRng& g, uint64_t seed, ui
 }
 __device__ __forceinline__ uint32_t keep_nibble(const DropRng& g, const uint4& w) {
   return (w.x < g.thresh ? 1u : 0u) | (w.y < g.thresh ? 2u : 0u) | (w.z < g.thresh ? 4u : 0u) | (w.w < g.thresh ? 8u : 0u);
+}
+
+// 4 selection keys of the sampler for CSR positions 4*q .. 4*q+3 at hop `hop`
+constexpr uint32_t STREAM_SAMPLE = 4;
+__device__ __forceinline__ uint4 sample_keys4(uint64_t seed, uint32_t q, uint32_t hop) {
+  return philox4x32_10(make_uint4(q, hop, STREAM_SAMPLE, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
 static inline bool make_rng(float p, const void* seed, uint32_t stream_id, DropRng* g) {

@@ -1,5 +1,5 @@
 """The GATv2 score over the entries of a sparse pattern whose two sides are different tables -- a sampled block of a large graph
-(destination nodes x sampled sources), attention from one node set to another, a GATv2 head inside a model built from the pattern ops.
+(destination nodes x sampled sources: what pygat_amd.sample_neighbors returns), attention from one node set to another, a GATv2 head inside a model built from the pattern ops.
 
   gatv2_attention  out[i, h, :] = sum over the entries e = (i, j) of row i of
                    softmax_row(sum_f a[h, f] LeakyReLU(x_dst[i, h, f] + x_src[j, h, f]))[e, h] * v[j, h, :]

@@ -1,0 +1,168 @@
+"""Seeded neighbour sampling on the K22 kernels (csrc/k22_sample.hip): the block -- destination nodes x sampled sources -- that the
+pattern ops (dot_attention, additive_attention, gatv2_attention and their variants, spmm, edge_softmax) take as an EdgePattern.
+
+    blk = sample_neighbors(graph, dst, fanout=10, seed=seed)            # one block around `dst`
+    out = gatv2_attention(blk.pattern, x[blk.dst_nodes], x[blk.src_nodes], a)
+    blocks = sample_blocks(graph, seeds, [10, 25], seed=seed)           # a mini-batch of two layers, outermost hop first
+    h = x[blocks[0].src_nodes]
+    for blk, layer in zip(blocks, layers):
+        h = layer(blk.pattern, h[:blk.n_dst], h)
+
+What is sampled (tests/sampler_ref.py restates it in NumPy; the kernels agree with it entry for entry):
+  - the entry at position p of the graph's CSR (graph.fwd.col[p]) has the 32-bit key: word (p & 3) of Philox-4x32-10 with counter
+    (p >> 2, hop, STREAM_SAMPLE, 0) and key (seed & 0xFFFFFFFF, seed >> 32).  It depends on the position only;
+  - row r of the block is node dst[r].  A row of at most `fanout` entries is kept whole; otherwise the `fanout` entries smallest in
+    (key, p) are kept.  Kept entries stay in ascending position, so their global columns ascend.  Every fanout-subset of a row is
+    equally likely, and with one seed the sample at a smaller fanout is a subset of the sample at a larger one;
+  - src_nodes = dst in the caller's order, then every other kept column once in ascending id; the local column of a node is its index
+    in src_nodes, so x_dst = x_src[:n_dst] (the block convention of DGL and PyG).
+
+Host interaction: one read per hop -- the two counts (entries, sources) and the two validity flags of dst, four int32 in one copy --
+and, once per graph, its largest degree (it bounds the output buffers, which are allocated before anything is known about the sample).
+Because of that read, sampling is refused during stream capture.  There is no CPU path and no torch fallback.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Optional, Sequence
+
+import torch
+
+from . import _lib
+from ._lib import lib, check
+from .dropout import STREAM_SAMPLE    # noqa: F401  (the Philox stream of the keys above; the kernels hold the same constant, csrc/rng.h)
+from .graph import CSRGraph
+from .spmm import EdgePattern
+
+KEEP_ALL = 2 ** 31 - 1     # the fanout the kernels take for "whole rows"
+TRIM_FACTOR = 2            # buffers more than this many times the result are copied down to size
+
+
+class SampledBlock(NamedTuple):
+    """One sampled block.  pattern: an EdgePattern of shape (n_dst, n_src) whose rowptr / col / edge_rc the kernels wrote (perm is
+    None: the entry order is the CSR order, as in CSRGraph.edge_pattern(); its transpose is built on first use by transposed()).
+    src_nodes [n_src], dst_nodes [n_dst]: int64 global ids, src_nodes[:n_dst] == dst_nodes.  edge_ids [nnz]: int64, the graph's CSR
+    position of every entry -- e_full[blk.edge_ids] gathers per-edge inputs for gatv2_attention_edge / dot_attention_edge."""
+    pattern: EdgePattern
+    src_nodes: torch.Tensor
+    dst_nodes: torch.Tensor
+    edge_ids: torch.Tensor
+    n_dst: int
+    n_src: int
+    nnz: int
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _seed(op: str, device, seed):
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or tuple(seed.shape) != (1,) or seed.device != device:
+        got = f"{seed.dtype} {tuple(seed.shape)} on {seed.device}" if isinstance(seed, torch.Tensor) else type(seed).__name__
+        raise ValueError(f"pygat_amd {op}: seed must be an int64 tensor of shape [1] on the graph's device {device} (the kernels read "
+                         f"it there), got {got}")
+    return seed.contiguous()
+
+
+def _fanout(op: str, fanout) -> int:
+    if fanout is None:
+        return KEEP_ALL
+    if isinstance(fanout, bool) or not isinstance(fanout, int) or not 1 <= fanout <= KEEP_ALL:
+        raise ValueError(f"pygat_amd {op}: fanout = {fanout!r}: an int >= 1, or None for whole rows, expected")
+    return fanout
+
+
+def _max_degree(graph: CSRGraph) -> int:
+    """The graph's largest degree, read once per graph."""
+    if getattr(graph, "_max_degree", None) is None:
+        rp = graph.fwd.rowptr
+        graph._max_degree = int((rp[1:] - rp[:-1]).max().item())
+    return graph._max_degree
+
+
+def _checked(op: str, graph, dst, fanout, seed, hop):
+    """Every refusal that needs no device work -> (dst int64 contiguous, fanout as the kernels take it, seed or None)."""
+    if not isinstance(graph, CSRGraph):
+        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
+    fanout = _fanout(op, fanout)
+    if isinstance(hop, bool) or not isinstance(hop, int) or not 0 <= hop < 2 ** 32:
+        raise ValueError(f"pygat_amd {op}: hop = {hop!r}: an int in [0, 2^32) expected")
+    if seed is not None:
+        seed = _seed(op, graph.device, seed)
+    if not isinstance(dst, torch.Tensor) or not dst.is_cuda:
+        raise ValueError(f"pygat_amd {op}: dst must be a tensor on the GPU (there is no CPU path)")
+    if dst.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"pygat_amd {op}: dst must be int32 or int64, not {dst.dtype}")
+    if dst.dim() != 1 or dst.numel() < 1:
+        raise ValueError(f"pygat_amd {op}: dst [n_dst] with n_dst >= 1 expected, got {tuple(dst.shape)}")
+    if dst.device != graph.device:
+        raise ValueError(f"pygat_amd {op}: dst lives on {dst.device}, the graph on {graph.device}")
+    return dst.to(torch.int64).contiguous(), fanout, seed
+
+
+def _trim(t: torch.Tensor, n: int) -> torch.Tensor:
+    return t[:n].clone() if t.shape[0] > TRIM_FACTOR * max(n, 1) else t[:n]
+
+
+def sample_neighbors(graph: CSRGraph, dst: torch.Tensor, fanout: Optional[int], *, seed: Optional[torch.Tensor] = None, generator=None,
+                     hop: int = 0) -> SampledBlock:
+    """The block of `dst` [n_dst] (distinct node ids of `graph`, int32 or int64, on its device) with at most `fanout` neighbours per
+    node (an int >= 1; None keeps whole rows), as the module docstring defines it.  seed: an int64 [1] tensor on the graph's device,
+    read by the kernels; None draws one with torch.randint(0, 2**62, ..., generator=generator).  hop in [0, 2^32) separates the draws
+    of one seed.  The same (seed, hop) gives the same block, bit for bit; nothing is sorted and all arithmetic is integer.
+    A repeated id in dst, or one outside [0, N), raises ValueError: both are found on the device -- an id outside the graph is never
+    used as an index -- and their flags arrive with the block's two counts in the ONE host read of the call.  For that read sampling
+    is refused during stream capture.  There is no CPU path and no fallback."""
+    op = "sample_neighbors"
+    dst, fanout, seed = _checked(op, graph, dst, fanout, seed, hop)
+    n_dst, N, nnz, dev = int(dst.numel()), graph.n, graph.nnz, graph.device
+    if n_dst > N:
+        raise ValueError(f"pygat_amd {op}: dst holds {n_dst} ids but the graph has {N} nodes: some id repeats")
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError(f"pygat_amd {op}: a block cannot be sampled during stream capture (its counts and the check of dst are read "
+                         f"back); sample before the capture")
+    with torch.cuda.device(dev):
+        if seed is None:
+            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev, generator=generator)
+        cap = max(1, min(n_dst * min(fanout, _max_degree(graph)), nnz))
+        src_cap = n_dst + min(cap, N)
+        i32 = dict(dtype=torch.int32, device=dev)
+        rowptr, col, edge_rc = torch.empty(n_dst + 1, **i32), torch.empty(cap, **i32), torch.empty(cap, 2, **i32)
+        edge_ids = torch.empty(cap, dtype=torch.int64, device=dev)
+        src_nodes = torch.empty(src_cap, dtype=torch.int64, device=dev)
+        info = torch.empty(4, **i32)
+        ws = torch.empty(_lib._workspace_bytes("sample_workspace_bytes", N, n_dst), dtype=torch.uint8, device=dev)
+        check(lib.pygat_sample_block(N, nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n_dst, dst.data_ptr(), fanout,
+                                     seed.data_ptr(), hop, cap, src_cap, rowptr.data_ptr(), col.data_ptr(), edge_rc.data_ptr(),
+                                     edge_ids.data_ptr(), src_nodes.data_ptr(), info.data_ptr(), ws.data_ptr(), _stream()), "sample_block")
+        E, n_src, outside, repeat = info.tolist()                     # the one host read
+    if outside:
+        raise ValueError(f"pygat_amd {op}: an id in dst lies outside the graph's nodes [0, {N})")
+    if repeat:
+        raise ValueError(f"pygat_amd {op}: an id repeats in dst (the destination nodes of a block are distinct)")
+    assert 0 <= E <= cap and n_dst <= n_src <= src_cap, (E, cap, n_src, src_cap)
+    col, edge_rc, edge_ids, src_nodes = _trim(col, E), _trim(edge_rc, E), _trim(edge_ids, E), _trim(src_nodes, n_src)
+    pattern = EdgePattern((n_dst, n_src), edge_rc, rowptr, col, None)
+    return SampledBlock(pattern, src_nodes, dst, edge_ids, n_dst, n_src, E)
+
+
+def sample_blocks(graph: CSRGraph, seeds: torch.Tensor, fanouts: Sequence[Optional[int]], *, seed: Optional[torch.Tensor] = None,
+                  generator=None) -> List[SampledBlock]:
+    """The blocks of a len(fanouts)-layer mini-batch around `seeds`: hop 0 samples around the seeds with fanouts[-1], hop t around the
+    previous hop's src_nodes with fanouts[-1 - t]; the list is returned OUTERMOST hop first, so that
+        h = x[blocks[0].src_nodes]
+        for blk, layer in zip(blocks, layers): h = layer(blk.pattern, h[:blk.n_dst], h)
+    ends with one row per seed.  One seed serves all hops (the hop number is a word of the Philox counter).  One host read per hop."""
+    op = "sample_blocks"
+    if isinstance(fanouts, (str, bytes)) or not hasattr(fanouts, "__len__") or len(fanouts) < 1:
+        raise ValueError(f"pygat_amd {op}: fanouts: a non-empty list of fanouts (one per layer) expected")
+    for f in fanouts:
+        _fanout(op, f)
+    _checked(op, graph, seeds, fanouts[-1], seed, 0)
+    if seed is None:
+        with torch.cuda.device(graph.device):
+            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=graph.device, generator=generator)
+    blocks, dst = [], seeds
+    for t in range(len(fanouts)):
+        blocks.append(sample_neighbors(graph, dst, fanouts[-1 - t], seed=seed, hop=t))
+        dst = blocks[-1].src_nodes
+    return blocks[::-1]
