@@ -811,6 +811,17 @@ int pygat_add_attn_dropout_backward_rows(int n_rows, int64_t nnz, const int32_t*
                                          int64_t ldv, const float* edge_logit, int logit_head_stride, float p, const void* seed,
                                          uint32_t stream_id, const float* out, int64_t ldo, const float* m, const float* Z,
                                          const float* G, int64_t ldg, float* ds_dst, float* P, float* S, void* ws, void* stream);
+/* The K20 forward on a bf16 v table, for inference (the BF16 instantiations of the two K20 forward kernels), additive under ABI 16.  v is
+ * rows of H*F bf16 values, 8-byte aligned, ldv in ELEMENTS, >= H*F and a multiple of 4; s_dst, s_src, edge_logit, out and ws as in
+ * pygat_add_attn_forward (fp32; out and ws 16 bytes).  A lane's chunk is the same 4 row elements as in the fp32 kernels, one 8-byte load
+ * widened in registers, and everything after the load is theirs: out is pygat_add_attn_forward's on the widened table bit for bit, at
+ * 2 H*F + 4 H + 4 gathered bytes per entry instead of 4 H*F + 4 H + 4.  edge_logit may be null: the kernels without the term, perm and
+ * logit_head_stride are then not looked at; otherwise as in pygat_add_attn_forward.  m and Z are neither taken nor written: there is no
+ * backward on a bf16 table.  Refusals as for pygat_add_attn_forward after the launcher's own name (v: 8-byte aligned).  The workspace
+ * is pygat_add_attn_workspace_bytes'. */
+int pygat_add_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H, int F,
+                                float negative_slope, const float* s_dst, const float* s_src, const void* v, int64_t ldv,
+                                const float* edge_logit, int logit_head_stride, float* out, int64_t ldo, void* ws, void* stream);
 
 /* ------------------------------------------------ K21: the GATv2 score fused over an edge pattern (csrc/k21_gatv2_attention.hip)
  * Additive under ABI 16 (no existing entry point changes).  For H heads, over a CSR pattern (rowptr [n_rows + 1], col [nnz]) whose row
@@ -907,6 +918,22 @@ int pygat_v2_attn_edge_backward_cols(int n_cols, int64_t nnz, const int32_t* row
                                      int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const float* x_src,
                                      int64_t lds, const float* a, const float* e, int64_t lde, const float* S, float* dx_src,
                                      int64_t lddx, float* da, void* ws, void* stream);
+/* The K21 forwards on bf16 tables, for inference (the BF16 instantiations of the two K21 forward kernels, without and with EDGE),
+ * additive under ABI 16.  x_src, v and (the edge launcher) e are rows of H*F bf16 values, 8-byte aligned, lds, ldv and lde in ELEMENTS,
+ * >= H*F and multiples of 4; x_dst, a, out and ws as in pygat_v2_attn_forward (fp32, 16 bytes).  v == NULL: v is x_src, the one gathered
+ * row, widened once, serves the score and the sum.  A lane's chunk is the same 4 row elements as in the fp32 kernels, one 8-byte load
+ * widened in registers, and everything after the load is theirs: out is pygat_v2_attn_forward's (pygat_v2_attn_edge_forward's) on the
+ * widened tables bit for bit, at half the gathered and per-entry row bytes.  pygat_v2_attn_bf16_forward takes no perm, as
+ * pygat_v2_attn_forward; the edge launcher takes it (it may be null: the position itself): the entry index places the rows of e.  m
+ * and Z are neither taken nor written: there is no backward on bf16 tables, and no dropout variant.  Refusals as for the fp32 forward
+ * launchers after the launcher's own name (x_src, v, e: 8-byte aligned).  The workspace is pygat_v2_attn_workspace_bytes'. */
+int pygat_v2_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F, float negative_slope,
+                               const float* x_dst, int64_t ldd, const void* x_src, int64_t lds, const float* a, const void* v,
+                               int64_t ldv, float* out, int64_t ldo, void* ws, void* stream);
+int pygat_v2_attn_edge_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                    int F, float negative_slope, const float* x_dst, int64_t ldd, const void* x_src, int64_t lds,
+                                    const float* a, const void* v, int64_t ldv, const void* e, int64_t lde, float* out, int64_t ldo,
+                                    void* ws, void* stream);
 
 /* ------------------------------------------------ K22: seeded neighbour sampling of a block (csrc/k22_sample.hip), additive under ABI 16
  * The block the pattern ops above are fed with: n_dst destination nodes of the graph (n, nnz, rowptr, col: columns strictly increasing

@@ -17,8 +17,9 @@ from .gatv2 import GraphAttentionLayerV2, SpGraphAttentionLayerV2, gatv2_level, 
 from .spmm import EdgePattern, spmm, SpecialSpmmFunction, SpecialSpmm, clear_pattern_cache    # noqa: F401
 from .edge_softmax import edge_softmax                  # noqa: F401
 from .dot_attention import edge_dot, dot_attention, dot_attention_dropout, attention_dropout_mask, dot_attention_edge      # noqa: F401
-from .additive_attention import additive_attention, additive_attention_dropout    # noqa: F401
-from .gatv2_attention import gatv2_attention, gatv2_attention_dropout, gatv2_attention_edge    # noqa: F401
+from .additive_attention import additive_attention, additive_attention_bf16, additive_attention_dropout    # noqa: F401
+from .gatv2_attention import (gatv2_attention, gatv2_attention_bf16, gatv2_attention_dropout, gatv2_attention_edge,    # noqa: F401
+                              gatv2_attention_edge_bf16)
 from .sampling import sample_neighbors, sample_blocks, SampledBlock    # noqa: F401
 
 __all__ = ["Adam", "BCEWithLogits", "CSRGraph", "as_graph", "gat_level", "GATLevelFn", "gemm", "set_gemm_mode", "get_gemm_mode", "gemm_mode", "GraphAttentionLayer",
@@ -27,4 +28,5 @@ __all__ = ["Adam", "BCEWithLogits", "CSRGraph", "as_graph", "gat_level", "GATLev
            "EdgePattern", "spmm", "SpecialSpmmFunction", "SpecialSpmm", "clear_pattern_cache", "edge_softmax", "edge_dot", "dot_attention",
            "dot_attention_dropout", "attention_dropout_mask", "dot_attention_edge", "additive_attention"]
 __all__ += ["gatv2_attention", "additive_attention_dropout", "gatv2_attention_dropout", "gatv2_attention_edge"]
+__all__ += ["additive_attention_bf16", "gatv2_attention_bf16", "gatv2_attention_edge_bf16"]
 __all__ += ["sample_neighbors", "sample_blocks", "SampledBlock"]

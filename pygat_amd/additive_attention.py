@@ -11,6 +11,8 @@
     out = additive_attention(pattern, s_dst, s_src, v, 0.2, edge_logit=emb(edge_type))             # gat_level's edge_logit, [E, H] | [E]
     out = additive_attention_dropout(pattern, s_dst, s_src, v, 0.6, training=self.training)        # training: dropout p on the coefficients,
                                                                 # after the softmax, drawn in the kernels from a seed on the device
+    with torch.no_grad():                                       # inference: a bf16 v table, made once -- half the gathered bytes, the
+        out = additive_attention_bf16(pattern, s_dst, s_src, v16)    # bits of additive_attention(pattern, s_dst, s_src, v16.float())
 
 A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate entries; entries may be unsorted and the pattern
 rectangular.  Differentiable in every tensor.  The backward keeps out and (m, Z) per row; its two per-entry tensors P and S ([E, H]
@@ -26,33 +28,37 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
+from .dot_attention import (_drop_p, _drop_seed, _require_dtypes, _require_heads, _require_inference, _require_pattern, _require_tensor,
+                            _slope)
 from .dropout import STREAM_ATT
 from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "additive_attention"
 _OP_DROP = "additive_attention_dropout"
+_OP_BF16 = "additive_attention_bf16"
 _PAD_HINT = ("zero-padding the columns of v to the next allowed F leaves the first F columns of the result unchanged (no scale "
              "depends on F)")
 
 
-def _checked(pattern, s_dst, s_src, v, edge_logit, op: str = _OP):
+def _checked(pattern, s_dst, s_src, v, edge_logit, op: str = _OP, bf16: bool = False):
     """Every refusal that looks at the pattern and the tensors, those of edge_logit alone first, under the op's name -> (H, F, no
-    head axis, the logit's head stride | None)."""
+    head axis, the logit's head stride | None).  bf16: v is the bfloat16 table v16 of additive_attention_bf16 (its dtype was looked at
+    by _require_dtypes)."""
     if edge_logit is not None:
         _require_tensor(op, pattern, "edge_logit", edge_logit)
     _require_pattern(op, pattern)
-    for name, t in (("s_dst", s_dst), ("s_src", s_src), ("v", v)):
-        _require_tensor(op, pattern, name, t)
-    named = (("s_dst", s_dst, pattern.n_rows, "rows"), ("s_src", s_src, pattern.n_cols, "columns"), ("v", v, pattern.n_cols, "columns"))
+    vn = "v16" if bf16 else "v"
+    for name, t in (("s_dst", s_dst), ("s_src", s_src), (vn, v)):
+        _require_tensor(op, pattern, name, t, torch.bfloat16 if name == "v16" else torch.float32)
+    named = (("s_dst", s_dst, pattern.n_rows, "rows"), ("s_src", s_src, pattern.n_cols, "columns"), (vn, v, pattern.n_cols, "columns"))
     if s_dst.dim() not in (1, 2):
         raise ValueError(f"pygat_amd {op}: s_dst [n_rows] or [n_rows, H] expected, got {tuple(s_dst.shape)}")
     if s_src.dim() != s_dst.dim() or s_src.shape[1:] != s_dst.shape[1:]:
         raise ValueError(f"pygat_amd {op}: s_src {tuple(s_src.shape)} does not match s_dst {tuple(s_dst.shape)}: the same number of "
                          f"heads expected")
     if v.dim() != s_dst.dim() + 1 or v.shape[1:-1] != s_dst.shape[1:]:
-        raise ValueError(f"pygat_amd {op}: v {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: v [n_cols, F] with s_dst "
-                         f"[n_rows], or v [n_cols, H, F] with s_dst [n_rows, H] and the same number of heads, expected")
+        raise ValueError(f"pygat_amd {op}: {vn} {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: {vn} [n_cols, F] with s_dst "
+                         f"[n_rows], or {vn} [n_cols, H, F] with s_dst [n_rows, H] and the same number of heads, expected")
     for name, t, rows, side in named:
         if t.shape[0] != rows:
             raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
@@ -163,8 +169,9 @@ def additive_attention(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.T
     Differentiable in s_dst, s_src, v and edge_logit (the gradient of an [E] logit is the sum over the heads); a gradient that is not
     asked for costs no launch.  float32 GPU tensors on the pattern's device; 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024;
     for another F zero-pad the columns of v: the first F columns of the result are unchanged.
-    Not provided: dropout on the coefficients (that is the sibling op's, additive_attention_dropout), bfloat16 tables, a
-    fused column pass (dv and ds_src are two K17 launches on the transposed pattern)."""
+    Not provided: dropout on the coefficients (that is the sibling op's, additive_attention_dropout), a fused column pass (dv and
+    ds_src are two K17 launches on the transposed pattern).  Inference on a bfloat16 v table is the sibling op's,
+    additive_attention_bf16."""
     return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, _slope(_OP, negative_slope), edge_logit)
 
 
@@ -196,3 +203,34 @@ def additive_attention_dropout(pattern: EdgePattern, s_dst: torch.Tensor, s_src:
     if seed is None:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
     return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, slope, edge_logit, (p, seed))
+
+
+def additive_attention_bf16(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.Tensor, v16: torch.Tensor,
+                            negative_slope: float = 0.2, edge_logit: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """additive_attention for inference on a bfloat16 value table: v16 [n_cols, H, F] (or [n_cols, F]) is torch.bfloat16, made once
+    (v.bfloat16()); s_dst, s_src, edge_logit and the result stay float32.  The result is additive_attention(pattern, s_dst, s_src,
+    v16.float(), negative_slope, edge_logit) bit for bit: on the BF16 instantiations of the K20 forward kernels a lane loads the same
+    4 row elements as 8 bytes and widens them in registers, and everything after the load is the float32 kernels' arithmetic in their
+    order -- at half the gathered bytes of v and half the memory of the table; no float32 copy of it is made.  Forward only: nothing
+    is saved, no per-row softmax state is written and no transpose of the pattern is built.  With grad mode on and an argument that
+    requires grad it raises: call it under torch.no_grad(), or use additive_attention on float32 tables.  A float32 v16, or a bfloat16
+    tensor in any other place, is refused.  A row without entries gets zeros; a pattern without entries launches nothing.  The limits
+    are additive_attention's: 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024.
+    Not provided: a backward, dropout, bfloat16 s_dst, s_src, edge_logit or results."""
+    op = _OP_BF16
+    slope = _slope(op, negative_slope)
+    _require_inference(op, _OP, (s_dst, s_src, v16, edge_logit))
+    _require_dtypes(op, (("s_dst", s_dst, torch.float32), ("s_src", s_src, torch.float32), ("v16", v16, torch.bfloat16),
+                         ("edge_logit", edge_logit, torch.float32)))
+    H, F, flat, uhs = _checked(pattern, s_dst, s_src, v16, edge_logit, op, bf16=True)
+    n, dev = pattern.n_rows, v16.device
+    if pattern.nnz == 0:                                           # every row is without entries: zeros, and nothing is launched
+        return torch.zeros((n,) + tuple(v16.shape[1:]), dtype=torch.float32, device=dev)
+    sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v16, edge_logit))
+    with torch.cuda.device(dev):
+        out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.add_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=dev)
+        check(lib.pygat_add_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope,
+                                              _ptr(sd), _ptr(ss), _ptr(vc), H * F, _ptr(uc), uhs or 0, _ptr(out), H * F, _ptr(ws),
+                                              _stream()), "add_attn_bf16_forward")
+    return out.view((n,) + tuple(v16.shape[1:]))

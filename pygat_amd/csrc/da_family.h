@@ -1,7 +1,7 @@
 // The kernel skeleton and the launcher tail of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip), K20
 // (k20_additive_attention.hip) and K21 (k21_gatv2_attention.hip), on the lane mapping of da_lanes.h.  A pass is two kernels, a piece
 // kernel for the long rows (one wave per chunk, the rule of long_rows.h) and a row kernel; their bodies are here once, templated on
-// the family, a type (DaFam<variant>, AaFam<LOGIT, DROP>, V2Fam<SHARED, DROP, EDGE>) that says what a lane group holds of its row and how it
+// the family, a type (DaFam<variant>, AaFam<LOGIT, DROP, BF16>, V2Fam<SHARED, DROP, EDGE, BF16>) that says what a lane group holds of its row and how it
 // walks it:
 //   forward   Fam::Own<VEC>; Fam::load<VEC>(g, ln, row, own); Fam::KEEP_MZ
 //   backward  Fam::Row<VEC>, a DaGrad<VEC> and the row's own operand; Fam::bwd_load<LPR, VEC>(g, ln, row, r);
@@ -219,15 +219,16 @@ static int da_check_drop(const char* what, const DaDrop& d, DropRng* rng) {
 }
 
 // the per-entry rows of the EDGE launchers of K19 and K21: e, and de where it is asked for, are row tables like the gathered ones,
-// [nnz x H*F] at the caller's entry index; e is non-null where there are entries
+// [nnz x H*F] at the caller's entry index; e is non-null where there are entries.  e_align: 16, or 8 where e is rows of bf16 values
+// (K21's inference forward; the pointer then only stands for them)
 struct DaEdge {
   const float* e;
   int64_t lde;
   float* de;                   // backward rows only; null: not asked for
   int64_t ldde;
 };
-static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed) {
-  if (nnz > 0 || ed.e) DA_TABLE(what, "e", ed.e, ed.lde, HF);
+static int da_check_edge(const char* what, int64_t nnz, int HF, const DaEdge& ed, int e_align = 16) {
+  if (nnz > 0 || ed.e) DA_TABLE_ALIGNED(what, "e", ed.e, ed.lde, HF, e_align);
   if (ed.de) DA_TABLE(what, "de", ed.de, ed.ldde, HF);
   return PYGAT_OK;
 }

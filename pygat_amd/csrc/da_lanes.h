@@ -1,6 +1,6 @@
 // The lanes of the fused attention families over an edge pattern: K19 (k19_dot_attention.hip, the dot-product score), K20
 // (k20_additive_attention.hip, the GAT score) and K21 (k21_gatv2_attention.hip, the GATv2 score).  The kernel arguments, the lane
-// mapping of a row of H*F floats, the online softmax fold of one head and the merge of two partial records, the caller's entry index
+// mapping of a row of H*F floats, the row loads (16 bytes of a float table, 8 of a bf16 one), the online softmax fold of one head and the merge of two partial records, the caller's entry index
 // of a CSR position, the per-entry scalar term, the draws of the DROP instantiations (the seeded dropout of the coefficients, one copy
 // for the three families), the lane-shape dispatch and the table checks of the launchers.  Moved here from
 // k19_dot_attention.hip as it stood; K19's device code is the same before and after (profiles/k20_k19_unchanged.txt).  The kernels
@@ -101,6 +101,17 @@ template <int VEC>
 __device__ __forceinline__ void da_load_row(const float* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
 #pragma unroll
   for (int v = 0; v < VEC; ++v) w[v] = ld4(p + ln.ofs[v]);
+}
+// a bf16 table (the inference forwards of all three families): the same 4 row elements per chunk in one 8-byte load, widened exactly (element 0 is the low half of the first word)
+typedef unsigned short da_bf16;
+template <int VEC>
+__device__ __forceinline__ void da_load_row(const da_bf16* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    const uint2 r = *reinterpret_cast<const uint2*>(p + ln.ofs[v]);
+    w[v] = make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
+                       __uint_as_float(r.y & 0xffff0000u));
+  }
 }
 template <int VEC>
 __device__ __forceinline__ void da_store_row(float* p, const DaLane<VEC>& ln, const float4 (&w)[VEC]) {

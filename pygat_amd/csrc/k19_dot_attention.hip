@@ -65,17 +65,7 @@ constexpr bool da_exists(unsigned v, bool bwd) {
   return v < 16 && !(da_has(v, DA_EDGE) && da_has(v, DA_DROP | DA_BF16)) && !(da_has(v, DA_BF16) && (bwd || da_has(v, DA_DROP)));
 }
 
-// a bf16 table: the same 4 row elements per chunk in one 8-byte load, widened exactly (element 0 is the low half of the first word)
-typedef unsigned short da_bf16;
-template <int VEC>
-__device__ __forceinline__ void da_load_row(const da_bf16* p, const DaLane<VEC>& ln, float4 (&w)[VEC]) {
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p + ln.ofs[v]);
-    w[v] = make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                       __uint_as_float(r.y & 0xffff0000u));
-  }
-}
+// (a bf16 table, da_bf16, and its 8-byte da_load_row: da_lanes.h, shared with K20 and K21)
 
 // the score of one entry: one rounding of the product, so the forward and the backward see the same bits
 template <int LPR>

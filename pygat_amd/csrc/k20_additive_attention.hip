@@ -23,6 +23,10 @@
 //     stream id, drawn in registers in both passes (da_keep_batch, da_lanes.h) -- no mask tensor exists.  backward_rows: dp = mask <G, v>,
 //     T = p (dp - D), dz and ds_dst as above, P[c, h] = p mask, S[c, h] = dz.  The walk then carries c in both passes, on LOGIT's path,
 //     and the forward reads perm; without LOGIT it loads no logit.
+//   BF16 (forward only, inference: additive_attention_bf16): v is rows of H*F bf16 values, a lane's chunk one 8-byte load widened in
+//     registers (da_load_row, da_lanes.h); s_src stays float, and everything after the load sees the fp32 kernels' values in their
+//     order: the result of the fp32 forward on the widened table bit for bit.  Neither m nor Z is written.  BF16 goes with LOGIT and
+//     not with DROP.
 //
 // Lane mapping: K19's (da_lanes.h).  Rows of v, out and G are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.
 // A group of LPR lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane, chunk c = c0 + 64 v; the chunks of a head sit
@@ -62,13 +66,15 @@ struct AaRows {
   float t[U][VEC];
   float4 v[U][VEC];
 };
-template <int VEC, int U>
+// T: the element type of the v table (float, or da_bf16 in the inference forward: g.v then points at bf16 rows, ldv counting elements
+// all the same)
+template <int VEC, int U, typename T = float>
 __device__ __forceinline__ void aa_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], AaRows<VEC, U>& w) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
 #pragma unroll
     for (int v = 0; v < VEC; ++v) w.t[u][v] = g.k[(int64_t)src[u] * g.ldk + ln.head[v]];
-    da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+    da_load_row<VEC>(reinterpret_cast<const T*>(g.v) + (int64_t)src[u] * g.ldv, ln, w.v[u]);
   }
 }
 
@@ -86,8 +92,8 @@ __device__ __forceinline__ float aa_z(float sd, float t, float u) {
 // ahead of the next gather.  Without LOGIT the forward carries no entry index; the backward needs it only for its stores and forms it
 // whole (da_entry) a batch ahead.  DROP: the entry index places the draws, so it travels on LOGIT's path in BOTH passes (EID), the
 // forward's included, whether or not there is a logit to load; ent = eid x H is then formed in the forward too.  key: the key of the
-// draws under DROP (by value, K19's way), a DaNoKey without.
-template <int VEC, bool LOGIT, bool DROP, bool BWD, typename Fold, typename Key, typename... Ctx>
+// draws under DROP (by value, K19's way), a DaNoKey without.  T: the element type of the v table (aa_gather).
+template <int VEC, bool LOGIT, bool DROP, bool BWD, typename Fold, typename T = float, typename Key, typename... Ctx>
 __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, Key key,
                                         Ctx&... ctx) {
   constexpr int U = da_unroll(BWD, VEC);
@@ -111,7 +117,7 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
     }
     while (full) {
       AaRows<VEC, U> w;
-      aa_gather<VEC, U>(g, ln, src, w);
+      aa_gather<VEC, U, T>(g, ln, src, w);
       if constexpr (BWD && !EID) {
 #pragma unroll
         for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
@@ -149,7 +155,7 @@ __device__ __forceinline__ void aa_walk(const DaArgs& g, const DaLane<VEC>& ln, 
       da_bias_load<VEC, 1>(g, ln, eid, bs);
     }
     AaRows<VEC, 1> w;
-    aa_gather<VEC, 1>(g, ln, src, w);
+    aa_gather<VEC, 1, T>(g, ln, src, w);
     Fold::fold(g, ln, key, ctx..., w, ent, bs);
   }
 }
@@ -187,10 +193,11 @@ struct AaFwdFold {
 
 // the family: what the forward kernels of da_family.h hold of a row and how they walk it, per LOGIT and DROP.  walk forwards to
 // aa_walk, which the backward kernels below call themselves: as the family's member, K21's way, it moved the LOGIT forward at 64
-// lanes a row
-template <bool LOGIT, bool DROP>
+// lanes a row.  BF16: the inference forward on a bf16 v table; m and Z are what a backward reads, and it has none
+template <bool LOGIT, bool DROP, bool BF16 = false>
 struct AaFam {
-  static constexpr bool KEEP_MZ = true;
+  static_assert(!(BF16 && DROP), "bf16 tables are for inference: no dropout");
+  static constexpr bool KEEP_MZ = !BF16;
   template <int VEC> using Own = float[VEC];                   // s_dst of the row, per chunk slot
   __device__ __forceinline__ static AaKey<DROP> key([[maybe_unused]] const DaArgs& g) {
     if constexpr (DROP) return da_key<true>(g);
@@ -203,7 +210,9 @@ struct AaFam {
   template <int LPR, int VEC, int PASS>
   __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
                                               AaKey<DROP> key, const float (&sd)[VEC], DaState<VEC>& st) {
-    aa_walk<VEC, LOGIT, DROP, false, AaFwdFold<VEC, LOGIT, DROP>>(g, ln, e0, e1, step, key, sd, st);
+    static_assert(PASS == 0, "the family serves the forward pair alone");
+    aa_walk<VEC, LOGIT, DROP, false, AaFwdFold<VEC, LOGIT, DROP>, std::conditional_t<BF16, da_bf16, float>>(g, ln, e0, e1, step, key, sd,
+                                                                                                       st);
   }
 };
 
@@ -312,36 +321,45 @@ __global__ __launch_bounds__(256) void aa_bwd_row_kernel(DaArgs g) {
     if (ln.lead >> v & 1) g.dq[row * g.lddq + ln.head[v]] = ds[v];
 }
 
-// the table of the family: (LOGIT, DROP, forward | backward, long | row, lane shape) -> the kernel.  What a launcher starts and what
-// pygat_kernel_footprint reports on both come from here
-template <int LPR, int VEC, bool LOGIT, bool DROP>
+// the table of the family: (LOGIT, DROP, BF16, forward | backward, long | row, lane shape) -> the kernel; null where there is none
+// (bf16 tables: the forward pair alone, without DROP).  What a launcher starts and what pygat_kernel_footprint reports on both come
+// from here
+template <int LPR, int VEC, bool LOGIT, bool DROP, bool BF16>
 static const void* aa_kernel_at(bool bwd, bool lng) {
-  if (bwd) return lng ? reinterpret_cast<const void*>(&aa_bwd_long_kernel<LPR, VEC, LOGIT, DROP>)
-                      : reinterpret_cast<const void*>(&aa_bwd_row_kernel<LPR, VEC, LOGIT, DROP>);
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<AaFam<LOGIT, DROP>, LPR, VEC>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<AaFam<LOGIT, DROP>, LPR, VEC>);
+  if constexpr (BF16) {
+    if (bwd) return nullptr;
+  } else if (bwd) return lng ? reinterpret_cast<const void*>(&aa_bwd_long_kernel<LPR, VEC, LOGIT, DROP>)
+                             : reinterpret_cast<const void*>(&aa_bwd_row_kernel<LPR, VEC, LOGIT, DROP>);
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<AaFam<LOGIT, DROP, BF16>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<AaFam<LOGIT, DROP, BF16>, LPR, VEC>);
 }
-template <bool LOGIT, bool DROP>
+template <bool LOGIT, bool DROP, bool BF16 = false>
 static const void* aa_kernel_of(bool bwd, bool lng, int lpr, int vec) {
-  PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, LOGIT, DROP>(bwd, lng)));
+  PYGAT_DA_DISPATCH(lpr, vec, return (aa_kernel_at<LPR, VEC, LOGIT, DROP, BF16>(bwd, lng)));
   return nullptr;
 }
-static const void* aa_kernel(bool logit, bool drop, bool bwd, bool lng, int lpr, int vec) {
+static const void* aa_kernel(bool logit, bool drop, bool bf16, bool bwd, bool lng, int lpr, int vec) {
+  if (bf16) {
+    if (drop) return nullptr;
+    return logit ? aa_kernel_of<true, false, true>(bwd, lng, lpr, vec) : aa_kernel_of<false, false, true>(bwd, lng, lpr, vec);
+  }
   if (drop) return logit ? aa_kernel_of<true, true>(bwd, lng, lpr, vec) : aa_kernel_of<false, true>(bwd, lng, lpr, vec);
   return logit ? aa_kernel_of<true, false>(bwd, lng, lpr, vec) : aa_kernel_of<false, false>(bwd, lng, lpr, vec);
 }
 
 // pygat_kernel_footprint: <prefix>{fwd,bwd}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k20_: the kernels without
-// a flag, k20u_: LOGIT, k20d_: DROP, k20du_: DROP and LOGIT
+// a flag, k20u_: LOGIT, k20d_: DROP, k20du_: DROP and LOGIT, k20h_: bf16 v table, k20hu_: bf16 v table and LOGIT (fwd only)
 int footprint_k20(const char* name, int* regs, int* scratch) {
-  static const struct { const char* prefix; bool logit, drop; } names[] = {
-      {"k20_", false, false}, {"k20u_", true, false}, {"k20d_", false, true}, {"k20du_", true, true}};
+  static const struct { const char* prefix; bool logit, drop, bf16; } names[] = {
+      {"k20_", false, false, false}, {"k20u_", true, false, false}, {"k20d_", false, true, false}, {"k20du_", true, true, false},
+      {"k20h_", false, false, true}, {"k20hu_", true, false, true}};
   const void* fn = nullptr;
   DaKernelName k;
   for (const auto& nm : names)
-    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1) fn = aa_kernel(nm.logit, nm.drop, k.pass == 1, k.lng, k.lpr, k.vec);
+    if (da_parse_kernel_name(name, nm.prefix, &k) && k.pass <= 1)
+      fn = aa_kernel(nm.logit, nm.drop, nm.bf16, k.pass == 1, k.lng, k.lpr, k.vec);
   if (!fn) {
-    set_error("kernel_footprint: unknown kernel '%s' (k20{,u,d,du}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>)", name);
+    set_error("kernel_footprint: unknown kernel '%s' (k20{,u,d,du,h,hu}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>; k20h*: fwd only)", name);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
@@ -361,8 +379,10 @@ struct AaCall {
   const int32_t *rowptr, *col, *perm;
   int H, F;
   float negative_slope;
-  const float *s_dst, *s_src, *v;
+  const float *s_dst, *s_src;
+  const void* v;               // float rows, or bf16 rows under v_bytes == 2
   int64_t ldv;
+  int v_bytes;                 // the size of an element of v: 4, or 2 (the bf16 inference forward, which neither writes nor takes m and Z)
   const float* edge_logit;     // null: the kernels without LOGIT
   int logit_head_stride;
   bool dropout;                // the DROP kernels, on the mask of drop
@@ -379,7 +399,7 @@ struct AaCall {
 // both launchers: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
 static int aa_launch(const AaCall& c) {
   const char* what = c.what;
-  const bool logit = c.edge_logit != nullptr;
+  const bool logit = c.edge_logit != nullptr, bf16 = c.v_bytes == 2;
   const int rc = aa_check_shape(what, c.nnz, c.H, c.F);
   if (rc != PYGAT_OK) return rc;
   PYGAT_REQUIRE(isfinite(c.negative_slope), "%s: negative_slope=%g, a finite slope expected", what, (double)c.negative_slope);
@@ -390,10 +410,10 @@ static int aa_launch(const AaCall& c) {
   PYGAT_REQUIRE(c.nnz == 0 || c.col, "%s: null col", what);
   PYGAT_REQUIRE(c.s_dst, "%s: null s_dst", what);
   PYGAT_REQUIRE(c.s_src, "%s: null s_src", what);
-  DA_TABLE(what, "v", c.v, c.ldv, HF);
+  DA_TABLE_ALIGNED(what, "v", c.v, c.ldv, HF, 4 * c.v_bytes);
   DA_TABLE(what, "out", c.out, c.ldo, HF);
-  PYGAT_REQUIRE(c.m, "%s: null m", what);
-  PYGAT_REQUIRE(c.Z, "%s: null Z", what);
+  PYGAT_REQUIRE(c.m || bf16, "%s: null m", what);
+  PYGAT_REQUIRE(c.Z || bf16, "%s: null Z", what);
   PYGAT_REQUIRE(c.ws, "%s: null workspace", what);
   PYGAT_REQUIRE(aligned16(c.ws), "%s: the workspace must be 16-byte aligned", what);
   if (c.bwd) {
@@ -413,15 +433,15 @@ static int aa_launch(const AaCall& c) {
   DaArgs g;
   memset(&g, 0, sizeof(g));
   g.n = c.n_rows; g.H = c.H; g.F = c.F; g.NCH = HF / 4; g.LH = c.F / 4; g.nnz = c.nnz; g.rowptr = c.rowptr; g.col = c.col;
-  g.scale = c.negative_slope; g.q = c.s_dst; g.ldq = c.H; g.k = c.s_src; g.ldk = c.H; g.v = c.v; g.ldv = c.ldv;
+  g.scale = c.negative_slope; g.q = c.s_dst; g.ldq = c.H; g.k = c.s_src; g.ldk = c.H; g.v = static_cast<const float*>(c.v); g.ldv = c.ldv;
   g.out = c.out; g.ldo = c.ldo; g.m = c.m; g.Z = c.Z; g.part = static_cast<float*>(c.ws); g.pstride = da_pstride(c.H, c.F);
   if (c.bwd || logit || c.dropout) g.perm = c.perm;               // (the forward without a flag walks in CSR order alone)
   if (c.bwd) { g.G = c.G; g.ldg = c.ldg; g.dq = c.ds_dst; g.lddq = c.H; g.P = c.P; g.S = c.S; }
   if (logit) { g.bias = c.edge_logit; g.bhs = c.logit_head_stride; g.bstride = c.logit_head_stride ? c.H : 1; }
   if (c.dropout) g.rng = rng;
   const DaGrid gd = da_grid(c.n_rows, c.nnz, c.H, c.F);
-  da_launch_pair(aa_kernel(logit, c.dropout, c.bwd, true, gd.lpr, gd.vec), aa_kernel(logit, c.dropout, c.bwd, false, gd.lpr, gd.vec), g,
-                 gd.chunks, gd.blocks, c.stream);
+  da_launch_pair(aa_kernel(logit, c.dropout, bf16, c.bwd, true, gd.lpr, gd.vec),
+                 aa_kernel(logit, c.dropout, bf16, c.bwd, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks, c.stream);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -441,7 +461,8 @@ extern "C" int pygat_add_attn_workspace_bytes(int64_t nnz, int H, int F, size_t*
 #define AA_CALL(c, name, back)                                                                                                      \
   AaCall c = {};                                                                                                                    \
   c.what = name; c.bwd = back; c.n_rows = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H; c.F = F;    \
-  c.negative_slope = negative_slope; c.s_dst = s_dst; c.s_src = s_src; c.v = v; c.ldv = ldv; c.edge_logit = edge_logit;             \
+  c.negative_slope = negative_slope; c.s_dst = s_dst; c.s_src = s_src; c.v = v; c.ldv = ldv; c.v_bytes = 4;                         \
+  c.edge_logit = edge_logit;                                                                                                        \
   c.logit_head_stride = logit_head_stride; c.out = const_cast<float*>(out); c.ldo = ldo; c.m = const_cast<float*>(m);               \
   c.Z = const_cast<float*>(Z); c.ws = ws; c.stream = stream
 
@@ -460,6 +481,18 @@ extern "C" int pygat_add_attn_backward_rows(int n_rows, int64_t nnz, const int32
                                             float* ds_dst, float* P, float* S, void* ws, void* stream) {
   AA_CALL(c, "add_attn_backward_rows", true);
   c.G = G; c.ldg = ldg; c.ds_dst = ds_dst; c.P = P; c.S = S;
+  return aa_launch(c);
+}
+
+// the inference forward on a bf16 v table (8-byte aligned rows, ldv in elements): the BF16 instantiations of the forward pair.  m and
+// Z are neither taken nor written.  A null edge_logit: the kernels without LOGIT; perm and logit_head_stride are then not looked at
+extern "C" int pygat_add_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int H,
+                                           int F, float negative_slope, const float* s_dst, const float* s_src, const void* v,
+                                           int64_t ldv, const float* edge_logit, int logit_head_stride, float* out, int64_t ldo, void* ws,
+                                           void* stream) {
+  const float *m = nullptr, *Z = nullptr;
+  AA_CALL(c, "add_attn_bf16_forward", false);
+  c.v_bytes = 2;
   return aa_launch(c);
 }
 

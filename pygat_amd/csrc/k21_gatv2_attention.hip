@@ -34,6 +34,10 @@
 //     e = 0: t + 0 is t bit for bit (an exact zero may change its sign, which LeakyReLU and its slope treat alike), so every output has
 //     gatv2_attention's bits.  EDGE goes with SHARED and not with DROP.  The unroll is da_unroll's at every lane shape: no EDGE kernel
 //     spills at it (the e rows are one more gathered row per entry, and the widest lane shapes hold one or two entries in flight).
+//   BF16 (forward only, inference: gatv2_attention_bf16, gatv2_attention_edge_bf16): x_src, the separate v and, under EDGE, e are rows of
+//     H*F bf16 values, a lane's chunk one 8-byte load widened in registers (da_load_row, da_lanes.h); x_dst and a stay float, and
+//     everything after the load sees the fp32 kernels' values in their order: the result of the fp32 forward on the widened tables bit
+//     for bit.  Neither m nor Z is written.  BF16 goes with SHARED and EDGE and not with DROP; there is no backward pass on it.
 //
 // Lane mapping: K19's (da_lanes.h).  Rows are H*F floats, heads side by side, NOT padded; F a power of two in 4..256.  A group of LPR
 // lanes holds one row, VEC chunks of 4 floats (16-byte loads) per lane; the chunks of a head sit on LH = F / 4 adjacent lanes of one
@@ -146,14 +150,16 @@ struct V2Rows : V2EdgeRows<VEC, U, EDGE> {
     else return v2_t(own, x[u][c]);
   }
 };
-template <int VEC, int U, int MODE, bool SHARED, bool EDGE>
+// T: the element type of the gathered tables x, v and e (float, or da_bf16 in the inference forward: g.k, g.v and g.e then point at
+// bf16 rows, their strides counting elements all the same)
+template <int VEC, int U, int MODE, bool SHARED, bool EDGE, typename T = float>
 __device__ __forceinline__ void v2_gather(const DaArgs& g, const DaLane<VEC>& ln, const int32_t (&src)[U], const int64_t (&ent)[U],
                                           V2Rows<VEC, U, MODE, SHARED, EDGE>& w) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    da_load_row<VEC>(g.k + (int64_t)src[u] * g.ldk, ln, w.x[u]);
-    if constexpr (MODE != 2 && !SHARED) da_load_row<VEC>(g.v + (int64_t)src[u] * g.ldv, ln, w.v[u]);
-    if constexpr (EDGE) da_load_row<VEC>(g.e + ent[u] * g.lde, ln, w.e[u]);
+    da_load_row<VEC>(reinterpret_cast<const T*>(g.k) + (int64_t)src[u] * g.ldk, ln, w.x[u]);
+    if constexpr (MODE != 2 && !SHARED) da_load_row<VEC>(reinterpret_cast<const T*>(g.v) + (int64_t)src[u] * g.ldv, ln, w.v[u]);
+    if constexpr (EDGE) da_load_row<VEC>(reinterpret_cast<const T*>(g.e) + ent[u] * g.lde, ln, w.e[u]);
     if constexpr (MODE == 2) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v) w.s[u][v] = g.S[v2_scalars<EDGE>(g, ent[u]) + ln.head[v]];
@@ -247,11 +253,12 @@ template <int VEC, bool EDGE>
 struct V2ColFold;
 
 // the family: what the kernels of da_family.h hold of a row and how they walk it, per SHARED, DROP and EDGE (the column pass: per
-// EDGE alone)
-template <bool SHARED, bool DROP = false, bool EDGE = false>
+// EDGE alone).  BF16: the inference forward on bf16 x_src, v and e tables; m and Z are what a backward reads, and it has none
+template <bool SHARED, bool DROP = false, bool EDGE = false, bool BF16 = false>
 struct V2Fam {
   static_assert(!(DROP && EDGE), "EDGE does not combine with DROP");
-  static constexpr bool KEEP_MZ = true;
+  static_assert(!(DROP && BF16), "bf16 tables are for inference: no dropout");
+  static constexpr bool KEEP_MZ = !BF16;
   template <int VEC> using Own = V2Own<VEC>;
   template <int VEC> using Row = V2BwdRow<VEC>;
   __device__ __forceinline__ static V2Key<DROP> key([[maybe_unused]] const DaArgs& g) {
@@ -274,6 +281,8 @@ struct V2Fam {
   __device__ __forceinline__ static void walk(const DaArgs& g, const DaLane<VEC>& ln, int64_t e0, int64_t e1, int64_t step, bool,
                                                 V2Key<DROP> key, Ctx&... ctx) {
     static_assert(MODE != 2 || !DROP, "the column pass reads S alone: it has no DROP variant");
+    static_assert(MODE == 0 || !BF16, "bf16 tables are for inference: the forward alone");
+    using T = std::conditional_t<BF16, da_bf16, float>;         // the element type of the gathered tables
     using Fold = std::conditional_t<MODE == 0, V2FwdFold<LPR, VEC, SHARED, DROP, EDGE>,
                                     std::conditional_t<MODE == 1, V2BwdFold<LPR, VEC, SHARED, DROP, EDGE>, V2ColFold<VEC, EDGE>>>;
     constexpr int U = v2_unroll(MODE != 0, VEC, EDGE);
@@ -298,7 +307,7 @@ struct V2Fam {
           for (int u = 0; u < U; ++u) ent[u] = ent_next[u];
         }
         V2Rows<VEC, U, MODE, SHARED, EDGE> w;
-        v2_gather<VEC, U, MODE, SHARED, EDGE>(g, ln, src, ent, w);
+        v2_gather<VEC, U, MODE, SHARED, EDGE, T>(g, ln, src, ent, w);
         e += U * step;
         full = e + (U - 1) * step < e1;
         if (full) {
@@ -316,7 +325,7 @@ struct V2Fam {
       int64_t ent[1] = {0};
       if constexpr (ENT) ent[0] = v2_entry<EDGE>(g, e);
       V2Rows<VEC, 1, MODE, SHARED, EDGE> w;
-      v2_gather<VEC, 1, MODE, SHARED, EDGE>(g, ln, src, ent, w);
+      v2_gather<VEC, 1, MODE, SHARED, EDGE, T>(g, ln, src, ent, w);
       Fold::fold(g, ln, key, ctx..., w, ent);
     }
   }
@@ -458,23 +467,33 @@ __global__ __launch_bounds__(256) void v2_da_final_kernel(int R, const float* __
 
 // the table of the family: (SHARED, DROP, EDGE, forward | backward rows | columns, long | row, lane shape) -> the kernel.  What a
 // launcher starts and what pygat_kernel_footprint reports on both come from here.  pass: 0 forward, 1 backward rows, 2 columns (per
-// EDGE alone)
-template <int LPR, int VEC, bool SHARED, bool DROP, bool EDGE>
+// EDGE alone).  BF16: the forward pair alone, null for the other passes
+template <int LPR, int VEC, bool SHARED, bool DROP, bool EDGE, bool BF16>
 static const void* v2_kernel_at(int pass, bool lng) {
-  if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC, EDGE>)
-                            : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC, EDGE>);
-  if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>)
-                            : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>);
-  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>)
-             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>);
+  if constexpr (BF16) {
+    if (pass != 0) return nullptr;
+  } else {
+    if (pass == 2) return lng ? reinterpret_cast<const void*>(&v2_col_long_kernel<LPR, VEC, EDGE>)
+                              : reinterpret_cast<const void*>(&v2_col_row_kernel<LPR, VEC, EDGE>);
+    if (pass == 1) return lng ? reinterpret_cast<const void*>(&da_bwd_long_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>)
+                              : reinterpret_cast<const void*>(&da_bwd_row_kernel<V2Fam<SHARED, DROP, EDGE>, LPR, VEC>);
+  }
+  return lng ? reinterpret_cast<const void*>(&da_fwd_long_kernel<V2Fam<SHARED, DROP, EDGE, BF16>, LPR, VEC>)
+             : reinterpret_cast<const void*>(&da_fwd_row_kernel<V2Fam<SHARED, DROP, EDGE, BF16>, LPR, VEC>);
 }
-template <bool SHARED, bool DROP, bool EDGE>
+template <bool SHARED, bool DROP, bool EDGE, bool BF16 = false>
 static const void* v2_kernel_of(int pass, bool lng, int lpr, int vec) {
-  PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, SHARED, DROP, EDGE>(pass, lng)));
+  PYGAT_DA_DISPATCH(lpr, vec, return (v2_kernel_at<LPR, VEC, SHARED, DROP, EDGE, BF16>(pass, lng)));
   return nullptr;
 }
-// (the column pass has one variant per EDGE: whatever else is asked for, the kernels without SHARED and DROP; EDGE is without DROP)
-static const void* v2_kernel(bool shared, bool drop, bool edge, int pass, bool lng, int lpr, int vec) {
+// (the column pass has one variant per EDGE: whatever else is asked for, the kernels without SHARED and DROP; EDGE is without DROP;
+// bf16 tables: the forward alone, without DROP)
+static const void* v2_kernel(bool shared, bool drop, bool edge, bool bf16, int pass, bool lng, int lpr, int vec) {
+  if (bf16) {
+    if (drop || pass != 0) return nullptr;
+    if (edge) return shared ? v2_kernel_of<true, false, true, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, true, true>(pass, lng, lpr, vec);
+    return shared ? v2_kernel_of<true, false, false, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, false, true>(pass, lng, lpr, vec);
+  }
   if (pass == 2) return edge ? v2_kernel_of<false, false, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, false>(pass, lng, lpr, vec);
   if (edge) return shared ? v2_kernel_of<true, false, true>(pass, lng, lpr, vec) : v2_kernel_of<false, false, true>(pass, lng, lpr, vec);
   if (drop) return shared ? v2_kernel_of<true, true, false>(pass, lng, lpr, vec) : v2_kernel_of<false, true, false>(pass, lng, lpr, vec);
@@ -483,21 +502,24 @@ static const void* v2_kernel(bool shared, bool drop, bool edge, int pass, bool l
 
 // pygat_kernel_footprint: <prefix>{fwd,bwd,col}_{long,row}_l<LPR>v<VEC> (the lane shapes of PYGAT_DA_DISPATCH); k21_: a v table of its
 // own, k21s_: SHARED, k21d_: DROP, k21ds_: DROP and SHARED (fwd and bwd only: the column pass has one variant, under k21_);
-// k21e_: EDGE, with a column pass of its own, k21es_: EDGE and SHARED (fwd and bwd only); k21_da_stage, k21_da_final: the reduce of da
+// k21e_: EDGE, with a column pass of its own, k21es_: EDGE and SHARED (fwd and bwd only); k21h_, k21hs_, k21he_, k21hes_: the same four
+// on bf16 tables (fwd only); k21_da_stage, k21_da_final: the reduce of da
 int footprint_k21(const char* name, int* regs, int* scratch) {
-  static const struct { const char* prefix; bool shared, drop, edge; } names[] = {
-      {"k21_", false, false, false}, {"k21s_", true, false, false}, {"k21d_", false, true, false}, {"k21ds_", true, true, false},
-      {"k21e_", false, false, true}, {"k21es_", true, false, true}};
+  static const struct { const char* prefix; bool shared, drop, edge, bf16; } names[] = {
+      {"k21_", false, false, false, false}, {"k21s_", true, false, false, false}, {"k21d_", false, true, false, false},
+      {"k21ds_", true, true, false, false}, {"k21e_", false, false, true, false}, {"k21es_", true, false, true, false},
+      {"k21h_", false, false, false, true}, {"k21hs_", true, false, false, true}, {"k21he_", false, false, true, true},
+      {"k21hes_", true, false, true, true}};
   const void* fn = nullptr;
   if (!strcmp(name, "k21_da_stage")) fn = reinterpret_cast<const void*>(&v2_da_stage_kernel);
   if (!strcmp(name, "k21_da_final")) fn = reinterpret_cast<const void*>(&v2_da_final_kernel);
   DaKernelName k;
   for (const auto& nm : names)
     if (!fn && da_parse_kernel_name(name, nm.prefix, &k) && (k.pass != 2 || !(nm.shared || nm.drop)))
-      fn = v2_kernel(nm.shared, nm.drop, nm.edge, k.pass, k.lng, k.lpr, k.vec);
+      fn = v2_kernel(nm.shared, nm.drop, nm.edge, nm.bf16, k.pass, k.lng, k.lpr, k.vec);
   if (!fn) {
     set_error("kernel_footprint: unknown kernel '%s' (k21{,s,d,ds,e,es}_{fwd,bwd}_{long,row}_l<LPR>v<VEC>, "
-              "k21{,e}_col_{long,row}_l<LPR>v<VEC>, k21_da_stage, k21_da_final)", name);
+              "k21{,e}_col_{long,row}_l<LPR>v<VEC>, k21h{,s,e,es}_fwd_{long,row}_l<LPR>v<VEC>, k21_da_stage, k21_da_final)", name);
     return PYGAT_EINVAL;
   }
   return kernel_footprint_of(fn, regs, scratch);
@@ -527,8 +549,11 @@ struct V2Call {
   const int32_t *rowptr, *col, *perm;
   int H, F;
   float negative_slope;
-  const float *x_dst, *x_src, *a, *v;
+  const float *x_dst, *a;
+  const void *x_src, *v;       // float rows, or bf16 rows under kv_bytes == 2
   int64_t ldd, lds, ldv;
+  int kv_bytes;                // the size of an element of x_src, v and e: 4, or 2 (the bf16 inference forward, pass 0 alone, which
+                               // neither writes nor takes m and Z); 0 counts as 4
   float* out;
   int64_t ldo;
   float *m, *Z;
@@ -547,7 +572,8 @@ struct V2Call {
 // all three launchers: the checks, in one order; the kernel arguments; the piece kernel where there are long rows, then the row kernel
 static int v2_launch(const V2Call& c) {
   const char* what = c.what;
-  const bool cols = c.pass == 2;
+  const bool cols = c.pass == 2, bf16 = c.kv_bytes == 2;
+  const int talign = bf16 ? 8 : 16;                              // a lane's chunk of a gathered table: 4 elements
   const int rc = v2_check_shape(what, c.nnz, c.H, c.F);
   if (rc != PYGAT_OK) return rc;
   PYGAT_REQUIRE(isfinite(c.negative_slope), "%s: negative_slope=%g, a finite slope expected", what, (double)c.negative_slope);
@@ -558,14 +584,14 @@ static int v2_launch(const V2Call& c) {
   PYGAT_REQUIRE(c.rowptr, "%s: null %s", what, cols ? "rowptr_t" : "rowptr");
   PYGAT_REQUIRE(c.nnz == 0 || c.col, "%s: null %s", what, cols ? "row_t" : "col");
   DA_TABLE(what, "x_dst", c.x_dst, c.ldd, HF);
-  DA_TABLE(what, "x_src", c.x_src, c.lds, HF);
+  DA_TABLE_ALIGNED(what, "x_src", c.x_src, c.lds, HF, talign);
   PYGAT_REQUIRE(c.a, "%s: null a", what);
   PYGAT_REQUIRE(aligned16(c.a), "%s: a must be 16-byte aligned", what);
   if (!cols) {
-    if (c.v) DA_TABLE(what, "v", c.v, c.ldv, HF);              // (null: v is x_src, the SHARED kernels)
+    if (c.v) DA_TABLE_ALIGNED(what, "v", c.v, c.ldv, HF, talign);      // (null: v is x_src, the SHARED kernels)
     DA_TABLE(what, "out", c.out, c.ldo, HF);
-    PYGAT_REQUIRE(c.m, "%s: null m", what);
-    PYGAT_REQUIRE(c.Z, "%s: null Z", what);
+    PYGAT_REQUIRE(c.m || bf16, "%s: null m", what);
+    PYGAT_REQUIRE(c.Z || bf16, "%s: null Z", what);
   }
   PYGAT_REQUIRE(c.ws, "%s: null workspace", what);
   PYGAT_REQUIRE(aligned16(c.ws), "%s: the workspace must be 16-byte aligned", what);
@@ -582,7 +608,7 @@ static int v2_launch(const V2Call& c) {
     PYGAT_REQUIRE(aligned16(c.da), "%s: da must be 16-byte aligned", what);
   }
   if (c.edge) {
-    const int re = da_check_edge(what, c.nnz, HF, c.ed);
+    const int re = da_check_edge(what, c.nnz, HF, c.ed, talign);
     if (re != PYGAT_OK) return re;
   }
   DropRng rng;
@@ -595,9 +621,10 @@ static int v2_launch(const V2Call& c) {
   memset(&g, 0, sizeof(g));
   g.n = c.n; g.H = c.H; g.F = c.F; g.NCH = HF / 4; g.LH = c.F / 4; g.nnz = c.nnz; g.rowptr = c.rowptr; g.col = c.col;
   g.scale = c.negative_slope; g.bias = c.a; g.part = static_cast<float*>(c.ws); g.pstride = da_pstride(c.H, c.F);
-  if (cols) { g.q = c.x_src; g.ldq = c.lds; g.k = c.x_dst; g.ldk = c.ldd; }
+  if (cols) { g.q = static_cast<const float*>(c.x_src); g.ldq = c.lds; g.k = c.x_dst; g.ldk = c.ldd; }
   else {
-    g.q = c.x_dst; g.ldq = c.ldd; g.k = c.x_src; g.ldk = c.lds; g.v = c.v; g.ldv = c.ldv;
+    g.q = c.x_dst; g.ldq = c.ldd; g.k = static_cast<const float*>(c.x_src); g.ldk = c.lds; g.v = static_cast<const float*>(c.v);
+    g.ldv = c.ldv;
     g.out = c.out; g.ldo = c.ldo; g.m = c.m; g.Z = c.Z;
   }
   if (c.pass != 0) { g.perm = c.perm; g.dq = c.dx; g.lddq = c.lddx; g.S = c.S; }   // (the forward walks in CSR order alone)
@@ -616,8 +643,8 @@ static int v2_launch(const V2Call& c) {
   }
   hipStream_t st = (hipStream_t)c.stream;
   const bool shared = !cols && !c.v;
-  da_launch_pair(v2_kernel(shared, c.dropout, c.edge, c.pass, true, gd.lpr, gd.vec),
-                 v2_kernel(shared, c.dropout, c.edge, c.pass, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks, c.stream);
+  da_launch_pair(v2_kernel(shared, c.dropout, c.edge, bf16, c.pass, true, gd.lpr, gd.vec),
+                 v2_kernel(shared, c.dropout, c.edge, bf16, c.pass, false, gd.lpr, gd.vec), g, gd.chunks, gd.blocks, c.stream);
   if (cols) {
     const int nrec = (int)(gd.chunks + 4 * gd.blocks);
     hipLaunchKernelGGL(v2_da_stage_kernel, dim3(V2_DA_STAGE), dim3(256), 0, st, HF, nrec, (const float*)g.de, stage);
@@ -715,6 +742,30 @@ extern "C" int pygat_v2_attn_edge_forward(int n_rows, int64_t nnz, const int32_t
   c.what = "v2_attn_edge_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
   c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
   c.out = out; c.ldo = ldo; c.m = m; c.Z = Z; c.ws = ws; c.stream = stream; c.edge = true; c.ed = {e, lde, nullptr, 0};
+  return v2_launch(c);
+}
+
+// the two inference forwards on bf16 tables (8-byte aligned rows, strides in elements): the BF16 instantiations of the forward pair,
+// x_src, v and (the edge one) e rows of bf16 values; x_dst, a and out stay float.  m and Z are neither taken nor written
+extern "C" int pygat_v2_attn_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, int H, int F,
+                                          float negative_slope, const float* x_dst, int64_t ldd, const void* x_src, int64_t lds,
+                                          const float* a, const void* v, int64_t ldv, float* out, int64_t ldo, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_bf16_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.H = H; c.F = F;
+  c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
+  c.kv_bytes = 2; c.out = out; c.ldo = ldo; c.ws = ws; c.stream = stream;
+  return v2_launch(c);
+}
+
+extern "C" int pygat_v2_attn_edge_bf16_forward(int n_rows, int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                               int H, int F, float negative_slope, const float* x_dst, int64_t ldd, const void* x_src,
+                                               int64_t lds, const float* a, const void* v, int64_t ldv, const void* e, int64_t lde,
+                                               float* out, int64_t ldo, void* ws, void* stream) {
+  V2Call c = {};
+  c.what = "v2_attn_edge_bf16_forward"; c.pass = 0; c.n = n_rows; c.nnz = nnz; c.rowptr = rowptr; c.col = col; c.perm = perm; c.H = H;
+  c.F = F; c.negative_slope = negative_slope; c.x_dst = x_dst; c.ldd = ldd; c.x_src = x_src; c.lds = lds; c.a = a; c.v = v; c.ldv = ldv;
+  c.kv_bytes = 2; c.out = out; c.ldo = ldo; c.ws = ws; c.stream = stream; c.edge = true;
+  c.ed = {static_cast<const float*>(e), lde, nullptr, 0};
   return v2_launch(c);
 }
 

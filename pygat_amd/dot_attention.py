@@ -79,6 +79,25 @@ def _slope(op: str, negative_slope) -> float:
     return float(negative_slope)
 
 
+def _require_inference(op: str, f32_op: str, tensors):
+    """The bf16-table siblings of additive_attention and gatv2_attention are forward only: with grad mode on, an argument that
+    requires grad is refused, and the message names both ways out."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        raise ValueError(f"pygat_amd {op}: bfloat16 tables are for inference (there is no backward through this op) and an argument "
+                         f"requires grad: call it under torch.no_grad(), or use {f32_op} on float32 tables")
+
+
+def _require_dtypes(op: str, named):
+    """named = ((name, tensor | None, dtype), ...) of a bf16-table op: which of its tensors are bfloat16 tables and which stay
+    float32.  A tensor of the other kind is refused in words that name it and both dtypes (anything that is no tensor is left to
+    _require_tensor)."""
+    for name, t, dtype in named:
+        if isinstance(t, torch.Tensor) and t.dtype != dtype:
+            role = ("a bfloat16 table of this op (make it once: t.bfloat16())" if dtype == torch.bfloat16 else
+                    "float32 in this op: only the row tables of H * F values are bfloat16")
+            raise ValueError(f"pygat_amd {op}: {name} must be {dtype}, not {t.dtype}: it is {role}")
+
+
 def _tables(op: str, pattern, q, others, bf16_others: bool = False):
     """The refusals both ops share -> (H, F, no head axis): q [n_rows, (H,) F]; others = ((name, tensor), ...) over the columns,
     float32 like q, or bfloat16 where bf16_others (dot_attention's inference forward)."""

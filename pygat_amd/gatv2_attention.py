@@ -14,6 +14,9 @@
                                                                 # the softmax, drawn in the kernels from a seed on the device
     out = gatv2_attention_edge(pattern, x_dst, x_src, a, lin_edge(edge_attr).view(E, H, F))    # edge features inside the score, before
                                                                 # LeakyReLU (PyG's GATv2Conv with edge_dim); differentiable in e too
+    with torch.no_grad():                                       # inference: bf16 tables, made once -- half the gathered bytes, the bits
+        out = gatv2_attention_bf16(pattern, x_dst, x_src16, a)       # of gatv2_attention(pattern, x_dst, x_src16.float(), a)
+        out = gatv2_attention_edge_bf16(pattern, x_dst, x_src16, a, e16)      # ... and of gatv2_attention_edge on the widened tables
 
 The nonlinearity sits inside the sum over the features, so the score needs a whole F-wide row per entry and cannot be written as
 additive_attention's sum of two per-node scalars.  A row's softmax runs over exactly its entries; repeated (row, col) pairs are separate
@@ -31,33 +34,38 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import _E_WANT, _drop_p, _drop_seed, _require_heads, _require_pattern, _require_tensor, _slope
+from .dot_attention import (_E_WANT, _drop_p, _drop_seed, _require_dtypes, _require_heads, _require_inference, _require_pattern,
+                            _require_tensor, _slope)
 from .dropout import STREAM_ATT
 from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
 
 _OP = "gatv2_attention"
 _OP_DROP = "gatv2_attention_dropout"
 _OP_EDGE = "gatv2_attention_edge"
+_OP_BF16 = "gatv2_attention_bf16"
+_OP_EDGE_BF16 = "gatv2_attention_edge_bf16"
 _PAD_HINT = ("zero-pad the columns of all four tensors (x_dst, x_src, a and v) to the next allowed F: zero columns of a add nothing "
              "to a score, and the first F columns of the result are unchanged")
 
 
-def _checked(pattern, x_dst, x_src, a, v, op: str = _OP):
-    """Every refusal that looks at the pattern and the tensors, under the op's name -> (H, F)."""
+def _checked(pattern, x_dst, x_src, a, v, op: str = _OP, sfx: str = ""):
+    """Every refusal that looks at the pattern and the tensors, under the op's name -> (H, F).  sfx "16": x_src and v are the bfloat16
+    tables x_src16 and v16 of the bf16 ops (their dtypes were looked at by _require_dtypes)."""
     _require_pattern(op, pattern)
-    for name, t in (("x_dst", x_dst), ("x_src", x_src), ("a", a), ("v", v)):
-        _require_tensor(op, pattern, name, t)
+    xn, vn = "x_src" + sfx, "v" + sfx
+    for name, t in (("x_dst", x_dst), (xn, x_src), ("a", a), (vn, v)):
+        _require_tensor(op, pattern, name, t, torch.bfloat16 if sfx and name in (xn, vn) else torch.float32)
     if x_dst.dim() not in (2, 3):
         raise ValueError(f"pygat_amd {op}: x_dst [n_rows, F] or [n_rows, H, F] expected, got {tuple(x_dst.shape)}")
-    for name, t in (("x_src", x_src), ("v", v)):
+    for name, t in ((xn, x_src), (vn, v)):
         if t.dim() != x_dst.dim() or t.shape[1:] != x_dst.shape[1:]:
             raise ValueError(f"pygat_amd {op}: {name} {tuple(t.shape)} does not match x_dst {tuple(x_dst.shape)}: the same number of "
                              f"heads and the same width expected")
     if a.shape != x_dst.shape[1:]:
         raise ValueError(f"pygat_amd {op}: a {tuple(a.shape)} does not match x_dst {tuple(x_dst.shape)}: a [F] with x_dst [n_rows, F], "
                          f"or a [H, F] with x_dst [n_rows, H, F], expected")
-    for name, t, rows, side in (("x_dst", x_dst, pattern.n_rows, "rows"), ("x_src", x_src, pattern.n_cols, "columns"),
-                                ("v", v, pattern.n_cols, "columns")):
+    for name, t, rows, side in (("x_dst", x_dst, pattern.n_rows, "rows"), (xn, x_src, pattern.n_cols, "columns"),
+                                (vn, v, pattern.n_cols, "columns")):
         if t.shape[0] != rows:
             raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
     H, F = (1 if x_dst.dim() == 2 else int(x_dst.shape[1])), int(x_dst.shape[-1])
@@ -69,19 +77,21 @@ def _workspace(pattern, H: int, F: int, dev):
     return torch.empty(_lib.v2_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=dev)
 
 
-def _checked_e(pattern, x_dst, e, op: str = _OP_EDGE):
+def _checked_e(pattern, x_dst, e, op: str = _OP_EDGE, name: str = "e"):
     """The refusals of e's shape, after _checked: a row per entry, shaped like a row of x_dst."""
     if tuple(e.shape) != (pattern.nnz,) + tuple(x_dst.shape[1:]):
-        raise ValueError(f"pygat_amd {op}: e {[pattern.nnz] + list(x_dst.shape[1:])} expected for E = {pattern.nnz} entries and x_dst "
+        raise ValueError(f"pygat_amd {op}: {name} {[pattern.nnz] + list(x_dst.shape[1:])} expected for E = {pattern.nnz} entries and x_dst "
                          f"{tuple(x_dst.shape)} -- (E,) + x_dst.shape[1:], a row per entry -- got {tuple(e.shape)}")
 
 
 def _edge_rows(e, HF: int):
-    """e as the launchers take it -> (tensor, leading dimension): the tensor itself where its rows are H * F dense floats a multiple
-    of 4 floats apart and 16-byte aligned (a column slice of a wider tensor: no copy), a contiguous copy otherwise."""
+    """e as the launchers take it -> (tensor, leading dimension): the tensor itself where its rows are H * F dense elements a multiple
+    of 4 elements apart and aligned to a lane's chunk of 4 (16 bytes of float32, 8 of bfloat16; a column slice of a wider tensor: no
+    copy), a contiguous copy otherwise."""
     e = e.detach()
     inner = e.dim() == 2 or e.shape[1] == 1 or e.stride(1) == e.shape[2]
-    if e.shape[0] > 1 and e.stride(-1) == 1 and inner and e.stride(0) >= HF and e.stride(0) % 4 == 0 and e.data_ptr() % 16 == 0:
+    chunk = 4 * e.element_size()
+    if e.shape[0] > 1 and e.stride(-1) == 1 and inner and e.stride(0) >= HF and e.stride(0) % 4 == 0 and e.data_ptr() % chunk == 0:
         return e, e.stride(0)
     return e.contiguous(), HF
 
@@ -194,8 +204,8 @@ def gatv2_attention(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tens
     add nothing to a score.
     Not provided: a per-entry term or edge features in this op (a feature row per entry inside the score is the sibling op's,
     gatv2_attention_edge; a scalar term per entry is not provided), dropout on the coefficients (that is the sibling op's,
-    gatv2_attention_dropout), bfloat16 tables, the value product fused into the column pass (dv is a K17 launch on the transposed
-    pattern)."""
+    gatv2_attention_dropout), the value product fused into the column pass (dv is a K17 launch on the transposed pattern).
+    Inference on bfloat16 tables is the sibling op's, gatv2_attention_bf16."""
     slope = _slope(_OP, negative_slope)
     if v is None:
         return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src, slope, True)
@@ -251,8 +261,8 @@ def gatv2_attention_edge(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch
     there is no column pass.  A row without entries gets zeros; a row of one entry (i, j) gets v[j] bit for bit and an all-zero row of
     de; a pattern without entries launches nothing.  float32 GPU tensors with gatv2_attention's limits (1 <= H <= 64, F a power of two
     in 4..256, H * F <= 1024).
-    Not provided: dropout on the coefficients together with edge features, bfloat16 tables, e in the value sum, a scalar term per
-    entry, the value product fused into the column pass."""
+    Not provided: dropout on the coefficients together with edge features, e in the value sum, a scalar term per entry, the value
+    product fused into the column pass.  Inference on bfloat16 tables is the sibling op's, gatv2_attention_edge_bf16."""
     op = _OP_EDGE
     if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (x_dst, x_src, a, v, e)):
         raise ValueError(f"pygat_amd {op}: x_dst, x_src, a, v and e must be float32: there are no bfloat16 tables in this op")
@@ -261,3 +271,66 @@ def gatv2_attention_edge(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch
     _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op)
     _checked_e(pattern, x_dst, e, op)
     return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, None, e)
+
+
+def _forward_bf16(op: str, pattern, x_dst, x_src16, a, v16, e16, negative_slope):
+    """gatv2_attention_bf16 (e16 None) and gatv2_attention_edge_bf16: every refusal, then one launch of the bf16 forward on the tables
+    as they are -- nothing is widened, nothing is kept for a backward."""
+    slope = _slope(op, negative_slope)
+    _require_inference(op, _OP_EDGE if op == _OP_EDGE_BF16 else _OP, (x_dst, x_src16, a, v16, e16))
+    _require_dtypes(op, (("x_dst", x_dst, torch.float32), ("x_src16", x_src16, torch.bfloat16), ("a", a, torch.float32),
+                         ("v16", v16, torch.bfloat16), ("e16", e16, torch.bfloat16)))
+    if op == _OP_EDGE_BF16:
+        _require_tensor(op, pattern, "e16", e16, torch.bfloat16, want=_E_WANT)     # (a None here would be gatv2_attention_bf16)
+    H, F = _checked(pattern, x_dst, x_src16, a, x_src16 if v16 is None else v16, op, sfx="16")
+    if e16 is not None:
+        _checked_e(pattern, x_dst, e16, op, "e16")
+    if pattern.nnz == 0:                                           # every row is without entries: zeros, and nothing is launched
+        return torch.zeros_like(x_dst)
+    xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src16, a))
+    vc = None if v16 is None else v16.detach().contiguous()
+    n, HF, dev = pattern.n_rows, H * F, xd.device
+    with torch.cuda.device(dev):
+        out = torch.empty(n, HF, dtype=torch.float32, device=dev)
+        ws = _workspace(pattern, H, F, dev)
+        tables = (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF)
+        rest = (_ptr(out), HF, _ptr(ws), _stream())
+        if e16 is None:                                            # (no entry index is needed: CSR order alone)
+            check(lib.pygat_v2_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), *tables, *rest),
+                  "v2_attn_bf16_forward")
+        else:                                                      # (the entry index places the rows of e16: perm)
+            ec, lde = _edge_rows(e16, HF)
+            check(lib.pygat_v2_attn_edge_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
+                                                      *tables, _ptr(ec), lde, *rest), "v2_attn_edge_bf16_forward")
+    return out.view(x_dst.shape)
+
+
+def gatv2_attention_bf16(pattern: EdgePattern, x_dst: torch.Tensor, x_src16: torch.Tensor, a: torch.Tensor,
+                         v16: Optional[torch.Tensor] = None, negative_slope: float = 0.2) -> torch.Tensor:
+    """gatv2_attention for inference on bfloat16 tables: x_src16 [n_cols, H, F] (or [n_cols, F]) and v16 (None, or like x_src16) are
+    torch.bfloat16, made once (x_src.bfloat16()); x_dst, a and the result stay float32.  The result is gatv2_attention(pattern, x_dst,
+    x_src16.float(), a, None if v16 is None else v16.float(), negative_slope) bit for bit: on the BF16 instantiations of the K21
+    forward kernels a lane loads the same 4 row elements as 8 bytes and widens them in registers, and everything after the load is the
+    float32 kernels' arithmetic in their order -- at half the gathered bytes and half the memory of the tables; no float32 copy of
+    either is made.  v16=None: the widened x_src16 row of the one gather per entry serves the score and the sum.  Forward only: nothing
+    is saved, no per-row softmax state is written and no transpose of the pattern is built.  With grad mode on and an argument that
+    requires grad it raises: call it under torch.no_grad(), or use gatv2_attention on float32 tables.  A float32 x_src16 or v16, or a
+    bfloat16 x_dst or a, is refused.  A row without entries gets zeros; a pattern without entries launches nothing.  The limits are
+    gatv2_attention's: 1 <= H <= 64, F a power of two in 4..256, H * F <= 1024.
+    Not provided: a backward, dropout, bfloat16 x_dst, a or results."""
+    return _forward_bf16(_OP_BF16, pattern, x_dst, x_src16, a, v16, None, negative_slope)
+
+
+def gatv2_attention_edge_bf16(pattern: EdgePattern, x_dst: torch.Tensor, x_src16: torch.Tensor, a: torch.Tensor, e16: torch.Tensor,
+                              v16: Optional[torch.Tensor] = None, negative_slope: float = 0.2) -> torch.Tensor:
+    """gatv2_attention_edge for inference on bfloat16 tables: x_src16, v16 (None, or like x_src16) and e16 [E, H, F] (or [E, F]; a row
+    per entry at the caller's entry index) are torch.bfloat16; x_dst, a and the result stay float32.  The result is
+    gatv2_attention_edge on x_src16.float(), v16.float() and e16.float() bit for bit (the BF16 | EDGE instantiations of the K21 forward
+    kernels: 8-byte loads widened in registers, the float32 kernels' arithmetic after them) -- at half the bytes of the e stream, the
+    largest of the op and one no cache can hold, and of the gathered rows.  A row-strided e16 -- a column slice of a wider bfloat16
+    tensor, the row stride a multiple of 4 elements and the first row 8-byte aligned -- is read in place by its leading dimension; no
+    float32 copy of any table is made.  Forward only, as gatv2_attention_bf16: with grad mode on and an argument that requires grad it
+    raises (torch.no_grad(), or gatv2_attention_edge on float32 tables).  A float32 x_src16, v16 or e16, or a bfloat16 x_dst or a, is
+    refused.  A pattern without entries launches nothing.  The limits are gatv2_attention's.
+    Not provided: a backward, dropout, bfloat16 x_dst, a or results."""
+    return _forward_bf16(_OP_EDGE_BF16, pattern, x_dst, x_src16, a, v16, e16, negative_slope)

@@ -8,6 +8,8 @@ against the same result from the parts it fuses -- two torch gathers and their s
     python tools/additive_attention_bench.py --dropout [...]    # additive_attention_dropout at p = 0.5: three contenders alternated --
                                                                 # fused with dropout, fused without, the composition with the mask as a
                                                                 # tensor -> profiles/additive_attention_dropout_bench.jsonl
+    python tools/additive_attention_bench.py --tables-bf16 [--logit] [...]    # additive_attention_bf16: the fp32 fused forward against
+                                                                # the bf16 one -> profiles/additive_attention_bf16_bench.jsonl
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
@@ -19,7 +21,13 @@ Before timing, both contenders' outputs are priced on the same seeded inputs by 
 computation on the CPU, on a sample of rows (the row of most entries among them).  Algorithmic bytes are computed from the shapes (E
 entries, N rows, M columns, H heads, R = H F floats per row), `*_bytes` below; `*_roof_ms` is their time at 8 TB/s, and
 `*_roof_fraction` that over the measured time: the whole op's share of the HBM roof on the byte model, not a kernel's.  Recorded, not
-gated.  One JSON object per shape, appended."""
+gated.  One JSON object per shape, appended.
+
+--tables-bf16 measures the inference forward on a bfloat16 v table (forward only), as tools/dot_attention_bench.py --kv-bf16 does for
+K19: in the one child process it alternates the fused forward on a float32 table with the fused forward on a bfloat16 table.  Both are
+fed the same values -- N(0, 1) draws rounded to bfloat16, and those widened to float32 -- so the two outputs are compared with
+torch.equal here (asserted); the bfloat16 one is priced on the sampled rows as above.  Recorded per shape: both medians with their
+spreads, their ratio, and the byte model's ratio beside it.  The yardstick is the float32 forward of the same run."""
 import argparse
 import json
 import os
@@ -56,6 +64,13 @@ def fused_backward_bytes(E, N, M, H, F, logit=False, perm=False):
     rows = E * entry + N * (4 * H + 2 * 4 * R + 2 * 4 * H + 4 * H + 4)
     cols = E * (4 * H + 8 + 4 * R) + M * (4 * R + 4) + E * (4 * H + 8 + sectors(4 * H)) + M * (4 * H + 4)
     return rows + cols
+
+
+def bf16_forward_bytes(E, N, M, H, F, logit=False, perm=False):
+    """A bfloat16 v table (inference): the v row at 2 bytes a value; m and Z are not written; everything else as fused_forward_bytes."""
+    R = H * F
+    entry = 4 + sectors(4 * H) + 2 * R + ((4 * H + (4 if perm else 0)) if logit else 0)
+    return E * entry + N * (4 * H + 4 * R + 4)
 
 
 def composed_forward_bytes(E, N, M, H, F, logit=False):
@@ -152,6 +167,11 @@ def measure(args):
                 return torch.autograd.grad(fn(*mine), mine, G)
             return run
 
+        if args.tables_bf16:
+            measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, rp_t, col_t, deg, rows, perm)
+            del s_dst, s_src, v, G, leaves
+            torch.cuda.empty_cache()
+            continue
         if args.dropout:
             measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg,
                             rows, perm, forward_of, both_of, fused)
@@ -191,6 +211,54 @@ def measure(args):
         print(json.dumps(res), flush=True)
         del s_dst, s_src, v, G, leaves
         torch.cuda.empty_cache()
+
+
+def measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, rp_t, col_t, deg, rows, perm):
+    """--tables-bf16, one shape: the fused forward on a float32 v table against additive_attention_bf16 on the bfloat16 table of the
+    same values (with --logit: both with the [E, H] edge_logit); one JSON object."""
+    N, E, R = pattern.n_rows, pattern.nnz, H * F
+    s_dst, s_src, v = leaves[:3]
+    u = leaves[3] if args.logit else None
+    v16 = v.bfloat16()
+    vw = v16.float()                                                # the same values, widened: what the float32 contender is fed
+
+    def run_fp32():
+        with torch.no_grad():
+            return pg.additive_attention(pattern, s_dst, s_src, vw, slope, u)
+
+    def run_bf16():
+        with torch.no_grad():
+            return pg.additive_attention_bf16(pattern, s_dst, s_src, v16, slope, u)
+
+    out_w, out_h = run_fp32(), run_bf16()
+    equal = bool(torch.equal(out_w, out_h))
+    assert equal, f"{shape}: the bf16 forward differs from the float32 forward on the widened table"
+    ref64 = sampled_reference(rp_t, col_t, rows, s_dst, s_src, vw, slope, torch.float64, u)
+    ref32 = sampled_reference(rp_t, col_t, rows, s_dst, s_src, vw, slope, torch.float32, u)
+    err_h = parity.close_fwd(out_h[rows.to(dev)], ref64, f"{shape} fused, bf16 table: out", ref32)
+    res = {"bench": "additive_attention --tables-bf16" + (" --logit" if args.logit else ""), "device": torch.cuda.get_device_name(0),
+           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
+           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
+           "longest_checked_row": int(deg[rows].max()), "out_bf16_equals_out_fp32_on_widened_tables": equal,
+           "out_err_fused_bf16": err_h, "out_err_fp32_reference": parity.err(ref32, ref64),
+           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, args.logit, perm),
+           "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F, args.logit, perm)}
+    res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
+    del out_w, out_h
+    r = alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
+    for name in ("fused_fp32", "fused_bf16"):
+        res[f"{name}_forward_ms"], res[f"{name}_forward_spread_ms"] = r[name]
+        res[f"{name}_forward_roof_fraction"] = (1e3 * res["fused_bf16_forward_bytes" if name == "fused_bf16" else "fused_forward_bytes"]
+                                                / HBM_BYTES_PER_S / res[f"{name}_forward_ms"])
+    res["measured_ratio"] = res["fused_bf16_forward_ms"] / res["fused_fp32_forward_ms"]
+    res["faster_by_more_than_the_spread"] = (res["fused_fp32_forward_ms"] - res["fused_bf16_forward_ms"]
+                                             > max(res["fused_fp32_forward_spread_ms"], res["fused_bf16_forward_spread_ms"]))
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+    print(json.dumps(res), flush=True)
+    print(f"{shape}: the bf16 table takes {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
+          f"{res['byte_model_ratio']:.3f}; outputs bit-equal", flush=True)
 
 
 def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg, rows,
@@ -257,11 +325,18 @@ def main():
     ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
     ap.add_argument("--dropout", action="store_true", help="additive_attention_dropout at p = 0.5 against the op without dropout and "
                     "the composition with the mask as a tensor")
-    ap.add_argument("--out", default=None, help="profiles/additive_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout")
+    ap.add_argument("--tables-bf16", action="store_true", help="additive_attention_bf16: the fused forward on a float32 v table against "
+                    "the fused forward on the bfloat16 table of the same values (forward only; goes with --logit)")
+    ap.add_argument("--out", default=None, help="profiles/additive_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout, "
+                    "..._bf16_bench.jsonl under --tables-bf16")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.tables_bf16 and args.dropout:
+        ap.error("--tables-bf16 and --dropout are two measurements: there is no op with both")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "additive_attention_dropout_bench.jsonl" if args.dropout else "additive_attention_bench.jsonl")
+        name = "additive_attention_bf16_bench.jsonl" if args.tables_bf16 else "additive_attention_dropout_bench.jsonl" if args.dropout else \
+            "additive_attention_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.child:
         return measure(args)
     cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]

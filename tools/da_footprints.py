@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Device code of K19, K20 and K21 of two trees, per kernel by its pygat_kernel_footprint name, without a device run.
 
-    tools/da_footprints.py PARENT_CSRC THIS_CSRC > profiles/attention_dropout_footprints.txt     (..._edge_footprints.txt)
+    tools/da_footprints.py PARENT_CSRC THIS_CSRC > profiles/attention_dropout_footprints.txt     (..._edge_, ..._bf16_footprints.txt)
 
 Each directory holds the three files compiled for the device alone (the Makefile's flags and --cuda-device-only -c, to
 <file>.dev.o).  Per kernel: clang-offload-bundler --unbundle, llvm-readelf --notes (register counts, scratch bytes, spill counts) and
@@ -18,8 +18,9 @@ import tempfile
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
 FILES = ("k19_dot_attention", "k20_additive_attention", "k21_gatv2_attention")
 K19 = {0: "k19_", 1: "k19b_", 8: "k19h_", 9: "k19hb_", 2: "k19d_", 3: "k19db_", 4: "k19e_", 5: "k19eb_"}
-K20 = {(0, 0): "k20_", (1, 0): "k20u_", (0, 1): "k20d_", (1, 1): "k20du_"}
-K21 = {(0, 0, 0): "k21_", (1, 0, 0): "k21s_", (0, 1, 0): "k21d_", (1, 1, 0): "k21ds_", (0, 0, 1): "k21e_", (1, 0, 1): "k21es_"}   # SHARED, DROP, EDGE
+K20 = {(0, 0, 0): "k20_", (1, 0, 0): "k20u_", (0, 1, 0): "k20d_", (1, 1, 0): "k20du_", (0, 0, 1): "k20h_", (1, 0, 1): "k20hu_"}   # LOGIT, DROP, BF16
+K21 = {(0, 0, 0, 0): "k21_", (1, 0, 0, 0): "k21s_", (0, 1, 0, 0): "k21d_", (1, 1, 0, 0): "k21ds_", (0, 0, 1, 0): "k21e_", (1, 0, 1, 0): "k21es_",
+       (0, 0, 0, 1): "k21h_", (1, 0, 0, 1): "k21hs_", (0, 0, 1, 1): "k21he_", (1, 0, 1, 1): "k21hes_"}                  # SHARED, DROP, EDGE, BF16
 
 
 def run(*cmd):
@@ -41,12 +42,12 @@ def footprint_name(sym):
         if name.endswith("DaFam"):
             prefix = K19[ints(fargs)[0]]
         elif name.endswith("AaFam"):
-            prefix = K20[(flags(fargs) + (0,))[:2]]
+            prefix = K20[(flags(fargs) + (0, 0))[:3]]
         else:
-            prefix = K21[(flags(fargs) + (0, 0))[:3]]               # (a tree from before a flag has the kernels without it)
+            prefix = K21[(flags(fargs) + (0, 0, 0))[:4]]            # (a tree from before a flag has the kernels without it)
     else:
         lpr, vec = ints(args)[:2]
-        prefix = K20[(flags(args) + (0,))[:2]] if owner == "aa" else ("k21e_" if flags(args) == (1,) else "k21_")
+        prefix = K20[(flags(args) + (0,))[:2] + (0,)] if owner == "aa" else ("k21e_" if flags(args) == (1,) else "k21_")
     return f"{prefix}{d}_{kind}_l{lpr}v{vec}"
 
 

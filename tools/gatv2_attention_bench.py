@@ -6,6 +6,8 @@ features, edge_softmax (K18) and spmm (pygat_spmm_forward) -- at H x F = 8x16 an
 
     python tools/gatv2_attention_bench.py [--shapes 8x16,8x64] [--values shared,separate] [--rounds 5] [--steps 10] [--warmup 10]
                                           [--dropout | --edge] [--out profiles/gatv2_attention_bench.jsonl]
+    python tools/gatv2_attention_bench.py --tables-bf16 [--edge] [...]      # gatv2_attention_bf16 (gatv2_attention_edge_bf16): the fp32
+                                          # fused forward against the bf16 one -> profiles/gatv2_attention_bf16_bench.jsonl (..._edge_bf16_...)
 
 The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
 run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
@@ -22,7 +24,14 @@ gated.  One JSON object per (shape, value table), appended.
 --edge measures pygat_amd.gatv2_attention_edge, e [E, H, F] ~ N(0, 1) inside the score, against the same composition with e added
 before leaky_relu, at 8x16 and 8x32 by default (an [E, R] tensor is 5.5 and 11 GB there; at 8x64 it is 22 GB, and the composition,
 which keeps some ten of them for autograd, runs only where the device has the room: otherwise the fused op is recorded alone and the
-line says so), into profiles/gatv2_attention_edge_bench.jsonl."""
+line says so), into profiles/gatv2_attention_edge_bench.jsonl.
+
+--tables-bf16 measures the inference forwards on bfloat16 tables (forward only), as tools/dot_attention_bench.py --kv-bf16 does for
+K19: in the one child process it alternates the fused forward on float32 tables with the fused forward on bfloat16 tables -- x_src,
+the separate v and, with --edge, e.  Both are fed the same values -- N(0, 1) draws rounded to bfloat16, and those widened to float32
+-- so the two outputs are compared with torch.equal here (asserted); the bfloat16 one is priced on the sampled rows as above.
+Recorded per (shape, value table): both medians with their spreads, their ratio, and the byte model's ratio beside it.  The yardstick
+is the float32 forward of the same run."""
 import argparse
 import json
 import os
@@ -47,6 +56,13 @@ def fused_forward_bytes(E, N, M, H, F, shared):
     x_dst read, out, m and Z written, the row pointer."""
     R = H * F
     return E * (4 + (1 if shared else 2) * 4 * R) + N * (2 * 4 * R + 2 * 4 * H + 4)
+
+
+def bf16_forward_bytes(E, N, M, H, F, shared, edge=False, perm=False):
+    """bfloat16 x_src, v and e tables (inference): their rows at 2 bytes a value; x_dst read and out written in float32; m and Z are
+    not written; with e the entry index where the pattern carries a permutation."""
+    R = H * F
+    return E * (4 + ((1 if shared else 2) + (1 if edge else 0)) * 2 * R + (4 if edge and perm else 0)) + N * (2 * 4 * R + 4)
 
 
 def fused_backward_bytes(E, N, M, H, F, shared, perm=False):
@@ -165,6 +181,12 @@ def measure(args):
                 return run
 
             v = leaves[-1] if not shared else x_src
+            if args.tables_bf16:
+                measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, rp_t, col_t, deg, rows,
+                             perm)
+                del x_dst, x_src, a, G, leaves, v
+                torch.cuda.empty_cache()
+                continue
             if args.edge:
                 measure_edge(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, G, row_d, col_d, rp_t,
                              col_t, deg, rows, perm)
@@ -211,6 +233,61 @@ def measure(args):
             print(json.dumps(res), flush=True)
             del x_dst, x_src, a, G, leaves, v
             torch.cuda.empty_cache()
+
+
+def measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, rp_t, col_t, deg, rows, perm):
+    """--tables-bf16, one shape and one kind of v: the fused forward on float32 tables against gatv2_attention_bf16 on the bfloat16
+    tables of the same values; with --edge gatv2_attention_edge against gatv2_attention_edge_bf16, e [E, H, F] among the tables; one
+    JSON object."""
+    N, E, shared = pattern.n_rows, pattern.nnz, values == "shared"
+    x_dst, a = leaves[0], leaves[2]
+    x16 = leaves[1].bfloat16()
+    v16 = None if shared else leaves[3].bfloat16()
+    e16 = torch.randn(E, H, F, generator=torch.Generator(device=dev).manual_seed(5), device=dev).bfloat16() if args.edge else None
+    xw, vw, ew = (None if t is None else t.float() for t in (x16, v16, e16))      # the same values, widened: the float32 contender's
+
+    def run_fp32():
+        with torch.no_grad():
+            if args.edge:
+                return pg.gatv2_attention_edge(pattern, x_dst, xw, a, ew, vw, slope)
+            return pg.gatv2_attention(pattern, x_dst, xw, a, vw, slope)
+
+    def run_bf16():
+        with torch.no_grad():
+            if args.edge:
+                return pg.gatv2_attention_edge_bf16(pattern, x_dst, x16, a, e16, v16, slope)
+            return pg.gatv2_attention_bf16(pattern, x_dst, x16, a, v16, slope)
+
+    out_w, out_h = run_fp32(), run_bf16()
+    equal = bool(torch.equal(out_w, out_h))
+    assert equal, f"{shape} {values}: the bf16 forward differs from the float32 forward on the widened tables"
+    ref64 = sampled_reference(rp_t, col_t, rows, x_dst, xw, a, xw if shared else vw, slope, torch.float64, e=ew)
+    ref32 = sampled_reference(rp_t, col_t, rows, x_dst, xw, a, xw if shared else vw, slope, torch.float32, e=ew)
+    err_h = parity.close_fwd(out_h[rows.to(dev)], ref64, f"{shape} {values} fused, bf16 tables: out", ref32)
+    fp32_bytes = fused_forward_bytes(E, N, N, H, F, shared) + (edge_bytes(E, H, F, perm)["fused_forward"] if args.edge else 0)
+    res = {"bench": "gatv2_attention --tables-bf16" + (" --edge" if args.edge else ""), "values": values,
+           "device": torch.cuda.get_device_name(0), "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H,
+           "F": F, "negative_slope": slope, "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup,
+           "checked_rows": int(rows.numel()), "longest_checked_row": int(deg[rows].max()),
+           "out_bf16_equals_out_fp32_on_widened_tables": equal, "out_err_fused_bf16": err_h,
+           "out_err_fp32_reference": parity.err(ref32, ref64), "fused_forward_bytes": fp32_bytes,
+           "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F, shared, args.edge, perm)}
+    res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
+    del out_w, out_h
+    r = alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
+    for name in ("fused_fp32", "fused_bf16"):
+        res[f"{name}_forward_ms"], res[f"{name}_forward_spread_ms"] = r[name]
+        res[f"{name}_forward_roof_fraction"] = (1e3 * res["fused_bf16_forward_bytes" if name == "fused_bf16" else "fused_forward_bytes"]
+                                                / HBM_BYTES_PER_S / res[f"{name}_forward_ms"])
+    res["measured_ratio"] = res["fused_bf16_forward_ms"] / res["fused_fp32_forward_ms"]
+    res["faster_by_more_than_the_spread"] = (res["fused_fp32_forward_ms"] - res["fused_bf16_forward_ms"]
+                                             > max(res["fused_fp32_forward_spread_ms"], res["fused_bf16_forward_spread_ms"]))
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+    print(json.dumps(res), flush=True)
+    print(f"{shape} {values}: bf16 tables take {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
+          f"{res['byte_model_ratio']:.3f}; outputs bit-equal", flush=True)
 
 
 def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, values, H, F, slope, leaves, v, row_d, col_d, rp_t, col_t, deg,
@@ -363,14 +440,20 @@ def main():
                     "composition with the mask as a tensor")
     ap.add_argument("--edge", action="store_true", help="gatv2_attention_edge, e [E, H, F] inside the score, against the composition "
                     "with e added before leaky_relu")
+    ap.add_argument("--tables-bf16", action="store_true", help="gatv2_attention_bf16 (with --edge: gatv2_attention_edge_bf16): the fused "
+                    "forward on float32 tables against the fused forward on the bfloat16 tables of the same values (forward only)")
     ap.add_argument("--out", default=None, help="profiles/gatv2_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout, "
-                    "..._edge_bench.jsonl under --edge")
+                    "..._edge_bench.jsonl under --edge, ..._bf16_bench.jsonl and ..._edge_bf16_bench.jsonl under --tables-bf16")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.edge and args.dropout:
         ap.error("--edge and --dropout are two measurements: there is no op with both")
     if args.shapes is None:
         args.shapes = "8x16,8x32" if args.edge else "8x16,8x64"
+    if args.tables_bf16 and args.dropout:
+        ap.error("--tables-bf16 and --dropout are two measurements: there is no op with both")
+    if args.out is None and args.tables_bf16:
+        args.out = os.path.join(ROOT, "profiles", "gatv2_attention_edge_bf16_bench.jsonl" if args.edge else "gatv2_attention_bf16_bench.jsonl")
     if args.out is None:
         name = "gatv2_attention_edge_bench.jsonl" if args.edge else "gatv2_attention_dropout_bench.jsonl" if args.dropout else \
             "gatv2_attention_bench.jsonl"
