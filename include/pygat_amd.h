@@ -957,6 +957,25 @@ int pygat_sample_workspace_bytes(int n, int n_dst, size_t* bytes);
 int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst, int fanout,
                        const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr, int32_t* blk_col,
                        int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws, void* stream);
+/* The same block sampled WEIGHTED BY EDGE, without replacement (Efraimidis-Spirakis / exponential clocks; the WEIGHTED instantiations
+ * of the K22 kernels), additive under ABI 16: pygat_sample_block's arguments plus weight, nnz floats (4-byte aligned), one per entry at
+ * its CSR position.  For the entry at position p with the Philox word k = key(p) above and w = weight[p]:
+ *   w == 0: never sampled.  w > 0, finite or +inf: its clock is c(p) = E(k) / w with E(k) = -ln(1 - (k + 0.5) / 2^32) a unit exponential
+ *     variate; a row keeps its fanout entries smallest in (c, p) among those with w > 0, and all of them if they number at most fanout.
+ *     w = +inf gives c = 0: the entry is always kept (a self loop, say); of more than fanout such entries the first fanout by position.
+ *   w < 0 or NaN in a row of dst: info[4] = 1 and the entry is never selected.  Rows that dst does not name are not looked at.
+ *   The clock is fp32 throughout: E = -log1pf(-u), u = ((float)k + 0.5f) 2^-32 for k < 2^31, else E = -logf(v), v = ((float)(~k) + 0.5f)
+ *     2^-32 (accurate logarithms; a few ulps from the exact value at every k); the key that is ordered is the bit pattern of E / w.  It
+ *     depends on (seed, hop, p, w) only, so the sample at a smaller fanout is a subset of the one at a larger fanout.  tests/
+ *     sampler_weighted_ref.py restates it in fp64.  No float is summed across lanes: two runs give the same bits.
+ * Everything else -- kept positions ascending, src_nodes, the outputs and their bounds, ws (pygat_sample_workspace_bytes: the weighted
+ * passes need no more) and the refusals, each after `weighted_block: ` -- is pygat_sample_block's; info has FIVE words: (entries,
+ * sources, id outside, id repeated, bad weight).  The rows' counts are their numbers of positive weights: the long rows are listed
+ * before the counts are scanned and counted by a work-group each, so no single thread walks a hub's weights. */
+int pygat_weighted_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst, int fanout,
+                         const float* weight, const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr,
+                         int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws,
+                         void* stream);
 
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads

@@ -16,6 +16,15 @@
 //   relabel   per entry: row by binary search in blk_rowptr, local column = dst position (marker) or n_dst + rank; edge_rc
 // The marker table is never cleared: marker[j] = m names a dst row only if 1 <= m <= n_dst and dst[m - 1] == j, which is checked.
 // Every loop runs over a row's positions or a list's length; all arithmetic is integer.
+//
+// pygat_weighted_block is the same passes on the WEIGHTED instantiations: the key of an entry becomes sample_weighted_key(Philox word,
+// weight[p]) (rng.h: the bits of an fp32 exponential clock, which order like it), and only entries of weight > 0 are candidates.  The
+// weight is re-read wherever the key is recomputed.  What changes in the order of the passes: a row's count is its number of positive
+// weights, which no single thread may walk along a hub, so the list of long rows is built BEFORE the counts are scanned (the long-row
+// flags depend on the degrees only) and a work-group per long row counts it (count_long); info[0] is then written by a pass of its own
+// (entries), and a weight that is negative or NaN raises info[4] in count / count_long.  A row is kept whole ("all") when its count is
+// below the fanout; at exactly the fanout the select runs and ends at the row's largest key, which keeps the same entries.  No float
+// is summed across lanes and no result depends on an order of atomics: two runs give the same bits.
 #include "common.h"
 #include "rng.h"
 #include <string.h>
@@ -38,8 +47,12 @@ __device__ __forceinline__ bool sample_row(int n, const int32_t* __restrict__ ro
 
 __device__ __forceinline__ int sample_quads(int b, int e) { return ((e - 1) >> 2) - (b >> 2) + 1; }   // e > b
 
+// WEIGHTED: d is the number of positive weights of a short row (at most 256 of them, one thread); a long row's count is left to
+// sample_count_long_kernel
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void sample_count_kernel(int n, const int32_t* __restrict__ rowptr, int n_dst,
-                                                           const int64_t* __restrict__ dst, int fanout, int32_t* __restrict__ marker,
+                                                           const int64_t* __restrict__ dst, int fanout,
+                                                           const float* __restrict__ weight, int32_t* __restrict__ marker,
                                                            int32_t* __restrict__ cnt, int32_t* __restrict__ lflag,
                                                            int64_t* __restrict__ src_nodes, int32_t* __restrict__ info) {
   const int r = blockIdx.x * 256 + threadIdx.x;
@@ -47,10 +60,23 @@ __global__ __launch_bounds__(256) void sample_count_kernel(int n, const int32_t*
   int b, e;
   if (sample_row(n, rowptr, dst, r, &b, &e)) marker[dst[r]] = r + 1;
   else info[2] = 1;
-  const int d = e - b;
+  int d = e - b;
+  const int lf = (d > 0 && sample_quads(b, e) > SAMPLE_WAVE_QUADS) ? 1 : 0;
+  if constexpr (WEIGHTED) {
+    d = 0;
+    if (!lf) {
+      bool bad = false;
+      for (int p = b; p < e; ++p) {
+        const float w = weight[p];
+        d += w > 0.f ? 1 : 0;
+        bad |= !(w >= 0.f);
+      }
+      if (bad) info[4] = 1;
+    }
+  }
   src_nodes[r] = dst[r];
   cnt[r] = d < fanout ? d : fanout;
-  lflag[r] = (d > 0 && sample_quads(b, e) > SAMPLE_WAVE_QUADS) ? 1 : 0;
+  lflag[r] = lf;
 }
 
 __global__ __launch_bounds__(256) void sample_verify_kernel(int n, int n_dst, const int64_t* __restrict__ dst,
@@ -61,12 +87,19 @@ __global__ __launch_bounds__(256) void sample_verify_kernel(int n, int n_dst, co
   if (id >= 0 && id < n && marker[id] != r + 1) info[3] = 1;
 }
 
+// WEIGHTED: the counts are not scanned yet (blk_rowptr is not read); sample_entries_kernel writes info[0] later
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void sample_list_kernel(int n_dst, const int32_t* __restrict__ lflag, const int32_t* __restrict__ lptr,
                                                           const int32_t* __restrict__ blk_rowptr, int32_t* __restrict__ llist,
                                                           int32_t* __restrict__ info) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r == 0) info[0] = blk_rowptr[n_dst];
+  if constexpr (!WEIGHTED)
+    if (r == 0) info[0] = blk_rowptr[n_dst];
   if (r < n_dst && lflag[r]) llist[lptr[r]] = r;
+}
+
+__global__ void sample_entries_kernel(int n_dst, const int32_t* __restrict__ blk_rowptr, int32_t* __restrict__ info) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) info[0] = blk_rowptr[n_dst];
 }
 
 // exclusive prefix of v over the THREADS (64: the wave; 256: the work-group, wsum = 4 ints of LDS) threads, and the total
@@ -101,10 +134,11 @@ __device__ __forceinline__ int sample_scan(int v, int* total, int* wsum) {
 // Writes the kept positions of the row [b, e) in ascending order at edge_ids[base ...] (at most `room` of them) and marks their
 // columns: all of them (`all`), or those with key < T and the first `ties` of those with key == T.  The index of an entry is the
 // number of kept entries in front of it, from one prefix count over (entries below T, entries equal to T) per THREADS Philox calls.
-template <int THREADS>
+// WEIGHTED: only entries of weight > 0 are kept at all, and the key is sample_weighted_key of the Philox word and the weight.
+template <int THREADS, bool WEIGHTED>
 __device__ __forceinline__ void sample_emit(uint64_t seed, uint32_t hop, int b, int e, bool all, uint32_t T, int ties, int64_t base,
-                                            int room, const int32_t* __restrict__ gcol, int64_t* __restrict__ edge_ids,
-                                            int32_t* __restrict__ mark, int* wsum) {
+                                            int room, const int32_t* __restrict__ gcol, const float* __restrict__ weight,
+                                            int64_t* __restrict__ edge_ids, int32_t* __restrict__ mark, int* wsum) {
   const int tid = THREADS == 64 ? (threadIdx.x & 63) : threadIdx.x;
   const int qb = b >> 2, qe = (e - 1) >> 2;
   int less_before = 0, eq_before = 0;
@@ -116,8 +150,14 @@ __device__ __forceinline__ void sample_emit(uint64_t seed, uint32_t hop, int b, 
       if (!all) w = sample_keys4(seed, (uint32_t)q, hop);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t p = 4u * (uint32_t)q + j, key = word_of(w, j);
+        const uint32_t p = 4u * (uint32_t)q + j;
+        uint32_t key = word_of(w, j);
         if (p >= (uint32_t)b && p < (uint32_t)e) {
+          if constexpr (WEIGHTED) {
+            const float wt = weight[p];
+            if (!(wt > 0.f)) continue;
+            if (!all) key = sample_weighted_key(key, wt);
+          }
           if (all || key < T) lm |= 1u << j;
           else if (key == T) em |= 1u << j;
         }
@@ -153,10 +193,40 @@ __device__ __forceinline__ bool sample_room(const int32_t* __restrict__ blk_rowp
   return true;
 }
 
+// ---- WEIGHTED, long rows: the number of positive weights of every row of the list, one work-group per row (integer sums) ----------
+__global__ __launch_bounds__(256) void sample_count_long_kernel(int n, const int32_t* __restrict__ rowptr, int n_dst,
+                                                                const int64_t* __restrict__ dst, int fanout,
+                                                                const float* __restrict__ weight, const int32_t* __restrict__ lptr,
+                                                                const int32_t* __restrict__ llist, int32_t* __restrict__ cnt,
+                                                                int32_t* __restrict__ info) {
+  __shared__ int wsum[4];
+  int n_long = lptr[n_dst];
+  if (n_long > n_dst) n_long = n_dst;
+  for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
+    const int r = llist[x];
+    if (r < 0 || r >= n_dst) continue;
+    int b, e;
+    sample_row(n, rowptr, dst, r, &b, &e);
+    int pos = 0;
+    bool bad = false;
+    for (int p = b + (int)threadIdx.x; p < e; p += 256) {
+      const float w = weight[p];
+      pos += w > 0.f ? 1 : 0;
+      bad |= !(w >= 0.f);
+    }
+    if (bad) info[4] = 1;
+    int tot;
+    sample_scan<256>(pos, &tot, wsum);
+    if (threadIdx.x == 0) cnt[r] = tot < fanout ? tot : fanout;
+  }
+}
+
 // ---- short rows: one wave per row, the row's keys in registers (one Philox call per lane) ---------------------------------------
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const int32_t* __restrict__ rowptr,
                                                                  const int32_t* __restrict__ gcol, int n_dst,
                                                                  const int64_t* __restrict__ dst, int fanout,
+                                                                 const float* __restrict__ weight,
                                                                  const uint64_t* __restrict__ seedp, uint32_t hop, int64_t cap,
                                                                  const int32_t* __restrict__ blk_rowptr, int64_t* __restrict__ edge_ids,
                                                                  int32_t* __restrict__ mark, const int32_t* __restrict__ info) {
@@ -168,7 +238,7 @@ __global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const in
   sample_row(n, rowptr, dst, r, &b, &e);
   if (e <= b || sample_quads(b, e) > SAMPLE_WAVE_QUADS || !sample_room(blk_rowptr, info, r, cap, &base, &room)) return;
   const uint64_t seed = seedp[0];
-  const bool all = e - b <= fanout;
+  const bool all = WEIGHTED ? room < fanout : e - b <= fanout;     // (room = min(positive weights, fanout))
   uint32_t T = 0;
   int kk = 0;
   if (!all) {
@@ -179,7 +249,14 @@ __global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const in
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t p = 4u * (uint32_t)q + j;
-      if (p >= (uint32_t)b && p < (uint32_t)e) cand |= 1u << j;
+      if (p >= (uint32_t)b && p < (uint32_t)e) {
+        if constexpr (WEIGHTED) {
+          const float wt = weight[p];
+          if (!(wt > 0.f)) continue;
+          w[j] = sample_weighted_key(w[j], wt);
+        }
+        cand |= 1u << j;
+      }
     }
     kk = fanout;                       // the rank sought among the candidates, 1-based
     for (int bit = 31; bit >= 0; --bit) {
@@ -195,13 +272,15 @@ __global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const in
       else { kk -= c0; T |= 1u << bit; cand &= ~z; }
     }
   }
-  sample_emit<64>(seed, hop, b, e, all, T, kk, base, room, gcol, edge_ids, mark, nullptr);
+  sample_emit<64, WEIGHTED>(seed, hop, b, e, all, T, kk, base, room, gcol, weight, edge_ids, mark, nullptr);
 }
 
 // ---- long rows: one work-group per row of the list, radix select over the 32-bit key in four 8-bit passes -------------------------
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const int32_t* __restrict__ rowptr,
                                                                   const int32_t* __restrict__ gcol, int n_dst,
                                                                   const int64_t* __restrict__ dst, int fanout,
+                                                                  const float* __restrict__ weight,
                                                                   const uint64_t* __restrict__ seedp, uint32_t hop, int64_t cap,
                                                                   const int32_t* __restrict__ blk_rowptr,
                                                                   const int32_t* __restrict__ lptr, const int32_t* __restrict__ llist,
@@ -221,7 +300,7 @@ __global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const i
     int64_t base;
     sample_row(n, rowptr, dst, r, &b, &e);
     if (e <= b || !sample_room(blk_rowptr, info, r, cap, &base, &room)) continue;
-    const bool all = e - b <= fanout;
+    const bool all = WEIGHTED ? room < fanout : e - b <= fanout;
     uint32_t T = 0;
     int kk = fanout;
     if (!all) {
@@ -234,8 +313,15 @@ __global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const i
           const uint4 w = sample_keys4(seed, (uint32_t)q, hop);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const uint32_t p = 4u * (uint32_t)q + j, key = word_of(w, j);
-            const bool in = p >= (uint32_t)b && p < (uint32_t)e && (pass == 0 || ((key ^ T) >> (shift + 8)) == 0);
+            const uint32_t p = 4u * (uint32_t)q + j;
+            uint32_t key = word_of(w, j);
+            bool in = p >= (uint32_t)b && p < (uint32_t)e;
+            if constexpr (WEIGHTED) {
+              const float wt = in ? weight[p] : 0.f;
+              in = wt > 0.f;
+              if (in) key = sample_weighted_key(key, wt);
+            }
+            in = in && (pass == 0 || ((key ^ T) >> (shift + 8)) == 0);
             if (in) atomicAdd(&hist[(key >> shift) & 255u], 1);
           }
         }
@@ -250,7 +336,7 @@ __global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const i
         __syncthreads();
       }
     }
-    sample_emit<256>(seed, hop, b, e, all, T, kk, base, room, gcol, edge_ids, mark, wsum);
+    sample_emit<256, WEIGHTED>(seed, hop, b, e, all, T, kk, base, room, gcol, weight, edge_ids, mark, wsum);
   }
 }
 
@@ -319,18 +405,25 @@ static inline SampleWs sample_ws(int n, int n_dst) {
 
 int footprint_k22(const char* name, int* regs, int* scratch) {
   static const struct { const char* name; const void* fn; } names[] = {
-      {"k22_count", reinterpret_cast<const void*>(&sample_count_kernel)},
+      {"k22_count", reinterpret_cast<const void*>(&sample_count_kernel<false>)},
       {"k22_verify", reinterpret_cast<const void*>(&sample_verify_kernel)},
-      {"k22_list", reinterpret_cast<const void*>(&sample_list_kernel)},
-      {"k22_select_wave", reinterpret_cast<const void*>(&sample_select_wave_kernel)},
-      {"k22_select_block", reinterpret_cast<const void*>(&sample_select_block_kernel)},
+      {"k22_list", reinterpret_cast<const void*>(&sample_list_kernel<false>)},
+      {"k22_select_wave", reinterpret_cast<const void*>(&sample_select_wave_kernel<false>)},
+      {"k22_select_block", reinterpret_cast<const void*>(&sample_select_block_kernel<false>)},
       {"k22_clear_dst", reinterpret_cast<const void*>(&sample_clear_dst_kernel)},
       {"k22_sources", reinterpret_cast<const void*>(&sample_sources_kernel)},
-      {"k22_relabel", reinterpret_cast<const void*>(&sample_relabel_kernel)}};
+      {"k22_relabel", reinterpret_cast<const void*>(&sample_relabel_kernel)},
+      {"k22_count_weighted", reinterpret_cast<const void*>(&sample_count_kernel<true>)},
+      {"k22_list_weighted", reinterpret_cast<const void*>(&sample_list_kernel<true>)},
+      {"k22_count_long_weighted", reinterpret_cast<const void*>(&sample_count_long_kernel)},
+      {"k22_entries_weighted", reinterpret_cast<const void*>(&sample_entries_kernel)},
+      {"k22_select_wave_weighted", reinterpret_cast<const void*>(&sample_select_wave_kernel<true>)},
+      {"k22_select_block_weighted", reinterpret_cast<const void*>(&sample_select_block_kernel<true>)}};
   for (const auto& nm : names)
     if (!strcmp(name, nm.name)) return kernel_footprint_of(nm.fn, regs, scratch);
   set_error("kernel_footprint: unknown kernel '%s' (k22_count, k22_verify, k22_list, k22_select_wave, k22_select_block, k22_clear_dst, "
-            "k22_sources, k22_relabel)", name);
+            "k22_sources, k22_relabel; k22_count_weighted, k22_list_weighted, k22_count_long_weighted, k22_entries_weighted, "
+            "k22_select_wave_weighted, k22_select_block_weighted)", name);
   return PYGAT_EINVAL;
 }
 
@@ -345,11 +438,12 @@ extern "C" int pygat_sample_workspace_bytes(int n, int n_dst, size_t* bytes) {
   return PYGAT_OK;
 }
 
-extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst,
-                                  int fanout, const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr,
-                                  int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws,
-                                  void* stream) {
-  const char* what = "sample_block";
+// the passes of pygat_sample_block (weight == nullptr) and pygat_weighted_block, in the order the head of this file gives
+template <bool WEIGHTED>
+static int sample_block_launch(const char* what, int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst,
+                               const int64_t* dst, int fanout, const float* weight, const void* seed, uint32_t hop, int64_t cap,
+                               int64_t src_cap, int32_t* blk_rowptr, int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids,
+                               int64_t* src_nodes, int32_t* info, void* ws, void* stream) {
   PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
                 (long long)nnz);
   PYGAT_REQUIRE(n_dst > 0 && n_dst <= n, "%s: n_dst=%d: 1 <= n_dst <= n = %d expected (distinct node ids)", what, n_dst, n);
@@ -358,6 +452,10 @@ extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, con
       {rowptr, "rowptr"}, {col, "col"}, {dst, "dst"}, {seed, "seed"}, {blk_rowptr, "blk_rowptr"}, {blk_col, "blk_col"},
       {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {src_nodes, "src_nodes"}, {info, "info"}, {ws, "workspace"}};
   for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  if constexpr (WEIGHTED) {
+    PYGAT_REQUIRE(weight, "%s: null weight", what);
+    PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(weight) & 3u) == 0, "%s: weight must be 4-byte aligned", what);
+  }
   PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
   PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 7u) == 0 && (reinterpret_cast<uintptr_t>(edge_ids) & 7u) == 0 &&
                     (reinterpret_cast<uintptr_t>(src_nodes) & 7u) == 0, "%s: dst, edge_ids and src_nodes must be 8-byte aligned", what);
@@ -373,26 +471,40 @@ extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, con
   hipStream_t st = (hipStream_t)stream;
   const uint64_t* seedp = (const uint64_t*)seed;
   const dim3 rows((unsigned)cdiv(n_dst, 256)), tpb(256);
+  const dim3 longs((unsigned)(n_dst < SAMPLE_LONG_BLOCKS ? n_dst : SAMPLE_LONG_BLOCKS));
 
   hipError_t me = hipMemsetAsync(mark, 0, (size_t)n * sizeof(int32_t), st);
-  if (me == hipSuccess) me = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), st);
+  if (me == hipSuccess) me = hipMemsetAsync(info, 0, (WEIGHTED ? 5 : 4) * sizeof(int32_t), st);
   if (me != hipSuccess) {
     (void)hipGetLastError();
     set_error("%s: %s", what, hipGetErrorString(me));
     return PYGAT_EHIP;
   }
-  hipLaunchKernelGGL(sample_count_kernel, rows, tpb, 0, st, n, rowptr, n_dst, dst, fanout, marker, cnt, lflag, src_nodes, info);
+  hipLaunchKernelGGL(sample_count_kernel<WEIGHTED>, rows, tpb, 0, st, n, rowptr, n_dst, dst, fanout, weight, marker, cnt, lflag,
+                     src_nodes, info);
   hipLaunchKernelGGL(sample_verify_kernel, rows, tpb, 0, st, n, n_dst, dst, marker, info);
   PYGAT_CHECK_LAUNCH(what);
-  int rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
-  rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
-  hipLaunchKernelGGL(sample_list_kernel, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
-  hipLaunchKernelGGL(sample_select_wave_kernel, dim3((unsigned)cdiv(n_dst, 4)), tpb, 0, st, n, rowptr, col, n_dst, dst, fanout, seedp,
-                     hop, cap, blk_rowptr, edge_ids, mark, info);
-  hipLaunchKernelGGL(sample_select_block_kernel, dim3((unsigned)(n_dst < SAMPLE_LONG_BLOCKS ? n_dst : SAMPLE_LONG_BLOCKS)), tpb, 0, st, n,
-                     rowptr, col, n_dst, dst, fanout, seedp, hop, cap, blk_rowptr, lptr, llist, edge_ids, mark, info);
+  int rc;
+  if constexpr (WEIGHTED) {
+    rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
+    if (rc != PYGAT_OK) return rc;
+    hipLaunchKernelGGL(sample_list_kernel<true>, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
+    hipLaunchKernelGGL(sample_count_long_kernel, longs, tpb, 0, st, n, rowptr, n_dst, dst, fanout, weight, lptr, llist, cnt, info);
+    PYGAT_CHECK_LAUNCH(what);
+    rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
+    if (rc != PYGAT_OK) return rc;
+    hipLaunchKernelGGL(sample_entries_kernel, dim3(1), dim3(64), 0, st, n_dst, blk_rowptr, info);
+  } else {
+    rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
+    if (rc != PYGAT_OK) return rc;
+    rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
+    if (rc != PYGAT_OK) return rc;
+    hipLaunchKernelGGL(sample_list_kernel<false>, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
+  }
+  hipLaunchKernelGGL(sample_select_wave_kernel<WEIGHTED>, dim3((unsigned)cdiv(n_dst, 4)), tpb, 0, st, n, rowptr, col, n_dst, dst, fanout,
+                     weight, seedp, hop, cap, blk_rowptr, edge_ids, mark, info);
+  hipLaunchKernelGGL(sample_select_block_kernel<WEIGHTED>, longs, tpb, 0, st, n, rowptr, col, n_dst, dst, fanout, weight, seedp, hop, cap,
+                     blk_rowptr, lptr, llist, edge_ids, mark, info);
   hipLaunchKernelGGL(sample_clear_dst_kernel, rows, tpb, 0, st, n, n_dst, dst, mark);
   PYGAT_CHECK_LAUNCH(what);
   rc = pygat_exclusive_scan_i32(mark, n, rank, tiles, stream);
@@ -402,4 +514,20 @@ extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, con
                      rank, edge_ids, blk_col, edge_rc, info);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
+}
+
+extern "C" int pygat_sample_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst,
+                                  int fanout, const void* seed, uint32_t hop, int64_t cap, int64_t src_cap, int32_t* blk_rowptr,
+                                  int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws,
+                                  void* stream) {
+  return sample_block_launch<false>("sample_block", n, nnz, rowptr, col, n_dst, dst, fanout, nullptr, seed, hop, cap, src_cap, blk_rowptr,
+                                    blk_col, edge_rc, edge_ids, src_nodes, info, ws, stream);
+}
+
+extern "C" int pygat_weighted_block(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int n_dst, const int64_t* dst,
+                                    int fanout, const float* weight, const void* seed, uint32_t hop, int64_t cap, int64_t src_cap,
+                                    int32_t* blk_rowptr, int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes,
+                                    int32_t* info, void* ws, void* stream) {
+  return sample_block_launch<true>("weighted_block", n, nnz, rowptr, col, n_dst, dst, fanout, weight, seed, hop, cap, src_cap, blk_rowptr,
+                                   blk_col, edge_rc, edge_ids, src_nodes, info, ws, stream);
 }

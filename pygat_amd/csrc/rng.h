@@ -12,7 +12,8 @@
 //   sample_keys4 the selection keys of the neighbour sampler (k22_sample.hip): key of the entry at CSR position p of the graph =
 //               word (p & 3) of Philox(counter = (p >> 2, hop, STREAM_SAMPLE = 4, 0), key = seed) -- four POSITIONS per call; the
 //               key depends on the position alone.  No other layout uses stream 4.  tests/sampler_ref.py restates it and
-//               tests/test_gpu_sample.py compares the sampled blocks with it entry for entry.
+//               tests/test_gpu_sample.py compares the sampled blocks with it entry for entry.  The weighted sampler orders a row
+//               by sample_weighted_key(that word, weight[p]) instead.
 #pragma once
 #include "common.h"
 
@@ -57,6 +58,15 @@ __device__ __forceinline__ uint32_t keep_nibble(const DropRng& g, const uint4& w
 constexpr uint32_t STREAM_SAMPLE = 4;
 __device__ __forceinline__ uint4 sample_keys4(uint64_t seed, uint32_t q, uint32_t hop) {
   return philox4x32_10(make_uint4(q, hop, STREAM_SAMPLE, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+
+// The weighted sampler's key of an entry with Philox word k and weight w > 0 (finite or +inf): the bits of the exponential clock
+// E(k) / w, E(k) = -ln(1 - (k + 0.5) / 2^32), all in fp32.  Two branches keep the logarithm's condition number at or below 1.45 at
+// every k (one log1pf(-u) alone loses 1e-4 relative near u -> 1).  E > 0, so the clock is a non-negative float (+0 at w = +inf, +inf
+// where E / w overflows) and its bit pattern orders like it.  tests/sampler_weighted_ref.py restates the clock in fp64.
+__device__ __forceinline__ uint32_t sample_weighted_key(uint32_t k, float w) {
+  const float E = k < 0x80000000u ? -log1pf(-(((float)k + 0.5f) * 0x1p-32f)) : -logf(((float)(~k) + 0.5f) * 0x1p-32f);
+  return __float_as_uint(E / w);
 }
 
 static inline bool make_rng(float p, const void* seed, uint32_t stream_id, DropRng* g) {
