@@ -11,17 +11,11 @@ against the same result from the parts it fuses -- two torch gathers and their s
     python tools/additive_attention_bench.py --tables-bf16 [--logit] [...]    # additive_attention_bf16: the fp32 fused forward against
                                                                 # the bf16 one -> profiles/additive_attention_bf16_bench.jsonl
 
-The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
-run in that one process, alternated round by round, timed as tools/dot_attention_bench.py times its own (`alternate`, imported): a
-round times `steps` calls of one contender, each between two HIP events, then the same of the other.  Reported per contender: the
-median over all rounds x steps timed calls (at least 50) and the spread of the rounds' medians: a difference below that spread is
-not a difference.  The composition is the baseline: it runs kernels and torch ops that exist without K20, on the same build.
-
-Before timing, both contenders' outputs are priced on the same seeded inputs by the rule of tests/parity.py against an fp64
-computation on the CPU, on a sample of rows (the row of most entries among them).  Algorithmic bytes are computed from the shapes (E
-entries, N rows, M columns, H heads, R = H F floats per row), `*_bytes` below; `*_roof_ms` is their time at 8 TB/s, and
-`*_roof_fraction` that over the measured time: the whole op's share of the HBM roof on the byte model, not a kernel's.  Recorded, not
-gated.  One JSON object per shape, appended.
+How it measures is tools/pattern_bench.py's and described there: the child process under `timeout -k 10 <--limit seconds>`, the
+contenders alternated round by round in that one process (at least 50 timed calls each), the median and the spread, the pricing of
+the outputs on a sample of rows, the roof fields.  The composition is the baseline: it runs kernels and torch ops that exist without
+K20, on the same build.  Algorithmic bytes are computed from the shapes (E entries, N rows, M columns, H heads, R = H F floats per
+row), `*_bytes` below.  Recorded, not gated.  One JSON object per shape, appended.
 
 --tables-bf16 measures the inference forward on a bfloat16 v table (forward only), as tools/dot_attention_bench.py --kv-bf16 does for
 K19: in the one child process it alternates the fused forward on a float32 table with the fused forward on a bfloat16 table.  Both are
@@ -29,22 +23,12 @@ fed the same values -- N(0, 1) draws rounded to bfloat16, and those widened to f
 torch.equal here (asserted); the bfloat16 one is priced on the sampled rows as above.  Recorded per shape: both medians with their
 spreads, their ratio, and the byte model's ratio beside it.  The yardstick is the float32 forward of the same run."""
 import argparse
-import json
 import os
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pattern_bench as pb
+from pattern_bench import sectors          # the H floats of s_src[j] are counted at 32-byte granularity
 
-SAMPLE_ROWS = 1024
-HBM_BYTES_PER_S = 8e12
-SECTOR = 32          # bytes: the granularity at which the H floats of s_src[j] are counted
-
-
-def sectors(nbytes):
-    return -(-nbytes // SECTOR) * SECTOR
+SLOPE = 0.2
 
 
 def fused_forward_bytes(E, N, M, H, F, logit=False, perm=False):
@@ -95,128 +79,81 @@ def composed_backward_bytes(E, N, M, H, F, logit=False):
     return spmm_b + softmax_b + rest
 
 
-def sampled_reference(rp, col, rows, s_dst, s_src, v, slope, dtype, u=None, mask=None):
-    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of leaky_relu((s_dst_i + s_src_j) + u) (u [E, H],
-    at the CSR position), times mask (the dropout's, [E, H] at the CSR position, after the softmax), times v_j."""
-    import torch
-    deg = rp[rows + 1] - rp[rows]
-    idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
-    sub = torch.repeat_interleave(torch.arange(rows.numel()), deg)
-    cols, inv = torch.unique(col[idx], return_inverse=True)
-    sd, ss, vs = s_dst[rows].cpu().to(dtype), s_src[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
-    z = sd[sub] + ss[inv]
-    if u is not None:
-        z = z + u[idx.to(u.device)].cpu().to(dtype)
-    l = torch.nn.functional.leaky_relu(z, slope)
-    m = torch.full(sd.shape, -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, l.shape[1]), l, "amax")
-    p = torch.exp(l - m[sub])
-    alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
-    if mask is not None:
-        alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
-    return torch.zeros(rows.numel(), v.shape[1], v.shape[2], dtype=dtype).index_add(0, sub, alpha[:, :, None] * vs[inv])
+def record_bytes(mode, E, N, H, F, logit=False, perm=False):
+    """The byte-model fields of a record of `mode` (None, "dropout" or "tables_bf16"), in the record's order; the bench's pattern is
+    square, M = N.  Under dropout the fused op's bytes are those without it -- the mask is drawn in registers -- but for the
+    permutation entry the forward now reads where the pattern carries one and no logit made it read it already."""
+    fused_f = fused_forward_bytes(E, N, N, H, F, logit, perm)
+    if mode == "tables_bf16":
+        return {"fused_forward_bytes": fused_f, "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F, logit, perm)}
+    fused_b = fused_backward_bytes(E, N, N, H, F, logit, perm)
+    if mode == "dropout":
+        return {"fused_forward_bytes": fused_f, "fused_backward_bytes": fused_b,
+                "fused_dropout_extra_forward_bytes": 0 if logit or not perm else 4 * E, "mask_tensor_bytes": E * H * 4}
+    return {"fused_forward_bytes": fused_f, "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F, logit),
+            "fused_backward_bytes": fused_b, "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F, logit)}
 
 
-def measure(args):
+def entry_terms(s_dst, s_src, v, u=None):
+    """The family's part of pattern_bench.sampled_reference: the score leaky_relu((s_dst_i + s_src_j) + u) (u [E, H], at the CSR
+    position) and the values v_j."""
     import torch
-    if not torch.cuda.is_available():
-        sys.exit("additive_attention_bench: needs a GPU (a time taken anywhere else says nothing)")
+
+    def terms(dtype, part, idx, sub, cols, inv):
+        z = pb.taken(s_dst, part, dtype)[sub] + pb.taken(s_src, cols, dtype)[inv]
+        if u is not None:
+            z = z + pb.taken(u, idx, dtype)
+        return torch.nn.functional.leaky_relu(z, SLOPE), pb.taken(v, cols, dtype)[inv]
+    return terms
+
+
+def inputs(args, w, H, F):
+    """One shape's seeded tensors and the two plain contenders -> (leaves, G, fused, composed); leaves: s_dst, s_src, v and, under
+    --logit, the [E, H] edge_logit."""
+    import torch
     import pygat_amd as pg
-    from pygat_amd.rmat import rmat_csr_numpy
-    from dot_attention_bench import alternate                        # the one timing routine of these tools
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity                                                     # the one tolerance rule (tests/parity.py)
-    dev = torch.device("cuda", 0)
-    rp, col = rmat_csr_numpy(args.scale, args.draws, seed=1)
-    graph = pg.CSRGraph(torch.from_numpy(rp).to(dev), torch.from_numpy(col).to(dev))
-    pattern = graph.edge_pattern()
-    pattern.transposed()
-    N, E = graph.n, graph.nnz
-    row_d, col_d = pattern.edge_rc[:, 0].long(), pattern.edge_rc[:, 1].long()
-    rp_t, col_t = torch.from_numpy(rp).long(), torch.from_numpy(col).long()
-    deg = rp_t[1:] - rp_t[:-1]
-    picked = torch.randperm(N, generator=torch.Generator().manual_seed(3))[:SAMPLE_ROWS]
-    rows = torch.unique(torch.cat([picked, torch.argmax(deg)[None]]))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    slope, perm = 0.2, pattern.perm is not None
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        g = torch.Generator(device=dev).manual_seed(2)
-        s_dst, s_src = (torch.randn(N, H, generator=g, device=dev) for _ in range(2))
-        v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(2))
-        leaves = (s_dst, s_src, v) + ((torch.randn(E, H, generator=g, device=dev),) if args.logit else ())
+    g = w.generator()
+    s_dst, s_src = (torch.randn(w.N, H, generator=g, device=w.dev) for _ in range(2))
+    v, G = (torch.randn(w.N, H, F, generator=g, device=w.dev) for _ in range(2))
+    leaves = (s_dst, s_src, v) + ((torch.randn(w.E, H, generator=g, device=w.dev),) if args.logit else ())
+    row_d, col_d = w.row_d, w.col_d
 
-        def fused(sd, ss, v_, u=None):
-            return pg.additive_attention(pattern, sd, ss, v_, slope, u)
+    def fused(sd, ss, v_, u=None):
+        return pg.additive_attention(w.pattern, sd, ss, v_, SLOPE, u)
 
-        def composed(sd, ss, v_, u=None):
-            z = sd[row_d] + ss[col_d]
-            if u is not None:
-                z = z + u
-            return pg.spmm(pattern, pg.edge_softmax(pattern, torch.nn.functional.leaky_relu(z, slope)), v_)
+    def composed(sd, ss, v_, u=None):
+        z = sd[row_d] + ss[col_d]
+        if u is not None:
+            z = z + u
+        return pg.spmm(w.pattern, pg.edge_softmax(w.pattern, torch.nn.functional.leaky_relu(z, SLOPE)), v_)
 
-        def forward_of(fn):
-            def run():
-                with torch.no_grad():
-                    return fn(*leaves)
-            return run
-
-        def both_of(fn):
-            mine = [t.detach().clone().requires_grad_(True) for t in leaves]
-
-            def run():
-                return torch.autograd.grad(fn(*mine), mine, G)
-            return run
-
-        if args.tables_bf16:
-            measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, rp_t, col_t, deg, rows, perm)
-            del s_dst, s_src, v, G, leaves
-            torch.cuda.empty_cache()
-            continue
-        if args.dropout:
-            measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg,
-                            rows, perm, forward_of, both_of, fused)
-            del s_dst, s_src, v, G, leaves
-            torch.cuda.empty_cache()
-            continue
-        # the same seeded inputs, both contenders priced on the sampled rows
-        out_f, out_c = forward_of(fused)(), forward_of(composed)()
-        ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float64, *leaves[3:])
-        ref32 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float32, *leaves[3:])
-        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused out", ref32)
-        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed out", ref32)
-        res = {"bench": "additive_attention" + (" --logit" if args.logit else ""), "device": torch.cuda.get_device_name(0),
-               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
-               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-               "longest_checked_row": int(deg[rows].max()), "out_err_fused": err_f, "out_err_composed": err_c,
-               "out_err_fp32_reference": parity.err(ref32, ref64), "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
-               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, args.logit, perm),
-               "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F, args.logit),
-               "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, args.logit, perm),
-               "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F, args.logit)}
-        del out_f, out_c
-        legs = [("forward", alternate({"fused": forward_of(fused), "composed": forward_of(composed)}, args.rounds, args.steps, args.warmup))]
-        if not args.forward_only:
-            legs.append(("forward_backward", alternate({"fused": both_of(fused), "composed": both_of(composed)}, args.rounds, args.steps,
-                                                       args.warmup)))
-        for what, r in legs:
-            for name in ("fused", "composed"):
-                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-            res[f"{what}_speedup"] = res[f"composed_{what}_ms"] / res[f"fused_{what}_ms"]
-            model = res["fused_forward_bytes"] + (res["fused_backward_bytes"] if what == "forward_backward" else 0)
-            res[f"fused_{what}_roof_ms"] = 1e3 * model / HBM_BYTES_PER_S
-            res[f"fused_{what}_roof_fraction"] = res[f"fused_{what}_roof_ms"] / res[f"fused_{what}_ms"]
-        res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        del s_dst, s_src, v, G, leaves
-        torch.cuda.empty_cache()
+    return leaves, G, fused, composed
 
 
-def measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, rp_t, col_t, deg, rows, perm):
-    """--tables-bf16, one shape: the fused forward on a float32 v table against additive_attention_bf16 on the bfloat16 table of the
-    same values (with --logit: both with the [E, H] edge_logit); one JSON object."""
-    N, E, R = pattern.n_rows, pattern.nnz, H * F
+def measure_plain(args, w, shape, H, F):
+    """No mode flag: the fused op against the composition (under --logit both with the edge_logit); one JSON object."""
+    import torch
+    leaves, G, fused, composed = inputs(args, w, H, F)
+    # the same seeded inputs, both contenders priced on the sampled rows
+    out_f, out_c = pb.forward_of(fused, leaves)(), pb.forward_of(composed, leaves)()
+    err_of, ref_err = pb.pricer(w, entry_terms(*leaves))
+    res = pb.base_record("additive_attention" + (" --logit" if args.logit else ""), args, w, H, F, negative_slope=SLOPE)
+    res.update({"out_err_fused": err_of(out_f, f"{shape} fused out"), "out_err_composed": err_of(out_c, f"{shape} composed out"),
+                "out_err_fp32_reference": ref_err, "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
+                **record_bytes(None, w.E, w.N, H, F, args.logit, w.perm)})
+    del out_f, out_c
+    legs = pb.run_legs(args, {"fused": (fused, leaves), "composed": (composed, leaves)}, G)
+    pb.add_legs(res, legs, speedup=("composed", "fused"), roof="fused")
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(w.dev)
+    pb.write(res, args.out)
+
+
+def measure_bf16(args, w, shape, H, F):
+    """--tables-bf16: the fused forward on a float32 v table against additive_attention_bf16 on the bfloat16 table of the same values
+    (with --logit: both with the [E, H] edge_logit); one JSON object."""
+    import torch
+    import pygat_amd as pg
+    leaves, G = inputs(args, w, H, F)[:2]      # (G is drawn and held though nothing reads it: peak_device_bytes has always counted it)
     s_dst, s_src, v = leaves[:3]
     u = leaves[3] if args.logit else None
     v16 = v.bfloat16()
@@ -224,123 +161,103 @@ def measure_bf16(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, 
 
     def run_fp32():
         with torch.no_grad():
-            return pg.additive_attention(pattern, s_dst, s_src, vw, slope, u)
+            return pg.additive_attention(w.pattern, s_dst, s_src, vw, SLOPE, u)
 
     def run_bf16():
         with torch.no_grad():
-            return pg.additive_attention_bf16(pattern, s_dst, s_src, v16, slope, u)
+            return pg.additive_attention_bf16(w.pattern, s_dst, s_src, v16, SLOPE, u)
 
     out_w, out_h = run_fp32(), run_bf16()
     equal = bool(torch.equal(out_w, out_h))
     assert equal, f"{shape}: the bf16 forward differs from the float32 forward on the widened table"
-    ref64 = sampled_reference(rp_t, col_t, rows, s_dst, s_src, vw, slope, torch.float64, u)
-    ref32 = sampled_reference(rp_t, col_t, rows, s_dst, s_src, vw, slope, torch.float32, u)
-    err_h = parity.close_fwd(out_h[rows.to(dev)], ref64, f"{shape} fused, bf16 table: out", ref32)
-    res = {"bench": "additive_attention --tables-bf16" + (" --logit" if args.logit else ""), "device": torch.cuda.get_device_name(0),
-           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
-           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-           "longest_checked_row": int(deg[rows].max()), "out_bf16_equals_out_fp32_on_widened_tables": equal,
-           "out_err_fused_bf16": err_h, "out_err_fp32_reference": parity.err(ref32, ref64),
-           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, args.logit, perm),
-           "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F, args.logit, perm)}
+    err_of, ref_err = pb.pricer(w, entry_terms(s_dst, s_src, vw, u))
+    res = pb.base_record("additive_attention --tables-bf16" + (" --logit" if args.logit else ""), args, w, H, F, negative_slope=SLOPE)
+    res.update({"out_bf16_equals_out_fp32_on_widened_tables": equal, "out_err_fused_bf16": err_of(out_h, f"{shape} fused, bf16 table: out"),
+                "out_err_fp32_reference": ref_err, **record_bytes("tables_bf16", w.E, w.N, H, F, args.logit, w.perm)})
     res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
     del out_w, out_h
-    r = alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
-    for name in ("fused_fp32", "fused_bf16"):
+    r = pb.alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
+    for name, model in (("fused_fp32", "fused_forward_bytes"), ("fused_bf16", "fused_bf16_forward_bytes")):
         res[f"{name}_forward_ms"], res[f"{name}_forward_spread_ms"] = r[name]
-        res[f"{name}_forward_roof_fraction"] = (1e3 * res["fused_bf16_forward_bytes" if name == "fused_bf16" else "fused_forward_bytes"]
-                                                / HBM_BYTES_PER_S / res[f"{name}_forward_ms"])
-    res["measured_ratio"] = res["fused_bf16_forward_ms"] / res["fused_fp32_forward_ms"]
-    res["faster_by_more_than_the_spread"] = (res["fused_fp32_forward_ms"] - res["fused_bf16_forward_ms"]
-                                             > max(res["fused_fp32_forward_spread_ms"], res["fused_bf16_forward_spread_ms"]))
-    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
-    with open(args.out, "a") as f:
-        f.write(json.dumps(res) + "\n")
-    print(json.dumps(res), flush=True)
+        res[f"{name}_forward_roof_fraction"] = 1e3 * res[model] / pb.HBM_BYTES_PER_S / res[f"{name}_forward_ms"]
+    pb.add_bf16_ratio(res)
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(w.dev)
+    pb.write(res, args.out)
     print(f"{shape}: the bf16 table takes {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
           f"{res['byte_model_ratio']:.3f}; outputs bit-equal", flush=True)
 
 
-def measure_dropout(args, torch, pg, parity, alternate, dev, pattern, shape, H, F, slope, leaves, G, row_d, col_d, rp_t, col_t, deg, rows,
-                    perm, forward_of, both_of, fused):
-    """--dropout, one shape: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object.  The fused
-    op's algorithmic bytes are those without dropout -- the mask is drawn in registers -- but for the permutation entry the forward now
-    reads where the pattern carries one (4 bytes an entry; this graph's pattern carries none)."""
+def measure_dropout(args, w, shape, H, F):
+    """--dropout: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object."""
+    import torch
+    import pygat_amd as pg
+    leaves, G, fused, _ = inputs(args, w, H, F)
     p = 0.5
-    seed = torch.tensor([20240607], dtype=torch.int64, device=dev)
-    N, E = pattern.n_rows, pattern.nnz
+    seed = torch.tensor([20240607], dtype=torch.int64, device=w.dev)
+    row_d, col_d = w.row_d, w.col_d
 
     def fused_dropout(sd, ss, v_, u=None):
-        return pg.additive_attention_dropout(pattern, sd, ss, v_, p, slope, u, seed=seed)
+        return pg.additive_attention_dropout(w.pattern, sd, ss, v_, p, SLOPE, u, seed=seed)
 
     def composed_dropout(sd, ss, v_, u=None):
         z = sd[row_d] + ss[col_d]
         if u is not None:
             z = z + u
-        alpha = pg.edge_softmax(pattern, torch.nn.functional.leaky_relu(z, slope))
-        return pg.spmm(pattern, alpha * pg.attention_dropout_mask(pattern, H, p, seed), v_)
+        alpha = pg.edge_softmax(w.pattern, torch.nn.functional.leaky_relu(z, SLOPE))
+        return pg.spmm(w.pattern, alpha * pg.attention_dropout_mask(w.pattern, H, p, seed), v_)
 
-    contenders = {"fused_dropout": fused_dropout, "composed_dropout": composed_dropout, "fused": fused}
-    out_f, out_c = forward_of(fused_dropout)(), forward_of(composed_dropout)()
-    mask = pg.attention_dropout_mask(pattern, H, p, seed)
-    ref64 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float64, *leaves[3:4], mask=mask)
-    ref32 = sampled_reference(rp_t, col_t, rows, *leaves[:3], slope, torch.float32, *leaves[3:4], mask=mask)
-    err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, dropout: out", ref32)
-    err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, dropout: out", ref32)
-    res = {"bench": "additive_attention --dropout" + (" --logit" if args.logit else ""), "device": torch.cuda.get_device_name(0), "p": p,
-           "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "negative_slope": slope,
-           "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-           "longest_checked_row": int(deg[rows].max()), "kept_fraction": float((mask != 0).float().mean()),
-           "out_err_fused_dropout": err_f, "out_err_composed_dropout": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
-           "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F, args.logit, perm),
-           "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F, args.logit, perm),
-           "fused_dropout_extra_forward_bytes": 0 if args.logit or not perm else 4 * E, "mask_tensor_bytes": E * H * 4}
+    out_f, out_c = pb.forward_of(fused_dropout, leaves)(), pb.forward_of(composed_dropout, leaves)()
+    mask = pg.attention_dropout_mask(w.pattern, H, p, seed)
+    err_of, ref_err = pb.pricer(w, entry_terms(*leaves), mask)
+    res = pb.base_record("additive_attention --dropout" + (" --logit" if args.logit else ""), args, w, H, F, p=p, negative_slope=SLOPE)
+    res.update({"kept_fraction": float((mask != 0).float().mean()), "out_err_fused_dropout": err_of(out_f, f"{shape} fused, dropout: out"),
+                "out_err_composed_dropout": err_of(out_c, f"{shape} composed, dropout: out"), "out_err_fp32_reference": ref_err,
+                **record_bytes("dropout", w.E, w.N, H, F, args.logit, w.perm)})
     del out_f, out_c, mask
-    legs = [("forward", alternate({k: forward_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup))]
-    if not args.forward_only:
-        legs.append(("forward_backward", alternate({k: both_of(fn) for k, fn in contenders.items()}, args.rounds, args.steps, args.warmup)))
-    for what, r in legs:
-        for name in contenders:
-            res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-        res[f"{what}_speedup"] = res[f"composed_dropout_{what}_ms"] / res[f"fused_dropout_{what}_ms"]
+
+    def increment(what):
         res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
-    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
-    with open(args.out, "a") as f:
-        f.write(json.dumps(res) + "\n")
-    print(json.dumps(res), flush=True)
+    legs = pb.run_legs(args, {"fused_dropout": (fused_dropout, leaves), "composed_dropout": (composed_dropout, leaves),
+                              "fused": (fused, leaves)}, G)
+    pb.add_legs(res, legs, speedup=("composed_dropout", "fused_dropout"), each=increment)
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(w.dev)
+    pb.write(res, args.out)
     print(f"{shape}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged bytes; "
           f"the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
 
 
-def main():
+def measure(args):
+    w = pb.Workload(args, "additive_attention_bench", row_d=True, col_d=True)
+    one_shape = measure_bf16 if args.tables_bf16 else measure_dropout if args.dropout else measure_plain
+    for shape, H, F in pb.shapes(args):
+        one_shape(args, w, shape, H, F)
+
+
+def parse(argv=None):
+    """-> (the parser, the arguments with --out and what else depends on the mode filled in)."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="8x16,8x64")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=10, help="timed calls per round and contender")
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--forward-only", action="store_true", help="skip the forward + backward leg")
+    pb.common_arguments(ap, 420, "profiles/additive_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout, "
+                        "..._bf16_bench.jsonl under --tables-bf16")
     ap.add_argument("--logit", action="store_true", help="both contenders with an [E, H] edge_logit that requires a gradient")
-    ap.add_argument("--scale", type=int, default=20)
-    ap.add_argument("--draws", type=int, default=5_000_000)
-    ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
     ap.add_argument("--dropout", action="store_true", help="additive_attention_dropout at p = 0.5 against the op without dropout and "
                     "the composition with the mask as a tensor")
     ap.add_argument("--tables-bf16", action="store_true", help="additive_attention_bf16: the fused forward on a float32 v table against "
                     "the fused forward on the bfloat16 table of the same values (forward only; goes with --logit)")
-    ap.add_argument("--out", default=None, help="profiles/additive_attention_bench.jsonl, or ..._dropout_bench.jsonl under --dropout, "
-                    "..._bf16_bench.jsonl under --tables-bf16")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.tables_bf16 and args.dropout:
         ap.error("--tables-bf16 and --dropout are two measurements: there is no op with both")
     if args.out is None:
         name = "additive_attention_bf16_bench.jsonl" if args.tables_bf16 else "additive_attention_dropout_bench.jsonl" if args.dropout else \
             "additive_attention_bench.jsonl"
-        args.out = os.path.join(ROOT, "profiles", name)
+        args.out = os.path.join(pb.ROOT, "profiles", name)
+    return ap, args
+
+
+def main():
+    args = parse()[1]
     if args.child:
         return measure(args)
-    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
-    sys.exit(subprocess.call(cmd))
+    pb.run_in_child(__file__, args.limit)
 
 
 if __name__ == "__main__":

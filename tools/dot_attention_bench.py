@@ -10,15 +10,10 @@ at H x F = 8x16 and 8x64, N(0, 1) tensors, scale 1 / sqrt(F), the forward alone 
     python tools/dot_attention_bench.py --dropout [...]    # seeded attention dropout: three contenders -> profiles/dot_attention_dropout_bench.jsonl
     python tools/dot_attention_bench.py --edge [...]       # per-entry key and value features: fused against the chain of parts -> profiles/dot_attention_edge_bench.jsonl
 
-The measuring step runs in a child process under `timeout -k 10 <--limit seconds>`; this process never opens the GPU.  Both contenders
-run in that one process, alternated round by round: a round times `steps` calls of one contender, each between two HIP events, then
-the same of the other.  Reported per contender: the median over all rounds x steps timed calls (at least 50) and the spread of the
-rounds' medians (largest minus smallest): a difference below that spread is not a difference.  The composition is given q already
-multiplied by the scale, so it runs the parent's kernels and nothing else.
-
-Before timing, both contenders' outputs are priced on the same seeded inputs by the rule of tests/parity.py against an fp64
-computation on the CPU, on a sample of rows (the row of most entries among them): the whole [E, H, F] product does not fit an fp64
-CPU run.  Algorithmic bytes are computed from the shapes (E entries, N rows, M columns, R = H F floats per row), `*_bytes` below.
+How it measures is tools/pattern_bench.py's and described there: the child process under `timeout -k 10 <--limit seconds>`, the
+contenders alternated round by round in that one process (at least 50 timed calls each), the median and the spread, the pricing of
+the outputs on a sample of rows.  The composition is given q already multiplied by the scale, so it runs the parent's kernels and
+nothing else.  Algorithmic bytes are computed from the shapes (E entries, N rows, M columns, R = H F floats per row), `*_bytes` below.
 Recorded, not gated.  One JSON object per shape, appended.
 
 --bias measures dot_attention's per-entry bias instead: in the one child process it alternates the fused op with an N(0, 1) [E, H] bias
@@ -47,17 +42,10 @@ with e on both sides.  e alone is E H F 4 bytes (5.5 GB at 8x16, 22 GB at 8x64) 
 tensors of that size at once.  Free device memory is asked for first: a contender that does not fit is left out and the record
 says so (`skipped`), a shape where not even the fused op fits is skipped whole; the tool does not fail over it."""
 import argparse
-import json
 import math
 import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-SAMPLE_ROWS = 1024
+import pattern_bench as pb
 
 
 def fused_forward_bytes(E, N, M, H, F):
@@ -145,432 +133,252 @@ def chain_edge_backward_bytes(E, N, H, F):
     return value + key
 
 
-def timed_round(fn, steps):
-    """-> the ms of `steps` calls, each between two events."""
-    import torch
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-    for a, b in ev:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    return [a.elapsed_time(b) for a, b in ev]
-
-
-def alternate(contenders, rounds, steps, warmup):
-    """{name: fn} -> {name: (median ms of all timed calls, spread of the rounds' medians)}."""
-    for fn in contenders.values():
-        for _ in range(warmup):
-            fn()
-    times = {name: [] for name in contenders}
-    for _ in range(rounds):
-        for name, fn in contenders.items():
-            times[name].append(timed_round(fn, steps))
-    out = {}
-    for name, per_round in times.items():
-        medians = [statistics.median(r) for r in per_round]
-        out[name] = (statistics.median([t for r in per_round for t in r]), max(medians) - min(medians))
-    return out
-
-
-def sampled_reference(rp, col, rows, q, k, v, scale, dtype, bias=None, mask=None, edge=None):
-    """out of `rows` by torch on the CPU in `dtype`: the softmax over each row's entries of scale q_i . k_j (+ bias [E, H], at the
-    CSR position), times mask [E, H] (pre-scaled, after the softmax) where given, times v_j.  edge [E, H, F], at the CSR position:
-    added to k_j and to v_j."""
-    import torch
-    deg = rp[rows + 1] - rp[rows]
-    idx = torch.cat([torch.arange(int(rp[r]), int(rp[r + 1])) for r in rows.tolist()])
-    sub = torch.repeat_interleave(torch.arange(rows.numel()), deg)
-    cols, inv = torch.unique(col[idx], return_inverse=True)
-    qs, ks, vs = q[rows].cpu().to(dtype), k[cols].cpu().to(dtype), v[cols].cpu().to(dtype)
-    kk, vv = ks[inv], vs[inv]
-    if edge is not None:
-        es = edge[idx.to(edge.device)].cpu().to(dtype)
-        kk, vv = kk + es, vv + es
-    s = (qs[sub] * kk).sum(-1) * scale
-    if bias is not None:
-        s = s + bias[idx.to(bias.device)].cpu().to(dtype)
-    m = torch.full(qs.shape[:2], -float("inf"), dtype=dtype).scatter_reduce(0, sub[:, None].expand(-1, s.shape[1]), s, "amax")
-    p = torch.exp(s - m[sub])
-    alpha = p / torch.zeros_like(m).index_add(0, sub, p)[sub]
-    if mask is not None:
-        alpha = alpha * mask[idx.to(mask.device)].cpu().to(dtype)
-    return torch.zeros_like(qs).index_add(0, sub, alpha[:, :, None] * vv)
-
-
-def measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
-    """--bias: fused with a bias, the composition with the same bias, fused without one; one JSON object per shape."""
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        scale = 1.0 / math.sqrt(F)
-        g = torch.Generator(device=dev).manual_seed(2)
-        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
-        bias = torch.randn(E, H, generator=g, device=dev)
-        qs = q * scale
-
-        def fused_bias(q_, k_, v_, b_):
-            return pg.dot_attention(pattern, q_, k_, v_, scale, b_)
-
-        def composed_bias(qs_, k_, v_, b_):
-            return pg.spmm(pattern, pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_) + b_), v_)
-
-        def fused(q_, k_, v_):
-            return pg.dot_attention(pattern, q_, k_, v_, scale)
-
-        def forward_of(fn, leaves):
-            def run():
-                with torch.no_grad():
-                    return fn(*leaves)
-            return run
-
-        def both_of(fn, leaves):
-            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
-
-            def run():
-                return torch.autograd.grad(fn(*leaves), leaves, G)
-            return run
-
-        out_f, out_c = forward_of(fused_bias, (q, k, v, bias))(), forward_of(composed_bias, (qs, k, v, bias))()
-        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, bias)
-        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, bias)
-        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, bias: out", ref32)
-        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, bias: out", ref32)
-        perm = pattern.perm is not None
-        res = {"bench": "dot_attention --bias", "device": torch.cuda.get_device_name(0),
-               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
-               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-               "longest_checked_row": int(deg[rows].max()), "out_err_fused_bias": err_f, "out_err_composed_bias": err_c,
-               "out_err_fp32_reference": parity.err(ref32, ref64), "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F),
-               "bias_forward_bytes": bias_forward_bytes(E, H, perm), "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F),
-               "bias_backward_bytes": bias_backward_bytes(E, H, perm)}
-        res["bias_forward_expected_increment"] = res["bias_forward_bytes"] / res["fused_forward_bytes"]
-        del out_f, out_c
-        legs = [("forward", alternate({"fused_bias": forward_of(fused_bias, (q, k, v, bias)),
-                                       "composed_bias": forward_of(composed_bias, (qs, k, v, bias)),
-                                       "fused": forward_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup))]
-        if not args.forward_only:
-            legs.append(("forward_backward", alternate({"fused_bias": both_of(fused_bias, (q, k, v, bias)),
-                                                        "composed_bias": both_of(composed_bias, (qs, k, v, bias)),
-                                                        "fused": both_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup)))
-        for what, r in legs:
-            for name in ("fused_bias", "composed_bias", "fused"):
-                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-            res[f"{what}_speedup"] = res[f"composed_bias_{what}_ms"] / res[f"fused_bias_{what}_ms"]
-            res[f"bias_{what}_measured_increment"] = res[f"fused_bias_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        print(f"{shape}: the byte model expects the bias to add {100 * res['bias_forward_expected_increment']:.1f} % to the fused "
-              f"forward; measured {100 * res['bias_forward_measured_increment']:.1f} %", flush=True)
-        del q, k, v, G, qs, bias
-        torch.cuda.empty_cache()
-
-
-def measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
-    """--kv-bf16: the fused forward on float32 tables against the fused forward on bfloat16 tables; one JSON object per shape."""
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        R = H * F
-        scale = 1.0 / math.sqrt(F)
-        g = torch.Generator(device=dev).manual_seed(2)
-        q = torch.randn(N, H, F, generator=g, device=dev)
-        k16, v16 = (torch.randn(N, H, F, generator=g, device=dev).bfloat16() for _ in range(2))
-        kw, vw = k16.float(), v16.float()                           # the same values, widened: what the float32 contender is fed
-
-        def run_fp32():
-            with torch.no_grad():
-                return pg.dot_attention(pattern, q, kw, vw, scale)
-
-        def run_bf16():
-            with torch.no_grad():
-                return pg.dot_attention(pattern, q, k16, v16, scale)
-
-        out_w, out_h = run_fp32(), run_bf16()
-        equal = bool(torch.equal(out_w, out_h))
-        ref64 = sampled_reference(rp_t, col_t, rows, q, kw, vw, scale, torch.float64)
-        ref32 = sampled_reference(rp_t, col_t, rows, q, kw, vw, scale, torch.float32)
-        err_h = parity.close_fwd(out_h[rows.to(dev)], ref64, f"{shape} fused, bf16 tables: out", ref32)
-        res = {"bench": "dot_attention --kv-bf16", "device": torch.cuda.get_device_name(0),
-               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
-               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-               "longest_checked_row": int(deg[rows].max()), "out_bf16_equals_out_fp32_on_widened_tables": equal,
-               "out_err_fused_bf16": err_h, "out_err_fp32_reference": parity.err(ref32, ref64),
-               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F),
-               "byte_model_ratio_per_entry": (4 * R + 4) / (8 * R + 4)}
-        res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
-        del out_w, out_h
-        r = alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup)
-        for name in ("fused_fp32", "fused_bf16"):
-            res[f"{name}_forward_ms"], res[f"{name}_forward_spread_ms"] = r[name]
-        res["measured_ratio"] = res["fused_bf16_forward_ms"] / res["fused_fp32_forward_ms"]
-        res["faster_by_more_than_the_spread"] = (res["fused_fp32_forward_ms"] - res["fused_bf16_forward_ms"]
-                                                 > max(res["fused_fp32_forward_spread_ms"], res["fused_bf16_forward_spread_ms"]))
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        print(f"{shape}: bf16 tables take {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
-              f"{res['byte_model_ratio']:.3f} ({res['byte_model_ratio_per_entry']:.3f} per entry); outputs "
-              f"{'bit-equal' if equal else 'DIFFER'}", flush=True)
-        del q, k16, v16, kw, vw
-        torch.cuda.empty_cache()
-
-
-def measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
-    """--dropout: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object per shape."""
-    p = 0.5
-    seed = torch.tensor([20240607], dtype=torch.int64, device=dev)
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        scale = 1.0 / math.sqrt(F)
-        g = torch.Generator(device=dev).manual_seed(2)
-        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
-        qs = q * scale
-
-        def fused_dropout(q_, k_, v_):
-            return pg.dot_attention_dropout(pattern, q_, k_, v_, p, scale, seed=seed)
-
-        def composed_dropout(qs_, k_, v_):
-            alpha = pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_))
-            return pg.spmm(pattern, alpha * pg.attention_dropout_mask(pattern, H, p, seed), v_)
-
-        def fused(q_, k_, v_):
-            return pg.dot_attention(pattern, q_, k_, v_, scale)
-
-        def forward_of(fn, leaves):
-            def run():
-                with torch.no_grad():
-                    return fn(*leaves)
-            return run
-
-        def both_of(fn, leaves):
-            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
-
-            def run():
-                return torch.autograd.grad(fn(*leaves), leaves, G)
-            return run
-
-        out_f, out_c = forward_of(fused_dropout, (q, k, v))(), forward_of(composed_dropout, (qs, k, v))()
-        mask = pg.attention_dropout_mask(pattern, H, p, seed)
-        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, mask=mask)
-        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, mask=mask)
-        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused, dropout: out", ref32)
-        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed, dropout: out", ref32)
-        res = {"bench": "dot_attention --dropout", "device": torch.cuda.get_device_name(0), "p": p,
-               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
-               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "checked_rows": int(rows.numel()),
-               "longest_checked_row": int(deg[rows].max()), "kept_fraction": float((mask != 0).float().mean()),
-               "out_err_fused_dropout": err_f, "out_err_composed_dropout": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
-               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F),
-               "mask_tensor_bytes": E * H * 4}
-        del out_f, out_c, mask
-        legs = [("forward", alternate({"fused_dropout": forward_of(fused_dropout, (q, k, v)),
-                                       "composed_dropout": forward_of(composed_dropout, (qs, k, v)),
-                                       "fused": forward_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup))]
-        if not args.forward_only:
-            legs.append(("forward_backward", alternate({"fused_dropout": both_of(fused_dropout, (q, k, v)),
-                                                        "composed_dropout": both_of(composed_dropout, (qs, k, v)),
-                                                        "fused": both_of(fused, (q, k, v))}, args.rounds, args.steps, args.warmup)))
-        for what, r in legs:
-            for name in ("fused_dropout", "composed_dropout", "fused"):
-                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-            res[f"{what}_speedup"] = res[f"composed_dropout_{what}_ms"] / res[f"fused_dropout_{what}_ms"]
-            res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        print(f"{shape}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged bytes; "
-              f"the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
-        del q, k, v, G, qs
-        torch.cuda.empty_cache()
-
-
-def measure_edge(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows):
-    """--edge: dot_attention_edge against the chain of parts; one JSON object per shape, a shape or a contender that does not fit the
-    free device memory left out and named in the record."""
-    row = pattern.edge_rc[:, 0].long()
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        scale = 1.0 / math.sqrt(F)
-        e_bytes = E * H * F * 4
-        torch.cuda.empty_cache()
-        free = torch.cuda.mem_get_info(dev)[0]
+def record_bytes(mode, E, N, H, F, perm=False):
+    """The byte-model fields of a record of `mode` (None, "bias", "kv_bf16", "dropout" or "edge"), in the record's order; the bench's
+    pattern is square, M = N."""
+    fused_f, fused_b = fused_forward_bytes(E, N, N, H, F), fused_backward_bytes(E, N, N, H, F)
+    if mode == "bias":
+        return {"fused_forward_bytes": fused_f, "bias_forward_bytes": bias_forward_bytes(E, H, perm), "fused_backward_bytes": fused_b,
+                "bias_backward_bytes": bias_backward_bytes(E, H, perm)}
+    if mode == "kv_bf16":
+        return {"fused_forward_bytes": fused_f, "fused_bf16_forward_bytes": bf16_forward_bytes(E, N, N, H, F)}
+    if mode == "dropout":
+        return {"fused_forward_bytes": fused_f, "fused_backward_bytes": fused_b, "mask_tensor_bytes": E * H * 4}
+    composed_f, composed_b = composed_forward_bytes(E, N, N, H, F), composed_backward_bytes(E, N, N, H, F)
+    if mode == "edge":
         # e, de and a margin for the fused op; the chain holds q[row], two products, their gradients and autograd's saved copies besides
-        need = {"fused_edge": 3 * e_bytes + (2 << 30), "composed_edge": 12 * e_bytes + (2 << 30)}
-        fits = [name for name in need if need[name] <= free]
-        res = {"bench": "dot_attention --edge", "device": torch.cuda.get_device_name(0),
-               "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E, "H": H, "F": F, "scale": scale,
-               "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup, "e_bytes": e_bytes,
-               "free_device_bytes": free, "needed_device_bytes": need,
-               "skipped": {name: f"needs {need[name]} bytes of device memory, {free} are free" for name in need if name not in fits}}
-        if "fused_edge" not in fits:
-            with open(args.out, "a") as f:
-                f.write(json.dumps(res) + "\n")
-            print(json.dumps(res), flush=True)
-            print(f"{shape}: skipped, e alone is {e_bytes / 1e9:.1f} GB and {free / 1e9:.1f} GB are free", flush=True)
-            continue
-        g = torch.Generator(device=dev).manual_seed(2)
-        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
-        e = torch.randn(E, H, F, generator=g, device=dev)
+        e_bytes = E * H * F * 4
+        return {"e_bytes": e_bytes, "needed_device_bytes": {"fused_edge": 3 * e_bytes + (2 << 30), "composed_edge": 12 * e_bytes + (2 << 30)},
+                "fused_forward_bytes": fused_f + edge_forward_bytes(E, H, F, perm),
+                "fused_backward_bytes": fused_b + edge_backward_bytes(E, H, F, perm),
+                "composed_forward_bytes": composed_f + chain_edge_forward_bytes(E, N, H, F),
+                "composed_backward_bytes": composed_b + chain_edge_backward_bytes(E, N, H, F)}
+    return {"fused_forward_bytes": fused_f, "composed_forward_bytes": composed_f, "fused_backward_bytes": fused_b,
+            "composed_backward_bytes": composed_b}
 
-        def fused_edge(q_, k_, v_, e_):
-            return pg.dot_attention_edge(pattern, q_, k_, v_, e_, scale)
 
-        def composed_edge(q_, k_, v_, e_):
-            s = pg.edge_dot(pattern, q_, k_, scale) + scale * (q_[row] * e_).sum(-1)
-            alpha = pg.edge_softmax(pattern, s)
-            return pg.spmm(pattern, alpha, v_) + torch.zeros_like(q_).index_add(0, row, alpha[..., None] * e_)
+def entry_terms(q, k, v, scale, bias=None, edge=None):
+    """The family's part of pattern_bench.sampled_reference: the score scale q_i . k_j (+ bias [E, H], at the CSR position) and the
+    values v_j; edge [E, H, F], at the CSR position: added to k_j and to v_j."""
+    def terms(dtype, part, idx, sub, cols, inv):
+        kk, vv = pb.taken(k, cols, dtype)[inv], pb.taken(v, cols, dtype)[inv]
+        if edge is not None:
+            es = pb.taken(edge, idx, dtype)
+            kk, vv = kk + es, vv + es
+        s = (pb.taken(q, part, dtype)[sub] * kk).sum(-1) * scale
+        if bias is not None:
+            s = s + pb.taken(bias, idx, dtype)
+        return s, vv
+    return terms
 
-        fns = {"fused_edge": fused_edge, "composed_edge": composed_edge}
 
-        def forward_of(fn):
-            def run():
-                with torch.no_grad():
-                    return fn(q, k, v, e)
-            return run
+def measure_plain(args, w, shape, H, F):
+    """No flag: the fused op against the composition; one JSON object."""
+    import torch
+    import pygat_amd as pg
+    scale = 1.0 / math.sqrt(F)
+    g = w.generator()
+    q, k, v, G = (torch.randn(w.N, H, F, generator=g, device=w.dev) for _ in range(4))
+    qs = q * scale
 
-        def both_of(fn):
-            leaves = [t.detach().requires_grad_(True) for t in (q, k, v, e)]      # (fresh leaves on the same memory: no second e)
+    def fused(*leaves):
+        return pg.dot_attention(w.pattern, *leaves, scale)
 
-            def run():
-                return torch.autograd.grad(fn(*leaves), leaves, G)
-            return run
+    def composed(qs_, k_, v_):
+        return pg.spmm(w.pattern, pg.edge_softmax(w.pattern, pg.edge_dot(w.pattern, qs_, k_)), v_)
 
-        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64, edge=e)
-        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32, edge=e)
-        res.update({"checked_rows": int(rows.numel()), "longest_checked_row": int(deg[rows].max()),
-                    "out_err_fp32_reference": parity.err(ref32, ref64)})
-        for name in list(fits):
-            try:                                                    # (the estimate above is one: what does not fit after all is left out too)
-                out = forward_of(fns[name])()
-                res[f"out_err_{name}"] = parity.close_fwd(out[rows.to(dev)], ref64, f"{shape} {name}: out", ref32)
-                del out
-                if not args.forward_only:
-                    both_of(fns[name])()
-            except torch.cuda.OutOfMemoryError as err:
-                fits.remove(name)
-                res["skipped"][name] = "out of device memory in a trial call: " + str(err).split("\n")[0]
-            torch.cuda.empty_cache()
-        if not fits:
-            with open(args.out, "a") as f:
-                f.write(json.dumps(res) + "\n")
-            print(json.dumps(res), flush=True)
-            continue
-        perm = pattern.perm is not None
-        res.update({"fused_forward_bytes": fused_forward_bytes(E, N, N, H, F) + edge_forward_bytes(E, H, F, perm),
-                    "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F) + edge_backward_bytes(E, H, F, perm),
-                    "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F) + chain_edge_forward_bytes(E, N, H, F),
-                    "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F) + chain_edge_backward_bytes(E, N, H, F)})
-        legs = [("forward", alternate({name: forward_of(fns[name]) for name in fits}, args.rounds, args.steps, args.warmup))]
-        if not args.forward_only:
-            legs.append(("forward_backward", alternate({name: both_of(fns[name]) for name in fits}, args.rounds, args.steps,
-                                                       args.warmup)))
-        for what, r in legs:
-            for name in fits:
-                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-            if "composed_edge" in fits:
-                res[f"{what}_speedup"] = res[f"composed_edge_{what}_ms"] / res[f"fused_edge_{what}_ms"]
-        res["peak_device_bytes"] = torch.cuda.max_memory_allocated(dev)
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        del q, k, v, G, e
+    contenders = {"fused": (fused, (q, k, v)), "composed": (composed, (qs, k, v))}
+    # the same seeded inputs, both contenders priced on the sampled rows
+    out_f, out_c = pb.forward_of(*contenders["fused"])(), pb.forward_of(*contenders["composed"])()
+    err_of, ref_err = pb.pricer(w, entry_terms(q, k, v, scale))
+    res = pb.base_record(None, args, w, H, F, scale=scale)
+    res.update({"out_err_fused": err_of(out_f, f"{shape} fused out"), "out_err_composed": err_of(out_c, f"{shape} composed out"),
+                "out_err_fp32_reference": ref_err, "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
+                **record_bytes(None, w.E, w.N, H, F, w.perm)})
+    del out_f, out_c
+    pb.add_legs(res, pb.run_legs(args, contenders, G), speedup=("composed", "fused"))
+    pb.write(res, args.out)
+
+
+def measure_bias(args, w, shape, H, F):
+    """--bias: fused with a bias, the composition with the same bias, fused without one; one JSON object."""
+    import torch
+    import pygat_amd as pg
+    scale = 1.0 / math.sqrt(F)
+    g = w.generator()
+    q, k, v, G = (torch.randn(w.N, H, F, generator=g, device=w.dev) for _ in range(4))
+    bias = torch.randn(w.E, H, generator=g, device=w.dev)
+    qs = q * scale
+
+    def fused_bias(q_, k_, v_, b_):
+        return pg.dot_attention(w.pattern, q_, k_, v_, scale, b_)
+
+    def composed_bias(qs_, k_, v_, b_):
+        return pg.spmm(w.pattern, pg.edge_softmax(w.pattern, pg.edge_dot(w.pattern, qs_, k_) + b_), v_)
+
+    def fused(q_, k_, v_):
+        return pg.dot_attention(w.pattern, q_, k_, v_, scale)
+
+    contenders = {"fused_bias": (fused_bias, (q, k, v, bias)), "composed_bias": (composed_bias, (qs, k, v, bias)), "fused": (fused, (q, k, v))}
+    out_f, out_c = pb.forward_of(*contenders["fused_bias"])(), pb.forward_of(*contenders["composed_bias"])()
+    err_of, ref_err = pb.pricer(w, entry_terms(q, k, v, scale, bias))
+    res = pb.base_record("dot_attention --bias", args, w, H, F, scale=scale)
+    res.update({"out_err_fused_bias": err_of(out_f, f"{shape} fused, bias: out"),
+                "out_err_composed_bias": err_of(out_c, f"{shape} composed, bias: out"), "out_err_fp32_reference": ref_err,
+                **record_bytes("bias", w.E, w.N, H, F, w.perm)})
+    res["bias_forward_expected_increment"] = res["bias_forward_bytes"] / res["fused_forward_bytes"]
+    del out_f, out_c
+
+    def increment(what):
+        res[f"bias_{what}_measured_increment"] = res[f"fused_bias_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+    pb.add_legs(res, pb.run_legs(args, contenders, G), speedup=("composed_bias", "fused_bias"), each=increment)
+    pb.write(res, args.out)
+    print(f"{shape}: the byte model expects the bias to add {100 * res['bias_forward_expected_increment']:.1f} % to the fused "
+          f"forward; measured {100 * res['bias_forward_measured_increment']:.1f} %", flush=True)
+
+
+def measure_kv_bf16(args, w, shape, H, F):
+    """--kv-bf16: the fused forward on float32 tables against the fused forward on bfloat16 tables; one JSON object."""
+    import torch
+    import pygat_amd as pg
+    R = H * F
+    scale = 1.0 / math.sqrt(F)
+    g = w.generator()
+    q = torch.randn(w.N, H, F, generator=g, device=w.dev)
+    k16, v16 = (torch.randn(w.N, H, F, generator=g, device=w.dev).bfloat16() for _ in range(2))
+    kw, vw = k16.float(), v16.float()                           # the same values, widened: what the float32 contender is fed
+
+    def fused(*leaves):
+        return pg.dot_attention(w.pattern, *leaves, scale)
+
+    run_fp32, run_bf16 = pb.forward_of(fused, (q, kw, vw)), pb.forward_of(fused, (q, k16, v16))
+    out_w, out_h = run_fp32(), run_bf16()
+    equal = bool(torch.equal(out_w, out_h))
+    err_of, ref_err = pb.pricer(w, entry_terms(q, kw, vw, scale))
+    res = pb.base_record("dot_attention --kv-bf16", args, w, H, F, scale=scale)
+    res.update({"out_bf16_equals_out_fp32_on_widened_tables": equal, "out_err_fused_bf16": err_of(out_h, f"{shape} fused, bf16 tables: out"),
+                "out_err_fp32_reference": ref_err, **record_bytes("kv_bf16", w.E, w.N, H, F),
+                "byte_model_ratio_per_entry": (4 * R + 4) / (8 * R + 4)})
+    res["byte_model_ratio"] = res["fused_bf16_forward_bytes"] / res["fused_forward_bytes"]
+    del out_w, out_h
+    pb.add_legs(res, [("forward", pb.alternate({"fused_fp32": run_fp32, "fused_bf16": run_bf16}, args.rounds, args.steps, args.warmup))])
+    pb.add_bf16_ratio(res)
+    pb.write(res, args.out)
+    print(f"{shape}: bf16 tables take {res['measured_ratio']:.3f} of the float32 forward's time; the byte model says "
+          f"{res['byte_model_ratio']:.3f} ({res['byte_model_ratio_per_entry']:.3f} per entry); outputs "
+          f"{'bit-equal' if equal else 'DIFFER'}", flush=True)
+
+
+def measure_dropout(args, w, shape, H, F):
+    """--dropout: fused with dropout, fused without, the composition with the mask as a tensor; one JSON object."""
+    import torch
+    import pygat_amd as pg
+    p = 0.5
+    seed = torch.tensor([20240607], dtype=torch.int64, device=w.dev)
+    scale = 1.0 / math.sqrt(F)
+    g = w.generator()
+    q, k, v, G = (torch.randn(w.N, H, F, generator=g, device=w.dev) for _ in range(4))
+    qs = q * scale
+
+    def fused_dropout(q_, k_, v_):
+        return pg.dot_attention_dropout(w.pattern, q_, k_, v_, p, scale, seed=seed)
+
+    def composed_dropout(qs_, k_, v_):
+        alpha = pg.edge_softmax(w.pattern, pg.edge_dot(w.pattern, qs_, k_))
+        return pg.spmm(w.pattern, alpha * pg.attention_dropout_mask(w.pattern, H, p, seed), v_)
+
+    def fused(q_, k_, v_):
+        return pg.dot_attention(w.pattern, q_, k_, v_, scale)
+
+    contenders = {"fused_dropout": (fused_dropout, (q, k, v)), "composed_dropout": (composed_dropout, (qs, k, v)), "fused": (fused, (q, k, v))}
+    out_f, out_c = pb.forward_of(*contenders["fused_dropout"])(), pb.forward_of(*contenders["composed_dropout"])()
+    mask = pg.attention_dropout_mask(w.pattern, H, p, seed)
+    err_of, ref_err = pb.pricer(w, entry_terms(q, k, v, scale), mask)
+    res = pb.base_record("dot_attention --dropout", args, w, H, F, p=p, scale=scale)
+    res.update({"kept_fraction": float((mask != 0).float().mean()), "out_err_fused_dropout": err_of(out_f, f"{shape} fused, dropout: out"),
+                "out_err_composed_dropout": err_of(out_c, f"{shape} composed, dropout: out"), "out_err_fp32_reference": ref_err,
+                **record_bytes("dropout", w.E, w.N, H, F)})
+    del out_f, out_c, mask
+
+    def increment(what):
+        res[f"dropout_{what}_measured_increment"] = res[f"fused_dropout_{what}_ms"] / res[f"fused_{what}_ms"] - 1.0
+    pb.add_legs(res, pb.run_legs(args, contenders, G), speedup=("composed_dropout", "fused_dropout"), each=increment)
+    pb.write(res, args.out)
+    print(f"{shape}: dropout adds {100 * res['dropout_forward_measured_increment']:.1f} % to the fused forward at unchanged bytes; "
+          f"the fused op with dropout takes 1 / {res['forward_speedup']:.2f} of the composition's forward", flush=True)
+
+
+def measure_edge(args, w, shape, H, F):
+    """--edge: dot_attention_edge against the chain of parts; one JSON object, a shape or a contender that does not fit the free
+    device memory left out and named in the record."""
+    import torch
+    import pygat_amd as pg
+    row = w.row_d
+    scale = 1.0 / math.sqrt(F)
+    model = record_bytes("edge", w.E, w.N, H, F, w.perm)
+    e_bytes, need = model.pop("e_bytes"), model.pop("needed_device_bytes")
+    torch.cuda.empty_cache()
+    free = torch.cuda.mem_get_info(w.dev)[0]
+    fits = [name for name in need if need[name] <= free]
+    res = pb.base_record("dot_attention --edge", args, w, H, F, scale=scale)
+    checked = {key: res.pop(key) for key in ("checked_rows", "longest_checked_row")}      # (behind the memory fields in this record)
+    res.update({"e_bytes": e_bytes, "free_device_bytes": free, "needed_device_bytes": need,
+                "skipped": {name: f"needs {need[name]} bytes of device memory, {free} are free" for name in need if name not in fits}})
+    if "fused_edge" not in fits:
+        pb.write(res, args.out)
+        print(f"{shape}: skipped, e alone is {e_bytes / 1e9:.1f} GB and {free / 1e9:.1f} GB are free", flush=True)
+        return
+    g = w.generator()
+    q, k, v, G = (torch.randn(w.N, H, F, generator=g, device=w.dev) for _ in range(4))
+    e = torch.randn(w.E, H, F, generator=g, device=w.dev)
+
+    def fused_edge(q_, k_, v_, e_):
+        return pg.dot_attention_edge(w.pattern, q_, k_, v_, e_, scale)
+
+    def composed_edge(q_, k_, v_, e_):
+        s = pg.edge_dot(w.pattern, q_, k_, scale) + scale * (q_[row] * e_).sum(-1)
+        alpha = pg.edge_softmax(w.pattern, s)
+        return pg.spmm(w.pattern, alpha, v_) + torch.zeros_like(q_).index_add(0, row, alpha[..., None] * e_)
+
+    fns, leaves = {"fused_edge": fused_edge, "composed_edge": composed_edge}, (q, k, v, e)
+    err_of, ref_err = pb.pricer(w, entry_terms(q, k, v, scale, edge=e))
+    res.update({**checked, "out_err_fp32_reference": ref_err})
+    for name in list(fits):
+        try:                                                    # (the estimate above is one: what does not fit after all is left out too)
+            out = pb.forward_of(fns[name], leaves)()
+            res[f"out_err_{name}"] = err_of(out, f"{shape} {name}: out")
+            del out
+            if not args.forward_only:
+                pb.both_of(fns[name], leaves, G, clone=False)()      # (fresh leaves on the same memory: no second e)
+        except torch.cuda.OutOfMemoryError as err:
+            fits.remove(name)
+            res["skipped"][name] = "out of device memory in a trial call: " + str(err).split("\n")[0]
         torch.cuda.empty_cache()
+    if not fits:
+        pb.write(res, args.out)
+        return
+    res.update(model)
+    legs = pb.run_legs(args, {name: (fns[name], leaves) for name in fits}, G, clone=False)
+    pb.add_legs(res, legs, speedup=("composed_edge", "fused_edge") if "composed_edge" in fits else None)
+    res["peak_device_bytes"] = torch.cuda.max_memory_allocated(w.dev)
+    pb.write(res, args.out)
 
 
 def measure(args):
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("dot_attention_bench: needs a GPU (a time taken anywhere else says nothing)")
-    import pygat_amd as pg
-    from pygat_amd.rmat import rmat_csr_numpy
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity                                                     # the one tolerance rule (tests/parity.py)
-    dev = torch.device("cuda", 0)
-    rp, col = rmat_csr_numpy(args.scale, args.draws, seed=1)
-    graph = pg.CSRGraph(torch.from_numpy(rp).to(dev), torch.from_numpy(col).to(dev))
-    pattern = graph.edge_pattern()
-    pattern.transposed()
-    N, E = graph.n, graph.nnz
-    rp_t, col_t = torch.from_numpy(rp).long(), torch.from_numpy(col).long()
-    deg = rp_t[1:] - rp_t[:-1]
-    picked = torch.randperm(N, generator=torch.Generator().manual_seed(3))[:SAMPLE_ROWS]
-    rows = torch.unique(torch.cat([picked, torch.argmax(deg)[None]]))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.bias:
-        return measure_bias(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
-    if args.kv_bf16:
-        return measure_kv_bf16(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
-    if args.dropout:
-        return measure_dropout(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
-    if args.edge:
-        return measure_edge(args, torch, pg, parity, dev, pattern, N, E, rp_t, col_t, deg, rows)
-    for shape in args.shapes.split(","):
-        H, F = (int(x) for x in shape.split("x"))
-        scale = 1.0 / math.sqrt(F)
-        g = torch.Generator(device=dev).manual_seed(2)
-        q, k, v, G = (torch.randn(N, H, F, generator=g, device=dev) for _ in range(4))
-        qs = q * scale
-
-        def fused(*leaves):
-            return pg.dot_attention(pattern, *leaves, scale)
-
-        def composed(qs_, k_, v_):
-            return pg.spmm(pattern, pg.edge_softmax(pattern, pg.edge_dot(pattern, qs_, k_)), v_)
-
-        def forward_of(fn, leaves):
-            def run():
-                with torch.no_grad():
-                    return fn(*leaves)
-            return run
-
-        def both_of(fn, leaves):
-            leaves = [t.detach().clone().requires_grad_(True) for t in leaves]
-
-            def run():
-                return torch.autograd.grad(fn(*leaves), leaves, G)
-            return run
-
-        # the same seeded inputs, both contenders priced on the sampled rows
-        out_f, out_c = forward_of(fused, (q, k, v))(), forward_of(composed, (qs, k, v))()
-        ref64 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float64)
-        ref32 = sampled_reference(rp_t, col_t, rows, q, k, v, scale, torch.float32)
-        err_f = parity.close_fwd(out_f[rows.to(dev)], ref64, f"{shape} fused out", ref32)
-        err_c = parity.close_fwd(out_c[rows.to(dev)], ref64, f"{shape} composed out", ref32)
-        res = {"device": torch.cuda.get_device_name(0), "graph": f"rmat scale {args.scale}, {args.draws} draws, seed 1", "N": N, "E": E,
-               "H": H, "F": F, "scale": scale, "rounds": args.rounds, "steps_per_round": args.steps, "warmup": args.warmup,
-               "checked_rows": int(rows.numel()), "longest_checked_row": int(deg[rows].max()),
-               "out_err_fused": err_f, "out_err_composed": err_c, "out_err_fp32_reference": parity.err(ref32, ref64),
-               "out_max_abs_fused_minus_composed": float((out_f - out_c).abs().max()),
-               "fused_forward_bytes": fused_forward_bytes(E, N, N, H, F), "composed_forward_bytes": composed_forward_bytes(E, N, N, H, F),
-               "fused_backward_bytes": fused_backward_bytes(E, N, N, H, F), "composed_backward_bytes": composed_backward_bytes(E, N, N, H, F)}
-        del out_f, out_c
-        fwd = alternate({"fused": forward_of(fused, (q, k, v)), "composed": forward_of(composed, (qs, k, v))}, args.rounds, args.steps,
-                        args.warmup)
-        legs = [("forward", fwd)]
-        if not args.forward_only:
-            legs.append(("forward_backward", alternate({"fused": both_of(fused, (q, k, v)), "composed": both_of(composed, (qs, k, v))},
-                                                       args.rounds, args.steps, args.warmup)))
-        for what, r in legs:
-            for name in ("fused", "composed"):
-                res[f"{name}_{what}_ms"], res[f"{name}_{what}_spread_ms"] = r[name]
-            res[f"{what}_speedup"] = res[f"composed_{what}_ms"] / res[f"fused_{what}_ms"]
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-        print(json.dumps(res), flush=True)
-        del q, k, v, G, qs
-        torch.cuda.empty_cache()
+    w = pb.Workload(args, "dot_attention_bench", row_d=args.edge)
+    one_shape = (measure_bias if args.bias else measure_kv_bf16 if args.kv_bf16 else measure_dropout if args.dropout else
+                 measure_edge if args.edge else measure_plain)
+    for shape, H, F in pb.shapes(args):
+        one_shape(args, w, shape, H, F)
 
 
-def main():
+def parse(argv=None):
+    """-> (the parser, the arguments with --out and what else depends on the mode filled in)."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="8x16,8x64")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=10, help="timed calls per round and contender")
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--forward-only", action="store_true", help="skip the forward + backward leg (a kernel trace of the forward alone)")
-    ap.add_argument("--scale", type=int, default=20)
-    ap.add_argument("--draws", type=int, default=5_000_000)
-    ap.add_argument("--limit", type=int, default=420, help="seconds the measuring child may take")
+    pb.common_arguments(ap, 420, "profiles/dot_attention_bench.jsonl; profiles/dot_attention_bias_bench.jsonl with --bias, "
+                        "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16, profiles/dot_attention_dropout_bench.jsonl with --dropout, "
+                        "profiles/dot_attention_edge_bench.jsonl with --edge",
+                        forward_only_help="skip the forward + backward leg (a kernel trace of the forward alone)")
     ap.add_argument("--bias", action="store_true", help="measure the per-entry bias: fused with a bias, the composition with it, fused without")
     ap.add_argument("--kv-bf16", action="store_true", help="measure bfloat16 k and v tables: the fused forward on float32 tables "
                     "against the fused forward on bfloat16 tables (forward only)")
@@ -578,22 +386,22 @@ def main():
                     "without, the composition with the mask as a tensor")
     ap.add_argument("--edge", action="store_true", help="measure dot_attention_edge, per-entry key and value features: the fused op "
                     "against the chain of parts; a shape or contender that does not fit the free device memory is skipped")
-    ap.add_argument("--out", default=None, help="profiles/dot_attention_bench.jsonl; profiles/dot_attention_bias_bench.jsonl with --bias, "
-                    "profiles/dot_attention_bf16_bench.jsonl with --kv-bf16, profiles/dot_attention_dropout_bench.jsonl with --dropout, "
-                    "profiles/dot_attention_edge_bench.jsonl with --edge")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.bias + args.kv_bf16 + args.dropout + args.edge > 1:
         ap.error("--bias, --kv-bf16, --dropout and --edge are separate measurements")
     if args.out is None:
         name = ("dot_attention_bias_bench.jsonl" if args.bias else "dot_attention_bf16_bench.jsonl" if args.kv_bf16 else
                 "dot_attention_dropout_bench.jsonl" if args.dropout else "dot_attention_edge_bench.jsonl" if args.edge else
                 "dot_attention_bench.jsonl")
-        args.out = os.path.join(ROOT, "profiles", name)
+        args.out = os.path.join(pb.ROOT, "profiles", name)
+    return ap, args
+
+
+def main():
+    args = parse()[1]
     if args.child:
         return measure(args)
-    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
-    sys.exit(subprocess.call(cmd))
+    pb.run_in_child(__file__, args.limit)
 
 
 if __name__ == "__main__":

@@ -14,8 +14,9 @@ The fraction of the 8 TB/s HBM roof is those bytes over the measured time.  Reco
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from pattern_bench import run_in_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -82,7 +83,8 @@ def measure(args):
     print(json.dumps(res))
 
 
-def main():
+def parse(argv=None):
+    """-> (the parser, the arguments with --out and what else depends on the mode filled in)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--by", choices=("row", "col"), default="row")
@@ -94,11 +96,15 @@ def main():
     ap.add_argument("--limit", type=int, default=240, help="seconds the measuring child may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "edge_softmax_bench.jsonl"))
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    return ap, args
+
+
+def main():
+    args = parse()[1]
     if args.child:
         return measure(args)
-    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
-    sys.exit(subprocess.call(cmd))
+    run_in_child(__file__, args.limit)
 
 
 if __name__ == "__main__":
