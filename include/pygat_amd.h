@@ -977,6 +977,42 @@ int pygat_weighted_block(int n, int64_t nnz, const int32_t* rowptr, const int32_
                          int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids, int64_t* src_nodes, int32_t* info, void* ws,
                          void* stream);
 
+/* ------------------------------------------------ K23: the induced subgraph of a node set and seeded random walks
+ * (csrc/k23_subgraph.hip), additive under ABI 16.  The square sub-pattern of the graph (n, nnz, rowptr, col: columns strictly
+ * increasing inside a row) on the SET of the n_in ids in `nodes` (int64, any order, repeats allowed; 1 <= n_in < 2^31), written as a
+ * CSR directly -- no sort, all arithmetic integer, no atomics, two runs give the same bits:
+ *   local ids are ranks in ascending global id: sub_nodes [n_sub] = the distinct ids ascending, index[i] = the local id of nodes[i]
+ *     (sub_nodes[index[i]] == nodes[i]; -1 for an id outside [0, n)).  The relabelling is monotone, so
+ *   row r holds, in ascending position, the positions p of graph row sub_nodes[r] whose col[p] is in the set, with local column
+ *     rank(col[p]): strictly ascending.  edge_ids = those positions, strictly increasing over the whole sub-pattern.
+ * Two calls with ONE host read between them, so that the entry tables are allocated at their exact size:
+ *   pygat_subgraph_count writes sub_nodes and sub_rowptr (room for m and m + 1 words, m = min(n_in, n): valid up to n_sub and n_sub + 1),
+ *     index [n_in] and info [4] = (rows n_sub, entries, 1 if some id lies outside [0, n), rows without an entry); nothing is read
+ *     back inside it.  An id outside [0, n) is never used as an index: it is not part of the set.
+ *   pygat_subgraph_fill takes n_sub = info[0] and sub_nnz = info[1] as read by the caller (both >= 1), the SAME n_in, sub_nodes,
+ *     sub_rowptr and workspace with its contents intact (the marks, their ranks and the list of long rows), and writes sub_col
+ *     [sub_nnz], edge_rc [sub_nnz x 2] (row, local column) and edge_ids [sub_nnz].  Every store is bounded by the row's range in
+ *     sub_rowptr and by sub_nnz, whatever the workspace holds.
+ * ws >= pygat_subgraph_workspace_bytes(n, n_in) bytes, 16-byte aligned: an n-sized int32 mark table, its scan, the per-row counts
+ * and the list of the long rows.  Rows of at most 64 entries are counted and filled by one thread, rows of at most 256 by one wave
+ * (64 positions per round), longer ones by a work-group each (1024 positions per round).  Each refusal names its entry point:
+ * `subgraph_workspace_bytes: `, `subgraph_count: `, `subgraph_fill: `. */
+int pygat_subgraph_workspace_bytes(int n, int64_t n_in, size_t* bytes);
+int pygat_subgraph_count(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_in, const int64_t* nodes,
+                         int64_t* sub_nodes, int64_t* index, int32_t* sub_rowptr, int32_t* info, void* ws, void* stream);
+int pygat_subgraph_fill(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_in, int n_sub, int64_t sub_nnz,
+                        const int64_t* sub_nodes, const int32_t* sub_rowptr, int32_t* sub_col, int32_t* edge_rc, int64_t* edge_ids,
+                        void* ws, void* stream);
+/* Seeded uniform random walks: walks [n_walk x (length + 1)] int64, walks[w, 0] = start[w] (int64, repeats allowed), and for t = 1 ..
+ * length, with cur = walks[w, t - 1], [b, e) its row and d = e - b:
+ *   k = word (t & 3) of Philox-4x32-10(counter (w, hop, 5, t >> 2), key (seed lo, seed hi)); *seed is a uint64 in DEVICE memory;
+ *   walks[w, t] = col[b + ((k * d) >> 32)] (the high word of the 64-bit product); a walker on a row without entries stays.
+ * The pick is uniform up to d / 2^32; the same (seed, hop) gives the same walks bit for bit.  info [1] = 1 if some start[w] lies
+ * outside [0, n): it is never used as an index (that walker stays where it is).  One thread per walker, one Philox call per four
+ * steps; refusals after `random_walk: `. */
+int pygat_random_walk(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_walk, const int64_t* start, int length,
+                      const void* seed, uint32_t hop, int64_t* walks, int32_t* info, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

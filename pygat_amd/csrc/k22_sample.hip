@@ -26,6 +26,7 @@
 // below the fanout; at exactly the fanout the select runs and ends at the row's largest key, which keeps the same entries.  No float
 // is summed across lanes and no result depends on an order of atomics: two runs give the same bits.
 #include "common.h"
+#include "prefix_scan.h"
 #include "rng.h"
 #include <string.h>
 
@@ -102,34 +103,7 @@ __global__ void sample_entries_kernel(int n_dst, const int32_t* __restrict__ blk
   if (blockIdx.x == 0 && threadIdx.x == 0) info[0] = blk_rowptr[n_dst];
 }
 
-// exclusive prefix of v over the THREADS (64: the wave; 256: the work-group, wsum = 4 ints of LDS) threads, and the total
-template <int THREADS>
-__device__ __forceinline__ int sample_scan(int v, int* total, int* wsum) {
-  const int lane = threadIdx.x & 63;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  if constexpr (THREADS == 64) {
-    *total = __shfl(x, 63);
-    return x - v;
-  } else {
-    const int w = threadIdx.x >> 6;
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < THREADS / 64; ++k) {
-      if (k < w) pre += wsum[k];
-      tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + x - v;
-  }
-}
+// (sample_scan, the wave and work-group prefix count used below, lives in prefix_scan.h: k23_subgraph.hip shares it)
 
 // Writes the kept positions of the row [b, e) in ascending order at edge_ids[base ...] (at most `room` of them) and marks their
 // columns: all of them (`all`), or those with key < T and the first `ties` of those with key == T.  The index of an entry is the

@@ -14,6 +14,9 @@
 //               key depends on the position alone.  No other layout uses stream 4.  tests/sampler_ref.py restates it and
 //               tests/test_gpu_sample.py compares the sampled blocks with it entry for entry.  The weighted sampler orders a row
 //               by sample_weighted_key(that word, weight[p]) instead.
+//   walk_keys4  the step keys of the random walk (k23_subgraph.hip): key of step t of walker w = word (t & 3) of Philox(counter =
+//               (w, hop, STREAM_WALK = 5, t >> 2), key = seed) -- four STEPS of one walker per call.  No other layout uses stream 5.
+//               tests/subgraph_ref.py restates it and tests/test_gpu_subgraph.py compares the walks with it entry for entry.
 #pragma once
 #include "common.h"
 
@@ -58,6 +61,12 @@ __device__ __forceinline__ uint32_t keep_nibble(const DropRng& g, const uint4& w
 constexpr uint32_t STREAM_SAMPLE = 4;
 __device__ __forceinline__ uint4 sample_keys4(uint64_t seed, uint32_t q, uint32_t hop) {
   return philox4x32_10(make_uint4(q, hop, STREAM_SAMPLE, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+
+// 4 step keys of the random walk (k23_subgraph.hip) for steps 4*tq .. 4*tq+3 of walker w at hop `hop`
+constexpr uint32_t STREAM_WALK = 5;
+__device__ __forceinline__ uint4 walk_keys4(uint64_t seed, uint32_t w, uint32_t hop, uint32_t tq) {
+  return philox4x32_10(make_uint4(w, hop, STREAM_WALK, tq), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
 // The weighted sampler's key of an entry with Philox word k and weight w > 0 (finite or +inf): the bits of the exponential clock

@@ -382,6 +382,11 @@ class CSRGraph:
                                              (self.bwd.rowptr, self.bwd.col, self.perm_t))
         return self._edge_pattern
 
+    def subgraph(self, nodes: torch.Tensor):
+        """pygat_amd.induced_subgraph(self, nodes): the sub-pattern on the set of `nodes`, written by the K23 kernels."""
+        from .subgraph import induced_subgraph
+        return induced_subgraph(self, nodes)
+
     def internal_view(self) -> InternalOrderView:
         """The degree-ordered pattern for node arrays that are themselves in internal order (see InternalOrderView)."""
         g, to_user, to_int = self.degree_ordered()
