@@ -1013,6 +1013,30 @@ int pygat_subgraph_fill(int n, int64_t nnz, const int32_t* rowptr, const int32_t
 int pygat_random_walk(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_walk, const int64_t* start, int length,
                       const void* seed, uint32_t hop, int64_t* walks, int32_t* info, void* stream);
 
+/* ------------------------------------------------ K24: link-prediction mini-batches -- the CSR position of (row, col) pairs and seeded
+ * negative destinations per source node (csrc/k24_linkpred.hip), additive under ABI 16.  The graph is (n, nnz, rowptr, col) with the
+ * columns strictly increasing inside a row; all arithmetic is integer, there are no atomics and no workspace, and two runs give the
+ * same bits.
+ * pygat_find_edges: for each of the n_pairs pairs (row[i], colq[i]) (int64; 1 <= n_pairs < 2^31), pos[i] (int64) = the position p
+ *   with rowptr[row[i]] <= p < rowptr[row[i] + 1] and col[p] == colq[i], or -1 if the pair is no entry: the positions that
+ *   pygat_sample_block and pygat_subgraph_fill write as edge_ids.  One thread per pair, one binary search over the row.  info [1] = 1
+ *   if an id of some pair lies outside [0, n) on either side: it is never used as an index, and that pair gets -1.
+ * pygat_draw_negatives: neg [n_src x num_neg] int64 -- for every source node src[w] (int64, repeats allowed; 1 <= n_src, num_neg >= 1,
+ *   n_src * num_neg < 2^31) num_neg ids that are NOT its neighbours.  For the flat draw i = w * num_neg + s, with u = src[w]:
+ *     the forbidden list c_0 < ... < c_{f-1} is the columns of row u, with u merged in at its sorted place if exclude_self == 1 and u is
+ *       not already a column; m = n - f ids are left;
+ *     k = word (i & 3) of Philox-4x32-10(counter (i >> 2, hop, 6, 0), key (seed lo, seed hi)); *seed is a uint64 in DEVICE memory;
+ *     r = (k * m) >> 32 (the high word of the 64-bit product); t* = #{t : c_t - t <= r}; neg[i] = r + t*, the r-th smallest id outside
+ *       the list.  c_t - t does not decrease with t, so t* is one upper-bound binary search over the row: there is no rejection loop.
+ *   Each draw is uniform over the m candidates up to m / 2^32; the draws of a row are independent, so ids may repeat; the same (seed,
+ *   hop) gives the same draws bit for bit.  info [2]: info[0] = 1 if some src[w] lies outside [0, n) -- it is never used as an index,
+ *   and its draws are -1; info[1] = 1 if some row has no candidate (m == 0) -- its draws are -1.  One thread per draw.
+ * Each refusal names its entry point: `find_edges: `, `draw_negatives: `. */
+int pygat_find_edges(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_pairs, const int64_t* row,
+                     const int64_t* colq, int64_t* pos, int32_t* info, void* stream);
+int pygat_draw_negatives(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_src, const int64_t* src, int num_neg,
+                         int exclude_self, const void* seed, uint32_t hop, int64_t* neg, int32_t* info, void* stream);
+
 /* ------------------------------------------------ K7: train-mode dropout around the projection
  * The reference drops out inside every head, each head with its own masks (models.py:32,34 call the heads
  * one after another): the input (layers.py:34,132), Wh (layers.py:37,136), the attention (layers.py:43,153).

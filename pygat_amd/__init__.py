@@ -23,6 +23,7 @@ from .gatv2_attention import (gatv2_attention, gatv2_attention_bf16, gatv2_atten
 from .sampling import sample_neighbors, sample_blocks, SampledBlock    # noqa: F401
 from .sampling import sample_neighbors_weighted, sample_blocks_weighted    # noqa: F401
 from .subgraph import induced_subgraph, random_walk, InducedSubgraph       # noqa: F401
+from .linkpred import find_edges, negative_edges, link_batch, LinkBatch    # noqa: F401
 
 __all__ = ["Adam", "BCEWithLogits", "CSRGraph", "as_graph", "gat_level", "GATLevelFn", "gemm", "set_gemm_mode", "get_gemm_mode", "gemm_mode", "GraphAttentionLayer",
            "SpGraphAttentionLayer", "GAT", "padded_width", "LIB_PATH", "GraphAttentionLayerV2",
@@ -33,3 +34,4 @@ __all__ += ["gatv2_attention", "additive_attention_dropout", "gatv2_attention_dr
 __all__ += ["additive_attention_bf16", "gatv2_attention_bf16", "gatv2_attention_edge_bf16"]
 __all__ += ["sample_neighbors", "sample_blocks", "SampledBlock", "sample_neighbors_weighted", "sample_blocks_weighted"]
 __all__ += ["induced_subgraph", "random_walk", "InducedSubgraph"]
+__all__ += ["find_edges", "negative_edges", "link_batch", "LinkBatch"]

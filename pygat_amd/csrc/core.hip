@@ -38,6 +38,7 @@ int footprint_k20(const char* name, int* regs, int* scratch);
 int footprint_k21(const char* name, int* regs, int* scratch);
 int footprint_k22(const char* name, int* regs, int* scratch);
 int footprint_k23(const char* name, int* regs, int* scratch);
+int footprint_k24(const char* name, int* regs, int* scratch);
 }  // namespace pygat
 
 extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* scratch_bytes) {
@@ -60,6 +61,7 @@ extern "C" int pygat_kernel_footprint(const char* kernel, int* num_regs, int* sc
   if (!strncmp(kernel, "k21", 3)) return pygat::footprint_k21(kernel, num_regs, scratch_bytes);      // (k21_, k21s_)
   if (!strncmp(kernel, "k22_", 4)) return pygat::footprint_k22(kernel, num_regs, scratch_bytes);
   if (!strncmp(kernel, "k23_", 4)) return pygat::footprint_k23(kernel, num_regs, scratch_bytes);
+  if (!strncmp(kernel, "k24_", 4)) return pygat::footprint_k24(kernel, num_regs, scratch_bytes);
   pygat::set_error("kernel_footprint: unknown kernel '%s' (k2_headline, k4_headline_da, tn_x3w, x3gw, k1_x3_tail, k14_rows_long, "
                    "k14_cols_long, k14_rows_wave, k14_cols_wave, k14_apply)", kernel);
   return PYGAT_EINVAL;

@@ -17,6 +17,10 @@
 //   walk_keys4  the step keys of the random walk (k23_subgraph.hip): key of step t of walker w = word (t & 3) of Philox(counter =
 //               (w, hop, STREAM_WALK = 5, t >> 2), key = seed) -- four STEPS of one walker per call.  No other layout uses stream 5.
 //               tests/subgraph_ref.py restates it and tests/test_gpu_subgraph.py compares the walks with it entry for entry.
+//   neg_keys4   the draw keys of the negative sampler (k24_linkpred.hip): key of the flat draw i = w * num_neg + s (draw s of source
+//               w) = word (i & 3) of Philox(counter = (i >> 2, hop, STREAM_NEG = 6, 0), key = seed) -- four consecutive flat DRAWS
+//               per call.  No other layout uses stream 6.  tests/linkpred_ref.py restates it and tests/test_gpu_linkpred.py compares
+//               the draws with it integer for integer.
 #pragma once
 #include "common.h"
 
@@ -67,6 +71,12 @@ __device__ __forceinline__ uint4 sample_keys4(uint64_t seed, uint32_t q, uint32_
 constexpr uint32_t STREAM_WALK = 5;
 __device__ __forceinline__ uint4 walk_keys4(uint64_t seed, uint32_t w, uint32_t hop, uint32_t tq) {
   return philox4x32_10(make_uint4(w, hop, STREAM_WALK, tq), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+
+// 4 draw keys of the negative sampler (k24_linkpred.hip) for the flat draws 4*q .. 4*q+3 at hop `hop`
+constexpr uint32_t STREAM_NEG = 6;
+__device__ __forceinline__ uint4 neg_keys4(uint64_t seed, uint32_t q, uint32_t hop) {
+  return philox4x32_10(make_uint4(q, hop, STREAM_NEG, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
 // The weighted sampler's key of an entry with Philox word k and weight w > 0 (finite or +inf): the bits of the exponential clock

@@ -43,6 +43,7 @@ from .ops import _Level, _ptr, _span, _stream, gemm, gemm_mode, get_gemm_mode, s
 STREAM_X, STREAM_WH, STREAM_ATT = 1, 2, 3     # Philox stream ids of the three masks drawn from one seed
 STREAM_SAMPLE = 4                           # the selection keys of the neighbour sampler (sampling.py; csrc/rng.h sample_keys4)
 STREAM_WALK = 5                             # the step keys of random_walk (subgraph.py; csrc/rng.h walk_keys4)
+STREAM_NEG = 6                              # the draw keys of negative_edges (linkpred.py; csrc/rng.h neg_keys4)
 FORCE_WIDE = _config.dropout_wide   # round 1's wide-operand projection everywhere
 
 

@@ -387,6 +387,27 @@ class CSRGraph:
         from .subgraph import induced_subgraph
         return induced_subgraph(self, nodes)
 
+    def find_edges(self, row: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+        """pygat_amd.find_edges(self, row, col): the CSR position of every pair (row[i], col[i]), or -1 (K24 kernel)."""
+        from .linkpred import find_edges
+        return find_edges(self, row, col)
+
+    def has_edges(self, row: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+        """bool [n]: the pair (row[i], col[i]) is an entry of the pattern -- find_edges(row, col) >= 0."""
+        return self.find_edges(row, col) >= 0
+
+    def reverse_edge_ids(self) -> torch.Tensor:
+        """int64 [nnz], cached: for the entry (i, j) at every CSR position, the position of (j, i), or -1 if the pattern does not
+        hold it.  A symmetric pattern has it already (the mirror permutation perm_f, no kernel); otherwise one find_edges over the
+        swapped pairs of edge_rc (one host read, refused during stream capture)."""
+        if getattr(self, "_reverse_edge_ids", None) is None:
+            if self.symmetric:
+                self._reverse_edge_ids = self.perm_f.long()
+            else:
+                rc = self.fwd.edge_rc
+                self._reverse_edge_ids = self.find_edges(rc[:, 1], rc[:, 0])
+        return self._reverse_edge_ids
+
     def internal_view(self) -> InternalOrderView:
         """The degree-ordered pattern for node arrays that are themselves in internal order (see InternalOrderView)."""
         g, to_user, to_int = self.degree_ordered()
