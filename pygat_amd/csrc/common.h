@@ -43,6 +43,7 @@ static inline int kernel_footprint_of(const void* fn, int* regs, int* scratch) {
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 static inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 #ifdef __HIPCC__
 __host__ __device__

@@ -25,26 +25,15 @@
 // (entries), and a weight that is negative or NaN raises info[4] in count / count_long.  A row is kept whole ("all") when its count is
 // below the fanout; at exactly the fanout the select runs and ends at the row's largest key, which keeps the same entries.  No float
 // is summed across lanes and no result depends on an order of atomics: two runs give the same bits.
-#include "common.h"
-#include "prefix_scan.h"
+//
+// Shared with K23 and K24 (minibatch.h): the row of an id that may be no node (node_row, is_node), the list of long rows, the room of
+// a row in the block's CSR, the workspace cursor, the launcher's refusals and the footprint lookup; prefix_scan.h: sample_scan.
+#include "minibatch.h"
 #include "rng.h"
-#include <string.h>
 
 namespace pygat {
 
 constexpr int SAMPLE_WAVE_QUADS = 64;     // a row whose positions span more Philox calls than this goes to a work-group
-constexpr int SAMPLE_LONG_BLOCKS = 1024;  // work-groups that walk the list of long rows
-
-// positions [b, e) of block row r in the graph; an id outside [0, n) is an empty row and is never used as an index
-__device__ __forceinline__ bool sample_row(int n, const int32_t* __restrict__ rowptr, const int64_t* __restrict__ dst, int r, int* b,
-                                           int* e) {
-  const int64_t id = dst[r];
-  *b = *e = 0;
-  if (id < 0 || id >= n) return false;
-  const int rb = rowptr[id], re = rowptr[id + 1];
-  if (re > rb) { *b = rb; *e = re; }
-  return true;
-}
 
 __device__ __forceinline__ int sample_quads(int b, int e) { return ((e - 1) >> 2) - (b >> 2) + 1; }   // e > b
 
@@ -59,7 +48,7 @@ __global__ __launch_bounds__(256) void sample_count_kernel(int n, const int32_t*
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= n_dst) return;
   int b, e;
-  if (sample_row(n, rowptr, dst, r, &b, &e)) marker[dst[r]] = r + 1;
+  if (node_row(n, rowptr, dst[r], &b, &e)) marker[dst[r]] = r + 1;
   else info[2] = 1;
   int d = e - b;
   const int lf = (d > 0 && sample_quads(b, e) > SAMPLE_WAVE_QUADS) ? 1 : 0;
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(256) void sample_verify_kernel(int n, int n_dst, co
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= n_dst) return;
   const int64_t id = dst[r];
-  if (id >= 0 && id < n && marker[id] != r + 1) info[3] = 1;
+  if (is_node(id, n) && marker[id] != r + 1) info[3] = 1;
 }
 
 // WEIGHTED: the counts are not scanned yet (blk_rowptr is not read); sample_entries_kernel writes info[0] later
@@ -96,7 +85,7 @@ __global__ __launch_bounds__(256) void sample_list_kernel(int n_dst, const int32
   const int r = blockIdx.x * 256 + threadIdx.x;
   if constexpr (!WEIGHTED)
     if (r == 0) info[0] = blk_rowptr[n_dst];
-  if (r < n_dst && lflag[r]) llist[lptr[r]] = r;
+  long_list_put(n_dst, lflag, lptr, llist, r);
 }
 
 __global__ void sample_entries_kernel(int n_dst, const int32_t* __restrict__ blk_rowptr, int32_t* __restrict__ info) {
@@ -156,17 +145,6 @@ __device__ __forceinline__ void sample_emit(uint64_t seed, uint32_t hop, int b, 
   }
 }
 
-// where block row r writes: false if nothing is to be written (a repeat in dst was seen, an empty row, or a range that does not
-// lie inside the caller's cap -- which no valid input produces)
-__device__ __forceinline__ bool sample_room(const int32_t* __restrict__ blk_rowptr, const int32_t* __restrict__ info, int r, int64_t cap,
-                                            int64_t* base, int* room) {
-  if (info[3]) return false;
-  const int bb = blk_rowptr[r], be = blk_rowptr[r + 1];
-  if (bb < 0 || be <= bb || (int64_t)be > cap) return false;
-  *base = bb; *room = be - bb;
-  return true;
-}
-
 // ---- WEIGHTED, long rows: the number of positive weights of every row of the list, one work-group per row (integer sums) ----------
 __global__ __launch_bounds__(256) void sample_count_long_kernel(int n, const int32_t* __restrict__ rowptr, int n_dst,
                                                                 const int64_t* __restrict__ dst, int fanout,
@@ -174,13 +152,12 @@ __global__ __launch_bounds__(256) void sample_count_long_kernel(int n, const int
                                                                 const int32_t* __restrict__ llist, int32_t* __restrict__ cnt,
                                                                 int32_t* __restrict__ info) {
   __shared__ int wsum[4];
-  int n_long = lptr[n_dst];
-  if (n_long > n_dst) n_long = n_dst;
+  const int n_long = long_list_len(lptr, n_dst);
   for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
-    const int r = llist[x];
-    if (r < 0 || r >= n_dst) continue;
+    int r;
+    if (!long_list_row(llist, x, n_dst, &r)) continue;
     int b, e;
-    sample_row(n, rowptr, dst, r, &b, &e);
+    node_row(n, rowptr, dst[r], &b, &e);
     int pos = 0;
     bool bad = false;
     for (int p = b + (int)threadIdx.x; p < e; p += 256) {
@@ -209,8 +186,8 @@ __global__ __launch_bounds__(256) void sample_select_wave_kernel(int n, const in
   if (r >= n_dst) return;
   int b, e, room;
   int64_t base;
-  sample_row(n, rowptr, dst, r, &b, &e);
-  if (e <= b || sample_quads(b, e) > SAMPLE_WAVE_QUADS || !sample_room(blk_rowptr, info, r, cap, &base, &room)) return;
+  node_row(n, rowptr, dst[r], &b, &e);
+  if (e <= b || sample_quads(b, e) > SAMPLE_WAVE_QUADS || !csr_room(blk_rowptr, r, cap, &base, &room, info + 3)) return;
   const uint64_t seed = seedp[0];
   const bool all = WEIGHTED ? room < fanout : e - b <= fanout;     // (room = min(positive weights, fanout))
   uint32_t T = 0;
@@ -265,15 +242,14 @@ __global__ __launch_bounds__(256) void sample_select_block_kernel(int n, const i
   __shared__ int sel[2];
   const int tid = threadIdx.x;
   const uint64_t seed = seedp[0];
-  int n_long = lptr[n_dst];
-  if (n_long > n_dst) n_long = n_dst;
+  const int n_long = long_list_len(lptr, n_dst);
   for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
-    const int r = llist[x];
-    if (r < 0 || r >= n_dst) continue;
+    int r;
+    if (!long_list_row(llist, x, n_dst, &r)) continue;
     int b, e, room;
     int64_t base;
-    sample_row(n, rowptr, dst, r, &b, &e);
-    if (e <= b || !sample_room(blk_rowptr, info, r, cap, &base, &room)) continue;
+    node_row(n, rowptr, dst[r], &b, &e);
+    if (e <= b || !csr_room(blk_rowptr, r, cap, &base, &room, info + 3)) continue;
     const bool all = WEIGHTED ? room < fanout : e - b <= fanout;
     uint32_t T = 0;
     int kk = fanout;
@@ -319,7 +295,7 @@ __global__ __launch_bounds__(256) void sample_clear_dst_kernel(int n, int n_dst,
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= n_dst) return;
   const int64_t id = dst[r];
-  if (id >= 0 && id < n) mark[id] = 0;
+  if (is_node(id, n)) mark[id] = 0;
 }
 
 __global__ __launch_bounds__(256) void sample_sources_kernel(int n, int n_dst, const int32_t* __restrict__ mark,
@@ -362,43 +338,32 @@ struct SampleWs {
   int64_t marker, mark, rank, cnt, lflag, lptr, llist, tiles, total;
 };
 static inline SampleWs sample_ws(int n, int n_dst) {
-  auto up = [](int64_t v) { return (v + 3) & ~(int64_t)3; };
+  WsCursor c;
   SampleWs w;
-  int64_t at = 0;
-  w.marker = at; at += up(n);
-  w.mark = at; at += up(n);
-  w.rank = at; at += up((int64_t)n + 1);
-  w.cnt = at; at += up(n_dst);
-  w.lflag = at; at += up(n_dst);
-  w.lptr = at; at += up((int64_t)n_dst + 1);
-  w.llist = at; at += up(n_dst);
-  w.tiles = at; at += up((int64_t)(pygat_scan_workspace_bytes(n > n_dst ? n : n_dst) / sizeof(int32_t)));
-  w.total = at;
+  w.marker = c.take(n);
+  w.mark = c.take(n);
+  w.rank = c.take((int64_t)n + 1);
+  w.cnt = c.take(n_dst);
+  w.lflag = c.take(n_dst);
+  w.lptr = c.take((int64_t)n_dst + 1);
+  w.llist = c.take(n_dst);
+  w.tiles = c.take((int64_t)(pygat_scan_workspace_bytes(n > n_dst ? n : n_dst) / sizeof(int32_t)));
+  w.total = c.at;
   return w;
 }
 
 int footprint_k22(const char* name, int* regs, int* scratch) {
-  static const struct { const char* name; const void* fn; } names[] = {
-      {"k22_count", reinterpret_cast<const void*>(&sample_count_kernel<false>)},
-      {"k22_verify", reinterpret_cast<const void*>(&sample_verify_kernel)},
-      {"k22_list", reinterpret_cast<const void*>(&sample_list_kernel<false>)},
-      {"k22_select_wave", reinterpret_cast<const void*>(&sample_select_wave_kernel<false>)},
-      {"k22_select_block", reinterpret_cast<const void*>(&sample_select_block_kernel<false>)},
-      {"k22_clear_dst", reinterpret_cast<const void*>(&sample_clear_dst_kernel)},
-      {"k22_sources", reinterpret_cast<const void*>(&sample_sources_kernel)},
-      {"k22_relabel", reinterpret_cast<const void*>(&sample_relabel_kernel)},
-      {"k22_count_weighted", reinterpret_cast<const void*>(&sample_count_kernel<true>)},
-      {"k22_list_weighted", reinterpret_cast<const void*>(&sample_list_kernel<true>)},
-      {"k22_count_long_weighted", reinterpret_cast<const void*>(&sample_count_long_kernel)},
-      {"k22_entries_weighted", reinterpret_cast<const void*>(&sample_entries_kernel)},
-      {"k22_select_wave_weighted", reinterpret_cast<const void*>(&sample_select_wave_kernel<true>)},
-      {"k22_select_block_weighted", reinterpret_cast<const void*>(&sample_select_block_kernel<true>)}};
-  for (const auto& nm : names)
-    if (!strcmp(name, nm.name)) return kernel_footprint_of(nm.fn, regs, scratch);
-  set_error("kernel_footprint: unknown kernel '%s' (k22_count, k22_verify, k22_list, k22_select_wave, k22_select_block, k22_clear_dst, "
-            "k22_sources, k22_relabel; k22_count_weighted, k22_list_weighted, k22_count_long_weighted, k22_entries_weighted, "
-            "k22_select_wave_weighted, k22_select_block_weighted)", name);
-  return PYGAT_EINVAL;
+  return footprint_lookup(
+      name,
+      {{"k22_count", &sample_count_kernel<false>}, {"k22_verify", &sample_verify_kernel}, {"k22_list", &sample_list_kernel<false>},
+       {"k22_select_wave", &sample_select_wave_kernel<false>}, {"k22_select_block", &sample_select_block_kernel<false>},
+       {"k22_clear_dst", &sample_clear_dst_kernel}, {"k22_sources", &sample_sources_kernel}, {"k22_relabel", &sample_relabel_kernel},
+       {"k22_count_weighted", &sample_count_kernel<true>}, {"k22_list_weighted", &sample_list_kernel<true>},
+       {"k22_count_long_weighted", &sample_count_long_kernel}, {"k22_entries_weighted", &sample_entries_kernel},
+       {"k22_select_wave_weighted", &sample_select_wave_kernel<true>}, {"k22_select_block_weighted", &sample_select_block_kernel<true>}},
+      "k22_count, k22_verify, k22_list, k22_select_wave, k22_select_block, k22_clear_dst, k22_sources, k22_relabel; k22_count_weighted, "
+      "k22_list_weighted, k22_count_long_weighted, k22_entries_weighted, k22_select_wave_weighted, k22_select_block_weighted",
+      regs, scratch);
 }
 
 }  // namespace pygat
@@ -418,21 +383,18 @@ static int sample_block_launch(const char* what, int n, int64_t nnz, const int32
                                const int64_t* dst, int fanout, const float* weight, const void* seed, uint32_t hop, int64_t cap,
                                int64_t src_cap, int32_t* blk_rowptr, int32_t* blk_col, int32_t* edge_rc, int64_t* edge_ids,
                                int64_t* src_nodes, int32_t* info, void* ws, void* stream) {
-  PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
-                (long long)nnz);
+  PYGAT_PASS(require_graph(what, n, nnz));
   PYGAT_REQUIRE(n_dst > 0 && n_dst <= n, "%s: n_dst=%d: 1 <= n_dst <= n = %d expected (distinct node ids)", what, n_dst, n);
   PYGAT_REQUIRE(fanout > 0, "%s: fanout=%d: a fanout >= 1 expected (INT32_MAX keeps whole rows)", what, fanout);
-  const struct { const void* p; const char* name; } tables[] = {
-      {rowptr, "rowptr"}, {col, "col"}, {dst, "dst"}, {seed, "seed"}, {blk_rowptr, "blk_rowptr"}, {blk_col, "blk_col"},
-      {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {src_nodes, "src_nodes"}, {info, "info"}, {ws, "workspace"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {dst, "dst"}, {seed, "seed"}, {blk_rowptr, "blk_rowptr"},
+                                   {blk_col, "blk_col"}, {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {src_nodes, "src_nodes"},
+                                   {info, "info"}, {ws, "workspace"}}));
   if constexpr (WEIGHTED) {
     PYGAT_REQUIRE(weight, "%s: null weight", what);
     PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(weight) & 3u) == 0, "%s: weight must be 4-byte aligned", what);
   }
-  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(seed) & 7u) == 0, "%s: seed must be 8-byte aligned", what);
-  PYGAT_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 7u) == 0 && (reinterpret_cast<uintptr_t>(edge_ids) & 7u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(src_nodes) & 7u) == 0, "%s: dst, edge_ids and src_nodes must be 8-byte aligned", what);
+  PYGAT_REQUIRE(aligned8(seed), "%s: seed must be 8-byte aligned", what);
+  PYGAT_REQUIRE(aligned8(dst) && aligned8(edge_ids) && aligned8(src_nodes), "%s: dst, edge_ids and src_nodes must be 8-byte aligned", what);
   PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
   PYGAT_REQUIRE(cap > 0 && cap < ((int64_t)1 << 31), "%s: cap=%lld: room for 1 <= cap < 2^31 entries expected", what, (long long)cap);
   PYGAT_REQUIRE(src_cap >= n_dst, "%s: src_cap=%lld is below n_dst=%d", what, (long long)src_cap, n_dst);
@@ -445,34 +407,24 @@ static int sample_block_launch(const char* what, int n, int64_t nnz, const int32
   hipStream_t st = (hipStream_t)stream;
   const uint64_t* seedp = (const uint64_t*)seed;
   const dim3 rows((unsigned)cdiv(n_dst, 256)), tpb(256);
-  const dim3 longs((unsigned)(n_dst < SAMPLE_LONG_BLOCKS ? n_dst : SAMPLE_LONG_BLOCKS));
+  const dim3 longs = long_grid(n_dst);
 
-  hipError_t me = hipMemsetAsync(mark, 0, (size_t)n * sizeof(int32_t), st);
-  if (me == hipSuccess) me = hipMemsetAsync(info, 0, (WEIGHTED ? 5 : 4) * sizeof(int32_t), st);
-  if (me != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %s", what, hipGetErrorString(me));
-    return PYGAT_EHIP;
-  }
+  PYGAT_PASS(clear_async(what, mark, (size_t)n * sizeof(int32_t), st));
+  PYGAT_PASS(clear_async(what, info, (WEIGHTED ? 5 : 4) * sizeof(int32_t), st));
   hipLaunchKernelGGL(sample_count_kernel<WEIGHTED>, rows, tpb, 0, st, n, rowptr, n_dst, dst, fanout, weight, marker, cnt, lflag,
                      src_nodes, info);
   hipLaunchKernelGGL(sample_verify_kernel, rows, tpb, 0, st, n, n_dst, dst, marker, info);
   PYGAT_CHECK_LAUNCH(what);
-  int rc;
   if constexpr (WEIGHTED) {
-    rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
-    if (rc != PYGAT_OK) return rc;
+    PYGAT_PASS(pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream));
     hipLaunchKernelGGL(sample_list_kernel<true>, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
     hipLaunchKernelGGL(sample_count_long_kernel, longs, tpb, 0, st, n, rowptr, n_dst, dst, fanout, weight, lptr, llist, cnt, info);
     PYGAT_CHECK_LAUNCH(what);
-    rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
-    if (rc != PYGAT_OK) return rc;
+    PYGAT_PASS(pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream));
     hipLaunchKernelGGL(sample_entries_kernel, dim3(1), dim3(64), 0, st, n_dst, blk_rowptr, info);
   } else {
-    rc = pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream);
-    if (rc != PYGAT_OK) return rc;
-    rc = pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream);
-    if (rc != PYGAT_OK) return rc;
+    PYGAT_PASS(pygat_exclusive_scan_i32(cnt, n_dst, blk_rowptr, tiles, stream));
+    PYGAT_PASS(pygat_exclusive_scan_i32(lflag, n_dst, lptr, tiles, stream));
     hipLaunchKernelGGL(sample_list_kernel<false>, rows, tpb, 0, st, n_dst, lflag, lptr, blk_rowptr, llist, info);
   }
   hipLaunchKernelGGL(sample_select_wave_kernel<WEIGHTED>, dim3((unsigned)cdiv(n_dst, 4)), tpb, 0, st, n, rowptr, col, n_dst, dst, fanout,
@@ -481,8 +433,7 @@ static int sample_block_launch(const char* what, int n, int64_t nnz, const int32
                      blk_rowptr, lptr, llist, edge_ids, mark, info);
   hipLaunchKernelGGL(sample_clear_dst_kernel, rows, tpb, 0, st, n, n_dst, dst, mark);
   PYGAT_CHECK_LAUNCH(what);
-  rc = pygat_exclusive_scan_i32(mark, n, rank, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(pygat_exclusive_scan_i32(mark, n, rank, tiles, stream));
   hipLaunchKernelGGL(sample_sources_kernel, dim3((unsigned)cdiv(n, 256)), tpb, 0, st, n, n_dst, mark, rank, src_cap, src_nodes, info);
   hipLaunchKernelGGL(sample_relabel_kernel, dim3((unsigned)cdiv(cap, 256)), tpb, 0, st, nnz, col, n_dst, dst, cap, blk_rowptr, marker,
                      rank, edge_ids, blk_col, edge_rc, info);

@@ -29,29 +29,24 @@
 // pygat_random_walk: one thread per walker, one Philox call per four steps (rng.h walk_keys4).  A step is three DEPENDENT loads
 // (rowptr[cur], rowptr[cur + 1] -- one line --, then col[...]) at random addresses: the walk is bound by their latency, hundreds of
 // cycles each from L2 or the Infinity Cache, and hides it only through the number of walkers in flight.  It is not tuned beyond that.
-#include "common.h"
-#include "prefix_scan.h"
+//
+// Shared with K22 and K24 (minibatch.h): the row of an id that may be no node (node_row, is_node), the list of long rows, the room of
+// a row in the sub-pattern's CSR, the workspace cursor, the launchers' refusals and the footprint lookup; prefix_scan.h: sample_scan.
+#include "minibatch.h"
 #include "rng.h"
-#include <string.h>
 
 namespace pygat {
 
 constexpr int SUB_THREAD_ROW = 64;      // a row of at most this many entries is counted and filled by one thread
 constexpr int SUB_WAVE_ROW = 256;       // ... of at most this many by one wave, 64 positions per round; longer rows: a work-group
 constexpr int SUB_BLOCK_ROUND = 1024;   // positions a work-group takes per round (256 threads x 4 consecutive positions)
-constexpr int SUB_LONG_BLOCKS = 1024;   // work-groups that walk the list of long rows
 constexpr int SUB_PART_BLOCKS = 1024;   // work-groups (and partial counts) of the empty-row count
 
 // positions [b, e) of sub-row r in the graph; false (an empty range) if r is no row or its id is no node
 __device__ __forceinline__ bool sub_row(int n, const int32_t* __restrict__ rowptr, const int64_t* __restrict__ sub_nodes, int r,
                                         int n_sub, int* b, int* e) {
   *b = *e = 0;
-  if (r < 0 || r >= n_sub) return false;
-  const int64_t id = sub_nodes[r];
-  if (id < 0 || id >= n) return false;
-  const int rb = rowptr[id], re = rowptr[id + 1];
-  if (re > rb) { *b = rb; *e = re; }
-  return true;
+  return is_node(r, n_sub) && node_row(n, rowptr, sub_nodes[r], b, e);
 }
 
 __global__ __launch_bounds__(256) void subgraph_mark_kernel(int n, int n_in, const int64_t* __restrict__ nodes,
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(256) void subgraph_mark_kernel(int n, int n_in, con
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_in) return;
   const int64_t id = nodes[i];
-  if (id < 0 || id >= n) info[2] = 1;
+  if (!is_node(id, n)) info[2] = 1;
   else mark[id] = 1;
 }
 
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(256) void subgraph_nodes_kernel(int n, int n_in, co
   if (j < n && mark[j]) sub_nodes[rank[j]] = j;
   if (j < n_in) {
     const int64_t id = nodes[j];
-    index[j] = (id >= 0 && id < n) ? rank[id] : -1;
+    index[j] = is_node(id, n) ? rank[id] : -1;
   }
 }
 
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(256) void subgraph_count_rows_kernel(int n, const i
 __global__ __launch_bounds__(256) void subgraph_list_kernel(int m, const int32_t* __restrict__ lflag, const int32_t* __restrict__ lptr,
                                                             int32_t* __restrict__ llist) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r < m && lflag[r]) llist[lptr[r]] = r;
+  long_list_put(m, lflag, lptr, llist, r);
 }
 
 __global__ __launch_bounds__(256) void subgraph_count_long_kernel(int n, const int32_t* __restrict__ rowptr,
@@ -120,13 +115,12 @@ __global__ __launch_bounds__(256) void subgraph_count_long_kernel(int n, const i
                                                                   const int32_t* __restrict__ lptr, const int32_t* __restrict__ llist,
                                                                   int32_t* __restrict__ cnt) {
   __shared__ int wsum[4];
-  int n_sub = rank[n], n_long = lptr[m];
+  int n_sub = rank[n];
   if (n_sub > m) n_sub = m;
-  if (n_long > m) n_long = m;
+  const int n_long = long_list_len(lptr, m);
   for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
-    const int r = llist[x];
-    int b, e;
-    if (!sub_row(n, rowptr, sub_nodes, r, n_sub, &b, &e)) continue;
+    int r, b, e;
+    if (!long_list_row(llist, x, n_sub, &r) || !node_row(n, rowptr, sub_nodes[r], &b, &e)) continue;
     int t = 0, tot;
     for (int p = b + (int)threadIdx.x; p < e; p += 256) t += mark[gcol[p]] ? 1 : 0;
     sample_scan<256>(t, &tot, wsum);
@@ -173,15 +167,6 @@ __device__ __forceinline__ void sub_emit(const SubOut& o, int64_t k, int r, int 
   o.edge_ids[k] = (int64_t)p;
 }
 
-// where sub-row r writes: false if nothing is to be written (no row, no entry, or a range that does not lie inside [0, sub_nnz))
-__device__ __forceinline__ bool sub_room(const int32_t* __restrict__ sub_rowptr, int r, int64_t sub_nnz, int* base, int* room) {
-  const int sb = sub_rowptr[r], se = sub_rowptr[r + 1];
-  *base = *room = 0;
-  if (sb < 0 || se <= sb || (int64_t)se > sub_nnz) return false;
-  *base = sb; *room = se - sb;
-  return true;
-}
-
 __global__ __launch_bounds__(256) void subgraph_fill_rows_kernel(int n, const int32_t* __restrict__ rowptr,
                                                                  const int32_t* __restrict__ gcol, int n_sub, int64_t sub_nnz,
                                                                  const int64_t* __restrict__ sub_nodes,
@@ -191,7 +176,7 @@ __global__ __launch_bounds__(256) void subgraph_fill_rows_kernel(int n, const in
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 256 + threadIdx.x;
   int b, e, base = 0, room = 0;
-  if (!sub_row(n, rowptr, sub_nodes, r, n_sub, &b, &e) || !sub_room(sub_rowptr, r, sub_nnz, &base, &room)) b = e = 0;
+  if (!sub_row(n, rowptr, sub_nodes, r, n_sub, &b, &e) || !csr_room(sub_rowptr, r, sub_nnz, &base, &room)) b = e = 0;
   const int d = e - b;
   if (d <= SUB_THREAD_ROW) {
     int k = 0;
@@ -230,12 +215,11 @@ __global__ __launch_bounds__(256) void subgraph_fill_long_kernel(int n, const in
                                                                  const int32_t* __restrict__ lptr, const int32_t* __restrict__ llist,
                                                                  SubOut out) {
   __shared__ int wsum[4];
-  int n_long = lptr[m];
-  if (n_long > m) n_long = m;
+  const int n_long = long_list_len(lptr, m);
   for (int x = blockIdx.x; x < n_long; x += gridDim.x) {       // (every condition below is uniform over the work-group)
-    const int r = llist[x];
-    int b, e, base, room;
-    if (!sub_row(n, rowptr, sub_nodes, r, n_sub, &b, &e) || e - b <= SUB_WAVE_ROW || !sub_room(sub_rowptr, r, sub_nnz, &base, &room))
+    int r, b, e, base = 0, room = 0;
+    if (!long_list_row(llist, x, n_sub, &r) || !node_row(n, rowptr, sub_nodes[r], &b, &e) || e - b <= SUB_WAVE_ROW ||
+        !csr_room(sub_rowptr, r, sub_nnz, &base, &room))
       continue;
     int before = 0;
     for (int p0 = b; p0 < e; p0 += SUB_BLOCK_ROUND) {
@@ -272,7 +256,7 @@ __global__ __launch_bounds__(256) void random_walk_kernel(int n, const int32_t* 
   const int64_t id = start[w];
   int64_t* out = walks + w * ((int64_t)length + 1);
   out[0] = id;
-  if (id < 0 || id >= n) {                // never used as an index: the walker stays, and the caller hears of it
+  if (!is_node(id, n)) {                  // never used as an index: the walker stays, and the caller hears of it
     info[0] = 1;
     for (int t = 1; t <= length; ++t) out[t] = id;
     return;
@@ -295,41 +279,30 @@ struct SubWs {
 };
 static inline int sub_rows_bound(int n, int64_t n_in) { return n_in < n ? (int)n_in : n; }
 static inline SubWs sub_ws(int n, int m) {
-  auto up = [](int64_t v) { return (v + 3) & ~(int64_t)3; };
+  WsCursor c;
   SubWs w;
-  int64_t at = 0;
-  w.mark = at; at += up(n);
-  w.rank = at; at += up((int64_t)n + 1);
-  w.cnt = at; at += up(m);
-  w.lflag = at; at += up(m);
-  w.lptr = at; at += up((int64_t)m + 1);
-  w.llist = at; at += up(m);
-  w.part = at; at += up(SUB_PART_BLOCKS);
-  w.tiles = at; at += up((int64_t)(pygat_scan_workspace_bytes(n) / sizeof(int32_t)));
-  w.total = at;
+  w.mark = c.take(n);
+  w.rank = c.take((int64_t)n + 1);
+  w.cnt = c.take(m);
+  w.lflag = c.take(m);
+  w.lptr = c.take((int64_t)m + 1);
+  w.llist = c.take(m);
+  w.part = c.take(SUB_PART_BLOCKS);
+  w.tiles = c.take((int64_t)(pygat_scan_workspace_bytes(n) / sizeof(int32_t)));
+  w.total = c.at;
   return w;
 }
 
 int footprint_k23(const char* name, int* regs, int* scratch) {
-  static const struct { const char* name; const void* fn; } names[] = {
-      {"k23_mark", reinterpret_cast<const void*>(&subgraph_mark_kernel)},
-      {"k23_nodes", reinterpret_cast<const void*>(&subgraph_nodes_kernel)},
-      {"k23_count_rows", reinterpret_cast<const void*>(&subgraph_count_rows_kernel)},
-      {"k23_list", reinterpret_cast<const void*>(&subgraph_list_kernel)},
-      {"k23_count_long", reinterpret_cast<const void*>(&subgraph_count_long_kernel)},
-      {"k23_empties", reinterpret_cast<const void*>(&subgraph_empties_kernel)},
-      {"k23_info", reinterpret_cast<const void*>(&subgraph_info_kernel)},
-      {"k23_fill_rows", reinterpret_cast<const void*>(&subgraph_fill_rows_kernel)},
-      {"k23_fill_long", reinterpret_cast<const void*>(&subgraph_fill_long_kernel)},
-      {"k23_walk", reinterpret_cast<const void*>(&random_walk_kernel)}};
-  for (const auto& nm : names)
-    if (!strcmp(name, nm.name)) return kernel_footprint_of(nm.fn, regs, scratch);
-  set_error("kernel_footprint: unknown kernel '%s' (k23_mark, k23_nodes, k23_count_rows, k23_list, k23_count_long, k23_empties, "
-            "k23_info, k23_fill_rows, k23_fill_long, k23_walk)", name);
-  return PYGAT_EINVAL;
+  return footprint_lookup(
+      name,
+      {{"k23_mark", &subgraph_mark_kernel}, {"k23_nodes", &subgraph_nodes_kernel}, {"k23_count_rows", &subgraph_count_rows_kernel},
+       {"k23_list", &subgraph_list_kernel}, {"k23_count_long", &subgraph_count_long_kernel}, {"k23_empties", &subgraph_empties_kernel},
+       {"k23_info", &subgraph_info_kernel}, {"k23_fill_rows", &subgraph_fill_rows_kernel}, {"k23_fill_long", &subgraph_fill_long_kernel},
+       {"k23_walk", &random_walk_kernel}},
+      "k23_mark, k23_nodes, k23_count_rows, k23_list, k23_count_long, k23_empties, k23_info, k23_fill_rows, k23_fill_long, k23_walk", regs,
+      scratch);
 }
-
-static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // the refusals that the count, the fill and the workspace query share
 static int sub_sizes(const char* what, int n, int64_t n_in) {
@@ -344,8 +317,7 @@ using namespace pygat;
 
 extern "C" int pygat_subgraph_workspace_bytes(int n, int64_t n_in, size_t* bytes) {
   PYGAT_REQUIRE(bytes, "subgraph_workspace_bytes: null bytes");
-  const int rc = sub_sizes("subgraph_workspace_bytes", n, n_in);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(sub_sizes("subgraph_workspace_bytes", n, n_in));
   *bytes = (size_t)sub_ws(n, sub_rows_bound(n, n_in)).total * sizeof(int32_t);
   return PYGAT_OK;
 }
@@ -353,13 +325,10 @@ extern "C" int pygat_subgraph_workspace_bytes(int n, int64_t n_in, size_t* bytes
 extern "C" int pygat_subgraph_count(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_in, const int64_t* nodes,
                                     int64_t* sub_nodes, int64_t* index, int32_t* sub_rowptr, int32_t* info, void* ws, void* stream) {
   const char* what = "subgraph_count";
-  int rc = sub_sizes(what, n, n_in);
-  if (rc != PYGAT_OK) return rc;
-  PYGAT_REQUIRE(nnz > 0 && nnz < ((int64_t)1 << 31), "%s: nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, (long long)nnz);
-  const struct { const void* p; const char* name; } tables[] = {{rowptr, "rowptr"}, {col, "col"}, {nodes, "nodes"},
-                                                                {sub_nodes, "sub_nodes"}, {index, "index"},
-                                                                {sub_rowptr, "sub_rowptr"}, {info, "info"}, {ws, "workspace"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(sub_sizes(what, n, n_in));
+  PYGAT_PASS(require_graph(what, n, nnz, false));
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {nodes, "nodes"}, {sub_nodes, "sub_nodes"}, {index, "index"},
+                                   {sub_rowptr, "sub_rowptr"}, {info, "info"}, {ws, "workspace"}}));
   PYGAT_REQUIRE(aligned8(nodes) && aligned8(sub_nodes) && aligned8(index), "%s: nodes, sub_nodes and index must be 8-byte aligned", what);
   PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
 
@@ -372,29 +341,21 @@ extern "C" int pygat_subgraph_count(int n, int64_t nnz, const int32_t* rowptr, c
   hipStream_t st = (hipStream_t)stream;
   const dim3 tpb(256), rows((unsigned)cdiv(m, 256)), ids((unsigned)cdiv(ni, 256)), both((unsigned)cdiv(ni > n ? ni : n, 256));
   const int nparts = (int)(cdiv(m, 256) < SUB_PART_BLOCKS ? cdiv(m, 256) : SUB_PART_BLOCKS);
-  const dim3 longs((unsigned)(m < SUB_LONG_BLOCKS ? m : SUB_LONG_BLOCKS));
+  const dim3 longs = long_grid(m);
 
-  hipError_t me = hipMemsetAsync(mark, 0, (size_t)n * sizeof(int32_t), st);
-  if (me == hipSuccess) me = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), st);
-  if (me != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %s", what, hipGetErrorString(me));
-    return PYGAT_EHIP;
-  }
+  PYGAT_PASS(clear_async(what, mark, (size_t)n * sizeof(int32_t), st));
+  PYGAT_PASS(clear_async(what, info, 4 * sizeof(int32_t), st));
   hipLaunchKernelGGL(subgraph_mark_kernel, ids, tpb, 0, st, n, ni, nodes, mark, info);
   PYGAT_CHECK_LAUNCH(what);
-  rc = pygat_exclusive_scan_i32(mark, n, rank, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(pygat_exclusive_scan_i32(mark, n, rank, tiles, stream));
   hipLaunchKernelGGL(subgraph_nodes_kernel, both, tpb, 0, st, n, ni, nodes, mark, rank, sub_nodes, index);
   hipLaunchKernelGGL(subgraph_count_rows_kernel, rows, tpb, 0, st, n, rowptr, col, m, sub_nodes, mark, rank, cnt, lflag);
   PYGAT_CHECK_LAUNCH(what);
-  rc = pygat_exclusive_scan_i32(lflag, m, lptr, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(pygat_exclusive_scan_i32(lflag, m, lptr, tiles, stream));
   hipLaunchKernelGGL(subgraph_list_kernel, rows, tpb, 0, st, m, lflag, lptr, llist);
   hipLaunchKernelGGL(subgraph_count_long_kernel, longs, tpb, 0, st, n, rowptr, col, m, sub_nodes, mark, rank, lptr, llist, cnt);
   PYGAT_CHECK_LAUNCH(what);
-  rc = pygat_exclusive_scan_i32(cnt, m, sub_rowptr, tiles, stream);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(pygat_exclusive_scan_i32(cnt, m, sub_rowptr, tiles, stream));
   hipLaunchKernelGGL(subgraph_empties_kernel, dim3((unsigned)nparts), tpb, 0, st, n, m, rank, cnt, part);
   hipLaunchKernelGGL(subgraph_info_kernel, dim3(1), tpb, 0, st, n, m, nparts, rank, sub_rowptr, part, info);
   PYGAT_CHECK_LAUNCH(what);
@@ -405,18 +366,15 @@ extern "C" int pygat_subgraph_fill(int n, int64_t nnz, const int32_t* rowptr, co
                                    int64_t sub_nnz, const int64_t* sub_nodes, const int32_t* sub_rowptr, int32_t* sub_col,
                                    int32_t* edge_rc, int64_t* edge_ids, void* ws, void* stream) {
   const char* what = "subgraph_fill";
-  const int rc = sub_sizes(what, n, n_in);
-  if (rc != PYGAT_OK) return rc;
-  PYGAT_REQUIRE(nnz > 0 && nnz < ((int64_t)1 << 31), "%s: nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, (long long)nnz);
+  PYGAT_PASS(sub_sizes(what, n, n_in));
+  PYGAT_PASS(require_graph(what, n, nnz, false));
   const int m = sub_rows_bound(n, n_in);
   PYGAT_REQUIRE(n_sub > 0 && n_sub <= m, "%s: n_sub=%d rows: 1 <= n_sub <= min(n_in, n) = %d expected (info[0] of subgraph_count)", what,
                 n_sub, m);
   PYGAT_REQUIRE(sub_nnz > 0 && sub_nnz <= nnz, "%s: sub_nnz=%lld entries: 1 <= sub_nnz <= nnz = %lld expected (info[1] of subgraph_count)",
                 what, (long long)sub_nnz, (long long)nnz);
-  const struct { const void* p; const char* name; } tables[] = {{rowptr, "rowptr"}, {col, "col"}, {sub_nodes, "sub_nodes"},
-                                                                {sub_rowptr, "sub_rowptr"}, {sub_col, "sub_col"},
-                                                                {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {ws, "workspace"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {sub_nodes, "sub_nodes"}, {sub_rowptr, "sub_rowptr"},
+                                   {sub_col, "sub_col"}, {edge_rc, "edge_rc"}, {edge_ids, "edge_ids"}, {ws, "workspace"}}));
   PYGAT_REQUIRE(aligned8(sub_nodes) && aligned8(edge_rc) && aligned8(edge_ids), "%s: sub_nodes, edge_rc and edge_ids must be 8-byte aligned",
                 what);
   PYGAT_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
@@ -426,11 +384,10 @@ extern "C" int pygat_subgraph_fill(int n, int64_t nnz, const int32_t* rowptr, co
   const int32_t *mark = base + w.mark, *rank = base + w.rank, *lptr = base + w.lptr, *llist = base + w.llist;
   hipStream_t st = (hipStream_t)stream;
   const SubOut out = {sub_col, reinterpret_cast<int2*>(edge_rc), edge_ids};
-  const dim3 longs((unsigned)(n_sub < SUB_LONG_BLOCKS ? n_sub : SUB_LONG_BLOCKS));
   hipLaunchKernelGGL(subgraph_fill_rows_kernel, dim3((unsigned)cdiv(n_sub, 256)), dim3(256), 0, st, n, rowptr, col, n_sub, sub_nnz,
                      sub_nodes, sub_rowptr, mark, rank, out);
-  hipLaunchKernelGGL(subgraph_fill_long_kernel, longs, dim3(256), 0, st, n, rowptr, col, m, n_sub, sub_nnz, sub_nodes, sub_rowptr, mark,
-                     rank, lptr, llist, out);
+  hipLaunchKernelGGL(subgraph_fill_long_kernel, long_grid(n_sub), dim3(256), 0, st, n, rowptr, col, m, n_sub, sub_nnz, sub_nodes,
+                     sub_rowptr, mark, rank, lptr, llist, out);
   PYGAT_CHECK_LAUNCH(what);
   return PYGAT_OK;
 }
@@ -438,23 +395,15 @@ extern "C" int pygat_subgraph_fill(int n, int64_t nnz, const int32_t* rowptr, co
 extern "C" int pygat_random_walk(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_walk, const int64_t* start,
                                  int length, const void* seed, uint32_t hop, int64_t* walks, int32_t* info, void* stream) {
   const char* what = "random_walk";
-  PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
-                (long long)nnz);
+  PYGAT_PASS(require_graph(what, n, nnz));
   PYGAT_REQUIRE(n_walk > 0 && n_walk < ((int64_t)1 << 31), "%s: n_walk=%lld: 1 <= n_walk < 2^31 walkers expected", what,
                 (long long)n_walk);
   PYGAT_REQUIRE(length > 0, "%s: length=%d: a walk of length >= 1 expected", what, length);
-  const struct { const void* p; const char* name; } tables[] = {{rowptr, "rowptr"}, {col, "col"}, {start, "start"},
-                                                                {seed, "seed"}, {walks, "walks"}, {info, "info"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {start, "start"}, {seed, "seed"}, {walks, "walks"}, {info, "info"}}));
   PYGAT_REQUIRE(aligned8(seed), "%s: seed must be 8-byte aligned", what);
   PYGAT_REQUIRE(aligned8(start) && aligned8(walks), "%s: start and walks must be 8-byte aligned", what);
   hipStream_t st = (hipStream_t)stream;
-  const hipError_t me = hipMemsetAsync(info, 0, sizeof(int32_t), st);
-  if (me != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %s", what, hipGetErrorString(me));
-    return PYGAT_EHIP;
-  }
+  PYGAT_PASS(clear_async(what, info, sizeof(int32_t), st));
   hipLaunchKernelGGL(random_walk_kernel, dim3((unsigned)cdiv(n_walk, 256)), dim3(256), 0, st, n, rowptr, col, n_walk, start, length,
                      (const uint64_t*)seed, hop, walks, info);
   PYGAT_CHECK_LAUNCH(what);

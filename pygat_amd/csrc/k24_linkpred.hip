@@ -20,13 +20,15 @@
 // addresses -- rowptr[u], rowptr[u + 1] (one line), then about log2(d) columns per search (two searches for a draw with
 // exclude_self) -- so both are bound by the latency of those loads, hundreds of cycles each from L2 or the Infinity Cache, and hide
 // it only through the number of threads in flight.  They are not tuned beyond that occupancy.
-#include "common.h"
+//
+// Shared with K22 and K23 (minibatch.h): is_node, the launchers' refusals and the footprint lookup.
+#include "minibatch.h"
 #include "rng.h"
-#include <string.h>
 
 namespace pygat {
 
-// the row [b, e) of node u, kept inside [0, nnz) whatever rowptr holds
+// the row [b, e) of node u, kept inside [0, nnz) whatever rowptr holds.  Not minibatch.h's node_row with the clamp on top: that
+// reads the same rows but compiles to other code, and these two kernels stay the bytes they were
 __device__ __forceinline__ void lp_row(const int32_t* __restrict__ rowptr, int u, int nnz, int* b, int* e) {
   int rb = rowptr[u], re = rowptr[u + 1];
   if (rb < 0) rb = 0;
@@ -54,7 +56,8 @@ __global__ __launch_bounds__(256) void find_edges_kernel(int n, int nnz, const i
   if (gi >= n_pairs) return;
   const int i = (int)gi;
   const int64_t r = row[i], c = colq[i];
-  if (r < 0 || r >= n || c < 0 || c >= n) {       // never used as an index, and the caller hears of it
+  if (r < 0 || r >= n || c < 0 || c >= n) {       // never used as an index, and the caller hears of it.  (Written out: on
+                                                  // is_node the two checks compile to other code, and this kernel stays its bytes)
     info[0] = 1;
     pos[i] = -1;
     return;
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(256) void draw_negatives_kernel(int n, int nnz, con
   if (gi >= n_draws) return;
   const int i = (int)gi;
   const int64_t id = src[i / num_neg];
-  if (id < 0 || id >= n) {                        // never used as an index, and the caller hears of it
+  if (!is_node(id, n)) {                          // never used as an index, and the caller hears of it
     info[0] = 1;
     neg[i] = -1;
     return;
@@ -115,26 +118,7 @@ __global__ __launch_bounds__(256) void draw_negatives_kernel(int n, int nnz, con
 }
 
 int footprint_k24(const char* name, int* regs, int* scratch) {
-  static const struct { const char* name; const void* fn; } names[] = {
-      {"k24_find", reinterpret_cast<const void*>(&find_edges_kernel)},
-      {"k24_draw", reinterpret_cast<const void*>(&draw_negatives_kernel)}};
-  for (const auto& nm : names)
-    if (!strcmp(name, nm.name)) return kernel_footprint_of(nm.fn, regs, scratch);
-  set_error("kernel_footprint: unknown kernel '%s' (k24_find, k24_draw)", name);
-  return PYGAT_EINVAL;
-}
-
-static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-// clears info [words] on the stream; the launchers' one HIP call before the kernel
-static int lp_clear_info(const char* what, int32_t* info, int words, hipStream_t st) {
-  const hipError_t me = hipMemsetAsync(info, 0, (size_t)words * sizeof(int32_t), st);
-  if (me != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %s", what, hipGetErrorString(me));
-    return PYGAT_EHIP;
-  }
-  return PYGAT_OK;
+  return footprint_lookup(name, {{"k24_find", &find_edges_kernel}, {"k24_draw", &draw_negatives_kernel}}, "k24_find, k24_draw", regs, scratch);
 }
 
 }  // namespace pygat
@@ -144,17 +128,13 @@ using namespace pygat;
 extern "C" int pygat_find_edges(int n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int64_t n_pairs, const int64_t* row,
                                 const int64_t* colq, int64_t* pos, int32_t* info, void* stream) {
   const char* what = "find_edges";
-  PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
-                (long long)nnz);
+  PYGAT_PASS(require_graph(what, n, nnz));
   PYGAT_REQUIRE(n_pairs > 0 && n_pairs < ((int64_t)1 << 31), "%s: n_pairs=%lld: 1 <= n_pairs < 2^31 pairs expected", what,
                 (long long)n_pairs);
-  const struct { const void* p; const char* name; } tables[] = {{rowptr, "rowptr"}, {col, "col"}, {row, "row"},
-                                                                {colq, "colq"}, {pos, "pos"}, {info, "info"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {row, "row"}, {colq, "colq"}, {pos, "pos"}, {info, "info"}}));
   PYGAT_REQUIRE(aligned8(row) && aligned8(colq) && aligned8(pos), "%s: row, colq and pos must be 8-byte aligned", what);
   hipStream_t st = (hipStream_t)stream;
-  const int rc = lp_clear_info(what, info, 1, st);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(clear_async(what, info, sizeof(int32_t), st));
   hipLaunchKernelGGL(find_edges_kernel, dim3((unsigned)cdiv(n_pairs, 256)), dim3(256), 0, st, n, (int)nnz, rowptr, col, (int)n_pairs, row,
                      colq, pos, info);
   PYGAT_CHECK_LAUNCH(what);
@@ -165,22 +145,18 @@ extern "C" int pygat_draw_negatives(int n, int64_t nnz, const int32_t* rowptr, c
                                     int num_neg, int exclude_self, const void* seed, uint32_t hop, int64_t* neg, int32_t* info,
                                     void* stream) {
   const char* what = "draw_negatives";
-  PYGAT_REQUIRE(n > 0 && nnz > 0 && nnz < ((int64_t)1 << 31), "%s: n=%d nodes, nnz=%lld: a graph with 1 <= nnz < 2^31 expected", what, n,
-                (long long)nnz);
+  PYGAT_PASS(require_graph(what, n, nnz));
   PYGAT_REQUIRE(n_src > 0 && n_src < ((int64_t)1 << 31), "%s: n_src=%lld: 1 <= n_src < 2^31 source nodes expected", what,
                 (long long)n_src);
   PYGAT_REQUIRE(num_neg > 0, "%s: num_neg=%d: num_neg >= 1 draws per source node expected", what, num_neg);
   PYGAT_REQUIRE(n_src * (int64_t)num_neg < ((int64_t)1 << 31), "%s: n_src=%lld x num_neg=%d draws: fewer than 2^31 expected", what,
                 (long long)n_src, num_neg);
   PYGAT_REQUIRE(exclude_self == 0 || exclude_self == 1, "%s: exclude_self=%d: 0 or 1 expected", what, exclude_self);
-  const struct { const void* p; const char* name; } tables[] = {{rowptr, "rowptr"}, {col, "col"}, {src, "src"},
-                                                                {seed, "seed"}, {neg, "neg"}, {info, "info"}};
-  for (const auto& t : tables) PYGAT_REQUIRE(t.p, "%s: null %s", what, t.name);
+  PYGAT_PASS(require_tables(what, {{rowptr, "rowptr"}, {col, "col"}, {src, "src"}, {seed, "seed"}, {neg, "neg"}, {info, "info"}}));
   PYGAT_REQUIRE(aligned8(seed), "%s: seed must be 8-byte aligned", what);
   PYGAT_REQUIRE(aligned8(src) && aligned8(neg), "%s: src and neg must be 8-byte aligned", what);
   hipStream_t st = (hipStream_t)stream;
-  const int rc = lp_clear_info(what, info, 2, st);
-  if (rc != PYGAT_OK) return rc;
+  PYGAT_PASS(clear_async(what, info, 2 * sizeof(int32_t), st));
   const int n_draws = (int)(n_src * num_neg);
   hipLaunchKernelGGL(draw_negatives_kernel, dim3((unsigned)cdiv(n_draws, 256)), dim3(256), 0, st, n, (int)nnz, rowptr, col, n_draws, src,
                      num_neg, exclude_self, (const uint64_t*)seed, hop, neg, info);

@@ -1,5 +1,6 @@
 // The wave and work-group prefix count of the sampler family (k22_sample.hip: sample_emit, the radix select and count_long;
-// k23_subgraph.hip: the long rows' count and fill): one copy.  Integer only, no atomics.
+// k23_subgraph.hip: the long rows' count and fill): one copy.  Integer only, no atomics.  What else the family shares -- the row of
+// an id that may be no node, the list of long rows, the launchers' preamble -- is in minibatch.h, which includes this file.
 #pragma once
 #include "common.h"
 

@@ -31,11 +31,11 @@ from typing import List, NamedTuple, Optional, Sequence
 import torch
 
 from ._lib import lib, check
+from ._minibatch import _at_least_one, _draw_seed, _graph, _hop, _ids, _no_capture, _seed, _stream, graph_head
 from .dropout import STREAM_NEG    # noqa: F401  (the Philox stream of the draw keys; the kernels hold the same constant, csrc/rng.h)
 from .graph import CSRGraph
-from .sampling import SampledBlock, _fanouts, _seed, _stream, _weight, sample_blocks_weighted
+from .sampling import SampledBlock, _fanouts, _weight, sample_blocks_weighted
 from .spmm import EdgePattern
-from .subgraph import _ids
 
 
 class LinkBatch(NamedTuple):
@@ -66,25 +66,17 @@ def find_edges(graph: CSRGraph, row: torch.Tensor, col: torch.Tensor) -> torch.T
     col = _ids(op, graph, col, "col", "n")
     if row.numel() != col.numel():
         raise ValueError(f"pygat_amd {op}: row holds {row.numel()} ids and col {col.numel()}: one pair per index expected")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: pairs cannot be looked up during stream capture (the check of row and col is read back); "
-                         f"look them up before the capture")
+    _no_capture(op, "pairs cannot be looked up", "the check of row and col is", "look them up")
     n, N, dev = int(row.numel()), graph.n, graph.device
     with torch.cuda.device(dev):
         pos = torch.empty(n, dtype=torch.int64, device=dev)
         info = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib.pygat_find_edges(N, graph.nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n, row.data_ptr(), col.data_ptr(),
-                                   pos.data_ptr(), info.data_ptr(), _stream()), "find_edges")
+        check(lib.pygat_find_edges(*graph_head(graph), n, row.data_ptr(), col.data_ptr(), pos.data_ptr(), info.data_ptr(), _stream()),
+              "find_edges")
         outside = info.item()                                           # the one host read
     if outside:
         raise ValueError(f"pygat_amd {op}: an id in row or col lies outside the graph's nodes [0, {N})")
     return pos
-
-
-def _num_neg(op: str, num_neg) -> int:
-    if isinstance(num_neg, bool) or not isinstance(num_neg, int) or not 1 <= num_neg < 2 ** 31:
-        raise ValueError(f"pygat_amd {op}: num_neg = {num_neg!r}: an int >= 1 expected")
-    return num_neg
 
 
 def negative_edges(graph: CSRGraph, src: torch.Tensor, num_neg: int, *, seed: Optional[torch.Tensor] = None, generator=None,
@@ -99,11 +91,9 @@ def negative_edges(graph: CSRGraph, src: torch.Tensor, num_neg: int, *, seed: Op
     arrive in the ONE host read of the call (two int32).  For that read the call is refused during stream capture.  There is no CPU
     path and no fallback."""
     op = "negative_edges"
-    if not isinstance(graph, CSRGraph):
-        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
-    num_neg = _num_neg(op, num_neg)
-    if isinstance(hop, bool) or not isinstance(hop, int) or not 0 <= hop < 2 ** 32:
-        raise ValueError(f"pygat_amd {op}: hop = {hop!r}: an int in [0, 2^32) expected")
+    _graph(op, graph)
+    _at_least_one(op, "num_neg", num_neg)
+    _hop(op, hop)
     for name, flag in (("exclude_self", exclude_self), ("allow_full", allow_full)):
         if not isinstance(flag, bool):
             raise ValueError(f"pygat_amd {op}: {name} = {flag!r}: True or False expected")
@@ -113,17 +103,14 @@ def negative_edges(graph: CSRGraph, src: torch.Tensor, num_neg: int, *, seed: Op
     n_src, N, dev = int(src.numel()), graph.n, graph.device
     if n_src * num_neg >= 2 ** 31:
         raise ValueError(f"pygat_amd {op}: {n_src} source nodes x {num_neg} draws: fewer than 2^31 draws expected")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: negatives cannot be drawn during stream capture (the check of src is read back); draw them "
-                         f"before the capture")
+    _no_capture(op, "negatives cannot be drawn", "the check of src is", "draw them")
     with torch.cuda.device(dev):
         if seed is None:
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev, generator=generator)
+            seed = _draw_seed(dev, generator)
         neg = torch.empty(n_src, num_neg, dtype=torch.int64, device=dev)
         info = torch.empty(2, dtype=torch.int32, device=dev)
-        check(lib.pygat_draw_negatives(N, graph.nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n_src, src.data_ptr(), num_neg,
-                                       int(exclude_self), seed.data_ptr(), hop, neg.data_ptr(), info.data_ptr(), _stream()),
-              "draw_negatives")
+        check(lib.pygat_draw_negatives(*graph_head(graph), n_src, src.data_ptr(), num_neg, int(exclude_self), seed.data_ptr(), hop,
+                                       neg.data_ptr(), info.data_ptr(), _stream()), "draw_negatives")
         outside, full = info.tolist()                                   # the one host read
     if outside:
         raise ValueError(f"pygat_amd {op}: an id in src lies outside the graph's nodes [0, {N})")
@@ -172,9 +159,8 @@ def link_batch(graph: CSRGraph, edge_ids: torch.Tensor, num_neg: int, fanouts: S
     degree); the index check of EdgePattern.from_indices.  Because of them the call is refused during stream capture.  The wrong
     type, dtype, rank or device is a ValueError before any device work.  There is no CPU path and no fallback."""
     op = "link_batch"
-    if not isinstance(graph, CSRGraph):
-        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
-    num_neg = _num_neg(op, num_neg)
+    _graph(op, graph)
+    _at_least_one(op, "num_neg", num_neg)
     _fanouts(op, fanouts)
     if exclude not in EXCLUDE:
         raise ValueError(f"pygat_amd {op}: exclude = {exclude!r}: one of \"none\", \"positive\", \"reverse\" expected")
@@ -186,14 +172,12 @@ def link_batch(graph: CSRGraph, edge_ids: torch.Tensor, num_neg: int, fanouts: S
     B, nnz, dev = int(edge_ids.numel()), graph.nnz, graph.device
     if B * (2 + num_neg) >= 2 ** 31:
         raise ValueError(f"pygat_amd {op}: {B} positives x (2 + {num_neg}) ids: fewer than 2^31 expected")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: a batch cannot be built during stream capture (its checks and counts are read back); build "
-                         f"it before the capture")
+    _no_capture(op, "a batch cannot be built", "its checks and counts are", "build it")
     with torch.cuda.device(dev):
         if bool(((edge_ids < 0) | (edge_ids >= nnz)).any()):            # a host read
             raise ValueError(f"pygat_amd {op}: an id in edge_ids lies outside the graph's entries [0, {nnz})")
         if seed is None:
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev, generator=generator)
+            seed = _draw_seed(dev, generator)
         u, v = graph.fwd.edge_rc[edge_ids, 0].long(), graph.fwd.col[edge_ids].long()
         neg = negative_edges(graph, u, num_neg, seed=seed, hop=0)
         seeds, inv = torch.unique(torch.cat([u, v, neg.flatten()]), sorted=True, return_inverse=True)

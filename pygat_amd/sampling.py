@@ -41,12 +41,12 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
+from ._minibatch import _at_least_one, _draw_seed, _graph, _hop, _ids, _no_capture, _seed, _stream, _trim, graph_head
 from .dropout import STREAM_SAMPLE    # noqa: F401  (the Philox stream of the keys above; the kernels hold the same constant, csrc/rng.h)
 from .graph import CSRGraph
 from .spmm import EdgePattern
 
 KEEP_ALL = 2 ** 31 - 1     # the fanout the kernels take for "whole rows"
-TRIM_FACTOR = 2            # buffers more than this many times the result are copied down to size
 
 
 class SampledBlock(NamedTuple):
@@ -63,24 +63,8 @@ class SampledBlock(NamedTuple):
     nnz: int
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _seed(op: str, device, seed):
-    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or tuple(seed.shape) != (1,) or seed.device != device:
-        got = f"{seed.dtype} {tuple(seed.shape)} on {seed.device}" if isinstance(seed, torch.Tensor) else type(seed).__name__
-        raise ValueError(f"pygat_amd {op}: seed must be an int64 tensor of shape [1] on the graph's device {device} (the kernels read "
-                         f"it there), got {got}")
-    return seed.contiguous()
-
-
 def _fanout(op: str, fanout) -> int:
-    if fanout is None:
-        return KEEP_ALL
-    if isinstance(fanout, bool) or not isinstance(fanout, int) or not 1 <= fanout <= KEEP_ALL:
-        raise ValueError(f"pygat_amd {op}: fanout = {fanout!r}: an int >= 1, or None for whole rows, expected")
-    return fanout
+    return KEEP_ALL if fanout is None else _at_least_one(op, "fanout", fanout, "an int >= 1, or None for whole rows, expected")
 
 
 def _max_degree(graph: CSRGraph) -> int:
@@ -93,26 +77,12 @@ def _max_degree(graph: CSRGraph) -> int:
 
 def _checked(op: str, graph, dst, fanout, seed, hop):
     """Every refusal that needs no device work -> (dst int64 contiguous, fanout as the kernels take it, seed or None)."""
-    if not isinstance(graph, CSRGraph):
-        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
+    _graph(op, graph)
     fanout = _fanout(op, fanout)
-    if isinstance(hop, bool) or not isinstance(hop, int) or not 0 <= hop < 2 ** 32:
-        raise ValueError(f"pygat_amd {op}: hop = {hop!r}: an int in [0, 2^32) expected")
+    _hop(op, hop)
     if seed is not None:
         seed = _seed(op, graph.device, seed)
-    if not isinstance(dst, torch.Tensor) or not dst.is_cuda:
-        raise ValueError(f"pygat_amd {op}: dst must be a tensor on the GPU (there is no CPU path)")
-    if dst.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"pygat_amd {op}: dst must be int32 or int64, not {dst.dtype}")
-    if dst.dim() != 1 or dst.numel() < 1:
-        raise ValueError(f"pygat_amd {op}: dst [n_dst] with n_dst >= 1 expected, got {tuple(dst.shape)}")
-    if dst.device != graph.device:
-        raise ValueError(f"pygat_amd {op}: dst lives on {dst.device}, the graph on {graph.device}")
-    return dst.to(torch.int64).contiguous(), fanout, seed
-
-
-def _trim(t: torch.Tensor, n: int) -> torch.Tensor:
-    return t[:n].clone() if t.shape[0] > TRIM_FACTOR * max(n, 1) else t[:n]
+    return _ids(op, graph, dst, "dst", "n_dst", limit=False), fanout, seed     # (n_dst is held against graph.n in _sample)
 
 
 def _weight(op: str, graph, w):
@@ -138,12 +108,10 @@ def _sample(op: str, graph, dst, fanout, weight, seed, generator, hop) -> Sample
     n_dst, N, nnz, dev = int(dst.numel()), graph.n, graph.nnz, graph.device
     if n_dst > N:
         raise ValueError(f"pygat_amd {op}: dst holds {n_dst} ids but the graph has {N} nodes: some id repeats")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: a block cannot be sampled during stream capture (its counts and the check of dst are read "
-                         f"back); sample before the capture")
+    _no_capture(op, "a block cannot be sampled", "its counts and the check of dst are", "sample")
     with torch.cuda.device(dev):
         if seed is None:
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev, generator=generator)
+            seed = _draw_seed(dev, generator)
         cap = max(1, min(n_dst * min(fanout, _max_degree(graph)), nnz))
         src_cap = n_dst + min(cap, N)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -152,7 +120,7 @@ def _sample(op: str, graph, dst, fanout, weight, seed, generator, hop) -> Sample
         src_nodes = torch.empty(src_cap, dtype=torch.int64, device=dev)
         info = torch.empty(4 if weight is None else 5, **i32)
         ws = torch.empty(_lib._workspace_bytes("sample_workspace_bytes", N, n_dst), dtype=torch.uint8, device=dev)
-        head = (N, nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n_dst, dst.data_ptr(), fanout)
+        head = (*graph_head(graph), n_dst, dst.data_ptr(), fanout)
         tail = (seed.data_ptr(), hop, cap, src_cap, rowptr.data_ptr(), col.data_ptr(), edge_rc.data_ptr(), edge_ids.data_ptr(),
                 src_nodes.data_ptr(), info.data_ptr(), ws.data_ptr(), _stream())
         if weight is None:
@@ -185,7 +153,7 @@ def _hops(graph, seeds, fanouts, weight, seed, generator) -> List[SampledBlock]:
     op = "sample_neighbors" if weight is None else "sample_neighbors_weighted"
     if seed is None:
         with torch.cuda.device(graph.device):
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=graph.device, generator=generator)
+            seed = _draw_seed(graph.device, generator)
     blocks, dst = [], seeds
     for t in range(len(fanouts)):
         blocks.append(_sample(op, graph, dst, fanouts[-1 - t], weight, seed, None, t))
@@ -241,7 +209,5 @@ def sample_blocks_weighted(graph: CSRGraph, seeds: torch.Tensor, fanouts: Sequen
     op = "sample_blocks_weighted"
     _fanouts(op, fanouts)
     _checked(op, graph, seeds, fanouts[-1], seed, 0)
-    if edge_weight is None:
-        raise ValueError(f"pygat_amd {op}: edge_weight must be a float32 tensor [graph.nnz], not NoneType")
-    _weight(op, graph, edge_weight)
+    _weight(op, graph, edge_weight)                                 # (None included: no tensor)
     return _hops(graph, seeds, fanouts, edge_weight, seed, generator)

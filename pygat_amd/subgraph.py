@@ -38,8 +38,8 @@ import torch
 from . import _lib
 from ._lib import lib, check
 from .dropout import STREAM_WALK    # noqa: F401  (the Philox stream of the step keys; the kernels hold the same constant, csrc/rng.h)
+from ._minibatch import _at_least_one, _draw_seed, _graph, _hop, _ids, _no_capture, _seed, _stream, _trim, graph_head
 from .graph import CSRGraph
-from .sampling import _seed, _stream, _trim
 from .spmm import EdgePattern
 
 
@@ -74,23 +74,6 @@ class InducedSubgraph:
         return f"InducedSubgraph(n={self.n}, nnz={self.nnz}, n_empty_rows={self.n_empty_rows})"
 
 
-def _ids(op: str, graph, ids, name: str, shape: str):
-    """Every refusal of a list of node ids that needs no device work, worded as sampling._checked -> int64 contiguous."""
-    if not isinstance(graph, CSRGraph):
-        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
-    if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
-        raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path)")
-    if ids.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"pygat_amd {op}: {name} must be int32 or int64, not {ids.dtype}")
-    if ids.dim() != 1 or ids.numel() < 1:
-        raise ValueError(f"pygat_amd {op}: {name} [{shape}] with {shape} >= 1 expected, got {tuple(ids.shape)}")
-    if ids.device != graph.device:
-        raise ValueError(f"pygat_amd {op}: {name} lives on {ids.device}, the graph on {graph.device}")
-    if ids.numel() >= 2 ** 31:
-        raise ValueError(f"pygat_amd {op}: {name} holds {ids.numel()} ids: fewer than 2^31 expected")
-    return ids.to(torch.int64).contiguous()
-
-
 def induced_subgraph(graph: CSRGraph, nodes: torch.Tensor) -> InducedSubgraph:
     """The square sub-pattern of `graph` on the set of `nodes` [n_in] (node ids of `graph`, int32 or int64, on its device, n_in >= 1;
     ids may repeat and come in any order), as the module docstring defines it: local ids are ranks in ascending global id, rows keep
@@ -102,16 +85,14 @@ def induced_subgraph(graph: CSRGraph, nodes: torch.Tensor) -> InducedSubgraph:
     CPU path and no fallback."""
     op = "induced_subgraph"
     nodes = _ids(op, graph, nodes, "nodes", "n_in")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: a subgraph cannot be taken during stream capture (its counts and the check of nodes are "
-                         f"read back); take it before the capture")
+    _no_capture(op, "a subgraph cannot be taken", "its counts and the check of nodes are", "take it")
     n_in, N, nnz, dev = int(nodes.numel()), graph.n, graph.nnz, graph.device
     m = min(n_in, N)
     with torch.cuda.device(dev):
         i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
         sub_nodes, index, rowptr, info = torch.empty(m, **i64), torch.empty(n_in, **i64), torch.empty(m + 1, **i32), torch.empty(4, **i32)
         ws = torch.empty(_lib._workspace_bytes("subgraph_workspace_bytes", N, n_in), dtype=torch.uint8, device=dev)
-        head = (N, nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n_in)
+        head = (*graph_head(graph), n_in)
         check(lib.pygat_subgraph_count(*head, nodes.data_ptr(), sub_nodes.data_ptr(), index.data_ptr(), rowptr.data_ptr(),
                                        info.data_ptr(), ws.data_ptr(), _stream()), "subgraph_count")
         n, E, outside, empty = info.tolist()                            # the one host read
@@ -137,26 +118,21 @@ def random_walk(graph: CSRGraph, start: torch.Tensor, length: int, *, seed: Opti
     A start id outside [0, N) raises ValueError: it is found on the device, never used as an index, and its flag is the ONE host
     read of the call (one int32).  For that read the call is refused during stream capture.  There is no CPU path and no fallback."""
     op = "random_walk"
-    if not isinstance(graph, CSRGraph):
-        raise ValueError(f"pygat_amd {op}: a CSRGraph expected, not {type(graph).__name__}")
-    if isinstance(length, bool) or not isinstance(length, int) or not 1 <= length < 2 ** 31:
-        raise ValueError(f"pygat_amd {op}: length = {length!r}: an int >= 1 expected")
-    if isinstance(hop, bool) or not isinstance(hop, int) or not 0 <= hop < 2 ** 32:
-        raise ValueError(f"pygat_amd {op}: hop = {hop!r}: an int in [0, 2^32) expected")
+    _graph(op, graph)
+    _at_least_one(op, "length", length)
+    _hop(op, hop)
     if seed is not None:
         seed = _seed(op, graph.device, seed)
     start = _ids(op, graph, start, "start", "n_walk")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"pygat_amd {op}: walks cannot be drawn during stream capture (the check of start is read back); draw them "
-                         f"before the capture")
+    _no_capture(op, "walks cannot be drawn", "the check of start is", "draw them")
     n_walk, N, dev = int(start.numel()), graph.n, graph.device
     with torch.cuda.device(dev):
         if seed is None:
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev, generator=generator)
+            seed = _draw_seed(dev, generator)
         walks = torch.empty(n_walk, length + 1, dtype=torch.int64, device=dev)
         info = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib.pygat_random_walk(N, graph.nnz, graph.fwd.rowptr.data_ptr(), graph.fwd.col.data_ptr(), n_walk, start.data_ptr(), length,
-                                    seed.data_ptr(), hop, walks.data_ptr(), info.data_ptr(), _stream()), "random_walk")
+        check(lib.pygat_random_walk(*graph_head(graph), n_walk, start.data_ptr(), length, seed.data_ptr(), hop, walks.data_ptr(),
+                                    info.data_ptr(), _stream()), "random_walk")
         outside = info.item()                                           # the one host read
     if outside:
         raise ValueError(f"pygat_amd {op}: an id in start lies outside the graph's nodes [0, {N})")

@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from sample_bench import timed, summary    # noqa: E402  (the shared timing conventions)
+from sample_bench import alternate, footprints, summary, timed    # noqa: E402  (the shared timing conventions and footprint writer)
 
 K24_KERNELS = ("k24_find", "k24_draw")
 
@@ -55,29 +55,6 @@ def torch_negatives(torch, keys, N, src, num_neg):
         if todo.numel() == 0:
             return out.view(-1, num_neg), trips
         out[todo] = torch.randint(0, N, todo.shape, dtype=torch.int64, device=u.device)
-
-
-def footprints(torch, path):
-    import ctypes as C
-    from pygat_amd import _lib
-    torch.cuda.init()
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as f:
-        f.write(f"# pygat_kernel_footprint of the K24 kernels on {torch.cuda.get_device_name(0)}: VGPRs per lane, scratch bytes per lane\n")
-        for name in K24_KERNELS:
-            regs, scratch = C.c_int(0), C.c_int(0)
-            _lib.check(_lib.lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)), name)
-            f.write(f"{name:16s} regs={regs.value:3d} scratch={scratch.value}\n")
-
-
-def alternate(torch, args, ours, theirs):
-    for _ in range(args.warmup):
-        ours(), theirs()
-    a, b = [], []
-    for _ in range(args.rounds):
-        a.append(timed(torch, ours, args.steps))
-        b.append(timed(torch, theirs, args.steps))
-    return summary(a), summary(b)
 
 
 def alone(torch, args, fn):
@@ -108,7 +85,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("linkpred_bench: needs a GPU (there is nothing to time without one)")
     if args.footprints:
-        return footprints(torch, args.footprints)
+        return footprints(torch, args.footprints, "K24", K24_KERNELS)
     dev = "cuda"
     rowptr, col = rmat_csr(scale=args.scale, device=dev)
     graph = pg.CSRGraph(rowptr, col)

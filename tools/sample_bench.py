@@ -83,16 +83,30 @@ K22_KERNELS = ("k22_count", "k22_verify", "k22_list", "k22_select_wave", "k22_se
                "k22_select_block_weighted")
 
 
-def footprints(torch, path):
+def alternate(torch, args, ours, theirs):
+    """Warm both up, then `rounds` rounds of `steps` calls of the one and `steps` calls of the other -> their two summaries."""
+    for _ in range(args.warmup):
+        ours(), theirs()
+    a, b = [], []
+    for _ in range(args.rounds):
+        a.append(timed(torch, ours, args.steps))
+        b.append(timed(torch, theirs, args.steps))
+    return summary(a), summary(b)
+
+
+def footprints(torch, path, family, names):
+    """pygat_kernel_footprint of the kernels `names` of `family` (K22, K23, K24) -> the text file at `path`; nothing is timed."""
     import ctypes as C
     from pygat_amd import _lib
     torch.cuda.init()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    width = max(16, max(len(name) for name in names) + 1)
     with open(path, "w") as f:
-        f.write(f"# pygat_kernel_footprint of the K22 kernels on {torch.cuda.get_device_name(0)}: VGPRs per lane, scratch bytes per lane\n")
-        for name in K22_KERNELS:
+        f.write(f"# pygat_kernel_footprint of the {family} kernels on {torch.cuda.get_device_name(0)}: VGPRs per lane, scratch bytes per lane\n")
+        for name in names:
             regs, scratch = C.c_int(0), C.c_int(0)
             _lib.check(_lib.lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)), name)
-            f.write(f"{name:26s} regs={regs.value:3d} scratch={scratch.value}\n")
+            f.write(f"{name:{width}s} regs={regs.value:3d} scratch={scratch.value}\n")
 
 
 def weighted_leg(args, torch, pg, graph, deg, seed):
@@ -108,22 +122,16 @@ def weighted_leg(args, torch, pg, graph, deg, seed):
                 dst, fanout = blk.dst_nodes, fanouts[-1 - t]
                 plain = lambda: pg.sample_neighbors(graph, dst, fanout, seed=seed, hop=t)                    # noqa: E731
                 weighted = lambda: pg.sample_neighbors_weighted(graph, dst, fanout, w, seed=seed, hop=t)    # noqa: E731
-                for _ in range(args.warmup):
-                    plain(), weighted()
                 wb = weighted()
                 assert wb.nnz == blk.nnz, "every weight is positive: both keep min(degree, fanout) entries per row"
-                a, b = [], []
-                for _ in range(args.rounds):
-                    a.append(timed(torch, weighted, args.steps))
-                    b.append(timed(torch, plain, args.steps))
-                sa, sb = summary(a), summary(b)
+                sa, sb = alternate(torch, args, weighted, plain)
                 cand = int(deg[dst].sum())
                 hops.append(dict(hop=t, n_dst=blk.n_dst, fanout=fanout, candidates=cand, kept=wb.nnz, n_src=wb.n_src, unweighted_n_src=blk.n_src,
                                  long_rows=int((deg[dst] > 256).sum()), longest_row=int(deg[dst].max()), weighted=sa, unweighted=sb,
                                  weighted_over_unweighted=round(sa["median_ms"] / sb["median_ms"], 3),
                                  extra_us=round((sa["median_ms"] - sb["median_ms"]) * 1e3, 1)))
                 print(json.dumps(hops[-1]), flush=True)
-            a, b = [], []
+            a, b = [], []                                                       # (both are warm from the hops)
             for _ in range(args.rounds):
                 a.append(timed(torch, lambda: pg.sample_blocks_weighted(graph, seeds, fanouts, w, seed=seed), args.steps))
                 b.append(timed(torch, lambda: pg.sample_blocks(graph, seeds, fanouts, seed=seed), args.steps))
@@ -156,7 +164,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("sample_bench: needs a GPU (there is nothing to time without one)")
     if args.footprints:
-        return footprints(torch, args.footprints)
+        return footprints(torch, args.footprints, "K22", K22_KERNELS)
     dev = "cuda"
     rowptr, col = rmat_csr(scale=args.scale, device=dev)
     graph = pg.CSRGraph(rowptr, col)
@@ -175,15 +183,9 @@ def main():
                 dst, fanout = blk.dst_nodes, fanouts[-1 - t]
                 ours = lambda: pg.sample_neighbors(graph, dst, fanout, seed=seed, hop=t)    # noqa: E731
                 theirs = lambda: torch_hop(pg, torch, graph, dst, fanout)                    # noqa: E731
-                for _ in range(args.warmup):
-                    ours(), theirs()
                 pattern, src, cand = theirs()
                 assert pattern.nnz == blk.nnz and int(deg[dst].sum()) == cand, "both keep min(degree, fanout) entries per row"
-                a, b = [], []
-                for _ in range(args.rounds):
-                    a.append(timed(torch, ours, args.steps))
-                    b.append(timed(torch, theirs, args.steps))
-                sa, sb = summary(a), summary(b)
+                sa, sb = alternate(torch, args, ours, theirs)
                 hops.append(dict(hop=t, n_dst=blk.n_dst, fanout=fanout, candidates=cand, philox_calls_per_pass=-(-cand // 4), kept=blk.nnz,
                                  n_src=blk.n_src, baseline_n_src=int(src.numel()), long_rows=int((deg[dst] > 256).sum()),
                                  longest_row=int(deg[dst].max()), sampler=sa, composition=sb,
