@@ -28,10 +28,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import (_drop_p, _drop_seed, _require_dtypes, _require_heads, _require_inference, _require_pattern, _require_tensor,
-                            _slope)
+from ._pattern_ops import (EdgePattern, _backward_opening, _dropout_front, _entry_buffers, _forward_buffers, _head_stride, _ptr,
+                           _require_dtypes, _require_heads, _require_inference, _require_pattern, _require_rows, _require_tensor, _slope,
+                           _stream)
 from .dropout import STREAM_ATT
-from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
+from .spmm import _launch_spmm
 
 _OP = "additive_attention"
 _OP_DROP = "additive_attention_dropout"
@@ -59,32 +60,18 @@ def _checked(pattern, s_dst, s_src, v, edge_logit, op: str = _OP, bf16: bool = F
     if v.dim() != s_dst.dim() + 1 or v.shape[1:-1] != s_dst.shape[1:]:
         raise ValueError(f"pygat_amd {op}: {vn} {tuple(v.shape)} does not match s_dst {tuple(s_dst.shape)}: {vn} [n_cols, F] with s_dst "
                          f"[n_rows], or {vn} [n_cols, H, F] with s_dst [n_rows, H] and the same number of heads, expected")
-    for name, t, rows, side in named:
-        if t.shape[0] != rows:
-            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+    _require_rows(op, named)
     flat = s_dst.dim() == 1
     H, F = (1 if flat else int(s_dst.shape[1])), int(v.shape[-1])
     _require_heads(op, H, F, _PAD_HINT)
-    return H, F, flat, None if edge_logit is None else _logit_head_stride(pattern, edge_logit, H, flat, op)
+    return H, F, flat, None if edge_logit is None else _head_stride(op, pattern, "edge_logit", edge_logit, H, flat)
 
 
-def _logit_head_stride(pattern, edge_logit, H: int, flat: bool, op: str = _OP) -> int:
-    """1: one value per entry and head ([E, H]; [E] where the tensors have no head axis); 0: one per entry, shared by the heads."""
-    E = pattern.nnz
-    if tuple(edge_logit.shape) == (E,):
-        return 1 if flat else 0
-    if not flat and tuple(edge_logit.shape) == (E, H):
-        return 1
-    want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
-    raise ValueError(f"pygat_amd {op}: edge_logit {want} expected for E = {E} entries and H = {H} heads, got "
-                     f"{tuple(edge_logit.shape)}")
-
-
-def _launch(pattern, which: str, H: int, F: int, slope: float, sd, ss, vc, uc, uhs, drop, rest):
-    """One K20 launcher call, `which` "forward" or "backward_rows", at the entry point of what is present -- a dropout (p, seed) or
-    none: the pattern's arrays, the three tables, the logit (None: the kernels without the term, which without dropout need no
-    permutation in the forward), the dropout group, then `rest`, the pass's own arguments up to the workspace."""
-    kind = "" if drop is None else "dropout_"
+def _launch(pattern, which: str, H: int, F: int, slope: float, sd, ss, vc, uc, uhs, drop, rest, bf16: bool = False):
+    """One K20 launcher call, `which` "forward" or "backward_rows", at the entry point of what is present -- a bf16 v table, a dropout
+    (p, seed) or none: the pattern's arrays, the three tables, the logit (None: the kernels without the term, which without dropout
+    need no permutation in the forward), the dropout group, then `rest`, the pass's own arguments up to the workspace."""
+    kind = "bf16_" if bf16 else "" if drop is None else "dropout_"
     group = () if drop is None else (drop[0], _ptr(drop[1]), STREAM_ATT)
     ws = torch.empty(_lib.add_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=vc.device)
     check(getattr(lib, f"pygat_add_attn_{kind}{which}")(pattern.n_rows, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col),
@@ -109,8 +96,7 @@ class _AdditiveAttentionFn(torch.autograd.Function):
         sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
         n, dev = pattern.n_rows, vc.device
         with torch.cuda.device(dev):
-            out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
-            m, Z = (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
+            out, m, Z = _forward_buffers(n, H, F, dev)
             _launch(pattern, "forward", H, F, slope, sd, ss, vc, uc, uhs, drop, (_ptr(out), H * F, _ptr(m), _ptr(Z)))
         out = out.view((n,) + tuple(v.shape[1:]))
         ctx.save_for_backward(s_dst, s_src, v, edge_logit, out, m, Z, seed)
@@ -121,22 +107,17 @@ class _AdditiveAttentionFn(torch.autograd.Function):
     def backward(ctx, G):
         s_dst, s_src, v, edge_logit, out, m, Z, seed = ctx.saved_tensors
         pattern, slope, (H, F), uhs = ctx.pattern, ctx.slope, ctx.hf, ctx.uhs
-        if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_d, need_s, need_v = ctx.needs_input_grad[1:4]
         need_u = edge_logit is not None and ctx.needs_input_grad[5]
-        if not (need_d or need_s or need_v or need_u):
-            return (None,) * 7
-        if out is None:                                            # no entries: zeros, nothing launched
-            zd, zs, zv, zu = (torch.zeros_like(t) if need else None for t, need in
-                              ((s_dst, need_d), (s_src, need_s), (v, need_v), (edge_logit, need_u)))
-            return None, zd, zs, zv, None, zu, None
+        early = _backward_opening(ctx.op, G, out, 7, {1: (s_dst, need_d), 2: (s_src, need_s), 3: (v, need_v), 5: (edge_logit, need_u)})
+        if early is not None:
+            return early
         n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, v.device
         sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v, edge_logit))
         Gc = G.contiguous().view(n, HF)
         with torch.cuda.device(dev):
             dd = torch.empty(n, H, dtype=torch.float32, device=dev)
-            P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            P, S = _entry_buffers(nnz, H, dev)
             _launch(pattern, "backward_rows", H, F, slope, sd, ss, vc, uc, uhs, None if seed is None else (ctx.p, seed),
                     (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), _ptr(P), _ptr(S)))
             du = None
@@ -191,18 +172,12 @@ def additive_attention_dropout(pattern: EdgePattern, s_dst: torch.Tensor, s_src:
     gets exact zeros.  Differentiable in s_dst, s_src, v and edge_logit; a gradient that is not asked for costs no launch.  float32 GPU
     tensors with additive_attention's limits; bfloat16 tensors are refused."""
     op = _OP_DROP
-    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (s_dst, s_src, v, edge_logit)):
-        raise ValueError(f"pygat_amd {op}: s_dst, s_src, v and edge_logit must be float32: there is no training path on bfloat16 "
-                         f"tensors")
-    p, slope = _drop_p(op, p), _slope(op, negative_slope)
-    if seed is not None:
-        seed = _drop_seed(op, pattern, seed)
-    _checked(pattern, s_dst, s_src, v, edge_logit, op)             # (refusals under this op's name, before anything touches the device)
-    if not training or p == 0.0:
+    slope, drop = _dropout_front(op, pattern, (s_dst, s_src, v, edge_logit), "s_dst, s_src, v and edge_logit must be float32: there is no "
+                                 "training path on bfloat16 tensors", p, negative_slope, seed, generator, training,
+                                 lambda: _checked(pattern, s_dst, s_src, v, edge_logit, op))
+    if drop is None:
         return additive_attention(pattern, s_dst, s_src, v, slope, edge_logit)
-    if seed is None:
-        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
-    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, slope, edge_logit, (p, seed))
+    return _AdditiveAttentionFn.apply(pattern, s_dst, s_src, v, slope, edge_logit, drop)
 
 
 def additive_attention_bf16(pattern: EdgePattern, s_dst: torch.Tensor, s_src: torch.Tensor, v16: torch.Tensor,
@@ -228,9 +203,6 @@ def additive_attention_bf16(pattern: EdgePattern, s_dst: torch.Tensor, s_src: to
         return torch.zeros((n,) + tuple(v16.shape[1:]), dtype=torch.float32, device=dev)
     sd, ss, vc, uc = (None if t is None else t.detach().contiguous() for t in (s_dst, s_src, v16, edge_logit))
     with torch.cuda.device(dev):
-        out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
-        ws = torch.empty(_lib.add_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=dev)
-        check(lib.pygat_add_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope,
-                                              _ptr(sd), _ptr(ss), _ptr(vc), H * F, _ptr(uc), uhs or 0, _ptr(out), H * F, _ptr(ws),
-                                              _stream()), "add_attn_bf16_forward")
+        out = _forward_buffers(n, H, F, dev, state=False)[0]
+        _launch(pattern, "forward", H, F, slope, sd, ss, vc, uc, uhs, None, (_ptr(out), H * F), bf16=True)
     return out.view((n,) + tuple(v16.shape[1:]))

@@ -35,67 +35,13 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from ._lib import lib, check
 from .dropout import STREAM_ATT
-from .spmm import EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _launch_spmm, _ptr, _stream
-
-MIN_F, MAX_F = 4, 256      # a head's width in dot_attention: a power of two in this range (csrc/k19_dot_attention.hip)
+from ._pattern_ops import (EdgePattern, MAX_HEADS, _E_WANT, _backward_opening, _drop_p, _drop_seed, _dropout_front, _entry_buffers,
+                           _forward_buffers, _head_stride, _ptr, _require_entry_rows, _require_float32_grad, _require_heads,
+                           _require_pattern, _require_row_floats, _require_rows, _require_tensor, _stream)
+from .spmm import _launch_spmm
 
 _PAD_HINT = ("zero-padding the columns of q, k and v to the next allowed F leaves the first F columns of the result unchanged "
              "(pass scale yourself: the default follows the padded F)")
-
-
-def _require_pattern(op: str, pattern):
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError(f"pygat_amd {op}: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
-
-
-def _require_tensor(op: str, pattern, name: str, t, dtype=torch.float32, want: str = ""):
-    """The refusals of one tensor (q, k, v, bias, e) that look at nothing but it and the pattern: a tensor on the GPU, of `dtype`
-    (float32, or bfloat16: k and v in dot_attention's inference forward), on the pattern's device.  want: what the message adds."""
-    _require_pattern(op, pattern)
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"pygat_amd {op}: {name} must be a tensor on the GPU (there is no CPU path){want}")
-    if t.dtype != dtype:
-        like = "float32" if dtype == torch.float32 else "bfloat16 like the other table"
-        raise ValueError(f"pygat_amd {op}: {name} must be {like}, not {t.dtype}{want}")
-    if t.device != pattern.device:
-        raise ValueError(f"pygat_amd {op}: {name} lives on {t.device}, the pattern on {pattern.device}{want}")
-
-
-def _require_heads(op: str, H: int, F: int, pad_hint: str):
-    """The row shapes the K19, K20 and K21 kernels take (csrc/da_family.h); pad_hint: how the op's caller reaches an allowed F."""
-    if not (1 <= H <= MAX_HEADS):
-        raise ValueError(f"pygat_amd {op}: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
-    if not (MIN_F <= F <= MAX_F) or F & (F - 1):
-        raise ValueError(f"pygat_amd {op}: F = {F}: a head's width must be a power of two in {MIN_F}..{MAX_F}; {pad_hint}")
-    if H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd {op}: H * F = {H} * {F} = {H * F} floats per row: the limit is H * F <= {MAX_ROW_FLOATS}; "
-                         f"{pad_hint}")
-
-
-def _slope(op: str, negative_slope) -> float:
-    """The negative slope of additive_attention's and gatv2_attention's LeakyReLU: a finite float."""
-    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
-        raise ValueError(f"pygat_amd {op}: negative_slope = {negative_slope!r}: a finite float expected")
-    return float(negative_slope)
-
-
-def _require_inference(op: str, f32_op: str, tensors):
-    """The bf16-table siblings of additive_attention and gatv2_attention are forward only: with grad mode on, an argument that
-    requires grad is refused, and the message names both ways out."""
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
-        raise ValueError(f"pygat_amd {op}: bfloat16 tables are for inference (there is no backward through this op) and an argument "
-                         f"requires grad: call it under torch.no_grad(), or use {f32_op} on float32 tables")
-
-
-def _require_dtypes(op: str, named):
-    """named = ((name, tensor | None, dtype), ...) of a bf16-table op: which of its tensors are bfloat16 tables and which stay
-    float32.  A tensor of the other kind is refused in words that name it and both dtypes (anything that is no tensor is left to
-    _require_tensor)."""
-    for name, t, dtype in named:
-        if isinstance(t, torch.Tensor) and t.dtype != dtype:
-            role = ("a bfloat16 table of this op (make it once: t.bfloat16())" if dtype == torch.bfloat16 else
-                    "float32 in this op: only the row tables of H * F values are bfloat16")
-            raise ValueError(f"pygat_amd {op}: {name} must be {dtype}, not {t.dtype}: it is {role}")
 
 
 def _tables(op: str, pattern, q, others, bf16_others: bool = False):
@@ -111,22 +57,12 @@ def _tables(op: str, pattern, q, others, bf16_others: bool = False):
         if t.dim() != q.dim() or t.shape[1:] != q.shape[1:]:
             raise ValueError(f"pygat_amd {op}: {name} {tuple(t.shape)} does not match q {tuple(q.shape)}: the same number of heads "
                              f"and the same F expected")
-    for name, t, rows, side in named:
-        if t.shape[0] != rows:
-            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+    _require_rows(op, named)
     H, F = (1, int(q.shape[1])) if q.dim() == 2 else (int(q.shape[1]), int(q.shape[2]))
     return H, F, q.dim() == 2
 
 
 # ------------------------------------------------------------------------------------------------------------------------ edge_dot
-def _edge_dot_shapes(pattern, q, k):
-    H, F, flat = _tables("edge_dot", pattern, q, (("k", k),))
-    if not (1 <= H <= MAX_HEADS) or F < 1 or H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd edge_dot: H = {H} heads of F = {F} columns: the limits are 1 <= H <= {MAX_HEADS}, F >= 1 and "
-                         f"H * F <= {MAX_ROW_FLOATS} floats per row")
-    return H, F, flat
-
-
 def _sddmm(pattern: EdgePattern, H: int, F: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """u [E, H], u[e, h] = <a[row_e, h], b[col_e, h]>: one pygat_spmm_grad_values launch with G := a."""
     u = torch.empty(pattern.nnz, H, dtype=torch.float32, device=a.device)
@@ -140,7 +76,8 @@ def _sddmm(pattern: EdgePattern, H: int, F: int, a: torch.Tensor, b: torch.Tenso
 class _EdgeDotFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pattern, q, k, scale):
-        H, F, flat = _edge_dot_shapes(pattern, q, k)
+        H, F, flat = _tables("edge_dot", pattern, q, (("k", k),))
+        _require_row_floats("edge_dot", H, F)
         u = _sddmm(pattern, H, F, q.detach().contiguous(), k.detach().contiguous())
         if scale != 1.0:
             u.mul_(scale)
@@ -153,8 +90,7 @@ class _EdgeDotFn(torch.autograd.Function):
     def backward(ctx, g):
         q, k = ctx.saved_tensors
         pattern, (H, F) = ctx.pattern, ctx.hf
-        if g.dtype != torch.float32:
-            raise ValueError(f"pygat_amd edge_dot: the gradient of the output must be float32, not {g.dtype}")
+        _require_float32_grad("edge_dot", g)
         dq = dk = None
         gs = (g if ctx.scale == 1.0 else g * ctx.scale).contiguous().view(pattern.nnz, H)
         if ctx.needs_input_grad[1]:
@@ -174,26 +110,6 @@ def edge_dot(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, scale: floa
 
 
 # ------------------------------------------------------------------------------------------------------------------- dot_attention
-def _attention_shapes(pattern, q, k, v, bf16_tables: bool = False, op: str = "dot_attention"):
-    H, F, flat = _tables(op, pattern, q, (("k", k), ("v", v)), bf16_tables)
-    _require_heads(op, H, F, _PAD_HINT)
-    return H, F, flat
-
-
-def _bias_head_stride(pattern, bias, H: int, flat: bool, op: str = "dot_attention") -> int:
-    """1: one value per entry and head ([E, H]; [E] where q, k and v have no head axis); 0: one per entry, shared by the heads."""
-    E = pattern.nnz
-    if tuple(bias.shape) == (E,):
-        return 1 if flat else 0
-    if not flat and tuple(bias.shape) == (E, H):
-        return 1
-    want = f"[E] = [{E}]" if flat else f"[E, H] = [{E}, {H}] or [E] = [{E}]"
-    raise ValueError(f"pygat_amd {op}: bias {want} expected for E = {E} entries and H = {H} heads, got {tuple(bias.shape)}")
-
-
-_E_WANT = "; e [E, H, F] (or [E, F] without a head axis), a row per entry at the caller's entry index, expected"
-
-
 def _checked(op: str, pattern, q, k, v, bias, e=None, bf16_tables: bool = False):
     """Every refusal that looks at the pattern and the tensors, those of e and bias alone first -> (H, F, no head axis, the bias's
     head stride | None)."""
@@ -201,11 +117,11 @@ def _checked(op: str, pattern, q, k, v, bias, e=None, bf16_tables: bool = False)
         _require_tensor(op, pattern, "e", e, want=_E_WANT)
     if bias is not None:
         _require_tensor(op, pattern, "bias", bias)
-    H, F, flat = _attention_shapes(pattern, q, k, v, bf16_tables, op)
-    bhs = None if bias is None else _bias_head_stride(pattern, bias, H, flat, op)
-    if e is not None and tuple(e.shape) != (pattern.nnz,) + tuple(q.shape[1:]):
-        raise ValueError(f"pygat_amd {op}: e {[pattern.nnz] + list(q.shape[1:])} expected for E = {pattern.nnz} entries and q "
-                         f"{tuple(q.shape)} -- (E,) + q.shape[1:], a row per entry -- got {tuple(e.shape)}")
+    H, F, flat = _tables(op, pattern, q, (("k", k), ("v", v)), bf16_tables)
+    _require_heads(op, H, F, _PAD_HINT)
+    bhs = None if bias is None else _head_stride(op, pattern, "bias", bias, H, flat)
+    if e is not None:
+        _require_entry_rows(op, pattern, "e", e, "q", q)
     return H, F, flat, bhs
 
 
@@ -233,10 +149,8 @@ def _forward(pattern, H: int, F: int, scale: float, q, k, v, e, bias, bhs, drop,
     """The forward launch on the tensors as they are -> (out [n_rows, H * F], m, Z), m and Z [n_rows, H] what a backward reads (None
     on bf16 tables: nothing is kept for one)."""
     qc, kc, vc, ec, bc = (None if t is None else t.detach().contiguous() for t in (q, k, v, e, bias))
-    n, dev = pattern.n_rows, qc.device
-    with torch.cuda.device(dev):
-        out = torch.empty(n, H * F, dtype=torch.float32, device=dev)
-        m, Z = (None, None) if bf16 else (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
+    with torch.cuda.device(qc.device):
+        out, m, Z = _forward_buffers(pattern.n_rows, H, F, qc.device, state=not bf16)
         _launch(pattern, "forward", H, F, scale, qc, kc, vc, ec, bc, bhs, drop,
                 (_ptr(out), H * F) + (() if bf16 else (_ptr(m), _ptr(Z))), bf16)
     return out, m, Z
@@ -267,22 +181,17 @@ class _DotAttentionFn(torch.autograd.Function):
     def backward(ctx, G):
         q, k, v, e, out, m, Z, bias, seed = ctx.saved_tensors
         pattern, scale, (H, F), bhs = ctx.pattern, ctx.scale, ctx.hf, ctx.bhs
-        if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_q, need_k, need_v = ctx.needs_input_grad[1:4]
         need_e, need_b = e is not None and ctx.needs_input_grad[4], bias is not None and ctx.needs_input_grad[6]
-        if not (need_q or need_k or need_v or need_e or need_b):
-            return (None,) * 8
-        if out is None:                                            # no entries: zeros, nothing launched
-            zq, zk, zv, ze, zb = (torch.zeros_like(t) if need else None for t, need in
-                                  ((q, need_q), (k, need_k), (v, need_v), (e, need_e), (bias, need_b)))
-            return None, zq, zk, zv, ze, None, zb, None
+        early = _backward_opening(ctx.op, G, out, 8, {1: (q, need_q), 2: (k, need_k), 3: (v, need_v), 4: (e, need_e), 6: (bias, need_b)})
+        if early is not None:
+            return early
         n, nnz, HF = pattern.n_rows, pattern.nnz, H * F
         qc, kc, vc, ec, bc = (None if t is None else t.detach().contiguous() for t in (q, k, v, e, bias))
         Gc = G.contiguous().view(n, HF)
         with torch.cuda.device(qc.device):
             dq = torch.empty(n, HF, dtype=torch.float32, device=qc.device)
-            P, S = torch.empty(nnz, H, dtype=torch.float32, device=qc.device), torch.empty(nnz, H, dtype=torch.float32, device=qc.device)
+            P, S = _entry_buffers(nnz, H, qc.device)
             de = torch.empty(nnz, HF, dtype=torch.float32, device=qc.device) if need_e else None      # (every row is written once)
             db = torch.empty(nnz, H, dtype=torch.float32, device=qc.device) if need_b else None
             rest = (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dq), HF, _ptr(P), _ptr(S))
@@ -346,21 +255,6 @@ def dot_attention(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor, v: tor
 
 
 # ----------------------------------------------------------------------------------------------------------- dot_attention_dropout
-def _drop_p(op: str, p) -> float:
-    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:          # (a NaN is outside)
-        raise ValueError(f"pygat_amd {op}: p = {p!r}: a dropout probability in [0, 1] expected")
-    return float(p)
-
-
-def _drop_seed(op: str, pattern, seed):
-    _require_pattern(op, pattern)
-    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or tuple(seed.shape) != (1,) or seed.device != pattern.device:
-        got = f"{seed.dtype} {tuple(seed.shape)} on {seed.device}" if isinstance(seed, torch.Tensor) else type(seed).__name__
-        raise ValueError(f"pygat_amd {op}: seed must be an int64 tensor of shape [1] on the pattern's device {pattern.device} (the "
-                         f"kernels read it there, so a captured graph replays with the value it finds), got {got}")
-    return seed.contiguous()
-
-
 def attention_dropout_mask(pattern: EdgePattern, H: int, p: float, seed: torch.Tensor) -> torch.Tensor:
     """The mask dot_attention_dropout(pattern, ..., p, seed=seed) draws in its kernels, as a tensor: [E, H] float32, 0 or 1 / (1 - p),
     row e the caller's entry e -- one pygat_dropout_mask launch over E * H elements (stream STREAM_ATT of the seed).  For tests and for
@@ -390,18 +284,12 @@ def dot_attention_dropout(pattern: EdgePattern, q: torch.Tensor, k: torch.Tensor
     Differentiable in q, k, v and bias.  float32 GPU tensors with dot_attention's limits; bfloat16 tables are refused (they are for
     inference)."""
     op = "dot_attention_dropout"
-    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (k, v)):
-        raise ValueError(f"pygat_amd {op}: k and v must be float32: there is no training path on bfloat16 tables (they are for "
-                         f"dot_attention's inference forward)")
-    p = _drop_p(op, p)
-    if seed is not None:
-        seed = _drop_seed(op, pattern, seed)
-    _checked(op, pattern, q, k, v, bias)                           # (refusals under this op's name, before anything touches the device)
-    if not training or p == 0.0:
+    _, drop = _dropout_front(op, pattern, (k, v), "k and v must be float32: there is no training path on bfloat16 tables (they are for "
+                             "dot_attention's inference forward)", p, None, seed, generator, training,
+                             lambda: _checked(op, pattern, q, k, v, bias))
+    if drop is None:
         return dot_attention(pattern, q, k, v, scale, bias)
-    if seed is None:
-        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
-    return _DotAttentionFn.apply(pattern, q, k, v, None, scale, bias, (p, seed))
+    return _DotAttentionFn.apply(pattern, q, k, v, None, scale, bias, drop)
 
 
 # -------------------------------------------------------------------------------------------------------------- dot_attention_edge

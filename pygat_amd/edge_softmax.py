@@ -19,7 +19,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .spmm import EdgePattern, MAX_HEADS, _ptr, _stream
+from ._pattern_ops import EdgePattern, MAX_HEADS, _ptr, _require_float32_grad, _require_pattern, _require_rows, _require_tensor, _stream
 
 
 def _grouping(pattern: EdgePattern, by: str):
@@ -32,20 +32,13 @@ def _grouping(pattern: EdgePattern, by: str):
 
 def _heads(pattern, logits: torch.Tensor, by) -> int:
     """-> H of a call, after every refusal."""
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError("pygat_amd edge_softmax: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
+    _require_pattern("edge_softmax", pattern)
     if by not in ("row", "col"):
         raise ValueError(f"pygat_amd edge_softmax: by must be \"row\" or \"col\", not {by!r}")
-    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
-        raise ValueError("pygat_amd edge_softmax: logits must be a tensor on the GPU (there is no CPU path)")
-    if logits.dtype != torch.float32:
-        raise ValueError(f"pygat_amd edge_softmax: logits must be float32, not {logits.dtype}")
-    if logits.device != pattern.device:
-        raise ValueError(f"pygat_amd edge_softmax: logits lives on {logits.device}, the pattern on {pattern.device}")
+    _require_tensor("edge_softmax", pattern, "logits", logits)
     if logits.dim() not in (1, 2):
         raise ValueError(f"pygat_amd edge_softmax: logits [E] or [E, H] expected, got {tuple(logits.shape)}")
-    if logits.shape[0] != pattern.nnz:
-        raise ValueError(f"pygat_amd edge_softmax: logits has {logits.shape[0]} rows but the pattern has {pattern.nnz} entries")
+    _require_rows("edge_softmax", (("logits", logits, pattern.nnz, "entries"),))
     H = 1 if logits.dim() == 1 else int(logits.shape[1])
     if not (1 <= H <= MAX_HEADS):
         raise ValueError(f"pygat_amd edge_softmax: H = {H} heads: the limits are 1 <= H <= {MAX_HEADS}")
@@ -74,8 +67,7 @@ def _forward(pattern: EdgePattern, logits: torch.Tensor, by: str) -> torch.Tenso
 
 
 def _backward(pattern: EdgePattern, alpha: torch.Tensor, by: str, G: torch.Tensor) -> torch.Tensor:
-    if G.dtype != torch.float32:
-        raise ValueError(f"pygat_amd edge_softmax: the gradient of the output must be float32, not {G.dtype}")
+    _require_float32_grad("edge_softmax", G)
     G = G.contiguous()
     dl = torch.empty_like(alpha)
     if pattern.nnz == 0:

@@ -34,10 +34,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
-from .dot_attention import (_E_WANT, _drop_p, _drop_seed, _require_dtypes, _require_heads, _require_inference, _require_pattern,
-                            _require_tensor, _slope)
+from ._pattern_ops import (EdgePattern, _E_WANT, _backward_opening, _dropout_front, _entry_buffers, _forward_buffers, _ptr,
+                           _require_dtypes, _require_entry_rows, _require_heads, _require_inference, _require_pattern, _require_rows,
+                           _require_tensor, _slope, _stream)
 from .dropout import STREAM_ATT
-from .spmm import EdgePattern, _launch_spmm, _ptr, _stream
+from .spmm import _launch_spmm
 
 _OP = "gatv2_attention"
 _OP_DROP = "gatv2_attention_dropout"
@@ -64,10 +65,8 @@ def _checked(pattern, x_dst, x_src, a, v, op: str = _OP, sfx: str = ""):
     if a.shape != x_dst.shape[1:]:
         raise ValueError(f"pygat_amd {op}: a {tuple(a.shape)} does not match x_dst {tuple(x_dst.shape)}: a [F] with x_dst [n_rows, F], "
                          f"or a [H, F] with x_dst [n_rows, H, F], expected")
-    for name, t, rows, side in (("x_dst", x_dst, pattern.n_rows, "rows"), (xn, x_src, pattern.n_cols, "columns"),
-                                (vn, v, pattern.n_cols, "columns")):
-        if t.shape[0] != rows:
-            raise ValueError(f"pygat_amd {op}: {name} has {t.shape[0]} rows but the pattern has {rows} {side}")
+    _require_rows(op, (("x_dst", x_dst, pattern.n_rows, "rows"), (xn, x_src, pattern.n_cols, "columns"),
+                       (vn, v, pattern.n_cols, "columns")))
     H, F = (1 if x_dst.dim() == 2 else int(x_dst.shape[1])), int(x_dst.shape[-1])
     _require_heads(op, H, F, _PAD_HINT)
     return H, F
@@ -75,13 +74,6 @@ def _checked(pattern, x_dst, x_src, a, v, op: str = _OP, sfx: str = ""):
 
 def _workspace(pattern, H: int, F: int, dev):
     return torch.empty(_lib.v2_attn_workspace_bytes(pattern.nnz, H, F), dtype=torch.uint8, device=dev)
-
-
-def _checked_e(pattern, x_dst, e, op: str = _OP_EDGE, name: str = "e"):
-    """The refusals of e's shape, after _checked: a row per entry, shaped like a row of x_dst."""
-    if tuple(e.shape) != (pattern.nnz,) + tuple(x_dst.shape[1:]):
-        raise ValueError(f"pygat_amd {op}: {name} {[pattern.nnz] + list(x_dst.shape[1:])} expected for E = {pattern.nnz} entries and x_dst "
-                         f"{tuple(x_dst.shape)} -- (E,) + x_dst.shape[1:], a row per entry -- got {tuple(e.shape)}")
 
 
 def _edge_rows(e, HF: int):
@@ -94,6 +86,27 @@ def _edge_rows(e, HF: int):
     if e.shape[0] > 1 and e.stride(-1) == 1 and inner and e.stride(0) >= HF and e.stride(0) % 4 == 0 and e.data_ptr() % chunk == 0:
         return e, e.stride(0)
     return e.contiguous(), HF
+
+
+def _launch(pattern, which: str, H: int, F: int, slope: float, xd, xs, ac, vc, edge, drop, rest, ws, bf16: bool = False):
+    """One K21 launcher call, `which` "forward", "backward_rows" or "backward_cols" (the pass on the transposed pattern: no v, and
+    under dropout the plain entry point, since it reads S alone), at the entry point of what is present -- edge, the (rows, leading
+    dimension) of _edge_rows, a dropout (p, seed), bf16 tables, or none -- on its argument list: the pattern's arrays, the tables, the
+    group of e or of dropout, then `rest`, the pass's own arguments up to the workspace ws (one serves both passes of a backward)."""
+    cols, HF = which == "backward_cols", H * F
+    kind = ("edge_" if edge is not None else "dropout_" if drop is not None and not cols else "") + ("bf16_" if bf16 else "")
+    n, csr = (pattern.n_cols, pattern.transposed()) if cols else (pattern.n_rows, (pattern.rowptr, pattern.col, pattern.perm))
+    args = (n, pattern.nnz, _ptr(csr[0]), _ptr(csr[1]))
+    if edge is not None or drop is not None or which != "forward":     # (the forward without either walks in CSR order alone; the
+        args += (_ptr(csr[2]),)                                        # entry index places the rows of e and the mask's draws)
+    args += (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac))
+    if not cols:
+        args += (_ptr(vc), HF)
+    if edge is not None:
+        args += (_ptr(edge[0]), edge[1])
+    elif kind == "dropout_":
+        args += (drop[0], _ptr(drop[1]), STREAM_ATT)
+    check(getattr(lib, f"pygat_v2_attn_{kind}{which}")(*args, *rest, _ptr(ws), _stream()), f"v2_attn_{kind}{which}")
 
 
 class _Gatv2AttentionFn(torch.autograd.Function):
@@ -109,7 +122,7 @@ class _Gatv2AttentionFn(torch.autograd.Function):
         op = _OP_EDGE if e is not None else _OP if drop is None else _OP_DROP
         H, F = _checked(pattern, x_dst, x_src, a, v, op)
         if e is not None:
-            _checked_e(pattern, x_dst, e, op)
+            _require_entry_rows(op, pattern, "e", e, "x_dst", x_dst)
         p, seed = (None, None) if drop is None else drop
         ctx.pattern, ctx.slope, ctx.hf, ctx.shared, ctx.op, ctx.p = pattern, slope, (H, F), shared, op, p
         if pattern.nnz == 0:                                       # every row is without entries: zeros, and nothing is launched
@@ -119,21 +132,10 @@ class _Gatv2AttentionFn(torch.autograd.Function):
         vc = None if shared else v.detach().contiguous()
         n, HF, dev = pattern.n_rows, H * F, xd.device
         with torch.cuda.device(dev):
-            out = torch.empty(n, HF, dtype=torch.float32, device=dev)
-            m, Z = (torch.empty(n, H, dtype=torch.float32, device=dev) for _ in range(2))
+            out, m, Z = _forward_buffers(n, H, F, dev)
             ws = _workspace(pattern, H, F, dev)
-            tables = (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF)
-            rest = (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(ws), _stream())
-            if e is not None:                                      # (the entry index places the rows of e: perm)
-                ec, lde = _edge_rows(e, HF)
-                check(lib.pygat_v2_attn_edge_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
-                                                     *tables, _ptr(ec), lde, *rest), "v2_attn_edge_forward")
-            elif drop is None:                                     # (the forward without dropout walks in CSR order alone)
-                check(lib.pygat_v2_attn_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), *tables, *rest),
-                      "v2_attn_forward")
-            else:
-                check(lib.pygat_v2_attn_dropout_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
-                                                        *tables, p, _ptr(seed), STREAM_ATT, *rest), "v2_attn_dropout_forward")
+            _launch(pattern, "forward", H, F, slope, xd, xs, ac, vc, None if e is None else _edge_rows(e, HF), drop,
+                    (_ptr(out), HF, _ptr(m), _ptr(Z)), ws)
         out = out.view(x_dst.shape)
         ctx.save_for_backward(x_dst, x_src, a, v, out, m, Z, seed, e)
         return out
@@ -143,44 +145,34 @@ class _Gatv2AttentionFn(torch.autograd.Function):
     def backward(ctx, G):
         x_dst, x_src, a, v, out, m, Z, seed, e = ctx.saved_tensors
         pattern, slope, (H, F), shared = ctx.pattern, ctx.slope, ctx.hf, ctx.shared
-        if G.dtype != torch.float32:
-            raise ValueError(f"pygat_amd {ctx.op}: the gradient of the output must be float32, not {G.dtype}")
         need_d, need_s, need_a, need_v = ctx.needs_input_grad[1:5]
         need_e = e is not None and ctx.needs_input_grad[8]
-        if not (need_d or need_s or need_a or need_v or need_e):
-            return (None,) * 9
-        if out is None:                                            # no entries: zeros, nothing launched
-            return (None,) + tuple(torch.zeros_like(t) if need else None
-                                   for t, need in ((x_dst, need_d), (x_src, need_s), (a, need_a), (v, need_v))) + (
-                                       None, None, None, torch.zeros_like(e) if need_e else None)
+        early = _backward_opening(ctx.op, G, out, 9,
+                                  {1: (x_dst, need_d), 2: (x_src, need_s), 3: (a, need_a), 4: (v, need_v), 8: (e, need_e)})
+        if early is not None:
+            return early
         n, nnz, HF, dev = pattern.n_rows, pattern.nnz, H * F, x_dst.device
         xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src, a))
         vc = None if shared else v.detach().contiguous()
         Gc = G.contiguous().view(n, HF)
         with torch.cuda.device(dev):
             dd = torch.empty(n, HF, dtype=torch.float32, device=dev)
-            P, S = torch.empty(nnz, H, dtype=torch.float32, device=dev), torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            P, S = _entry_buffers(nnz, H, dev)
             ws = _workspace(pattern, H, F, dev)
-            kind = "edge_" if e is not None else "" if seed is None else "dropout_"
-            group, tail, de = () if seed is None else (ctx.p, _ptr(seed), STREAM_ATT), (), None
+            edge, drop, tail, de = None, None if seed is None else (ctx.p, seed), (), None
             if e is not None:
-                ec, lde = _edge_rows(e, HF)
+                edge = _edge_rows(e, HF)
                 de = torch.empty(nnz, HF, dtype=torch.float32, device=dev) if need_e else None    # (every row is written once)
-                group, tail = (_ptr(ec), lde), (_ptr(de), HF)
-            check(getattr(lib, f"pygat_v2_attn_{kind}backward_rows")(
-                n, nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm), H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac),
-                _ptr(vc), HF, *group, _ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S), *tail, _ptr(ws),
-                _stream()), f"v2_attn_{kind}backward_rows")
+                tail = (_ptr(de), HF)
+            _launch(pattern, "backward_rows", H, F, slope, xd, xs, ac, vc, edge, drop,
+                    (_ptr(out), HF, _ptr(m), _ptr(Z), _ptr(Gc), HF, _ptr(dd), HF, _ptr(P), _ptr(S)) + tail, ws)
             ds = da = dv = None
             if need_s or need_a or need_v:
                 rowptr_t, row_t, perm_t = pattern.transposed()
                 if need_s or need_a:                # one pass forms both: the column's dx_src in registers, da from per-wave records
                     ds = torch.empty(pattern.n_cols, HF, dtype=torch.float32, device=dev)
                     da = torch.empty(HF, dtype=torch.float32, device=dev)
-                    kind, group = ("edge_", (_ptr(ec), lde)) if e is not None else ("", ())
-                    check(getattr(lib, f"pygat_v2_attn_{kind}backward_cols")(
-                        pattern.n_cols, nnz, _ptr(rowptr_t), _ptr(row_t), _ptr(perm_t), H, F, slope, _ptr(xd), HF, _ptr(xs), HF,
-                        _ptr(ac), *group, _ptr(S), _ptr(ds), HF, _ptr(da), _ptr(ws), _stream()), f"v2_attn_{kind}backward_cols")
+                    _launch(pattern, "backward_cols", H, F, slope, xd, xs, ac, None, edge, drop, (_ptr(S), _ptr(ds), HF, _ptr(da)), ws)
                 if need_v:
                     dv = _launch_spmm(pattern.n_cols, nnz, rowptr_t, row_t, perm_t, H, F, P, Gc).view(v.shape)
         return (None, dd.view(x_dst.shape) if need_d else None, ds.view(x_src.shape) if need_s else None,
@@ -230,17 +222,12 @@ def gatv2_attention_dropout(pattern: EdgePattern, x_dst: torch.Tensor, x_src: to
     for costs no launch where a whole launch serves only it.  float32 GPU tensors with gatv2_attention's limits; bfloat16 tensors are
     refused."""
     op = _OP_DROP
-    if any(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for t in (x_dst, x_src, a, v)):
-        raise ValueError(f"pygat_amd {op}: x_dst, x_src, a and v must be float32: there is no training path on bfloat16 tensors")
-    p, slope = _drop_p(op, p), _slope(op, negative_slope)
-    if seed is not None:
-        seed = _drop_seed(op, pattern, seed)
-    _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op)      # (refusals under this op's name, before the device)
-    if not training or p == 0.0:
+    slope, drop = _dropout_front(op, pattern, (x_dst, x_src, a, v), "x_dst, x_src, a and v must be float32: there is no training path on "
+                                 "bfloat16 tensors", p, negative_slope, seed, generator, training,
+                                 lambda: _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op))
+    if drop is None:
         return gatv2_attention(pattern, x_dst, x_src, a, v, slope)
-    if seed is None:
-        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=pattern.device, generator=generator)
-    return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, (p, seed))
+    return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, drop)
 
 
 def gatv2_attention_edge(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch.Tensor, a: torch.Tensor, e: torch.Tensor,
@@ -269,7 +256,7 @@ def gatv2_attention_edge(pattern: EdgePattern, x_dst: torch.Tensor, x_src: torch
     slope = _slope(op, negative_slope)
     _require_tensor(op, pattern, "e", e, want=_E_WANT)             # (a None here would be gatv2_attention)
     _checked(pattern, x_dst, x_src, a, x_src if v is None else v, op)
-    _checked_e(pattern, x_dst, e, op)
+    _require_entry_rows(op, pattern, "e", e, "x_dst", x_dst)
     return _Gatv2AttentionFn.apply(pattern, x_dst, x_src, a, x_src if v is None else v, slope, v is None, None, e)
 
 
@@ -284,24 +271,17 @@ def _forward_bf16(op: str, pattern, x_dst, x_src16, a, v16, e16, negative_slope)
         _require_tensor(op, pattern, "e16", e16, torch.bfloat16, want=_E_WANT)     # (a None here would be gatv2_attention_bf16)
     H, F = _checked(pattern, x_dst, x_src16, a, x_src16 if v16 is None else v16, op, sfx="16")
     if e16 is not None:
-        _checked_e(pattern, x_dst, e16, op, "e16")
+        _require_entry_rows(op, pattern, "e16", e16, "x_dst", x_dst)
     if pattern.nnz == 0:                                           # every row is without entries: zeros, and nothing is launched
         return torch.zeros_like(x_dst)
     xd, xs, ac = (t.detach().contiguous() for t in (x_dst, x_src16, a))
     vc = None if v16 is None else v16.detach().contiguous()
     n, HF, dev = pattern.n_rows, H * F, xd.device
     with torch.cuda.device(dev):
-        out = torch.empty(n, HF, dtype=torch.float32, device=dev)
+        out = _forward_buffers(n, H, F, dev, state=False)[0]
         ws = _workspace(pattern, H, F, dev)
-        tables = (H, F, slope, _ptr(xd), HF, _ptr(xs), HF, _ptr(ac), _ptr(vc), HF)
-        rest = (_ptr(out), HF, _ptr(ws), _stream())
-        if e16 is None:                                            # (no entry index is needed: CSR order alone)
-            check(lib.pygat_v2_attn_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), *tables, *rest),
-                  "v2_attn_bf16_forward")
-        else:                                                      # (the entry index places the rows of e16: perm)
-            ec, lde = _edge_rows(e16, HF)
-            check(lib.pygat_v2_attn_edge_bf16_forward(n, pattern.nnz, _ptr(pattern.rowptr), _ptr(pattern.col), _ptr(pattern.perm),
-                                                      *tables, _ptr(ec), lde, *rest), "v2_attn_edge_bf16_forward")
+        _launch(pattern, "forward", H, F, slope, xd, xs, ac, vc, None if e16 is None else _edge_rows(e16, HF), None, (_ptr(out), HF), ws,
+                bf16=True)
     return out.view(x_dst.shape)
 
 

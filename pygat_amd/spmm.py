@@ -14,99 +14,23 @@ CPU path and no fallback to torch.sparse.
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Optional, Tuple
+from typing import Tuple
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import lib, check
+from ._pattern_ops import (EdgePattern, MAX_HEADS, MAX_ROW_FLOATS, _csr_of, _ptr, _require_float32_grad,    # noqa: F401
+                           _require_row_floats, _require_rows, _require_tensor, _stream)     # (the pattern's home was this module)
 
-MAX_ROW_FLOATS = 1024      # H * F of one call (csrc/k17_spmm.hip)
-MAX_HEADS = 64
 PATTERN_CACHE_SIZE = 8     # patterns SpecialSpmm keeps (the reference passes the same `edge` tensor to every head and every step)
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def _csr_of(key: torch.Tensor, other: torch.Tensor, n: int):
-    """Entries sorted by `key`, stable: -> (rowptr [n + 1], the other index in that order, perm = the caller's entry index of every
-    sorted position), all int32.  No host read."""
-    order = torch.sort(key, stable=True).indices
-    rowptr = torch.searchsorted(key[order].contiguous(), torch.arange(n + 1, device=key.device, dtype=key.dtype))
-    return rowptr.to(torch.int32), other[order].to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
-
-
-class EdgePattern:
-    """A device-resident COO entry list (row, col) of a sparse (n_rows, n_cols) matrix, which may be rectangular, as the K17
-    kernels read it: the entries in the caller's order (edge_rc), the CSR by rows (rowptr, col, perm) and -- built the first time a
-    gradient with respect to b is asked for -- the CSR by columns (rowptr_t, row_t, perm_t).  Entries may be unsorted and may
-    repeat; repeats are separate entries and add, as torch.sparse_coo_tensor's do.  Sorting is stable, so the entries of a row (of
-    a column) are added in the caller's order."""
-
-    def __init__(self, shape, edge_rc, rowptr, col, perm, transposed=None):
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.n_rows, self.n_cols = self.shape
-        self.edge_rc, self.rowptr, self.col, self.perm = edge_rc, rowptr, col, perm
-        self._t = transposed                                  # (rowptr_t, row_t, perm_t) or None: not built yet
-        self.nnz = int(edge_rc.shape[0])
-        self.device = edge_rc.device
-
-    @staticmethod
-    def from_indices(indices: torch.Tensor, shape) -> "EdgePattern":
-        """indices [2, E] (row 0 = the row, row 1 = the column of every entry, any integer dtype), shape = (n_rows, n_cols).
-        The indices are range-checked on the device, once, here: a violation is a ValueError."""
-        if not isinstance(indices, torch.Tensor) or indices.dim() != 2 or indices.shape[0] != 2:
-            raise ValueError("pygat_amd spmm: indices [2, E] expected")
-        if not indices.is_cuda:
-            raise ValueError("pygat_amd spmm: indices must live on the GPU (there is no CPU path)")
-        if indices.dtype.is_floating_point or indices.dtype in (torch.bool, torch.complex64, torch.complex128):
-            raise ValueError(f"pygat_amd spmm: integer indices expected, not {indices.dtype}")
-        if len(shape) != 2:
-            raise ValueError("pygat_amd spmm: shape (n_rows, n_cols) expected")
-        n_rows, n_cols, E = int(shape[0]), int(shape[1]), int(indices.shape[1])
-        if not (0 < n_rows < 2 ** 31 and 0 < n_cols < 2 ** 31 and E < 2 ** 31):
-            raise ValueError(f"pygat_amd spmm: n_rows={n_rows}, n_cols={n_cols} must lie in [1, 2^31) and nnz={E} below 2^31")
-        if torch.cuda.is_current_stream_capturing():
-            raise ValueError("pygat_amd spmm: a pattern cannot be built during stream capture (its index check reads a flag back); "
-                             "build it -- or call SpecialSpmm once with these indices -- before the capture")
-        with torch.cuda.device(indices.device):
-            row, col = indices[0].long(), indices[1].long()
-            if E and bool(((row < 0) | (row >= n_rows) | (col < 0) | (col >= n_cols)).any()):
-                raise ValueError(f"pygat_amd spmm: an index lies outside the shape ({n_rows}, {n_cols})")
-            edge_rc = torch.stack([row, col], 1).to(torch.int32).contiguous()
-            rowptr, c, perm = _csr_of(row, col, n_rows)
-        return EdgePattern((n_rows, n_cols), edge_rc, rowptr, c, perm)
-
-    @property
-    def has_transpose(self) -> bool:
-        return self._t is not None
-
-    def transposed(self) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        """(rowptr_t [n_cols + 1], row_t [E], perm_t [E]): the CSR by columns, built on first use."""
-        if self._t is None:
-            with torch.cuda.device(self.device):
-                self._t = _csr_of(self.edge_rc[:, 1].long(), self.edge_rc[:, 0].long(), self.n_cols)
-        return self._t
 
 
 def _shapes(pattern: EdgePattern, values: torch.Tensor, b: torch.Tensor):
     """-> (H, F) of a call, after every refusal."""
-    if not isinstance(pattern, EdgePattern):
-        raise ValueError("pygat_amd spmm: an EdgePattern expected (EdgePattern.from_indices, CSRGraph.edge_pattern)")
     for name, t in (("values", values), ("b", b)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"pygat_amd spmm: {name} must be a tensor on the GPU (there is no CPU path)")
-        if t.dtype != torch.float32:
-            raise ValueError(f"pygat_amd spmm: {name} must be float32, not {t.dtype}")
-        if t.device != pattern.device:
-            raise ValueError(f"pygat_amd spmm: {name} lives on {t.device}, the pattern on {pattern.device}")
+        _require_tensor("spmm", pattern, name, t)
     if values.dim() == 1 and b.dim() == 2:
         H, F = 1, int(b.shape[1])
     elif values.dim() == 2 and b.dim() == 3 and values.shape[1] == b.shape[1]:
@@ -114,13 +38,8 @@ def _shapes(pattern: EdgePattern, values: torch.Tensor, b: torch.Tensor):
     else:
         raise ValueError(f"pygat_amd spmm: values [E] with b [M, F], or values [E, H] with b [M, H, F], expected; got values "
                          f"{tuple(values.shape)} and b {tuple(b.shape)}")
-    if values.shape[0] != pattern.nnz:
-        raise ValueError(f"pygat_amd spmm: values has {values.shape[0]} rows but the pattern has {pattern.nnz} entries")
-    if b.shape[0] != pattern.n_cols:
-        raise ValueError(f"pygat_amd spmm: b has {b.shape[0]} rows but the pattern has {pattern.n_cols} columns")
-    if not (1 <= H <= MAX_HEADS) or F < 1 or H * F > MAX_ROW_FLOATS:
-        raise ValueError(f"pygat_amd spmm: H = {H} heads of F = {F} columns: the limits are 1 <= H <= {MAX_HEADS}, F >= 1 and "
-                         f"H * F <= {MAX_ROW_FLOATS} floats per row")
+    _require_rows("spmm", (("values", values, pattern.nnz, "entries"), ("b", b, pattern.n_cols, "columns")))
+    _require_row_floats("spmm", H, F)
     return H, F
 
 
@@ -146,8 +65,7 @@ def _backward(pattern: EdgePattern, values: torch.Tensor, b: torch.Tensor, G: to
     values_shape, b_shape = values.shape, b.shape
     H, F = (1, int(b.shape[1])) if b.dim() == 2 else (int(b.shape[1]), int(b.shape[2]))
     val, table = values.detach().contiguous(), b.detach().contiguous()
-    if G.dtype != torch.float32:
-        raise ValueError(f"pygat_amd spmm: the gradient of the output must be float32, not {G.dtype}")
+    _require_float32_grad("spmm", G)
     G = G.contiguous().view(pattern.n_rows, H * F)
     dval = db = None
     if need_values:
