@@ -13,8 +13,9 @@ tests/test_gpu_additive_attention_bf16.py runs them on the device."""
 import torch
 
 import additive_attention_case as base
-import parity
-from dot_attention_case import LANE_SHAPES, _coo, _hub_graph, _report  # noqa: F401
+from dot_attention_case import LANE_SHAPES  # noqa: F401
+from pattern_case import ForwardCase, seeded
+from pattern_graphs import _coo, _hub_graph  # noqa: F401
 
 WIDE_SHAPE = (8, 64)      # 128 chunks of 4 per row: two chunks per lane, which no entry of LANE_SHAPES has
 CHANGED = 0.9             # the share of the entries of an N(0, 1) table that rounding to bfloat16 changes, at least (measured: 0.99998)
@@ -25,7 +26,7 @@ def changed(wide, narrow):
     return float((narrow.double() != wide.double()).double().mean())
 
 
-class Bf16Case:
+class Bf16Case(ForwardCase):
     """`inner` (a Case of additive_attention_case) with v16 [n_cols, (H,) F] bfloat16 in the place of its v."""
     op = "additive_attention_bf16"
 
@@ -50,24 +51,6 @@ class Bf16Case:
         out = base.additive_attention_ref(self.row, self.col, self.shape[0], self.s_dst.to(dtype), self.s_src.to(dtype),
                                           self.widened(dtype), self.slope, u)
         return out.reshape(self.G.shape)
-
-    def refs(self):
-        """(the fp64 ground truth, its fp32 run), computed once."""
-        if self._refs is None:
-            self._refs = (self.ref(torch.float64), self.ref(torch.float32))
-        return self._refs
-
-    def price(self, out, what=None):
-        assert out.shape == self.G.shape and out.dtype == torch.float32, (self.name, out.shape, out.dtype)
-        y64, y32 = self.refs()
-        return _report(what or self.name, {"out": parity.close_fwd(out, y64, f"{what or self.name} out", y32)})
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place."""
-        return self.refs()[1]
-
-    def rehearse(self):
-        return self.price(self.stand_in())
 
 
 def _build_cases():
@@ -99,16 +82,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

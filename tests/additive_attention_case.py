@@ -20,8 +20,9 @@ import torch
 
 import parity
 from dot_attention_bias_case import MASK, first_of_row
-from dot_attention_case import (LANE_SHAPES, _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo, _report, edge_softmax_ref, f32,
-                                lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub)
+from dot_attention_case import LANE_SHAPES, edge_softmax_ref, f32, lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub
+from pattern_case import ModuleCase as ModuleCaseBase, OpCase, _report, seeded
+from pattern_graphs import _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo
 
 SLOPE = 0.2
 KINK_BAND = 2.0 ** -20
@@ -62,7 +63,7 @@ def product_kinks(row, col, s_dst, s_src):
     return kinks(row, col, s_dst, torch.zeros_like(s_src), s_src[col], MODULE_BAND, float(s_dst.abs().mean() + s_src.abs().mean()))
 
 
-class Case:
+class Case(OpCase):
     """One seeded case: the entries (row, col) of a `shape` pattern, s_dst [n_rows, H], s_src [n_cols, H] ~ N(0, std^2), v [n_cols, H, F],
     G [n_rows, H, F] (without the head axis where heads is False) and the logit u: None, "full" ([E, H]; [E] without a head axis),
     "shared" ([E] for H heads), "zeros" or "masked" (MASK on a seeded third of the entries, never on a row's first); `kind` = how the
@@ -115,21 +116,6 @@ class Case:
         z = logits_z(self.row, self.col, self.s_dst.to(dtype), self.s_src.to(dtype), None if self.u is None else self.u.to(dtype))
         return edge_softmax_ref(self.row, self.shape[0], torch.nn.functional.leaky_relu(z, self.slope))
 
-    def price(self, out, *grads, what=None):
-        """out and the gradients (ds_dst, ds_src, dv[, du]) of one run against the ground truth -> the report."""
-        assert out.shape == self.G.shape and len(grads) == len(self.leaves), self.name
-        for g, t in zip(grads, self.leaves):
-            assert g.shape == t.shape, (self.name, g.shape, t.shape)
-        rep, _ = parity.check_autograd(out.reshape(-1), list(grads), self.ref, self.leaves, self.G.reshape(-1), self.names,
-                                       what or self.name)
-        return _report(what or self.name, rep)
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place -> (out, ds_dst, ds_src, dv[, du])."""
-        leaves = [t.float().requires_grad_(True) for t in self.leaves]
-        out = self.ref(*leaves)
-        return (out.detach().reshape(self.G.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
-
     def check_masked(self, du):
         if self.masked is not None:
             assert float(du.detach().cpu()[self.masked].abs().max()) == 0.0, f"{self.name}: du at a masked entry is an exact zero"
@@ -160,12 +146,11 @@ class BipartiteGAT(torch.nn.Module):
         return torch.nn.functional.elu(self.attend(s_dst, s_src, h_src))
 
 
-class ModuleCase:
+class ModuleCase(ModuleCaseBase):
     """BipartiteGAT on the rectangular pattern: out and the gradients of its sum with respect to x_src, x_dst, W and a, against the same
     module with the ground truth as `attend`, in fp64."""
-    op = "module"
     F_IN, H, F = 24, 4, 8
-    NAMES = ("W", "a")
+    INPUTS, NAMES, GRADS = ("x_src", "x_dst"), ("W", "a"), ("dx_src", "dx_dst", "dW", "da")
 
     def __init__(self, name, row, col, shape, seed, kind="indices", csr=None):
         self.name, self.row, self.col, self.shape, self.kind, self.csr, self.seed = name, row, col, shape, kind, csr, seed
@@ -185,20 +170,6 @@ class ModuleCase:
 
     def ref_attend(self, s_dst, s_src, v):
         return additive_attention_ref(self.row, self.col, self.shape[0], s_dst, s_src, v, self.slope)
-
-    def ref(self, x_src, x_dst, *weights):
-        """The module with the ground truth as `attend`, its parameters replaced by `weights` (in their dtype)."""
-        return torch.func.functional_call(self.module(self.ref_attend), dict(zip(self.NAMES, weights)), (x_src, x_dst)).reshape(-1)
-
-    def price(self, out, dx_src, dx_dst, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx_src, dx_dst] + list(dweights), self.ref,
-                                       [self.x_src, self.x_dst] + self.weights, self.G, ["dx_src", "dx_dst", "dW", "da"], self.name)
-        return _report(self.name, rep)
-
-    def rehearse(self):
-        leaves = [t.float().requires_grad_(True) for t in [self.x_src, self.x_dst] + self.weights]
-        out = self.ref(*leaves)
-        return self.price(out.detach(), *torch.autograd.grad(out, leaves, self.G.float()))
 
 
 class LevelCase:
@@ -304,16 +275,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

@@ -13,14 +13,14 @@ import torch
 
 import dot_attention_bias_case as biased
 import dot_attention_case as base
-import parity
-from dot_attention_case import LANE_SHAPES, _report  # noqa: F401
-from edge_softmax_case import _coo
+from dot_attention_case import LANE_SHAPES  # noqa: F401
+from pattern_case import ForwardCase, seeded
+from pattern_graphs import _coo
 
 WIDE_SHAPE = (8, 64)      # 128 chunks of 4 per row: two chunks per lane, which no entry of LANE_SHAPES has; a shape of the measurements
 
 
-class Bf16Case:
+class Bf16Case(ForwardCase):
     """`inner` (a Case or a BiasCase) with k16, v16 [n_cols, (H,) F] bfloat16 in the place of its k and v; bias: inner's, or None."""
     op = "dot_attention_bf16"
 
@@ -36,6 +36,11 @@ class Bf16Case:
             assert changed >= 0.9, f"{name}: only {changed:.2f} of the entries change when rounded to bfloat16"
         self._refs = None
 
+    @property
+    def G(self):
+        """What the result is shaped like: the wrapped case's G, which has q's shape."""
+        return self.inner.G
+
     def widened(self, dtype=torch.float64):
         """k16 and v16 as `dtype`: exact."""
         return self.k16.to(dtype), self.v16.to(dtype)
@@ -49,24 +54,6 @@ class Bf16Case:
         else:
             out = biased.biased_ref(self.row, self.col, self.shape[0], q, k, v, self.scale, self.bias.to(dtype))
         return out.reshape(self.q.shape)
-
-    def refs(self):
-        """(the fp64 ground truth, its fp32 run), computed once."""
-        if self._refs is None:
-            self._refs = (self.ref(torch.float64), self.ref(torch.float32))
-        return self._refs
-
-    def price(self, out, what=None):
-        assert out.shape == self.q.shape and out.dtype == torch.float32, (self.name, out.shape, out.dtype)
-        y64, y32 = self.refs()
-        return _report(what or self.name, {"out": parity.close_fwd(out, y64, f"{what or self.name} out", y32)})
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place."""
-        return self.refs()[1]
-
-    def rehearse(self):
-        return self.price(self.stand_in())
 
 
 def _build_cases():
@@ -99,16 +86,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

@@ -10,9 +10,10 @@ on the CPU with the fp32 ground-truth run standing in for the device, tests/test
 import torch
 
 import dot_attention_case as base
-import parity
-from dot_attention_case import LANE_SHAPES, _report, edge_dot_ref
-from edge_softmax_case import _coo, edge_softmax_ref
+from dot_attention_case import LANE_SHAPES, edge_dot_ref
+from edge_softmax_case import edge_softmax_ref
+from pattern_case import OpCase, seeded
+from pattern_graphs import _coo
 from spmm_case import f32, normal, spmm_ref
 
 MASK = float(torch.tensor(-9e15).float())      # the reference's own "no edge here" as fp32 holds it: finite, exp(MASK - m) an exact zero
@@ -33,7 +34,7 @@ def first_of_row(row):
     return first[row] == torch.arange(E)
 
 
-class BiasCase:
+class BiasCase(OpCase):
     """`inner` (a dot_attention_case.Case: entries, q, k, v, G, scale, kind) with `bias` [E, H] | [E]; masked: bool [E], the entries
     whose bias is MASK in every head, or None."""
     op = "dot_attention_bias"
@@ -45,6 +46,12 @@ class BiasCase:
         assert bias.shape in ((self.row.numel(), self.H), (self.row.numel(),)) and (self.q.dim() == 3 or bias.dim() == 1)
         assert torch.equal(f32(bias), bias)
 
+    names = ["dq", "dk", "dv", "db"]
+
+    @property
+    def leaves(self):
+        return [self.q, self.k, self.v, self.bias]
+
     def ref(self, q, k, v, b):
         return biased_ref(self.row, self.col, self.shape[0], q, k, v, self.scale, b).reshape(-1)
 
@@ -54,20 +61,6 @@ class BiasCase:
         b = self.bias.to(dtype)
         s = s + (b[:, None] if b.dim() < s.dim() else b)
         return edge_softmax_ref(self.row, self.shape[0], s)
-
-    def price(self, out, dq, dk, dv, db, what=None):
-        """out and the four gradients of one run against the ground truth -> the report."""
-        assert out.shape == self.q.shape and dq.shape == self.q.shape and dk.shape == self.k.shape and dv.shape == self.v.shape, self.name
-        assert db.shape == self.bias.shape, (self.name, db.shape)
-        rep, _ = parity.check_autograd(out.reshape(-1), [dq, dk, dv, db], self.ref, [self.q, self.k, self.v, self.bias],
-                                       self.G.reshape(-1), ["dq", "dk", "dv", "db"], what or self.name)
-        return _report(what or self.name, rep)
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place -> (out, dq, dk, dv, db)."""
-        leaves = [t.float().requires_grad_(True) for t in (self.q, self.k, self.v, self.bias)]
-        out = self.ref(*leaves)
-        return (out.detach().reshape(self.q.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
 
     def db_row_sums(self, db):
         """The sums of db over the entries of every row, [n_rows, H] in fp64 on the host (0 in exact arithmetic: the coefficients of
@@ -90,7 +83,7 @@ class BiasModuleCase(base.ModuleCase):
     seeded: out and the gradients reaching x, the three weights and the embedding table, against the same module with the ground
     truth as `attend`, in fp64."""
     op = "module_bias"
-    NAMES = base.ModuleCase.NAMES + ("emb.weight",)
+    NAMES, GRADS = base.ModuleCase.NAMES + ("emb.weight",), base.ModuleCase.GRADS + ("dEmb",)
 
     def __init__(self, name, row, col, N, seed, kind="graph", csr=None):
         self.types = torch.randint(0, N_TYPES, (row.numel(),), generator=torch.Generator().manual_seed(seed + 7))
@@ -114,11 +107,6 @@ class BiasModuleCase(base.ModuleCase):
 
     def ref_attend(self, q, k, v, b):
         return biased_ref(self.row, self.col, self.shape[0], q, k, v, self.scale, b)
-
-    def price(self, out, dx, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx] + list(dweights), self.ref, [self.x] + self.weights, self.G,
-                                       ["dx", "dWq", "dWk", "dWv", "dEmb"], self.name)
-        return _report(self.name, rep)
 
 
 def _bias(E, H, seed, std=1.0, shared=False):
@@ -201,16 +189,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

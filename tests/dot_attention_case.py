@@ -10,13 +10,12 @@ import math
 
 import torch
 
-import parity
 from bf16_table_case import hub_graph as lonely_hub_graph
-from edge_softmax_case import _coo, edge_softmax_ref
+from edge_softmax_case import edge_softmax_ref
 from long_row_cases import nine_hubs, three_chunk_hub
+from pattern_case import ModuleCase as ModuleCaseBase, OpCase, seeded
+from pattern_graphs import _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo
 from spmm_case import f32, normal, spmm_ref
-from test_gpu_attention import _asym_graph, _hub_graph
-from test_gpu_spmm import _rect_coo, _repeat_coo
 
 # (H, F) of the lane-shape cases: chunks of 4 floats per row -> the lane layout (csrc/k19_dot_attention.hip)
 LANE_SHAPES = ((1, 4), (1, 8), (3, 8), (8, 16), (6, 16), (4, 64), (16, 16), (3, 64), (12, 64), (4, 256), (64, 16), (1, 256))
@@ -31,12 +30,7 @@ def edge_dot_ref(row, col, q, k, scale):
     return (q[row] * k[col]).sum(-1) * scale
 
 
-def _report(what, rep):
-    print(what, {k: f"{e:.2e}" for k, e in rep.items()})
-    return rep
-
-
-class Case:
+class Case(OpCase):
     """One seeded dot_attention case: the entries (row, col) of a `shape` pattern, q [n_rows, H, F], k, v [n_cols, H, F], G like q
     (without the head axis where heads is False); `kind` = how the device's pattern is built ("indices": EdgePattern.from_indices,
     entries as given; "graph": CSRGraph.edge_pattern() of the CSR the entries came from).  scale: None = the op's default
@@ -55,6 +49,12 @@ class Case:
         self.fed_scale = 3.0 / math.sqrt(F) if scale == "sharp" else scale      # what the op is given (None: its default)
         self.scale = 1.0 / math.sqrt(F) if self.fed_scale is None else float(self.fed_scale)
 
+    names = ["dq", "dk", "dv"]
+
+    @property
+    def leaves(self):
+        return [self.q, self.k, self.v]
+
     def ref(self, q, k, v):
         return dot_attention_ref(self.row, self.col, self.shape[0], q, k, v, self.scale).reshape(-1)
 
@@ -63,20 +63,7 @@ class Case:
 
     def price(self, out, dq, dk, dv, what=None):
         """out and the three gradients of one run against the ground truth -> (report, out in fp64 shaped like q)."""
-        assert out.shape == self.q.shape and dq.shape == self.q.shape and dk.shape == self.k.shape and dv.shape == self.v.shape, self.name
-        rep, (y64, _) = parity.check_autograd(out.reshape(-1), [dq, dk, dv], self.ref, [self.q, self.k, self.v], self.G.reshape(-1),
-                                              ["dq", "dk", "dv"], what or self.name)
-        return _report(what or self.name, rep), y64.reshape(self.q.shape)
-
-    def stand_in(self, fn=None):
-        """The fp32 ground-truth run (or fn, the composition from parts) in the device's place."""
-        leaves = [t.float().requires_grad_(True) for t in (self.q, self.k, self.v)]
-        out = (fn or self.ref)(*leaves)
-        grads = torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
-        return (out.detach().reshape(self.q.shape),) + grads
-
-    def rehearse(self):
-        return self.price(*self.stand_in())
+        return self.price_y64(out, dq, dk, dv, what=what)
 
 
 class ComposedCase(Case):
@@ -91,7 +78,7 @@ class ComposedCase(Case):
         return self.price(*self.stand_in(self.composed_ref), what=self.name + " from parts")
 
 
-class DotCase:
+class DotCase(OpCase):
     """One seeded edge_dot case: u [E, H] | [E] against (q[row] * k[col]).sum(-1) * scale, loss <u, G>."""
     op = "edge_dot"
 
@@ -103,18 +90,14 @@ class DotCase:
         self.G = f32(normal((row.numel(), H) if heads else (row.numel(),), seed + 2))
         self.scale = self.fed_scale = float(scale)
 
+    names = ["dq", "dk"]
+
+    @property
+    def leaves(self):
+        return [self.q, self.k]
+
     def ref(self, q, k):
         return edge_dot_ref(self.row, self.col, q, k, self.scale).reshape(-1)
-
-    def price(self, u, dq, dk):
-        assert u.shape == self.G.shape and dq.shape == self.q.shape and dk.shape == self.k.shape, self.name
-        rep, _ = parity.check_autograd(u.reshape(-1), [dq, dk], self.ref, [self.q, self.k], self.G.reshape(-1), ["dq", "dk"], self.name)
-        return _report(self.name, rep)
-
-    def rehearse(self):
-        leaves = [t.float().requires_grad_(True) for t in (self.q, self.k)]
-        u = self.ref(*leaves)
-        return self.price(u.detach().reshape(self.G.shape), *torch.autograd.grad(u, leaves, self.G.float().reshape(-1)))
 
 
 class AttentionModule(torch.nn.Module):
@@ -135,12 +118,11 @@ class AttentionModule(torch.nn.Module):
         return self.attend(q, k, v)
 
 
-class ModuleCase:
+class ModuleCase(ModuleCaseBase):
     """AttentionModule on the hub pattern: out and the gradients of its sum with respect to x and the three weights, against the same
     module with the ground truth as `attend`, in fp64."""
-    op = "module"
     F_IN, H, F = 48, 4, 16
-    NAMES = ("query.weight", "key.weight", "value.weight")
+    INPUTS, NAMES, GRADS = ("x",), ("query.weight", "key.weight", "value.weight"), ("dx", "dWq", "dWk", "dWv")
 
     def __init__(self, name, row, col, N, seed, kind="graph", csr=None):
         self.name, self.row, self.col, self.shape, self.kind, self.csr, self.seed = name, row, col, (N, N), kind, csr, seed
@@ -156,20 +138,6 @@ class ModuleCase:
 
     def ref_attend(self, q, k, v):
         return dot_attention_ref(self.row, self.col, self.shape[0], q, k, v, self.scale)
-
-    def ref(self, x, *weights):
-        """The module with the ground truth as `attend`, its parameters replaced by `weights` (in their dtype)."""
-        return torch.func.functional_call(self.module(self.ref_attend), dict(zip(self.NAMES, weights)), (x,)).reshape(-1)
-
-    def price(self, out, dx, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx] + list(dweights), self.ref, [self.x] + self.weights, self.G,
-                                       ["dx", "dWq", "dWk", "dWv"], self.name)
-        return _report(self.name, rep)
-
-    def rehearse(self):
-        leaves = [t.float().requires_grad_(True) for t in [self.x] + self.weights]
-        out = self.ref(*leaves)
-        return self.price(out.detach(), *torch.autograd.grad(out, leaves, self.G.float()))
 
 
 def _build_cases():
@@ -221,16 +189,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

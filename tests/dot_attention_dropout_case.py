@@ -16,10 +16,11 @@ import torch
 
 import dot_attention_bias_case as biased
 import dot_attention_case as base
-import parity
 import philox_ref
-from dot_attention_case import LANE_SHAPES, _report, edge_dot_ref
-from edge_softmax_case import _coo, edge_softmax_ref
+from dot_attention_case import LANE_SHAPES, edge_dot_ref
+from edge_softmax_case import edge_softmax_ref
+from pattern_case import DropoutChecks, OpCase, seeded
+from pattern_graphs import _coo
 from spmm_case import f32, normal, spmm_ref
 
 STREAM_ATT = 3                      # pygat_amd.dropout.STREAM_ATT (asserted by the CPU tests): the stream of the attention mask
@@ -42,7 +43,7 @@ def dropout_ref(row, col, n_rows, q, k, v, scale, bias, mask):
     return spmm_ref(row, col, n_rows, edge_softmax_ref(row, n_rows, s) * mask.to(s.dtype).reshape(s.shape), v)
 
 
-class DropCase:
+class DropCase(DropoutChecks, OpCase):
     """`inner` (a dot_attention_case.Case: entries, q, k, v, G, scale, kind) under dropout p with the mask of `seed`; bias: None,
     [E, H] or [E]; masked: bool [E], the entries whose bias is MASK, or None."""
     op = "dot_attention_dropout"
@@ -74,36 +75,9 @@ class DropCase:
             s = s + self.bias.to(dtype).reshape(self.row.numel(), -1)
         return s
 
-    def price(self, out, *grads, what=None):
-        """out and the gradients of one run (dq, dk, dv and, with a bias, db) against the ground truth -> the report."""
-        assert len(grads) == len(self.leaves), (self.name, len(grads))
-        for g, t in zip((out,) + grads, [self.q] + self.leaves):
-            assert g.shape == t.shape, (self.name, g.shape, t.shape)
-        rep, _ = parity.check_autograd(out.reshape(-1), list(grads), self.ref, self.leaves, self.G.reshape(-1), self.names,
-                                       what or self.name)
-        return _report(what or self.name, rep)
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place -> (out, dq, dk, dv[, db])."""
-        leaves = [t.float().requires_grad_(True) for t in self.leaves]
-        out = self.ref(*leaves)
-        return (out.detach().reshape(self.q.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
-
-    def all_dropped(self, min_entries=2):
-        """bool [n_rows, H]: the row has at least min_entries entries and every one of them is dropped in that head."""
-        kept = torch.zeros(self.shape[0], self.H).index_add(0, self.row, (self.mask != 0).float())
-        deg = torch.bincount(self.row, minlength=self.shape[0])
-        return (kept == 0) & (deg >= min_entries)[:, None]
-
     def check_masked(self, db):
         if self.masked is not None:
             assert float(db.detach().cpu()[self.masked].abs().max()) == 0.0, f"{self.name}: db at a masked entry is an exact zero"
-
-    def check_all_dropped(self, out):
-        gone = self.all_dropped()
-        if bool(gone.any()):
-            o = out.detach().cpu().reshape(self.shape[0], self.H, self.F)
-            assert float(o[gone].abs().max()) == 0.0, f"{self.name}: a row whose entries are all dropped is an exact zero"
 
     def rehearse(self):
         res = self.stand_in()
@@ -212,16 +186,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

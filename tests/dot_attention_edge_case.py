@@ -12,10 +12,11 @@ import torch
 
 import dot_attention_bias_case as biased
 import dot_attention_case as base
-import parity
 from dot_attention_bias_case import MASK, _masked, first_of_row  # noqa: F401
-from dot_attention_case import LANE_SHAPES, _report
-from edge_softmax_case import _coo, edge_softmax_ref
+from dot_attention_case import LANE_SHAPES
+from edge_softmax_case import edge_softmax_ref
+from pattern_case import OpCase, seeded
+from pattern_graphs import _coo
 from spmm_case import f32, normal, spmm_ref
 
 EDGE_DIM = 6           # columns of the module case's edge_attr
@@ -44,7 +45,7 @@ def composed_ref(row, col, n_rows, q, k, v, e, scale, bias=None):
     return spmm_ref(row, col, n_rows, alpha, v) + torch.zeros_like(q).index_add(0, row, alpha[..., None] * e)
 
 
-class EdgeCase:
+class EdgeCase(OpCase):
     """`inner` (a dot_attention_case.Case: entries, q, k, v, G, scale, kind) with `e` [E, H, F] | [E, F] and, optionally, `bias`
     [E, H] | [E]; masked: bool [E], the entries whose bias is MASK in every head, or None.  `e` is given as a function that makes
     it: it is drawn again from its seed wherever it is asked for, so the cases together do not hold every e at once."""
@@ -84,21 +85,6 @@ class EdgeCase:
         s = edge_scores(self.row, self.col, self.q.to(dtype), self.k.to(dtype), self.e.to(dtype), self.scale, b)
         return edge_softmax_ref(self.row, self.shape[0], s)
 
-    def price(self, out, *grads, what=None):
-        """out and the gradients (dq, dk, dv, de[, db]) of one run against the ground truth -> the report."""
-        leaves = self.leaves
-        assert len(grads) == len(leaves), (self.name, len(grads))
-        assert out.shape == self.q.shape and all(g.shape == t.shape for g, t in zip(grads, leaves)), self.name
-        rep, _ = parity.check_autograd(out.reshape(-1), list(grads), self.ref, leaves, self.G.reshape(-1), self.names,
-                                       what or self.name)
-        return _report(what or self.name, rep)
-
-    def stand_in(self, fn=None):
-        """The fp32 ground-truth run (or fn, the composition from parts) in the device's place -> (out, dq, dk, dv, de[, db])."""
-        leaves = [t.float().requires_grad_(True) for t in self.leaves]
-        out = (fn or self.ref)(*leaves)
-        return (out.detach().reshape(self.q.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
-
     def check_masked(self, res):
         """de (every element) and db at a masked entry are exact zeros: both p and ds are 0 there."""
         if self.masked is not None:
@@ -125,7 +111,7 @@ class EdgeModuleCase(base.ModuleCase):
     """The AttentionModule of dot_attention_case with e = lin_edge(edge_attr).view(E, H, F), edge_attr [E, EDGE_DIM] seeded: out and
     the gradients reaching x, the three weights and lin_edge.weight, against the same module with the ground truth as `attend`."""
     op = "module_edge"
-    NAMES = base.ModuleCase.NAMES + ("lin_edge.weight",)
+    NAMES, GRADS = base.ModuleCase.NAMES + ("lin_edge.weight",), base.ModuleCase.GRADS + ("dWe",)
 
     def __init__(self, name, row, col, N, seed, kind="graph", csr=None):
         self.edge_attr = f32(normal((row.numel(), EDGE_DIM), seed + 7))
@@ -151,11 +137,6 @@ class EdgeModuleCase(base.ModuleCase):
 
     def ref_attend(self, q, k, v, e):
         return edge_ref(self.row, self.col, self.shape[0], q, k, v, e, self.scale)
-
-    def price(self, out, dx, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx] + list(dweights), self.ref, [self.x] + self.weights, self.G,
-                                       ["dx", "dWq", "dWk", "dWv", "dWe"], self.name)
-        return _report(self.name, rep)
 
 
 def _e(inner, seed, std=1.0):
@@ -230,16 +211,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

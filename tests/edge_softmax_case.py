@@ -12,9 +12,9 @@ import torch
 import parity
 from bf16_table_case import hub_graph as lonely_hub_graph
 from long_row_cases import nine_hubs, three_chunk_hub
+from pattern_case import seeded
+from pattern_graphs import COMPOSE_SEED, SLOPE, _asym_graph, _coo, _hub_graph, _params, _rect_coo, _repeat_coo
 from spmm_case import coo_of, f32, normal, spmm_ref
-from test_gpu_attention import SLOPE, _asym_graph, _hub_graph, _params
-from test_gpu_spmm import COMPOSE_SEED, _rect_coo, _repeat_coo
 
 HEADS = (1, 2, 3, 6, 8, 64)
 
@@ -55,11 +55,6 @@ def price(what, group, n_groups, l, G, alpha, dl):
                                           G.reshape(-1), ["dlogits"], what)
     print(what, {k: f"{e:.2e}" for k, e in rep.items()})
     return rep, y64.reshape(l.shape)
-
-
-def _coo(csr):
-    """(rowptr, col) -> (row, col, N), the entries in CSR order."""
-    return coo_of(*csr) + (len(csr[0]) - 1,)
 
 
 class Case:
@@ -190,16 +185,4 @@ def price_composition(y, grads, rowptr, col, logits, Wh, G):
     return rep
 
 
-_CASES = None
-
-
-def cases():
-    """{name: Case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names():
-    return list(cases())
+cases, case_names = seeded(_build_cases)

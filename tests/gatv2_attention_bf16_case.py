@@ -19,14 +19,15 @@ import torch
 
 import gatv2_attention_case as plain
 import gatv2_attention_edge_case as edge
-import parity
 from additive_attention_bf16_case import WIDE_SHAPE, changed
-from dot_attention_case import LANE_SHAPES, _coo, _hub_graph, _report  # noqa: F401
+from dot_attention_case import LANE_SHAPES  # noqa: F401
+from pattern_case import ForwardCase, seeded
+from pattern_graphs import _coo, _hub_graph  # noqa: F401
 
 CHANGED, CHANGED_ON_GRID = 0.9, 0.5
 
 
-class Bf16Case:
+class Bf16Case(ForwardCase):
     """`inner` (a Case of gatv2_attention_case, or an EdgeCase of gatv2_attention_edge_case) with x_src16, v16 (None where v is x_src)
     and e16 (None without edge features) bfloat16 in the place of its x_src, v and e."""
 
@@ -70,24 +71,6 @@ class Bf16Case:
             out = plain.gatv2_attention_ref(self.row, self.col, self.shape[0], x_dst, x_src, a, v, self.slope)
         return out.reshape(self.G.shape)
 
-    def refs(self):
-        """(the fp64 ground truth, its fp32 run), computed once."""
-        if self._refs is None:
-            self._refs = (self.ref(torch.float64), self.ref(torch.float32))
-        return self._refs
-
-    def price(self, out, what=None):
-        assert out.shape == self.G.shape and out.dtype == torch.float32, (self.name, out.shape, out.dtype)
-        y64, y32 = self.refs()
-        return _report(what or self.name, {"out": parity.close_fwd(out, y64, f"{what or self.name} out", y32)})
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place."""
-        return self.refs()[1]
-
-    def rehearse(self):
-        return self.price(self.stand_in())
-
 
 def _build_cases():
     out = []
@@ -128,16 +111,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

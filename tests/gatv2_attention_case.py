@@ -27,8 +27,9 @@ import numpy as np
 import torch
 
 import parity
-from dot_attention_case import (LANE_SHAPES, _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo, _report, edge_softmax_ref, f32,
-                                lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub)
+from dot_attention_case import LANE_SHAPES, edge_softmax_ref, f32, lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub
+from pattern_case import ModuleCase as ModuleCaseBase, OpCase, seeded
+from pattern_graphs import _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo
 
 SLOPE = 0.2
 MODULE_BAND = 2.0 ** -16
@@ -73,7 +74,7 @@ def score_unit(slope):
     return math.sqrt(1.0 + slope * slope - (1.0 - slope) ** 2 / math.pi)
 
 
-class Case:
+class Case(OpCase):
     """One seeded case: the entries (row, col) of a `shape` pattern, x_dst [n_rows, H, F], x_src [n_cols, H, F] ~ N(0, 1), a [H, F] of
     norm std / score_unit per head, G like x_dst (without the head axis where heads is False) and v: None (shared: v is x_src, the
     op's v=None) or a table of its own; `kind` = how the device's pattern is built ("indices": EdgePattern.from_indices, entries as
@@ -113,27 +114,12 @@ class Case:
     def coefficients(self, dtype=torch.float64):
         return edge_softmax_ref(self.row, self.shape[0], self.scores(dtype))
 
-    def price(self, out, *grads, what=None, ref=None):
-        """out and the gradients (dx_dst, dx_src, da[, dv]) of one run against the ground truth -> the report."""
-        assert out.shape == self.G.shape and len(grads) == len(self.leaves), self.name
-        for g, t in zip(grads, self.leaves):
-            assert g.shape == t.shape, (self.name, g.shape, t.shape)
-        rep, _ = parity.check_autograd(out.reshape(-1), list(grads), ref or self.ref, self.leaves, self.G.reshape(-1), self.names,
-                                       what or self.name)
-        return _report(what or self.name, rep)
-
     def price_all(self, out, *grads, what=None):
         """... and, at slope 1, against the linear ground truth too."""
         rep = self.price(out, *grads, what=what)
         if self.slope == 1.0:
             self.price(out, *grads, what=(what or self.name) + " (linear)", ref=self.linear_ref)
         return rep
-
-    def stand_in(self, fn=None):
-        """The fp32 ground-truth run in the device's place -> (out, dx_dst, dx_src, da[, dv])."""
-        leaves = [t.float().requires_grad_(True) for t in self.leaves]
-        out = (fn or self.ref)(*leaves)
-        return (out.detach().reshape(self.G.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
 
     def rehearse(self):
         assert t_signs_agree(self.row, self.col, self.x_dst, self.x_src), self.name
@@ -158,12 +144,11 @@ class BipartiteGATv2(torch.nn.Module):
         return torch.nn.functional.elu(self.attend(h_dst, h_src, self.a))
 
 
-class ModuleCase:
+class ModuleCase(ModuleCaseBase):
     """BipartiteGATv2 on the rectangular pattern: out and the gradients of its sum with respect to x_src, x_dst, W_l, W_r and a,
     against the same module with the ground truth as `attend`, in fp64."""
-    op = "module"
     F_IN, H, F = 24, 2, 8
-    NAMES = ("W_l", "W_r", "a")
+    INPUTS, NAMES, GRADS = ("x_src", "x_dst"), ("W_l", "W_r", "a"), ("dx_src", "dx_dst", "dW_l", "dW_r", "da")
 
     def __init__(self, name, row, col, shape, seed, kind="indices", csr=None):
         self.name, self.row, self.col, self.shape, self.kind, self.csr, self.seed = name, row, col, shape, kind, csr, seed
@@ -182,21 +167,6 @@ class ModuleCase:
 
     def ref_attend(self, h_dst, h_src, a):
         return gatv2_attention_ref(self.row, self.col, self.shape[0], h_dst, h_src, a, h_src, self.slope)
-
-    def ref(self, x_src, x_dst, *weights):
-        """The module with the ground truth as `attend`, its parameters replaced by `weights` (in their dtype)."""
-        return torch.func.functional_call(self.module(self.ref_attend), dict(zip(self.NAMES, weights)), (x_src, x_dst)).reshape(-1)
-
-    def price(self, out, dx_src, dx_dst, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx_src, dx_dst] + list(dweights), self.ref,
-                                       [self.x_src, self.x_dst] + self.weights, self.G, ["dx_src", "dx_dst", "dW_l", "dW_r", "da"],
-                                       self.name)
-        return _report(self.name, rep)
-
-    def rehearse(self):
-        leaves = [t.float().requires_grad_(True) for t in [self.x_src, self.x_dst] + self.weights]
-        out = self.ref(*leaves)
-        return self.price(out.detach(), *torch.autograd.grad(out, leaves, self.G.float()))
 
 
 class LevelCase:
@@ -298,16 +268,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

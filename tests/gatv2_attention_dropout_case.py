@@ -17,10 +17,11 @@ in for the device, tests/test_gpu_gatv2_attention_dropout.py runs them on the de
 import torch
 
 import gatv2_attention_case as base
-import parity
 import philox_ref
 from additive_attention_dropout_case import _wrapped
-from dot_attention_case import LANE_SHAPES, _coo, _rect_coo, _report, edge_softmax_ref, nine_hubs, spmm_ref, three_chunk_hub
+from dot_attention_case import LANE_SHAPES, edge_softmax_ref, nine_hubs, spmm_ref, three_chunk_hub
+from pattern_case import DropoutChecks, OpCase, seeded
+from pattern_graphs import _coo, _rect_coo
 from dot_attention_dropout_case import P_NEAR_0, one_entry_rows
 from gatv2_attention_case import scores, t_signs_agree
 
@@ -33,7 +34,7 @@ def dropout_ref(row, col, n_rows, x_dst, x_src, a, v, slope, mask):
     return spmm_ref(row, col, n_rows, edge_softmax_ref(row, n_rows, s) * mask.to(s.dtype).reshape(s.shape), v)
 
 
-class DropCase:
+class DropCase(DropoutChecks, OpCase):
     """`inner` (a gatv2_attention_case.Case: entries, x_dst, x_src, a, v | shared, G, slope, kind) under dropout p with the mask of
     `seed`."""
     op = "gatv2_attention_dropout"
@@ -48,33 +49,6 @@ class DropCase:
     def ref(self, x_dst, x_src, a, v=None):
         return dropout_ref(self.row, self.col, self.shape[0], x_dst, x_src, a, x_src if v is None else v, self.slope,
                            self.mask).reshape(-1)
-
-    def price(self, out, *grads, what=None):
-        """out and the gradients (dx_dst, dx_src, da[, dv]) of one run against the ground truth -> the report."""
-        assert out.shape == self.G.shape and len(grads) == len(self.leaves), self.name
-        for g, t in zip(grads, self.leaves):
-            assert g.shape == t.shape, (self.name, g.shape, t.shape)
-        rep, _ = parity.check_autograd(out.reshape(-1), list(grads), self.ref, self.leaves, self.G.reshape(-1), self.names,
-                                       what or self.name)
-        return _report(what or self.name, rep)
-
-    def stand_in(self):
-        """The fp32 ground-truth run in the device's place -> (out, dx_dst, dx_src, da[, dv])."""
-        leaves = [t.float().requires_grad_(True) for t in self.leaves]
-        out = self.ref(*leaves)
-        return (out.detach().reshape(self.G.shape),) + torch.autograd.grad(out, leaves, self.G.float().reshape(-1))
-
-    def all_dropped(self, min_entries=2):
-        """bool [n_rows, H]: the row has at least min_entries entries and every one of them is dropped in that head."""
-        kept = torch.zeros(self.shape[0], self.H).index_add(0, self.row, (self.mask != 0).float())
-        deg = torch.bincount(self.row, minlength=self.shape[0])
-        return (kept == 0) & (deg >= min_entries)[:, None]
-
-    def check_all_dropped(self, out):
-        gone = self.all_dropped()
-        if bool(gone.any()):
-            o = out.detach().cpu().reshape(self.shape[0], self.H, self.F)
-            assert float(o[gone].abs().max()) == 0.0, f"{self.name}: a row whose entries are all dropped is an exact zero"
 
     def rehearse(self):
         assert t_signs_agree(self.row, self.col, self.x_dst, self.x_src), self.name
@@ -163,16 +137,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

@@ -27,9 +27,9 @@ import math
 import torch
 
 import gatv2_attention_case as plain
-import parity
-from dot_attention_case import (LANE_SHAPES, _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo, _report, edge_softmax_ref, f32,
-                                lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub)
+from dot_attention_case import LANE_SHAPES, edge_softmax_ref, f32, lonely_hub_graph, nine_hubs, normal, spmm_ref, three_chunk_hub
+from pattern_case import ModuleCase, seeded
+from pattern_graphs import _asym_graph, _coo, _hub_graph, _rect_coo, _repeat_coo
 
 SLOPE = plain.SLOPE
 MODULE_BAND = plain.MODULE_BAND
@@ -147,12 +147,12 @@ class BipartiteGATv2Edge(plain.BipartiteGATv2):
         return torch.nn.functional.elu(self.attend(h_dst, h_src, self.a, e))
 
 
-class EdgeModuleCase:
+class EdgeModuleCase(ModuleCase):
     """BipartiteGATv2Edge on the rectangular pattern: out and the gradients of its sum with respect to x_src, x_dst, edge_attr, W_l,
     W_r, a and the edge projection's weight, against the same module with the ground truth as `attend`, in fp64."""
-    op = "module"
     F_IN, H, F = 24, 2, 8
-    NAMES = ("W_l", "W_r", "a", "lin_edge.weight")
+    INPUTS, NAMES = ("x_src", "x_dst", "edge_attr"), ("W_l", "W_r", "a", "lin_edge.weight")
+    GRADS = ("dx_src", "dx_dst", "dedge_attr", "dW_l", "dW_r", "da", "dW_edge")
 
     def __init__(self, name, row, col, shape, seed, kind="indices", csr=None):
         self.name, self.row, self.col, self.shape, self.kind, self.csr, self.seed = name, row, col, shape, kind, csr, seed
@@ -175,22 +175,6 @@ class EdgeModuleCase:
 
     def ref_attend(self, h_dst, h_src, a, e):
         return gatv2_attention_edge_ref(self.row, self.col, self.shape[0], h_dst, h_src, a, h_src, e, self.slope)
-
-    def ref(self, x_src, x_dst, edge_attr, *weights):
-        """The module with the ground truth as `attend`, its parameters replaced by `weights` (in their dtype)."""
-        return torch.func.functional_call(self.module(self.ref_attend), dict(zip(self.NAMES, weights)),
-                                          (x_src, x_dst, edge_attr)).reshape(-1)
-
-    def price(self, out, dx_src, dx_dst, dedge, *dweights):
-        rep, _ = parity.check_autograd(out.reshape(-1), [dx_src, dx_dst, dedge] + list(dweights), self.ref,
-                                       [self.x_src, self.x_dst, self.edge_attr] + self.weights, self.G,
-                                       ["dx_src", "dx_dst", "dedge_attr", "dW_l", "dW_r", "da", "dW_edge"], self.name)
-        return _report(self.name, rep)
-
-    def rehearse(self):
-        leaves = [t.float().requires_grad_(True) for t in [self.x_src, self.x_dst, self.edge_attr] + self.weights]
-        out = self.ref(*leaves)
-        return self.price(out.detach(), *torch.autograd.grad(out, leaves, self.G.float()))
 
 
 def _build_cases():
@@ -265,16 +249,4 @@ def _build_cases():
     return out
 
 
-_CASES = None
-
-
-def cases():
-    """{name: case}, built once and shared (inputs are never written to)."""
-    global _CASES
-    if _CASES is None:
-        _CASES = {c.name: c for c in _build_cases()}
-    return _CASES
-
-
-def case_names(prefix=""):
-    return [n for n in cases() if n.startswith(prefix)]
+cases, case_names = seeded(_build_cases)

@@ -11,41 +11,16 @@ import pytest
 import torch
 
 import additive_attention_case as case
+from abi_support import ADDITIVE, DOT, P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_add_attn_workspace_bytes", "pygat_add_attn_forward", "pygat_add_attn_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-def _forward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, s_dst=P + 4, s_src=P + 4, v=P, ldv=16,
-             edge_logit=P + 4, logit_head_stride=1, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_add_attn_forward(*a.values(), None)
-
-
-def _backward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, s_dst=P + 4, s_src=P + 4, v=P, ldv=16,
-             edge_logit=P + 4, logit_head_stride=1, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, ds_dst=P + 4, P=P, S=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_add_attn_backward_rows(*a.values(), None)
-
-
-LAUNCHERS = ((_forward, "add_attn_forward"), (_backward, "add_attn_backward_rows"))
+LAUNCHERS = ADDITIVE
+_forward, _backward = (fn for fn, _ in LAUNCHERS)
 TABLES = {"add_attn_forward": (("v", "ldv"), ("out", "ldo")), "add_attn_backward_rows": (("v", "ldv"), ("out", "ldo"), ("G", "ldg"))}
 SCALARS = {"add_attn_forward": ("rowptr", "col", "s_dst", "s_src", "m", "Z", "ws"),
            "add_attn_backward_rows": ("rowptr", "col", "s_dst", "s_src", "m", "Z", "ds_dst", "P", "S", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -147,8 +122,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 def test_the_same_wording_as_dot_attention(lib):
     """Whatever pygat_dot_attn_forward / _backward_rows refuse of the arguments both families have, these refuse in the same words
     after their own name."""
-    import test_dot_attention_abi as plain
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS, plain.LAUNCHERS):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS, DOT):
         for kw in (dict(H=65), dict(nnz=-1), dict(n_rows=0), dict(v=None), dict(v=P + 4), dict(ldv=12), dict(m=None), dict(ws=None),
                    dict(ws=P + 8), dict(col=None), dict(out=P + 8)):
             assert fn(lib, **kw) == -1

@@ -12,27 +12,15 @@ import pytest
 import torch
 
 import additive_attention_bf16_case as case
+from abi_support import ADDITIVE, P, call, lib, msg as _msg  # noqa: F401
 
 NAME = "add_attn_bf16_forward"
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, s_dst=P + 4, s_src=P + 4, v=P + 8, ldv=16,
              edge_logit=P + 4, logit_head_stride=1, out=P, ldo=16, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_add_attn_bf16_forward(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
+    return call(L, "pygat_add_attn_bf16_forward", a, **kw)
 
 
 def test_additive_under_abi_16(lib):
@@ -110,13 +98,12 @@ def test_neither_m_nor_z_is_asked_for(lib):
 def test_the_same_wording_as_the_float32_launcher(lib):
     """Whatever pygat_add_attn_forward refuses, this launcher refuses in the same words after its own name (v: the same but for the
     8 bytes of its alignment)."""
-    import test_additive_attention_abi as plain
     for kw in (dict(H=65), dict(F=12), dict(H=8, F=256), dict(nnz=-1), dict(nnz=1 << 31), dict(n_rows=0), dict(v=None), dict(ldv=12),
                dict(ldv=18), dict(out=P + 8), dict(ws=None), dict(ws=P + 8), dict(col=None), dict(rowptr=None), dict(s_dst=None),
                dict(s_src=None), dict(logit_head_stride=3), dict(negative_slope=float("nan"))):
         assert _forward(lib, **kw) == -1
         got = _msg(lib)
-        assert plain._forward(lib, **kw) == -1
+        assert ADDITIVE[0][0](lib, **kw) == -1
         assert got[len(NAME):] == _msg(lib)[len("add_attn_forward"):] and got.startswith(NAME), (kw, got, _msg(lib))
 
 

@@ -15,31 +15,21 @@ import torch
 import additive_attention_dropout_case as case
 import dot_attention_dropout_case as dot_case
 import philox_ref
+from abi_support import ADDITIVE, P, call, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_add_attn_dropout_forward", "pygat_add_attn_dropout_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, s_dst=P, s_src=P, v=P, ldv=16, edge_logit=P + 4,
              logit_head_stride=1, p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_add_attn_dropout_forward(*a.values(), None)
+    return call(L, "pygat_add_attn_dropout_forward", a, **kw)
 
 
 def _backward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, s_dst=P, s_src=P, v=P, ldv=16, edge_logit=P + 4,
              logit_head_stride=1, p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, ds_dst=P, P=P, S=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_add_attn_dropout_backward_rows(*a.values(), None)
+    return call(L, "pygat_add_attn_dropout_backward_rows", a, **kw)
 
 
 LAUNCHERS = ((_forward, "add_attn_dropout_forward"), (_backward, "add_attn_dropout_backward_rows"))
@@ -47,10 +37,6 @@ TABLES = {"add_attn_dropout_forward": (("v", "ldv"), ("out", "ldo")),
           "add_attn_dropout_backward_rows": (("v", "ldv"), ("out", "ldo"), ("G", "ldg"))}
 SCALARS = {"add_attn_dropout_forward": ("rowptr", "col", "s_dst", "s_src", "m", "Z", "ws"),
            "add_attn_dropout_backward_rows": ("rowptr", "col", "s_dst", "s_src", "m", "Z", "ds_dst", "P", "S", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -114,8 +100,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 
 def test_the_same_wording_as_the_parent_pair(lib):
     """Whatever pygat_add_attn_forward / _backward_rows refuse, the dropout launchers refuse in the same words after their own name."""
-    import test_additive_attention_abi as parent
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS, parent.LAUNCHERS):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS, ADDITIVE):
         for kw in (dict(H=65), dict(F=12), dict(nnz=-1), dict(n_rows=0), dict(s_dst=None), dict(v=P + 4), dict(ldv=12), dict(m=None),
                    dict(ws=None), dict(ws=P + 8), dict(col=None), dict(logit_head_stride=2), dict(out=None), dict(negative_slope=float("nan"))):
             assert fn(lib, **kw) == -1

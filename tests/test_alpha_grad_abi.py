@@ -4,14 +4,7 @@ import ctypes as C
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
+from abi_support import P, lib, msg as _msg  # noqa: F401
 
 
 def _rows(L, **kw):
@@ -25,10 +18,6 @@ def _cols(L, **kw):
     a = dict(n=8, nnz=20, rowptr=P, edge_rc=P, perm_t=P, to_internal=None, H=2, Fo=16, alpha=0.2, t=P, rec=P, A=P, dt2=P, part=P)
     a.update(kw)
     return L.lib.pygat_alpha_grad_cols(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

@@ -4,14 +4,7 @@ import ctypes as C
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
+from abi_support import P, lib, msg as _msg  # noqa: F401
 
 
 def _v1(L, **kw):
@@ -25,10 +18,6 @@ def _v2(L, **kw):
     a = dict(n=8, nnz=20, rowptr=P, edge_rc=P, to_internal=None, H=2, Fo=16, alpha=0.2, WW=P, a2=P, m=P, Z=P, att=P)
     a.update(kw)
     return L.lib.pygat_gatv2_attention(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_abi_version_is_16(lib):

@@ -6,14 +6,9 @@ import re
 
 import pytest
 
+from abi_support import P, lib, msg as _msg  # noqa: F401
+
 NEW = ("pygat_gat_bf16_workspace_bytes", "pygat_gat_pack_bf16", "pygat_gat_forward_bf16")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _graph(L, **kw):
@@ -34,10 +29,6 @@ def _fwd(L, g=None, **kw):
     a = dict(H=2, Fo=16, alpha=0.2, flags=1, Whq=P, s=P, a_pad=P, sk=None, out=P, hattn=None, head_group=0, part=P)
     a.update(kw)
     return L.lib.pygat_gat_forward_bf16(C.byref(g) if g != "null" else None, *a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

@@ -9,40 +9,16 @@ import re
 import pytest
 
 import dot_attention_case as case
+from abi_support import DOT, P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_dot_attn_workspace_bytes", "pygat_dot_attn_forward", "pygat_dot_attn_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-def _forward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_forward(*a.values(), None)
-
-
-def _backward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, out=P, ldo=16, m=P,
-             Z=P, G=P, ldg=16, dq=P, lddq=16, P=P, S=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_backward_rows(*a.values(), None)
-
-
-LAUNCHERS = ((_forward, "dot_attn_forward"), (_backward, "dot_attn_backward_rows"))
+LAUNCHERS = DOT
+_forward, _backward = (fn for fn, _ in LAUNCHERS)
 TABLES = {"dot_attn_forward": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("out", "ldo")),
           "dot_attn_backward_rows": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("out", "ldo"), ("G", "ldg"), ("dq", "lddq"))}
 SCALARS = {"dot_attn_forward": ("rowptr", "col", "m", "Z", "ws"), "dot_attn_backward_rows": ("rowptr", "col", "m", "Z", "P", "S", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

@@ -12,27 +12,15 @@ import pytest
 import torch
 
 import dot_attention_bf16_case as case
+from abi_support import DOT, DOT_BIAS, P, call, lib, msg as _msg  # noqa: F401
 
 NAME = "dot_attn_bf16_forward"
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P + 8, ldk=16, v=P + 8, ldv=16,
              bias=P + 4, bias_head_stride=1, out=P, ldo=16, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_bf16_forward(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
+    return call(L, "pygat_dot_attn_bf16_forward", a, **kw)
 
 
 def test_additive_under_abi_16(lib):
@@ -100,10 +88,8 @@ def test_a_null_bias_is_no_bias(lib):
 def test_the_same_wording_as_the_float32_launchers(lib):
     """Whatever pygat_dot_attn_forward / pygat_dot_attn_bias_forward refuse, this launcher refuses in the same words after its own
     name (k and v: the same but for the 8 bytes of their alignment)."""
-    import test_dot_attention_abi as plain
-    import test_dot_attention_bias_abi as biased
-    for other, oname, mine in ((plain._forward, "dot_attn_forward", dict(bias=None)),
-                               (biased._forward, "dot_attn_bias_forward", dict())):
+    for other, oname, mine in ((DOT[0][0], "dot_attn_forward", dict(bias=None)),
+                               (DOT_BIAS[0][0], "dot_attn_bias_forward", dict())):
         for kw in (dict(H=65), dict(F=12), dict(H=8, F=256), dict(nnz=-1), dict(nnz=1 << 31), dict(n_rows=0), dict(q=None),
                    dict(q=P + 4), dict(k=None), dict(ldv=12), dict(ldk=18), dict(out=P + 8), dict(ws=None), dict(ws=P + 8),
                    dict(col=None), dict(rowptr=None)):
@@ -113,7 +99,7 @@ def test_the_same_wording_as_the_float32_launchers(lib):
             assert got[len(NAME):] == _msg(lib)[len(oname):] and got.startswith(NAME), (kw, got, _msg(lib))
     assert _forward(lib, bias_head_stride=3) == -1
     got = _msg(lib)
-    assert biased._forward(lib, bias_head_stride=3) == -1 and got[len(NAME):] == _msg(lib)[len("dot_attn_bias_forward"):]
+    assert DOT_BIAS[0][0](lib, bias_head_stride=3) == -1 and got[len(NAME):] == _msg(lib)[len("dot_attn_bias_forward"):]
 
 
 def _fake_pattern():

@@ -11,42 +11,17 @@ import pytest
 import torch
 
 import dot_attention_bias_case as case
+from abi_support import DOT, DOT_BIAS, P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_dot_attn_bias_forward", "pygat_dot_attn_bias_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-def _forward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, bias=P + 4,
-             bias_head_stride=1, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_bias_forward(*a.values(), None)
-
-
-def _backward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, bias=P + 4,
-             bias_head_stride=1, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, dq=P, lddq=16, P=P, S=P, dbias=None, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_bias_backward_rows(*a.values(), None)
-
-
-LAUNCHERS = ((_forward, "dot_attn_bias_forward"), (_backward, "dot_attn_bias_backward_rows"))
+LAUNCHERS = DOT_BIAS
+_forward, _backward = (fn for fn, _ in LAUNCHERS)
 TABLES = {"dot_attn_bias_forward": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("out", "ldo")),
           "dot_attn_bias_backward_rows": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("out", "ldo"), ("G", "ldg"), ("dq", "lddq"))}
 SCALARS = {"dot_attn_bias_forward": ("rowptr", "col", "m", "Z", "bias", "ws"),
            "dot_attn_bias_backward_rows": ("rowptr", "col", "m", "Z", "P", "S", "bias", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -98,8 +73,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 
 def test_the_same_wording_as_the_pair_without_a_bias(lib):
     """Whatever pygat_dot_attn_forward / _backward_rows refuse, the bias launchers refuse in the same words after their own name."""
-    import test_dot_attention_abi as plain
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS, plain.LAUNCHERS):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS, DOT):
         for kw in (dict(H=65), dict(F=12), dict(nnz=-1), dict(n_rows=0), dict(q=None), dict(k=P + 4), dict(ldv=12), dict(m=None),
                    dict(ws=None), dict(ws=P + 8), dict(col=None)):
             assert fn(lib, **kw) == -1

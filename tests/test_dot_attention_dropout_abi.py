@@ -15,32 +15,22 @@ import torch
 
 import dot_attention_dropout_case as case
 import philox_ref
+from abi_support import DOT_BIAS, P, call, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_dot_attn_dropout_forward", "pygat_dot_attn_dropout_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, bias=P + 4,
              bias_head_stride=1, p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_dropout_forward(*a.values(), None)
+    return call(L, "pygat_dot_attn_dropout_forward", a, **kw)
 
 
 def _backward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, scale=0.5, q=P, ldq=16, k=P, ldk=16, v=P, ldv=16, bias=P + 4,
              bias_head_stride=1, p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, dq=P, lddq=16, P=P, S=P,
              dbias=None, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_dot_attn_dropout_backward_rows(*a.values(), None)
+    return call(L, "pygat_dot_attn_dropout_backward_rows", a, **kw)
 
 
 LAUNCHERS = ((_forward, "dot_attn_dropout_forward"), (_backward, "dot_attn_dropout_backward_rows"))
@@ -48,10 +38,6 @@ TABLES = {"dot_attn_dropout_forward": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"),
           "dot_attn_dropout_backward_rows": (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("out", "ldo"), ("G", "ldg"), ("dq", "lddq"))}
 SCALARS = {"dot_attn_dropout_forward": ("rowptr", "col", "m", "Z", "ws"),
            "dot_attn_dropout_backward_rows": ("rowptr", "col", "m", "Z", "P", "S", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -109,8 +95,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 def test_the_same_wording_as_the_bias_pair(lib):
     """Whatever pygat_dot_attn_bias_forward / _backward_rows refuse, the dropout launchers refuse in the same words after their own
     name (a null bias apart: here it means no bias)."""
-    import test_dot_attention_bias_abi as biased
-    for (fn, name), (bfn, bname) in zip(LAUNCHERS, biased.LAUNCHERS):
+    for (fn, name), (bfn, bname) in zip(LAUNCHERS, DOT_BIAS):
         for kw in (dict(H=65), dict(F=12), dict(nnz=-1), dict(n_rows=0), dict(q=None), dict(k=P + 4), dict(ldv=12), dict(m=None),
                    dict(ws=None), dict(ws=P + 8), dict(col=None), dict(bias_head_stride=2), dict(out=None), dict(ldq=15)):
             assert fn(lib, **kw) == -1

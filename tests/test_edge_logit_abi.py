@@ -6,15 +6,10 @@ import re
 
 import pytest
 
+from abi_support import P, lib, msg as _msg  # noqa: F401
+
 NEW = ("pygat_gat_edge_workspace_bytes", "pygat_gat_edge_forward", "pygat_gat_edge_alpha", "pygat_gat_edge_backward_rows",
        "pygat_gat_edge_backward_cols")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _fwd(L, **kw):
@@ -42,10 +37,6 @@ def _cols(L, **kw):
              a_pad=P, dt=P, dWh=P, ws=P)
     a.update(kw)
     return L.lib.pygat_gat_edge_backward_cols(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

@@ -9,16 +9,10 @@ import re
 import pytest
 
 import edge_softmax_case as case
+from abi_support import P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_edge_softmax_workspace_bytes", "pygat_edge_softmax_rows", "pygat_edge_softmax_apply", "pygat_edge_softmax_grad_rows",
        "pygat_edge_softmax_grad_apply")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _rows(L, **kw):
@@ -47,10 +41,6 @@ def _grad_apply(L, **kw):
 
 LAUNCHERS = ((_rows, "edge_softmax_rows"), (_apply, "edge_softmax_apply"), (_grad_rows, "edge_softmax_grad_rows"),
              (_grad_apply, "edge_softmax_grad_apply"))
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

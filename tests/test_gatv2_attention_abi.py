@@ -11,52 +11,19 @@ import pytest
 import torch
 
 import gatv2_attention_case as case
+from abi_support import ADDITIVE, GATV2, P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_v2_attn_workspace_bytes", "pygat_v2_attn_forward", "pygat_v2_attn_backward_rows", "pygat_v2_attn_backward_cols")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-def _forward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P, ldv=16, out=P,
-             ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_forward(*a.values(), None)
-
-
-def _backward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P,
-             ldv=16, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, dx_dst=P, lddx=16, P=P, S=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_backward_rows(*a.values(), None)
-
-
-def _columns(L, **kw):
-    a = dict(n_cols=8, nnz=20, rowptr_t=P, row_t=P, perm_t=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P,
-             S=P, dx_src=P, lddx=16, da=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_backward_cols(*a.values(), None)
-
-
-LAUNCHERS = ((_forward, "v2_attn_forward"), (_backward, "v2_attn_backward_rows"), (_columns, "v2_attn_backward_cols"))
+LAUNCHERS = GATV2
+_forward, _backward, _columns = (fn for fn, _ in LAUNCHERS)
 TABLES = {"v2_attn_forward": (("x_dst", "ldd"), ("x_src", "lds"), ("v", "ldv"), ("out", "ldo")),
           "v2_attn_backward_rows": (("x_dst", "ldd"), ("x_src", "lds"), ("v", "ldv"), ("out", "ldo"), ("G", "ldg"), ("dx_dst", "lddx")),
           "v2_attn_backward_cols": (("x_dst", "ldd"), ("x_src", "lds"), ("dx_src", "lddx"))}
 SCALARS = {"v2_attn_forward": ("rowptr", "col", "a", "m", "Z", "ws"),
            "v2_attn_backward_rows": ("rowptr", "col", "a", "m", "Z", "P", "S", "ws"),
            "v2_attn_backward_cols": ("rowptr_t", "row_t", "a", "S", "da", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -172,8 +139,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 def test_the_same_wording_as_additive_attention(lib):
     """Whatever pygat_add_attn_forward / _backward_rows refuse of the arguments both families have, these refuse in the same words
     after their own name."""
-    import test_additive_attention_abi as plain
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS[:2], plain.LAUNCHERS):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS[:2], ADDITIVE):
         for kw in (dict(H=65), dict(nnz=-1), dict(n_rows=0), dict(n_rows=-1), dict(v=P + 4), dict(ldv=12), dict(m=None), dict(ws=None),
                    dict(ws=P + 8), dict(col=None), dict(rowptr=None), dict(out=P + 8), dict(out=None), dict(Z=None), dict(H=8, F=256),
                    dict(negative_slope=float("nan")), dict(nnz=1 << 31)):
@@ -184,7 +150,7 @@ def test_the_same_wording_as_additive_attention(lib):
     for kw in (dict(G=None), dict(G=P + 4), dict(ldg=12), dict(P=None), dict(S=None)):
         assert _backward(lib, **kw) == -1
         mine = _msg(lib)
-        assert plain._backward(lib, **kw) == -1
+        assert ADDITIVE[1][0](lib, **kw) == -1
         assert mine[len("v2_attn_backward_rows"):] == _msg(lib)[len("add_attn_backward_rows"):], (kw, mine, _msg(lib))
 
 

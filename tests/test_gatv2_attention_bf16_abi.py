@@ -12,40 +12,26 @@ import pytest
 import torch
 
 import gatv2_attention_bf16_case as case
+from abi_support import GATV2, GATV2_EDGE, P, call, lib, msg as _msg  # noqa: F401
 
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 H8 = P + 8        # 8 bytes off a 16-byte line: where a table of bf16 rows may begin and a table of floats may not
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=H8, lds=16, a=P, v=H8, ldv=16,
              out=P, ldo=16, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_bf16_forward(*a.values(), None)
+    return call(L, "pygat_v2_attn_bf16_forward", a, **kw)
 
 
 def _edge_forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=H8, lds=16, a=P, v=H8,
              ldv=16, e=H8, lde=16, out=P, ldo=16, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_edge_bf16_forward(*a.values(), None)
+    return call(L, "pygat_v2_attn_edge_bf16_forward", a, **kw)
 
 
 LAUNCHERS = ((_forward, "v2_attn_bf16_forward"), (_edge_forward, "v2_attn_edge_bf16_forward"))
 TABLES = {"v2_attn_bf16_forward": (("x_dst", "ldd", 16), ("x_src", "lds", 8), ("v", "ldv", 8), ("out", "ldo", 16)),
           "v2_attn_edge_bf16_forward": (("x_dst", "ldd", 16), ("x_src", "lds", 8), ("v", "ldv", 8), ("out", "ldo", 16), ("e", "lde", 8))}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -127,10 +113,8 @@ def test_each_launcher_refuses_its_own_tables(lib):
 def test_the_same_wording_as_the_float32_launchers(lib):
     """Whatever pygat_v2_attn_forward / pygat_v2_attn_edge_forward refuse, these launchers refuse in the same words after their own
     name (x_src, v and e: the same but for the 8 bytes of their alignment)."""
-    import test_gatv2_attention_abi as plain
-    import test_gatv2_attention_edge_abi as edged
-    for (fn, name), (pfn, pname) in ((LAUNCHERS[0], (plain._forward, "v2_attn_forward")),
-                                     (LAUNCHERS[1], (edged._forward, "v2_attn_edge_forward"))):
+    for (fn, name), (pfn, pname) in ((LAUNCHERS[0], (GATV2[0][0], "v2_attn_forward")),
+                                     (LAUNCHERS[1], (GATV2_EDGE[0][0], "v2_attn_edge_forward"))):
         for kw in (dict(H=65), dict(F=12), dict(H=8, F=256), dict(nnz=-1), dict(nnz=1 << 31), dict(n_rows=0), dict(x_dst=None),
                    dict(x_dst=P + 4), dict(x_src=None), dict(lds=15), dict(ldv=12), dict(ldd=18), dict(out=P + 8), dict(ws=None),
                    dict(ws=P + 8), dict(a=None), dict(a=P + 4), dict(col=None), dict(rowptr=None), dict(negative_slope=float("nan"))):
@@ -141,7 +125,7 @@ def test_the_same_wording_as_the_float32_launchers(lib):
     for kw in (dict(e=None), dict(lde=12), dict(lde=18)):
         assert _edge_forward(lib, **kw) == -1
         got = _msg(lib)
-        assert edged._forward(lib, **kw) == -1
+        assert GATV2_EDGE[0][0](lib, **kw) == -1
         assert got[len("v2_attn_edge_bf16_forward"):] == _msg(lib)[len("v2_attn_edge_forward"):], (kw, got, _msg(lib))
 
 

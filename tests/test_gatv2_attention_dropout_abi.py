@@ -15,31 +15,21 @@ import torch
 import dot_attention_dropout_case as dot_case
 import gatv2_attention_dropout_case as case
 import philox_ref
+from abi_support import GATV2, P, call, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_v2_attn_dropout_forward", "pygat_v2_attn_dropout_backward_rows")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _forward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P, ldv=16,
              p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_dropout_forward(*a.values(), None)
+    return call(L, "pygat_v2_attn_dropout_forward", a, **kw)
 
 
 def _backward(L, **kw):
     a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P,
              ldv=16, p=0.5, seed=P + 8, stream_id=3, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, dx_dst=P, lddx=16, P=P, S=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_dropout_backward_rows(*a.values(), None)
+    return call(L, "pygat_v2_attn_dropout_backward_rows", a, **kw)
 
 
 LAUNCHERS = ((_forward, "v2_attn_dropout_forward"), (_backward, "v2_attn_dropout_backward_rows"))
@@ -48,10 +38,6 @@ TABLES = {"v2_attn_dropout_forward": (("x_dst", "ldd"), ("x_src", "lds"), ("v", 
                                             ("dx_dst", "lddx"))}
 SCALARS = {"v2_attn_dropout_forward": ("rowptr", "col", "a", "m", "Z", "ws"),
            "v2_attn_dropout_backward_rows": ("rowptr", "col", "a", "m", "Z", "P", "S", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -117,8 +103,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 
 def test_the_same_wording_as_the_parent_pair(lib):
     """Whatever pygat_v2_attn_forward / _backward_rows refuse, the dropout launchers refuse in the same words after their own name."""
-    import test_gatv2_attention_abi as parent
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS, parent.LAUNCHERS[:2]):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS, GATV2[:2]):
         for kw in (dict(H=65), dict(F=12), dict(nnz=-1), dict(n_rows=0), dict(x_dst=None), dict(x_src=P + 4), dict(ldv=12), dict(m=None),
                    dict(ws=None), dict(ws=P + 8), dict(col=None), dict(a=None), dict(out=None), dict(lds=15),
                    dict(negative_slope=float("nan"))):

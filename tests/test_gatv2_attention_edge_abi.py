@@ -11,42 +11,13 @@ import pytest
 import torch
 
 import gatv2_attention_edge_case as case
+from abi_support import DOT_EDGE, GATV2, GATV2_EDGE, P, lib, msg as _msg  # noqa: F401
 
 NEW = ("pygat_v2_attn_edge_forward", "pygat_v2_attn_edge_backward_rows", "pygat_v2_attn_edge_backward_cols")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
-
-
-def _forward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P,
-             ldv=16, e=P, lde=16, out=P, ldo=16, m=P, Z=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_edge_forward(*a.values(), None)
-
-
-def _backward(L, **kw):
-    a = dict(n_rows=8, nnz=20, rowptr=P, col=P, perm=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P, v=P,
-             ldv=16, e=P, lde=16, out=P, ldo=16, m=P, Z=P, G=P, ldg=16, dx_dst=P, lddx=16, P=P, S=P, de=P, ldde=16, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_edge_backward_rows(*a.values(), None)
-
-
-def _columns(L, **kw):
-    a = dict(n_cols=8, nnz=20, rowptr_t=P, row_t=P, perm_t=None, H=2, F=8, negative_slope=0.2, x_dst=P, ldd=16, x_src=P, lds=16, a=P,
-             e=P, lde=16, S=P, dx_src=P, lddx=16, da=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_v2_attn_edge_backward_cols(*a.values(), None)
-
-
-LAUNCHERS = ((_forward, "v2_attn_edge_forward"), (_backward, "v2_attn_edge_backward_rows"), (_columns, "v2_attn_edge_backward_cols"))
+LAUNCHERS = GATV2_EDGE
+_forward, _backward, _columns = (fn for fn, _ in LAUNCHERS)
 TABLES = {"v2_attn_edge_forward": (("x_dst", "ldd"), ("x_src", "lds"), ("v", "ldv"), ("out", "ldo"), ("e", "lde")),
           "v2_attn_edge_backward_rows": (("x_dst", "ldd"), ("x_src", "lds"), ("v", "ldv"), ("out", "ldo"), ("G", "ldg"),
                                          ("dx_dst", "lddx"), ("e", "lde")),
@@ -54,10 +25,6 @@ TABLES = {"v2_attn_edge_forward": (("x_dst", "ldd"), ("x_src", "lds"), ("v", "ld
 SCALARS = {"v2_attn_edge_forward": ("rowptr", "col", "a", "m", "Z", "ws"),
            "v2_attn_edge_backward_rows": ("rowptr", "col", "a", "m", "Z", "P", "S", "ws"),
            "v2_attn_edge_backward_cols": ("rowptr_t", "row_t", "a", "S", "da", "ws")}
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):
@@ -139,8 +106,7 @@ def test_each_launcher_refuses_its_own_tables(lib):
 def test_the_same_wording_as_the_launchers_without_e(lib):
     """Whatever pygat_v2_attn_forward / _backward_rows / _backward_cols refuse, the EDGE launchers refuse in the same words after
     their own name."""
-    import test_gatv2_attention_abi as parent
-    for (fn, name), (pfn, pname) in zip(LAUNCHERS, parent.LAUNCHERS):
+    for (fn, name), (pfn, pname) in zip(LAUNCHERS, GATV2):
         cols = name.endswith("cols")
         for kw in (dict(H=65), dict(F=12), dict(nnz=-1), dict(x_dst=None), dict(x_src=P + 4), dict(lds=15), dict(ws=None),
                    dict(ws=P + 8), dict(a=None), dict(negative_slope=float("nan")), dict(H=8, F=256),
@@ -153,8 +119,7 @@ def test_the_same_wording_as_the_launchers_without_e(lib):
 
 
 def test_e_and_de_are_refused_in_the_words_of_dot_attn_edge(lib):
-    import test_dot_attention_edge_abi as dot
-    for (fn, name), (dfn, dname) in ((LAUNCHERS[0], dot.LAUNCHERS[0]), (LAUNCHERS[1], dot.LAUNCHERS[1]), (LAUNCHERS[2], dot.LAUNCHERS[0])):
+    for (fn, name), (dfn, dname) in ((LAUNCHERS[0], DOT_EDGE[0]), (LAUNCHERS[1], DOT_EDGE[1]), (LAUNCHERS[2], DOT_EDGE[0])):
         kws = [dict(e=None), dict(e=P + 4), dict(e=P + 8), dict(lde=15), dict(lde=12), dict(lde=18), dict(lde=0), dict(lde=-16)]
         if name.endswith("backward_rows"):
             kws += [dict(de=P + 4), dict(ldde=15), dict(ldde=18), dict(ldde=0), dict(e=None, de=P + 4)]

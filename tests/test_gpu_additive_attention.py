@@ -5,7 +5,6 @@ Ground truth, inputs and the seeded cases live in additive_attention_case.py: to
 pricing by parity.check_autograd unchanged (out by close_fwd, every gradient by close_grad).  Every seeded case is rehearsed on the CPU,
 the fp32 ground-truth run standing in for the device, by tests/test_additive_attention_abi.py and passes there; no case is built here."""
 import copy
-import ctypes as C
 import importlib
 import itertools
 
@@ -13,18 +12,14 @@ import pytest
 import torch
 
 import additive_attention_case as case
-from test_gpu_attention import DEV, _graph
-from test_gpu_dot_attention import _Spy, _pattern
+from pattern_device import DEV, _graph, _pattern, degree, device_run, no_scratch, spied, two_runs_bit_equal
+from pattern_device import leaves as _leaves
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))
 K20 = [f"{prefix}_{d}_{kind}_l{l}v{v}" for prefix in ("k20", "k20u") for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES]
 FWD, ROWS, SPMM = "pygat_add_attn_forward", "pygat_add_attn_backward_rows", "pygat_spmm_forward"
-
-
-def _leaves(c):
-    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
 
 
 def _fused(pattern, c):
@@ -46,10 +41,7 @@ def _from_parts(pattern, c):
 
 def _device_run(pattern, c, fn=None, leaves=None):
     """-> (out, ds_dst, ds_src, dv[, du]) on the device."""
-    leaves = leaves or _leaves(c)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == c.G.shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused, leaves)
 
 
 def _run_case(name):
@@ -57,10 +49,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     c.price(*res)
     return (c,) + res
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -92,7 +80,7 @@ def test_whole_number_scores(name):
 def test_rectangular_with_empty_rows_and_columns(name):
     c, out, dd, ds, dv = _run_case(name)[:5]
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     no_col = (torch.bincount(c.col, minlength=c.shape[1]) == 0).to(DEV)
     assert int(no_row.sum()) == 100 and int(no_col.sum()) == 125
     for t in (out[no_row], dd[no_row], ds[no_col], dv[no_col]):
@@ -113,7 +101,7 @@ def test_repeated_pairs_are_separate_entries(name):
 def test_a_row_of_one_entry_is_exact(name):
     res = _run_case(name)
     c, out, dd = res[:3]
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -144,12 +132,7 @@ def test_a_masked_entry_is_exactly_out(name):
 
 @pytest.mark.parametrize("name", case.case_names("twice-"))
 def test_two_runs_are_bit_equal(name):
-    c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    for p, q in zip(*runs):
-        assert torch.equal(p, q)
-    c.price(*runs[0])
+    two_runs_bit_equal(case.cases()[name], _device_run)
 
 
 # ------------------------------------------------------------------------------------------------------------------ composition
@@ -201,11 +184,7 @@ def test_a_bipartite_gat_layer(name):
 
 # ---------------------------------------------------------------------------------------------------------- launches and refusals
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.additive_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
+    return spied(monkeypatch, "pygat_amd.additive_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def test_only_the_needed_launches(monkeypatch):
@@ -338,12 +317,6 @@ def test_capture_and_replay(name):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_no_kernel_uses_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K20) == 80
-    for name in K20:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k20_fwd_row_l3v1", b"k20_fwd_row_l32v2", b"k20_fwd_row_l64v5", b"k20_mid_row_l8v1", b"k20_fwd_row_l8v1x", b"k20_",
-                b"k20", b"k20fwd_row_l8v1", b"k20b_fwd_row_l8v1", b"k20u_fwd_col_l8v1", b"k20u_bwd_row_l0v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K20, (b"k20_fwd_row_l3v1", b"k20_fwd_row_l32v2", b"k20_fwd_row_l64v5", b"k20_mid_row_l8v1", b"k20_fwd_row_l8v1x", b"k20_",
+                     b"k20", b"k20fwd_row_l8v1", b"k20b_fwd_row_l8v1", b"k20u_fwd_col_l8v1", b"k20u_bwd_row_l0v1"))

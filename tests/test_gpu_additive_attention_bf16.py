@@ -7,15 +7,11 @@ registers, and everything after the load is the float32 kernels' -- so those tes
 against the fp64 ground truth on the widened table by the one rule of parity.py, so that this file does not lean on the float32
 kernels alone.  The seeded cases live in additive_attention_bf16_case.py and are rehearsed on the CPU by
 tests/test_additive_attention_bf16_abi.py; no case is built here."""
-import ctypes as C
-import importlib
-
 import pytest
 import torch
 
 import additive_attention_bf16_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _indices_pattern, _pattern
+from pattern_device import DEV, _graph, _indices_pattern, _pattern, degree, no_scratch, spied
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +21,7 @@ K20H = [f"{prefix}_fwd_{kind}_l{l}v{v}" for prefix in ("k20h", "k20hu") for kind
 
 
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.additive_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):    # (package attributes of these names are functions)
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
+    return spied(monkeypatch, "pygat_amd.additive_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def _inputs(c):
@@ -53,10 +45,6 @@ def _both(c, pattern=None):
     pattern = pattern or _pattern(c)
     s_dst, s_src, v16, u = _inputs(c)
     return _attend(pattern, c, s_dst, s_src, v16, u), _attend(pattern, c, s_dst, s_src, v16.float(), u)
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ---------------------------------------------------------------------------------------------------------------- bit equality
@@ -163,7 +151,7 @@ def test_an_empty_pattern_gives_zeros_without_a_launch(monkeypatch):
 def test_a_row_of_one_entry_is_its_v_row(name):
     c = case.cases()[name]
     out = _attend(_pattern(c), c, *_inputs(c))
-    single = _degree(c)[c.row] == 1
+    single = degree(c)[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= (12 if "lonely" in name else 1)
     assert torch.equal(out[rows], c.v16.to(DEV)[cols].float()), "out_i == v16[j].float() bit for bit"
@@ -182,7 +170,7 @@ def test_a_masked_entry_contributes_exact_zeros(name):
     keep = ~c.masked
     kept = _indices_pattern(c.row[keep], c.col[keep], c.shape)
     want = _attend(kept, c, s_dst, s_src, v16, u[keep.to(DEV)].contiguous())
-    short = (_degree(c) <= 512).to(DEV)
+    short = (degree(c) <= 512).to(DEV)
     assert int(short.sum()) > 0.9 * c.shape[0]
     assert torch.equal(out[short], want[short]), name
     some = torch.bincount(c.row[c.masked], minlength=c.shape[0]).to(DEV) > 0
@@ -195,10 +183,10 @@ def test_a_sampled_block_with_gathered_bf16_rows():
     logit of the whole graph by blk.edge_ids, bit-equal to the float32 op on the widened gathers."""
     import pygat_amd as pg
     import sample_case
-    from test_gpu_sample import graph, seed_of
     t = sample_case.TWO_HOP
-    g = graph(t["graph"])
-    blocks = pg.sample_blocks(g, torch.as_tensor(sample_case.two_hop_seeds()).to(DEV), list(t["fanouts"]), seed=seed_of(t["seed"]))
+    g = _graph(*sample_case.graphs()[t["graph"]])
+    seed = torch.tensor([t["seed"]], dtype=torch.int64, device=DEV)
+    blocks = pg.sample_blocks(g, torch.as_tensor(sample_case.two_hop_seeds()).to(DEV), list(t["fanouts"]), seed=seed)
     gen = torch.Generator(device=DEV).manual_seed(7)
     H, F = 4, 16
     x16 = torch.randn(g.n, H, F, device=DEV, generator=gen).bfloat16()
@@ -266,13 +254,7 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_bf16_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K20H) == 40
-    for name in K20H:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k20h_bwd_row_l8v1", b"k20hu_bwd_long_l8v1", b"k20h_col_row_l8v1", b"k20h_fwd_row_l3v1", b"k20h_fwd_row_l32v2",
-                b"k20hu_fwd_row_l64v5", b"k20h_fwd_row_l8v1x", b"k20h_", b"k20h", b"k20hu_", b"k20hd_fwd_row_l8v1", b"k20hfwd_row_l8v1",
-                b"k20b_fwd_row_l8v1", b"k20hb_fwd_row_l8v1", b"k20dh_fwd_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K20H, (b"k20h_bwd_row_l8v1", b"k20hu_bwd_long_l8v1", b"k20h_col_row_l8v1", b"k20h_fwd_row_l3v1", b"k20h_fwd_row_l32v2",
+                      b"k20hu_fwd_row_l64v5", b"k20h_fwd_row_l8v1x", b"k20h_", b"k20h", b"k20hu_", b"k20hd_fwd_row_l8v1", b"k20hfwd_row_l8v1",
+                      b"k20b_fwd_row_l8v1", b"k20hb_fwd_row_l8v1", b"k20dh_fwd_row_l8v1"))

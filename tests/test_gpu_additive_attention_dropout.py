@@ -6,7 +6,6 @@ of tests/philox_ref.py, loss L = <out, G>, pricing by parity.check_autograd unch
 Every case is rehearsed on the CPU, the fp32 ground-truth run standing in for the device, by
 tests/test_additive_attention_dropout_abi.py and passes there; no case is built here."""
 import copy
-import ctypes as C
 import importlib
 import itertools
 
@@ -14,8 +13,8 @@ import pytest
 import torch
 
 import additive_attention_dropout_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern
+from pattern_device import DEV, _pattern, _seed, device_run, no_scratch, spied
+from pattern_device import leaves as _leaves
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +22,6 @@ FWD, ROWS, SPMM = "pygat_add_attn_forward", "pygat_add_attn_backward_rows", "pyg
 DFWD, DROWS, MASK = "pygat_add_attn_dropout_forward", "pygat_add_attn_dropout_backward_rows", "pygat_dropout_mask"
 SHAPES = ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))
 K20D = [f"{fam}_{d}_{kind}_l{l}v{v}" for fam in ("k20d", "k20du") for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES]
-
-
-def _seed(value):
-    return torch.tensor([value], dtype=torch.int64, device=DEV)
-
-
-def _leaves(c):
-    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
 
 
 def _fused(pattern, c, seed=None):
@@ -55,10 +46,7 @@ def _from_parts(pattern, c, seed=None):
 
 def _device_run(pattern, c, fn=None, seed=None, leaves=None):
     """-> (out, ds_dst, ds_src, dv[, du]) on the device."""
-    leaves = leaves or _leaves(c)
-    out = (fn or _fused)(pattern, c, seed)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == c.G.shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused, leaves, seed=seed)
 
 
 def _run_case(name):
@@ -70,11 +58,7 @@ def _run_case(name):
 
 
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.additive_attention", "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
+    return spied(monkeypatch, "pygat_amd.additive_attention", "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -361,12 +345,6 @@ def test_a_bipartite_gat_layer_under_dropout(name):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_dropout_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K20D) == 80
-    for name in K20D:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k20d_fwd_row_l3v1", b"k20d_fwd_row_l32v2", b"k20du_fwd_row_l64v5", b"k20d_mid_row_l8v1", b"k20du_fwd_row_l8v1x", b"k20d_",
-                b"k20d", b"k20dfwd_row_l8v1", b"k20b_fwd_row_l8v1", b"k20ud_fwd_row_l8v1", b"k20d_col_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K20D, (b"k20d_fwd_row_l3v1", b"k20d_fwd_row_l32v2", b"k20du_fwd_row_l64v5", b"k20d_mid_row_l8v1", b"k20du_fwd_row_l8v1x", b"k20d_",
+                      b"k20d", b"k20dfwd_row_l8v1", b"k20b_fwd_row_l8v1", b"k20ud_fwd_row_l8v1", b"k20d_col_row_l8v1"))

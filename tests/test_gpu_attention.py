@@ -11,12 +11,11 @@ import pytest
 import torch
 
 import parity
+from pattern_device import DEV, _graph
+from pattern_graphs import SHAPES, SID, SLOPE, _asym_graph, _hub_graph, _params
 from tail_case import _iso_csr
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-SLOPE = 0.2
 
 
 def _leaky(z):
@@ -84,40 +83,6 @@ def check_alpha(got, rowptr, a64, a32=None, what="alpha"):
     assert ((sums - 1).abs() <= bound)[live.expand_as(sums)].all(), f"{what}: a row sum is off by {(sums - 1).abs().max():.3e}"
     single = (deg == 1)[src]
     assert (g[single] == 1.0).all(), f"{what}: a single-edge row is not exactly 1"
-
-
-def _graph(rowptr, col):
-    import pygat_amd as pg
-    return pg.CSRGraph(torch.as_tensor(np.asarray(rowptr), device=DEV), torch.as_tensor(np.asarray(col), device=DEV))
-
-
-def _hub_graph(N=700, seed=3):
-    from oracle import gat_oracle as O
-    return O.random_symmetric_csr(N, 8, seed, hub=(5, N - 1))
-
-
-def _asym_graph(N=500, seed=4):
-    """Directed edges, a self loop on every other node only, some rows of one edge whose node is gathered elsewhere."""
-    rng = np.random.default_rng(seed)
-    r = rng.integers(0, N, 6 * N); c = rng.integers(0, N, 6 * N)
-    r = np.concatenate([r, np.arange(0, N, 2), np.arange(N)]); c = np.concatenate([c, np.arange(0, N, 2), (np.arange(N) * 7 + 1) % N])
-    key = np.unique(r.astype(np.int64) * N + c)
-    rr, cc = key // N, key % N
-    rowptr = np.concatenate([[0], np.cumsum(np.bincount(rr, minlength=N))]).astype(np.int32)
-    return rowptr, cc.astype(np.int32)
-
-
-def _params(N, Fin, H, Fo, seed, v2=False):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, Fin, generator=g).float()
-    W = (torch.randn(H, (2 if v2 else 1) * Fin, Fo, generator=g) * (1.414 * (2.0 / (Fin + Fo)) ** 0.5)).float()
-    a = (torch.randn(H, Fo if v2 else 2 * Fo, generator=g) * 0.5).float()
-    S = (torch.randn(H, Fin, Fo, generator=g) * 0.1).float()
-    return x, W, a, S
-
-
-SHAPES = [(1, 7), (8, 8), (8, 16), (4, 64), (4, 256), (16, 64)]
-SID = ["x".join(map(str, s)) for s in SHAPES]
 
 
 def _run_v1(x, W, a, graph, concat, S=None, **kw):

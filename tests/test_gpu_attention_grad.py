@@ -12,8 +12,10 @@ import torch
 import parity
 from alpha_grad_case import kink_count, level_ref, src_of
 from long_row_cases import nine_hubs, three_chunk_hub
+from pattern_device import DEV, _graph
+from pattern_graphs import SHAPES, SID, SLOPE, _asym_graph, _hub_graph, _params
 from tail_case import _iso_csr
-from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _force, _graph, _hub_graph, _params
+from test_gpu_attention import _force
 
 pytestmark = pytest.mark.gpu
 

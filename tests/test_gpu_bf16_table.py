@@ -15,7 +15,8 @@ import torch
 import parity
 from alpha_grad_case import src_of
 from bf16_table_case import SLOPE, case, exact_inputs, hub_graph, reference, table
-from test_gpu_attention import DEV, SHAPES, _asym_graph
+from pattern_device import DEV
+from pattern_graphs import SHAPES, _asym_graph
 
 pytestmark = pytest.mark.gpu
 

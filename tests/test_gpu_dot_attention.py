@@ -4,7 +4,6 @@
 Ground truth, inputs and the seeded cases live in dot_attention_case.py: torch autograd in fp64 on the CPU, loss L = <out, G>, pricing
 by parity.check_autograd unchanged (out by close_fwd, dq, dk, dv by close_grad).  Every seeded case is rehearsed on the CPU, the fp32
 ground-truth run standing in for the device, by tests/test_dot_attention_abi.py and passes there; no case is built here."""
-import ctypes as C
 import importlib
 
 import pytest
@@ -13,31 +12,12 @@ import torch
 import dot_attention_case as case
 import parity
 from edge_softmax_case import edge_softmax_ref
-from test_gpu_attention import DEV, _graph
+from pattern_device import DEV, FWD, ROWS, SDDMM, SPMM, _pattern, degree, device_run, no_scratch, spied, to_leaves, two_runs_bit_equal
 
 pytestmark = pytest.mark.gpu
 
 K19 = [f"k19_{d}_{kind}_l{l}v{v}" for d in ("fwd", "bwd") for kind in ("long", "row")
        for l, v in ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))]
-
-
-def _indices_pattern(row, col, shape):
-    import pygat_amd as pg
-    return pg.EdgePattern.from_indices(torch.stack([row, col]).to(DEV), shape)
-
-
-def _pattern(c):
-    if c.kind == "indices":
-        pattern = _indices_pattern(c.row, c.col, c.shape)
-        assert pattern.perm is not None
-        return pattern
-    pattern = _graph(*c.csr).edge_pattern()
-    assert pattern.perm is None and torch.equal(pattern.edge_rc.cpu().long(), torch.stack([c.row, c.col], 1))
-    return pattern
-
-
-def _leaves(*tensors):
-    return [t.float().to(DEV).requires_grad_(True) for t in tensors]
 
 
 def _fused(pattern, c):
@@ -52,10 +32,7 @@ def _from_parts(pattern, c):
 
 def _device_run(pattern, c, fn=None):
     """-> (out, dq, dk, dv) on the device."""
-    leaves = _leaves(c.q, c.k, c.v)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == leaves[0].shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused)
 
 
 def _run_case(name):
@@ -63,10 +40,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     _, y64 = c.price(*res)
     return (c,) + res + (y64,)
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -111,7 +84,7 @@ def test_whole_number_scores(name):
 def test_rectangular_with_empty_rows_and_columns(name):
     c, out, dq, dk, dv, _ = _run_case(name)
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     no_col = (torch.bincount(c.col, minlength=c.shape[1]) == 0).to(DEV)
     assert int(no_row.sum()) == 100 and int(no_col.sum()) == 125
     for t in (out[no_row], dq[no_row], dk[no_col], dv[no_col]):
@@ -133,7 +106,7 @@ def test_unsorted_entries_with_repeats(name):
 @pytest.mark.parametrize("name", case.case_names("lonely-"))
 def test_a_row_of_one_entry_is_exact(name):
     c, out, dq, dk, dv, _ = _run_case(name)
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -145,12 +118,7 @@ def test_a_row_of_one_entry_is_exact(name):
 # ---------------------------------------------------------------------------------------------------------------- reproducible
 @pytest.mark.parametrize("name", case.case_names("twice-"))
 def test_two_runs_are_bit_equal(name):
-    c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    for p, q in zip(*runs):
-        assert torch.equal(p, q)
-    c.price(*runs[0])
+    two_runs_bit_equal(case.cases()[name], _device_run)
 
 
 # ------------------------------------------------------------------------------------------------------------------ composition
@@ -171,7 +139,7 @@ def test_edge_dot(name):
     import pygat_amd as pg
     c = case.cases()[name]
     pattern = _pattern(c)
-    qd, kd = _leaves(c.q, c.k)
+    qd, kd = to_leaves(c.leaves)
     u = pg.edge_dot(pattern, qd, kd, c.fed_scale)
     assert u.dtype == torch.float32 and u.shape == c.G.shape and u.requires_grad
     c.price(u.detach(), *torch.autograd.grad(u, [qd, kd], c.G.float().to(DEV)))
@@ -194,30 +162,8 @@ def test_in_a_module(name):
 
 
 # ---------------------------------------------------------------------------------------------------------- launches and refusals
-class _Spy:
-    def __init__(self, real, seen):
-        self._real, self._seen = real, seen
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if not name.startswith("pygat_") or name == "pygat_last_error" or name.endswith("_workspace_bytes"):
-            return fn
-
-        def wrapped(*args):
-            self._seen.append(name)
-            return fn(*args)
-        return wrapped
-
-
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):    # (package attributes of these names are functions)
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
-
-
-FWD, ROWS, SPMM, SDDMM = "pygat_dot_attn_forward", "pygat_dot_attn_backward_rows", "pygat_spmm_forward", "pygat_spmm_grad_values"
+    return spied(monkeypatch, "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def test_only_the_needed_launches(monkeypatch):
@@ -332,11 +278,5 @@ def test_zero_padded_columns_change_nothing():
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_new_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K19) == 40
-    for name in K19:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k19_fwd_row_l3v1", b"k19_fwd_row_l32v2", b"k19_fwd_row_l64v5", b"k19_mid_row_l8v1", b"k19_fwd_row_l8v1x", b"k19_"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K19, (b"k19_fwd_row_l3v1", b"k19_fwd_row_l32v2", b"k19_fwd_row_l64v5", b"k19_mid_row_l8v1", b"k19_fwd_row_l8v1x", b"k19_"))

@@ -6,14 +6,12 @@ op on the widened tables -- a lane's chunk is the same 4 row elements, loaded as
 the load is the float32 kernels' -- so those tests carry no tolerance.  Beside it the op is priced against the fp64 ground truth on the
 widened tables by the one rule of parity.py, so that this file does not lean on the float32 kernels alone.  The seeded cases live in
 dot_attention_bf16_case.py and are rehearsed on the CPU by tests/test_dot_attention_bf16_abi.py; no case is built here."""
-import ctypes as C
 
 import pytest
 import torch
 
 import dot_attention_bf16_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _indices_pattern, _pattern, _spied, FWD  # noqa: F401
+from pattern_device import DEV, FWD, _indices_pattern, _pattern, degree, no_scratch, spied  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,8 +41,8 @@ def _both(c, pattern=None):
     return _attend(pattern, c, q, k16, v16, bias), _attend(pattern, c, q, k16.float(), v16.float(), bias)
 
 
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
+def _spied(monkeypatch):
+    return spied(monkeypatch, "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 # ---------------------------------------------------------------------------------------------------------------- bit equality
@@ -149,7 +147,7 @@ def test_an_empty_pattern_gives_zeros_without_a_launch(monkeypatch):
 def test_a_row_of_one_entry_is_its_v_row(name):
     c = case.cases()[name]
     out = _attend(_pattern(c), c, *_inputs(c))
-    single = _degree(c)[c.row] == 1
+    single = degree(c)[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= (12 if "lonely" in name else 1)
     assert torch.equal(out[rows], c.v16.to(DEV)[cols].float()), "out_i == v16[j].float() bit for bit"
@@ -171,7 +169,7 @@ def test_a_masked_entry_contributes_exact_zeros(name):
     kept = _indices_pattern(c.row[keep], c.col[keep], c.shape)
     with torch.no_grad():
         want = pg.dot_attention(kept, q, k16, v16, c.fed_scale, bias[keep.to(DEV)].contiguous())
-    short = (_degree(c) <= 512).to(DEV)
+    short = (degree(c) <= 512).to(DEV)
     assert int(short.sum()) > 0.9 * c.shape[0]
     assert torch.equal(out[short], want[short]), name
     some = torch.bincount(c.row[c.masked], minlength=c.shape[0]).to(DEV) > 0
@@ -229,12 +227,6 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_bf16_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K19H) == 40
-    for name in K19H:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k19h_bwd_row_l8v1", b"k19hb_bwd_long_l8v1", b"k19h_fwd_row_l3v1", b"k19h_fwd_row_l32v2", b"k19hb_fwd_row_l64v5",
-                b"k19h_fwd_row_l8v1x", b"k19h_", b"k19h", b"k19hb_", b"k19hc_fwd_row_l8v1", b"k19hfwd_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K19H, (b"k19h_bwd_row_l8v1", b"k19hb_bwd_long_l8v1", b"k19h_fwd_row_l3v1", b"k19h_fwd_row_l32v2", b"k19hb_fwd_row_l64v5",
+                      b"k19h_fwd_row_l8v1x", b"k19h_", b"k19h", b"k19hb_", b"k19hc_fwd_row_l8v1", b"k19hfwd_row_l8v1"))

@@ -4,25 +4,18 @@ and db, the gradient of the bias.
 Ground truth, inputs and the seeded cases live in dot_attention_bias_case.py: torch autograd in fp64 on the CPU, loss L = <out, G>,
 pricing by parity.check_autograd unchanged (out by close_fwd, every gradient by close_grad).  Every case is rehearsed on the CPU, the
 fp32 ground-truth run standing in for the device, by tests/test_dot_attention_bias_abi.py and passes there; no case is built here."""
-import ctypes as C
 import itertools
 
 import pytest
 import torch
 
 import dot_attention_bias_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern, _spied, FWD, ROWS, SPMM  # noqa: F401
+from pattern_device import BFWD, BROWS, DEV, FWD, ROWS, SPMM, _pattern, degree, device_run, no_scratch, spied, two_runs_bit_equal
 
 pytestmark = pytest.mark.gpu
 
-BFWD, BROWS = "pygat_dot_attn_bias_forward", "pygat_dot_attn_bias_backward_rows"
 K19B = [f"k19b_{d}_{kind}_l{l}v{v}" for d in ("fwd", "bwd") for kind in ("long", "row")
         for l, v in ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))]
-
-
-def _leaves(*tensors):
-    return [t.float().to(DEV).requires_grad_(True) for t in tensors]
 
 
 def _fused(pattern, c):
@@ -37,12 +30,19 @@ def _from_parts(pattern, c):
     return lambda q, k, v, b: pg.spmm(pattern, pg.edge_softmax(pattern, pg.edge_dot(pattern, q, k, c.scale) + b), v)
 
 
+def _unbiased(pattern, c):
+    """The op without a bias, on a case of dot_attention_case."""
+    import pygat_amd as pg
+    return lambda q, k, v: pg.dot_attention(pattern, q, k, v) if c.fed_scale is None else pg.dot_attention(pattern, q, k, v, c.fed_scale)
+
+
 def _device_run(pattern, c, fn=None):
     """-> (out, dq, dk, dv, db) on the device."""
-    leaves = _leaves(c.q, c.k, c.v, c.bias)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == leaves[0].shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused)
+
+
+def _spied(monkeypatch):
+    return spied(monkeypatch, "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def _run_case(name):
@@ -50,10 +50,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     c.price(*res)
     return (c,) + res
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -78,7 +74,7 @@ def test_unsorted_entries_take_their_own_bias(name):
     (row, col) pairs whose two entries carry different biases."""
     c, out, dq, dk, dv, db = _run_case(name)
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     if name.startswith("rect-"):
         assert int(no_row.sum()) == 100
         assert float(out[no_row].abs().max()) == 0.0 and float(dq[no_row].abs().max()) == 0.0
@@ -95,7 +91,7 @@ def test_a_masked_entry_is_exactly_out(name):
 @pytest.mark.parametrize("name", case.case_names("lonely-"))
 def test_a_row_of_one_entry_is_exact(name):
     c, out, dq, dk, dv, db = _run_case(name)
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -109,9 +105,8 @@ def test_a_row_of_one_entry_is_exact(name):
 def test_a_bias_of_zeros_changes_no_bit(name):
     """out, dq, dk and dv under a bias of zeros are bit-equal to the op without a bias on the same inputs: the biased kernels take the
     difference score - (m - bias) where the unbiased ones take score - m, and form ds as the unbiased ones do."""
-    import test_gpu_dot_attention as plain
     c, out, dq, dk, dv, db = _run_case(name)
-    want = plain._device_run(_pattern(c), c.inner)
+    want = device_run(_pattern(c), c.inner, _unbiased)
     for got, ref, what in zip((out, dq, dk, dv), want, ("out", "dq", "dk", "dv")):
         assert torch.equal(got, ref), (name, what)
 
@@ -129,13 +124,7 @@ def test_a_shift_per_row_leaves_the_row_sums_of_db_at_zero():
 
 @pytest.mark.parametrize("name", case.case_names("twice-"))
 def test_two_runs_are_bit_equal(name):
-    c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    assert len(runs[0]) == 5
-    for p, q in zip(*runs):
-        assert torch.equal(p, q)
-    c.price(*runs[0])
+    assert len(two_runs_bit_equal(case.cases()[name], _device_run)) == 5
 
 
 @pytest.mark.parametrize("name", case.case_names("composed-"))
@@ -255,12 +244,6 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_biased_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K19B) == 40
-    for name in K19B:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k19b_fwd_row_l3v1", b"k19b_fwd_row_l32v2", b"k19b_fwd_row_l64v5", b"k19b_mid_row_l8v1", b"k19b_fwd_row_l8v1x", b"k19b_",
-                b"k19b", b"k19bfwd_row_l8v1", b"k19c_fwd_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K19B, (b"k19b_fwd_row_l3v1", b"k19b_fwd_row_l32v2", b"k19b_fwd_row_l64v5", b"k19b_mid_row_l8v1", b"k19b_fwd_row_l8v1x",
+                      b"k19b_", b"k19b", b"k19bfwd_row_l8v1", b"k19c_fwd_row_l8v1"))

@@ -5,30 +5,20 @@ Ground truth, the mask and the seeded cases live in dot_attention_dropout_case.p
 tests/philox_ref.py, loss L = <out, G>, pricing by parity.check_autograd unchanged (out by close_fwd, every gradient by close_grad).
 Every case is rehearsed on the CPU, the fp32 ground-truth run standing in for the device, by tests/test_dot_attention_dropout_abi.py
 and passes there; no case is built here."""
-import ctypes as C
 import itertools
 
 import pytest
 import torch
 
 import dot_attention_dropout_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern, _spied, FWD, ROWS, SPMM  # noqa: F401
-from test_gpu_dot_attention_bias import BFWD, BROWS
+from pattern_device import BFWD, BROWS, DEV, FWD, ROWS, SPMM, _pattern, _seed, device_run, no_scratch, spied  # noqa: F401
+from pattern_device import leaves as _leaves
 
 pytestmark = pytest.mark.gpu
 
 DFWD, DROWS, MASK = "pygat_dot_attn_dropout_forward", "pygat_dot_attn_dropout_backward_rows", "pygat_dropout_mask"
 SHAPES = ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))
 K19D = [f"{fam}_{d}_{kind}_l{l}v{v}" for fam in ("k19d", "k19db") for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES]
-
-
-def _seed(value):
-    return torch.tensor([value], dtype=torch.int64, device=DEV)
-
-
-def _leaves(c):
-    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
 
 
 def _fused(pattern, c, seed=None):
@@ -50,10 +40,11 @@ def _from_parts(pattern, c, seed=None):
 
 def _device_run(pattern, c, fn=None, seed=None):
     """-> (out, dq, dk, dv[, db]) on the device."""
-    leaves = _leaves(c)
-    out = (fn or _fused)(pattern, c, seed)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == leaves[0].shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused, seed=seed)
+
+
+def _spied(monkeypatch):
+    return spied(monkeypatch, "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def _run_case(name):
@@ -335,12 +326,6 @@ def test_in_a_module(name):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_dropout_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K19D) == 80
-    for name in K19D:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k19d_fwd_row_l3v1", b"k19d_fwd_row_l32v2", b"k19db_fwd_row_l64v5", b"k19d_mid_row_l8v1", b"k19db_fwd_row_l8v1x", b"k19d_",
-                b"k19d", b"k19dfwd_row_l8v1", b"k19dh_fwd_row_l8v1", b"k19dbb_fwd_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K19D, (b"k19d_fwd_row_l3v1", b"k19d_fwd_row_l32v2", b"k19db_fwd_row_l64v5", b"k19d_mid_row_l8v1", b"k19db_fwd_row_l8v1x", b"k19d_",
+                      b"k19d", b"k19dfwd_row_l8v1", b"k19dh_fwd_row_l8v1", b"k19dbb_fwd_row_l8v1"))

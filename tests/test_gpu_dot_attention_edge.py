@@ -4,7 +4,6 @@ on the key and the value side -- out, dq, dk, dv, de and, with a bias, db.
 Ground truth, inputs and the seeded cases live in dot_attention_edge_case.py: torch autograd in fp64 on the CPU, loss L = <out, G>,
 pricing by parity.check_autograd unchanged (out by close_fwd, every gradient by close_grad).  Every case is rehearsed on the CPU, the
 fp32 ground-truth run standing in for the device, by tests/test_dot_attention_edge_abi.py and passes there; no case is built here."""
-import ctypes as C
 import importlib
 import itertools
 
@@ -12,18 +11,13 @@ import pytest
 import torch
 
 import dot_attention_edge_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern, _spied, FWD, ROWS, SPMM  # noqa: F401
+from pattern_device import DEV, FWD, ROWS, SPMM, _pattern, degree, device_run, no_scratch, spied, to_leaves, two_runs_bit_equal  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 EFWD, EROWS = "pygat_dot_attn_edge_forward", "pygat_dot_attn_edge_backward_rows"
 K19E = [f"k19{p}_{d}_{kind}_l{l}v{v}" for p in ("e", "eb") for d in ("fwd", "bwd") for kind in ("long", "row")
         for l, v in ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 3), (64, 4))]
-
-
-def _leaves(*tensors):
-    return [t.float().to(DEV).requires_grad_(True) for t in tensors]
 
 
 def _fused(pattern, c):
@@ -45,10 +39,11 @@ def _from_parts(pattern, c):
 
 def _device_run(pattern, c, fn=None):
     """-> (out, dq, dk, dv, de[, db]) on the device."""
-    leaves = _leaves(*c.leaves)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == leaves[0].shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused)
+
+
+def _spied(monkeypatch):
+    return spied(monkeypatch, "pygat_amd.dot_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def _run_case(name):
@@ -56,10 +51,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     c.price(*res)
     return (c,) + res
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -93,7 +84,7 @@ def test_unsorted_entries_take_their_own_row_of_e(name):
     repeated (row, col) pairs whose two entries carry different rows of e and get different rows of de."""
     c, out, dq, dk, dv, de = _run_case(name)
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     if name.startswith("rect-"):
         assert int(no_row.sum()) == 100
         assert float(out[no_row].abs().max()) == 0.0 and float(dq[no_row].abs().max()) == 0.0
@@ -105,7 +96,7 @@ def test_unsorted_entries_take_their_own_row_of_e(name):
 @pytest.mark.parametrize("name", case.case_names("lonely-"))
 def test_a_row_of_one_entry_is_exact(name):
     c, out, dq, dk, dv, de = _run_case(name)
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -123,7 +114,7 @@ def test_e_of_zeros_gives_the_values_of_dot_attention(name):
     import pygat_amd as pg
     c, out, *grads = _run_case(name)
     pattern = _pattern(c)
-    leaves = _leaves(*([c.q, c.k, c.v] + ([] if c.bias is None else [c.bias])))
+    leaves = to_leaves([c.q, c.k, c.v] + ([] if c.bias is None else [c.bias]))
     want = pg.dot_attention(pattern, *leaves[:3], c.fed_scale, leaves[3] if c.bias is not None else None)
     wgrads = torch.autograd.grad(want, leaves, c.G.float().to(DEV))
     got = [out] + grads[:3] + grads[4:]
@@ -137,12 +128,7 @@ def test_e_of_zeros_gives_the_values_of_dot_attention(name):
 @pytest.mark.parametrize("name", case.case_names("twice-"))
 def test_two_runs_are_bit_equal(name):
     c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    assert len(runs[0]) == 1 + len(c.names)
-    for p, q in zip(*runs):
-        assert torch.equal(p, q)
-    c.price(*runs[0])
+    assert len(two_runs_bit_equal(c, _device_run)) == 1 + len(c.names)
 
 
 @pytest.mark.parametrize("name", case.case_names("composed-"))
@@ -175,7 +161,7 @@ def test_a_strided_e_gives_the_result_of_its_copy():
     import pygat_amd as pg
     c = case.cases()["lanes-asym-8x16-indices"]
     pattern = _pattern(c)
-    q, k, v, e = _leaves(*c.leaves)
+    q, k, v, e = to_leaves(c.leaves)
     G = c.G.float().to(DEV)
     want = pg.dot_attention_edge(pattern, q, k, v, e)
     wgrads = torch.autograd.grad(want, [q, k, v, e], G)
@@ -303,13 +289,7 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_edge_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K19E) == 80 and len(set(K19E)) == 80
-    for name in K19E:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k19e_fwd_row_l3v1", b"k19e_fwd_row_l32v2", b"k19e_fwd_row_l64v5", b"k19e_mid_row_l8v1", b"k19e_fwd_row_l8v1x", b"k19e_",
-                b"k19e", b"k19eb_", b"k19efwd_row_l8v1", b"k19ee_fwd_row_l8v1", b"k19eh_fwd_row_l8v1", b"k19ed_fwd_row_l8v1",
-                b"k19be_fwd_row_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K19E, (b"k19e_fwd_row_l3v1", b"k19e_fwd_row_l32v2", b"k19e_fwd_row_l64v5", b"k19e_mid_row_l8v1", b"k19e_fwd_row_l8v1x", b"k19e_",
+                      b"k19e", b"k19eb_", b"k19efwd_row_l8v1", b"k19ee_fwd_row_l8v1", b"k19eh_fwd_row_l8v1", b"k19ed_fwd_row_l8v1",
+                      b"k19be_fwd_row_l8v1"))

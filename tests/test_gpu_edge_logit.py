@@ -18,7 +18,8 @@ from alpha_grad_case import level_ref as plain_ref
 from alpha_grad_case import src_of
 from edge_logit_case import edge_logits, kink_count, level_ref
 from long_row_cases import nine_hubs, three_chunk_hub
-from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _graph, _hub_graph, _params
+from pattern_device import DEV, _graph
+from pattern_graphs import SHAPES, SID, SLOPE, _asym_graph, _hub_graph, _params
 
 pytestmark = pytest.mark.gpu
 

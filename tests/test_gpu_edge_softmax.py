@@ -13,7 +13,8 @@ import torch
 import edge_softmax_case as case
 import parity
 from edge_softmax_case import edge_softmax_ref
-from test_gpu_attention import DEV, SLOPE, _graph
+from pattern_device import DEV, _graph
+from pattern_graphs import SLOPE
 
 pytestmark = pytest.mark.gpu
 

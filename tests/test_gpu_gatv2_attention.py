@@ -6,7 +6,6 @@ by parity.check_autograd unchanged (out by close_fwd, every gradient by close_gr
 seeded case is rehearsed on the CPU, the fp32 ground-truth run standing in for the device, by tests/test_gatv2_attention_abi.py and
 passes there; no case is built here."""
 import copy
-import ctypes as C
 import importlib
 import itertools
 
@@ -14,8 +13,8 @@ import pytest
 import torch
 
 import gatv2_attention_case as case
-from test_gpu_attention import DEV, _graph
-from test_gpu_dot_attention import _Spy, _pattern
+from pattern_device import DEV, _graph, _pattern, degree, device_run, no_scratch, spied, two_runs_bit_equal
+from pattern_device import leaves as _leaves
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +22,6 @@ SHAPES = ((1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (6
 K21 = ([f"{prefix}_{d}_{kind}_l{l}v{v}" for prefix in ("k21", "k21s") for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES]
        + [f"k21_col_{kind}_l{l}v{v}" for kind in ("long", "row") for l, v in SHAPES] + ["k21_da_stage", "k21_da_final"])
 FWD, ROWS, COLS, SPMM = "pygat_v2_attn_forward", "pygat_v2_attn_backward_rows", "pygat_v2_attn_backward_cols", "pygat_spmm_forward"
-
-
-def _leaves(c):
-    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
 
 
 def _fused(pattern, c):
@@ -46,10 +41,7 @@ def _from_parts(pattern, c):
 
 def _device_run(pattern, c, fn=None, leaves=None):
     """-> (out, dx_dst, dx_src, da[, dv]) on the device."""
-    leaves = leaves or _leaves(c)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == c.G.shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused, leaves)
 
 
 def _run_case(name):
@@ -57,10 +49,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     c.price_all(*res)
     return (c,) + res
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -87,7 +75,7 @@ def test_rectangular_with_empty_rows_and_columns(name):
     res = _run_case(name)
     c, out, dd, ds = res[:4]
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     no_col = (torch.bincount(c.col, minlength=c.shape[1]) == 0).to(DEV)
     assert int(no_row.sum()) == 100 and int(no_col.sum()) == 125
     for t in (out[no_row], dd[no_row], ds[no_col]) + ((res[5][no_col],) if not c.shared else ()):
@@ -114,7 +102,7 @@ def test_repeated_pairs_are_separate_entries(name):
 @pytest.mark.parametrize("name", case.case_names("lonely-"))
 def test_a_row_of_one_entry_is_exact(name):
     c, out, dd = _run_case(name)[:3]
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -151,12 +139,7 @@ def test_shared_against_a_copy_of_x_src(name):
 def test_two_runs_are_bit_equal(name):
     """out and every gradient, da -- the staged reduce of per-wave records -- included; a hub case and long-column cases."""
     c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    assert len(runs[0]) == 1 + len(c.names)
-    for p, q, what in zip(*runs, ["out"] + c.names):
-        assert torch.equal(p, q), what
-    c.price(*runs[0])
+    assert len(two_runs_bit_equal(c, _device_run)) == 1 + len(c.names)
 
 
 # ------------------------------------------------------------------------------------------------------------------ composition
@@ -212,11 +195,7 @@ def test_a_bipartite_gatv2_layer(name):
 
 # ---------------------------------------------------------------------------------------------------------- launches and refusals
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.gatv2_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
+    return spied(monkeypatch, "pygat_amd.gatv2_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def test_only_the_needed_launches(monkeypatch):
@@ -322,13 +301,7 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_no_kernel_uses_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K21) == 102
-    for name in K21:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k21_fwd_row_l3v1", b"k21_fwd_row_l32v2", b"k21_fwd_row_l64v5", b"k21_mid_row_l8v1", b"k21_fwd_row_l8v1x", b"k21_",
-                b"k21", b"k21fwd_row_l8v1", b"k21b_fwd_row_l8v1", b"k21s_col_row_l8v1", b"k21s_bwd_row_l0v1", b"k21_da_stage_",
-                b"k21s_da_final", b"k21_col_mid_l8v1"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K21, (b"k21_fwd_row_l3v1", b"k21_fwd_row_l32v2", b"k21_fwd_row_l64v5", b"k21_mid_row_l8v1", b"k21_fwd_row_l8v1x", b"k21_",
+                     b"k21", b"k21fwd_row_l8v1", b"k21b_fwd_row_l8v1", b"k21s_col_row_l8v1", b"k21s_bwd_row_l0v1", b"k21_da_stage_",
+                     b"k21s_da_final", b"k21_col_mid_l8v1"))

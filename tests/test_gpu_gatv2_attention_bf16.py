@@ -7,15 +7,13 @@ same 4 row elements, loaded as 8 bytes and widened in registers, and everything 
 carry no tolerance.  Beside it the ops are priced against the fp64 ground truth on the widened tables by the one rule of parity.py, so
 that this file does not lean on the float32 kernels alone.  The seeded cases live in gatv2_attention_bf16_case.py ("plain-..." and
 "edge-...") and are rehearsed on the CPU by tests/test_gatv2_attention_bf16_abi.py; no case is built here."""
-import ctypes as C
 import importlib
 
 import pytest
 import torch
 
 import gatv2_attention_bf16_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern
+from pattern_device import DEV, _graph, _pattern, degree, no_scratch, spied
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +24,7 @@ K21H = [f"{prefix}_fwd_{kind}_l{l}v{v}" for prefix in ("k21h", "k21hs", "k21he",
 
 
 def _spied(monkeypatch):
-    seen = []
-    for mod in ("pygat_amd.gatv2_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax"):    # (package attributes of these names are functions)
-        m = importlib.import_module(mod)
-        monkeypatch.setattr(m, "lib", _Spy(m.lib, seen))
-    return seen
+    return spied(monkeypatch, "pygat_amd.gatv2_attention", "pygat_amd.spmm", "pygat_amd.edge_softmax")
 
 
 def _inputs(c):
@@ -61,10 +55,6 @@ def _both(c, pattern=None):
     pattern = pattern or _pattern(c)
     tensors = _inputs(c)
     return _attend(pattern, c, *tensors), _attend(pattern, c, *_widened(tensors))
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ---------------------------------------------------------------------------------------------------------------- bit equality
@@ -212,7 +202,7 @@ def test_an_empty_pattern_gives_zeros_without_a_launch(monkeypatch):
 def test_a_row_of_one_entry_is_its_value_row(name):
     c = case.cases()[name]
     out = _attend(_pattern(c), c, *_inputs(c))
-    single = _degree(c)[c.row] == 1
+    single = degree(c)[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= (12 if "lonely" in name else 1)
     value = (c.x_src16 if c.shared else c.v16).to(DEV)
@@ -225,10 +215,10 @@ def test_a_sampled_block_with_gathered_bf16_rows():
     edge features of the whole graph by blk.edge_ids, bit-equal to the float32 ops on the widened gathers."""
     import pygat_amd as pg
     import sample_case
-    from test_gpu_sample import graph, seed_of
     t = sample_case.TWO_HOP
-    g = graph(t["graph"])
-    blocks = pg.sample_blocks(g, torch.as_tensor(sample_case.two_hop_seeds()).to(DEV), list(t["fanouts"]), seed=seed_of(t["seed"]))
+    g = _graph(*sample_case.graphs()[t["graph"]])
+    seed = torch.tensor([t["seed"]], dtype=torch.int64, device=DEV)
+    blocks = pg.sample_blocks(g, torch.as_tensor(sample_case.two_hop_seeds()).to(DEV), list(t["fanouts"]), seed=seed)
     gen = torch.Generator(device=DEV).manual_seed(11)
     H, F = 4, 16
     x = torch.randn(g.n, H, F, device=DEV, generator=gen)
@@ -311,14 +301,8 @@ def test_refusals(monkeypatch):
 
 # -------------------------------------------------------------------------------------------------------------------- footprint
 def test_bf16_kernels_have_no_scratch():
-    from pygat_amd._lib import lib
-    regs, scratch = C.c_int(-1), C.c_int(-1)
     assert len(K21H) == 80
-    for name in K21H:
-        assert lib.pygat_kernel_footprint(name.encode(), C.byref(regs), C.byref(scratch)) == 0, (name, lib.pygat_last_error())
-        assert scratch.value == 0 and regs.value > 0, (name, regs.value, scratch.value)
-    for bad in (b"k21h_bwd_row_l8v1", b"k21hs_bwd_long_l8v1", b"k21h_col_row_l8v1", b"k21he_col_long_l8v1", b"k21hes_bwd_row_l8v1",
-                b"k21hd_fwd_row_l8v1", b"k21hds_fwd_row_l8v1", b"k21h_fwd_row_l3v1", b"k21h_fwd_row_l32v2", b"k21hs_fwd_row_l64v5",
-                b"k21h_fwd_row_l8v1x", b"k21h_", b"k21h", b"k21hes_", b"k21hse_fwd_row_l8v1", b"k21hfwd_row_l8v1", b"k21b_fwd_row_l8v1",
-                b"k21hb_fwd_row_l8v1", b"k20h_bwd_row_l8v1", b"k21h_da_stage"):
-        assert lib.pygat_kernel_footprint(bad, C.byref(regs), C.byref(scratch)) == -1, bad
+    no_scratch(K21H, (b"k21h_bwd_row_l8v1", b"k21hs_bwd_long_l8v1", b"k21h_col_row_l8v1", b"k21he_col_long_l8v1", b"k21hes_bwd_row_l8v1",
+                      b"k21hd_fwd_row_l8v1", b"k21hds_fwd_row_l8v1", b"k21h_fwd_row_l3v1", b"k21h_fwd_row_l32v2", b"k21hs_fwd_row_l64v5",
+                      b"k21h_fwd_row_l8v1x", b"k21h_", b"k21h", b"k21hes_", b"k21hse_fwd_row_l8v1", b"k21hfwd_row_l8v1", b"k21b_fwd_row_l8v1",
+                      b"k21hb_fwd_row_l8v1", b"k20h_bwd_row_l8v1", b"k21h_da_stage"))

@@ -15,8 +15,8 @@ import pytest
 import torch
 
 import gatv2_attention_edge_case as case
-from test_gpu_attention import DEV
-from test_gpu_dot_attention import _Spy, _pattern
+from pattern_device import DEV, _Spy, _pattern, degree, device_run, two_runs_bit_equal
+from pattern_device import leaves as _leaves
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,6 @@ K21E = ([f"k21e_{d}_{kind}_l{l}v{v}" for d in ("fwd", "bwd", "col") for kind in 
         + [f"k21es_{d}_{kind}_l{l}v{v}" for d in ("fwd", "bwd") for kind in ("long", "row") for l, v in SHAPES])
 FWD, ROWS, COLS = "pygat_v2_attn_edge_forward", "pygat_v2_attn_edge_backward_rows", "pygat_v2_attn_edge_backward_cols"
 SPMM = "pygat_spmm_forward"
-
-
-def _leaves(c):
-    return [t.float().to(DEV).requires_grad_(True) for t in c.leaves]
 
 
 def _fused(pattern, c):
@@ -50,10 +46,7 @@ def _from_parts(pattern, c):
 
 def _device_run(pattern, c, fn=None, leaves=None):
     """-> (out, dx_dst, dx_src, da, [dv,] de) on the device."""
-    leaves = leaves or _leaves(c)
-    out = (fn or _fused)(pattern, c)(*leaves)
-    assert out.dtype == torch.float32 and out.shape == c.G.shape and out.requires_grad
-    return (out.detach(),) + torch.autograd.grad(out, leaves, c.G.float().to(DEV))
+    return device_run(pattern, c, fn or _fused, leaves)
 
 
 def _run_case(name):
@@ -61,10 +54,6 @@ def _run_case(name):
     res = _device_run(_pattern(c), c)
     c.price_all(*res)
     return (c,) + res
-
-
-def _degree(c):
-    return torch.bincount(c.row, minlength=c.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ lane shapes
@@ -83,7 +72,7 @@ def test_long_rows_and_long_columns(name):
     entry of a long row is written by the piece kernel: every row of it is priced."""
     c, res = (lambda r: (r[0], r[1:]))(_run_case(name))
     de = res[-1]
-    long_rows = (_degree(c) > 512)[c.row].to(DEV)
+    long_rows = (degree(c) > 512)[c.row].to(DEV)
     assert int(long_rows.sum()) > 512 and bool((de[long_rows].abs().amax(dim=(1, 2)) > 0.0).all()), "no row of de is left unwritten"
 
 
@@ -95,7 +84,7 @@ def test_rectangular_with_empty_rows_and_columns(name):
     res = _run_case(name)
     c, out, dd, ds = res[:4]
     assert bool((c.row[1:] < c.row[:-1]).any()), "the entries are unsorted"
-    no_row = (_degree(c) == 0).to(DEV)
+    no_row = (degree(c) == 0).to(DEV)
     no_col = (torch.bincount(c.col, minlength=c.shape[1]) == 0).to(DEV)
     assert int(no_row.sum()) == 100 and int(no_col.sum()) == 125
     for t in (out[no_row], dd[no_row], ds[no_col]) + ((res[5][no_col],) if not c.shared else ()):
@@ -125,7 +114,7 @@ def test_repeated_pairs_are_separate_entries(name):
 def test_a_row_of_one_entry_is_exact(name):
     res = _run_case(name)
     c, out, dd, de = res[0], res[1], res[2], res[-1]
-    deg = _degree(c)
+    deg = degree(c)
     single = deg[c.row] == 1
     rows, cols = c.row[single].to(DEV), c.col[single].to(DEV)                      # the one entry (i, j) of every such row
     assert rows.numel() >= 12
@@ -169,12 +158,7 @@ def test_the_slope_at_the_kink():
 def test_two_runs_are_bit_equal(name):
     """out and every gradient, de and da -- the staged reduce of per-wave records -- included; a hub case and long-column cases."""
     c = case.cases()[name]
-    pattern = _pattern(c)
-    runs = [_device_run(pattern, c) for _ in range(2)]
-    assert len(runs[0]) == 1 + len(c.names)
-    for p, q, what in zip(*runs, ["out"] + c.names):
-        assert torch.equal(p, q), what
-    c.price(*runs[0])
+    assert len(two_runs_bit_equal(c, _device_run)) == 1 + len(c.names)
 
 
 @pytest.mark.parametrize("name", case.case_names("strided-"))

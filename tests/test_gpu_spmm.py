@@ -9,19 +9,17 @@ of `_check`) and passes there.  The device and both ground-truth runs are fed th
 import ctypes as C
 import importlib
 
-import numpy as np
 import pytest
 import torch
 
 import parity
 from alpha_grad_case import kink_count, level_ref
 from long_row_cases import nine_hubs, three_chunk_hub
+from pattern_device import DEV, _graph
+from pattern_graphs import COMPOSE_SEED, SHAPES, SID, SLOPE, _asym_graph, _hub_graph, _params, _rect_coo, _repeat_coo
 from spmm_case import coo_of, f32, normal, softmax_values, spmm_ref
-from test_gpu_attention import DEV, SHAPES, SID, SLOPE, _asym_graph, _graph, _hub_graph, _params
 
 pytestmark = pytest.mark.gpu
-
-COMPOSE_SEED = 816      # _params seed of the composition case: no logit of its fp64 run lies in the LeakyReLU kink band
 
 
 def _inputs(row, n_rows, n_cols, H, F, seed, heads=True, values="softmax"):
@@ -83,33 +81,6 @@ def _asym_coo():
 def _big_hub_coo():
     rowptr, col = three_chunk_hub()
     return coo_of(rowptr, col) + (len(rowptr) - 1,)
-
-
-def _rect_coo(seed=12):
-    """(300, 500): every third row and every fourth column without entries; unsorted, no repeats."""
-    rng = np.random.default_rng(seed)
-    rows, cols = np.setdiff1d(np.arange(300), np.arange(0, 300, 3)), np.setdiff1d(np.arange(500), np.arange(0, 500, 4))
-    key = np.unique(rng.choice(rows, 4000).astype(np.int64) * 500 + rng.choice(cols, 4000))
-    key = key[rng.permutation(len(key))]
-    return torch.as_tensor(key // 500), torch.as_tensor(key % 500)
-
-
-def _repeat_coo(seed=13):
-    """The asymmetric pattern, 5 % of its entries duplicated, shuffled -> (row, col, N, [(k, k')] positions of repeated pairs)."""
-    row, col, N = _asym_coo()
-    rng = np.random.default_rng(seed)
-    E = row.numel()
-    dup = rng.choice(E, E // 20, replace=False)
-    order = rng.permutation(E + len(dup))
-    src = np.concatenate([np.arange(E), dup])[order]              # original entry of every new position
-    pos, pairs = {}, []
-    for k, s in enumerate(src):
-        s = int(s)
-        if s in pos:
-            pairs.append((pos[s], k))
-        pos[s] = k
-    assert len(pairs) == len(dup)
-    return row[src], col[src], N, torch.as_tensor(pairs)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- drop-in

@@ -9,32 +9,19 @@ import re
 import pytest
 import torch
 
+from abi_support import P, call, lib, msg as _msg  # noqa: F401
+
 NEW = ("pygat_find_edges", "pygat_draw_negatives")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _find(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_pairs=8, row=P, colq=P, pos=P, info=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_find_edges(*a.values(), None)
+    return call(L, "pygat_find_edges", a, **kw)
 
 
 def _draw(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_src=8, src=P, num_neg=5, exclude_self=1, seed=P, hop=0, neg=P, info=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_draw_negatives(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
+    return call(L, "pygat_draw_negatives", a, **kw)
 
 
 def test_additive_under_abi_16(lib):

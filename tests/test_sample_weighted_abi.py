@@ -10,26 +10,15 @@ import re
 import pytest
 import torch
 
+from abi_support import P, call, lib, msg as _msg  # noqa: F401
+
 NAME = "pygat_weighted_block"
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _block(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_dst=8, dst=P, fanout=5, weight=P, seed=P, hop=0, cap=40, src_cap=48, blk_rowptr=P,
              blk_col=P, edge_rc=P, edge_ids=P, src_nodes=P, info=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_weighted_block(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
+    return call(L, "pygat_weighted_block", a, **kw)
 
 
 def test_additive_under_abi_16(lib):

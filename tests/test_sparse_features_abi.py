@@ -7,15 +7,9 @@ import pytest
 
 import philox_ref as R
 import sparse_features_case as case
+from abi_support import P, lib  # noqa: F401
 
-P = 4096          # a stand-in address, never dereferenced: every call below fails a host check first
 EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 # ---------------------------------------------------------------------------------------------------

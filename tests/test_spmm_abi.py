@@ -6,14 +6,9 @@ import re
 
 import pytest
 
+from abi_support import P, lib, msg as _msg  # noqa: F401
+
 NEW = ("pygat_spmm_workspace_bytes", "pygat_spmm_forward", "pygat_spmm_grad_values")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _fwd(L, **kw):
@@ -26,10 +21,6 @@ def _gv(L, **kw):
     a = dict(nnz=20, edge_rc=P, H=2, F=16, G=P, ldg=32, b=P, ldb=32, dval=P)
     a.update(kw)
     return L.lib.pygat_spmm_grad_values(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
 
 
 def test_additive_under_abi_16(lib):

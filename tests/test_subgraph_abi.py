@@ -9,39 +9,24 @@ import re
 import pytest
 import torch
 
+from abi_support import P, call, lib, msg as _msg  # noqa: F401
+
 NEW = ("pygat_subgraph_workspace_bytes", "pygat_subgraph_count", "pygat_subgraph_fill", "pygat_random_walk")
-P = 4096          # a 16-byte aligned stand-in address (never dereferenced: every call below fails its checks first)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from pygat_amd import _lib
-    return _lib
 
 
 def _count(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_in=8, nodes=P, sub_nodes=P, index=P, sub_rowptr=P, info=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_subgraph_count(*a.values(), None)
+    return call(L, "pygat_subgraph_count", a, **kw)
 
 
 def _fill(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_in=8, n_sub=6, sub_nnz=20, sub_nodes=P, sub_rowptr=P, sub_col=P, edge_rc=P, edge_ids=P, ws=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_subgraph_fill(*a.values(), None)
+    return call(L, "pygat_subgraph_fill", a, **kw)
 
 
 def _walk(L, **kw):
     a = dict(n=100, nnz=500, rowptr=P, col=P, n_walk=8, start=P, length=4, seed=P, hop=0, walks=P, info=P)
-    assert set(kw) <= set(a), kw
-    a.update(kw)
-    return L.lib.pygat_random_walk(*a.values(), None)
-
-
-def _msg(L):
-    return L.lib.pygat_last_error().decode()
+    return call(L, "pygat_random_walk", a, **kw)
 
 
 def test_additive_under_abi_16(lib):
