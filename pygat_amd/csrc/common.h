@@ -93,6 +93,29 @@ __device__ __forceinline__ float dpp_mov(float x) {
   return __int_as_float(v);
 }
 
+// Lane Q (0..3) of every DPP quad handed to all four lanes of the quad: quad_perm [Q,Q,Q,Q] = 0x55 * Q.
+template <int Q>
+__device__ __forceinline__ float quad_bcast(float x) {
+  static_assert(Q >= 0 && Q < 4, "quad_bcast: a quad has lanes 0..3");
+  return dpp_mov<0x55 * Q>(x);
+}
+template <int Q>
+__device__ __forceinline__ int quad_bcast(int x) {
+  static_assert(Q >= 0 && Q < 4, "quad_bcast: a quad has lanes 0..3");
+  return __builtin_amdgcn_update_dpp(0, x, 0x55 * Q, 0xF, 0xF, true);
+}
+// the four int2 / float4 values the lanes of a quad hold, in every lane of it
+__device__ __forceinline__ void quad_spread(int2 mine, int2 (&p)[4]) {
+  p[0] = make_int2(quad_bcast<0>(mine.x), quad_bcast<0>(mine.y));
+  p[1] = make_int2(quad_bcast<1>(mine.x), quad_bcast<1>(mine.y));
+  p[2] = make_int2(quad_bcast<2>(mine.x), quad_bcast<2>(mine.y));
+  p[3] = make_int2(quad_bcast<3>(mine.x), quad_bcast<3>(mine.y));
+}
+template <int Q>
+__device__ __forceinline__ float4 quad_bcast4(float4 x) {
+  return make_float4(quad_bcast<Q>(x.x), quad_bcast<Q>(x.y), quad_bcast<Q>(x.z), quad_bcast<Q>(x.w));
+}
+
 // Sum over aligned groups of G consecutive lanes (G power of two <= 64); every lane
 // of a group ends with the group total.  Steps 1,2 use quad_perm, 4 and 8 use the
 // mirror controls (valid because after the previous steps all lanes of a

@@ -231,6 +231,9 @@ __device__ __forceinline__ void fwd_flush(const FwdArgs& a, const LaneCols<VEC>&
 #ifndef PYGAT_K2_PREFETCH_TRAIN
 #define PYGAT_K2_PREFETCH_TRAIN 1 // edge-record prefetch on the training forward (AUX && FAST, one chunk per lane)
 #endif
+#ifndef PYGAT_K2_QUAD_LOADS
+#define PYGAT_K2_QUAD_LOADS 1     // heads of one DPP quad (LPH == 4), 4 edges per round: lane q of a quad loads edge q's record and s_i, quad_bcast hands them round (0: every lane loads all four)
+#endif
 #ifndef PYGAT_K2_HEADLINE_WAVES
 #define PYGAT_K2_HEADLINE_WAVES 4 // (round 4: 5 waves at 96 VGPRs + 12 bytes of scratch without the prefetch, 1.04 ms; 4 waves at 104
 #endif                            //  VGPRs with it, 1.00 ms -- same box, gpurun_out r4a; the prefetch at 5 waves spills 24 bytes: 1.025)
@@ -283,17 +286,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((AUX && FAS
   RowState<VEC, AUX> st;
   st.reset();
 
-  int2 pn[PREF ? U : 1];
+  // QUAD: the operands of a round that are the same in all lanes of a head -- the edge records, s_i -- are loaded once per
+  // quad instead of once per lane: a head is one DPP quad and a round has four edges, so lane q of the quad loads edge q's
+  // copy (one instruction for the round) and quad_bcast hands the four round.  12 -> 6 vector-memory instructions per round;
+  // the addresses read, the arithmetic and its order are the same.  A quad lies inside one lane group: its lanes are
+  // switched on and off together.
+  constexpr bool QUAD = PYGAT_K2_QUAD_LOADS && LPH == 4 && VEC == 1 && U == 4 && !V2 && FAST;
+  const int ql = lane & 3;
+  int2 pn[PREF ? (QUAD ? 1 : U) : 1];
   if constexpr (PREF) {
+    if constexpr (QUAD) {
+      pn[0] = rc[(e0 + ql < e1) ? e0 + ql : e1 - 1];
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) pn[u] = rc[(e0 + u < e1) ? e0 + u : e1 - 1];
+      for (int u = 0; u < U; ++u) pn[u] = rc[(e0 + u < e1) ? e0 + u : e1 - 1];
+    }
   }
   for (int64_t e = e0; e < e1; e += U) {
     int2 p[U];
+    int2 pq = make_int2(0, 0);   // QUAD: the record of edge e + ql
+    if constexpr (QUAD) {
+      if constexpr (PREF) pq = pn[0];
+      else pq = rc[(e + ql < e1) ? e + ql : e1 - 1];
+      quad_spread(pq, p);
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if constexpr (PREF) p[u] = pn[u];
-      else p[u] = rc[(e + u < e1) ? e + u : e1 - 1];
+      for (int u = 0; u < U; ++u) {
+        if constexpr (PREF) p[u] = pn[u];
+        else p[u] = rc[(e + u < e1) ? e + u : e1 - 1];
+      }
     }
     // All U edge records are ISSUED before the first one is used.  Round 3's build of the headline instantiation had lost
     // this: hipcc sank record 0's first use above the loads of records 1..3 and waited vmcnt(0) for it -- one more dependent
@@ -318,15 +339,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((AUX && FAS
           const float4 hh = make_float4(wi.x + wj.x, wi.y + wj.y, wi.z + wj.z, wi.w + wj.w);
           const float4 ll = make_float4(lrelu(hh.x, a.alpha), lrelu(hh.y, a.alpha), lrelu(hh.z, a.alpha), lrelu(hh.w, a.alpha));
           sv[u][v] = dot4(ll, adst[v]);   // partial of e_ij over this lane's 4 features
+        } else if constexpr (QUAD) {   // (below, once per quad)
         } else if constexpr (FAST) {
           sv[u][v] = a.s[(uint32_t)((uint32_t)p[u].x * (uint32_t)ldh + (uint32_t)lc.head[v])];
         } else {
           sv[u][v] = a.s[(int64_t)p[u].x * ldh + lc.head[v]];
         }
       }
+    float sq = 0.f;   // QUAD: s_i of edge e + ql, this lane's head
+    if constexpr (QUAD) sq = a.s[(uint32_t)((uint32_t)pq.x * (uint32_t)ldh + (uint32_t)lc.head[0])];
     if constexpr (PREF) {   // next round's edge records: in flight together with this round's rows
+      if constexpr (QUAD) {
+        pn[0] = rc[(e + U + ql < e1) ? e + U + ql : e1 - 1];
+      } else {
 #pragma unroll
-      for (int u = 0; u < U; ++u) pn[u] = rc[(e + U + u < e1) ? e + U + u : e1 - 1];
+        for (int u = 0; u < U; ++u) pn[u] = rc[(e + U + u < e1) ? e + U + u : e1 - 1];
+      }
+    }
+    if constexpr (QUAD) {
+      sv[0][0] = quad_bcast<0>(sq); sv[1][0] = quad_bcast<1>(sq); sv[2][0] = quad_bcast<2>(sq); sv[3][0] = quad_bcast<3>(sq);
     }
     // per-head sums over the lanes of a head (all lanes of the group are active here):
     // V1: t_j = Wh_j . a_dst from the row just gathered; V2: the logit e_ij itself

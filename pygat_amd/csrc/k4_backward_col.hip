@@ -142,6 +142,12 @@ __device__ __forceinline__ T pick(const T (&x)[U], int u) {
 #ifndef PYGAT_K4_DA_WAVES
 #define PYGAT_K4_DA_WAVES 4         // minimum waves per SIMD asked of the dense 8 x 16 instantiation that takes da along
 #endif
+#ifndef PYGAT_K4_QUAD_LOADS
+#define PYGAT_K4_QUAD_LOADS 1       // heads of one DPP quad (LPH == 4), 4 edges per round: lane q of a quad loads edge q's record and row record, quad_bcast hands them round (0: every lane loads all four; 1: the dense instantiations, CR > 0; 2: those with run-time strides too)
+#endif
+#ifndef PYGAT_K4_QUAD_PREFETCH
+#define PYGAT_K4_QUAD_PREFETCH 1    // on top of PYGAT_K4_QUAD_LOADS: the next round's edge records (one int2 per lane) fetched a round ahead, as K2 does
+#endif
 #ifndef PYGAT_K4_HEADLINE_WAVES
 #define PYGAT_K4_HEADLINE_WAVES 1   // (experiment: minimum waves per SIMD asked of the CR > 0 instantiation)
 #endif
@@ -175,17 +181,37 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
 #pragma unroll
   for (int v = 0; v < VEC; ++v) { acc[v] = make_float4(0.f, 0.f, 0.f, 0.f); dt[v] = 0.f; }
 
+  // QUAD: the operands of a round that are the same in all lanes of a head -- the edge records and the (s, m, 1/Z, D) record of
+  // the gathered row -- are loaded once per quad instead of once per lane: a head is one DPP quad and a round has four edges,
+  // so lane q of the quad loads edge q's copy (one instruction for the round) and quad_bcast hands the four round.  16 -> 10
+  // vector-memory instructions per round; the addresses read (the row's fifth line among them), the arithmetic and its order
+  // are the same.  A quad lies inside one lane group: its lanes are switched on and off together.
+  // QPREF: with one record per lane, the next round's are fetched a round ahead, as in gat_fwd_kernel.
+  // (The instantiations with run-time strides, CR == 0, take it at PYGAT_K4_QUAD_LOADS=2 only: their 64-bit row addresses
+  // push them from 126 to 130 VGPRs, the fourth wave per SIMD, and 6 heads x 16 measured no gain: DESIGN.md section 8.)
+  constexpr bool QUAD = (PYGAT_K4_QUAD_LOADS >= (CR > 0 ? 1 : 2)) && LPH == 4 && VEC == 1 && U == 4 && !WRITE_DZ && !NARROW;
+  constexpr bool QPREF = QUAD && PYGAT_K4_QUAD_PREFETCH;
+  const int ql = (int)(threadIdx.x & 3);
   int2 pn[NARROW ? U : 1];
   if constexpr (NARROW) {
 #pragma unroll
     for (int u = 0; u < U; ++u) pn[u] = rc[(e0 + u < e1) ? e0 + u : e1 - 1];
+  } else if constexpr (QPREF) {
+    pn[0] = rc[(e0 + ql < e1) ? e0 + ql : e1 - 1];
   }
   for (int64_t e = e0; e < e1; e += U) {
     int2 p[U];  // (j, i): j = this (transposed) row, i = the forward row that attends to j
+    int2 pq = make_int2(0, 0);   // QUAD: the record of edge e + ql
+    if constexpr (QUAD) {
+      if constexpr (QPREF) pq = pn[0];
+      else pq = rc[(e + ql < e1) ? e + ql : e1 - 1];
+      quad_spread(pq, p);
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if constexpr (NARROW) p[u] = pn[u];
-      else p[u] = rc[(e + u < e1) ? e + u : e1 - 1];
+      for (int u = 0; u < U; ++u) {
+        if constexpr (NARROW) p[u] = pn[u];
+        else p[u] = rc[(e + u < e1) ? e + u : e1 - 1];
+      }
     }
     float4 rt[U][VEC], gv[U][VEC], wv[U][VEC];
     float mk[U][VEC];
@@ -199,17 +225,33 @@ __device__ __forceinline__ void col_walk(const ColArgs& a, const int64_t q, floa
           // the price is the gathered line, wherever it lies)
           const uint32_t go = (uint32_t)p[u].y * (uint32_t)RW;
           gv[u][v] = ld4(a.GR + (go + (uint32_t)lc.cofs[v]));
-          rt[u][v] = (PYGAT_DIAG_K4 & 8) ? gv[u][v] : ld4(a.GR + (go + (uint32_t)(R + 4 * lc.head[v])));   // (bit 3: diagnostic, no scalar-record read)
+          if constexpr (!QUAD)
+            rt[u][v] = (PYGAT_DIAG_K4 & 8) ? gv[u][v] : ld4(a.GR + (go + (uint32_t)(R + 4 * lc.head[v])));   // (bit 3: diagnostic, no scalar-record read)
           wv[u][v] = ld4(a.Wh + ((uint32_t)((PYGAT_DIAG_K4 & 4) ? (p[u].x & 63) : p[u].x) * (uint32_t)ldr + (uint32_t)lc.cofs[v]));   // (bit 2: diagnostic, row-local reads from 64 cached rows)
         } else {
         const float* gr = a.GR + (int64_t)p[u].y * RW;           // gathered: one contiguous row
         gv[u][v] = ld4(gr + lc.cofs[v]);
-        rt[u][v] = ld4(gr + R + 4 * lc.head[v]);
+        if constexpr (!QUAD) rt[u][v] = ld4(gr + R + 4 * lc.head[v]);
         wv[u][v] = ld4(a.Wh + (int64_t)p[u].x * ldr + lc.cofs[v]);  // row-local (L1 after the first edge)
         }
         mk[u][v] = 1.f;
         if (a.mask) mk[u][v] = a.mask[(int64_t)a.perm[(e + u < e1) ? e + u : e1 - 1] * ldh + lc.head[v]];
       }
+    if constexpr (QUAD) {   // the record of the row edge e + ql gathers, this lane's head
+      float4 rq;
+      if constexpr (CR > 0) {
+        if constexpr (PYGAT_DIAG_K4 & 8) rq = make_float4(0.f, 0.f, 0.f, 0.f);   // (bit 3: diagnostic, no scalar-record read)
+        else rq = ld4(a.GR + ((uint32_t)pq.y * (uint32_t)RW + (uint32_t)(R + 4 * lc.head[0])));
+      } else {
+        rq = ld4(a.GR + (int64_t)pq.y * RW + R + 4 * lc.head[0]);
+      }
+      if constexpr (QPREF) pn[0] = rc[(e + U + ql < e1) ? e + U + ql : e1 - 1];   // next round's records, behind this round's rows
+      if constexpr (CR > 0 && (PYGAT_DIAG_K4 & 8)) {
+        rt[0][0] = gv[0][0]; rt[1][0] = gv[1][0]; rt[2][0] = gv[2][0]; rt[3][0] = gv[3][0];
+      } else {
+        rt[0][0] = quad_bcast4<0>(rq); rt[1][0] = quad_bcast4<1>(rq); rt[2][0] = quad_bcast4<2>(rq); rt[3][0] = quad_bcast4<3>(rq);
+      }
+    }
     if constexpr (NARROW) {
 #pragma unroll
       for (int u = 0; u < U; ++u) pn[u] = rc[(e + U + u < e1) ? e + U + u : e1 - 1];
